@@ -8,7 +8,7 @@ configs[1]); for N>1 ranks each process its own batch shard (weak scaling) and t
 parameter gradients are summed with ONE flat RCCL all-reduce per step.
 Inputs are synthetic and already resident in HBM when the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -170,7 +170,15 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearse the multi-process protocol on CPU (gloo): rendezvous, one flat gradient all-reduce per step, "
                          "barrier + max-over-ranks timing, rank-0 JSON; no GPU work, the value is not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: the output and every gradient; "
+                         "vit: the loss, the updated parameters and their gradients) as DIR/<name>.npy, float32 or float64; "
+                         f"tensors above {DUMP_MAX_ELEMS} elements as a fixed seeded sample of that many elements")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs needs the GPU run, not --dry-run")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         _self_launch(args, sys.argv[1:])
@@ -220,6 +228,10 @@ def main():
             y.backward(dy)
             if world > 1:  # one flat gradient bucket, one RCCL all-reduce over xGMI
                 bucket.allreduce_(average=True)
+            return y
+
+        def outputs(y):
+            return {"y": y, "x.grad": x.grad, **{"grad." + n: p.grad for n, p in layer.named_parameters()}}
     elif args.workload in ("quartet", "whisper"):
         from mop_amd.nn import CausalSelfAttention, MultiheadSelfAttention, TransformerConfig
         torch.manual_seed(0)
@@ -245,6 +257,10 @@ def main():
             y.backward(dy)
             if world > 1:
                 bucket.allreduce_(average=True)
+            return y
+
+        def outputs(y):
+            return {"y": y, "x.grad": x.grad, **{"grad." + n: p.grad for n, p in mod.named_parameters()}}
     else:
         import torch.nn.functional as F
         from mop_amd.nn import ViT_MoP
@@ -260,7 +276,11 @@ def main():
                               params=[p for p in params if p.requires_grad])                              # flat all-reduce inside
 
         def step():
-            dp(xi, yi)
+            return dp(xi, yi)
+
+        def outputs(loss):
+            return {"loss": loss, **{"param." + n: p for n, p in model.named_parameters()},
+                    **{"grad." + n: p.grad for n, p in model.named_parameters()}}
 
     # one untimed initialisation pass (code-object loading, hipBLASLt kernel selection by TunableOp, allocator growth), so that the
     # W warm-up steps -- and with --warmup 0 the timed steps -- run the steady-state path
@@ -274,7 +294,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -283,6 +303,8 @@ def main():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:   # before the all-reduce timing below, which rewrites the gradients
+        dump_outputs(args.dump_outputs, outputs(last))
     tim = ops.timing_results()
     ops.enable_timing(False)
     ar_ms = None
@@ -349,6 +371,32 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 1 << 20     # per array; the largest dump (vit: 5.4 M parameters + their gradients, float32) stays below 64 MB
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tensors):
+    """`tensors`: name -> tensor (None: no gradient) -> out_dir/<name>.npy.  float64 stays float64, every other dtype becomes float32.
+    A tensor of more than DUMP_MAX_ELEMS elements is written, flattened, as the elements at DUMP_MAX_ELEMS flat indices drawn with a
+    fixed seed (sorted): the same indices for the same shape in every run, so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs exceeds {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def roofline(tim, B, dtype):

@@ -36,8 +36,16 @@ def timed(m, n=20):
 
 if not small:
     print("eager   %.2f ms/step" % timed(model), flush=True)
+# Warm up here and capture with no warm-up of make_graphed_callables' own.  Its warm-up runs on a side stream and keeps its last
+# outputs alive, so the parameters' AccumulateGrad nodes keep that stream; the backward capture then accumulates leaf gradients on
+# the side stream, which pulls a second stream into the capture (torch's AccumulateGrad stream-mismatch warning) and crashed
+# capture_end with a segmentation fault.  These steps initialise every kernel, library handle and dynamic-LDS attribute before
+# capture and leave no autograd graph behind, so the capture creates the AccumulateGrad nodes on its own stream.
+for _ in range(3):
+    step(model)
+torch.cuda.synchronize()
 try:
-    g = torch.cuda.make_graphed_callables(model, (x,))
+    g = torch.cuda.make_graphed_callables(model, (x,), num_warmup_iters=0)
 except RuntimeError as e:       # a Python-level refusal to capture (an op the capture mode does not allow): the one case the test may skip
     print("CAPTURE_UNSUPPORTED", repr(e)[:300], flush=True)
     sys.exit(0)
