@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPK_VERSION 118 /* 118: attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
+#define MOPK_VERSION 118 /* 118: mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
 
 typedef enum MopkStatus {
     MOPK_OK = 0,
@@ -369,6 +369,40 @@ typedef struct MopkLensMeansArgs {
 int mopk_lens_means_supported(const MopkLensMeansArgs *a, int backward);   /* 1 if the kernels take this shape (dimensions and dil only) */
 int mopk_lens_means_fwd(const MopkLensMeansArgs *a, void *stream);
 int mopk_lens_means_bwd(const MopkLensMeansArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
+ * 1-D MoP token gate of the GPT-MoP block (mop/models/gpt_mop.py:109-123), residual add included.  (Added under version 118:
+ * new exports only, no existing layout changes; callers detect it with mopk_token_gate_supported.)
+ * The reference gate  views = Wv r ; K = conv1d(views, Wk, pad 1) ; g = Wf [views ; K] ; gate = 1 + a0 g0 - a1 g1  is linear
+ * in r, so it folds (mop_amd/ops.py token_gate_taps, in torch) into three taps u (3,D):
+ *     r_t = x_t + a_t ,   gate_t = 1 + u[0] . r_{t-1} + u[1] . r_t + u[2] . r_{t+1}   (zero outside [0,T), never across b),
+ *     out_t = r_t * gate_t .
+ *   _fwd: out (o_dtype) and gate (B,T) fp32 (kept for the backward).
+ *   _bwd: with delta_t = dout_t . r_t (r recomputed from x, a):
+ *         dr_t = dout_t gate_t + u[0] delta_{t+1} + u[1] delta_t + u[2] delta_{t-1}    (the gradient of both x and a),
+ *         du[s] = sum_{b,t} delta_t r_{t+s-1}, per-workgroup partials in `workspace`, summed by a second launch in a fixed order.
+ * x / a: (B,T,D) with element strides (sb, st), innermost contiguous; a may be NULL (r = x).  o_dtype must be the promotion of
+ * x_dtype and a_dtype (F32 if either is F32, else BF16).  out / dout / dr: contiguous (B,T,D) o_dtype.  D % 8 == 0, D <= 1024,
+ * strides multiples of 8, 16-byte aligned pointers; mopk_token_gate_supported says whether a call is taken. */
+typedef struct MopkTokenGateArgs {
+    int32_t B, T, D;
+    int32_t x_dtype, a_dtype, o_dtype;   /* MopkDtype; a_dtype is ignored when a == NULL */
+    const void *x;
+    int64_t x_sb, x_st;
+    const void *a;                       /* NULL: no residual branch */
+    int64_t a_sb, a_st;
+    const float *u;                      /* (3,D) fp32 contiguous: taps of r_{t-1}, r_t, r_{t+1} */
+    void *out;                           /* fwd out */
+    float *gate;                         /* (B,T) fp32: fwd out, bwd in */
+    const void *dout;                    /* bwd in */
+    void *dr;                            /* bwd out */
+    float *du;                           /* bwd out (3,D) fp32 */
+    void *workspace;                     /* bwd: mopk_token_gate_workspace_bytes() */
+} MopkTokenGateArgs;
+int mopk_token_gate_supported(const MopkTokenGateArgs *a);                /* 1 if the kernels take this call (shape, dtypes, strides, alignment) */
+size_t mopk_token_gate_workspace_bytes(const MopkTokenGateArgs *a);
+int mopk_token_gate_fwd(const MopkTokenGateArgs *a, void *stream);
+int mopk_token_gate_bwd(const MopkTokenGateArgs *a, void *stream);
 
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);

@@ -132,6 +132,15 @@ class LensMeansArgs(C.Structure):
     ]
 
 
+class TokenGateArgs(C.Structure):
+    """MopkTokenGateArgs: 1-D MoP token gate (GPT-MoP block)."""
+    _fields_ = [
+        ("B", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("x_dtype", C.c_int32), ("a_dtype", C.c_int32), ("o_dtype", C.c_int32),
+        ("x", _fp), ("x_sb", C.c_int64), ("x_st", C.c_int64), ("a", _fp), ("a_sb", C.c_int64), ("a_st", C.c_int64),
+        ("u", _fp), ("out", _fp), ("gate", _fp), ("dout", _fp), ("dr", _fp), ("du", _fp), ("workspace", _fp),
+    ]
+
+
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),
@@ -170,6 +179,10 @@ SYMBOLS = {
     "mopk_lens_means_fwd": (C.c_int, [C.POINTER(LensMeansArgs), C.c_void_p]),
     "mopk_lens_means_bwd": (C.c_int, [C.POINTER(LensMeansArgs), C.c_void_p]),
     "mopk_layernorm_bwd": (C.c_int, [C.POINTER(LayerNormArgs), C.c_void_p]),
+    "mopk_token_gate_supported": (C.c_int, [C.POINTER(TokenGateArgs)]),
+    "mopk_token_gate_workspace_bytes": (C.c_size_t, [C.POINTER(TokenGateArgs)]),
+    "mopk_token_gate_fwd": (C.c_int, [C.POINTER(TokenGateArgs), C.c_void_p]),
+    "mopk_token_gate_bwd": (C.c_int, [C.POINTER(TokenGateArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -8,3 +8,8 @@ from .vit_mop import ViT_MoP  # noqa: F401
 from .whisper_mop import (EncoderBlock, FuseExcInh2D, Kernels2D, MoP2D, MultiheadSelfAttention,  # noqa: F401
                           ViewsConv2D, WhisperConfig)
 from .vit_edgewise import BlockEdgewise, ViTEdgewise  # noqa: F401
+# GPT line (mop/models/gpt_mop.py).  The Quartet MLP / Block / TinyTransformerLM live in .quartet_attn_patch; MLP and Block here stay
+# the ViT ones, as in the reference's mop.models.
+from .gpt_mop import (FuseExcInh1D, GPT_MoP, Kernels1D, MoPBlock, ViewsLinear1D, create_gpt_baseline,  # noqa: F401
+                      create_gpt_mop, create_gpt_quartet)
+from .quartet_attn_patch import TinyTransformerLM  # noqa: F401

@@ -1,4 +1,5 @@
-"""Quartet dual-path causal attention with the reference surface (mop/models/quartet_attn_patch.py:19-127).
+"""Quartet dual-path causal attention with the reference surface (mop/models/quartet_attn_patch.py:19-127), and the
+Quartet language model around it (`MLP`, `Block`, `TinyTransformerLM`, :130-213).
 
 The five/three Linear projections stay in PyTorch (hipBLASLt); scores, row z-normalisation, product
 mix, causal + additive mask, softmax and AV are one libmopk call (mopk_quartet_*).
@@ -11,6 +12,7 @@ from typing import Optional
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import ops
 from .linear import TokenLinear
@@ -76,3 +78,86 @@ class CausalSelfAttention(nn.Module):
         y, attn = out if need_weights else (out, None)
         y = self.resid_drop(self.o_proj(y))
         return (y, attn) if need_weights else y
+
+
+class MLP(nn.Module):
+    """fc -> GELU(tanh) -> proj -> dropout (reference :130-143)"""
+
+    def __init__(self, config: TransformerConfig):
+        super().__init__()
+        self.fc = TokenLinear(config.n_embd, 4 * config.n_embd, bias=config.bias)
+        self.proj = TokenLinear(4 * config.n_embd, config.n_embd, bias=config.bias)
+        self.drop = nn.Dropout(config.dropout)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.drop(self.proj(F.gelu(self.fc(x), approximate="tanh")))
+
+
+class Block(nn.Module):
+    """pre-norm block: x + attn(ln1(x)), then x + mlp(ln2(x)) (reference :146-159)"""
+
+    def __init__(self, config: TransformerConfig):
+        super().__init__()
+        self.ln1 = nn.LayerNorm(config.n_embd)
+        self.attn = CausalSelfAttention(config)
+        self.ln2 = nn.LayerNorm(config.n_embd)
+        self.mlp = MLP(config)
+
+    def forward(self, x: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = x + self.attn(self.ln1(x), attention_mask=attention_mask)
+        return x + self.mlp(self.ln2(x))
+
+
+def _init_gpt_weights(module: nn.Module) -> None:
+    """N(0, 0.02) for every Linear weight and Embedding, zero Linear biases (reference :177-183); convolutions keep torch's init"""
+    if isinstance(module, nn.Linear):
+        nn.init.normal_(module.weight, mean=0.0, std=0.02)
+        if module.bias is not None:
+            nn.init.zeros_(module.bias)
+    elif isinstance(module, nn.Embedding):
+        nn.init.normal_(module.weight, mean=0.0, std=0.02)
+
+
+class _LMBase(nn.Module):
+    """token (+ absolute position) embedding, a stack of blocks, final LayerNorm and the head tied to the token embedding"""
+
+    def _embed(self, idx: torch.Tensor) -> torch.Tensor:
+        T = idx.shape[1]
+        if T > self.config.block_size:
+            raise AssertionError("Sequence length > block size")
+        x = self.wte(idx)
+        if self.wpe is not None:
+            x = x + self.wpe(torch.arange(T, dtype=torch.long, device=idx.device).unsqueeze(0))
+        return self.drop(x)
+
+    def _head(self, x: torch.Tensor, targets: Optional[torch.Tensor]):
+        logits = self.lm_head(self.ln_f(x))
+        loss = None
+        if targets is not None:
+            loss = F.cross_entropy(logits.view(-1, logits.size(-1)), targets.view(-1))
+        return logits, loss
+
+    def _init_weights(self, module):
+        _init_gpt_weights(module)
+
+
+class TinyTransformerLM(_LMBase):
+    """GPT-style LM on Quartet (or plain z-normalised) causal attention (reference :162-213): forward -> (logits, loss)"""
+
+    def __init__(self, vocab_size: int, config: TransformerConfig):
+        super().__init__()
+        self.config = config
+        self.wte = nn.Embedding(vocab_size, config.n_embd)
+        self.wpe = nn.Embedding(config.block_size, config.n_embd) if config.use_abs_pos_emb else None
+        self.drop = nn.Dropout(config.dropout)
+        self.blocks = nn.ModuleList([Block(config) for _ in range(config.n_layer)])
+        self.ln_f = nn.LayerNorm(config.n_embd)
+        self.lm_head = nn.Linear(config.n_embd, vocab_size, bias=False)
+        self.lm_head.weight = self.wte.weight
+        self.apply(self._init_weights)
+
+    def forward(self, idx: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None):
+        x = self._embed(idx)
+        for block in self.blocks:
+            x = block(x, attention_mask=attention_mask)
+        return self._head(x, targets)

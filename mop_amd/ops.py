@@ -1223,3 +1223,110 @@ def layernorm_residual(x: torch.Tensor, weight: torch.Tensor, bias: Optional[tor
     """(x_res, ln(x)) for a pre-norm residual branch ``x_res + f(ln(x))``: ``x_res`` is ``x`` itself, routed through the same
     autograd node so that the backward returns ``d x_res + LN'(d ln)`` from ONE kernel instead of LN backward + an add."""
     return _LayerNormFn.apply(x, weight, bias, eps, out_dtype or x.dtype, True)
+
+
+# ---- 1-D MoP token gate of the GPT-MoP block (mopk_token_gate_*; reference mop/models/gpt_mop.py:109-123) ----
+def token_gate_taps(Wv: torch.Tensor, Wk: torch.Tensor, Wf: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
+    """Fold the gate's linear chain into three taps u (3, D), differentiable in all four parameters.
+
+    views = Wv r ; K_t = sum_j Wk[:,:,j] views_{t+j-1} ; g = Wf [views ; K] ; gate = 1 + alpha0 g0 - alpha1 g1.  With
+    w = (alpha0, -alpha1) Wf, w_V = w[:V], w_K = w[V:], c_j = sum_k w_K[k] Wk[k,:,j] and m_j = c_j + [j = 1] w_V:
+    gate_t = 1 + sum_j (Wv^T m_j) . r_{t+j-1}.   Wv (V,D) = views.proj.weight, Wk (K,V,3) = kernels.conv.weight,
+    Wf (2,V+K,1) = fuse.conv.weight, alpha (2,) = fuse.alpha.  Computed in fp32 (float64 for float64 parameters)."""
+    with torch.autocast(device_type=Wv.device.type, enabled=False):
+        V = Wv.shape[0]
+        ct = torch.float64 if Wv.dtype == torch.float64 else torch.float32
+        f32 = lambda t: t.to(ct)
+        a = torch.stack((f32(alpha[0]), -f32(alpha[1])))
+        w = a @ f32(Wf).reshape(2, -1)                             # (V+K,)
+        m = torch.einsum("k,kvj->jv", w[V:], f32(Wk))              # (3, V)
+        m = m + torch.stack((torch.zeros_like(w[:V]), w[:V], torch.zeros_like(w[:V])))
+        return m @ f32(Wv)                                         # (3, D)
+
+
+def token_gate_1d_torch(x: torch.Tensor, a: Optional[torch.Tensor], u: torch.Tensor) -> torch.Tensor:
+    """the folded gate in torch ops (any device / dtype): r = x + a, out_t = r_t (1 + u0.r_{t-1} + u1.r_t + u2.r_{t+1})"""
+    r = x if a is None else x + a
+    p = torch.einsum("btd,sd->bts", r, u.to(r.dtype))              # (B,T,3)
+    gate = 1 + p[..., 1]
+    gate = gate + F.pad(p[:, :-1, 0], (1, 0)) + F.pad(p[:, 1:, 2], (0, 1))
+    return r * gate.unsqueeze(-1)
+
+
+def _tg_args(x: torch.Tensor, a: Optional[torch.Tensor]) -> L.TokenGateArgs:
+    B, T, D = x.shape
+    g = L.TokenGateArgs()
+    g.B, g.T, g.D = B, T, D
+    g.x_dtype = _io_dtype(x)
+    g.x, g.x_sb, g.x_st = x.data_ptr(), (x.stride(0) if B > 1 else 0), (x.stride(1) if T > 1 else D)
+    f32 = x.dtype == torch.float32
+    if a is not None:
+        g.a_dtype = _io_dtype(a)
+        g.a, g.a_sb, g.a_st = a.data_ptr(), (a.stride(0) if B > 1 else 0), (a.stride(1) if T > 1 else D)
+        f32 = f32 or a.dtype == torch.float32
+    g.o_dtype = L.MOPK_F32 if f32 else L.MOPK_BF16
+    return g
+
+
+def token_gate_supported(x: torch.Tensor, a: Optional[torch.Tensor] = None) -> bool:
+    """True if mopk_token_gate_* take this call: GPU tensors, fp32 / bf16 (mixed pairs included), (B,T,D) with D % 8 == 0 and
+    D <= 1024, innermost dimension contiguous, row strides multiples of 8, 16-byte aligned data (the library's own query)."""
+    ts = (x,) if a is None else (x, a)
+    if any(not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 3 or t.stride(-1) != 1 for t in ts):
+        return False
+    if a is not None and a.shape != x.shape:
+        return False
+    if x.numel() == 0:
+        return False
+    return bool(L.lib().mopk_token_gate_supported(C.byref(_tg_args(x, a))))
+
+
+class _TokenGateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, a, u):
+        lib = L.lib()
+        g = _tg_args(x, a)
+        B, T, D = x.shape
+        uc = u.detach().to(torch.float32).contiguous()
+        odt = torch.float32 if g.o_dtype == L.MOPK_F32 else torch.bfloat16
+        out = torch.empty(B, T, D, dtype=odt, device=x.device)
+        gate = torch.empty(B, T, dtype=torch.float32, device=x.device)
+        g.u, g.out, g.gate = uc.data_ptr(), out.data_ptr(), gate.data_ptr()
+        LAST_PATH["token_gate_fwd"] = L.PATH_FUSED
+        with _timed("token_gate_fwd"):
+            rc = lib.mopk_token_gate_fwd(C.byref(g), _stream())
+        L.check(rc, "mopk_token_gate_fwd")
+        ctx.save_for_backward(x, a, uc, gate)
+        ctx.u_dtype = u.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.lib()
+        x, a, uc, gate = ctx.saved_tensors
+        g = _tg_args(x, a)
+        odt = torch.float32 if g.o_dtype == L.MOPK_F32 else torch.bfloat16
+        dout = dout.to(odt).contiguous()
+        dr = torch.empty(x.shape, dtype=odt, device=x.device)
+        du = torch.empty(3, x.shape[2], dtype=torch.float32, device=x.device)
+        g.u, g.gate, g.dout, g.dr, g.du = uc.data_ptr(), gate.data_ptr(), dout.data_ptr(), dr.data_ptr(), du.data_ptr()
+        ws = _bytes(lib.mopk_token_gate_workspace_bytes(C.byref(g)), x.device)
+        g.workspace = ws.data_ptr()
+        LAST_PATH["token_gate_bwd"] = L.PATH_FUSED
+        with _timed("token_gate_bwd"):
+            rc = lib.mopk_token_gate_bwd(C.byref(g), _stream())
+        L.check(rc, "mopk_token_gate_bwd")
+        dx = dr.to(x.dtype) if ctx.needs_input_grad[0] else None
+        da = dr.to(a.dtype) if a is not None and ctx.needs_input_grad[1] else None
+        return dx, da, (du.to(ctx.u_dtype) if ctx.needs_input_grad[2] else None)
+
+
+def token_gate_1d(x: torch.Tensor, a: Optional[torch.Tensor], u: torch.Tensor) -> torch.Tensor:
+    """out = r * gate with r = x + a (a may be None) and gate_t = 1 + u0.r_{t-1} + u1.r_t + u2.r_{t+1} (zero padding per sequence):
+    the GPT-MoP block's residual add and token gate as one HIP kernel forward and two launches backward.  x, a: (B,T,D); u: (3,D)
+    from token_gate_taps.  Output dtype: the promotion of x and a.  Calls the kernels do not take (token_gate_supported) run the
+    same formula in torch ops; LAST_PATH["token_gate_fwd"] records which (PATH_FUSED / PATH_GENERIC)."""
+    if not token_gate_supported(x, a):
+        LAST_PATH["token_gate_fwd"] = L.PATH_GENERIC
+        return token_gate_1d_torch(x, a, u)
+    return _TokenGateFn.apply(x, a, u)

@@ -51,6 +51,10 @@ def _perturb(mod: torch.nn.Module, seed: int):
                 p.fill_(0.8)
             elif name.endswith("chain_value_logit"):
                 p.fill_(-0.5)
+            elif name.endswith("fuse.alpha"):                   # GPT-MoP gate: ones(2) makes both channels' weights equal
+                p.copy_(torch.tensor([0.7, 1.3]) + 0.1 * torch.randn(p.shape, generator=g))
+            elif name.endswith("fuse.conv.weight") and p.dim() == 3:
+                p.add_(0.2 * torch.randn(p.shape, generator=g))
 
 
 def _bf16_self_error(mod, x, w, fwd_kwargs, ref):
@@ -373,8 +377,85 @@ def train_cases():
     _save("train_vit_tiny_adamw6", out)
 
 
+def gpt_cases():
+    """GPT line (gpt_mop.py, quartet_attn_patch.py:130-213): MoPBlock x -> y with dx and every parameter gradient; GPT_MoP and the
+    Quartet / baseline TinyTransformerLM idx, targets -> logits, loss and every parameter gradient of the loss (the tied
+    wte / lm_head weight included); GPT_MoP.get_gate_maps."""
+    from mop.models.gpt_mop import GPT_MoP, MoPBlock, create_gpt_baseline, create_gpt_quartet
+    blocks = [
+        # name, dim, heads, B, T, n_views, n_kernels, additive mask, bias
+        ("gpt_blk_v5k3", 64, 4, 2, 16, 5, 3, False, False),
+        ("gpt_blk_v2k1", 64, 2, 2, 33, 2, 1, False, False),
+        ("gpt_blk_v5k3_addmask_bias", 64, 2, 2, 20, 5, 3, True, True),
+    ]
+    for i, (name, dim, heads, B, T, V, K, addmask, bias) in enumerate(blocks):
+        torch.manual_seed(1100 + i)
+        cfg = TransformerConfig(n_head=heads, n_embd=dim, block_size=32 if T <= 32 else 64, dropout=0.0, bias=bias)
+        mod = MoPBlock(cfg, n_views=V, n_kernels=K).eval()
+        _perturb(mod, 1100 + i)
+        x = torch.randn(B, T, dim)
+        fk, extra = {}, {}
+        if addmask:
+            am = 0.5 * torch.randn(B, 1, T, T)
+            fk["attention_mask"] = am
+            extra["attention_mask"] = am.numpy()
+        meta = dict(kind="gpt_block", dim=dim, heads=heads, n_views=V, n_kernels=K, bias=bias, block_size=cfg.block_size)
+        extra.update({"meta:" + k: np.asarray(v) for k, v in meta.items()})
+        _save(name, _run(mod, x, fk, extra, bf16_self=True))
+
+    def lm_run(mod, idx, tgt):
+        mod.zero_grad(set_to_none=True)
+        logits, loss = mod(idx, targets=tgt)
+        loss.backward()
+        return logits, loss, {k: p.grad.clone() for k, p in mod.named_parameters() if p.grad is not None}
+
+    vocab = 100
+    lms = [    # d = 32, one 32-wide head (the fused Quartet kernels' head size): each fixture stays near 0.3 MB
+        # name, kind, n_layer, heads, dim, B, T, use_abs_pos_emb, bias
+        ("gpt_lm_mop", "mop", 2, 1, 32, 2, 16, True, False),
+        ("gpt_lm_mop_nopos", "mop", 2, 1, 32, 2, 24, False, False),
+        ("gpt_lm_quartet", "quartet", 2, 1, 32, 2, 16, True, False),
+        ("gpt_lm_baseline_bias", "baseline", 2, 1, 32, 2, 16, True, True),
+    ]
+    for i, (name, kind, nl, heads, dim, B, T, pos, bias) in enumerate(lms):
+        torch.manual_seed(1200 + i)
+        cfg = TransformerConfig(n_layer=nl, n_head=heads, n_embd=dim, block_size=32, dropout=0.0, bias=bias, use_abs_pos_emb=pos)
+        if kind == "mop":
+            mod = GPT_MoP(vocab, cfg, n_views=3, n_kernels=2)
+        else:
+            mod = (create_gpt_quartet if kind == "quartet" else create_gpt_baseline)(vocab, cfg)
+        mod.eval()
+        _perturb(mod, 1200 + i)
+        g = torch.Generator().manual_seed(1300 + i)
+        idx = torch.randint(0, vocab, (B, T), generator=g)
+        tgt = torch.randint(0, vocab, (B, T), generator=g)
+        logits, loss, grads = lm_run(mod, idx, tgt)
+        out = {"idx": idx.numpy(), "targets": tgt.numpy(), "logits": logits.detach().numpy(), "loss": np.float32(loss.item())}
+        for k, v in mod.state_dict().items():
+            out["param:" + k] = v.detach().numpy()
+        for k, v in grads.items():
+            out["grad:" + k] = v.numpy()
+        import copy
+        mb = copy.deepcopy(mod).to(torch.bfloat16)                 # the reference's own bf16 run: noise floor per gradient tensor
+        _, lb, gb = lm_run(mb, idx, tgt)
+        out["bf16err:loss"] = np.float32(abs(lb.item() - loss.item()))
+        for k, v in gb.items():
+            ref = grads[k].numpy()
+            out["bf16err:" + k] = np.float32(np.abs(v.float().numpy() - ref).max() / max(np.abs(ref).max(), 1e-30))
+        if kind == "mop":
+            with torch.no_grad():
+                gm, vm, km = mod.get_gate_maps(idx)
+            out.update({"gate_maps": gm.numpy(), "view_maps": vm.numpy(), "kernel_maps": km.numpy()})
+        meta = dict(kind="gpt_lm", model=kind, vocab=vocab, n_layer=nl, heads=heads, dim=dim, block_size=32, bias=bias,
+                    use_abs_pos_emb=pos, n_views=3, n_kernels=2, n_params=sum(p.numel() for p in mod.parameters()))
+        out.update({"meta:" + k: np.asarray(v) for k, v in meta.items()})
+        out["y"] = out["logits"]
+        _save(name, out)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
-    groups = dict(train=train_cases, vit=vit_cases, ew=edgewise_cases, ewx=edgewise_variant_cases, cv=crossview_cases, wh=whisper_cases, mh=multihop_cases, qt=quartet_cases, sdpa=sdpa_cases)
+    groups = dict(train=train_cases, vit=vit_cases, ew=edgewise_cases, ewx=edgewise_variant_cases, cv=crossview_cases, wh=whisper_cases, mh=multihop_cases, qt=quartet_cases, sdpa=sdpa_cases,
+                  gpt=gpt_cases)
     for name in (sys.argv[1:] or list(groups)):               # e.g. `gen_golden.py ewx` regenerates one group only
         groups[name]()
