@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPK_VERSION 118 /* 118: mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
+#define MOPK_VERSION 118 /* 118: MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
 
 typedef enum MopkStatus {
     MOPK_OK = 0,
@@ -240,7 +240,8 @@ int mopk_quartet_fused_supported(const MopkQuartetArgs *a);
 /* --------------------------------------------------------------------------
  * Plain scaled-dot-product attention core.
  * Replaces BaselineMSA.forward attention_variants.py:42-46, MSA.forward
- * components.py:61-64 and MultiheadSelfAttention.forward whisper_mop.py:163-175.
+ * components.py:61-64, MultiheadSelfAttention.forward whisper_mop.py:163-175
+ * and MultiheadCrossAttention.forward whisper_mop.py:198-228 (Nk != N).
  * path: MOPK_PATH_AUTO picks the fused kernels (sdpa_flash.hip: no N x N map in HBM) when they cover the call.
  * -------------------------------------------------------------------------- */
 typedef struct MopkSdpaArgs {
@@ -261,6 +262,10 @@ typedef struct MopkSdpaArgs {
      * same mask from a seed (the generic path multiplies its N x N map by it in a workspace plane). */
     float dropout_p;
     uint64_t dropout_seed;
+    /* key / value length (cross-attention, whisper_mop.py:180-228); 0 = N.  With Nk != N, N is the query length: q, y, dy, dq are
+     * (B, N, H, dk), k, v, dk_, dv are (B, Nk, H, dk), mask and bias are (., ., N, Nk) with the row strides above.  causal with
+     * Nk != N is MOPK_ERR_UNSUPPORTED. */
+    int32_t Nk;
 } MopkSdpaArgs;
 
 size_t mopk_sdpa_saved_bytes(const MopkSdpaArgs *a);

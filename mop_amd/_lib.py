@@ -96,6 +96,7 @@ class SdpaArgs(C.Structure):
         ("y", View4), ("saved", _fp), ("workspace", _fp),
         ("dy", View4), ("dq", View4), ("dk_", View4), ("dv", View4),
         ("dropout_p", C.c_float), ("dropout_seed", C.c_uint64),
+        ("Nk", C.c_int32),                     # key / value length, 0 = N
     ]
 
 

@@ -149,18 +149,28 @@ static int base_ok(int B, int H, int N, int dk, int io, int prec) {
 static bool sdpa_use_flash(const MopkSdpaArgs *a, bool bwd) {
     return a->path != MOPK_PATH_GENERIC && sdpa_flash_supported(a, bwd);
 }
-int mopk_sdpa_fused_supported(const MopkSdpaArgs *a) { return (a && a->B > 0 && a->H > 0 && a->N > 0 && a->dk > 0) ? sdpa_flash_supported(a, false) : 0; }
+// shape of a plain SDPA call: Nk (key length) >= 0, 0 = N; causal only when the call is square
+static bool sdpa_shape_ok(const MopkSdpaArgs *a) {
+    return a && a->B > 0 && a->H > 0 && a->N > 0 && a->dk > 0 && a->Nk >= 0 && !(a->causal && sdpa_nk(*a) != a->N);
+}
+static int sdpa_check(const MopkSdpaArgs *a) {
+    if (!a) return MOPK_ERR_BAD_ARG;
+    int rc = base_ok(a->B, a->H, a->N, a->dk, a->io_dtype, a->precision); if (rc) return rc;
+    if (a->Nk < 0) return MOPK_ERR_BAD_SHAPE;
+    if (a->causal && sdpa_nk(*a) != a->N) return MOPK_ERR_UNSUPPORTED;    // no top-left / bottom-right convention is guessed
+    return MOPK_OK;
+}
+int mopk_sdpa_fused_supported(const MopkSdpaArgs *a) { return sdpa_shape_ok(a) ? sdpa_flash_supported(a, false) : 0; }
 size_t mopk_sdpa_saved_bytes(const MopkSdpaArgs *a) {
-    if (!(a && a->B > 0 && a->H > 0 && a->N > 0 && a->dk > 0)) return 0;
+    if (!sdpa_shape_ok(a)) return 0;
     return sdpa_use_flash(a, false) ? sdpa_flash_saved_bytes(a) : sdpa_saved_bytes(a);
 }
 size_t mopk_sdpa_workspace_bytes(const MopkSdpaArgs *a) {
-    if (!(a && a->B > 0 && a->H > 0 && a->N > 0 && a->dk > 0)) return 0;
+    if (!sdpa_shape_ok(a)) return 0;
     return sdpa_use_flash(a, false) ? sdpa_flash_ws_bytes(a) : sdpa_ws_bytes(a);
 }
 int mopk_sdpa_fwd(const MopkSdpaArgs *a, void *stream) {
-    if (!a) return MOPK_ERR_BAD_ARG;
-    int rc = base_ok(a->B, a->H, a->N, a->dk, a->io_dtype, a->precision); if (rc) return rc;
+    int rc = sdpa_check(a); if (rc) return rc;
     if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !a->saved || !a->workspace) return MOPK_ERR_BAD_ARG;
     if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return MOPK_ERR_BAD_ARG;
     if (sdpa_use_flash(a, false)) return sdpa_flash_fwd(a, (hipStream_t)stream);
@@ -168,8 +178,7 @@ int mopk_sdpa_fwd(const MopkSdpaArgs *a, void *stream) {
     return sdpa_fwd(a, (hipStream_t)stream);
 }
 int mopk_sdpa_bwd(const MopkSdpaArgs *a, void *stream) {      // the fused path also reads `y` (the forward's output)
-    if (!a) return MOPK_ERR_BAD_ARG;
-    int rc = base_ok(a->B, a->H, a->N, a->dk, a->io_dtype, a->precision); if (rc) return rc;
+    int rc = sdpa_check(a); if (rc) return rc;
     if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !v4ok(a->dy) || !v4ok(a->dq) || !v4ok(a->dk_) || !v4ok(a->dv) ||
         !a->saved || !a->workspace)
         return MOPK_ERR_BAD_ARG;

@@ -13,8 +13,11 @@ namespace mopk {
 #define RET_IF(x) do { int rc_ = (x); if (rc_ != MOPK_OK) return rc_; } while (0)
 constexpr float EPS_CH = 1e-6f;
 
-struct Dm { int B, H, N, dk, LD; int64_t BH; };
-static Dm mkdm(int B, int H, int N, int dk) { Dm d{B, H, N, dk, (int)round_up(N, 4), (int64_t)B * H}; return d; }
+// score maps are N x Nk per (b,h) with leading dimension LD; Nk = N except for rectangular plain SDPA (cross-attention)
+struct Dm { int B, H, N, dk, LD; int64_t BH; int Nk; };
+static Dm mkdm(int B, int H, int N, int dk) { Dm d{B, H, N, dk, (int)round_up(N, 4), (int64_t)B * H, N}; return d; }
+static Dm mkdm_nk(int B, int H, int N, int Nk, int dk) { Dm d{B, H, N, dk, (int)round_up(Nk, 4), (int64_t)B * H, Nk}; return d; }
+static Dm key_rows(const Dm &d) { Dm e = d; e.N = d.Nk; return e; }        // gather / scatter extents of the (B, Nk, H, dk) tensors
 
 template <typename T>
 __global__ void gather_kernel(MopkView4 v, float *out, Dm d) {
@@ -66,13 +69,13 @@ __global__ void masked_softmax_kernel(const float *in, float *out, Dm d, MaskSpe
     float *o = out + row * d.LD;
     const float *bp = m.bias ? m.bias + b * m.bsb + h * m.bsh + i * m.bsi : nullptr;
     float mx = -INFINITY;
-    for (int j = lane; j < d.N; j += 64) if (!is_blocked(m, b, h, i, j)) mx = fmaxf(mx, p[j] + (bp ? bp[j] : 0.f));
+    for (int j = lane; j < d.Nk; j += 64) if (!is_blocked(m, b, h, i, j)) mx = fmaxf(mx, p[j] + (bp ? bp[j] : 0.f));
     mx = wave_max(mx);
     float den = 0.f;
-    for (int j = lane; j < d.N; j += 64) if (!is_blocked(m, b, h, i, j)) den += expf(p[j] + (bp ? bp[j] : 0.f) - mx);
+    for (int j = lane; j < d.Nk; j += 64) if (!is_blocked(m, b, h, i, j)) den += expf(p[j] + (bp ? bp[j] : 0.f) - mx);
     den = wave_sum(den);
     const float inv = 1.f / den;
-    for (int j = lane; j < d.N; j += 64)
+    for (int j = lane; j < d.Nk; j += 64)
         o[j] = is_blocked(m, b, h, i, j) ? 0.f : expf(p[j] + (bp ? bp[j] : 0.f) - mx) * inv;
 }
 // dS = P (dP - sum_j P dP) * alpha, in place over dP ; one wave per row
@@ -83,28 +86,27 @@ __global__ void softmax_bwd_kernel(const float *P, float *dP, Dm d, float alpha)
     const float *p = P + row * d.LD;
     float *g = dP + row * d.LD;
     float dot = 0.f;
-    for (int j = lane; j < d.N; j += 64) dot += p[j] * g[j];
+    for (int j = lane; j < d.Nk; j += 64) dot += p[j] * g[j];
     dot = wave_sum(dot);
-    for (int j = lane; j < d.N; j += 64) g[j] = p[j] * (g[j] - dot) * alpha;
+    for (int j = lane; j < d.Nk; j += 64) g[j] = p[j] * (g[j] - dot) * alpha;
 }
 
 static inline GemmDesc gd0(int M, int N, int K, int nb) {
     GemmDesc g{}; g.M = M; g.N = N; g.K = K; g.nb0 = 1; g.nb1 = nb; g.alpha = 1.f; g.beta = 0.f; g.alpha_dev = nullptr;
     return g;
 }
-// C(N,N) = alpha * X(N,dk) Y(N,dk)^T
 // attention dropout (`self.attn_drop(A)`): out = in * keep / (1 - p) over one N x N map per (b,h), with the counter-based mask of the
 // fused kernels (common.h: a seed means one mask on either path).  In place when out == in.  One wave per row (bh, i).
-__global__ void drop_rows_kernel(const float *in, int ld_in, float *out, int ld_out, FaDrop drop, int64_t rows, int N) {
+__global__ void drop_rows_kernel(const float *in, int ld_in, float *out, int ld_out, FaDrop drop, int64_t rows, int N, int Nk) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
     const uint32_t rowh = fa_drop_row(drop, (int)(row / N), (int)(row % N));
-    for (int j = lane; j < N; j += 64) out[row * ld_out + j] = fa_drop_keep(drop, rowh, j) ? in[row * ld_in + j] * drop.inv_keep : 0.f;
+    for (int j = lane; j < Nk; j += 64) out[row * ld_out + j] = fa_drop_keep(drop, rowh, j) ? in[row * ld_in + j] * drop.inv_keep : 0.f;
 }
 static void drop_map(const float *in, float *out, const Dm &d, float p, uint64_t seed, hipStream_t st) {
     const int64_t rows = d.BH * d.N;
-    hipLaunchKernelGGL(drop_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, in, d.LD, out, d.LD, fa_drop(p, seed), rows, d.N);
+    hipLaunchKernelGGL(drop_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, in, d.LD, out, d.LD, fa_drop(p, seed), rows, d.N, d.Nk);
 }
 // The backward of  y = drop(P) v :  dv = drop(P)^T dy  and  dP = (dy v^T) keep / (1 - p).  The dropped map is rebuilt in the dP plane
 // for the dv product BEFORE that plane receives dP (no extra workspace); the softmax backward then sees the undropped P and the
@@ -112,20 +114,22 @@ static void drop_map(const float *in, float *out, const Dm &d, float p, uint64_t
 static int drop_bwd_pair(const float *P, const float *dy, const float *v, float *dP, float *dv, const Dm &d, float p, uint64_t seed, bool mf,
                          hipStream_t st);
 
+// C(N,Nk) = alpha * X(N,dk) Y(Nk,dk)^T
 static int gemm_nt_scores(const float *X, const float *Y, float *C, const Dm &d, float alpha, bool mf, hipStream_t st, const float *adev = nullptr) {
-    GemmDesc g = gd0(d.N, d.N, d.dk, (int)d.BH);
+    GemmDesc g = gd0(d.N, d.Nk, d.dk, (int)d.BH);
     g.A = X; g.a_rs = d.dk; g.a_cs = 1; g.a_b1 = (int64_t)d.N * d.dk;
-    g.B = Y; g.b_rs = 1; g.b_cs = d.dk; g.b_b1 = (int64_t)d.N * d.dk;
+    g.B = Y; g.b_rs = 1; g.b_cs = d.dk; g.b_b1 = (int64_t)d.Nk * d.dk;
     g.C = C; g.c_rs = d.LD; g.c_b1 = (int64_t)d.N * d.LD; g.alpha = alpha; g.alpha_dev = adev;
     return bgemm(g, mf, st);
 }
-// C(N,dk) = alpha * op(M)(N,N) X(N,dk) + beta C ; trans: use M^T
+// C(N,dk) = alpha * M(N,Nk) X(Nk,dk) + beta C ; trans: C(Nk,dk) = alpha * M^T X(N,dk) + beta C
 static int gemm_map_vec(const float *M, bool trans, const float *X, float *C, const Dm &d, float alpha, float beta, bool mf,
                         hipStream_t st, const float *adev = nullptr) {
-    GemmDesc g = gd0(d.N, d.dk, d.N, (int)d.BH);
+    const int rows = trans ? d.Nk : d.N, inner = trans ? d.N : d.Nk;
+    GemmDesc g = gd0(rows, d.dk, inner, (int)d.BH);
     g.A = M; g.a_rs = trans ? 1 : d.LD; g.a_cs = trans ? d.LD : 1; g.a_b1 = (int64_t)d.N * d.LD;
-    g.B = X; g.b_rs = d.dk; g.b_cs = 1; g.b_b1 = (int64_t)d.N * d.dk;
-    g.C = C; g.c_rs = d.dk; g.c_b1 = (int64_t)d.N * d.dk; g.alpha = alpha; g.beta = beta; g.alpha_dev = adev;
+    g.B = X; g.b_rs = d.dk; g.b_cs = 1; g.b_b1 = (int64_t)inner * d.dk;
+    g.C = C; g.c_rs = d.dk; g.c_b1 = (int64_t)rows * d.dk; g.alpha = alpha; g.beta = beta; g.alpha_dev = adev;
     return bgemm(g, mf, st);
 }
 // C(N,N) = op(A)(N,N) op(B)(N,N) + beta C
@@ -154,21 +158,21 @@ static int drop_bwd_pair(const float *P, const float *dy, const float *v, float 
 struct SdpaBuf { float *q, *k, *v, *P, *y, *dy, *dP, *dq, *dk, *dv; };
 static SdpaBuf sdpa_carve(void *saved, void *ws, const Dm &d, size_t *ns, size_t *nw) {
     Carver cs(saved), cw(ws);
-    const size_t nd = d.BH * d.N * d.dk, nn = d.BH * (size_t)d.N * d.LD;
+    const size_t nd = d.BH * d.N * d.dk, nkd = d.BH * d.Nk * d.dk, nn = d.BH * (size_t)d.N * d.LD;
     SdpaBuf b;
-    b.q = cs.take<float>(nd); b.k = cs.take<float>(nd); b.v = cs.take<float>(nd); b.P = cs.take<float>(nn);
+    b.q = cs.take<float>(nd); b.k = cs.take<float>(nkd); b.v = cs.take<float>(nkd); b.P = cs.take<float>(nn);
     b.y = cw.take<float>(nd); b.dy = cw.take<float>(nd); b.dP = cw.take<float>(nn);
-    b.dq = cw.take<float>(nd); b.dk = cw.take<float>(nd); b.dv = cw.take<float>(nd);
+    b.dq = cw.take<float>(nd); b.dk = cw.take<float>(nkd); b.dv = cw.take<float>(nkd);
     if (ns) *ns = cs.off; if (nw) *nw = cw.off;
     return b;
 }
-size_t sdpa_saved_bytes(const MopkSdpaArgs *a) { size_t s; sdpa_carve(nullptr, nullptr, mkdm(a->B, a->H, a->N, a->dk), &s, nullptr); return s; }
-size_t sdpa_ws_bytes(const MopkSdpaArgs *a) { size_t w; sdpa_carve(nullptr, nullptr, mkdm(a->B, a->H, a->N, a->dk), nullptr, &w); return w; }
+size_t sdpa_saved_bytes(const MopkSdpaArgs *a) { size_t s; sdpa_carve(nullptr, nullptr, mkdm_nk(a->B, a->H, a->N, sdpa_nk(*a), a->dk), &s, nullptr); return s; }
+size_t sdpa_ws_bytes(const MopkSdpaArgs *a) { size_t w; sdpa_carve(nullptr, nullptr, mkdm_nk(a->B, a->H, a->N, sdpa_nk(*a), a->dk), nullptr, &w); return w; }
 int sdpa_fwd(const MopkSdpaArgs *a, hipStream_t st) {
-    const Dm d = mkdm(a->B, a->H, a->N, a->dk);
+    const Dm d = mkdm_nk(a->B, a->H, a->N, sdpa_nk(*a), a->dk), dkey = key_rows(d);
     const SdpaBuf b = sdpa_carve(a->saved, a->workspace, d, nullptr, nullptr);
     const bool mf = a->precision == MOPK_PREC_BF16;
-    RET_IF(gather(a->io_dtype, a->q, b.q, d, st)); RET_IF(gather(a->io_dtype, a->k, b.k, d, st)); RET_IF(gather(a->io_dtype, a->v, b.v, d, st));
+    RET_IF(gather(a->io_dtype, a->q, b.q, d, st)); RET_IF(gather(a->io_dtype, a->k, b.k, dkey, st)); RET_IF(gather(a->io_dtype, a->v, b.v, dkey, st));
     RET_IF(gemm_nt_scores(b.q, b.k, b.P, d, 1.f / sqrtf((float)d.dk), mf, st));
     const MaskSpec m{a->causal, a->mask, a->mask_sb, a->mask_sh, a->mask_si, a->bias, a->bias_sb, a->bias_sh, a->bias_si};
     const int64_t rows = d.BH * d.N;
@@ -179,7 +183,7 @@ int sdpa_fwd(const MopkSdpaArgs *a, hipStream_t st) {
     return scatter(a->io_dtype, b.y, a->y, d, st);
 }
 int sdpa_bwd(const MopkSdpaArgs *a, hipStream_t st) {
-    const Dm d = mkdm(a->B, a->H, a->N, a->dk);
+    const Dm d = mkdm_nk(a->B, a->H, a->N, sdpa_nk(*a), a->dk), dkey = key_rows(d);
     const SdpaBuf b = sdpa_carve(a->saved, a->workspace, d, nullptr, nullptr);
     const bool mf = a->precision == MOPK_PREC_BF16;
     const int64_t rows = d.BH * d.N;
@@ -189,8 +193,8 @@ int sdpa_bwd(const MopkSdpaArgs *a, hipStream_t st) {
     MOPK_CHECK_LAUNCH();
     RET_IF(gemm_map_vec(b.dP, false, b.k, b.dq, d, 1.f, 0.f, mf, st));
     RET_IF(gemm_map_vec(b.dP, true, b.q, b.dk, d, 1.f, 0.f, mf, st));
-    RET_IF(scatter(a->io_dtype, b.dq, a->dq, d, st)); RET_IF(scatter(a->io_dtype, b.dk, a->dk_, d, st));
-    return scatter(a->io_dtype, b.dv, a->dv, d, st);
+    RET_IF(scatter(a->io_dtype, b.dq, a->dq, d, st)); RET_IF(scatter(a->io_dtype, b.dk, a->dk_, dkey, st));
+    return scatter(a->io_dtype, b.dv, a->dv, dkey, st);
 }
 
 // =====================================================================  dual path (MultiHopMSA)
@@ -522,7 +526,7 @@ int qt_fwd(const MopkQuartetArgs *a, hipStream_t st) {
     hipLaunchKernelGGL(qt_mix_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, *a, d, b);
     if (a->dropout_p > 0.f) {                                                          // :119; the returned weights are the dropped ones (:125-126)
         drop_map(b.P, b.dP, d, a->dropout_p, a->dropout_seed, st);
-        if (a->attn) hipLaunchKernelGGL(drop_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.P, d.LD, a->attn, d.N, fa_drop(a->dropout_p, a->dropout_seed), rows, d.N);
+        if (a->attn) hipLaunchKernelGGL(drop_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.P, d.LD, a->attn, d.N, fa_drop(a->dropout_p, a->dropout_seed), rows, d.N, d.N);
     }
     MOPK_CHECK_LAUNCH();
     RET_IF(gemm_map_vec(a->dropout_p > 0.f ? b.dP : b.P, false, b.v, b.y, d, 1.f, 0.f, mf, st));   // :121

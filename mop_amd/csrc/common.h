@@ -48,6 +48,8 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// key / value length of a plain SDPA call: N queries attend to Nk keys (cross-attention); Nk = 0 means N (square)
+__host__ __device__ inline int sdpa_nk(const MopkSdpaArgs &a) { return a.Nk > 0 ? a.Nk : a.N; }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ---- attention dropout: counter-based keep mask, a pure function of (seed, b*H+h, query, key) -- evaluated again in the backward

@@ -49,11 +49,11 @@ __device__ __forceinline__ FaMB fa_mb(const MopkSdpaArgs &a, int b, int hh) {
     m.bias = a.bias ? a.bias + b * a.bias_sb + hh * a.bias_sh : nullptr;
     return m;
 }
-// one element: logit (base-2 units) -> logit + bias, or FA_NEG when blocked.  Written as selects on unconditionally loaded
+// one element (query i < N, key j < Nk): logit (base-2 units) -> logit + bias, or FA_NEG when blocked.  Written as selects on unconditionally loaded
 // values (indices clamped into range): a per-lane branch around an element write of the accumulator vector is miscompiled
 // by hipcc 7.2 (the taken path clobbers the other 15 elements).
-__device__ __forceinline__ float fa_apply_mb(float z, const FaMB &m, const MopkSdpaArgs &a, int i, int j, bool &blocked) {
-    const int ic = min(i, a.N - 1), jc = min(j, a.N - 1);
+__device__ __forceinline__ float fa_apply_mb(float z, const FaMB &m, const MopkSdpaArgs &a, int i, int j, int Nk, bool &blocked) {
+    const int ic = min(i, a.N - 1), jc = min(j, Nk - 1);
     float bz = 0.f;
     unsigned int keep = 1;
     if (m.bias) bz = m.bias[(int64_t)ic * a.bias_si + jc] * FA_LOG2E;          // wave-uniform pointer tests
@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
     constexpr int DT = DK / 32, LDK = DK + 8;
     __shared__ __attribute__((aligned(16))) unsigned short Ks[FA_KT * LDK], Vt[DK * FA_LDT], K2s[DUAL ? FA_KT * LDK : 8];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int N = a.N;
+    const int N = a.N, Nk = CAUSAL ? N : sdpa_nk(a);              // queries, keys (causal calls are square)
     int qb, bh;
     fa_block_id((N + FA_QB - 1) / FA_QB, qb, bh);
     const int b = bh / a.H, hh = bh % a.H;
@@ -93,12 +93,12 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
     f32x16 O[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) O[dt] = fa_zero();
-    int nkt = (N + FA_KT - 1) / FA_KT;
+    int nkt = (Nk + FA_KT - 1) / FA_KT;
     if (CAUSAL) nkt = min(nkt, (min(q0 + FA_QB, N) + FA_KT - 1) / FA_KT);   // keys beyond the block's last query are never seen
     FaTile<DK> fk, fv, fk2;               // next tile's K / V (/ K2) rows, in flight while the current tile is computed
-    fa_fetch<DK, IOT>(fk, kp, a.k.sn, 0, N, 1.f, tid);
-    fa_fetch<DK, IOT>(fv, vp, a.v.sn, 0, N, 1.f, tid);
-    if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, u.k2.sn, 0, N, 1.f, tid);
+    fa_fetch<DK, IOT>(fk, kp, a.k.sn, 0, Nk, 1.f, tid);
+    fa_fetch<DK, IOT>(fv, vp, a.v.sn, 0, Nk, 1.f, tid);
+    if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, u.k2.sn, 0, Nk, 1.f, tid);
     for (int kt = 0; kt < nkt; ++kt) {
         const int k0 = kt * FA_KT;
         __syncthreads();
@@ -106,14 +106,14 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
         fa_put<DK, false, true>(nullptr, Vt, fv, tid);
         if (DUAL) fa_put<DK, true, false>(K2s, nullptr, fk2, tid);
         if (kt + 1 < nkt) {
-            fa_fetch<DK, IOT>(fk, kp, a.k.sn, k0 + FA_KT, N, 1.f, tid);
-            fa_fetch<DK, IOT>(fv, vp, a.v.sn, k0 + FA_KT, N, 1.f, tid);
-            if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, u.k2.sn, k0 + FA_KT, N, 1.f, tid);
+            fa_fetch<DK, IOT>(fk, kp, a.k.sn, k0 + FA_KT, Nk, 1.f, tid);
+            fa_fetch<DK, IOT>(fv, vp, a.v.sn, k0 + FA_KT, Nk, 1.f, tid);
+            if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, u.k2.sn, k0 + FA_KT, Nk, 1.f, tid);
         }
         __syncthreads();
         f32x16 S[2];
         float mx = FA_NEG;
-        const bool edge = k0 + FA_KT > N || (CAUSAL && k0 + FA_KT - 1 > q0 + 32 * wu);
+        const bool edge = k0 + FA_KT > Nk || (CAUSAL && k0 + FA_KT - 1 > q0 + 32 * wu);
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             S[s2] = fa_mm_rows<DK>(Ks, 32 * s2, r, h, qe);
@@ -124,13 +124,13 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
             }
             if (MB) {
 #pragma unroll
-                for (int g = 0; g < 16; ++g) { bool blk; S[s2][g] = fa_apply_mb(S[s2][g], mb, a, qi, k0 + 32 * s2 + tile_row(g, h), blk); }
+                for (int g = 0; g < 16; ++g) { bool blk; S[s2][g] = fa_apply_mb(S[s2][g], mb, a, qi, k0 + 32 * s2 + tile_row(g, h), Nk, blk); }
             }
             if (edge) {                         // wave-uniform: only tiles that touch the end of the keys or this wave's diagonal pay for the mask
 #pragma unroll
                 for (int g = 0; g < 16; ++g) {
                     const int j = k0 + 32 * s2 + tile_row(g, h);
-                    S[s2][g] = (j >= N || (CAUSAL && j > qi)) ? FA_NEG : S[s2][g];      // select, not a branch around the element write
+                    S[s2][g] = (j >= Nk || (CAUSAL && j > qi)) ? FA_NEG : S[s2][g];      // select, not a branch around the element write
                 }
             }
 #pragma unroll
@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_d
     __shared__ __attribute__((aligned(16))) unsigned short Ks[FA_KT * LDK], Vs[FA_KT * LDK], Kt[DK * FA_LDT];
     __shared__ __attribute__((aligned(16))) unsigned short K2s[DUAL ? FA_KT * LDK : 8], K2t[DUAL ? DK * FA_LDT : 8];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int N = a.N;
+    const int N = a.N, Nk = CAUSAL ? N : sdpa_nk(a);              // queries, keys (causal calls are square)
     int qb, bh;
     fa_block_id((N + FA_QB - 1) / FA_QB, qb, bh);
     const int b = bh / a.H, hh = bh % a.H;
@@ -233,12 +233,12 @@ __global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_d
     f32x16 dQ[DT], dQ2[DUAL ? DT : 1];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) { dQ[dt] = fa_zero(); if (DUAL) dQ2[dt] = fa_zero(); }
-    int nkt = (N + FA_KT - 1) / FA_KT;
+    int nkt = (Nk + FA_KT - 1) / FA_KT;
     if (CAUSAL) nkt = min(nkt, (min(q0 + FA_QB, N) + FA_KT - 1) / FA_KT);
     FaTile<DK> fk, fv, fk2;
-    fa_fetch<DK, IOT>(fk, kp, a.k.sn, 0, N, 1.f, tid);
-    fa_fetch<DK, IOT>(fv, vp, a.v.sn, 0, N, 1.f, tid);
-    if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, u.k2.sn, 0, N, 1.f, tid);
+    fa_fetch<DK, IOT>(fk, kp, a.k.sn, 0, Nk, 1.f, tid);
+    fa_fetch<DK, IOT>(fv, vp, a.v.sn, 0, Nk, 1.f, tid);
+    if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, u.k2.sn, 0, Nk, 1.f, tid);
     for (int kt = 0; kt < nkt; ++kt) {
         const int k0 = kt * FA_KT;
         __syncthreads();
@@ -246,9 +246,9 @@ __global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_d
         fa_put<DK, true, false>(Vs, nullptr, fv, tid);
         if (DUAL) fa_put<DK, true, true>(K2s, K2t, fk2, tid);
         if (kt + 1 < nkt) {
-            fa_fetch<DK, IOT>(fk, kp, a.k.sn, k0 + FA_KT, N, 1.f, tid);
-            fa_fetch<DK, IOT>(fv, vp, a.v.sn, k0 + FA_KT, N, 1.f, tid);
-            if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, u.k2.sn, k0 + FA_KT, N, 1.f, tid);
+            fa_fetch<DK, IOT>(fk, kp, a.k.sn, k0 + FA_KT, Nk, 1.f, tid);
+            fa_fetch<DK, IOT>(fv, vp, a.v.sn, k0 + FA_KT, Nk, 1.f, tid);
+            if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, u.k2.sn, k0 + FA_KT, Nk, 1.f, tid);
         }
         __syncthreads();
 #pragma unroll
@@ -261,9 +261,9 @@ __global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_d
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
                 const int j = k0 + 32 * s2 + tile_row(g, h);
-                bool ok = qok && j < N && (!CAUSAL || j <= qi);
+                bool ok = qok && j < Nk && (!CAUSAL || j <= qi);
                 float z = DUAL ? fa_mix(S[g], T2[g], u.a2, u.g_or) : S[g];
-                if (MB) { bool blk; z = fa_apply_mb(z, mb, a, qi, j, blk); ok = ok && !blk; }
+                if (MB) { bool blk; z = fa_apply_mb(z, mb, a, qi, j, Nk, blk); ok = ok && !blk; }
                 const float p = ok ? __builtin_amdgcn_exp2f(z - Li) : 0.f;
                 float dp = dP[g];                                // dropout: dP = (dy v^T) keep / (1 - p); delta = dy . y already has it
                 if (drop.thresh) dp = fa_drop_keep(drop, rowh, j) ? dp * drop.inv_keep : 0.f;
@@ -292,12 +292,12 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
     __shared__ __attribute__((aligned(16))) float Ls[FA_KT], Ds[FA_KT];      // 16-byte aligned: the four consecutive rows of a register quad are one ds_read_b128
     __shared__ __attribute__((aligned(16))) uint32_t Hs[FA_KT];              // dropout row hashes of the tile's queries
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int N = a.N;
+    const int N = a.N, Nk = CAUSAL ? N : sdpa_nk(a);              // queries, keys (causal calls are square)
     int kb, bh;
-    fa_block_id((N + FA_QB - 1) / FA_QB, kb, bh);
+    fa_block_id((Nk + FA_QB - 1) / FA_QB, kb, bh);
     const int b = bh / a.H, hh = bh % a.H;
     const int k0 = kb * FA_QB, kj = k0 + 32 * w + r;
-    const bool kok = kj < N;
+    const bool kok = kj < Nk;
     const float c = rsqrtf((float)DK) * FA_LOG2E;
     const IOT *qp = (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh, *gp = (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh;
     bf16x8 kf[DK / 16], vf[DK / 16];
@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
                 const int il = 32 * s2 + tile_row(g, h), i = i0 + il;
                 bool ok = kok && i < N && (!CAUSAL || kj <= i);
                 float z = DUAL ? fa_mix(S[g], T2[g], u.a2, u.g_or) : S[g];
-                if (MB) { bool blk; z = fa_apply_mb(z, mb, a, i, kj, blk); ok = ok && !blk; }
+                if (MB) { bool blk; z = fa_apply_mb(z, mb, a, i, kj, Nk, blk); ok = ok && !blk; }
                 const float p = ok ? __builtin_amdgcn_exp2f(z - lrow[g]) : 0.f;
                 float dp = dP[g], pd = p;                         // dropout: dV sees P keep / (1 - p), dP = (dy v^T) keep / (1 - p)
                 if (drop.thresh) { const float kp = fa_drop_keep(drop, Hs[il], kj) ? drop.inv_keep : 0.f; dp *= kp; pd *= kp; }
@@ -392,6 +392,7 @@ static bool fa_aligned(const MopkView4 &v, int es) {
 int sdpa_flash_supported(const MopkSdpaArgs *a, bool bwd) {
     if (a->precision != MOPK_PREC_BF16) return 0;                 // fp32-exact arithmetic stays on the generic path
     if (a->dk != 32 && a->dk != 64) return 0;
+    if (a->causal && sdpa_nk(*a) != a->N) return 0;               // causal is defined for square calls only
     const int es = a->io_dtype == MOPK_BF16 ? 2 : 4;
     if (!fa_aligned(a->q, es) || !fa_aligned(a->k, es) || !fa_aligned(a->v, es) || !fa_aligned(a->y, es)) return 0;
     if (bwd && (!fa_aligned(a->dy, es) || !fa_aligned(a->dq, es) || !fa_aligned(a->dk_, es) || !fa_aligned(a->dv, es))) return 0;
@@ -429,10 +430,10 @@ int sdpa_flash_bwd(const MopkSdpaArgs *a, hipStream_t st) {
     if (a->io_dtype == MOPK_BF16) hipLaunchKernelGGL((sdpa_flash_delta_kernel<unsigned short>), dim3((rows * (a->dk / 8) + 255) / 256), dim3(256), 0, st, *a, delta);
     else hipLaunchKernelGGL((sdpa_flash_delta_kernel<float>), dim3((rows * (a->dk / 8) + 255) / 256), dim3(256), 0, st, *a, delta);
     MOPK_CHECK_LAUNCH();
-    const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H);
+    const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H), kgrid(((sdpa_nk(*a) + FA_QB - 1) / FA_QB) * a->B * a->H);
     FA_DISPATCH(sdpa_flash_dq_kernel, false, grid, *a, (const float *)a->saved, (const float *)delta, FaDual{});
     MOPK_CHECK_LAUNCH();
-    FA_DISPATCH(sdpa_flash_dkv_kernel, false, grid, *a, (const float *)a->saved, (const float *)delta, FaDual{});
+    FA_DISPATCH(sdpa_flash_dkv_kernel, false, kgrid, *a, (const float *)a->saved, (const float *)delta, FaDual{});
     MOPK_CHECK_LAUNCH();
     return MOPK_OK;
 }
@@ -466,7 +467,7 @@ static MopkView4 dp_tmp_view(void *p, const MopkDualPathArgs *a) {     // contig
     return MopkView4{p, (int64_t)a->N * a->H * a->dk, (int64_t)a->dk, (int64_t)a->H * a->dk};
 }
 static MopkSdpaArgs dp_sdpa(const MopkDualPathArgs *a) {
-    MopkSdpaArgs s{};
+    MopkSdpaArgs s{};                                              // Nk = 0: every dual-path pass is square
     s.B = a->B; s.H = a->H; s.N = a->N; s.dk = a->dk; s.io_dtype = a->io_dtype; s.precision = MOPK_PREC_BF16; s.path = MOPK_PATH_FUSED;
     s.causal = a->causal;
     s.mask = a->mask; s.mask_sb = a->mask_sb; s.mask_sh = a->mask_sh; s.mask_si = a->mask_si;      // every pass (A1, A2 and the mixed weights) sees it: :202-207, :219-220

@@ -1,9 +1,11 @@
-"""Encoder side of Whisper-MoP with the reference's parameter names (mop/models/whisper_mop.py).
+"""Whisper-MoP with the reference's parameter names (mop/models/whisper_mop.py).
 
-`MultiheadSelfAttention` (reference :137-177) runs its attention core in libmopk (plain SDPA with
-the causal flag and the additive `attn_bias`); the mel-map gate `MoP2D`
-(:91-124, row a17) and the MLP are stock PyTorch-ROCm layers.  The decoder and its
-cross-attention (:180-228, :291-317) are outside the hot path and are not mirrored.
+`MultiheadSelfAttention` (reference :137-177) and `MultiheadCrossAttention` (:180-221) run their attention cores in libmopk
+(plain SDPA: the causal flag and the additive bias for self-attention; rectangular SDPA with Nk = T_audio
+keys for cross-attention).  `EncoderBlock` (:241-264), `DecoderBlock` (:267-290), `WhisperMoP` (:296-424) and the factories
+`create_whisper_mop` / `create_whisper_baseline` (:427-437) follow the reference's constructors, forward signatures, return values,
+`state_dict` names and initialisation.  The mel-map gate `MoP2D` (:91-124, row a17), the LayerNorms, the MLP and the embeddings
+are stock PyTorch-ROCm layers.
 """
 from __future__ import annotations
 
@@ -107,6 +109,34 @@ class MultiheadSelfAttention(nn.Module):
         return self.resid_drop(self.o_proj(y))
 
 
+class MultiheadCrossAttention(nn.Module):
+    """queries from x_q, keys / values from x_kv; softmax(q k^T / sqrt(dh) [+ attn_mask]) v in libmopk with Nk = T_kv keys
+    (reference :180-221).  attn_mask is ADDITIVE in the reference (:213-214), so it is passed to the core as its bias."""
+
+    def __init__(self, dim_q: int, dim_kv: int, n_head: int, dropout: float, bias: bool):
+        super().__init__()
+        assert dim_q % n_head == 0
+        self.n_head, self.head_dim = n_head, dim_q // n_head
+        self.scale = self.head_dim ** -0.5
+        self.q_proj = TokenLinear(dim_q, dim_q, bias=bias)
+        self.k_proj = TokenLinear(dim_kv, dim_q, bias=bias)
+        self.v_proj = TokenLinear(dim_kv, dim_q, bias=bias)
+        self.o_proj = TokenLinear(dim_q, dim_q, bias=bias)
+        self.attn_drop = nn.Dropout(dropout)
+        self.resid_drop = nn.Dropout(dropout)
+
+    def forward(self, x_q: torch.Tensor, x_kv: torch.Tensor, attn_mask: Optional[torch.Tensor] = None):
+        pdrop = float(self.attn_drop.p) if self.training else 0.0      # dropout on the probabilities (:217), inside the kernels
+        B, Tq, _ = x_q.shape
+        Tk = x_kv.shape[1]
+        H, Dh = self.n_head, self.head_dim
+        q = self.q_proj(x_q).view(B, Tq, H, Dh)
+        k = self.k_proj(x_kv).view(B, Tk, H, Dh)
+        v = self.v_proj(x_kv).view(B, Tk, H, Dh)
+        y = ops.sdpa_core(q, k, v, bias=attn_mask, dropout_p=pdrop)
+        return self.resid_drop(self.o_proj(y))
+
+
 class MLP(nn.Module):
     def __init__(self, dim: int, dropout: float, bias: bool):
         super().__init__()
@@ -136,3 +166,114 @@ class EncoderBlock(nn.Module):
         x = x * gate_t
         x = x + self.mlp(self.ln2(x))
         return x, gate_t.squeeze(-1)
+
+
+class DecoderBlock(nn.Module):
+    """x + causal SA(ln1 x); x + CA(ln2 x, enc); x + MLP(ln3 x)   (reference :267-290)."""
+
+    def __init__(self, cfg: WhisperConfig):
+        super().__init__()
+        D = cfg.n_embd
+        self.ln1 = nn.LayerNorm(D)
+        self.self_attn = MultiheadSelfAttention(D, cfg.n_head, cfg.dropout, cfg.bias, causal=True)
+        self.ln2 = nn.LayerNorm(D)
+        self.cross_attn = MultiheadCrossAttention(D, D, cfg.n_head, cfg.dropout, cfg.bias)
+        self.ln3 = nn.LayerNorm(D)
+        self.mlp = MLP(D, cfg.dropout, cfg.bias)
+
+    def forward(self, x: torch.Tensor, enc: torch.Tensor) -> torch.Tensor:
+        x = x + self.self_attn(self.ln1(x))
+        x = x + self.cross_attn(self.ln2(x), enc)
+        x = x + self.mlp(self.ln3(x))
+        return x
+
+
+class WhisperMoP(nn.Module):
+    """Encoder-decoder with the MoP mel gate in every encoder block (reference :296-424).
+    forward(mel, dec_input_ids, targets=None) -> (logits, loss, gates); lm_head is tied to wte."""
+
+    def __init__(self, cfg: WhisperConfig):
+        super().__init__()
+        self.cfg = cfg
+        D = cfg.n_embd
+        self.audio_proj = nn.Linear(cfg.n_mels, D, bias=cfg.bias)
+        self.audio_pos = nn.Embedding(cfg.n_audio_ctx, D) if cfg.use_abs_pos_emb else None
+        self.wte = nn.Embedding(cfg.vocab_size, D)
+        self.text_pos = nn.Embedding(cfg.n_text_ctx, D) if cfg.use_abs_pos_emb else None
+        self.drop = nn.Dropout(cfg.dropout)
+        self.encoder = nn.ModuleList([EncoderBlock(cfg) for _ in range(cfg.n_layer_enc)])
+        self.decoder = nn.ModuleList([DecoderBlock(cfg) for _ in range(cfg.n_layer_dec)])
+        self.enc_ln_f = nn.LayerNorm(D)
+        self.dec_ln_f = nn.LayerNorm(D)
+        self.lm_head = nn.Linear(D, cfg.vocab_size, bias=False)
+        self.lm_head.weight = self.wte.weight
+        self.apply(self._init_weights)
+
+    def _init_weights(self, m):                                      # reference :336-346
+        if isinstance(m, nn.Linear):
+            nn.init.normal_(m.weight, mean=0.0, std=0.02)
+            if m.bias is not None:
+                nn.init.zeros_(m.bias)
+        elif isinstance(m, nn.Embedding):
+            nn.init.normal_(m.weight, mean=0.0, std=0.02)
+        elif isinstance(m, nn.LayerNorm):
+            nn.init.ones_(m.weight)
+            nn.init.zeros_(m.bias)
+
+    @torch.no_grad()
+    def _pos(self, T: int, device: torch.device) -> torch.Tensor:
+        return torch.arange(T, device=device, dtype=torch.long).unsqueeze(0)
+
+    def encode(self, mel: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """mel (B, T_audio, n_mels) -> enc_out (B, T_audio, D), gates (B, L_enc, T_audio)."""
+        B, T_a, F_ = mel.shape
+        assert F_ == self.cfg.n_mels, "mel dim mismatch"
+        x = self.audio_proj(mel)
+        if self.audio_pos is not None:
+            x = x + self.audio_pos(self._pos(T_a, mel.device))
+        x = self.drop(x)
+        mel2d = mel.unsqueeze(1).contiguous()                        # (B,1,T,F), as the reference's two transposes give
+        gate_layers = []
+        for blk in self.encoder:
+            x, gate_t = blk(x, mel2d)
+            gate_layers.append(gate_t)
+        x = self.enc_ln_f(x)
+        return x, torch.stack(gate_layers, dim=1)
+
+    def decode(self, enc_out: torch.Tensor, dec_input_ids: torch.Tensor) -> torch.Tensor:
+        """enc_out (B, T_audio, D), dec_input_ids (B, T_text) -> logits (B, T_text, vocab)."""
+        B, T_t = dec_input_ids.shape
+        x = self.wte(dec_input_ids)
+        if self.text_pos is not None:
+            x = x + self.text_pos(self._pos(T_t, dec_input_ids.device))
+        x = self.drop(x)
+        for blk in self.decoder:
+            x = blk(x, enc_out)
+        return self.lm_head(self.dec_ln_f(x))
+
+    def forward(self, mel: torch.Tensor, dec_input_ids: torch.Tensor, targets: Optional[torch.Tensor] = None):
+        enc_out, gates = self.encode(mel)
+        logits = self.decode(enc_out, dec_input_ids)
+        loss = None
+        if targets is not None:
+            loss = F.cross_entropy(logits.view(-1, logits.size(-1)), targets.view(-1))
+        return logits, loss, gates
+
+    @torch.no_grad()
+    def get_gate_maps(self, mel: torch.Tensor):
+        """per-layer time gates of the encoder, (B, L_enc, T_audio)."""
+        _, gates = self.encode(mel)
+        return gates
+
+
+def create_whisper_mop(cfg: WhisperConfig) -> WhisperMoP:
+    return WhisperMoP(cfg)
+
+
+def create_whisper_baseline(cfg: WhisperConfig) -> WhisperMoP:
+    """the same architecture with every encoder gate's alpha at 0: gate = 1 (reference :431-437)."""
+    model = WhisperMoP(cfg)
+    with torch.no_grad():
+        for blk in model.encoder:
+            blk.mop.fuse.alpha.zero_()
+    return model

@@ -674,25 +674,27 @@ def _heads_view(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
-def _mask_u8(attn_mask, B, H, N, dev):
-    """reference convention: broadcastable to (B,H,N,N), 0 = blocked (attention_variants.py:43-44)."""
+def _mask_u8(attn_mask, B, H, N, dev, Nk=None):
+    """reference convention: broadcastable to (B,H,N,Nk) (Nk = N unless given), 0 = blocked (attention_variants.py:43-44)."""
     if attn_mask is None:
         return None, (0, 0, 0)
+    Nk = N if Nk is None else Nk
     m = (attn_mask.to(dev) != 0).to(torch.uint8)
     while m.dim() < 4:
         m = m.unsqueeze(0)
-    m = m.contiguous().expand(B, H, N, N)
-    assert m.stride(3) == 1 or N == 1
+    m = m.contiguous().expand(B, H, N, Nk)
+    assert m.stride(3) == 1 or Nk == 1
     return m, (m.stride(0), m.stride(1), m.stride(2))
 
 
-def _bias_f32(bias, B, H, N, dev):
+def _bias_f32(bias, B, H, N, dev, Nk=None):
     if bias is None:
         return None, (0, 0, 0)
+    Nk = N if Nk is None else Nk
     b = bias.to(dev, torch.float32)
     while b.dim() < 4:
         b = b.unsqueeze(0)
-    b = b.contiguous().expand(B, H, N, N)
+    b = b.contiguous().expand(B, H, N, Nk)
     return b, (b.stride(0), b.stride(1), b.stride(2))
 
 
@@ -708,13 +710,14 @@ class _SdpaFn(torch.autograd.Function):
             q, k, v = q.contiguous().unbind(2)
         q, k, v = _heads_view(q), _heads_view(k), _heads_view(v)
         B, N, H, dk = q.shape
+        Nk = k.shape[1]                # key / value length (cross-attention); N for self-attention
         dev = q.device
         a = L.SdpaArgs()
-        a.B, a.H, a.N, a.dk = B, H, N, dk
+        a.B, a.H, a.N, a.dk, a.Nk = B, H, N, dk, Nk
         a.io_dtype, a.precision, a.path, a.causal = _io_dtype(q), prec, path, int(bool(causal))
         a.q, a.k, a.v = _v4(q), _v4(k), _v4(v)
-        m8, ms = _mask_u8(mask, B, H, N, dev)
-        bf, bs = _bias_f32(bias, B, H, N, dev)
+        m8, ms = _mask_u8(mask, B, H, N, dev, Nk)
+        bf, bs = _bias_f32(bias, B, H, N, dev, Nk)
         a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(m8), ms
         a.bias, (a.bias_sb, a.bias_sh, a.bias_si) = _ptr(bf), bs
         a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
@@ -740,11 +743,12 @@ class _SdpaFn(torch.autograd.Function):
         q, k, v, y, saved = ctx.saved_tensors
         causal, prec, path, m8, ms, bf, bs, drop = ctx.meta
         B, N, H, dk = q.shape
+        Nk = k.shape[1]
         dev = q.device
         dy = dy.contiguous().to(q.dtype).view(B, N, H, dk)
         a = L.SdpaArgs()
         a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
-        a.B, a.H, a.N, a.dk = B, H, N, dk
+        a.B, a.H, a.N, a.dk, a.Nk = B, H, N, dk, Nk
         a.io_dtype, a.precision, a.path, a.causal = _io_dtype(q), prec, path, int(bool(causal))
         a.q, a.k, a.v, a.y, a.dy = _v4(q), _v4(k), _v4(v), _v4(y), _v4(dy)
         a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(m8), ms
@@ -753,7 +757,8 @@ class _SdpaFn(torch.autograd.Function):
             dqkv = torch.empty(B, N, 3, H, dk, dtype=q.dtype, device=dev)
             dq, dk_, dv = dqkv.unbind(2)
         else:
-            dq, dk_, dv = (torch.empty(B, N, H, dk, dtype=q.dtype, device=dev) for _ in range(3))
+            dq = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
+            dk_, dv = (torch.empty(B, Nk, H, dk, dtype=q.dtype, device=dev) for _ in range(2))
         a.dq, a.dk_, a.dv = _v4(dq), _v4(dk_), _v4(dv)
         LAST_PATH["sdpa_bwd"] = path
         ws = _bytes(lib.mopk_sdpa_workspace_bytes(C.byref(a)), dev)
@@ -772,8 +777,10 @@ def dropout_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
 
-def dropout_keep_mask(seed: int, p: float, B: int, H: int, N: int) -> torch.Tensor:
-    """the kernels' keep mask as a (B,H,N,N) bool tensor (host restatement of `mopk_dropout_keep`, vectorised; tests / debugging)"""
+def dropout_keep_mask(seed: int, p: float, B: int, H: int, N: int, Nk: Optional[int] = None) -> torch.Tensor:
+    """the kernels' keep mask as a (B,H,N,Nk) bool tensor, Nk = N unless given (host restatement of `mopk_dropout_keep`, vectorised;
+    tests / debugging)"""
+    Nk = N if Nk is None else Nk
     import numpy as np
     def h32(x):
         x = x.astype(np.uint64)
@@ -787,17 +794,27 @@ def dropout_keep_mask(seed: int, p: float, B: int, H: int, N: int) -> torch.Tens
     thresh = np.uint64(0xffffffff if t >= 4294967295.0 else (1 if t < 1.0 else int(t)))
     bh = np.arange(B * H, dtype=np.uint64)[:, None, None]
     i = np.arange(N, dtype=np.uint64)[None, :, None]
-    j = np.arange(N, dtype=np.uint64)[None, None, :]
+    j = np.arange(Nk, dtype=np.uint64)[None, None, :]
     row = h32((i * np.uint64(0x9E3779B1) + bh * np.uint64(0x85EBCA77) + hi) & M) ^ lo
     keep = h32((row ^ ((j * np.uint64(0xC2B2AE3D)) & M)) & M) >= thresh
-    return torch.from_numpy(keep.reshape(B, H, N, N)) if p > 0 else torch.ones(B, H, N, N, dtype=torch.bool)
+    return torch.from_numpy(keep.reshape(B, H, N, Nk)) if p > 0 else torch.ones(B, H, N, Nk, dtype=torch.bool)
 
 
 @_half_via_fp32
 def sdpa_core(q, k=None, v=None, attn_mask=None, bias=None, causal=False, dropout_p: float = 0.0, seed: Optional[int] = None):
-    """q,k,v: (B,N,H,dk) views -- or packed: q = the (B,N,3,H,dk) output of one qkv projection, k = v = None (one packed gradient comes
-    back).  Returns (B,N,H*dk).  attn_mask: 0 = blocked; bias: additive.  dropout_p > 0: the probabilities are multiplied by
-    keep / (1 - p) (mask = `dropout_keep_mask(seed, ...)`, seed drawn when None)."""
+    """q: (B,N,H,dk), k, v: (B,Nk,H,dk) views -- Nk != N is rectangular (cross-)attention: N queries attend to Nk keys -- or packed:
+    q = the (B,N,3,H,dk) output of one qkv projection, k = v = None (square; one packed gradient comes back).  Returns (B,N,H*dk).
+    attn_mask: 0 = blocked; bias: additive; both broadcastable to (B,H,N,Nk).  causal needs Nk == N (ValueError otherwise).
+    dropout_p > 0: the probabilities are multiplied by keep / (1 - p) (mask = `dropout_keep_mask(seed, B, H, N, Nk)`, seed drawn
+    when None)."""
+    if k is not None:
+        if k.dim() != 4 or v is None or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2:] != q.shape[2:]:
+            raise ValueError(f"sdpa_core: k, v must be (B, Nk, H, dk) with q's B, H, dk; got q {tuple(q.shape)}, k {tuple(k.shape)}, "
+                             f"v {tuple(v.shape) if v is not None else None}")
+        if k.shape[1] == 0 and q.shape[1] > 0:        # Nk = 0 means "N" in the C ABI: never pass it through
+            raise ValueError("sdpa_core: k, v have no keys (Nk = 0)")
+        if causal and k.shape[1] != q.shape[1]:
+            raise ValueError(f"sdpa_core: causal attention needs as many keys as queries (N = {q.shape[1]}, Nk = {k.shape[1]})")
     if q.shape[0] == 0:
         if k is None:
             return _empty_batch(q, 0, q.shape[1], q.shape[-2] * q.shape[-1])

@@ -98,10 +98,10 @@ def _run(mod, x, fwd_kwargs=None, extra=None, hook=None, bf16_self=False):
     return out
 
 
-def _save(name, d):
+def _save(name, d, compress=False):
     os.makedirs(OUT, exist_ok=True)
     path = os.path.join(OUT, name + ".npz")
-    np.savez(path, **d)
+    (np.savez_compressed if compress else np.savez)(path, **d)
     ymax = f"|y|max={np.abs(d['y']).max():.4f}" if "y" in d else ""
     print(f"{name:40s} {os.path.getsize(path) / 1e6:7.3f} MB  {ymax}")
 
@@ -453,9 +453,97 @@ def gpt_cases():
         _save(name, out)
 
 
+def whisper_decoder_cases():
+    """Whisper decoder side (whisper_mop.py:180-221, :267-290, :296-437).  whdec_*: DecoderBlock (causal self-attention, cross-attention
+    to the encoder output, MLP) x, enc -> y with dx, d enc and every parameter gradient of L = sum(y * w), at query / key lengths off
+    the 64-token tiles on both sides of T_t = T_a.  whlm_*: a 2 + 2 layer WhisperMoP (and create_whisper_baseline) mel, ids, targets
+    -> logits, loss, gates and every parameter gradient of the loss (the tied wte / lm_head weight included)."""
+    import copy
+    from mop.models.whisper_mop import DecoderBlock, WhisperMoP, create_whisper_baseline
+    rel = lambda a, b: float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+    blocks = [
+        # name, dim, heads, B, T_t, T_a, bias    (dim / heads = 32: the fused kernels' head size; 16: the generic path only)
+        ("whdec_t37_a150", 32, 1, 2, 37, 150, False),
+        ("whdec_t130_a65_bias", 32, 1, 2, 130, 65, True),
+        ("whdec_t20_a48_h2", 32, 2, 2, 20, 48, False),
+    ]
+    for i, (name, dim, heads, B, Tt, Ta, bias) in enumerate(blocks):
+        torch.manual_seed(1500 + i)
+        cfg = WhisperConfig(n_mels=8, n_audio_ctx=Ta, n_text_ctx=Tt, n_embd=dim, n_head=heads, n_layer_enc=1, n_layer_dec=1, bias=bias)
+        mod = DecoderBlock(cfg).eval()
+        with torch.no_grad():                 # the default LayerNorm / zero-bias init hides the affine parameters' gradients
+            for k, p in mod.named_parameters():
+                if k.endswith(".bias") or k.startswith("ln"):
+                    p.add_(0.1 * torch.randn(p.shape))
+        x = torch.randn(B, Tt, dim).requires_grad_(True)
+        enc = torch.randn(B, Ta, dim).requires_grad_(True)
+        y = mod(x, enc)
+        w = torch.randn(y.shape, generator=torch.Generator().manual_seed(4242))
+        (y * w).sum().backward()
+        out = {"x": x.detach().numpy(), "enc": enc.detach().numpy(), "y": y.detach().numpy(), "w": w.numpy(),
+               "dx": x.grad.numpy(), "denc": enc.grad.numpy()}
+        for k, v in mod.state_dict().items():
+            out["param:" + k] = v.detach().numpy()
+        for k, p in mod.named_parameters():
+            out["grad:" + k] = p.grad.numpy()
+        mb = copy.deepcopy(mod).to(torch.bfloat16)           # the reference's own bf16 run: noise floor per tensor
+        xb = x.detach().to(torch.bfloat16).requires_grad_(True)
+        eb = enc.detach().to(torch.bfloat16).requires_grad_(True)
+        yb = mb(xb, eb)
+        (yb * w.to(torch.bfloat16)).sum().backward()
+        out["bf16err:y"] = np.float32(np.abs(yb.detach().float().numpy() - out["y"]).max())
+        out["bf16err:dx"] = np.float32(rel(xb.grad.float().numpy(), out["dx"]))
+        out["bf16err:denc"] = np.float32(rel(eb.grad.float().numpy(), out["denc"]))
+        for k, p in mb.named_parameters():
+            out["bf16err:" + k] = np.float32(rel(p.grad.float().numpy(), out["grad:" + k]))
+        meta = dict(kind="whisper_dec", dim=dim, heads=heads, T_t=Tt, T_a=Ta, bias=bias)
+        out.update({"meta:" + k: np.asarray(v) for k, v in meta.items()})
+        _save(name, out, compress=True)
+
+    def lm_run(mod, mel, idx, tgt):
+        mod.zero_grad(set_to_none=True)
+        logits, loss, gates = mod(mel, idx, tgt)
+        loss.backward()
+        return logits, loss, gates, {k: p.grad.clone() for k, p in mod.named_parameters() if p.grad is not None}
+
+    vocab, n_mels = 100, 10
+    lms = [
+        # name, factory, B, T_a, T_t, use_abs_pos_emb, bias
+        ("whlm_mop", "mop", 2, 40, 16, True, False),
+        ("whlm_mop_nopos", "mop", 2, 33, 21, False, False),
+        ("whlm_baseline_bias", "baseline", 2, 40, 16, True, True),
+    ]
+    for i, (name, kind, B, Ta, Tt, pos, bias) in enumerate(lms):
+        torch.manual_seed(1600 + i)
+        cfg = WhisperConfig(n_mels=n_mels, n_audio_ctx=Ta, vocab_size=vocab, n_text_ctx=Tt, n_embd=32, n_head=1, n_layer_enc=2,
+                            n_layer_dec=2, dropout=0.0, bias=bias, use_abs_pos_emb=pos, n_views=3, n_kernels=2, kernel_size=3)
+        mod = (WhisperMoP if kind == "mop" else create_whisper_baseline)(cfg).eval()
+        g = torch.Generator().manual_seed(1700 + i)
+        mel = torch.randn(B, Ta, n_mels, generator=g)
+        idx = torch.randint(0, vocab, (B, Tt), generator=g)
+        tgt = torch.randint(0, vocab, (B, Tt), generator=g)
+        logits, loss, gates, grads = lm_run(mod, mel, idx, tgt)
+        out = {"mel": mel.numpy(), "idx": idx.numpy(), "targets": tgt.numpy(), "logits": logits.detach().numpy(),
+               "loss": np.float32(loss.item()), "gates": gates.detach().numpy()}
+        for k, v in mod.state_dict().items():
+            out["param:" + k] = v.detach().numpy()
+        for k, v in grads.items():
+            out["grad:" + k] = v.numpy()
+        mb = copy.deepcopy(mod).to(torch.bfloat16)
+        _, lb, _, gb = lm_run(mb, mel.to(torch.bfloat16), idx, tgt)
+        out["bf16err:loss"] = np.float32(abs(lb.item() - loss.item()))
+        for k, v in gb.items():
+            out["bf16err:" + k] = np.float32(rel(v.float().numpy(), grads[k].numpy()))
+        meta = dict(kind="whisper_lm", model=kind, vocab=vocab, n_mels=n_mels, T_a=Ta, T_t=Tt, dim=32, heads=1, n_layer_enc=2,
+                    n_layer_dec=2, bias=bias, use_abs_pos_emb=pos, n_views=3, n_kernels=2, kernel_size=3)
+        out.update({"meta:" + k: np.asarray(v) for k, v in meta.items()})
+        out["y"] = out["logits"]
+        _save(name, out, compress=True)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     groups = dict(train=train_cases, vit=vit_cases, ew=edgewise_cases, ewx=edgewise_variant_cases, cv=crossview_cases, wh=whisper_cases, mh=multihop_cases, qt=quartet_cases, sdpa=sdpa_cases,
-                  gpt=gpt_cases)
+                  gpt=gpt_cases, whdec=whisper_decoder_cases)
     for name in (sys.argv[1:] or list(groups)):               # e.g. `gen_golden.py ewx` regenerates one group only
         groups[name]()
