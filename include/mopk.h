@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPK_VERSION 118 /* 118: MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
+#define MOPK_VERSION 118 /* 118: mopk_moe_* and MopkMoeArgs (added later without a bump: new exports only, detect with mopk_moe_supported), MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
 
 typedef enum MopkStatus {
     MOPK_OK = 0,
@@ -408,6 +408,50 @@ int mopk_token_gate_supported(const MopkTokenGateArgs *a);                /* 1 i
 size_t mopk_token_gate_workspace_bytes(const MopkTokenGateArgs *a);
 int mopk_token_gate_fwd(const MopkTokenGateArgs *a, void *stream);
 int mopk_token_gate_bwd(const MopkTokenGateArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
+ * Top-1 routed mixture-of-experts MLP (mop/models/components.py:84-121 MoEMLP), optional residual add.  (Added under version 118:
+ * new exports only, no existing layout changes; callers detect it with mopk_moe_supported.)
+ *   e_t = argmax_e (gate_w[e] . x_t + gate_b[e])   (fp32 FMA logits whatever the dtypes; ties -> lowest e, as torch.argmax)
+ *   y_t = W2_{e_t} gelu_tanh(W1_{e_t} x_t) [+ residual_t]
+ * Only the routed expert runs on a token.  Per-expert token counts stay on the device; every launch is graph-capturable.
+ * route: int32, 2 M + E + 1 entries = [expert of each token (M) | perm (M): sorted position -> token, experts in index order,
+ *        tokens ascending inside an expert (stable) | offsets (E + 1): expert e owns sorted positions [off[e], off[e+1])].
+ *   _route: writes route (used by _fwd, callable alone).
+ *   _fwd:   route, then u = W1_e x (pre-activation) and h = gelu(u), both (M,F) in sorted order and the activation dtype (BF16 under
+ *           PREC_BF16, else F32; kept for _bwd), then y (M,D) o_dtype in token order.
+ *   _bwd:   with route, u, h from _fwd and dy (M,D) o_dtype: dx (M,D) x_dtype (the residual's gradient is dy itself, not written),
+ *           dw1[e] (F,D) and dw2[e] (D,F) in w_dtype, zeros for an expert without tokens.  Weight gradients are fp32 partial slabs per
+ *           fixed-size row chunk summed in chunk order: no atomics, bitwise reproducible.
+ * x, y, residual, dy, dx: contiguous (M,D); gate_w (E,D), gate_b (E) or NULL in gate_dtype; w1[e] (F,D), w2[e] (D,F) contiguous in
+ * w_dtype, read in place.  PREC_FP32 (exact fp32 MFMA) needs x, w and o all F32; PREC_BF16 (bf16 MFMA operands, fp32 accumulation)
+ * takes any F32 / BF16 mix.  D % 8 == 0, F % 8 == 0, 2 <= E <= MOPK_MOE_MAX_EXPERTS, 16-byte aligned pointers. */
+#define MOPK_MOE_MAX_EXPERTS 64
+typedef struct MopkMoeArgs {
+    int32_t M, D, F, E;                  /* tokens, model width, hidden width, experts */
+    int32_t precision;                   /* MopkPrecision */
+    int32_t x_dtype, w_dtype, gate_dtype, o_dtype;   /* MopkDtype: x / dx; w1, w2, dw1, dw2; gate_w, gate_b; y, residual, dy */
+    int32_t reserved;
+    const void *x;
+    const void *gate_w;
+    const void *gate_b;                  /* NULL: no gate bias */
+    const void *w1[MOPK_MOE_MAX_EXPERTS];
+    const void *w2[MOPK_MOE_MAX_EXPERTS];
+    const void *residual;                /* NULL: no residual add */
+    void *y;                             /* fwd out */
+    void *u, *h;                         /* fwd out, bwd in: (M,F) activation dtype, sorted order */
+    int32_t *route;                      /* fwd / route out, bwd in */
+    const void *dy;                      /* bwd in */
+    void *dx;                            /* bwd out */
+    void *dw1[MOPK_MOE_MAX_EXPERTS];     /* bwd out */
+    void *dw2[MOPK_MOE_MAX_EXPERTS];     /* bwd out */
+    void *workspace;                     /* bwd: mopk_moe_workspace_bytes(a, 1) */
+} MopkMoeArgs;
+int mopk_moe_supported(const MopkMoeArgs *a);                       /* 1 if the kernels take this call (shape, dtypes, precision, alignment) */
+size_t mopk_moe_workspace_bytes(const MopkMoeArgs *a, int backward); /* 0 for the forward */
+int mopk_moe_route(const MopkMoeArgs *a, void *stream);
+int mopk_moe_fwd(const MopkMoeArgs *a, void *stream);
+int mopk_moe_bwd(const MopkMoeArgs *a, void *stream);
 
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);

@@ -142,6 +142,20 @@ class TokenGateArgs(C.Structure):
     ]
 
 
+MOE_MAX_EXPERTS = 64
+
+
+class MoeArgs(C.Structure):
+    """MopkMoeArgs: top-1 routed MoE MLP (ViT_MoP(use_moe=True))."""
+    _fields_ = [
+        ("M", C.c_int32), ("D", C.c_int32), ("F", C.c_int32), ("E", C.c_int32), ("precision", C.c_int32),
+        ("x_dtype", C.c_int32), ("w_dtype", C.c_int32), ("gate_dtype", C.c_int32), ("o_dtype", C.c_int32), ("reserved", C.c_int32),
+        ("x", _fp), ("gate_w", _fp), ("gate_b", _fp), ("w1", _fp * MOE_MAX_EXPERTS), ("w2", _fp * MOE_MAX_EXPERTS),
+        ("residual", _fp), ("y", _fp), ("u", _fp), ("h", _fp), ("route", _fp), ("dy", _fp), ("dx", _fp),
+        ("dw1", _fp * MOE_MAX_EXPERTS), ("dw2", _fp * MOE_MAX_EXPERTS), ("workspace", _fp),
+    ]
+
+
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),
@@ -184,6 +198,11 @@ SYMBOLS = {
     "mopk_token_gate_workspace_bytes": (C.c_size_t, [C.POINTER(TokenGateArgs)]),
     "mopk_token_gate_fwd": (C.c_int, [C.POINTER(TokenGateArgs), C.c_void_p]),
     "mopk_token_gate_bwd": (C.c_int, [C.POINTER(TokenGateArgs), C.c_void_p]),
+    "mopk_moe_supported": (C.c_int, [C.POINTER(MoeArgs)]),
+    "mopk_moe_workspace_bytes": (C.c_size_t, [C.POINTER(MoeArgs), C.c_int]),
+    "mopk_moe_route": (C.c_int, [C.POINTER(MoeArgs), C.c_void_p]),
+    "mopk_moe_fwd": (C.c_int, [C.POINTER(MoeArgs), C.c_void_p]),
+    "mopk_moe_bwd": (C.c_int, [C.POINTER(MoeArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 """ViT building blocks with the reference's parameter names (mop/models/components.py).
 
-Only `MSA` touches libmopk (plain SDPA core, reference components.py:56-66); the rest are stock
-PyTorch-ROCm layers kept so that `ViT_MoP` state_dicts load unchanged.
+`MSA` (plain SDPA core, reference components.py:56-66) and `MoEMLP` (routed grouped GEMMs, :84-121) run on libmopk; the rest
+are stock PyTorch-ROCm layers kept so that `ViT_MoP` state_dicts load unchanged.
 """
 from __future__ import annotations
 
@@ -84,6 +84,27 @@ class MLP(nn.Module):
         return residual + self.drop(self.fc2(hid))
 
 
+class MoEMLP(nn.Module):
+    """Top-1 mixture-of-experts MLP (reference components.py:84-121): E experts fc1.{e} / fc2.{e} (bias-free) and a gate Linear with
+    bias.  The reference computes every expert on every token and keeps the argmax one through a constant one-hot; ops.moe_mlp runs
+    the routed expert only (HIP), with the same output, no gradient for the gate and exact zeros for experts without tokens."""
+
+    def __init__(self, dim: int, mlp_ratio: float = 4.0, num_experts: int = 4):
+        super().__init__()
+        assert num_experts >= 2, "MoE requires at least 2 experts"
+        hidden = int(dim * mlp_ratio)
+        self.num_experts = int(num_experts)
+        self.fc1 = nn.ModuleList([nn.Linear(dim, hidden, bias=False) for _ in range(self.num_experts)])
+        self.fc2 = nn.ModuleList([nn.Linear(hidden, dim, bias=False) for _ in range(self.num_experts)])
+        self.act = nn.GELU(approximate="tanh")
+        self.gate = nn.Linear(dim, self.num_experts, bias=True)
+
+    def forward(self, x, residual=None):
+        """`residual` (default None = reference behaviour): returns `residual + moe(x)`, the add folded into fc2's epilogue"""
+        return ops.moe_mlp(x, self.gate.weight, self.gate.bias, [m.weight for m in self.fc1], [m.weight for m in self.fc2],
+                           residual)
+
+
 class Block(nn.Module):
     def __init__(self, dim, heads, mlp_ratio=4.0, drop=0.0, attn_drop=0.0, drop_path=0.0):
         super().__init__()
@@ -107,6 +128,20 @@ class Block(nn.Module):
         return self.mlp(h, residual=xr)
 
 
+class BlockMoE(Block):
+    """Block with the MoE MLP (reference components.py:144-168): same parameters and forward as Block, `mlp` is a MoEMLP"""
+
+    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, drop: float = 0.0, attn_drop: float = 0.0,
+                 drop_path: float = 0.0, num_experts: int = 4):
+        nn.Module.__init__(self)
+        self.ln1 = nn.LayerNorm(dim)
+        self.attn = MSA(dim, heads, attn_drop, drop)
+        self.dp1 = DropPath(drop_path)
+        self.ln2 = nn.LayerNorm(dim)
+        self.mlp = MoEMLP(dim, mlp_ratio, num_experts)
+        self.dp2 = DropPath(drop_path)
+
+
 class ViTEncoder(nn.Module):
     def __init__(self, dim=256, depth=6, heads=4, mlp_ratio=4.0, drop=0.0, drop_path=0.1, patch=4, num_tokens=64):
         super().__init__()
@@ -123,6 +158,21 @@ class ViTEncoder(nn.Module):
         for blk in self.blocks:
             tok = blk(tok)
         return self.ln_f(tok), grid
+
+
+class ViTEncoderMoE(ViTEncoder):
+    """ViTEncoder with BlockMoE blocks (reference components.py:208-252)"""
+
+    def __init__(self, dim=256, depth=6, heads=4, mlp_ratio=4.0, drop=0.0, drop_path=0.1, patch=4, num_tokens=64,
+                 num_experts: int = 4):
+        nn.Module.__init__(self)
+        self.patch = PatchEmbed(dim=dim, patch=patch)
+        self.pos = nn.Parameter(torch.zeros(1, num_tokens, dim))
+        rates = torch.linspace(0, drop_path, depth).tolist()
+        self.blocks = nn.ModuleList(BlockMoE(dim, heads, mlp_ratio, drop, 0.0, rates[i], num_experts=num_experts)
+                                    for i in range(depth))
+        self.ln_f = nn.LayerNorm(dim)
+        nn.init.normal_(self.pos, mean=0.0, std=0.02)
 
 
 class ViewsLinear(nn.Module):

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .components import FuseExcInh, Kernels3, ViewsLinear, ViTEncoder
+from .components import FuseExcInh, Kernels3, ViewsLinear, ViTEncoder, ViTEncoderMoE
 
 
 class ViT_MoP(nn.Module):
@@ -16,10 +16,13 @@ class ViT_MoP(nn.Module):
                  drop_path=0.1, patch=4, img_size=32, use_moe: bool = False, moe_experts: int = 4):
         super().__init__()
         assert dim % heads == 0, f"dim {dim} not divisible by heads {heads}"
-        if use_moe:
-            raise NotImplementedError("ViT_MoP(use_moe=True): the dense-MoE MLP is outside the hot path (SURVEY.md section 2 row 4)")
-        self.enc = ViTEncoder(dim=dim, depth=depth, heads=heads, mlp_ratio=mlp_ratio, drop_path=drop_path,
-                              patch=patch, num_tokens=(img_size // patch) ** 2)
+        num_tokens = (img_size // patch) ** 2
+        if use_moe:      # routed top-1 MoE MLP in every block (mopk_moe_*)
+            self.enc = ViTEncoderMoE(dim=dim, depth=depth, heads=heads, mlp_ratio=mlp_ratio, drop_path=drop_path, patch=patch,
+                                     num_tokens=num_tokens, num_experts=int(moe_experts))
+        else:
+            self.enc = ViTEncoder(dim=dim, depth=depth, heads=heads, mlp_ratio=mlp_ratio, drop_path=drop_path,
+                                  patch=patch, num_tokens=num_tokens)
         self.views = ViewsLinear(dim, n_views=n_views)
         self.kerns = Kernels3(in_ch=n_views, n_kernels=n_kernels)
         self.fuse = FuseExcInh(in_ch=n_views + n_kernels)

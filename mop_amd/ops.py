@@ -1347,3 +1347,169 @@ def token_gate_1d(x: torch.Tensor, a: Optional[torch.Tensor], u: torch.Tensor) -
         LAST_PATH["token_gate_fwd"] = L.PATH_GENERIC
         return token_gate_1d_torch(x, a, u)
     return _TokenGateFn.apply(x, a, u)
+
+
+# ---- top-1 routed MoE MLP (mopk_moe_*; reference mop/models/components.py:84-121 MoEMLP) ----
+def moe_mlp_torch(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.Tensor], w1s, w2s,
+                  residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the reference's dense composition in torch ops: every expert on every token, combined through a constant one-hot of the
+    gate's argmax (so the gate receives no gradient and an expert without tokens gets exact zeros)"""
+    D = x.shape[-1]
+    xf = x.reshape(-1, D)
+    logits = F.linear(xf, gate_w, gate_b)
+    top = logits.argmax(dim=-1)
+    one_hot = torch.zeros_like(logits).scatter_(1, top.unsqueeze(-1), 1.0)
+    y = torch.zeros_like(xf)
+    for e in range(len(w1s)):
+        y = y + one_hot[:, e].unsqueeze(-1) * F.linear(F.gelu(F.linear(xf, w1s[e]), approximate="tanh"), w2s[e])
+    y = y.reshape(x.shape)
+    return y if residual is None else residual + y
+
+
+def _moe_dtypes(x: torch.Tensor, w: torch.Tensor):
+    """(output dtype, precision) of a kernel call, or None when the kernels do not take the dtypes: under autocast the expert GEMMs
+    give the autocast dtype (as nn.Linear does) in bf16 arithmetic; otherwise x and the weights share a dtype"""
+    if torch.is_autocast_enabled():
+        if torch.get_autocast_dtype("cuda") != torch.bfloat16:
+            return None
+        return torch.bfloat16, L.PREC_BF16
+    if x.dtype != w.dtype:
+        return None
+    return x.dtype, _prec_for(x.dtype)
+
+
+def _moe_args(x2: Optional[torch.Tensor], gate_w, gate_b, w1s, w2s, odt: torch.dtype, prec: int, M: int = 0) -> L.MoeArgs:
+    """the call's MopkMoeArgs; x2 = None (support query): M rows of w1s' width, x not set"""
+    M, D = x2.shape if x2 is not None else (M, w1s[0].shape[1])
+    a = L.MoeArgs()
+    a.M, a.D, a.F, a.E = M, D, w1s[0].shape[0], len(w1s)
+    a.precision = prec
+    a.x_dtype = _io_dtype(x2 if x2 is not None else w1s[0])
+    a.w_dtype, a.gate_dtype = _io_dtype(w1s[0]), _io_dtype(gate_w)
+    a.o_dtype = L.MOPK_F32 if odt == torch.float32 else L.MOPK_BF16
+    a.x, a.gate_w, a.gate_b = _ptr(x2), gate_w.data_ptr(), _ptr(gate_b)
+    for e in range(len(w1s)):
+        a.w1[e], a.w2[e] = w1s[e].data_ptr(), w2s[e].data_ptr()
+    return a
+
+
+def moe_supported(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.Tensor], w1s, w2s) -> bool:
+    """True if mopk_moe_* take this call: GPU fp32 / bf16 tensors (bf16 autocast included), contiguous parameters of one dtype,
+    D and F multiples of 8, 2 <= E <= 64 (the library's own query decides shape, precision and alignment)"""
+    E = len(w1s)
+    ts = [x, gate_w] + list(w1s) + list(w2s) + ([] if gate_b is None else [gate_b])
+    if E < 2 or E > L.MOE_MAX_EXPERTS or x.numel() == 0:
+        return False
+    if any(not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16) for t in ts):
+        return False
+    if any(not w.is_contiguous() or w.dtype != w1s[0].dtype for w in list(w1s) + list(w2s)):
+        return False
+    if not gate_w.is_contiguous() or (gate_b is not None and (gate_b.dtype != gate_w.dtype or not gate_b.is_contiguous())):
+        return False
+    dt = _moe_dtypes(x, w1s[0])
+    if dt is None:
+        return False
+    D = x.shape[-1]
+    F_ = w1s[0].shape[0]
+    if any(w.shape != (F_, D) for w in w1s) or any(w.shape != (D, F_) for w in w2s) or gate_w.shape != (E, D):
+        return False
+    a = _moe_args(None, gate_w, gate_b, w1s, w2s, *dt, M=x.numel() // D)
+    a.x_dtype = _io_dtype(x)
+    return bool(L.lib().mopk_moe_supported(C.byref(a)))
+
+
+def _moe_route_buf(M: int, E: int, dev) -> torch.Tensor:
+    return torch.empty(2 * M + E + 1, dtype=torch.int32, device=dev)
+
+
+class _MoeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, gate_w, gate_b, n_exp, *ws):
+        w1s, w2s = ws[:n_exp], ws[n_exp:]
+        D = x.shape[-1]
+        x2 = x.detach().reshape(-1, D).contiguous()
+        odt, prec = _moe_dtypes(x, w1s[0])
+        a = _moe_args(x2, gate_w.detach(), None if gate_b is None else gate_b.detach(), w1s, w2s, odt, prec)
+        M, F_ = a.M, a.F
+        adt = torch.bfloat16 if prec == L.PREC_BF16 else torch.float32
+        y = torch.empty(M, D, dtype=odt, device=x.device)
+        u = torch.empty(M, F_, dtype=adt, device=x.device)
+        h = torch.empty_like(u)
+        route = _moe_route_buf(M, n_exp, x.device)
+        res = None
+        if residual is not None:
+            res = residual.detach().reshape(-1, D).contiguous()
+            a.residual = res.data_ptr()
+        a.y, a.u, a.h, a.route = y.data_ptr(), u.data_ptr(), h.data_ptr(), route.data_ptr()
+        LAST_PATH["moe_fwd"] = L.PATH_FUSED
+        with _timed("moe_fwd"):
+            rc = L.lib().mopk_moe_fwd(C.byref(a), _stream())
+        L.check(rc, "mopk_moe_fwd")
+        ctx.save_for_backward(x2, gate_w, gate_b, u, h, route, *ws)
+        ctx.meta = (n_exp, odt, prec, x.shape, x.dtype, residual is not None)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, gate_w, gate_b, u, h, route, *ws = ctx.saved_tensors
+        n_exp, odt, prec, xshape, xdt, has_res = ctx.meta
+        w1s, w2s = ws[:n_exp], ws[n_exp:]
+        D = x2.shape[1]
+        dyc = dy.reshape(-1, D).to(odt).contiguous()
+        a = _moe_args(x2, gate_w.detach(), None if gate_b is None else gate_b.detach(), w1s, w2s, odt, prec)
+        dx = torch.empty(x2.shape, dtype=xdt, device=x2.device)
+        dw1 = [torch.empty_like(w) for w in w1s]
+        dw2 = [torch.empty_like(w) for w in w2s]
+        a.u, a.h, a.route, a.dy, a.dx = u.data_ptr(), h.data_ptr(), route.data_ptr(), dyc.data_ptr(), dx.data_ptr()
+        for e in range(n_exp):
+            a.dw1[e], a.dw2[e] = dw1[e].data_ptr(), dw2[e].data_ptr()
+        ws_buf = _bytes(L.lib().mopk_moe_workspace_bytes(C.byref(a), 1), x2.device)
+        a.workspace = ws_buf.data_ptr()
+        LAST_PATH["moe_bwd"] = L.PATH_FUSED
+        with _timed("moe_bwd"):
+            rc = L.lib().mopk_moe_bwd(C.byref(a), _stream())
+        L.check(rc, "mopk_moe_bwd")
+        dres = dy if has_res else None
+        return (dx.view(xshape), dres, None, None, None, *dw1, *dw2)
+
+
+def moe_mlp(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.Tensor], w1s, w2s,
+            residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Top-1 MoE MLP ``[residual +] W2_e gelu_tanh(W1_e x)`` with ``e = argmax(gate(x))`` per token, the routed expert only (HIP:
+    route, grouped fc1 / fc2 GEMMs forward, four grouped GEMMs and a chunk-ordered sum backward; no host sync).  x (..., D);
+    gate_w (E, D), gate_b (E,) or None; w1s: E weights (F, D); w2s: E weights (D, F).  gate_w / gate_b get no gradient, as in the
+    reference (its one-hot is a constant).  Calls the kernels do not take (moe_supported: fp16, D or F not a multiple of 8, more
+    than 64 experts) run the reference's dense composition in torch; LAST_PATH["moe_fwd"] records which (PATH_FUSED / PATH_GENERIC)."""
+    _require_gpu(x, "moe_mlp")
+    w1s, w2s = list(w1s), list(w2s)
+    if not moe_supported(x, gate_w, gate_b, w1s, w2s):
+        LAST_PATH["moe_fwd"] = LAST_PATH["moe_bwd"] = L.PATH_GENERIC
+        return moe_mlp_torch(x, gate_w, gate_b, w1s, w2s, residual)
+    odt, _ = _moe_dtypes(x, w1s[0])
+    fold = residual is not None and residual.dtype == odt and residual.shape == x.shape
+    y = _MoeFn.apply(x, residual if fold else None, gate_w, gate_b, len(w1s), *w1s, *w2s)
+    if residual is not None and not fold:
+        y = residual + y
+    return y
+
+
+def moe_route(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 expert index per token (x (..., D) -> (M,)): the kernels' fp32-logit argmax (mopk_moe_route), or the same formula in
+    fp32 torch for calls the kernels do not take"""
+    _require_gpu(x, "moe_route")
+    D, E = x.shape[-1], gate_w.shape[0]
+    x2 = x.detach().reshape(-1, D).contiguous()
+    ok = (2 <= E <= L.MOE_MAX_EXPERTS and x2.shape[0] > 0 and D % 8 == 0 and x2.dtype in (torch.float32, torch.bfloat16)
+          and gate_w.dtype in (torch.float32, torch.bfloat16) and (gate_b is None or gate_b.dtype == gate_w.dtype))
+    if not ok:
+        return F.linear(x2.float(), gate_w.float(), None if gate_b is None else gate_b.float()).argmax(-1).to(torch.int32)
+    gw = gate_w.detach().contiguous()
+    gb = None if gate_b is None else gate_b.detach().contiguous()
+    a = L.MoeArgs()
+    a.M, a.D, a.F, a.E, a.precision = x2.shape[0], D, 8, E, L.PREC_BF16
+    a.x_dtype = a.w_dtype = a.o_dtype = _io_dtype(x2)
+    a.gate_dtype = _io_dtype(gw)
+    route = _moe_route_buf(a.M, E, x.device)
+    a.x, a.gate_w, a.gate_b, a.route = x2.data_ptr(), gw.data_ptr(), _ptr(gb), route.data_ptr()
+    L.check(L.lib().mopk_moe_route(C.byref(a), _stream()), "mopk_moe_route")
+    return route[:a.M]

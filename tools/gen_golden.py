@@ -541,9 +541,181 @@ def whisper_decoder_cases():
         _save(name, out, compress=True)
 
 
+def moe_cases():
+    """Top-1 MoE MLP (components.py:84-121), BlockMoE (:144-168) and ViT_MoP(use_moe=True) (vit_mop.py:53-75).  Names start with
+    `moe_` / `moevit_` only.  A token whose top two gate logits nearly tie is routed by summation order, so each case redraws the gate
+    perturbation seed until every token of every MoE layer clears a margin (top1 - top2 logit, in units of that layer's logit standard
+    deviation): >= 0.03 in the fp32 run and in the reference's own bf16 run, with identical routes, for the cases also checked in bf16;
+    >= 1e-3 for fp32-only ones.  Stored: route:<module> (the fp32 run's argmax per token), gradnone:<param> (grad is None in the
+    reference: the gate), meta:min_margin and the reference's bf16 self-error."""
+    import copy
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from vit_fixture import fill_params, grad_sample
+    from mop.models.components import BlockMoE, MoEMLP
+    from mop.models.vit_mop import ViT_MoP
+
+    def watch(mod):
+        """forward hooks on every MoEMLP: route and normalised margin of the last run, keyed by module name"""
+        rec = {}
+        for n, m in mod.named_modules():
+            if isinstance(m, MoEMLP):
+                def hook(m_, inp, out, n=n):
+                    lg = m_.gate(inp[0].reshape(-1, inp[0].shape[-1])).detach().double()
+                    top = lg.topk(2, dim=-1).values
+                    rec[n] = (lg.argmax(-1).numpy().astype(np.int32), float(((top[:, 0] - top[:, 1]) / lg.std()).min()))
+                m.register_forward_hook(hook)
+        return rec
+
+    def perturb_gates(mod, seed, bias_fn=None):
+        g = torch.Generator().manual_seed(seed)
+        with torch.no_grad():
+            for n, m in mod.named_modules():
+                if isinstance(m, MoEMLP):
+                    m.gate.weight.add_(0.5 * m.gate.weight.abs().mean() * torch.randn(m.gate.weight.shape, generator=g))
+                    if bias_fn is not None:
+                        bias_fn(m)
+
+    def routes_ok(mod, x, bf16, margin):
+        rec = watch(mod)
+        with torch.no_grad():
+            mod(x)
+        r32 = dict(rec)
+        mins = [v[1] for v in r32.values()]
+        if bf16:
+            mb = copy.deepcopy(mod).to(torch.bfloat16)
+            rec.clear()
+            with torch.no_grad():
+                mb(x.to(torch.bfloat16))
+            mins += [v[1] for v in rec.values()]
+            if any(not np.array_equal(rec[k][0], r32[k][0]) for k in r32):
+                return None
+        for m in mod.modules():          # drop the hooks again
+            m._forward_hooks.clear()
+        return (r32, min(mins)) if min(mins) >= margin else None
+
+    def search(build, x, bf16, margin, seed0):
+        for s in range(50):
+            mod = build(seed0 + s)
+            got = routes_ok(mod, x, bf16, margin)
+            if got is not None:
+                print(f"  seed draws: {s + 1}, min margin {got[1]:.4f}")
+                return mod, got[0], got[1], seed0 + s
+        raise RuntimeError("no gate seed within 50 draws: shrink B")
+
+    def finish(out, mod, routes, margin, kind, **meta):
+        for k, (r, _) in routes.items():
+            out["route:" + k] = r
+        for k, p in mod.named_parameters():
+            if p.grad is None:
+                out["gradnone:" + k] = np.int32(1)
+        meta = dict(kind=kind, n_params=sum(p.numel() for p in mod.parameters()), min_margin=margin, **meta)
+        out.update({"meta:" + k: np.asarray(v) for k, v in meta.items()})
+
+    def fill(m, pseed):
+        """expert weights from the numpy stream of tests/vit_fixture.py (regenerated by the test from meta:param_seed, not stored)"""
+        shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+        vals = fill_params(shapes, pseed)
+        m.load_state_dict({k: torch.from_numpy(np.asarray(v)).reshape(shapes[k]) for k, v in vals.items()}, strict=True)
+
+    def slim(out):
+        """keep the gate's parameters (perturbed after the fill) and drop the rest: the test regenerates them"""
+        for k in [k for k in out if k.startswith("param:") and ".gate." not in k and not k.startswith("param:gate.")]:
+            out["shape:" + k[6:]] = np.asarray(out[k].shape, dtype=np.int64)
+            del out[k]
+        return out
+
+    def skew(m):                       # the bias of expert 0 is set in build(); here the other two are zeroed
+        m.gate.bias.zero_()
+    mlp_cases = [("moe_d64_e4", 64, 4, 2, 16, None), ("moe_d72_e3", 72, 3, 2, 12, None), ("moe_skew_d64_e4", 64, 4, 2, 16, skew)]
+    for i, (name, D, E, B, N, bias_fn) in enumerate(mlp_cases):
+        g = torch.Generator().manual_seed(2100 + i)
+        x = torch.randn(B, N, D, generator=g)
+
+        def build(seed, D=D, E=E, bias_fn=bias_fn, x=x, i=i):
+            torch.manual_seed(seed)
+            m = MoEMLP(D, 4.0, E).eval()
+            fill(m, 2100 + i)
+            perturb_gates(m, seed, bias_fn)
+            if bias_fn is skew:        # then lift expert 0 until it takes ~80 % of the tokens
+                with torch.no_grad():
+                    lg = m.gate(x.reshape(-1, D))
+                    gs = (lg[:, 1:-1].max(-1).values - lg[:, 0]).sort().values
+                    lo, hi = int(0.75 * len(gs)), int(0.85 * len(gs))           # widest gap between sorted values near 80 %
+                    k = max(range(lo, hi), key=lambda j: float(gs[j + 1] - gs[j]))
+                    m.gate.bias[0] = 0.5 * float(gs[k] + gs[k + 1])
+                    lg = m.gate(x.reshape(-1, D))                                # the last expert: one std below every winner
+                    m.gate.bias[-1] -= float((lg[:, -1] - lg[:, :-1].max(-1).values).max()) + float(lg.std())
+            return m
+        mod, routes, mg, seed = search(build, x, True, 0.03, 2200 + 100 * i)
+        out = slim(_run(mod, x, bf16_self=True))
+        finish(out, mod, routes, mg, "moe_mlp", dim=D, mlp_ratio=4.0, num_experts=E, gate_seed=seed, param_seed=2100 + i)
+        _save(name, out)
+        counts = np.bincount(routes[""][0], minlength=E)
+        print(f"  tokens per expert {counts.tolist()}")
+
+    # BlockMoE
+    g = torch.Generator().manual_seed(2150)
+    x = torch.randn(1, 24, 64, generator=g)
+
+    def build_blk(seed):
+        torch.manual_seed(seed)
+        m = BlockMoE(64, 4, 4.0, num_experts=4).eval()
+        fill(m, 2150)
+        perturb_gates(m, seed)
+        return m
+    mod, routes, mg, seed = search(build_blk, x, True, 0.03, 2500)
+    out = slim(_run(mod, x, bf16_self=True))
+    finish(out, mod, routes, mg, "block_moe", dim=64, heads=4, mlp_ratio=4.0, num_experts=4, gate_seed=seed, param_seed=2150)
+    _save("moe_block_d64_e4", out)
+
+    # ViT_MoP(use_moe=True): parameters from tests/vit_fixture.py, then the gate perturbation (gate tensors stored as param:)
+    cases = [("moevit_tiny_e3", dict(dim=64, depth=2, heads=4, n_classes=10, n_views=3, n_kernels=2, drop_path=0.0, use_moe=True,
+                                    moe_experts=3), 1, 910, True, 0.03),
+             ("moevit_cfg0_e4", dict(dim=384, depth=3, heads=6, n_classes=100, n_views=5, n_kernels=3, drop_path=0.0, use_moe=True,
+                                    moe_experts=4), 2, 911, False, 1e-3)]
+    for name, kw, B, pseed, bf16, margin in cases:
+        x = torch.randn(B, 3, 32, 32, generator=torch.Generator().manual_seed(pseed))
+
+        def build_vit(seed, kw=kw, pseed=pseed):
+            torch.manual_seed(pseed)
+            m = ViT_MoP(**kw).eval()
+            shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+            vals = fill_params(shapes, pseed)
+            m.load_state_dict({k: torch.from_numpy(np.asarray(v)).reshape(shapes[k]) for k, v in vals.items()}, strict=True)
+            perturb_gates(m, seed)
+            return m
+        mod, routes, mg, seed = search(build_vit, x, bf16, margin, 3000 + pseed)
+        shapes = {k: tuple(v.shape) for k, v in mod.state_dict().items()}
+        xg = x.clone().requires_grad_(True)
+        y = mod(xg)
+        w = torch.randn(y.shape, generator=torch.Generator().manual_seed(4242))
+        (y * w).sum().backward()
+        out = {"x": x.numpy(), "y": y.detach().numpy(), "w": w.numpy(), "dx": xg.grad.numpy()}
+        for k, p in mod.named_parameters():
+            if ".gate." in k:
+                out["param:" + k] = p.detach().numpy()
+            if p.grad is not None:
+                out["gsample:" + k], out["gnorm:" + k] = grad_sample(p.grad.numpy())
+        for k, v in shapes.items():
+            out["shape:" + k] = np.asarray(v, dtype=np.int64)
+        if bf16:
+            mb = copy.deepcopy(mod).to(torch.bfloat16)
+            xb = x.to(torch.bfloat16).requires_grad_(True)
+            yb = mb(xb)
+            (yb * w.to(torch.bfloat16)).sum().backward()
+            out["bf16err:y"] = np.float32(np.abs(yb.detach().float().numpy() - out["y"]).max())
+            out["bf16err:dx"] = np.float32(np.abs(xb.grad.float().numpy() - out["dx"]).max() / np.abs(out["dx"]).max())
+            for k, p in mb.named_parameters():
+                if p.grad is not None:
+                    ref = dict(mod.named_parameters())[k].grad.numpy()
+                    out["bf16err:" + k] = np.float32(np.abs(p.grad.float().numpy() - ref).max() / max(np.abs(ref).max(), 1e-30))
+        finish(out, mod, routes, mg, "vit_mop_moe", param_seed=pseed, gate_seed=seed, **kw)
+        _save(name, out)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     groups = dict(train=train_cases, vit=vit_cases, ew=edgewise_cases, ewx=edgewise_variant_cases, cv=crossview_cases, wh=whisper_cases, mh=multihop_cases, qt=quartet_cases, sdpa=sdpa_cases,
-                  gpt=gpt_cases, whdec=whisper_decoder_cases)
+                  gpt=gpt_cases, whdec=whisper_decoder_cases, moe=moe_cases)
     for name in (sys.argv[1:] or list(groups)):               # e.g. `gen_golden.py ewx` regenerates one group only
         groups[name]()
