@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPK_VERSION 118 /* 118: mopk_moe_* and MopkMoeArgs (added later without a bump: new exports only, detect with mopk_moe_supported), MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
+#define MOPK_VERSION 118 /* 118: mopk_decode_attn_* and MopkDecodeAttnArgs (added later without a bump: new exports only, detect with mopk_decode_attn_supported), mopk_moe_* and MopkMoeArgs (added later without a bump: new exports only, detect with mopk_moe_supported), MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
 
 typedef enum MopkStatus {
     MOPK_OK = 0,
@@ -452,6 +452,35 @@ size_t mopk_moe_workspace_bytes(const MopkMoeArgs *a, int backward); /* 0 for th
 int mopk_moe_route(const MopkMoeArgs *a, void *stream);
 int mopk_moe_fwd(const MopkMoeArgs *a, void *stream);
 int mopk_moe_bwd(const MopkMoeArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
+ * Attention of a few new queries against a key / value cache: incremental (KV-cached) decoding of the WhisperMoP decoder
+ * (mop/models/whisper_mop.py:137-221 attention cores, one step at a time).  Inference only, no backward.  (Added under version 118:
+ * new exports only, no existing layout changes; callers detect it with mopk_decode_attn_supported.)
+ *   y_i = softmax_j(q_i . k_j / sqrt(dk)) v_j  over the keys j < L (and j < L - Tq + i + 1 with causal)
+ * L = *kv_len when kv_len != NULL (device memory, read by the kernels: the caller sets it to the length after this step's append, so
+ * the launch arguments do not change from step to step and a step can be captured once in a graph), else L = Nk.  L is clamped to
+ * [0, cap].  causal is BOTTOM-RIGHT aligned: the Tq queries are the last Tq positions of the L keys, query i (0-based) sees keys
+ * j < L - Tq + i + 1.  A query that sees no key gets y = 0.
+ * q, y: (B, Tq, H, dk) views; k, v: (B, cap, H, dk) views of a cache buffer (only the first L rows are read).  1 <= Tq <= 16,
+ * dk in {32, 64, 128}, 0 <= Nk <= cap (Nk >= 1 without kv_len).  k / v: 16-byte aligned pointers and strides that are whole 16-byte
+ * vectors; q / y: any element strides.  F32: exact fp32 arithmetic; BF16: bf16 io, fp32 arithmetic.
+ * Split-KV: one workgroup per (b, h, chunk of 64 or 128 keys), chunk count fixed by cap; a second launch merges the per-chunk
+ * partials in chunk order.  No atomics: bitwise reproducible.  workspace: mopk_decode_attn_workspace_bytes(). */
+typedef struct MopkDecodeAttnArgs {
+    int32_t B, H, Tq, dk;                /* batch, heads, new queries per row, head size */
+    int32_t cap;                         /* rows of the k / v cache views */
+    int32_t Nk;                          /* valid keys when kv_len is NULL */
+    int32_t io_dtype;                    /* MopkDtype of q, k, v and y */
+    int32_t causal;                      /* 0 / 1, bottom-right aligned (above) */
+    MopkView4 q, k, v;
+    MopkView4 y;                         /* out */
+    const int32_t *kv_len;               /* device: valid keys (one int32), or NULL for Nk */
+    void *workspace;
+} MopkDecodeAttnArgs;
+int mopk_decode_attn_supported(const MopkDecodeAttnArgs *a);         /* 1 if the kernels take this call (shape, dtype, strides, alignment) */
+size_t mopk_decode_attn_workspace_bytes(const MopkDecodeAttnArgs *a);
+int mopk_decode_attn_fwd(const MopkDecodeAttnArgs *a, void *stream);
 
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);

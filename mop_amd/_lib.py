@@ -156,6 +156,15 @@ class MoeArgs(C.Structure):
     ]
 
 
+class DecodeAttnArgs(C.Structure):
+    """MopkDecodeAttnArgs: a few new queries against a key / value cache (WhisperMoP incremental decoding)."""
+    _fields_ = [
+        ("B", C.c_int32), ("H", C.c_int32), ("Tq", C.c_int32), ("dk", C.c_int32), ("cap", C.c_int32), ("Nk", C.c_int32),
+        ("io_dtype", C.c_int32), ("causal", C.c_int32),
+        ("q", View4), ("k", View4), ("v", View4), ("y", View4), ("kv_len", _fp), ("workspace", _fp),
+    ]
+
+
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),
@@ -203,6 +212,9 @@ SYMBOLS = {
     "mopk_moe_route": (C.c_int, [C.POINTER(MoeArgs), C.c_void_p]),
     "mopk_moe_fwd": (C.c_int, [C.POINTER(MoeArgs), C.c_void_p]),
     "mopk_moe_bwd": (C.c_int, [C.POINTER(MoeArgs), C.c_void_p]),
+    "mopk_decode_attn_supported": (C.c_int, [C.POINTER(DecodeAttnArgs)]),
+    "mopk_decode_attn_workspace_bytes": (C.c_size_t, [C.POINTER(DecodeAttnArgs)]),
+    "mopk_decode_attn_fwd": (C.c_int, [C.POINTER(DecodeAttnArgs), C.c_void_p]),
 }
 
 _lib = None

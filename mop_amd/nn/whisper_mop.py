@@ -188,6 +188,23 @@ class DecoderBlock(nn.Module):
         return x
 
 
+class WhisperDecodeCache:
+    """Key / value cache of one incremental `WhisperMoP` decoding (`init_decode_cache`, `decode_step`, `generate`).
+
+    cross_k / cross_v: per decoder layer, the encoder output projected once to cross-attention keys / values (B, T_audio, H, dh).
+    self_k / self_v: per decoder layer, self-attention keys / values (B, max_len, H, dh), filled up to `length`.
+    length: the number of cached tokens as a (1,) int32 DEVICE tensor (the kernels read it, so a step's launch arguments do not
+    change from step to step); pos: its host mirror (the host drives the loop, so keeping it costs no sync)."""
+
+    def __init__(self, cross_k, cross_v, self_k, self_v, length: torch.Tensor, max_len: int):
+        self.cross_k, self.cross_v, self.self_k, self.self_v = cross_k, cross_v, self_k, self_v
+        self.length, self.pos, self.max_len = length, 0, int(max_len)
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return self.self_k[0].dtype
+
+
 class WhisperMoP(nn.Module):
     """Encoder-decoder with the MoP mel gate in every encoder block (reference :296-424).
     forward(mel, dec_input_ids, targets=None) -> (logits, loss, gates); lm_head is tied to wte."""
@@ -258,6 +275,114 @@ class WhisperMoP(nn.Module):
         if targets is not None:
             loss = F.cross_entropy(logits.view(-1, logits.size(-1)), targets.view(-1))
         return logits, loss, gates
+
+    # ---- incremental (KV-cached) greedy decoding; inference only, dropout off ----
+    @torch.no_grad()
+    def init_decode_cache(self, enc_out: torch.Tensor, max_len: int) -> WhisperDecodeCache:
+        """enc_out (B, T_audio, D) -> a cache for up to max_len text tokens: every decoder layer's cross-attention keys / values are
+        projected once here; self-attention buffers (B, max_len, H, dh) are allocated in the dtype the projections produce (bf16
+        under bf16 autocast)."""
+        if not 0 < int(max_len) <= self.cfg.n_text_ctx:
+            raise ValueError(f"init_decode_cache: max_len = {max_len} outside [1, n_text_ctx = {self.cfg.n_text_ctx}]")
+        B, T_a, _ = enc_out.shape
+        H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        ck = [blk.cross_attn.k_proj(enc_out).view(B, T_a, H, Dh) for blk in self.decoder]
+        cv = [blk.cross_attn.v_proj(enc_out).view(B, T_a, H, Dh) for blk in self.decoder]
+        kw = dict(dtype=ck[0].dtype, device=enc_out.device)
+        sk = [torch.zeros(B, int(max_len), H, Dh, **kw) for _ in self.decoder]
+        sv = [torch.zeros(B, int(max_len), H, Dh, **kw) for _ in self.decoder]
+        return WhisperDecodeCache(ck, cv, sk, sv, torch.zeros(1, dtype=torch.int32, device=enc_out.device), max_len)
+
+    @torch.no_grad()
+    def decode_step(self, cache: WhisperDecodeCache, ids: torch.Tensor) -> torch.Tensor:
+        """append ids (B, T_new) at positions [len, len + T_new) and run the decoder on them only -> logits (B, T_new, vocab).
+
+        Equals decode(enc_out, all ids so far)[:, -T_new:] in eval().  Attention runs on ops.decode_attention (the split-KV kernels)
+        with the device length; a first chunk of more than 16 tokens runs the square causal ops.sdpa_core and writes its keys /
+        values into the cache.  Positions, the append and the length update are device-indexed: no host sync, graph-capturable."""
+        B, T = ids.shape
+        if cache.pos + T > cache.max_len:
+            raise ValueError(f"decode_step: {cache.pos} cached + {T} new tokens exceed the cache's max_len = {cache.max_len}")
+        H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        idx = cache.length.to(torch.long) + torch.arange(T, device=ids.device)        # positions of the new tokens
+        x = self.wte(ids)
+        if self.text_pos is not None:
+            x = x + self.text_pos(idx).unsqueeze(0)
+        new_len = cache.length + T
+        long_chunk = T > ops.DECODE_MAX_TQ
+        prefill = long_chunk and cache.pos == 0
+        for l, blk in enumerate(self.decoder):
+            sa, ca = blk.self_attn, blk.cross_attn
+            h = blk.ln1(x)
+            q, k, v = (p(h).view(B, T, H, Dh) for p in (sa.q_proj, sa.k_proj, sa.v_proj))
+            cache.self_k[l].index_copy_(1, idx, k.to(cache.dtype))
+            cache.self_v[l].index_copy_(1, idx, v.to(cache.dtype))
+            if prefill:
+                y = ops.sdpa_core(q, k, v, causal=True)
+            else:
+                y = ops.decode_attention(q, cache.self_k[l], cache.self_v[l], kv_len=new_len, causal=True)
+            x = x + sa.o_proj(y)
+            q = ca.q_proj(blk.ln2(x)).view(B, T, H, Dh)
+            ck, cv = cache.cross_k[l], cache.cross_v[l]
+            if long_chunk:
+                y = ops.sdpa_core(q, ck, cv)
+            else:
+                y = ops.decode_attention(q, ck, cv, nk=ck.shape[1])
+            x = x + ca.o_proj(y)
+            x = x + blk.mlp.proj(F.gelu(blk.mlp.fc(blk.ln3(x)), approximate="tanh"))
+        cache.length.add_(T)
+        cache.pos += T
+        return self.lm_head(self.dec_ln_f(x))
+
+    @torch.no_grad()
+    def generate(self, mel: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
+                 graph: bool = False, *, return_logits: bool = False):
+        """greedy decoding: mel (B, T_audio, n_mels), prompt_ids (B, T_p) -> tokens (B, T_p + max_new_tokens), all on the device.
+
+        Rows that have emitted eos_token_id keep emitting it (torch.where: the loop never syncs the host).  graph=True runs the prompt
+        and the first single-token step eagerly, captures one single-token decode_step in a HIP graph (torch.cuda.graph, one stream,
+        static id / logit buffers) and replays it for every further token.  return_logits=True also returns the last-position logits
+        that chose each new token, (B, max_new_tokens, vocab)."""
+        B, T_p = prompt_ids.shape
+        if T_p < 1 or max_new_tokens < 1:
+            raise ValueError(f"generate: needs a prompt and at least one new token (T_p = {T_p}, max_new_tokens = {max_new_tokens})")
+        if T_p + max_new_tokens > self.cfg.n_text_ctx:
+            raise ValueError(f"generate: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        enc, _ = self.encode(mel)
+        cache = self.init_decode_cache(enc, T_p + max_new_tokens)
+        logits = self.decode_step(cache, prompt_ids)[:, -1]
+        done = torch.zeros(B, dtype=torch.bool, device=prompt_ids.device) if eos_token_id is not None else None
+        toks, steps = [], []
+        g = static_ids = static_logits = None
+        for t in range(max_new_tokens):
+            if return_logits:
+                steps.append(logits.clone())
+            nxt = logits.argmax(-1)
+            if done is not None:
+                nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)
+                done = done | (nxt == eos_token_id)
+            toks.append(nxt)
+            if t == max_new_tokens - 1:
+                break
+            ids = nxt.unsqueeze(1)
+            if not graph or t == 0:                  # the first single-token step runs eagerly (and warms every kernel up)
+                logits = self.decode_step(cache, ids)[:, -1]
+                continue
+            if g is None:
+                static_ids = ids.clone()
+                g = torch.cuda.CUDAGraph()
+                with torch.autocast(device_type="cuda", dtype=torch.get_autocast_dtype("cuda"),
+                                    enabled=torch.is_autocast_enabled("cuda"), cache_enabled=False):
+                    with torch.cuda.graph(g):
+                        static_logits = self.decode_step(cache, static_ids)[:, -1]
+                cache.pos -= 1                           # capture recorded the step without running it
+            else:
+                static_ids.copy_(ids)
+            g.replay()
+            cache.pos += 1
+            logits = static_logits
+        out = torch.cat([prompt_ids, torch.stack(toks, dim=1).to(prompt_ids.dtype)], dim=1)
+        return (out, torch.stack(steps, dim=1)) if return_logits else out
 
     @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):

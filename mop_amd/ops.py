@@ -1513,3 +1513,91 @@ def moe_route(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.Tens
     a.x, a.gate_w, a.gate_b, a.route = x2.data_ptr(), gw.data_ptr(), _ptr(gb), route.data_ptr()
     L.check(L.lib().mopk_moe_route(C.byref(a), _stream()), "mopk_moe_route")
     return route[:a.M]
+
+
+# ---- attention of a few new queries against a key / value cache (mopk_decode_attn_*; WhisperMoP incremental decoding) ----
+DECODE_MAX_TQ = 16
+
+
+def decode_attention_torch(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: Optional[torch.Tensor] = None,
+                           nk: Optional[int] = None, causal: bool = False) -> torch.Tensor:
+    """the reference composition of `decode_attention` in torch ops (fp32 arithmetic, float64 for float64 tensors); the valid length
+    stays on the device (a mask over the whole cache), so there is no host sync either"""
+    B, Tq, H, dk = q.shape
+    cap = k_cache.shape[1]
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    s = torch.einsum("bihd,bjhd->bhij", q.to(ct), k_cache.to(ct)) * dk ** -0.5
+    j = torch.arange(cap, device=q.device)
+    L = kv_len.reshape(()).to(torch.long).clamp(0, cap) if kv_len is not None else (cap if nk is None else int(nk))
+    i = torch.arange(Tq, device=q.device)
+    lim = L - Tq + i + 1 if causal else L + 0 * i                           # (Tq,): host ints never become device copies
+    ok = j.unsqueeze(0) < lim.unsqueeze(1)                                  # (Tq, cap)
+    s = s.masked_fill(~ok, float("-inf"))
+    p = torch.softmax(s, dim=-1).nan_to_num(0.0)                            # a query that sees no key gets y = 0, as the kernels
+    v = v_cache.to(ct).masked_fill(~(j < L).view(1, cap, 1, 1), 0.0)       # rows past L may hold anything
+    y = torch.einsum("bhij,bjhd->bihd", p, v)
+    return y.to(q.dtype).reshape(B, Tq, H * dk)
+
+
+def _da_args(q, k_cache, v_cache, kv_len, nk, causal) -> L.DecodeAttnArgs:
+    B, Tq, H, dk = q.shape
+    a = L.DecodeAttnArgs()
+    a.B, a.H, a.Tq, a.dk, a.cap = B, H, Tq, dk, k_cache.shape[1]
+    a.Nk = a.cap if (nk is None and kv_len is None) else (0 if nk is None else int(nk))
+    a.io_dtype, a.causal = _io_dtype(q), int(bool(causal))
+    a.q, a.k, a.v = _v4(q), _v4(k_cache), _v4(v_cache)
+    a.kv_len = _ptr(kv_len)
+    return a
+
+
+def decode_attention_supported(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: Optional[torch.Tensor] = None,
+                               nk: Optional[int] = None, causal: bool = False) -> bool:
+    """True if mopk_decode_attn_* take this call: GPU tensors of one dtype (fp32 / bf16), 1 <= Tq <= 16, dk in {32, 64, 128}, unit
+    inner strides, 16-byte aligned cache views, an int32 kv_len (the library's own query decides the rest)"""
+    ts = (q, k_cache, v_cache)
+    if any(not t.is_cuda or t.dtype != q.dtype or t.dtype not in (torch.float32, torch.bfloat16) or t.stride(-1) != 1 for t in ts):
+        return False
+    if kv_len is not None and (not kv_len.is_cuda or kv_len.dtype != torch.int32 or kv_len.numel() != 1):
+        return False
+    if q.numel() == 0 or k_cache.shape[1] == 0:
+        return False
+    return bool(L.lib().mopk_decode_attn_supported(C.byref(_da_args(q, k_cache, v_cache, kv_len, nk, causal))))
+
+
+def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: Optional[torch.Tensor] = None,
+                     nk: Optional[int] = None, causal: bool = False) -> torch.Tensor:
+    """softmax(q k^T / sqrt(dk) [causal]) v of Tq new queries against the first L keys of a cache; inference only (no autograd).
+
+    q: (B, Tq, H, dk); k_cache, v_cache: (B, cap, H, dk) views (a buffer larger than its fill is passed without a copy).
+    L = kv_len, a one-element int32 DEVICE tensor read by the kernels (set it to the length after this step's append: the call's
+    arguments then do not change from step to step and can be captured in a graph), else nk (host int), else cap.  causal is
+    bottom-right aligned: query i sees keys j < L - Tq + i + 1.  Returns (B, Tq, H * dk) in q's dtype.  Runs the split-KV HIP kernel
+    pair when decode_attention_supported() accepts the call, else decode_attention_torch(); LAST_PATH["decode_attn"] records which
+    (PATH_FUSED / PATH_GENERIC).  No host synchronisation."""
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError(f"decode_attention: q must be (B, Tq, H, dk) and k_cache, v_cache (B, cap, H, dk) of one shape; got q "
+                         f"{tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)}")
+    if k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
+        raise ValueError(f"decode_attention: k_cache / v_cache {tuple(k_cache.shape)} do not match q's B, H, dk {tuple(q.shape)}")
+    if kv_len is not None and nk is not None:
+        raise ValueError("decode_attention: pass kv_len (device) or nk (host), not both")
+    if nk is not None and not 0 < int(nk) <= k_cache.shape[1]:
+        raise ValueError(f"decode_attention: nk = {nk} outside [1, cap = {k_cache.shape[1]}]")
+    if kv_len is not None and kv_len.numel() != 1:
+        raise ValueError(f"decode_attention: kv_len must hold one element, got shape {tuple(kv_len.shape)}")
+    _require_gpu(q, "decode_attention")
+    with torch.no_grad():
+        if not decode_attention_supported(q, k_cache, v_cache, kv_len, nk, causal):
+            LAST_PATH["decode_attn"] = L.PATH_GENERIC
+            return decode_attention_torch(q, k_cache, v_cache, kv_len, nk, causal)
+        lib = L.lib()
+        B, Tq, H, dk = q.shape
+        a = _da_args(q, k_cache, v_cache, kv_len, nk, causal)
+        y = torch.empty(B, Tq, H, dk, dtype=q.dtype, device=q.device)
+        ws = _bytes(lib.mopk_decode_attn_workspace_bytes(C.byref(a)), q.device)
+        a.y, a.workspace = _v4(y), ws.data_ptr()
+        LAST_PATH["decode_attn"] = L.PATH_FUSED
+        with _timed("decode_attn"):
+            rc = lib.mopk_decode_attn_fwd(C.byref(a), _stream())
+        L.check(rc, "mopk_decode_attn_fwd")
+        return y.view(B, Tq, H * dk)

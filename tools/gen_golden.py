@@ -713,9 +713,68 @@ def moe_cases():
         _save(name, out)
 
 
+def whisper_generate_cases():
+    """Greedy decoding of WhisperMoP (whisper_mop.py:296-424), for the KV-cached `generate`.  whgen_*: a 2 + 2 layer model; the
+    tokens come from calling the reference's `decode` on the whole growing prefix for every new token (float32, CPU).  The seed is
+    re-drawn until the top-1 / top-2 gap of every step's last-position logits clears `min_margin`, so tokens compare exactly.
+    The default init is de-degenerated: at std 0.02 the residual stream is the token's own embedding and a random model repeats its
+    last token, with logits too close for any margin.  So every decoder Linear is redrawn with std 0.3 (attention and MLP dominate
+    the stream), and dec_ln_f's weight is 20 + N(0, 1) (logit gaps of order 1).  Stores params, mel, prompt, tokens (prompt
+    included) and the per-step last-position logits."""
+    from mop.models.whisper_mop import WhisperMoP
+    vocab, n_mels, dim, margin = 32, 10, 32, 1e-3
+    cases = [
+        # name, B, T_a, T_p, n_new, use_abs_pos_emb
+        ("whgen_p1", 2, 150, 1, 24, True),
+        ("whgen_p4_nopos", 2, 70, 4, 24, False),
+        ("whgen_p4_t140", 2, 150, 4, 136, True),
+    ]
+    for i, (name, B, Ta, Tp, n_new, pos) in enumerate(cases):
+        for attempt in range(200):
+            seed = 1800 + 100 * i + attempt
+            torch.manual_seed(seed)
+            cfg = WhisperConfig(n_mels=n_mels, n_audio_ctx=Ta, vocab_size=vocab, n_text_ctx=Tp + n_new, n_embd=dim, n_head=1,
+                                n_layer_enc=2, n_layer_dec=2, dropout=0.0, bias=False, use_abs_pos_emb=pos, n_views=3, n_kernels=2,
+                                kernel_size=3)
+            mod = WhisperMoP(cfg).eval()
+            with torch.no_grad():
+                for blk in mod.decoder:
+                    for m_ in blk.modules():
+                        if isinstance(m_, torch.nn.Linear):
+                            m_.weight.normal_(0.0, 0.3)
+                mod.dec_ln_f.weight.copy_(20.0 + torch.randn(dim))
+            g = torch.Generator().manual_seed(seed)
+            mel = torch.randn(B, Ta, n_mels, generator=g)
+            ids = torch.randint(0, vocab, (B, Tp), generator=g)
+            with torch.no_grad():
+                enc, _ = mod.encode(mel)
+                steps = []
+                for _ in range(n_new):
+                    lg = mod.decode(enc, ids)[:, -1]
+                    steps.append(lg)
+                    ids = torch.cat([ids, lg.argmax(-1, keepdim=True)], dim=1)
+            lg = torch.stack(steps, dim=1)
+            top = lg.topk(2, dim=-1).values
+            mg = float((top[..., 0] - top[..., 1]).min())
+            if mg >= margin:
+                break
+        else:
+            raise RuntimeError(f"{name}: no seed clears the margin")
+        out = {"mel": mel.numpy(), "prompt": ids[:, :Tp].numpy(), "tokens": ids.numpy(), "step_logits": lg.numpy()}
+        for k, v in mod.state_dict().items():
+            out["param:" + k] = v.detach().numpy()
+        meta = dict(kind="whisper_generate", vocab=vocab, n_mels=n_mels, T_a=Ta, T_p=Tp, n_new=n_new, n_text_ctx=Tp + n_new, dim=dim,
+                    heads=1, n_layer_enc=2, n_layer_dec=2, use_abs_pos_emb=pos, n_views=3, n_kernels=2, kernel_size=3, seed=seed,
+                    min_margin=mg)
+        out.update({"meta:" + k: np.asarray(v) for k, v in meta.items()})
+        _save(name, out, compress=True)
+        print(f"  seed {seed}, min top-1 / top-2 gap {mg:.2e}")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     groups = dict(train=train_cases, vit=vit_cases, ew=edgewise_cases, ewx=edgewise_variant_cases, cv=crossview_cases, wh=whisper_cases, mh=multihop_cases, qt=quartet_cases, sdpa=sdpa_cases,
-                  gpt=gpt_cases, whdec=whisper_decoder_cases, moe=moe_cases)
+                  gpt=gpt_cases, whdec=whisper_decoder_cases, moe=moe_cases,
+                  whgen=whisper_generate_cases)
     for name in (sys.argv[1:] or list(groups)):               # e.g. `gen_golden.py ewx` regenerates one group only
         groups[name]()
