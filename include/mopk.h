@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPK_VERSION 118 /* 118: mopk_decode_attn_* and MopkDecodeAttnArgs (added later without a bump: new exports only, detect with mopk_decode_attn_supported), mopk_moe_* and MopkMoeArgs (added later without a bump: new exports only, detect with mopk_moe_supported), MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
+#define MOPK_VERSION 118 /* 118: mopk_decode_attn_rows_*, MopkDecodeAttnRowsArgs, mopk_beam_* and MopkBeamArgs (added later without a bump: new exports only, detect with mopk_decode_attn_rows_supported / mopk_beam_supported), mopk_decode_attn_* and MopkDecodeAttnArgs (added later without a bump: new exports only, detect with mopk_decode_attn_supported), mopk_moe_* and MopkMoeArgs (added later without a bump: new exports only, detect with mopk_moe_supported), MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
 
 typedef enum MopkStatus {
     MOPK_OK = 0,
@@ -481,6 +481,66 @@ typedef struct MopkDecodeAttnArgs {
 int mopk_decode_attn_supported(const MopkDecodeAttnArgs *a);         /* 1 if the kernels take this call (shape, dtype, strides, alignment) */
 size_t mopk_decode_attn_workspace_bytes(const MopkDecodeAttnArgs *a);
 int mopk_decode_attn_fwd(const MopkDecodeAttnArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
+ * Row-indirect decode attention: beam search over a cache whose slots are written once.  (Added under version 118: new exports
+ * only; callers detect it with mopk_decode_attn_rows_supported.)  Exactly mopk_decode_attn_fwd, except that key / value j of query
+ * row b is read from cache row rows[b * rows_ld + j] at position j instead of from row b.  rows: device int32 (B, >= cap) table,
+ * rows_ld >= cap; an entry outside [0, B) is clamped into it.  With rows[b, j] = b the result is bitwise that of
+ * mopk_decode_attn_fwd (same chunks, softmax, merge order and fp32 arithmetic).  Cost: one int32 read per key.  Workspace:
+ * mopk_decode_attn_rows_workspace_bytes() (that of base). */
+typedef struct MopkDecodeAttnRowsArgs {
+    MopkDecodeAttnArgs base;             /* unchanged meaning; base.k / base.v: (B, cap, H, dk) views of the cache */
+    const int32_t *rows;                 /* device: (B, rows_ld) int32 source-row table */
+    int64_t rows_ld;                     /* elements between table rows, >= cap */
+} MopkDecodeAttnRowsArgs;
+int mopk_decode_attn_rows_supported(const MopkDecodeAttnRowsArgs *a);
+size_t mopk_decode_attn_rows_workspace_bytes(const MopkDecodeAttnRowsArgs *a);
+int mopk_decode_attn_rows_fwd(const MopkDecodeAttnRowsArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
+ * One step of batched beam search (WhisperMoP.beam_search): updates the device beam state in place from the step's last-position
+ * logits, with no host synchronisation, so a step can be captured once in a graph.  (Added under version 118: new exports only;
+ * callers detect it with mopk_beam_supported.)  Per batch item b that is not done (done[b] == 0):
+ *   candidates (k, v), score = scores[b*K + k] + (logit[b, k, v] - lse[b, k]) in fp32, k < K, v < V; a beam's candidates are its 2K
+ *   largest logits (ties: smaller v);  the item's top 2K candidates by score descending, ties to the smaller k * V + v;
+ *   walk them in order: token eos with a finite score -> stored as finished hypothesis fin_count[b] (while fin_count[b] < K) with
+ *   score / (pos - prompt_len + 1) ** length_penalty and tokens hist[b*K + k, :pos], eos; never a live beam.  Any other candidate
+ *   -> the next live beam k': scores, parents (k), next_ids (v).  The walk stops when K live beams are filled.
+ *   then hist and rows are reordered in place: row b*K + k' takes columns [0, pos) of row b*K + parents[k'], hist[., pos] = next_ids,
+ *   rows[., pos] = b*K + k';  done[b] = fin_count[b] >= K.
+ * pos = *pos: the history column of the new token (the cache length after the step's decode).  Done items are left untouched.
+ * logits: row (b, k) at logits + b * logits_sb + k * logits_sk elements (logits_sk = 0: one row per item shared by its beams, the
+ * first step), F32 or BF16, element-aligned; finite or -inf values.  1 <= K <= 8, 2 <= V, K * V < 2^31, pos in [prompt_len, T).
+ * Launch A: one workgroup per (beam row, vocab slice): (max, sum-exp) and the top 2K of the slice, 16-byte loads;  launch B: one
+ * workgroup per item: lse by a fixed-order merge, candidate merge, the walk and the reorder.  No atomics: bitwise reproducible. */
+#define MOPK_BEAM_MAX_K 8
+typedef struct MopkBeamArgs {
+    int32_t B, K, V;                     /* batch items, beams per item, vocabulary */
+    int32_t T;                           /* columns of hist, rows and fin_tokens */
+    int32_t logits_dtype;                /* MopkDtype */
+    int32_t eos;                         /* eos token id, or -1: no eos */
+    int32_t prompt_len;                  /* history columns before the first new token */
+    float length_penalty;
+    const void *logits;
+    int64_t logits_sb, logits_sk;        /* element strides of an item's and of a beam's logit row */
+    const int32_t *pos;                  /* device: the new token's history column (one int32) */
+    float *scores;                       /* (B*K) in / out: live beam log-probabilities */
+    int32_t *next_ids;                   /* (B*K) out: the live beams' new tokens (the next decoder step's ids) */
+    int32_t *parents;                    /* (B*K) out: beam index (0..K-1) each live beam extends */
+    int32_t *hist;                       /* (B*K, hist_ld) in / out: token history */
+    int64_t hist_ld;
+    int32_t *rows;                       /* (B*K, rows_ld) in / out: MopkDecodeAttnRowsArgs.rows */
+    int64_t rows_ld;
+    int32_t *fin_tokens;                 /* (B, K, T) out: finished hypotheses; columns past their eos are not written */
+    float *fin_scores;                   /* (B, K) out: length-normalised scores */
+    int32_t *fin_count;                  /* (B) in / out */
+    int32_t *done;                       /* (B) in / out */
+    void *workspace;
+} MopkBeamArgs;
+int mopk_beam_supported(const MopkBeamArgs *a);                      /* 1 if the kernels take this call (K, V, T, dtype, strides) */
+size_t mopk_beam_workspace_bytes(const MopkBeamArgs *a);
+int mopk_beam_step(const MopkBeamArgs *a, void *stream);
 
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);

@@ -165,6 +165,22 @@ class DecodeAttnArgs(C.Structure):
     ]
 
 
+class DecodeAttnRowsArgs(C.Structure):
+    """MopkDecodeAttnRowsArgs: decode attention whose keys / values are read through a (B, cap) source-row table (beam search)."""
+    _fields_ = [("base", DecodeAttnArgs), ("rows", _fp), ("rows_ld", C.c_int64)]
+
+
+class BeamArgs(C.Structure):
+    """MopkBeamArgs: one step of batched beam search over device state (WhisperMoP.beam_search)."""
+    _fields_ = [
+        ("B", C.c_int32), ("K", C.c_int32), ("V", C.c_int32), ("T", C.c_int32), ("logits_dtype", C.c_int32), ("eos", C.c_int32),
+        ("prompt_len", C.c_int32), ("length_penalty", C.c_float),
+        ("logits", _fp), ("logits_sb", C.c_int64), ("logits_sk", C.c_int64), ("pos", _fp),
+        ("scores", _fp), ("next_ids", _fp), ("parents", _fp), ("hist", _fp), ("hist_ld", C.c_int64), ("rows", _fp),
+        ("rows_ld", C.c_int64), ("fin_tokens", _fp), ("fin_scores", _fp), ("fin_count", _fp), ("done", _fp), ("workspace", _fp),
+    ]
+
+
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),
@@ -215,6 +231,12 @@ SYMBOLS = {
     "mopk_decode_attn_supported": (C.c_int, [C.POINTER(DecodeAttnArgs)]),
     "mopk_decode_attn_workspace_bytes": (C.c_size_t, [C.POINTER(DecodeAttnArgs)]),
     "mopk_decode_attn_fwd": (C.c_int, [C.POINTER(DecodeAttnArgs), C.c_void_p]),
+    "mopk_decode_attn_rows_supported": (C.c_int, [C.POINTER(DecodeAttnRowsArgs)]),
+    "mopk_decode_attn_rows_workspace_bytes": (C.c_size_t, [C.POINTER(DecodeAttnRowsArgs)]),
+    "mopk_decode_attn_rows_fwd": (C.c_int, [C.POINTER(DecodeAttnRowsArgs), C.c_void_p]),
+    "mopk_beam_supported": (C.c_int, [C.POINTER(BeamArgs)]),
+    "mopk_beam_workspace_bytes": (C.c_size_t, [C.POINTER(BeamArgs)]),
+    "mopk_beam_step": (C.c_int, [C.POINTER(BeamArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -18,6 +18,11 @@
 // Algorithmic traffic: 2 * B * L * H * dk * sizeof(T) bytes of K and V (read once), plus q, y and the fp32 partials
 // (B * H * chunks * Tq * (dk + 2) * 4 bytes, written and read back once).  Static LDS only (<= 59 KB): nothing to set before a
 // graph capture.
+//
+// Row-indirect variant (mopk_decode_attn_rows_*, beam search): the same kernels with ROWS = true, where key / value j of query row b
+// comes from cache row rows[b * rows_ld + j] (clamped into [0, B)) at position j.  Only the staging address changes: one int32 table
+// read per key, the key's dk elements still one run of 16-byte vectors, and every later step is the same code, so an identity table
+// gives bitwise the result of the plain kernels.
 #include "common.h"
 
 namespace mopk {
@@ -55,9 +60,9 @@ __device__ __forceinline__ void da_unpack(const uint4 &u, float (&f)[4], float) 
     f[2] = __builtin_bit_cast(float, u.z); f[3] = __builtin_bit_cast(float, u.w);
 }
 
-// launch 1: one (row, chunk) partial
-template <typename T, int DK, int TQB>
-__global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs a, int nsplit) {
+// launch 1: one (row, chunk) partial; ROWS: keys / values through the row table
+template <typename T, int DK, int TQB, bool ROWS>
+__global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs a, int nsplit, const int32_t *rows, int64_t rows_ld) {
     using C = DaCfg<T, DK, TQB>;
     __shared__ uint4 tile[C::CH * C::PITCH];
     __shared__ float4 qs4[TQB * DK / 4];
@@ -90,8 +95,15 @@ __global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs
         const int idx = tid + DA_THREADS * u, row = idx / C::R16, col = idx - row * C::R16;
         kreg[u] = vreg[u] = make_uint4(0u, 0u, 0u, 0u);
         if (row < nv) {
-            kreg[u] = *(const uint4 *)(kb + (int64_t)(c0 + row) * a.k.sn * C::ES + col * 16);
-            vreg[u] = *(const uint4 *)(vb + (int64_t)(c0 + row) * a.v.sn * C::ES + col * 16);
+            int64_t kro = 0, vro = 0;                               // element offset of the source row from row b
+            if constexpr (ROWS) {
+                int r = rows[(int64_t)b * rows_ld + c0 + row];
+                r = r < 0 ? 0 : (r >= a.B ? a.B - 1 : r);
+                kro = (int64_t)(r - b) * a.k.sb;
+                vro = (int64_t)(r - b) * a.v.sb;
+            }
+            kreg[u] = *(const uint4 *)(kb + ((int64_t)(c0 + row) * a.k.sn + kro) * C::ES + col * 16);
+            vreg[u] = *(const uint4 *)(vb + ((int64_t)(c0 + row) * a.v.sn + vro) * C::ES + col * 16);
         }
     }
     const T *qb = (const T *)a.q.ptr + (int64_t)b * a.q.sb + (int64_t)h * a.q.sh;
@@ -256,21 +268,30 @@ int da_check(const MopkDecodeAttnArgs *a) {
     return MOPK_OK;
 }
 
-template <typename T, int DK>
-void da_launch_dk(const MopkDecodeAttnArgs *a, hipStream_t st) {
+template <typename T, int DK, bool ROWS>
+void da_launch_dk(const MopkDecodeAttnArgs *a, const int32_t *rows, int64_t rows_ld, hipStream_t st) {
     const int ns = da_nsplit(a);
     const dim3 grid((unsigned)(a->B * a->H), (unsigned)ns), block(DA_THREADS);
-    if (a->Tq <= 1) hipLaunchKernelGGL((da_split_kernel<T, DK, 1>), grid, block, 0, st, *a, ns);
-    else if (a->Tq <= 4) hipLaunchKernelGGL((da_split_kernel<T, DK, 4>), grid, block, 0, st, *a, ns);
-    else hipLaunchKernelGGL((da_split_kernel<T, DK, 16>), grid, block, 0, st, *a, ns);
+    if (a->Tq <= 1) hipLaunchKernelGGL((da_split_kernel<T, DK, 1, ROWS>), grid, block, 0, st, *a, ns, rows, rows_ld);
+    else if (a->Tq <= 4) hipLaunchKernelGGL((da_split_kernel<T, DK, 4, ROWS>), grid, block, 0, st, *a, ns, rows, rows_ld);
+    else hipLaunchKernelGGL((da_split_kernel<T, DK, 16, ROWS>), grid, block, 0, st, *a, ns, rows, rows_ld);
     hipLaunchKernelGGL(da_merge_kernel<T>, dim3((unsigned)(a->B * a->H)), block, 0, st, *a, ns);
 }
 
-template <typename T>
-void da_launch(const MopkDecodeAttnArgs *a, hipStream_t st) {
-    if (a->dk == 32) da_launch_dk<T, 32>(a, st);
-    else if (a->dk == 64) da_launch_dk<T, 64>(a, st);
-    else da_launch_dk<T, 128>(a, st);
+template <typename T, bool ROWS>
+void da_launch(const MopkDecodeAttnArgs *a, const int32_t *rows, int64_t rows_ld, hipStream_t st) {
+    if (a->dk == 32) da_launch_dk<T, 32, ROWS>(a, rows, rows_ld, st);
+    else if (a->dk == 64) da_launch_dk<T, 64, ROWS>(a, rows, rows_ld, st);
+    else da_launch_dk<T, 128, ROWS>(a, rows, rows_ld, st);
+}
+
+int da_rows_check(const MopkDecodeAttnRowsArgs *a) {
+    if (!a) return MOPK_ERR_BAD_ARG;
+    const int rc = da_check(&a->base);
+    if (rc != MOPK_OK) return rc;
+    if (a->rows_ld < a->base.cap) return MOPK_ERR_BAD_SHAPE;
+    if ((uintptr_t)a->rows & 3) return MOPK_ERR_UNSUPPORTED;
+    return MOPK_OK;
 }
 
 }  // namespace
@@ -291,8 +312,24 @@ int mopk_decode_attn_fwd(const MopkDecodeAttnArgs *a, void *stream) {
     const int rc = da_check(a);
     if (rc != MOPK_OK) return rc;
     if (!a->q.ptr || !a->k.ptr || !a->v.ptr || !a->y.ptr || !a->workspace) return MOPK_ERR_BAD_ARG;
-    if (a->io_dtype == MOPK_BF16) da_launch<unsigned short>(a, (hipStream_t)stream);
-    else da_launch<float>(a, (hipStream_t)stream);
+    if (a->io_dtype == MOPK_BF16) da_launch<unsigned short, false>(a, nullptr, 0, (hipStream_t)stream);
+    else da_launch<float, false>(a, nullptr, 0, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+}
+
+int mopk_decode_attn_rows_supported(const MopkDecodeAttnRowsArgs *a) { return da_rows_check(a) == MOPK_OK; }
+
+size_t mopk_decode_attn_rows_workspace_bytes(const MopkDecodeAttnRowsArgs *a) {
+    return da_rows_check(a) == MOPK_OK ? mopk_decode_attn_workspace_bytes(&a->base) : 0;
+}
+
+int mopk_decode_attn_rows_fwd(const MopkDecodeAttnRowsArgs *a, void *stream) {
+    const int rc = da_rows_check(a);
+    if (rc != MOPK_OK) return rc;
+    const MopkDecodeAttnArgs *b = &a->base;
+    if (!b->q.ptr || !b->k.ptr || !b->v.ptr || !b->y.ptr || !b->workspace || !a->rows) return MOPK_ERR_BAD_ARG;
+    if (b->io_dtype == MOPK_BF16) da_launch<unsigned short, true>(b, a->rows, a->rows_ld, (hipStream_t)stream);
+    else da_launch<float, true>(b, a->rows, a->rows_ld, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
 }
 

@@ -284,14 +284,21 @@ class WhisperMoP(nn.Module):
         under bf16 autocast)."""
         if not 0 < int(max_len) <= self.cfg.n_text_ctx:
             raise ValueError(f"init_decode_cache: max_len = {max_len} outside [1, n_text_ctx = {self.cfg.n_text_ctx}]")
-        B, T_a, _ = enc_out.shape
+        B = enc_out.shape[0]
         H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
-        ck = [blk.cross_attn.k_proj(enc_out).view(B, T_a, H, Dh) for blk in self.decoder]
-        cv = [blk.cross_attn.v_proj(enc_out).view(B, T_a, H, Dh) for blk in self.decoder]
+        ck, cv = self._cross_kv(enc_out)
         kw = dict(dtype=ck[0].dtype, device=enc_out.device)
         sk = [torch.zeros(B, int(max_len), H, Dh, **kw) for _ in self.decoder]
         sv = [torch.zeros(B, int(max_len), H, Dh, **kw) for _ in self.decoder]
         return WhisperDecodeCache(ck, cv, sk, sv, torch.zeros(1, dtype=torch.int32, device=enc_out.device), max_len)
+
+    def _cross_kv(self, enc_out: torch.Tensor):
+        """every decoder layer's cross-attention keys / values, (B, T_audio, H, dh) each, projected once"""
+        B, T_a, _ = enc_out.shape
+        H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        ck = [blk.cross_attn.k_proj(enc_out).view(B, T_a, H, Dh) for blk in self.decoder]
+        cv = [blk.cross_attn.v_proj(enc_out).view(B, T_a, H, Dh) for blk in self.decoder]
+        return ck, cv
 
     @torch.no_grad()
     def decode_step(self, cache: WhisperDecodeCache, ids: torch.Tensor) -> torch.Tensor:
@@ -300,6 +307,13 @@ class WhisperMoP(nn.Module):
         Equals decode(enc_out, all ids so far)[:, -T_new:] in eval().  Attention runs on ops.decode_attention (the split-KV kernels)
         with the device length; a first chunk of more than 16 tokens runs the square causal ops.sdpa_core and writes its keys /
         values into the cache.  Positions, the append and the length update are device-indexed: no host sync, graph-capturable."""
+        return self._decode_tokens(cache, ids)
+
+    def _decode_tokens(self, cache: WhisperDecodeCache, ids: torch.Tensor, rows: Optional[torch.Tensor] = None,
+                       beams: int = 1) -> torch.Tensor:
+        """decode_step's body.  rows / beams (beam search): self-attention reads row b's key / value j from cache row rows[b, j]
+        (ops.decode_attention_rows), and the B = items * beams rows share their item's cross cache (items, T_audio, H, dh): the
+        beams' queries of one item go to ops.decode_attention together as one row of beams * T_new queries."""
         B, T = ids.shape
         if cache.pos + T > cache.max_len:
             raise ValueError(f"decode_step: {cache.pos} cached + {T} new tokens exceed the cache's max_len = {cache.max_len}")
@@ -319,6 +333,8 @@ class WhisperMoP(nn.Module):
             cache.self_v[l].index_copy_(1, idx, v.to(cache.dtype))
             if prefill:
                 y = ops.sdpa_core(q, k, v, causal=True)
+            elif rows is not None:
+                y = ops.decode_attention_rows(q, cache.self_k[l], cache.self_v[l], rows, kv_len=new_len, causal=True)
             else:
                 y = ops.decode_attention(q, cache.self_k[l], cache.self_v[l], kv_len=new_len, causal=True)
             x = x + sa.o_proj(y)
@@ -326,6 +342,8 @@ class WhisperMoP(nn.Module):
             ck, cv = cache.cross_k[l], cache.cross_v[l]
             if long_chunk:
                 y = ops.sdpa_core(q, ck, cv)
+            elif beams > 1:
+                y = ops.decode_attention(q.view(B // beams, beams * T, H, Dh), ck, cv, nk=ck.shape[1]).view(B, T, H * Dh)
             else:
                 y = ops.decode_attention(q, ck, cv, nk=ck.shape[1])
             x = x + ca.o_proj(y)
@@ -383,6 +401,68 @@ class WhisperMoP(nn.Module):
             logits = static_logits
         out = torch.cat([prompt_ids, torch.stack(toks, dim=1).to(prompt_ids.dtype)], dim=1)
         return (out, torch.stack(steps, dim=1)) if return_logits else out
+
+    @torch.no_grad()
+    def beam_search(self, mel: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int, num_beams: int,
+                    eos_token_id: Optional[int] = None, length_penalty: float = 1.0, graph: bool = False):
+        """beam-search decoding: mel (B, T_audio, n_mels), prompt_ids (B, T_p) -> (tokens (B, T_p + max_new_tokens) in prompt_ids'
+        dtype, scores (B,) fp32), all on the device; the step loop never syncs the host.
+
+        The prompt runs once per item (its keys / values land in cache row b * K); beam scores start at [0, -inf, ...].  Each step
+        (ops.beam_step) ranks the candidates (k, v) by score_k + log_softmax(logits_k)[v] in fp32, takes the top 2K (ties to the
+        smaller k * V + v) and walks them in order: eos_token_id with a finite score is stored as a finished hypothesis while the item
+        has fewer than K (score / gen_len ** length_penalty, gen_len counting the eos), and is never a live beam; any other candidate
+        becomes the next live beam; the walk stops at K live beams.  An item holding K finished hypotheses is done (patience 1) and
+        no longer changes.  After max_new_tokens steps an item that is not done adds its live beams in beam order until it holds K;
+        the answer is the best normalised score (ties to the earlier stored hypothesis), eos-filled past its eos.  Without
+        eos_token_id that is the best live beam.
+        Beams never copy cache slots: each step's keys / values are written once into the beam's own row, and the self-attention
+        reads a beam's history through the device row table (ops.decode_attention_rows).  graph=True captures one step (decoder
+        step + beam_step) after the first eager one and replays it (torch.cuda.graph, one stream, static buffers)."""
+        B, T_p = prompt_ids.shape
+        K = int(num_beams)
+        if not 1 <= K <= ops.BEAM_MAX_K:
+            raise ValueError(f"beam_search: num_beams = {num_beams} outside [1, {ops.BEAM_MAX_K}]")
+        if self.cfg.vocab_size < 2:
+            raise ValueError(f"beam_search: needs vocab_size >= 2, got {self.cfg.vocab_size}")
+        if T_p < 1 or max_new_tokens < 1:
+            raise ValueError(f"beam_search: needs a prompt and at least one new token (T_p = {T_p}, max_new_tokens = {max_new_tokens})")
+        if T_p + max_new_tokens > self.cfg.n_text_ctx:
+            raise ValueError(f"beam_search: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        cap = T_p + max_new_tokens
+        H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        enc, _ = self.encode(mel)
+        ck, cv = self._cross_kv(enc)
+        kw = dict(dtype=ck[0].dtype, device=enc.device)
+        sk = [torch.zeros(B * K, cap, H, Dh, **kw) for _ in self.decoder]
+        sv = [torch.zeros(B * K, cap, H, Dh, **kw) for _ in self.decoder]
+        length = torch.zeros(1, dtype=torch.int32, device=enc.device)
+        prompt_cache = WhisperDecodeCache(ck, cv, [t[::K] for t in sk], [t[::K] for t in sv], length, cap)
+        logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]              # (B, V): shared by the item's beams
+        cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
+        cache.pos = T_p
+        st = ops.BeamState(prompt_ids, K, cap, eos_token_id, length_penalty)
+        ops.beam_step(logits, st, length)
+
+        def step():
+            ops.beam_step(self._decode_tokens(cache, st.next_ids, rows=st.rows, beams=K)[:, -1], st, cache.length)
+
+        g = None
+        for t in range(1, max_new_tokens):
+            if not graph or t == 1:                  # the first full step runs eagerly (and warms every kernel up)
+                step()
+                continue
+            if g is None:
+                g = torch.cuda.CUDAGraph()
+                with torch.autocast(device_type="cuda", dtype=torch.get_autocast_dtype("cuda"),
+                                    enabled=torch.is_autocast_enabled("cuda"), cache_enabled=False):
+                    with torch.cuda.graph(g):
+                        step()
+                cache.pos -= 1                           # capture recorded the step without running it
+            g.replay()
+            cache.pos += 1
+        tokens, scores = ops.beam_finalize(st, max_new_tokens)
+        return tokens.to(prompt_ids.dtype), scores
 
     @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):

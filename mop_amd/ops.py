@@ -1601,3 +1601,272 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
             rc = lib.mopk_decode_attn_fwd(C.byref(a), _stream())
         L.check(rc, "mopk_decode_attn_fwd")
         return y.view(B, Tq, H * dk)
+
+
+# ---- decode attention through a source-row table (mopk_decode_attn_rows_*; WhisperMoP beam search) ----
+def decode_attention_rows_torch(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, rows: torch.Tensor,
+                                kv_len: Optional[torch.Tensor] = None, causal: bool = False) -> torch.Tensor:
+    """the reference composition of `decode_attention_rows`: gather key / value j of row b from cache row rows[b, j] (clamped into
+    [0, B)), then decode_attention_torch"""
+    B, cap = k_cache.shape[:2]
+    r = rows[:, :cap].to(torch.long).clamp(0, B - 1)
+    j = torch.arange(cap, device=k_cache.device).unsqueeze(0)
+    return decode_attention_torch(q, k_cache[r, j], v_cache[r, j], kv_len, None, causal)
+
+
+def _dar_args(q, k_cache, v_cache, rows, kv_len, causal) -> L.DecodeAttnRowsArgs:
+    a = L.DecodeAttnRowsArgs()
+    a.base = _da_args(q, k_cache, v_cache, kv_len, None, causal)
+    a.rows, a.rows_ld = rows.data_ptr(), rows.stride(0)
+    return a
+
+
+def decode_attention_rows_supported(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, rows: torch.Tensor,
+                                    kv_len: Optional[torch.Tensor] = None, causal: bool = False) -> bool:
+    """True if mopk_decode_attn_rows_* take this call: what decode_attention_supported asks, and a CUDA int32 (B, >= cap) table with
+    unit inner stride"""
+    if not rows.is_cuda or rows.dtype != torch.int32 or rows.dim() != 2 or rows.stride(1) != 1:
+        return False
+    if not decode_attention_supported(q, k_cache, v_cache, kv_len, None, causal):
+        return False
+    return bool(L.lib().mopk_decode_attn_rows_supported(C.byref(_dar_args(q, k_cache, v_cache, rows, kv_len, causal))))
+
+
+def decode_attention_rows(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, rows: torch.Tensor,
+                          kv_len: Optional[torch.Tensor] = None, causal: bool = False) -> torch.Tensor:
+    """`decode_attention` whose key / value j of query row b is read from cache row rows[b, j] at position j: a beam's history lives
+    in the rows its ancestors wrote, and no cache slot is copied when beams are reordered.  Inference only (no autograd).
+
+    q: (B, Tq, H, dk); k_cache, v_cache: (B, cap, H, dk); rows: int32 (B, >= cap) device table (entries outside [0, B) are clamped);
+    kv_len as in decode_attention (else L = cap).  With rows[b, j] = b the result is bitwise that of decode_attention.  Returns
+    (B, Tq, H * dk) in q's dtype.  Runs the row-indirect split-KV HIP kernels when decode_attention_rows_supported() accepts the call,
+    else decode_attention_rows_torch(); LAST_PATH["decode_attn_rows"] records which.  No host synchronisation."""
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError(f"decode_attention_rows: q must be (B, Tq, H, dk) and k_cache, v_cache (B, cap, H, dk) of one shape; got q "
+                         f"{tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)}")
+    if k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
+        raise ValueError(f"decode_attention_rows: k_cache / v_cache {tuple(k_cache.shape)} do not match q's B, H, dk {tuple(q.shape)}")
+    if rows.dim() != 2 or rows.shape[0] != q.shape[0] or rows.shape[1] < k_cache.shape[1]:
+        raise ValueError(f"decode_attention_rows: rows must be (B, >= cap) = ({q.shape[0]}, >= {k_cache.shape[1]}), "
+                         f"got {tuple(rows.shape)}")
+    if kv_len is not None and kv_len.numel() != 1:
+        raise ValueError(f"decode_attention_rows: kv_len must hold one element, got shape {tuple(kv_len.shape)}")
+    _require_gpu(q, "decode_attention_rows")
+    with torch.no_grad():
+        if not decode_attention_rows_supported(q, k_cache, v_cache, rows, kv_len, causal):
+            LAST_PATH["decode_attn_rows"] = L.PATH_GENERIC
+            return decode_attention_rows_torch(q, k_cache, v_cache, rows, kv_len, causal)
+        lib = L.lib()
+        B, Tq, H, dk = q.shape
+        a = _dar_args(q, k_cache, v_cache, rows, kv_len, causal)
+        y = torch.empty(B, Tq, H, dk, dtype=q.dtype, device=q.device)
+        ws = _bytes(lib.mopk_decode_attn_rows_workspace_bytes(C.byref(a)), q.device)
+        a.base.y, a.base.workspace = _v4(y), ws.data_ptr()
+        LAST_PATH["decode_attn_rows"] = L.PATH_FUSED
+        with _timed("decode_attn_rows"):
+            rc = lib.mopk_decode_attn_rows_fwd(C.byref(a), _stream())
+        L.check(rc, "mopk_decode_attn_rows_fwd")
+        return y.view(B, Tq, H * dk)
+
+
+# ---- batched beam search on device state (mopk_beam_*; WhisperMoP.beam_search) ----
+BEAM_MAX_K = 8
+
+
+class BeamState:
+    """Device state of a beam search over B items with K beams each, updated in place by `beam_step` (no host sync, static
+    buffers: a step can be captured in a graph).  Rows b * K + k hold item b's beam k.
+
+    scores (B*K,) fp32: live beam log-probabilities, [0, -inf, ...] per item at the start (the prompt is one hypothesis);
+    next_ids (B*K, 1) int32: the live beams' newest tokens (the next decoder step's ids); parents (B*K,) int32: the beam each live
+    beam extended at the last step; hist (B*K, cap) int32: token histories, the prompt in columns [0, T_p); rows (B*K, cap) int32:
+    the cache row holding each history position's keys / values (the prompt's in row b * K, every later one in the row that wrote
+    it; entries past a beam's length point at the beam's own row); fin_tokens (B, K, cap) int32, fin_scores (B, K) fp32,
+    fin_count (B,) int32: finished hypotheses (eos-filled past their eos, scores length-normalised); done (B,) int32."""
+
+    def __init__(self, prompt_ids: torch.Tensor, num_beams: int, cap: int, eos_token_id: Optional[int] = None,
+                 length_penalty: float = 1.0):
+        B, T_p = prompt_ids.shape
+        K, dev = int(num_beams), prompt_ids.device
+        self.B, self.K, self.T, self.prompt_len = B, K, int(cap), T_p
+        self.eos, self.length_penalty = eos_token_id, float(length_penalty)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.scores = torch.zeros(B, K, dtype=torch.float32, device=dev)
+        self.scores[:, 1:] = float("-inf")
+        self.scores = self.scores.view(B * K)
+        self.next_ids = torch.zeros(B * K, 1, **i32)
+        self.parents = torch.zeros(B * K, **i32)
+        self.hist = torch.zeros(B * K, self.T, **i32)
+        self.hist[:, :T_p] = prompt_ids.to(torch.int32).repeat_interleave(K, 0)
+        r = torch.arange(B * K, **i32)
+        self.rows = r.unsqueeze(1).repeat(1, self.T)
+        self.rows[:, :T_p] = (r // K * K).unsqueeze(1)
+        self.fin_tokens = torch.full((B, K, self.T), 0 if eos_token_id is None else int(eos_token_id), **i32)
+        self.fin_scores = torch.full((B, K), float("-inf"), dtype=torch.float32, device=dev)
+        self.fin_count = torch.zeros(B, **i32)
+        self.done = torch.zeros(B, **i32)
+
+
+def _beam_logits_strides(logits: torch.Tensor, st: BeamState):
+    """(item stride, beam stride) of (B*K, V) logits, or of (B, V) logits shared by each item's beams (beam stride 0)"""
+    if logits.shape[0] == st.B * st.K:
+        return st.K * logits.stride(0), logits.stride(0)
+    return logits.stride(0), 0
+
+
+def _beam_args(logits: torch.Tensor, st: BeamState, pos: torch.Tensor) -> L.BeamArgs:
+    a = L.BeamArgs()
+    a.B, a.K, a.V, a.T = st.B, st.K, logits.shape[-1], st.T
+    a.logits_dtype = L.MOPK_BF16 if logits.dtype == torch.bfloat16 else L.MOPK_F32
+    a.eos = -1 if st.eos is None else int(st.eos)
+    a.prompt_len, a.length_penalty = st.prompt_len, st.length_penalty
+    a.logits, (a.logits_sb, a.logits_sk), a.pos = logits.data_ptr(), _beam_logits_strides(logits, st), pos.data_ptr()
+    a.scores, a.next_ids, a.parents = st.scores.data_ptr(), st.next_ids.data_ptr(), st.parents.data_ptr()
+    a.hist, a.hist_ld, a.rows, a.rows_ld = st.hist.data_ptr(), st.hist.stride(0), st.rows.data_ptr(), st.rows.stride(0)
+    a.fin_tokens, a.fin_scores = st.fin_tokens.data_ptr(), st.fin_scores.data_ptr()
+    a.fin_count, a.done = st.fin_count.data_ptr(), st.done.data_ptr()
+    return a
+
+
+def beam_step_supported(logits: torch.Tensor, state: BeamState, pos: torch.Tensor) -> bool:
+    """True if mopk_beam_* take this call: CUDA fp32 / bf16 logits with unit inner stride, 1 <= K <= 8, V >= 2, an int32 device pos
+    (the library's own query decides the rest)"""
+    if not logits.is_cuda or logits.dtype not in (torch.float32, torch.bfloat16) or logits.stride(-1) != 1:
+        return False
+    if not pos.is_cuda or pos.dtype != torch.int32 or pos.numel() != 1:
+        return False
+    return bool(L.lib().mopk_beam_supported(C.byref(_beam_args(logits, state, pos))))
+
+
+def _beam_check(logits: torch.Tensor, state: BeamState, pos: torch.Tensor, what: str):
+    if logits.dim() != 2 or logits.shape[0] not in (state.B, state.B * state.K):
+        raise ValueError(f"{what}: logits must be (B*K, V) = ({state.B * state.K}, V) or (B, V) = ({state.B}, V), "
+                         f"got {tuple(logits.shape)}")
+    if not 1 <= state.K <= BEAM_MAX_K or logits.shape[1] < 2:
+        raise ValueError(f"{what}: needs 1 <= K <= {BEAM_MAX_K} and V >= 2 (K = {state.K}, V = {logits.shape[1]})")
+    if pos.numel() != 1:
+        raise ValueError(f"{what}: pos must hold one element, got shape {tuple(pos.shape)}")
+
+
+def beam_step_torch(logits: torch.Tensor, state: BeamState, pos: torch.Tensor) -> None:
+    """the reference composition of `beam_step` in torch ops (CPU or GPU, no host sync): the same candidates, order, walk and
+    in-place updates, vectorised over items with a loop over the 2K candidate ranks"""
+    _beam_check(logits, state, pos, "beam_step_torch")
+    B, K, T = state.B, state.K, state.T
+    V, NC, dev = logits.shape[1], 2 * K, logits.device
+    x = logits.float()
+    if x.shape[0] != B * K:
+        x = x.repeat_interleave(K, 0)
+    lse = torch.logsumexp(x, dim=-1, keepdim=True)
+    top, idx = torch.sort(x, dim=-1, descending=True, stable=True)                 # a beam's 2K best, ties to the smaller v
+    n = min(NC, V)
+    top, idx = top[:, :n], idx[:, :n]
+    s0 = state.scores.view(B * K, 1)
+    inf = torch.tensor(float("-inf"), device=dev)
+    sc = torch.where((top == float("-inf")) | (s0 == float("-inf")), inf, s0 + (top - lse))
+    flat = (torch.arange(B * K, device=dev) % K).unsqueeze(1) * V + idx
+    sc, flat = sc.view(B, K * n), flat.view(B, K * n)
+    o = torch.argsort(flat, dim=1, stable=True)                                     # ties to the smaller flat index ...
+    sc, flat = sc.gather(1, o), flat.gather(1, o)
+    o = torch.argsort(sc, dim=1, descending=True, stable=True)                      # ... under score descending
+    cs, cf = sc.gather(1, o)[:, :NC], flat.gather(1, o)[:, :NC]
+    ck, cv = cf // V, cf % V
+
+    p = pos.reshape(()).to(torch.long)
+    upd = (state.done == 0) & (p >= state.prompt_len) & (p < T)
+    norm = (p - state.prompt_len + 1).to(torch.float32).pow(state.length_penalty)
+    eos = -1 if state.eos is None else int(state.eos)
+    hist, rows = state.hist.view(B, K, T), state.rows.view(B, K, T)
+    j = torch.arange(T, device=dev)
+    before, at = j < p, j == p
+    nl = torch.zeros(B, dtype=torch.long, device=dev)
+    nf = state.fin_count.to(torch.long)
+    new_s = state.scores.view(B, K).clone()
+    par, tok = torch.zeros(B, K, dtype=torch.long, device=dev), torch.zeros(B, K, dtype=torch.long, device=dev)
+    fin_s, fin_t = state.fin_scores.clone(), state.fin_tokens.clone()
+
+    def put(t, i, val, m):                                                          # t[b, i[b]] = val[b] where m[b]
+        i = i.unsqueeze(1)
+        t.scatter_(1, i, torch.where(m, val.to(t.dtype), t.gather(1, i).squeeze(1)).unsqueeze(1))
+
+    for c in range(NC):
+        s, k, v = cs[:, c], ck[:, c], cv[:, c]
+        active = nl < K
+        is_fin = (v == eos) & torch.isfinite(s)
+        store = active & is_fin & (nf < K)
+        slot = nf.clamp(max=K - 1)
+        put(fin_s, slot, s / norm, store)
+        src = hist.gather(1, k.view(B, 1, 1).expand(B, 1, T))                        # the parent's history, before this step
+        row = torch.where(before, src, torch.where(at, torch.full_like(src, max(eos, 0)), fin_t.gather(
+            1, slot.view(B, 1, 1).expand(B, 1, T))))
+        fin_t.scatter_(1, slot.view(B, 1, 1).expand(B, 1, T),
+                       torch.where(store.view(B, 1, 1), row, fin_t.gather(1, slot.view(B, 1, 1).expand(B, 1, T))))
+        nf = nf + store.to(torch.long)
+        live = active & ~is_fin
+        li = nl.clamp(max=K - 1)
+        put(new_s, li, s, live)
+        put(par, li, k, live)
+        put(tok, li, v, live)
+        nl = nl + live.to(torch.long)
+
+    g = par.unsqueeze(2).expand(B, K, T)
+    own = (torch.arange(B * K, device=dev, dtype=torch.int32).view(B, K, 1)).expand(B, K, T)
+    new_hist = torch.where(before, hist.gather(1, g), torch.where(at, tok.to(torch.int32).unsqueeze(2).expand(B, K, T), hist))
+    new_rows = torch.where(before, rows.gather(1, g), torch.where(at, own, rows))
+    u1, u2, u3 = upd.view(B, 1), upd.view(B, 1, 1), upd
+    state.hist.copy_(torch.where(u2, new_hist, hist).view(B * K, T))
+    state.rows.copy_(torch.where(u2, new_rows, rows).view(B * K, T))
+    state.scores.copy_(torch.where(u1, new_s, state.scores.view(B, K)).view(B * K))
+    state.parents.copy_(torch.where(u1, par.to(torch.int32), state.parents.view(B, K)).view(B * K))
+    state.next_ids.copy_(torch.where(u1, tok.to(torch.int32), state.next_ids.view(B, K)).view(B * K, 1))
+    state.fin_scores.copy_(torch.where(u1, fin_s, state.fin_scores))
+    state.fin_tokens.copy_(torch.where(u2, fin_t, state.fin_tokens))
+    state.fin_count.copy_(torch.where(u3, nf.to(torch.int32), state.fin_count))
+    state.done.copy_(torch.where(u3, (nf >= K).to(torch.int32), state.done))
+
+
+def beam_step(logits: torch.Tensor, state: BeamState, pos: torch.Tensor) -> None:
+    """one beam-search step: update `state` in place from the step's last-position logits.  Inference only.
+
+    logits: (B*K, V), or (B, V) shared by each item's beams (the prompt's, at the first step); fp32 or bf16.  pos: (1,) int32 device
+    tensor, the history column of the new tokens (the decoder cache's length after the step).  Per item not yet done:
+    - candidates (k, v) score scores[k] + log_softmax(logits[k])[v] in fp32; the top 2K in descending score, ties to the smaller
+      k * V + v (each beam contributes its 2K largest logits, ties to the smaller v);
+    - walk them in order: eos_token_id with a finite score -> a finished hypothesis while the item has fewer than K, stored with
+      score / (pos - T_p + 1) ** length_penalty (the generated length, eos counted) and its history + eos; never a live beam.  Any
+      other candidate -> the next live beam.  Stop once K live beams are filled;
+    - reorder hist / rows in place by parent, write the new tokens at column pos and rows[b*K + k, pos] = b*K + k (the slot the next
+      decoder step appends), and mark the item done once it holds K finished hypotheses.
+    pos outside [T_p, cap) changes nothing.  Runs the two-launch HIP kernel pair (mopk_beam_step) when beam_step_supported() accepts
+    the call, else beam_step_torch(); LAST_PATH["beam_step"] records which.  No host synchronisation."""
+    _beam_check(logits, state, pos, "beam_step")
+    _require_gpu(logits, "beam_step")
+    with torch.no_grad():
+        if not beam_step_supported(logits, state, pos):
+            LAST_PATH["beam_step"] = L.PATH_GENERIC
+            return beam_step_torch(logits, state, pos)
+        lib = L.lib()
+        a = _beam_args(logits, state, pos)
+        ws = _bytes(lib.mopk_beam_workspace_bytes(C.byref(a)), logits.device)
+        a.workspace = ws.data_ptr()
+        LAST_PATH["beam_step"] = L.PATH_FUSED
+        with _timed("beam_step"):
+            rc = lib.mopk_beam_step(C.byref(a), _stream())
+        L.check(rc, "mopk_beam_step")
+
+
+def beam_finalize(state: BeamState, n_new: int):
+    """the search's answer after n_new steps -> (tokens (B, cap) int32, scores (B,) fp32), on the device without a sync.  An item
+    that is not done adds its live beams in beam order (score / n_new ** length_penalty) until it holds K hypotheses; the answer is
+    the best normalised score, ties to the earlier stored hypothesis; columns past its eos hold eos."""
+    B, K, T = state.B, state.K, state.T
+    dev = state.scores.device
+    cnt = state.fin_count.to(torch.long).unsqueeze(1)
+    j = torch.arange(K, device=dev).unsqueeze(0)
+    src = (j - cnt).clamp(0, K - 1)
+    fill = (j >= cnt) & (state.done == 0).unsqueeze(1)
+    live = state.scores.view(B, K) / float(n_new) ** state.length_penalty
+    s = torch.where(fill, live.gather(1, src), state.fin_scores)
+    t = torch.where(fill.unsqueeze(2), state.hist.view(B, K, T).gather(1, src.unsqueeze(2).expand(B, K, T)), state.fin_tokens)
+    best = s.argmax(dim=1, keepdim=True)
+    return t.gather(1, best.unsqueeze(2).expand(B, 1, T)).squeeze(1), s.gather(1, best).squeeze(1)

@@ -6,6 +6,8 @@
     python tools/bench_whisper_decode.py --workload core       # the decode attention core vs ops.sdpa_core (N = 1) and torch SDPA
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload core-trace
     python tools/bench_whisper_decode.py --stats DIR/<host>/<pid>_kernel_stats.csv   # decode kernels against the byte bound
+    python tools/bench_whisper_decode.py --workload beam --out profiles/whisper_beam_bench.jsonl   # beam search, K = 5
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload beam-trace
 
 Model: d = 512, H = 8, 6 + 6 layers, T_a = 1500, vocab 51865 (Whisper-base-like), fp32 parameters under bf16 autocast, prompt 4,
 220 new tokens, B in {1, 8}.  Variants: (a) naive: decode(enc, whole prefix) per token; (b) cached eager: generate(); (c) cached +
@@ -13,6 +15,11 @@ graph: generate(graph=True).  Each variant is timed end to end (encoder included
 latency = time / new tokens.  Core: B = 8, H = 8, dk = 64, Tq = 1, Nk in {448, 1500}, bf16.  Byte bound: K and V are read once,
 2 B Nk H dk 2 bytes, at 6.3 TB/s (the MI355X's achievable HBM rate); a kernel faster than that bound was served from the 256 MiB
 Infinity Cache (the same 2-12 MB cache is read by every timed call).
+Beam: K = 5, B in {1, 8}, same model, prompt and length.  Variants: (a) torch_beam: the same search composed of torch ops
+(log_softmax + topk over K * V + an index_select of every layer's self-attention cache by parent beam, cross cache repeated K times,
+no eos); (b) beam_search eager; (c) beam_search(graph=True).  beam-trace runs (b) at B = 8 for rocprofv3; --stats then also prints
+the beam kernels (bs_*) and the row-indirect attention (da_* with ROWS) next to their byte bounds: B K V 2 bytes of bf16 logits per
+step, and 2 B K L H dk 2 + 4 B K L bytes of K, V and row table per layer and step at the mean length L = T_p + 110.
 """
 from __future__ import annotations
 
@@ -85,6 +92,75 @@ def bench_generate(args):
                              graph_equals_eager=bool(torch.equal(outs["cached"], outs["cached_graph"]))))
 
 
+def _base_model():
+    import torch
+    from mop_amd.nn import WhisperConfig, WhisperMoP
+    cfg = WhisperConfig(n_mels=NMELS, n_audio_ctx=TA, vocab_size=VOCAB, n_text_ctx=448, n_embd=D, n_head=H, n_layer_enc=LAYERS,
+                        n_layer_dec=LAYERS)
+    torch.manual_seed(0)
+    return WhisperMoP(cfg).cuda().eval()
+
+
+@__import__("torch").no_grad()
+def torch_beam(m, mel, prompt, K, n_new):
+    """the beam search of WhisperMoP.beam_search (without eos) composed of torch ops: log_softmax + topk, and every layer's
+    self-attention cache copied by parent beam (index_select) at every step"""
+    import torch
+    B, V = prompt.shape[0], m.cfg.vocab_size
+    enc, _ = m.encode(mel)
+    cache = m.init_decode_cache(enc.repeat_interleave(K, 0), prompt.shape[1] + n_new)
+    hist = prompt.repeat_interleave(K, 0)
+    logits = m.decode_step(cache, hist)[:, -1]
+    scores = torch.zeros(B, K, device=mel.device)
+    scores[:, 1:] = float("-inf")
+    base = (torch.arange(B, device=mel.device) * K).unsqueeze(1)
+    for t in range(n_new):
+        cand = (torch.log_softmax(logits.float(), -1).view(B, K, V) + scores.unsqueeze(2)).view(B, K * V)
+        scores, idx = cand.topk(K, dim=1)
+        sel = (base + idx // V).view(-1)
+        tok = (idx % V).view(-1, 1)
+        hist = torch.cat([hist.index_select(0, sel), tok], dim=1)
+        if t == n_new - 1:
+            break
+        for l in range(len(cache.self_k)):
+            cache.self_k[l] = cache.self_k[l].index_select(0, sel)
+            cache.self_v[l] = cache.self_v[l].index_select(0, sel)
+        logits = m.decode_step(cache, tok)[:, -1]
+    return hist.view(B, K, -1)[:, 0], scores[:, 0] / n_new
+
+
+def bench_beam(args):
+    import torch
+    m = _base_model()
+    K = 5
+    for B in args.batch:
+        mel = torch.randn(B, TA, NMELS, device="cuda")
+        prompt = torch.randint(0, VOCAB, (B, TP), device="cuda")
+        outs = {}
+        for name, fn in (("torch_beam", lambda: torch_beam(m, mel, prompt, K, NEW)),
+                         ("beam_search", lambda: m.beam_search(mel, prompt, NEW, K)),
+                         ("beam_search_graph", lambda: m.beam_search(mel, prompt, NEW, K, graph=True))):
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                ms = _time(lambda: outs.__setitem__(name, fn()), args.steps, args.warmup)
+            _emit(args, dict(workload="whisper_beam", variant=name, K=K, B=B, T_a=TA, T_p=TP, new_tokens=NEW, d=D, H=H, layers="6+6",
+                             vocab=VOCAB, dtype="bf16-autocast", total_ms=round(ms, 3), ms_per_token=round(ms / NEW, 4),
+                             steps=args.steps, warmup=args.warmup))
+        _emit(args, dict(workload="whisper_beam_agreement", K=K, B=B,
+                         rows_equal_torch_vs_kernels=(outs["torch_beam"][0] == outs["beam_search"][0]).all(1).float().mean().item(),
+                         graph_equals_eager=bool(torch.equal(outs["beam_search"][0], outs["beam_search_graph"][0]))))
+
+
+def bench_beam_trace(args):
+    import torch
+    m = _base_model()
+    mel = torch.randn(8, TA, NMELS, device="cuda")
+    prompt = torch.randint(0, VOCAB, (8, TP), device="cuda")
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        for _ in range(2):
+            m.beam_search(mel, prompt, NEW, 5)
+    torch.cuda.synchronize()
+
+
 def _core_inputs(Nk):
     import torch
     B = 8
@@ -131,13 +207,17 @@ def bench_core_trace(args):
 def stats(path):
     rows = list(csv.DictReader(open(path)))
     for r in rows:
-        if "da_" in r["Name"] or "sdpa" in r["Name"] or "attention" in r["Name"].lower() or "fmha" in r["Name"].lower():
+        if "da_" in r["Name"] or "sdpa" in r["Name"] or "attention" in r["Name"].lower() or "fmha" in r["Name"].lower() \
+                or "bs_" in r["Name"]:
             print(f"{float(r['AverageNs']) / 1e3:9.2f} us  x{r['Calls']:>5}  {r['Name'][:150]}")
+    B, K, L = 8, 5, TP + NEW // 2
+    print(f"beam bounds at B = {B}, K = {K}: logits {B * K * VOCAB * 2 / HBM_BPS * 1e6:.2f} us; row-indirect attention per layer at "
+          f"L = {L}: {(2 * B * K * L * H * 64 * 2 + 4 * B * K * L) / HBM_BPS * 1e6:.2f} us")
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["generate", "core", "core-trace"], default="generate")
+    ap.add_argument("--workload", choices=["generate", "core", "core-trace", "beam", "beam-trace"], default="generate")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
@@ -148,7 +228,8 @@ def main():
     args = ap.parse_args()
     if args.stats:
         return stats(args.stats)
-    {"generate": bench_generate, "core": bench_core, "core-trace": bench_core_trace}[args.workload](args)
+    {"generate": bench_generate, "core": bench_core, "core-trace": bench_core_trace, "beam": bench_beam,
+     "beam-trace": bench_beam_trace}[args.workload](args)
 
 
 if __name__ == "__main__":
