@@ -129,6 +129,18 @@ class _timed:
         return False
 
 
+def _launch(sym: str, a, key: Optional[str] = None) -> None:
+    """libmopk's `sym` on the args struct `a` and the current stream; with timing on, HIP events around it under `key`
+    (None: never timed)"""
+    fn = getattr(L.lib(), sym)
+    if _TIMING is None or key is None:
+        rc = fn(C.byref(a), _stream())
+    else:
+        with _timed(key):
+            rc = fn(C.byref(a), _stream())
+    L.check(rc, sym)
+
+
 def _bytes(n: int, dev) -> torch.Tensor:
     return torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
 
@@ -151,6 +163,26 @@ def _ew_views(args: L.EdgewiseArgs, qkv: torch.Tensor, prefix: str):
     setattr(args, v0n, L.View4(base + 2 * H * dk * isz, s_b, dk, s_n))
     last = (Vq - 1) * 3 * H * dk
     setattr(args, vLn, L.View4(base + (last + 2 * H * dk) * isz, s_b, dk, s_n))
+
+
+def _ew_args(qkv, y, V, r, prec, path, beta_not=0.0, drop=(0.0, 0), small=None, head=None,
+             mask=(None, (0, 0, 0))) -> L.EdgewiseArgs:
+    """the MopkEdgewiseArgs fields forward and backward share.  y: the (B,N,H,dk) output, or a non-null stand-in where the call
+    writes none; small: float32 (sqk, vs0, vsL, chain_logit), None in a support query; head: the low-rank head's float32
+    (Wr, br, Wc, bc), None otherwise; mask: (uint8 mask or None, strides) from _mask_u8"""
+    B, N, _, _, H, dk = qkv.shape
+    a = L.EdgewiseArgs()
+    a.B, a.H, a.N, a.dk, a.V, a.r = B, H, N, dk, V, r
+    a.io_dtype, a.precision, a.path, a.beta_not = _io_dtype(qkv), prec, path, float(beta_not)
+    a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
+    a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(mask[0]), mask[1]
+    _ew_views(a, qkv, "")
+    a.y = L.View4(y.data_ptr(), N * H * dk, dk, H * dk)
+    if small is not None:
+        a.sqk, a.vs0, a.vsL, a.chain_logit = map(torch.Tensor.data_ptr, small)
+    if head is not None:
+        a.Wr, a.br, a.Wc, a.bc = map(torch.Tensor.data_ptr, head)
+    return a
 
 
 _SAVE_CHAIN_STATE = True
@@ -181,24 +213,16 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
                      _f32_pack([sqk, vs0, vsL, Wr, br, Wc, bc, logit.reshape(1)])))
         ctx.small_dtype = sqk.dtype if len({t.dtype for t in (sqk, vs0, vsL, Wr, br, Wc, bc, logit)}) == 1 else None
         r = f["Wr"].shape[0] // 4
-        a = L.EdgewiseArgs()
-        a.B, a.H, a.N, a.dk, a.V, a.r = B, H, N, dk, V, r
-        a.io_dtype, a.precision, a.path, a.beta_not = _io_dtype(qkv), prec, path, float(beta_not)
-        _ew_views(a, qkv, "")
-        a.sqk, a.vs0, a.vsL = f["sqk"].data_ptr(), f["vs0"].data_ptr(), f["vsL"].data_ptr()
-        a.Wr, a.br, a.Wc, a.bc = (f["Wr"].data_ptr(), f["br"].data_ptr(), f["Wc"].data_ptr(),
-                                  f["bc"].data_ptr())
-        a.chain_logit = f["logit"].data_ptr()
         y = torch.empty(B, N, H, dk, dtype=qkv.dtype, device=dev)
-        a.y = L.View4(y.data_ptr(), N * H * dk, dk, H * dk)
+        a = _ew_args(qkv, y, V, r, prec, path, beta_not, drop, (f["sqk"], f["vs0"], f["vsL"], f["logit"]),
+                     (f["Wr"], f["br"], f["Wc"], f["bc"]))
         extras = ()
         ctx.lens_dil, ctx.lens_dtype = tuple(lens_dil), (None if lens_w is None else lens_w.dtype)
         if n_extra:
             lens_w = _f32c(lens_w)
             row_x, col_x = lens_means_hip(qkv, f["sqk"], lens_w, lens_dil)
             extras = (row_x, col_x, lens_w)
-            ext = L.EdgewiseExt()
-            ext.n_extra, ext.row_extra, ext.col_extra = n_extra, extras[0].data_ptr(), extras[1].data_ptr()
+            ext = _extra_ext(n_extra, row_x, col_x)
             a.ext = C.pointer(ext)
             if path == L.PATH_GENERIC or not lib.mopk_edgewise_fused_supported(C.byref(a)):
                 raise NotImplementedError("extra feature channels are an input of the fused Edgewise kernels only")
@@ -206,7 +230,6 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
         if path == L.PATH_AUTO:   # AUTO: fused gfx950 kernels when they cover the shape, generic otherwise
             path = L.PATH_FUSED if lib.mopk_edgewise_fused_supported(C.byref(a)) else L.PATH_GENERIC
         a.path = path
-        a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
         # training forward of the fused path also exports the chain state its backward would otherwise recompute
         a.save_for_backward = int(bool(want_bwd) and path == L.PATH_FUSED and _SAVE_CHAIN_STATE)
         LAST_PATH["edgewise_fwd"] = path
@@ -215,9 +238,7 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
         if _KEEP_WS:
             LAST_PATH["_fwd_ws"] = ws  # diagnostics only (stamp builds read it back): pins the buffer until the next call
-        with _timed("edgewise_fwd"):
-            rc = lib.mopk_edgewise_lowrank_fwd(C.byref(a), _stream())
-        L.check(rc, "mopk_edgewise_lowrank_fwd")
+        _launch("mopk_edgewise_lowrank_fwd", a, "edgewise_fwd")
         ctx.save_for_backward(qkv, saved, *f.values(), *extras)
         ctx.meta = (beta_not, V, prec, path, r, int(a.save_for_backward), drop)
         return y.view(B, N, H * dk)
@@ -232,16 +253,9 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
         dy = dy.contiguous()
         if dy.dtype != qkv.dtype:
             dy = dy.to(qkv.dtype)
-        a = L.EdgewiseArgs()
-        a.B, a.H, a.N, a.dk, a.V, a.r = B, H, N, dk, V, r
-        a.io_dtype, a.precision, a.path, a.beta_not = _io_dtype(qkv), prec, path, float(beta_not)
+        # a.y = dy: unused by bwd, must be non-null
+        a = _ew_args(qkv, dy, V, r, prec, path, beta_not, drop, (sqk, vs0, vsL, logit), (Wr, br, Wc, bc))
         a.save_for_backward = sfb
-        a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
-        _ew_views(a, qkv, "")
-        a.sqk, a.vs0, a.vsL = sqk.data_ptr(), vs0.data_ptr(), vsL.data_ptr()
-        a.Wr, a.br, a.Wc, a.bc = Wr.data_ptr(), br.data_ptr(), Wc.data_ptr(), bc.data_ptr()
-        a.chain_logit = logit.data_ptr()
-        a.y = L.View4(dy.data_ptr(), N * H * dk, dk, H * dk)  # unused by bwd, must be non-null
         a.dy = L.View4(dy.data_ptr(), N * H * dk, dk, H * dk)
         # unshared: only v of view 0 and V-1 receive gradient -> zero-fill the rest
         dqkv = (torch.empty_like(qkv) if Vq == 1 else torch.zeros_like(qkv))
@@ -252,8 +266,7 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
         d_extras = None
         if n_extra:
             d_extras = (torch.empty_like(extras[0]), torch.empty_like(extras[1]))
-            ext = L.EdgewiseExt()
-            ext.n_extra, ext.row_extra, ext.col_extra = n_extra, extras[0].data_ptr(), extras[1].data_ptr()
+            ext = _extra_ext(n_extra, extras[0], extras[1])
             ext.d_row_extra, ext.d_col_extra = d_extras[0].data_ptr(), d_extras[1].data_ptr()
             a.ext = C.pointer(ext)
         # per-batch partials of the small gradients, and ONE buffer for their final values (reduced by the library in a single
@@ -271,9 +284,7 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
         if _KEEP_WS:
             LAST_PATH["_bwd_ws"] = ws  # diagnostics only (stamp builds read it back): pins the buffer until the next call
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        with _timed("edgewise_bwd"):
-            rc = lib.mopk_edgewise_lowrank_bwd(C.byref(a), _stream())
-        L.check(rc, "mopk_edgewise_lowrank_bwd")
+        _launch("mopk_edgewise_lowrank_bwd", a, "edgewise_bwd")
         L.check(lib.mopk_edgewise_reduce_parts(C.byref(a), dsqk.data_ptr(), dvs0.data_ptr(), dvsL.data_ptr(), dlg.data_ptr(),
                                                _stream()), "mopk_edgewise_reduce_parts")
         dlens = None
@@ -297,13 +308,26 @@ class EdgewiseVariant:
             raise ValueError(f"at most {L.MAX_LENS} lens dilations are supported")
 
 
-def _fill_ext(ext: L.EdgewiseExt, var: EdgewiseVariant, t: dict):
+def _extra_ext(n_extra: int, row, col) -> L.EdgewiseExt:
+    """MopkEdgewiseExt of a low-rank call whose head takes n_extra lens-mean channels; row / col: their (B,H,E,N) means"""
+    ext = L.EdgewiseExt()
+    ext.n_extra, ext.row_extra, ext.col_extra = n_extra, row.data_ptr(), col.data_ptr()
+    return ext
+
+
+def _variant_ext(var: EdgewiseVariant, f: dict) -> L.EdgewiseExt:
+    """MopkEdgewiseExt of an _EdgewiseGeneralFn call; f: its float32 tensors (head h0..h3, W3, b3, lens_w)"""
+    ext = L.EdgewiseExt()
     ext.gate_mode, ext.use_k3, ext.n_lens = int(var.dense), int(var.use_k3), len(var.lens_dilations)
     for i, d in enumerate(var.lens_dilations):
         ext.lens_dil[i] = d
-    for k in ("lens_w", "W1", "b1", "W3", "b3", "W2", "b2"):
-        if t.get(k) is not None:
-            setattr(ext, k, t[k].data_ptr())
+    if var.lens_dilations:
+        ext.lens_w = f["lens_w"].data_ptr()
+    if var.dense:
+        ext.W1, ext.b1, ext.W2, ext.b2 = f["h0"].data_ptr(), f["h1"].data_ptr(), f["h2"].data_ptr(), f["h3"].data_ptr()
+        if var.use_k3:
+            ext.W3, ext.b3 = f["W3"].data_ptr(), f["b3"].data_ptr()
+    return ext
 
 
 class _EdgewiseGeneralFn(torch.autograd.Function):
@@ -322,37 +346,24 @@ class _EdgewiseGeneralFn(torch.autograd.Function):
         dev = qkv.device
         f = dict(sqk=_f32c(sqk), vs0=_f32c(vs0), vsL=_f32c(vsL), logit=_f32c(logit).reshape(1),
                  h0=_f32c(h0), h1=_f32c(h1), h2=_f32c(h2), h3=_f32c(h3), W3=_f32c(W3), b3=_f32c(b3), lens_w=_f32c(lens_w))
-        a, ext = L.EdgewiseArgs(), L.EdgewiseExt()
-        a.B, a.H, a.N, a.dk, a.V = B, H, N, dk, V
-        a.r = 1 if var.dense else f["h0"].shape[0] // 4
-        a.io_dtype, a.precision, a.path, a.beta_not = _io_dtype(qkv), prec, L.PATH_GENERIC, float(beta_not)
-        _ew_views(a, qkv, "")
-        a.sqk, a.vs0, a.vsL, a.chain_logit = f["sqk"].data_ptr(), f["vs0"].data_ptr(), f["vsL"].data_ptr(), f["logit"].data_ptr()
-        if var.dense:
-            _fill_ext(ext, var, dict(lens_w=f["lens_w"] if var.lens_dilations else None, W1=f["h0"], b1=f["h1"], W2=f["h2"], b2=f["h3"],
-                                     W3=f["W3"] if var.use_k3 else None, b3=f["b3"] if var.use_k3 else None))
-        else:
-            a.Wr, a.br, a.Wc, a.bc = f["h0"].data_ptr(), f["h1"].data_ptr(), f["h2"].data_ptr(), f["h3"].data_ptr()
-            _fill_ext(ext, var, dict(lens_w=f["lens_w"] if var.lens_dilations else None))
-        a.ext = C.pointer(ext)
         y = torch.empty(B, N, H, dk, dtype=qkv.dtype, device=dev)
-        a.y = L.View4(y.data_ptr(), N * H * dk, dk, H * dk)
+        m8, ms = _mask_u8(mask, B, H, N, dev)
+        small, head = (f["sqk"], f["vs0"], f["vsL"], f["logit"]), (f["h0"], f["h1"], f["h2"], f["h3"])
+        a = _ew_args(qkv, y, V, 1 if var.dense else f["h0"].shape[0] // 4, prec, L.PATH_GENERIC, beta_not, drop, small,
+                     None if var.dense else head, (m8, ms))
+        ext = _variant_ext(var, f)
+        a.ext = C.pointer(ext)
         # dense head without the 3x3 convolution / lens bank: the fused kernels evaluate it inside their mix loops (the backward
         # keeps dW1[k][:] and db1[k] in one 16-slot row, i.e. covers V <= 6)
-        m8, ms = _mask_u8(mask, B, H, N, dev)
-        a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(m8), ms
         if var.dense and not var.use_k3 and not var.lens_dilations and m8 is None and _PATH != L.PATH_GENERIC and (not wants_grad or V <= 6):
             a.path, a.save_for_backward = L.PATH_FUSED, 1
             if not lib.mopk_edgewise_fused_supported(C.byref(a)):
                 a.path, a.save_for_backward = L.PATH_GENERIC, 0
-        a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
         LAST_PATH["edgewise_fwd"] = int(a.path)
         saved = _bytes(lib.mopk_edgewise_saved_bytes(C.byref(a)), dev)
         ws = _bytes(256 if a.path == L.PATH_FUSED else lib.mopk_edgewise_workspace_bytes(C.byref(a)), dev)
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        with _timed("edgewise_fwd"):
-            rc = lib.mopk_edgewise_fwd(C.byref(a), _stream())
-        L.check(rc, "mopk_edgewise_fwd")
+        _launch("mopk_edgewise_fwd", a, "edgewise_fwd")
         ctx.save_for_backward(qkv, saved, *f.values())
         ctx.keys = list(f.keys())
         ctx.meta = (beta_not, V, prec, var, int(a.r))
@@ -371,15 +382,9 @@ class _EdgewiseGeneralFn(torch.autograd.Function):
         dy = dy.contiguous()
         if dy.dtype != qkv.dtype:
             dy = dy.to(qkv.dtype)
-        a, ext = L.EdgewiseArgs(), L.EdgewiseExt()
-        a.B, a.H, a.N, a.dk, a.V, a.r = B, H, N, dk, V, r
-        a.io_dtype, a.precision, a.path, a.beta_not = _io_dtype(qkv), prec, path, float(beta_not)
+        small, head = (f["sqk"], f["vs0"], f["vsL"], f["logit"]), (f["h0"], f["h1"], f["h2"], f["h3"])
+        a = _ew_args(qkv, dy, V, r, prec, path, beta_not, ctx.drop, small, None if var.dense else head, ctx.mask)
         a.save_for_backward = int(path == L.PATH_FUSED)
-        a.dropout_p, a.dropout_seed = float(ctx.drop[0]), int(ctx.drop[1])
-        a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(ctx.mask[0]), ctx.mask[1]
-        _ew_views(a, qkv, "")
-        a.sqk, a.vs0, a.vsL, a.chain_logit = f["sqk"].data_ptr(), f["vs0"].data_ptr(), f["vsL"].data_ptr(), f["logit"].data_ptr()
-        a.y = L.View4(dy.data_ptr(), N * H * dk, dk, H * dk)
         a.dy = L.View4(dy.data_ptr(), N * H * dk, dk, H * dk)
         dqkv = (torch.empty_like(qkv) if Vq == 1 else torch.zeros_like(qkv))
         _ew_views(a, dqkv, "d")
@@ -387,26 +392,20 @@ class _EdgewiseGeneralFn(torch.autograd.Function):
         dsqk, dvs0, dvsL, dlg = torch.empty(B, V, H, dk, **f32), torch.empty(B, H, dk, **f32), torch.empty(B, H, dk, **f32), torch.empty(B, H, **f32)
         a.dsqk_part, a.dvs0_part, a.dvsL_part, a.dlogit_part = dsqk.data_ptr(), dvs0.data_ptr(), dvsL.data_ptr(), dlg.data_ptr()
         g = {k: torch.zeros_like(f[k]) for k in ("h0", "h1", "h2", "h3", "W3", "b3", "lens_w")}
-        lens = f["lens_w"] if var.lens_dilations else None
+        ext = _variant_ext(var, f)
         if var.dense:
-            _fill_ext(ext, var, dict(lens_w=lens, W1=f["h0"], b1=f["h1"], W2=f["h2"], b2=f["h3"],
-                                     W3=f["W3"] if var.use_k3 else None, b3=f["b3"] if var.use_k3 else None))
             ext.dW1, ext.db1, ext.dW2, ext.db2 = g["h0"].data_ptr(), g["h1"].data_ptr(), g["h2"].data_ptr(), g["h3"].data_ptr()
             if var.use_k3:
                 ext.dW3, ext.db3 = g["W3"].data_ptr(), g["b3"].data_ptr()
         else:
-            a.Wr, a.br, a.Wc, a.bc = f["h0"].data_ptr(), f["h1"].data_ptr(), f["h2"].data_ptr(), f["h3"].data_ptr()
             a.dWr, a.dbr, a.dWc, a.dbc = g["h0"].data_ptr(), g["h1"].data_ptr(), g["h2"].data_ptr(), g["h3"].data_ptr()
-            _fill_ext(ext, var, dict(lens_w=lens))
         if var.lens_dilations:
             ext.dlens_w = g["lens_w"].data_ptr()
         a.ext = C.pointer(ext)
         LAST_PATH["edgewise_bwd"] = path
         ws = _bytes(lib.mopk_edgewise_workspace_bytes(C.byref(a)), dev)
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        with _timed("edgewise_bwd"):
-            rc = lib.mopk_edgewise_bwd(C.byref(a), _stream())
-        L.check(rc, "mopk_edgewise_bwd")
+        _launch("mopk_edgewise_bwd", a, "edgewise_bwd")
         return (dqkv, dsqk.sum(0), dvs0.sum(0), dvsL.sum(0), dlg.sum().reshape(()), g["h0"], g["h1"], g["h2"], g["h3"],
                 g["W3"], g["b3"], g["lens_w"], None, None, None, None, None, None, None)
 
@@ -453,7 +452,7 @@ def edgewise_general_core(qkv, sqk, vs0, vsL, chain_logit, head, beta_not: float
         return _empty_batch(qkv, 0, qkv.shape[1], qkv.shape[-2] * qkv.shape[-1])
     prec = _prec_for(qkv.dtype) if precision is None else precision
     e = qkv.new_zeros(0, dtype=torch.float32)
-    drop = (float(dropout_p), (dropout_seed() if seed is None else int(seed))) if dropout_p > 0 else (0.0, 0)
+    drop = _drop(dropout_p, seed)
     # decided here: inside Function.forward autograd is already switched off
     wants_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad
                                                  for t in (qkv, sqk, vs0, vsL, chain_logit, *head, W3, b3, lens_w))
@@ -528,13 +527,16 @@ def _lens_unshift(dM, dil, dmax, N, V):
                         for l, d in enumerate(dil)], 2).reshape(B, H, -1, N)
 
 
-def _lens_args(qkv, sqk, lens_w, dilations) -> L.LensMeansArgs:
+def _lens_args(qkv, sqk, lens_w, dilations, V: int = 0) -> L.LensMeansArgs:
+    """the call's MopkLensMeansArgs; sqk = lens_w = None (support query): the shape of V views only, no dtype or pointers"""
     B, N, _, _, H, dk = qkv.shape
     a = L.LensMeansArgs()
-    a.B, a.H, a.N, a.dk, a.V, a.L = B, H, N, dk, sqk.shape[0], len(dilations)
-    a.io_dtype = _io_dtype(qkv)
+    a.B, a.H, a.N, a.dk, a.V, a.L = B, H, N, dk, V if sqk is None else sqk.shape[0], len(dilations)
     for i, d in enumerate(dilations):
         a.dil[i] = int(d)
+    if sqk is None:
+        return a
+    a.io_dtype = _io_dtype(qkv)
     s_n = 3 * H * dk
     a.q = L.View4(qkv.data_ptr(), N * s_n, dk, s_n)
     a.k = L.View4(qkv.data_ptr() + H * dk * qkv.element_size(), N * s_n, dk, s_n)
@@ -551,7 +553,7 @@ def lens_means_hip(qkv, sqk, lens_w, dilations):
     a = _lens_args(qkv, sqk, lens_w, dilations)
     row, col = torch.empty(B, H, E, N, dtype=torch.float32, device=qkv.device), torch.empty(B, H, E, N, dtype=torch.float32, device=qkv.device)
     a.row, a.col = row.data_ptr(), col.data_ptr()
-    L.check(L.lib().mopk_lens_means_fwd(C.byref(a), _stream()), "mopk_lens_means_fwd")
+    _launch("mopk_lens_means_fwd", a)
     return row, col
 
 
@@ -566,7 +568,7 @@ def lens_means_bwd_hip(d_row, d_col, qkv, dqkv, sqk, lens_w, dilations):
     dsqk_p = torch.empty(B, V, H, dk, dtype=torch.float32, device=qkv.device)
     dlens_p = torch.empty(B * H, Ln, V, 3, 3, dtype=torch.float32, device=qkv.device)
     a.d_row, a.d_col, a.dsqk_part, a.dlens_part = d_row.data_ptr(), d_col.data_ptr(), dsqk_p.data_ptr(), dlens_p.data_ptr()
-    L.check(L.lib().mopk_lens_means_bwd(C.byref(a), _stream()), "mopk_lens_means_bwd")
+    _launch("mopk_lens_means_bwd", a)
     return dsqk_p.sum(0), dlens_p.sum(0)
 
 
@@ -625,20 +627,11 @@ def lowrank_lens_fused_supported(qkv, n_views: int, rank: int, dilations, precis
         return False
     if not 1 <= n_lens <= L.MAX_LENS:
         return False
-    B, N, _, _, H, dk = qkv.shape
-    lm = L.LensMeansArgs()
-    lm.B, lm.H, lm.N, lm.dk, lm.V, lm.L = B, H, N, dk, n_views, n_lens
-    for i, d in enumerate(dilations):
-        lm.dil[i] = int(d)
-    if not L.lib().mopk_lens_means_supported(C.byref(lm), 1):
+    if not L.lib().mopk_lens_means_supported(C.byref(_lens_args(qkv, None, None, dilations, n_views)), 1):
         return False
-    a, ext = L.EdgewiseArgs(), L.EdgewiseExt()
-    a.B, a.H, a.N, a.dk, a.V, a.r = B, H, N, dk, n_views, rank
-    a.io_dtype, a.path = _io_dtype(qkv), L.PATH_FUSED
-    a.precision = _prec_for(qkv.dtype) if precision is None else precision
-    _ew_views(a, qkv, "")
-    a.y = L.View4(qkv.data_ptr(), N * H * dk, dk, H * dk)
-    ext.n_extra, ext.row_extra, ext.col_extra = n_lens * n_views, qkv.data_ptr(), qkv.data_ptr()      # non-null stand-ins: nothing is read
+    # qkv: non-null stand-in for y and the extra channels, nothing is read
+    a = _ew_args(qkv, qkv, n_views, rank, _prec_for(qkv.dtype) if precision is None else precision, L.PATH_FUSED)
+    ext = _extra_ext(n_lens * n_views, qkv, qkv)
     a.ext = C.pointer(ext)
     return bool(L.lib().mopk_edgewise_fused_supported(C.byref(a)))
 
@@ -650,10 +643,10 @@ def edgewise_lowrank_core(qkv, sqk, vs0, vsL, Wr, br, Wc, bc, chain_logit, beta_
     """qkv: (B,N,Vq,3,H,dk) with Vq in {1 (share_qkv), n_views}; returns (B,N,H*dk).  dropout_p > 0: attn_drop on the mixed
     attention weights (:552) inside the fused kernels (see `sdpa_core`).  lens_w (L,V,3,3) + lens_dilations: the S lens bank, fed to
     the fused kernels as extra mean-feature channels (`lens_mean_features` states the closed form; the Function evaluates it and its
-    backward by hand, `_lens_means_fwd` / `_lens_means_bwd`; callers check `lowrank_lens_fused_supported` first)."""
+    backward with libmopk's kernels, `lens_means_hip` / `lens_means_bwd_hip`; callers check `lowrank_lens_fused_supported` first)."""
     if qkv.shape[0] == 0:
         return _empty_batch(qkv, 0, qkv.shape[1], qkv.shape[-2] * qkv.shape[-1])
-    drop = (float(dropout_p), (dropout_seed() if seed is None else int(seed))) if dropout_p > 0 else (0.0, 0)
+    drop = _drop(dropout_p, seed)
     prec = _prec_for(qkv.dtype) if precision is None else precision
     want_bwd = torch.is_grad_enabled() and any(
         t is not None and t.requires_grad for t in (qkv, sqk, vs0, vsL, Wr, br, Wc, bc, chain_logit, lens_w))
@@ -698,6 +691,19 @@ def _bias_f32(bias, B, H, N, dev, Nk=None):
     return b, (b.stride(0), b.stride(1), b.stride(2))
 
 
+def _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop) -> L.SdpaArgs:
+    """the MopkSdpaArgs fields forward and backward share; mask / bias: (tensor or None, strides) from _mask_u8 / _bias_f32"""
+    B, N, H, dk = q.shape
+    a = L.SdpaArgs()
+    a.B, a.H, a.N, a.dk, a.Nk = B, H, N, dk, k.shape[1]
+    a.io_dtype, a.precision, a.path, a.causal = _io_dtype(q), prec, path, int(bool(causal))
+    a.q, a.k, a.v, a.y = _v4(q), _v4(k), _v4(v), _v4(y)
+    a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(mask[0]), mask[1]
+    a.bias, (a.bias_sb, a.bias_sh, a.bias_si) = _ptr(bias[0]), bias[1]
+    a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
+    return a
+
+
 class _SdpaFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, mask, bias, causal, prec, path, drop=(0.0, 0)):
@@ -712,17 +718,9 @@ class _SdpaFn(torch.autograd.Function):
         B, N, H, dk = q.shape
         Nk = k.shape[1]                # key / value length (cross-attention); N for self-attention
         dev = q.device
-        a = L.SdpaArgs()
-        a.B, a.H, a.N, a.dk, a.Nk = B, H, N, dk, Nk
-        a.io_dtype, a.precision, a.path, a.causal = _io_dtype(q), prec, path, int(bool(causal))
-        a.q, a.k, a.v = _v4(q), _v4(k), _v4(v)
-        m8, ms = _mask_u8(mask, B, H, N, dev, Nk)
-        bf, bs = _bias_f32(bias, B, H, N, dev, Nk)
-        a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(m8), ms
-        a.bias, (a.bias_sb, a.bias_sh, a.bias_si) = _ptr(bf), bs
-        a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
+        mask, bias = _mask_u8(mask, B, H, N, dev, Nk), _bias_f32(bias, B, H, N, dev, Nk)
         y = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
-        a.y = _v4(y)
+        a = _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop)
         if path == L.PATH_AUTO:       # resolve once so forward, backward and the size queries agree
             path = L.PATH_FUSED if lib.mopk_sdpa_fused_supported(C.byref(a)) else L.PATH_GENERIC
             a.path = path
@@ -730,29 +728,22 @@ class _SdpaFn(torch.autograd.Function):
         saved = _bytes(lib.mopk_sdpa_saved_bytes(C.byref(a)), dev)
         ws = _bytes(lib.mopk_sdpa_workspace_bytes(C.byref(a)), dev)
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        with _timed("sdpa_fwd"):
-            rc = lib.mopk_sdpa_fwd(C.byref(a), _stream())
-        L.check(rc, "mopk_sdpa_fwd")
+        _launch("mopk_sdpa_fwd", a, "sdpa_fwd")
         ctx.save_for_backward(q, k, v, y, saved)
-        ctx.meta = (causal, prec, path, m8, ms, bf, bs, drop)
+        ctx.meta = (causal, prec, path, mask, bias, drop)
         return y.view(B, N, H * dk)
 
     @staticmethod
     def backward(ctx, dy):
         lib = L.lib()
         q, k, v, y, saved = ctx.saved_tensors
-        causal, prec, path, m8, ms, bf, bs, drop = ctx.meta
+        causal, prec, path, mask, bias, drop = ctx.meta
         B, N, H, dk = q.shape
         Nk = k.shape[1]
         dev = q.device
         dy = dy.contiguous().to(q.dtype).view(B, N, H, dk)
-        a = L.SdpaArgs()
-        a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
-        a.B, a.H, a.N, a.dk, a.Nk = B, H, N, dk, Nk
-        a.io_dtype, a.precision, a.path, a.causal = _io_dtype(q), prec, path, int(bool(causal))
-        a.q, a.k, a.v, a.y, a.dy = _v4(q), _v4(k), _v4(v), _v4(y), _v4(dy)
-        a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(m8), ms
-        a.bias, (a.bias_sb, a.bias_sh, a.bias_si) = _ptr(bf), bs
+        a = _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop)
+        a.dy = _v4(dy)
         if ctx.packed:
             dqkv = torch.empty(B, N, 3, H, dk, dtype=q.dtype, device=dev)
             dq, dk_, dv = dqkv.unbind(2)
@@ -763,9 +754,7 @@ class _SdpaFn(torch.autograd.Function):
         LAST_PATH["sdpa_bwd"] = path
         ws = _bytes(lib.mopk_sdpa_workspace_bytes(C.byref(a)), dev)
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        with _timed("sdpa_bwd"):
-            rc = lib.mopk_sdpa_bwd(C.byref(a), _stream())
-        L.check(rc, "mopk_sdpa_bwd")
+        _launch("mopk_sdpa_bwd", a, "sdpa_bwd")
         if ctx.packed:
             return dqkv, None, None, None, None, None, None, None, None
         return dq, dk_, dv, None, None, None, None, None, None
@@ -775,6 +764,11 @@ def dropout_seed() -> int:
     """a fresh 63-bit seed for the in-kernel dropout mask, drawn from torch's CPU generator (so `torch.manual_seed` makes runs
     reproducible, like it does for `nn.Dropout`)"""
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+
+
+def _drop(dropout_p: float, seed: Optional[int]) -> tuple:
+    """(p, seed) of a core's in-kernel dropout: a fresh seed when none is given, (0.0, 0) when off"""
+    return (float(dropout_p), (dropout_seed() if seed is None else int(seed))) if dropout_p > 0 else (0.0, 0)
 
 
 def dropout_keep_mask(seed: int, p: float, B: int, H: int, N: int, Nk: Optional[int] = None) -> torch.Tensor:
@@ -819,11 +813,25 @@ def sdpa_core(q, k=None, v=None, attn_mask=None, bias=None, causal=False, dropou
         if k is None:
             return _empty_batch(q, 0, q.shape[1], q.shape[-2] * q.shape[-1])
         return _empty_batch(q, 0, q.shape[1], q.shape[2] * q.shape[3]) + (k.sum() + v.sum()) * 0
-    drop = (float(dropout_p), (dropout_seed() if seed is None else int(seed))) if dropout_p > 0 else (0.0, 0)
+    drop = _drop(dropout_p, seed)
     return _SdpaFn.apply(q, k, v, attn_mask, bias, causal, _prec_for(q.dtype), _PATH, drop)
 
 
 _ANCHOR_MODES = {"fixed": 0, "argmax_row_sum": 1}          # any other string -> row 0 (reference :141-145)
+
+
+def _cv_args(ts, mx, y, cfg, mask, causal, prec, drop) -> L.CrossViewArgs:
+    """the MopkCrossViewArgs fields forward and backward share; ts: the five (B,N,H,dk) views q1 k1 v1 q2 k2, mx: float32 mix"""
+    B, N, H, dk = ts[0].shape
+    a = L.CrossViewArgs()
+    a.B, a.H, a.N, a.dk = B, H, N, dk
+    a.io_dtype, a.precision, a.path, a.causal = _io_dtype(ts[0]), prec, L.PATH_GENERIC, int(bool(causal))
+    a.t1, a.t2, a.prior_weight, a.use_prior, a.anchor_mode, a.fixed_k_star = cfg
+    a.q1, a.k1, a.v1, a.q2, a.k2 = (_v4(t) for t in ts)
+    a.mix, a.y = mx.data_ptr(), _v4(y)
+    a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(mask[0]), mask[1]
+    a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
+    return a
 
 
 class _CrossViewFn(torch.autograd.Function):
@@ -837,57 +845,49 @@ class _CrossViewFn(torch.autograd.Function):
         B, N, H, dk = ts[0].shape
         dev = ts[0].device
         mx = _f32c(mix).reshape(4)
-        a = L.CrossViewArgs()
-        a.B, a.H, a.N, a.dk = B, H, N, dk
-        a.io_dtype, a.precision, a.path, a.causal = _io_dtype(ts[0]), prec, L.PATH_GENERIC, int(bool(causal))
-        a.t1, a.t2, a.prior_weight, a.use_prior, a.anchor_mode, a.fixed_k_star = cfg
-        a.q1, a.k1, a.v1, a.q2, a.k2 = (_v4(t) for t in ts)
-        a.mix = mx.data_ptr()
-        m8, ms = _mask_u8(mask, B, H, N, dev)
-        a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(m8), ms
-        a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
+        mask = _mask_u8(mask, B, H, N, dev)
         y = torch.empty(B, N, H, dk, dtype=ts[0].dtype, device=dev)
-        a.y = _v4(y)
+        a = _cv_args(ts, mx, y, cfg, mask, causal, prec, drop)
         kst = torch.zeros(B, H, dtype=torch.int32, device=dev)
         a.k_star = kst.data_ptr()
         saved = _bytes(lib.mopk_crossview_saved_bytes(C.byref(a)), dev)
         ws = _bytes(lib.mopk_crossview_workspace_bytes(C.byref(a)), dev)
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        with _timed("crossview_fwd"):
-            rc = lib.mopk_crossview_fwd(C.byref(a), _stream())
-        L.check(rc, "mopk_crossview_fwd")
+        _launch("mopk_crossview_fwd", a, "crossview_fwd")
         LAST_PATH["crossview_k_star"] = kst
         ctx.save_for_backward(*ts, mx, saved)
-        ctx.meta = (cfg, causal, prec, m8, ms, drop)
+        ctx.meta = (cfg, causal, prec, mask, drop)
         return y.view(B, N, H * dk)
 
     @staticmethod
     def backward(ctx, dy):
         lib = L.lib()
         *ts, mx, saved = ctx.saved_tensors
-        cfg, causal, prec, m8, ms, drop = ctx.meta
+        cfg, causal, prec, mask, drop = ctx.meta
         B, N, H, dk = ts[0].shape
         dev = ts[0].device
         dy = dy.contiguous().to(ts[0].dtype).view(B, N, H, dk)
-        a = L.CrossViewArgs()
-        a.B, a.H, a.N, a.dk = B, H, N, dk
-        a.io_dtype, a.precision, a.path, a.causal = _io_dtype(ts[0]), prec, L.PATH_GENERIC, int(bool(causal))
-        a.t1, a.t2, a.prior_weight, a.use_prior, a.anchor_mode, a.fixed_k_star = cfg
-        a.q1, a.k1, a.v1, a.q2, a.k2 = (_v4(t) for t in ts)
-        a.mix = mx.data_ptr()
-        a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(m8), ms
-        a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
-        a.y, a.dy = _v4(dy), _v4(dy)
+        a = _cv_args(ts, mx, dy, cfg, mask, causal, prec, drop)          # a.y = dy: unused by bwd, must be non-null
+        a.dy = _v4(dy)
         outs = [torch.empty(B, N, H, dk, dtype=ts[0].dtype, device=dev) for _ in range(5)]
         a.dq1, a.dk1, a.dv1, a.dq2, a.dk2 = (_v4(t) for t in outs)
         dmix = torch.empty(B, H, 4, dtype=torch.float32, device=dev)
         a.dmix_part = dmix.data_ptr()
         ws = _bytes(lib.mopk_crossview_workspace_bytes(C.byref(a)), dev)
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        with _timed("crossview_bwd"):
-            rc = lib.mopk_crossview_bwd(C.byref(a), _stream())
-        L.check(rc, "mopk_crossview_bwd")
+        _launch("mopk_crossview_bwd", a, "crossview_bwd")
         return (*outs, dmix.sum((0, 1)).view(2, 2), None, None, None, None, None)
+
+
+def _cv_folds(t1, t2, prior_weight, prec, dk) -> bool:
+    """the 2x2 mix folds into the dual-path kernels: no transpose cues or prior, fused path allowed, bf16 arithmetic, dk 32 / 64"""
+    return (prior_weight <= 0.0 and t1 == 0.0 and t2 == 0.0 and _PATH != L.PATH_GENERIC and prec == L.PREC_BF16
+            and dk in (32, 64))
+
+
+def _cv_mixed_keys(m, k1, k2):
+    """S = q1 (m11 k1 + m12 k2)^T + q2 (m21 k1 + m22 k2)^T: the mixed keys k1', k2' (contiguous) from m, the mix in k1's dtype"""
+    return (m[0, 0] * k1 + m[0, 1] * k2).contiguous(), (m[1, 0] * k1 + m[1, 1] * k2).contiguous()
 
 
 @_half_via_fp32
@@ -897,14 +897,11 @@ def crossview_core(q1, k1, v1, q2, k2, mix, t1=0.0, t2=0.0, prior_weight=0.0, an
     if q1.shape[0] == 0:
         return _empty_batch(q1, 0, q1.shape[1], q1.shape[2] * q1.shape[3])
     prec = _prec_for(q1.dtype)
-    drop = (float(dropout_p), (dropout_seed() if seed is None else int(seed))) if dropout_p > 0 else (0.0, 0)
-    if (prior_weight <= 0.0 and t1 == 0.0 and t2 == 0.0 and _PATH != L.PATH_GENERIC and prec == L.PREC_BF16
-            and q1.shape[-1] in (32, 64)):
-        # S = q1 (m11 k1 + m12 k2)^T + q2 (m21 k1 + m22 k2)^T: the 2x2 mix folds into two mixed key tensors (autograd carries
-        # d mix, d k1, d k2) and the core is the fused two-score attention (dual-path kernels without the transport term)
-        m = mix.to(k1.dtype)
-        k1p = (m[0, 0] * k1 + m[0, 1] * k2).contiguous()
-        k2p = (m[1, 0] * k1 + m[1, 1] * k2).contiguous()
+    drop = _drop(dropout_p, seed)
+    if _cv_folds(t1, t2, prior_weight, prec, q1.shape[-1]):
+        # the 2x2 mix folds into two mixed key tensors (autograd carries d mix, d k1, d k2) and the core is the fused two-score
+        # attention (dual-path kernels without the transport term)
+        k1p, k2p = _cv_mixed_keys(mix.to(k1.dtype), k1, k2)
         zero = q1.new_zeros((), dtype=torch.float32)
         LAST_PATH["crossview_fwd"] = L.PATH_FUSED
         return _DualPathFn.apply(q1, k1p, v1, q2, k2p, v1, zero, (1.0, 0.0, 0.0, 0.0), 0.0, 0, attn_mask, causal, prec, L.PATH_FUSED, drop)
@@ -922,9 +919,8 @@ def crossview_core_packed(qkv1, qkv2, mix, t1=0.0, t2=0.0, prior_weight=0.0, anc
     if qkv1.shape[0] == 0:
         return _empty_batch(qkv1, 0, qkv1.shape[1], qkv1.shape[-2] * qkv1.shape[-1])
     prec = _prec_for(qkv1.dtype)
-    if (prior_weight <= 0.0 and t1 == 0.0 and t2 == 0.0 and _PATH != L.PATH_GENERIC and prec == L.PREC_BF16
-            and qkv1.shape[-1] in (32, 64) and qkv1.dtype != torch.float16):
-        drop = (float(dropout_p), (dropout_seed() if seed is None else int(seed))) if dropout_p > 0 else (0.0, 0)
+    if _cv_folds(t1, t2, prior_weight, prec, qkv1.shape[-1]):
+        drop = _drop(dropout_p, seed)
         LAST_PATH["crossview_fwd"] = L.PATH_FUSED
         return _CrossViewFoldedFn.apply(qkv1, qkv2, mix, attn_mask, causal, prec, drop)
     return crossview_core(qkv1[:, :, 0], qkv1[:, :, 1], qkv1[:, :, 2], qkv2[:, :, 0], qkv2[:, :, 1], mix, t1=t1, t2=t2,
@@ -932,59 +928,52 @@ def crossview_core_packed(qkv1, qkv2, mix, t1=0.0, t2=0.0, prior_weight=0.0, anc
                           dropout_p=dropout_p, seed=seed)
 
 
-def _dp_fwd(ts, lg, gates, beta_not, hops, m8, ms, causal, prec, path, drop):
+def _dp_args(ts, lg, y, gates, beta_not, hops, mask, causal, prec, path, drop) -> L.DualPathArgs:
+    """the MopkDualPathArgs fields forward and backward share; ts: the six (B,N,H,dk) views q1 k1 v1 q2 k2 v2"""
+    B, N, H, dk = ts[0].shape
+    a = L.DualPathArgs()
+    a.B, a.H, a.N, a.dk, a.hops = B, H, N, dk, hops
+    a.io_dtype, a.precision, a.path, a.causal = _io_dtype(ts[0]), prec, path, int(bool(causal))
+    a.g_and, a.g_or, a.g_not, a.g_chain = (float(g) for g in gates)
+    a.beta_not = float(beta_not)
+    a.q1, a.k1, a.v1, a.q2, a.k2, a.v2 = (_v4(t) for t in ts)
+    a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(mask[0]), mask[1]
+    a.chain_logit, a.y = lg.data_ptr(), _v4(y)
+    a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
+    return a
+
+
+def _dp_fwd(ts, lg, gates, beta_not, hops, mask, causal, prec, path, drop):
     """one mopk_dualpath_fwd call on six (B,N,H,dk) views -> (y (B,N,H,dk), saved, resolved path)"""
     lib = L.lib()
     B, N, H, dk = ts[0].shape
     dev = ts[0].device
-    a = L.DualPathArgs()
-    a.B, a.H, a.N, a.dk, a.hops = B, H, N, dk, hops
-    a.io_dtype, a.precision, a.path, a.causal = _io_dtype(ts[0]), prec, path, int(bool(causal))
-    a.g_and, a.g_or, a.g_not, a.g_chain = (float(g) for g in gates)
-    a.beta_not = float(beta_not)
-    a.q1, a.k1, a.v1, a.q2, a.k2, a.v2 = (_v4(t) for t in ts)
-    a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(m8), ms
-    a.chain_logit = lg.data_ptr()
     y = torch.empty(B, N, H, dk, dtype=ts[0].dtype, device=dev)
-    a.y = _v4(y)
+    a = _dp_args(ts, lg, y, gates, beta_not, hops, mask, causal, prec, path, drop)
     if path == L.PATH_AUTO:
         path = L.PATH_FUSED if lib.mopk_dualpath_fused_supported(C.byref(a)) else L.PATH_GENERIC
         a.path = path
-    a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
     LAST_PATH["dualpath_fwd"] = path
     saved = _bytes(lib.mopk_dualpath_saved_bytes(C.byref(a)), dev)
     ws = _bytes(lib.mopk_dualpath_workspace_bytes(C.byref(a)), dev)
     a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-    with _timed("dualpath_fwd"):
-        rc = lib.mopk_dualpath_fwd(C.byref(a), _stream())
-    L.check(rc, "mopk_dualpath_fwd")
+    _launch("mopk_dualpath_fwd", a, "dualpath_fwd")
     return y, saved, path
 
 
-def _dp_bwd(ts, lg, y, saved, dy, gs, gates, beta_not, hops, m8, ms, causal, prec, path, drop):
+def _dp_bwd(ts, lg, y, saved, dy, gs, gates, beta_not, hops, mask, causal, prec, path, drop):
     """one mopk_dualpath_bwd call: gradients into the six (B,N,H,dk) views `gs`; -> d chain_logit partials (B,H)"""
-    lib = L.lib()
     B, N, H, dk = ts[0].shape
     dev = ts[0].device
-    a = L.DualPathArgs()
-    a.B, a.H, a.N, a.dk, a.hops = B, H, N, dk, hops
-    a.io_dtype, a.precision, a.path, a.causal = _io_dtype(ts[0]), prec, path, int(bool(causal))
-    a.g_and, a.g_or, a.g_not, a.g_chain = (float(g) for g in gates)
-    a.beta_not = float(beta_not)
-    a.q1, a.k1, a.v1, a.q2, a.k2, a.v2 = (_v4(t) for t in ts)
-    a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(m8), ms
-    a.chain_logit = lg.data_ptr()
-    a.y, a.dy = _v4(y), _v4(dy)
-    a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
+    a = _dp_args(ts, lg, y, gates, beta_not, hops, mask, causal, prec, path, drop)
+    a.dy = _v4(dy)
     a.dq1, a.dk1, a.dv1, a.dq2, a.dk2, a.dv2 = (_v4(g) for g in gs)
     dlg = torch.empty(B, H, dtype=torch.float32, device=dev)
     a.dlogit_part = dlg.data_ptr()
     LAST_PATH["dualpath_bwd"] = path
-    ws = _bytes(lib.mopk_dualpath_workspace_bytes(C.byref(a)), dev)
+    ws = _bytes(L.lib().mopk_dualpath_workspace_bytes(C.byref(a)), dev)
     a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-    with _timed("dualpath_bwd"):
-        rc = lib.mopk_dualpath_bwd(C.byref(a), _stream())
-    L.check(rc, "mopk_dualpath_bwd")
+    _launch("mopk_dualpath_bwd", a, "dualpath_bwd")
     return dlg
 
 
@@ -999,16 +988,16 @@ class _DualPathFn(torch.autograd.Function):
         ts = [_heads_view(t) for t in (q1, k1, v1, q2, k2, v2)]
         B, N, H, dk = ts[0].shape
         lg = _f32c(logit).reshape(1)
-        m8, ms = _mask_u8(mask, B, H, N, ts[0].device)
-        y, saved, path = _dp_fwd(ts, lg, gates, beta_not, hops, m8, ms, causal, prec, path, drop)
+        mask = _mask_u8(mask, B, H, N, ts[0].device)
+        y, saved, path = _dp_fwd(ts, lg, gates, beta_not, hops, mask, causal, prec, path, drop)
         ctx.save_for_backward(*ts, lg, y, saved)
-        ctx.meta = (gates, beta_not, hops, causal, prec, path, m8, ms, drop)
+        ctx.meta = (gates, beta_not, hops, causal, prec, path, mask, drop)
         return y.view(B, N, H * dk)
 
     @staticmethod
     def backward(ctx, dy):
         *ts, lg, y, saved = ctx.saved_tensors
-        gates, beta_not, hops, causal, prec, path, m8, ms, drop = ctx.meta
+        gates, beta_not, hops, causal, prec, path, mask, drop = ctx.meta
         B, N, H, dk = ts[0].shape
         dev = ts[0].device
         dy = dy.contiguous().to(ts[0].dtype).view(B, N, H, dk)
@@ -1018,7 +1007,7 @@ class _DualPathFn(torch.autograd.Function):
             gs = [*packs[0].unbind(2), *packs[1].unbind(2)]
         else:
             gs = [mk(B, N, H, dk, dtype=ts[0].dtype, device=dev) for _ in range(6)]
-        dlg = _dp_bwd(ts, lg, y, saved, dy, gs, gates, beta_not, hops, m8, ms, causal, prec, path, drop)
+        dlg = _dp_bwd(ts, lg, y, saved, dy, gs, gates, beta_not, hops, mask, causal, prec, path, drop)
         if ctx.packed:
             return (packs[0], None, None, packs[1], None, None, dlg.sum().reshape(()), None, None, None, None, None, None, None, None)
         return (*gs, dlg.sum().reshape(()), None, None, None, None, None, None, None, None)
@@ -1036,21 +1025,19 @@ class _CrossViewFoldedFn(torch.autograd.Function):
         q1, k1, v1 = qkv1.contiguous().unbind(2)
         q2, k2, _ = qkv2.contiguous().unbind(2)
         B, N, H, dk = q1.shape
-        m = mix.detach().to(k1.dtype)
-        k1p = (m[0, 0] * k1 + m[0, 1] * k2).contiguous()
-        k2p = (m[1, 0] * k1 + m[1, 1] * k2).contiguous()
+        k1p, k2p = _cv_mixed_keys(mix.detach().to(k1.dtype), k1, k2)
         ts = [q1, k1p, v1, q2, k2p, v1]
         lg = torch.zeros(1, dtype=torch.float32, device=q1.device)
-        m8, ms = _mask_u8(mask, B, H, N, q1.device)
-        y, saved, path = _dp_fwd(ts, lg, (1.0, 0.0, 0.0, 0.0), 0.0, 0, m8, ms, causal, prec, L.PATH_FUSED, drop)
+        mask = _mask_u8(mask, B, H, N, q1.device)
+        y, saved, path = _dp_fwd(ts, lg, (1.0, 0.0, 0.0, 0.0), 0.0, 0, mask, causal, prec, L.PATH_FUSED, drop)
         ctx.save_for_backward(qkv1, qkv2, mix, k1p, k2p, lg, y, saved)
-        ctx.meta = (causal, prec, path, m8, ms, drop)
+        ctx.meta = (causal, prec, path, mask, drop)
         return y.view(B, N, H * dk)
 
     @staticmethod
     def backward(ctx, dy):
         qkv1, qkv2, mix, k1p, k2p, lg, y, saved = ctx.saved_tensors
-        causal, prec, path, m8, ms, drop = ctx.meta
+        causal, prec, path, mask, drop = ctx.meta
         q1, k1, v1 = qkv1.unbind(2)
         q2, k2, _ = qkv2.unbind(2)
         B, N, H, dk = q1.shape
@@ -1060,7 +1047,7 @@ class _CrossViewFoldedFn(torch.autograd.Function):
         dk1p, dk2p = torch.empty(B, N, H, dk, dtype=q1.dtype, device=dev), torch.empty(B, N, H, dk, dtype=q1.dtype, device=dev)
         dv2 = torch.zeros(B, N, H, dk, dtype=q1.dtype, device=dev)          # hops == 0: never written
         gs = [d1[:, :, 0], dk1p, d1[:, :, 2], d2[:, :, 0], dk2p, dv2]
-        _dp_bwd([q1, k1p, v1, q2, k2p, v1], lg, y, saved, dy, gs, (1.0, 0.0, 0.0, 0.0), 0.0, 0, m8, ms, causal, prec, path, drop)
+        _dp_bwd([q1, k1p, v1, q2, k2p, v1], lg, y, saved, dy, gs, (1.0, 0.0, 0.0, 0.0), 0.0, 0, mask, causal, prec, path, drop)
         m = mix.detach().to(q1.dtype)
         d1k, d2k = d1[:, :, 1], d2[:, :, 1]                                  # k1' = m11 k1 + m12 k2, k2' = m21 k1 + m22 k2
         torch.mul(dk1p, m[0, 0], out=d1k); d1k.addcmul_(dk2p, m[1, 0])
@@ -1076,9 +1063,26 @@ def dualpath_core(q1, k1, v1, q2, k2, v2, chain_logit, g_and, g_or, g_not, g_cha
     """q*, k*, v*: (B,N,H,dk) views -- or packed: q1 / q2 = the (B,N,3,H,dk) outputs of the two qkv projections, k1 = v1 = k2 = v2 = None"""
     if q1.shape[0] == 0:
         return _empty_batch(q1, 0, q1.shape[1], q1.shape[-2] * q1.shape[-1])
-    drop = (float(dropout_p), (dropout_seed() if seed is None else int(seed))) if dropout_p > 0 else (0.0, 0)
+    drop = _drop(dropout_p, seed)
     return _DualPathFn.apply(q1, k1, v1, q2, k2, v2, chain_logit, (g_and, g_or, g_not, g_chain), beta_not,
                              int(hops), attn_mask, causal, _prec_for(q1.dtype), _PATH, drop)
+
+
+def _qt_args(ts, sc, y, am, eps, prec, path, drop) -> L.QuartetArgs:
+    """the MopkQuartetArgs fields forward and backward share; ts: the (B,T,H,dh) views q k v, plus q2 k2 with the quartet term,
+    whose float32 scalars are sc = (mixture, scale); am: (additive mask or None, strides) from _bias_f32"""
+    B, T, H, dh = ts[0].shape
+    a = L.QuartetArgs()
+    a.B, a.H, a.T, a.dh = B, H, T, dh
+    a.io_dtype, a.precision, a.path = _io_dtype(ts[0]), prec, path
+    a.use_quartet, a.eps = int(len(ts) == 5), float(eps)
+    a.q, a.k, a.v, a.y = _v4(ts[0]), _v4(ts[1]), _v4(ts[2]), _v4(y)
+    if len(ts) == 5:
+        a.q2, a.k2 = _v4(ts[3]), _v4(ts[4])
+        a.mixture, a.quartet_scale = sc[0].data_ptr(), sc[1].data_ptr()
+    a.add_mask, (a.am_sb, a.am_sh, a.am_si) = _ptr(am[0]), am[1]
+    a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
+    return a
 
 
 class _QuartetFn(torch.autograd.Function):
@@ -1089,23 +1093,12 @@ class _QuartetFn(torch.autograd.Function):
         ts = [_heads_view(t) for t in ((q, k, v, q2, k2) if use_quartet else (q, k, v))]
         B, T, H, dh = ts[0].shape
         dev = ts[0].device
-        a = L.QuartetArgs()
-        a.B, a.H, a.T, a.dh = B, H, T, dh
-        a.io_dtype, a.precision, a.path = _io_dtype(ts[0]), prec, path
-        a.use_quartet, a.eps = int(bool(use_quartet)), float(eps)
-        a.q, a.k, a.v = _v4(ts[0]), _v4(ts[1]), _v4(ts[2])
-        sc = []
-        if use_quartet:
-            a.q2, a.k2 = _v4(ts[3]), _v4(ts[4])
-            sc = [_f32c(mixture).reshape(1), _f32c(qscale).reshape(1)]
-            a.mixture, a.quartet_scale = sc[0].data_ptr(), sc[1].data_ptr()
-        am, ams = _bias_f32(add_mask, B, H, T, dev)
-        a.add_mask, (a.am_sb, a.am_sh, a.am_si) = _ptr(am), ams
+        sc = [_f32c(mixture).reshape(1), _f32c(qscale).reshape(1)] if use_quartet else []
+        am = _bias_f32(add_mask, B, H, T, dev)
         y = torch.empty(B, T, H, dh, dtype=ts[0].dtype, device=dev)
-        a.y = _v4(y)
+        a = _qt_args(ts, sc, y, am, eps, prec, path, drop)
         attn = torch.empty(B, H, T, T, dtype=torch.float32, device=dev) if need_weights else None
         a.attn = _ptr(attn)
-        a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
         if path == L.PATH_AUTO:
             path = L.PATH_FUSED if lib.mopk_quartet_fused_supported(C.byref(a)) else L.PATH_GENERIC
             a.path = path
@@ -1113,11 +1106,9 @@ class _QuartetFn(torch.autograd.Function):
         saved = _bytes(lib.mopk_quartet_saved_bytes(C.byref(a)), dev)
         ws = _bytes(lib.mopk_quartet_workspace_bytes(C.byref(a)), dev)
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        with _timed("quartet_fwd"):
-            rc = lib.mopk_quartet_fwd(C.byref(a), _stream())
-        L.check(rc, "mopk_quartet_fwd")
+        _launch("mopk_quartet_fwd", a, "quartet_fwd")
         ctx.save_for_backward(*ts, *sc, y, saved)
-        ctx.meta = (eps, use_quartet, prec, path, am, ams, drop)
+        ctx.meta = (eps, use_quartet, prec, path, am, drop)
         out = y.view(B, T, H * dh)
         if need_weights:
             ctx.mark_non_differentiable(attn)
@@ -1127,36 +1118,26 @@ class _QuartetFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, *unused):
         lib = L.lib()
-        eps, use_quartet, prec, path, am, ams, drop = ctx.meta
-        if use_quartet:
-            q, k, v, q2, k2, mix, qs, y, saved = ctx.saved_tensors
-        else:
-            q, k, v, y, saved = ctx.saved_tensors
-        B, T, H, dh = q.shape
-        dev = q.device
-        dy = dy.contiguous().to(q.dtype).view(B, T, H, dh)
-        a = L.QuartetArgs()
-        a.B, a.H, a.T, a.dh = B, H, T, dh
-        a.io_dtype, a.precision, a.path = _io_dtype(q), prec, path
-        a.use_quartet, a.eps = int(bool(use_quartet)), float(eps)
-        a.q, a.k, a.v, a.y, a.dy = _v4(q), _v4(k), _v4(v), _v4(y), _v4(dy)
-        a.add_mask, (a.am_sb, a.am_sh, a.am_si) = _ptr(am), ams
-        a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
+        eps, use_quartet, prec, path, am, drop = ctx.meta
         n = 5 if use_quartet else 3
-        gs = [torch.empty(B, T, H, dh, dtype=q.dtype, device=dev) for _ in range(n)]
+        *ts, y, saved = ctx.saved_tensors
+        ts, sc = ts[:n], ts[n:]
+        B, T, H, dh = ts[0].shape
+        dev = ts[0].device
+        dy = dy.contiguous().to(ts[0].dtype).view(B, T, H, dh)
+        a = _qt_args(ts, sc, y, am, eps, prec, path, drop)
+        a.dy = _v4(dy)
+        gs = [torch.empty(B, T, H, dh, dtype=ts[0].dtype, device=dev) for _ in range(n)]
         a.dq, a.dk_, a.dv = _v4(gs[0]), _v4(gs[1]), _v4(gs[2])
         dmix = dqs = None
         if use_quartet:
-            a.q2, a.k2, a.dq2, a.dk2 = _v4(q2), _v4(k2), _v4(gs[3]), _v4(gs[4])
-            a.mixture, a.quartet_scale = mix.data_ptr(), qs.data_ptr()
+            a.dq2, a.dk2 = _v4(gs[3]), _v4(gs[4])
             dmix = torch.empty(B, H, dtype=torch.float32, device=dev)
             dqs = torch.empty(B, H, dtype=torch.float32, device=dev)
             a.dmixture_part, a.dqscale_part = dmix.data_ptr(), dqs.data_ptr()
         ws = _bytes(lib.mopk_quartet_workspace_bytes(C.byref(a)), dev)
         a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        with _timed("quartet_bwd"):
-            rc = lib.mopk_quartet_bwd(C.byref(a), _stream())
-        L.check(rc, "mopk_quartet_bwd")
+        _launch("mopk_quartet_bwd", a, "quartet_bwd")
         if use_quartet:
             return (gs[0], gs[1], gs[2], gs[3], gs[4], dmix.sum().reshape(1), dqs.sum().reshape(1),
                     None, None, None, None, None, None, None)
@@ -1169,7 +1150,7 @@ def quartet_core(q, k, v, q2, k2, mixture, quartet_scale, add_mask, eps, use_qua
     if q.shape[0] == 0:                   # q: (B,T,H,dk)
         out = _empty_batch(q, 0, q.shape[1], q.shape[2] * q.shape[3])
         return (out, q.new_zeros((0, q.shape[2], q.shape[1], q.shape[1]), dtype=torch.float32)) if need_weights else out
-    drop = (float(dropout_p), (dropout_seed() if seed is None else int(seed))) if dropout_p > 0 else (0.0, 0)
+    drop = _drop(dropout_p, seed)
     return _QuartetFn.apply(q, k, v, q2, k2, mixture, quartet_scale, add_mask, eps, use_quartet, need_weights,
                             _prec_for(q.dtype), _PATH, drop)
 
@@ -1182,22 +1163,28 @@ def layernorm_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
             and d % 8 == 0 and d <= 4096 and x.numel() > 0)
 
 
+def _ln_args(xc, w, mean, rstd, y, eps) -> L.LayerNormArgs:
+    """the MopkLayerNormArgs fields forward and backward share; xc: contiguous (..., dim) input, y: the output (forward) or its
+    gradient (backward), whose dtype is y_dtype"""
+    d = xc.shape[-1]
+    return L.LayerNormArgs(rows=xc.numel() // d, dim=d, x_dtype=_io_dtype(xc), y_dtype=_io_dtype(y), p_dtype=_io_dtype(w), eps=float(eps),
+                           x_ld=d, y_ld=d, x=_ptr(xc), gamma=_ptr(w), mean=_ptr(mean), rstd=_ptr(rstd))
+
+
 class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, out_dtype, with_residual):
         _require_gpu(x, "layernorm")
         xc = x.contiguous()
-        d = xc.shape[-1]
-        rows = xc.numel() // d
+        rows = xc.numel() // xc.shape[-1]
         y = torch.empty(xc.shape, dtype=out_dtype, device=x.device)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
         w = weight.detach().contiguous()
         b = None if bias is None else bias.detach().to(w.dtype).contiguous()
-        a = L.LayerNormArgs(rows=rows, dim=d, x_dtype=_io_dtype(xc), y_dtype=_io_dtype(y), p_dtype=_io_dtype(w), eps=float(eps),
-                            x_ld=d, y_ld=d, x=_ptr(xc), gamma=_ptr(w), beta=_ptr(b), y=_ptr(y), mean=_ptr(mean), rstd=_ptr(rstd))
-        with _timed("layernorm_fwd"):
-            L.check(L.lib().mopk_layernorm_fwd(C.byref(a), _stream()), "mopk_layernorm_fwd")
+        a = _ln_args(xc, w, mean, rstd, y, eps)
+        a.beta, a.y = _ptr(b), _ptr(y)
+        _launch("mopk_layernorm_fwd", a, "layernorm_fwd")
         ctx.save_for_backward(xc, w, mean, rstd)
         ctx.meta = (float(eps), bias is not None, with_residual, weight.dtype, None if bias is None else bias.dtype)
         if with_residual:
@@ -1210,7 +1197,6 @@ class _LayerNormFn(torch.autograd.Function):
         eps, has_bias, with_residual, wdt, bdt = ctx.meta
         dres, dy = (grads if with_residual else (None, grads[0]))
         d = xc.shape[-1]
-        rows = xc.numel() // d
         if dy is None:                                    # only the residual branch carries a gradient
             return (dres, None, None, None, None, None)
         dy = dy.contiguous()
@@ -1219,13 +1205,11 @@ class _LayerNormFn(torch.autograd.Function):
         dx = torch.empty_like(xc)
         dg = torch.empty(d, dtype=torch.float32, device=xc.device)
         db = torch.empty(d, dtype=torch.float32, device=xc.device) if has_bias else None
-        a = L.LayerNormArgs(rows=rows, dim=d, x_dtype=_io_dtype(xc), y_dtype=_io_dtype(dy), p_dtype=_io_dtype(w), eps=eps,
-                            x_ld=d, y_ld=d, x=_ptr(xc), gamma=_ptr(w), mean=_ptr(mean), rstd=_ptr(rstd),
-                            dy=_ptr(dy), dres=_ptr(dres), dx=_ptr(dx), dgamma=_ptr(dg), dbeta=_ptr(db))
+        a = _ln_args(xc, w, mean, rstd, dy, eps)
+        a.dy, a.dres, a.dx, a.dgamma, a.dbeta = _ptr(dy), _ptr(dres), _ptr(dx), _ptr(dg), _ptr(db)
         ws = torch.empty(max(1, L.lib().mopk_layernorm_workspace_bytes(C.byref(a))), dtype=torch.uint8, device=xc.device)
         a.workspace = _ptr(ws)
-        with _timed("layernorm_bwd"):
-            L.check(L.lib().mopk_layernorm_bwd(C.byref(a), _stream()), "mopk_layernorm_bwd")
+        _launch("mopk_layernorm_bwd", a, "layernorm_bwd")
         return dx, dg.to(wdt), (db.to(bdt) if has_bias else None), None, None, None
 
 
@@ -1301,7 +1285,6 @@ def token_gate_supported(x: torch.Tensor, a: Optional[torch.Tensor] = None) -> b
 class _TokenGateFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, a, u):
-        lib = L.lib()
         g = _tg_args(x, a)
         B, T, D = x.shape
         uc = u.detach().to(torch.float32).contiguous()
@@ -1310,9 +1293,7 @@ class _TokenGateFn(torch.autograd.Function):
         gate = torch.empty(B, T, dtype=torch.float32, device=x.device)
         g.u, g.out, g.gate = uc.data_ptr(), out.data_ptr(), gate.data_ptr()
         LAST_PATH["token_gate_fwd"] = L.PATH_FUSED
-        with _timed("token_gate_fwd"):
-            rc = lib.mopk_token_gate_fwd(C.byref(g), _stream())
-        L.check(rc, "mopk_token_gate_fwd")
+        _launch("mopk_token_gate_fwd", g, "token_gate_fwd")
         ctx.save_for_backward(x, a, uc, gate)
         ctx.u_dtype = u.dtype
         return out
@@ -1330,9 +1311,7 @@ class _TokenGateFn(torch.autograd.Function):
         ws = _bytes(lib.mopk_token_gate_workspace_bytes(C.byref(g)), x.device)
         g.workspace = ws.data_ptr()
         LAST_PATH["token_gate_bwd"] = L.PATH_FUSED
-        with _timed("token_gate_bwd"):
-            rc = lib.mopk_token_gate_bwd(C.byref(g), _stream())
-        L.check(rc, "mopk_token_gate_bwd")
+        _launch("mopk_token_gate_bwd", g, "token_gate_bwd")
         dx = dr.to(x.dtype) if ctx.needs_input_grad[0] else None
         da = dr.to(a.dtype) if a is not None and ctx.needs_input_grad[1] else None
         return dx, da, (du.to(ctx.u_dtype) if ctx.needs_input_grad[2] else None)
@@ -1442,9 +1421,7 @@ class _MoeFn(torch.autograd.Function):
             a.residual = res.data_ptr()
         a.y, a.u, a.h, a.route = y.data_ptr(), u.data_ptr(), h.data_ptr(), route.data_ptr()
         LAST_PATH["moe_fwd"] = L.PATH_FUSED
-        with _timed("moe_fwd"):
-            rc = L.lib().mopk_moe_fwd(C.byref(a), _stream())
-        L.check(rc, "mopk_moe_fwd")
+        _launch("mopk_moe_fwd", a, "moe_fwd")
         ctx.save_for_backward(x2, gate_w, gate_b, u, h, route, *ws)
         ctx.meta = (n_exp, odt, prec, x.shape, x.dtype, residual is not None)
         return y.view(x.shape)
@@ -1466,9 +1443,7 @@ class _MoeFn(torch.autograd.Function):
         ws_buf = _bytes(L.lib().mopk_moe_workspace_bytes(C.byref(a), 1), x2.device)
         a.workspace = ws_buf.data_ptr()
         LAST_PATH["moe_bwd"] = L.PATH_FUSED
-        with _timed("moe_bwd"):
-            rc = L.lib().mopk_moe_bwd(C.byref(a), _stream())
-        L.check(rc, "mopk_moe_bwd")
+        _launch("mopk_moe_bwd", a, "moe_bwd")
         dres = dy if has_res else None
         return (dx.view(xshape), dres, None, None, None, *dw1, *dw2)
 
@@ -1511,7 +1486,7 @@ def moe_route(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.Tens
     a.gate_dtype = _io_dtype(gw)
     route = _moe_route_buf(a.M, E, x.device)
     a.x, a.gate_w, a.gate_b, a.route = x2.data_ptr(), gw.data_ptr(), _ptr(gb), route.data_ptr()
-    L.check(L.lib().mopk_moe_route(C.byref(a), _stream()), "mopk_moe_route")
+    _launch("mopk_moe_route", a)
     return route[:a.M]
 
 
@@ -1597,9 +1572,7 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         ws = _bytes(lib.mopk_decode_attn_workspace_bytes(C.byref(a)), q.device)
         a.y, a.workspace = _v4(y), ws.data_ptr()
         LAST_PATH["decode_attn"] = L.PATH_FUSED
-        with _timed("decode_attn"):
-            rc = lib.mopk_decode_attn_fwd(C.byref(a), _stream())
-        L.check(rc, "mopk_decode_attn_fwd")
+        _launch("mopk_decode_attn_fwd", a, "decode_attn")
         return y.view(B, Tq, H * dk)
 
 
@@ -1663,9 +1636,7 @@ def decode_attention_rows(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
         ws = _bytes(lib.mopk_decode_attn_rows_workspace_bytes(C.byref(a)), q.device)
         a.base.y, a.base.workspace = _v4(y), ws.data_ptr()
         LAST_PATH["decode_attn_rows"] = L.PATH_FUSED
-        with _timed("decode_attn_rows"):
-            rc = lib.mopk_decode_attn_rows_fwd(C.byref(a), _stream())
-        L.check(rc, "mopk_decode_attn_rows_fwd")
+        _launch("mopk_decode_attn_rows_fwd", a, "decode_attn_rows")
         return y.view(B, Tq, H * dk)
 
 
@@ -1850,9 +1821,7 @@ def beam_step(logits: torch.Tensor, state: BeamState, pos: torch.Tensor) -> None
         ws = _bytes(lib.mopk_beam_workspace_bytes(C.byref(a)), logits.device)
         a.workspace = ws.data_ptr()
         LAST_PATH["beam_step"] = L.PATH_FUSED
-        with _timed("beam_step"):
-            rc = lib.mopk_beam_step(C.byref(a), _stream())
-        L.check(rc, "mopk_beam_step")
+        _launch("mopk_beam_step", a, "beam_step")
 
 
 def beam_finalize(state: BeamState, n_new: int):
