@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPK_VERSION 118 /* 118: mopk_decode_attn_rows_*, MopkDecodeAttnRowsArgs, mopk_beam_* and MopkBeamArgs (added later without a bump: new exports only, detect with mopk_decode_attn_rows_supported / mopk_beam_supported), mopk_decode_attn_* and MopkDecodeAttnArgs (added later without a bump: new exports only, detect with mopk_decode_attn_supported), mopk_moe_* and MopkMoeArgs (added later without a bump: new exports only, detect with mopk_moe_supported), MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
+#define MOPK_VERSION 118 /* 118: mopk_sample_* and MopkSampleArgs (added later without a bump: new exports only, detect with mopk_sample_supported), mopk_decode_attn_rows_*, MopkDecodeAttnRowsArgs, mopk_beam_* and MopkBeamArgs (added later without a bump: new exports only, detect with mopk_decode_attn_rows_supported / mopk_beam_supported), mopk_decode_attn_* and MopkDecodeAttnArgs (added later without a bump: new exports only, detect with mopk_decode_attn_supported), mopk_moe_* and MopkMoeArgs (added later without a bump: new exports only, detect with mopk_moe_supported), MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
 
 typedef enum MopkStatus {
     MOPK_OK = 0,
@@ -541,6 +541,44 @@ typedef struct MopkBeamArgs {
 int mopk_beam_supported(const MopkBeamArgs *a);                      /* 1 if the kernels take this call (K, V, T, dtype, strides) */
 size_t mopk_beam_workspace_bytes(const MopkBeamArgs *a);
 int mopk_beam_step(const MopkBeamArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
+ * Temperature / top-k / top-p sampling of one token per row (WhisperMoP.sample; inference only).  (Added under version 118: new
+ * exports only; callers detect it with mopk_sample_supported.)  Row r (0 <= r < R) reads logits x at
+ * logits + (r / n) * logits_sb + (r % n) * logits_sk elements (logits_sk = 0: one row shared by the n rows of an item), F32 or BF16,
+ * element-aligned, finite or -inf values.  pos = *pos (device memory: one set of launch arguments serves every decoding step).
+ *   greedy:  tokens[r] = argmax_v x_v, ties to the smaller v.
+ *   else:    z_v = x_v * inv_temp (fp32);  top_k in (0, V): keep z_v >= the k-th largest z (counted with multiplicity, ties kept);
+ *            top_p < 1: q_v = (uint64)(expf(z_v - max z) * 2^40) over the kept set, Q = sum q_v, P = ceil((double)top_p * Q),
+ *            tau = the largest z_u with sum_{kept, z_v >= z_u} q_v >= P; keep z_v >= tau (tie-inclusive, never empty);
+ *            tokens[r] = argmax_{v kept} z_v + G_v, ties to the smaller v, G_v = -logf(-logf(u)), u = ((h >> 9) + 0.5) * 2^-23,
+ *            h = fa_hash(rh ^ v * 0xC2B2AE3D), rh = fa_hash(fa_hash(seed_lo ^ r * 0x9E3779B1) ^ seed_hi ^ pos * 0x85EBCA77)
+ *            (common.h's fa_hash; all products mod 2^32).
+ *   logprobs[r] = log_softmax(x)[tokens[r]] on the unscaled, unfiltered row.
+ * One workgroup of 1024 threads per row streams the row once per pass (it stays in L2); the top-k and top-p thresholds are found by a
+ * radix walk over the order-preserving uint32 key of z with integer LDS counts / fixed-point masses, so no result depends on the
+ * order of an atomic.  No host synchronisation; bitwise reproducible.  workspace: mopk_sample_workspace_bytes() (0 today). */
+#define MOPK_SAMPLE_MAX_V (1 << 24)       /* the fixed-point masses of a row sum exactly in 64 bits */
+typedef struct MopkSampleArgs {
+    int32_t R;                           /* rows sampled */
+    int32_t n;                           /* rows per item: row r reads the logit row of item r / n */
+    int32_t V;                           /* vocabulary, 2 <= V <= MOPK_SAMPLE_MAX_V */
+    int32_t logits_dtype;                /* MopkDtype: F32 or BF16 */
+    int32_t top_k;                       /* 0: off */
+    int32_t greedy;                      /* 1: temperature 0 (argmax; inv_temp, top_k, top_p and seed unused) */
+    float inv_temp;                      /* 1 / temperature rounded to fp32 once, finite and > 0 */
+    float top_p;                         /* 1: off, else in (0, 1) */
+    uint64_t seed;
+    const void *logits;
+    int64_t logits_sb, logits_sk;        /* element strides of an item's and of a row-in-item's logit row */
+    const int32_t *pos;                  /* device: the sampled token's position (one int32) */
+    int32_t *tokens;                     /* (R) out */
+    float *logprobs;                     /* (R) out */
+    void *workspace;                     /* may be NULL while mopk_sample_workspace_bytes() is 0 */
+} MopkSampleArgs;
+int mopk_sample_supported(const MopkSampleArgs *a);                  /* 1 if the kernel takes this call (V, dtype, filters, strides) */
+size_t mopk_sample_workspace_bytes(const MopkSampleArgs *a);
+int mopk_sample_step(const MopkSampleArgs *a, void *stream);
 
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);

@@ -181,6 +181,16 @@ class BeamArgs(C.Structure):
     ]
 
 
+class SampleArgs(C.Structure):
+    """MopkSampleArgs: temperature / top-k / top-p sampling of one token per row (WhisperMoP.sample)."""
+    _fields_ = [
+        ("R", C.c_int32), ("n", C.c_int32), ("V", C.c_int32), ("logits_dtype", C.c_int32), ("top_k", C.c_int32), ("greedy", C.c_int32),
+        ("inv_temp", C.c_float), ("top_p", C.c_float), ("seed", C.c_uint64),
+        ("logits", _fp), ("logits_sb", C.c_int64), ("logits_sk", C.c_int64), ("pos", _fp), ("tokens", _fp), ("logprobs", _fp),
+        ("workspace", _fp),
+    ]
+
+
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),
@@ -237,6 +247,9 @@ SYMBOLS = {
     "mopk_beam_supported": (C.c_int, [C.POINTER(BeamArgs)]),
     "mopk_beam_workspace_bytes": (C.c_size_t, [C.POINTER(BeamArgs)]),
     "mopk_beam_step": (C.c_int, [C.POINTER(BeamArgs), C.c_void_p]),
+    "mopk_sample_supported": (C.c_int, [C.POINTER(SampleArgs)]),
+    "mopk_sample_workspace_bytes": (C.c_size_t, [C.POINTER(SampleArgs)]),
+    "mopk_sample_step": (C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -465,6 +465,85 @@ class WhisperMoP(nn.Module):
         return tokens.to(prompt_ids.dtype), scores
 
     @torch.no_grad()
+    def sample(self, mel: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
+               top_p: float = 1.0, num_samples: int = 1, eos_token_id: Optional[int] = None, seed: int = 0, graph: bool = False):
+        """sampled decoding: mel (B, T_audio, n_mels), prompt_ids (B, T_p) -> (tokens (B, num_samples, T_p + max_new_tokens) in
+        prompt_ids' dtype, sum_logprobs (B, num_samples) fp32), all on the device; the step loop never syncs the host.
+
+        Every token is drawn by ops.sample_tokens (temperature, top_k, top_p and the draw rule are documented there; temperature 0 is
+        greedy and equals generate).  Row b * num_samples + s is sample s of item b (Whisper's best_of): the encoder and the prompt
+        run once per item (its keys / values land in cache row b * num_samples, the first draw reads the item's prompt logits for
+        all its samples), and a constant row table lets the samples read the shared prompt through ops.decode_attention_rows; no
+        cache slot is copied.  The draw at position pos of sample row r is a pure function of (logits, seed, r, pos).  A row that has
+        emitted eos_token_id keeps emitting it; sum_logprobs adds log_softmax(logits)[token] of every token up to and including the
+        first eos.  graph=True captures one step (decoder step + sample_tokens + the eos / sum update) after the first eager one and
+        replays it (torch.cuda.graph, one stream, static buffers)."""
+        B, T_p = prompt_ids.shape
+        n = int(num_samples)
+        if not 1 <= n <= ops.BEAM_MAX_K:
+            raise ValueError(f"sample: num_samples = {num_samples} outside [1, {ops.BEAM_MAX_K}]")
+        if T_p < 1 or max_new_tokens < 1:
+            raise ValueError(f"sample: needs a prompt and at least one new token (T_p = {T_p}, max_new_tokens = {max_new_tokens})")
+        if T_p + max_new_tokens > self.cfg.n_text_ctx:
+            raise ValueError(f"sample: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        ops._sample_params(temperature, top_k, top_p, "sample")                 # argument errors before encoding
+        dev = prompt_ids.device
+        length = torch.zeros(1, dtype=torch.int32, device=dev)
+        cap = T_p + max_new_tokens
+        H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        enc, _ = self.encode(mel)
+        ck, cv = self._cross_kv(enc)
+        kw = dict(dtype=ck[0].dtype, device=enc.device)
+        sk = [torch.zeros(B * n, cap, H, Dh, **kw) for _ in self.decoder]
+        sv = [torch.zeros(B * n, cap, H, Dh, **kw) for _ in self.decoder]
+        prompt_cache = WhisperDecodeCache(ck, cv, [t[::n] for t in sk], [t[::n] for t in sv], length, cap)
+        logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]              # (B, V): shared by the item's samples
+        cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
+        cache.pos = T_p
+        i32 = dict(dtype=torch.int32, device=dev)
+        r = torch.arange(B * n, **i32)
+        table = r.unsqueeze(1).repeat(1, cap)                                   # constant: the prompt from row b * n, then own rows
+        table[:, :T_p] = (r // n * n).unsqueeze(1)
+        tokens = torch.zeros(B * n, cap, **i32)
+        tokens[:, :T_p] = prompt_ids.to(torch.int32).repeat_interleave(n, 0)
+        tok, lp = torch.zeros(B * n, **i32), torch.zeros(B * n, dtype=torch.float32, device=dev)
+        ids = torch.zeros(B * n, 1, **i32)
+        sum_lp = torch.zeros(B * n, dtype=torch.float32, device=dev)
+        done = torch.zeros(B * n, dtype=torch.bool, device=dev)
+        eos = None if eos_token_id is None else int(eos_token_id)
+
+        def draw(lg):
+            ops.sample_tokens(lg, cache.length, temperature, top_k, top_p, seed, out=(tok, lp))
+            if eos is None:
+                sum_lp.add_(lp)
+                ids.copy_(tok.unsqueeze(1))
+            else:
+                sum_lp.add_(torch.where(done, torch.zeros_like(lp), lp))
+                ids.copy_(torch.where(done, torch.full_like(tok, eos), tok).unsqueeze(1))
+                done.logical_or_(ids.squeeze(1) == eos)
+            tokens.index_copy_(1, cache.length.to(torch.long), ids)
+
+        def step():
+            draw(self._decode_tokens(cache, ids, rows=table, beams=n)[:, -1])
+
+        draw(logits)
+        g = None
+        for t in range(1, max_new_tokens):
+            if not graph or t == 1:                  # the first full step runs eagerly (and warms every kernel up)
+                step()
+                continue
+            if g is None:
+                g = torch.cuda.CUDAGraph()
+                with torch.autocast(device_type="cuda", dtype=torch.get_autocast_dtype("cuda"),
+                                    enabled=torch.is_autocast_enabled("cuda"), cache_enabled=False):
+                    with torch.cuda.graph(g):
+                        step()
+                cache.pos -= 1                           # capture recorded the step without running it
+            g.replay()
+            cache.pos += 1
+        return tokens.view(B, n, cap).to(prompt_ids.dtype), sum_lp.view(B, n)
+
+    @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):
         """per-layer time gates of the encoder, (B, L_enc, T_audio)."""
         _, gates = self.encode(mel)

@@ -7,6 +7,7 @@ tensor or a missing library raises -- there is no fallback path.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -1839,3 +1840,161 @@ def beam_finalize(state: BeamState, n_new: int):
     t = torch.where(fill.unsqueeze(2), state.hist.view(B, K, T).gather(1, src.unsqueeze(2).expand(B, K, T)), state.fin_tokens)
     best = s.argmax(dim=1, keepdim=True)
     return t.gather(1, best.unsqueeze(2).expand(B, 1, T)).squeeze(1), s.gather(1, best).squeeze(1)
+
+
+# ---- temperature / top-k / top-p sampling of one token per row (mopk_sample_*; WhisperMoP.sample) ----
+_M32 = 0xFFFFFFFF
+
+
+def _f32(x: float) -> float:
+    """x rounded to fp32 (what the C ABI's float fields carry)"""
+    return C.c_float(x).value
+
+
+def _mul32(a: torch.Tensor, c: int) -> torch.Tensor:
+    """(a * c) mod 2^32 for int64 a in [0, 2^32) and a constant c < 2^32, in two 16-bit halves so no product leaves int64"""
+    return (a * (c & 0xFFFF) + (((a * (c >> 16)) & 0xFFFF) << 16)) & _M32
+
+
+def _hash32(x: torch.Tensor) -> torch.Tensor:
+    """common.h's fa_hash ("lowbias32") on int64 tensors holding uint32 values"""
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def _sample_params(temperature, top_k, top_p, what: str):
+    """validate the sampling parameters -> (inv_t (fp32 value, None for temperature 0), top_p (fp32 value))"""
+    t = float(temperature)
+    if not math.isfinite(t) or t < 0:
+        raise ValueError(f"{what}: temperature must be finite and >= 0, got {temperature}")
+    inv_t = None if t == 0 else _f32(1.0 / t)
+    if inv_t is not None and not (0 < inv_t < math.inf):
+        raise ValueError(f"{what}: 1 / temperature = {1.0 / t} is not a finite positive fp32 value")
+    if isinstance(top_k, bool) or int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"{what}: top_k must be an integer >= 0 (0: off), got {top_k}")
+    p = float(top_p)
+    if not 0 < p <= 1:
+        raise ValueError(f"{what}: top_p must lie in (0, 1] (1: off), got {top_p}")
+    return inv_t, _f32(p)
+
+
+def _sample_check(logits: torch.Tensor, pos: torch.Tensor, temperature, top_k, top_p, out, what: str):
+    """validate a sampling call before any device work -> (R, n, inv_t (fp32 value, None for temperature 0), top_p (fp32 value))"""
+    inv_t, tp = _sample_params(temperature, top_k, top_p, what)
+    if logits.dim() != 2 or logits.shape[1] < 2 or logits.shape[0] < 1:
+        raise ValueError(f"{what}: logits must be (rows, V) with V >= 2, got {tuple(logits.shape)}")
+    if tuple(pos.shape) != (1,):
+        raise ValueError(f"{what}: pos must be a (1,) tensor, got shape {tuple(pos.shape)}")
+    R = logits.shape[0]
+    if out is not None:
+        tok, lp = out
+        R = tok.shape[0] if tok.dim() == 1 else -1
+        if R < 1 or tuple(lp.shape) != (R,) or tok.dtype != torch.int32 or lp.dtype != torch.float32 or R % logits.shape[0]:
+            raise ValueError(f"{what}: out must be (tokens int32 (R,), logprobs fp32 (R,)) with R a multiple of the "
+                             f"{logits.shape[0]} logit rows, got {tuple(tok.shape)} {tok.dtype}, {tuple(lp.shape)} {lp.dtype}")
+    return R, R // logits.shape[0], inv_t, tp
+
+
+def sample_tokens_torch(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                        seed: int = 0, out=None):
+    """the reference composition of `sample_tokens` in torch ops (CPU or GPU, no host sync): the same z, filters, fixed-point top-p
+    masses, hash and Gumbel-max, in int64 / fp32 tensors"""
+    R, n, inv_t, tp = _sample_check(logits, pos, temperature, top_k, top_p, out, "sample_tokens_torch")
+    x = logits.float()
+    if n > 1:
+        x = x.repeat_interleave(n, 0)
+    V, dev = x.shape[1], x.device
+    if inv_t is None:
+        tok = x.argmax(-1)
+    else:
+        z = x * torch.tensor(inv_t, dtype=torch.float32, device=dev)
+        ninf = torch.tensor(float("-inf"), device=dev)
+        keep = torch.ones_like(z, dtype=torch.bool)
+        if 0 < top_k < V:
+            keep = z >= z.topk(int(top_k), dim=-1).values[:, -1:]
+        if tp < 1:
+            mz = z.max(-1, keepdim=True).values
+            live = keep & (mz != float("-inf"))                                   # a row of -inf only keeps everything
+            q = torch.where(live, (torch.exp(z - mz) * 2.0 ** 40).nan_to_num(0.0).to(torch.int64), 0)
+            P = torch.ceil(q.sum(-1, keepdim=True).double() * tp).to(torch.int64)
+            zs, order = torch.sort(torch.where(keep, z, ninf), dim=-1, descending=True, stable=True)
+            first = (q.gather(-1, order).cumsum(-1) >= P).to(torch.int8).argmax(-1, keepdim=True)
+            tau = zs.gather(-1, first)                                            # the largest z whose upper mass reaches P
+            keep = torch.where(live.any(-1, keepdim=True), keep & (z >= tau), keep)
+        s = int(seed) & 0xFFFFFFFFFFFFFFFF
+        r = torch.arange(R, device=dev, dtype=torch.int64).unsqueeze(1)
+        p = pos.reshape(1, 1).to(torch.int64) & _M32
+        rh = _hash32(_hash32((s & _M32) ^ _mul32(r, 0x9E3779B1)) ^ (s >> 32) ^ _mul32(p, 0x85EBCA77))
+        h = _hash32(rh ^ _mul32(torch.arange(V, device=dev, dtype=torch.int64).unsqueeze(0), 0xC2B2AE3D))
+        u = ((h >> 9).to(torch.float32) + 0.5) * 2.0 ** -23
+        tok = torch.where(keep, z + -torch.log(-torch.log(u)), ninf).argmax(-1)
+    lp = torch.log_softmax(x, -1).gather(1, tok.unsqueeze(1)).squeeze(1)
+    if out is None:
+        return tok.to(torch.int32), lp
+    out[0].copy_(tok)
+    out[1].copy_(lp)
+    return out[0], out[1]
+
+
+def _sample_args(logits: torch.Tensor, pos: torch.Tensor, R: int, n: int, inv_t, tp: float, top_k: int, seed: int) -> L.SampleArgs:
+    a = L.SampleArgs()
+    a.R, a.n, a.V = R, n, logits.shape[1]
+    a.logits_dtype = L.MOPK_BF16 if logits.dtype == torch.bfloat16 else L.MOPK_F32
+    a.top_k = min(int(top_k), a.V)
+    a.greedy, a.inv_temp, a.top_p = int(inv_t is None), 1.0 if inv_t is None else inv_t, tp
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.logits, a.logits_sb, a.logits_sk, a.pos = logits.data_ptr(), logits.stride(0), 0, pos.data_ptr()
+    return a
+
+
+def sample_tokens_supported(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                            seed: int = 0, out=None) -> bool:
+    """True if mopk_sample_* take this call: CUDA fp32 / bf16 logits with unit inner stride, an int32 device pos, contiguous CUDA
+    out buffers (the library's own query decides the rest: 2 <= V <= 2^24).  Raises ValueError on bad arguments."""
+    R, n, inv_t, tp = _sample_check(logits, pos, temperature, top_k, top_p, out, "sample_tokens_supported")
+    if not logits.is_cuda or logits.dtype not in (torch.float32, torch.bfloat16) or logits.stride(-1) != 1:
+        return False
+    if not pos.is_cuda or pos.dtype != torch.int32:
+        return False
+    if out is not None and not all(t.is_cuda and t.is_contiguous() for t in out):
+        return False
+    return bool(L.lib().mopk_sample_supported(C.byref(_sample_args(logits, pos, R, n, inv_t, tp, top_k, seed))))
+
+
+def sample_tokens(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                  seed: int = 0, out=None):
+    """draw one token per row from last-position logits -> (tokens int32 (R,), logprobs fp32 (R,)).  Inference only.
+
+    logits: (R, V), or (R / n, V) shared by each item's n rows (then pass out buffers of R rows: row r reads logit row r // n);
+    fp32 or bf16.  pos: (1,) int32 device tensor, the position of the token being chosen (the decoder cache's length after the step
+    that produced the logits).  Per row r:
+    - temperature == 0: argmax, ties to the smaller index (torch.argmax);
+    - else z = x * inv_t with inv_t = 1 / temperature rounded to fp32 once; top_k > 0 keeps z >= the k-th largest z (counted with
+      multiplicity, ties kept; top_k >= V is off); top_p < 1 keeps z >= tau, the largest z_u whose kept upper set
+      {z_v >= z_u} holds at least top_p of the kept softmax mass.  The mass is fixed-point, q_v = int(exp(z_v - max z) * 2^40), and
+      the test is sum q >= ceil(top_p * Q) in float64, so the threshold does not depend on summation order.  The rule is
+      tie-inclusive (HF's top-p cuts a tie group by sort order instead) and never empty;
+    - the draw is a Gumbel-max, argmax over the kept v of z_v - log(-log(u_v)) (ties to the smaller v): an exact sample of
+      softmax(z) over the kept set.  u_v = ((h >> 9) + 0.5) * 2^-23, with h a hash of (seed, r, pos, v) built on common.h's fa_hash.
+      It is a pure function of (logits, pos, seed, r);
+    - logprobs[r] = log_softmax(float(x))[token] on the unscaled, unfiltered row (Whisper's sum_logprobs convention).
+    out: static (tokens, logprobs) buffers, written in place (graph capture).  Runs the HIP kernel (mopk_sample_step) when
+    sample_tokens_supported() accepts the call, else sample_tokens_torch(); LAST_PATH["sample"] records which.  No host sync."""
+    R, n, inv_t, tp = _sample_check(logits, pos, temperature, top_k, top_p, out, "sample_tokens")
+    with torch.no_grad():
+        if not sample_tokens_supported(logits, pos, temperature, top_k, top_p, seed, out):
+            LAST_PATH["sample"] = L.PATH_GENERIC
+            return sample_tokens_torch(logits, pos, temperature, top_k, top_p, seed, out)
+        if out is None:
+            out = (torch.empty(R, dtype=torch.int32, device=logits.device), torch.empty(R, dtype=torch.float32, device=logits.device))
+        a = _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed)
+        a.tokens, a.logprobs = out[0].data_ptr(), out[1].data_ptr()
+        ws_bytes = L.lib().mopk_sample_workspace_bytes(C.byref(a))
+        ws = _bytes(ws_bytes, logits.device) if ws_bytes else None
+        a.workspace = _ptr(ws)
+        LAST_PATH["sample"] = L.PATH_FUSED
+        _launch("mopk_sample_step", a, "sample")
+        return out[0], out[1]

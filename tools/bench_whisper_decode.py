@@ -8,6 +8,8 @@
     python tools/bench_whisper_decode.py --stats DIR/<host>/<pid>_kernel_stats.csv   # decode kernels against the byte bound
     python tools/bench_whisper_decode.py --workload beam --out profiles/whisper_beam_bench.jsonl   # beam search, K = 5
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload beam-trace
+    python tools/bench_whisper_decode.py --workload sample --out profiles/whisper_sample_bench.jsonl   # sampling against greedy
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload sample-trace
 
 Model: d = 512, H = 8, 6 + 6 layers, T_a = 1500, vocab 51865 (Whisper-base-like), fp32 parameters under bf16 autocast, prompt 4,
 220 new tokens, B in {1, 8}.  Variants: (a) naive: decode(enc, whole prefix) per token; (b) cached eager: generate(); (c) cached +
@@ -20,6 +22,9 @@ Beam: K = 5, B in {1, 8}, same model, prompt and length.  Variants: (a) torch_be
 no eos); (b) beam_search eager; (c) beam_search(graph=True).  beam-trace runs (b) at B = 8 for rocprofv3; --stats then also prints
 the beam kernels (bs_*) and the row-indirect attention (da_* with ROWS) next to their byte bounds: B K V 2 bytes of bf16 logits per
 step, and 2 B K L H dk 2 + 4 B K L bytes of K, V and row table per layer and step at the mean length L = T_p + 110.
+Sample: temperature 0.7, top_k 50, top_p 0.95, n in {1, 5} samples per item, B in {1, 8}, same model, prompt and length.  Variants:
+(a) generate(graph=True), the greedy baseline; (b) sample eager; (c) sample(graph=True).  sample-trace runs (c) at B = 8, n = 1 and
+n = 5 for rocprofv3; --stats then also prints the sampling kernel (sp_row_kernel).
 """
 from __future__ import annotations
 
@@ -161,6 +166,44 @@ def bench_beam_trace(args):
     torch.cuda.synchronize()
 
 
+SAMPLE_CFG = dict(temperature=0.7, top_k=50, top_p=0.95)
+
+
+def bench_sample(args):
+    import torch
+    m = _base_model()
+    for B in args.batch:
+        mel = torch.randn(B, TA, NMELS, device="cuda")
+        prompt = torch.randint(0, VOCAB, (B, TP), device="cuda")
+        for n in (1, 5):
+            outs = {}
+            for name, fn in (("generate_graph", lambda: m.generate(mel, prompt, NEW, graph=True)),
+                             ("sample", lambda: m.sample(mel, prompt, NEW, num_samples=n, **SAMPLE_CFG)),
+                             ("sample_graph", lambda: m.sample(mel, prompt, NEW, num_samples=n, graph=True, **SAMPLE_CFG))):
+                if name == "generate_graph" and n != 1:
+                    continue
+                with torch.autocast("cuda", dtype=torch.bfloat16):
+                    ms = _time(lambda: outs.__setitem__(name, fn()), args.steps, args.warmup)
+                _emit(args, dict(workload="whisper_sample", variant=name, n=n, B=B, T_a=TA, T_p=TP, new_tokens=NEW, d=D, H=H,
+                                 layers="6+6", vocab=VOCAB, dtype="bf16-autocast", **SAMPLE_CFG, total_ms=round(ms, 3),
+                                 ms_per_token=round(ms / NEW, 4), steps=args.steps, warmup=args.warmup))
+            _emit(args, dict(workload="whisper_sample_agreement", n=n, B=B,
+                             graph_equals_eager=bool(torch.equal(outs["sample"][0], outs["sample_graph"][0]) and
+                                                     torch.equal(outs["sample"][1], outs["sample_graph"][1]))))
+
+
+def bench_sample_trace(args):
+    import torch
+    m = _base_model()
+    mel = torch.randn(8, TA, NMELS, device="cuda")
+    prompt = torch.randint(0, VOCAB, (8, TP), device="cuda")
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        for n in (1, 5):
+            for _ in range(2):
+                m.sample(mel, prompt, NEW, num_samples=n, graph=True, **SAMPLE_CFG)
+    torch.cuda.synchronize()
+
+
 def _core_inputs(Nk):
     import torch
     B = 8
@@ -208,7 +251,7 @@ def stats(path):
     rows = list(csv.DictReader(open(path)))
     for r in rows:
         if "da_" in r["Name"] or "sdpa" in r["Name"] or "attention" in r["Name"].lower() or "fmha" in r["Name"].lower() \
-                or "bs_" in r["Name"]:
+                or "bs_" in r["Name"] or "sp_row" in r["Name"]:
             print(f"{float(r['AverageNs']) / 1e3:9.2f} us  x{r['Calls']:>5}  {r['Name'][:150]}")
     B, K, L = 8, 5, TP + NEW // 2
     print(f"beam bounds at B = {B}, K = {K}: logits {B * K * VOCAB * 2 / HBM_BPS * 1e6:.2f} us; row-indirect attention per layer at "
@@ -217,7 +260,8 @@ def stats(path):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["generate", "core", "core-trace", "beam", "beam-trace"], default="generate")
+    ap.add_argument("--workload", choices=["generate", "core", "core-trace", "beam", "beam-trace", "sample",
+                                                        "sample-trace"], default="generate")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
@@ -229,7 +273,7 @@ def main():
     if args.stats:
         return stats(args.stats)
     {"generate": bench_generate, "core": bench_core, "core-trace": bench_core_trace, "beam": bench_beam,
-     "beam-trace": bench_beam_trace}[args.workload](args)
+     "beam-trace": bench_beam_trace, "sample": bench_sample, "sample-trace": bench_sample_trace}[args.workload](args)
 
 
 if __name__ == "__main__":
