@@ -58,7 +58,8 @@ __device__ __forceinline__ bool is_blocked(const MaskSpec &m, int b, int h, int 
     if (m.mask && m.mask[b * m.msb + h * m.msh + i * m.msi + j] == 0) return true;
     return false;
 }
-// in-place-capable: out = softmax_j(in + bias) over non-blocked j ; one wave per row
+// in-place-capable: out = softmax_j(in + bias) over non-blocked j ; one wave per row.  A row with no open key of finite logit (all
+// blocked, or an all -inf bias) is 0, as torch's SDPA gives: no exp(-inf - -inf) = NaN, and its backward is 0 too.
 __global__ void masked_softmax_kernel(const float *in, float *out, Dm d, MaskSpec m) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= d.BH * d.N) return;
@@ -71,10 +72,11 @@ __global__ void masked_softmax_kernel(const float *in, float *out, Dm d, MaskSpe
     float mx = -INFINITY;
     for (int j = lane; j < d.Nk; j += 64) if (!is_blocked(m, b, h, i, j)) mx = fmaxf(mx, p[j] + (bp ? bp[j] : 0.f));
     mx = wave_max(mx);
+    if (mx == -INFINITY) mx = 0.f;                 // empty row: every exp below is exp(-inf) = 0
     float den = 0.f;
     for (int j = lane; j < d.Nk; j += 64) if (!is_blocked(m, b, h, i, j)) den += expf(p[j] + (bp ? bp[j] : 0.f) - mx);
     den = wave_sum(den);
-    const float inv = 1.f / den;
+    const float inv = den > 0.f ? 1.f / den : 0.f;
     for (int j = lane; j < d.Nk; j += 64)
         o[j] = is_blocked(m, b, h, i, j) ? 0.f : expf(p[j] + (bp ? bp[j] : 0.f) - mx) * inv;
 }
@@ -249,10 +251,11 @@ __global__ void dp_mix_fwd_kernel(MopkDualPathArgs a, Dm d, DpBuf b, const float
         P[j] = sm; mx = fmaxf(mx, sm);
     }
     mx = wave_max(mx);
+    if (mx == -INFINITY) mx = 0.f;                 // every key blocked: a zero row (masked_softmax_kernel)
     float den = 0.f;
     for (int j = lane; j < d.N; j += 64) { const float e = expf(P[j] - mx); P[j] = e; den += e; }
     den = wave_sum(den);
-    const float inv = 1.f / den;
+    const float inv = den > 0.f ? 1.f / den : 0.f;
     for (int j = lane; j < d.N; j += 64) P[j] *= inv;
 }
 template <typename T>

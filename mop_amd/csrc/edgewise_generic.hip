@@ -442,10 +442,11 @@ __global__ void mix_fwd_kernel(MopkEdgewiseArgs a, EwDims d, EwSaved s) {
         P[j] = sm; mx = fmaxf(mx, sm);
     }
     mx = wave_max(mx);
+    if (mx == -INFINITY) mx = 0.f;                                      // every key masked: a zero row, as torch's SDPA gives
     float den = 0.f;
     for (int j = lane; j < d.N; j += 64) { float e = expf(P[j] - mx); P[j] = e; den += e; }
     den = wave_sum(den);
-    const float inv = 1.f / den;
+    const float inv = den > 0.f ? 1.f / den : 0.f;
     for (int j = lane; j < d.N; j += 64) P[j] *= inv;
 }
 

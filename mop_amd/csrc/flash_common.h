@@ -5,7 +5,9 @@
 namespace mopk {
 namespace {   // internal linkage: each translation unit gets its own copies
 constexpr int FA_NW = 4, FA_QB = 32 * FA_NW, FA_KT = 64, FA_LDT = FA_KT + 8;
-constexpr float FA_NEG = -1e30f, FA_LOG2E = 1.4426950408889634f, FA_LN2 = 0.6931471805599453f;
+constexpr float FA_NEG = -1e30f, FA_LOG2E = 1.4426950408889634f;
+// 1 / sqrt(dk) of the fused head dims; sdpa_flash.hip applies the softmax scale to the fp32 MFMA scores
+template <int DK> constexpr float FA_RSQ = DK == 64 ? 0.125f : 0.17677669529663688f;
 
 __device__ __forceinline__ f32x16 fa_zero() { return f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; }
 __device__ __forceinline__ void fa_pack(bf16x8 &lo, bf16x8 &hi, const f32x16 &x) {

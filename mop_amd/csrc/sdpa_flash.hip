@@ -49,17 +49,17 @@ __device__ __forceinline__ FaMB fa_mb(const MopkSdpaArgs &a, int b, int hh) {
     m.bias = a.bias ? a.bias + b * a.bias_sb + hh * a.bias_sh : nullptr;
     return m;
 }
-// one element (query i < N, key j < Nk): logit (base-2 units) -> logit + bias, or FA_NEG when blocked.  Written as selects on unconditionally loaded
+// one element (query i < N, key j < Nk): score -> score * cz + bias (base-2 units), or FA_NEG when blocked.  Written as selects on unconditionally loaded
 // values (indices clamped into range): a per-lane branch around an element write of the accumulator vector is miscompiled
 // by hipcc 7.2 (the taken path clobbers the other 15 elements).
-__device__ __forceinline__ float fa_apply_mb(float z, const FaMB &m, const MopkSdpaArgs &a, int i, int j, int Nk, bool &blocked) {
+__device__ __forceinline__ float fa_apply_mb(float z, float cz, const FaMB &m, const MopkSdpaArgs &a, int i, int j, int Nk, bool &blocked) {
     const int ic = min(i, a.N - 1), jc = min(j, Nk - 1);
     float bz = 0.f;
     unsigned int keep = 1;
     if (m.bias) bz = m.bias[(int64_t)ic * a.bias_si + jc] * FA_LOG2E;          // wave-uniform pointer tests
     if (m.mask) keep = m.mask[(int64_t)ic * a.mask_si + jc];
     blocked = keep == 0;
-    return blocked ? FA_NEG : z + bz;
+    return blocked ? FA_NEG : fmaf(z, cz, bz);
 }
 }  // namespace
 
@@ -76,14 +76,17 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
     const int q0 = qb * FA_QB, qi = q0 + 32 * w + r;
     const int wu = __builtin_amdgcn_readfirstlane(w);              // the wave index as a scalar (uniform branches on it)
     const bool qok = qi < N;
-    const float c = rsqrtf((float)DK) * FA_LOG2E;                  // logits in base-2 units: exp2 without a multiply
+    // logits in base-2 units: the scale c = log2(e) / sqrt(dk) multiplies the fp32 scores (q stays as given).  Plain
+    // scores stay raw until the exp2 argument (an fma in place of the subtraction); bias / mask and the dual mix scale them first.
+    constexpr bool RAW = !DUAL && !MB;
+    constexpr float c = FA_RSQ<DK> * FA_LOG2E, ce = RAW ? c : 1.f;
     const IOT *kp = (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh, *vp = (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh;
     bf16x8 qe[DK / 16];
-    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, c);
+    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, 1.f);
     bf16x8 q2e[DUAL ? DK / 16 : 1];
     const IOT *k2p = nullptr;
     if (DUAL) {
-        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)u.q2.ptr + b * u.q2.sb + hh * u.q2.sh + (int64_t)qi * u.q2.sn, qok, h, c);
+        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)u.q2.ptr + b * u.q2.sb + hh * u.q2.sh + (int64_t)qi * u.q2.sn, qok, h, 1.f);
         k2p = (const IOT *)u.k2.ptr + b * u.k2.sb + hh * u.k2.sh;
     }
     const FaMB mb = fa_mb(a, b, hh);
@@ -120,11 +123,11 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
             if (DUAL) {
                 const f32x16 T2 = fa_mm_rows<DK>(K2s, 32 * s2, r, h, *(const bf16x8(*)[DK / 16]) & q2e);
 #pragma unroll
-                for (int g = 0; g < 16; ++g) S[s2][g] = fa_mix(S[s2][g], T2[g], u.a2, u.g_or);
+                for (int g = 0; g < 16; ++g) S[s2][g] = fa_mix(S[s2][g] * c, T2[g] * c, u.a2, u.g_or);   // lse2 needs base-2 units
             }
             if (MB) {
 #pragma unroll
-                for (int g = 0; g < 16; ++g) { bool blk; S[s2][g] = fa_apply_mb(S[s2][g], mb, a, qi, k0 + 32 * s2 + tile_row(g, h), Nk, blk); }
+                for (int g = 0; g < 16; ++g) { bool blk; S[s2][g] = fa_apply_mb(S[s2][g], DUAL ? 1.f : c, mb, a, qi, k0 + 32 * s2 + tile_row(g, h), Nk, blk); }
             }
             if (edge) {                         // wave-uniform: only tiles that touch the end of the keys or this wave's diagonal pay for the mask
 #pragma unroll
@@ -137,12 +140,12 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
             for (int g = 0; g < 16; ++g) mx = fmaxf(mx, S[s2][g]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mn = fmaxf(m, mx), alpha = __builtin_amdgcn_exp2f(m - mn);
+        const float mn = fmaxf(m, mx * ce), alpha = __builtin_amdgcn_exp2f(m - mn);
         float ps = 0.f;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-            for (int g = 0; g < 16; ++g) { const float p = __builtin_amdgcn_exp2f(S[s2][g] - mn); S[s2][g] = p; ps += p; }
+            for (int g = 0; g < 16; ++g) { const float p = __builtin_amdgcn_exp2f(fmaf(S[s2][g], ce, -mn)); S[s2][g] = p; ps += p; }
         ps += __shfl_xor(ps, 32, 64);
         l = fmaf(l, alpha, ps);
         m = mn;
@@ -164,8 +167,11 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
         }
     }
     if (qok) {
-        fa_store_rows<DK, IOT>((IOT *)a.y.ptr + b * a.y.sb + hh * a.y.sh + (int64_t)qi * a.y.sn, O, h, 1.f / l);
-        if (h == 0) lse[(int64_t)bh * N + qi] = m + __builtin_amdgcn_logf(l);     // log2 of the row sum of 2^(logit)
+        // no open key with a finite logit (every key blocked, or an all -inf bias): the row is 0, as torch's SDPA gives, and lse = +inf
+        // makes the backward's P = 2^(z - lse) exactly 0 on it.  (The sum over blocked keys still in O and l is finite: 0 * O = 0.)
+        const bool empty = m == FA_NEG;
+        fa_store_rows<DK, IOT>((IOT *)a.y.ptr + b * a.y.sb + hh * a.y.sh + (int64_t)qi * a.y.sn, O, h, empty ? 0.f : 1.f / l);
+        if (h == 0) lse[(int64_t)bh * N + qi] = empty ? INFINITY : m + __builtin_amdgcn_logf(l);     // log2 of the row sum of 2^(logit)
     }
 }
 
@@ -215,15 +221,16 @@ __global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_d
     const int b = bh / a.H, hh = bh % a.H;
     const int q0 = qb * FA_QB, qi = q0 + 32 * w + r;
     const bool qok = qi < N;
-    const float sc = rsqrtf((float)DK), c = sc * FA_LOG2E;
+    constexpr bool RAW = !DUAL && !MB;                             // scale of the fp32 scores as in the forward
+    constexpr float sc = FA_RSQ<DK>, c = sc * FA_LOG2E, ce = RAW ? c : 1.f;
     const IOT *kp = (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh, *vp = (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh;
     bf16x8 qe[DK / 16], dof[DK / 16];
-    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, c);
+    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, 1.f);
     fa_frags<DK, IOT>(dof, (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh + (int64_t)qi * a.dy.sn, qok, h, 1.f);
     bf16x8 q2e[DUAL ? DK / 16 : 1];
     const IOT *k2p = nullptr;
     if (DUAL) {
-        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)u.q2.ptr + b * u.q2.sb + hh * u.q2.sh + (int64_t)qi * u.q2.sn, qok, h, c);
+        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)u.q2.ptr + b * u.q2.sb + hh * u.q2.sh + (int64_t)qi * u.q2.sn, qok, h, 1.f);
         k2p = (const IOT *)u.k2.ptr + b * u.k2.sb + hh * u.k2.sh;
     }
     const float Li = qok ? lse[(int64_t)bh * N + qi] : 0.f, di = qok ? delta[(int64_t)bh * N + qi] : 0.f;
@@ -262,13 +269,14 @@ __global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_d
             for (int g = 0; g < 16; ++g) {
                 const int j = k0 + 32 * s2 + tile_row(g, h);
                 bool ok = qok && j < Nk && (!CAUSAL || j <= qi);
-                float z = DUAL ? fa_mix(S[g], T2[g], u.a2, u.g_or) : S[g];
-                if (MB) { bool blk; z = fa_apply_mb(z, mb, a, qi, j, Nk, blk); ok = ok && !blk; }
-                const float p = ok ? __builtin_amdgcn_exp2f(z - Li) : 0.f;
+                const float s1 = DUAL ? S[g] * c : S[g], s2 = DUAL ? T2[g] * c : 0.f;
+                float z = DUAL ? fa_mix(s1, s2, u.a2, u.g_or) : s1;
+                if (MB) { bool blk; z = fa_apply_mb(z, DUAL ? 1.f : c, mb, a, qi, j, Nk, blk); ok = ok && !blk; }
+                const float p = ok ? __builtin_amdgcn_exp2f(fmaf(z, ce, -Li)) : 0.f;
                 float dp = dP[g];                                // dropout: dP = (dy v^T) keep / (1 - p); delta = dy . y already has it
                 if (drop.thresh) dp = fa_drop_keep(drop, rowh, j) ? dp * drop.inv_keep : 0.f;
                 const float dz = p * (dp - di) * sc;             // d logits / sqrt(dk)
-                if (DUAL) { float c1, c2; fa_mix_grad(S[g], T2[g], u.a2, u.g_or, c1, c2); dS[g] = dz * c1; dS2[g] = dz * c2; }
+                if (DUAL) { float c1, c2; fa_mix_grad(s1, s2, u.a2, u.g_or, c1, c2); dS[g] = dz * c1; dS2[g] = dz * c2; }
                 else dS[g] = dz;
             }
             bf16x8 lo, hi;
@@ -298,7 +306,8 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
     const int b = bh / a.H, hh = bh % a.H;
     const int k0 = kb * FA_QB, kj = k0 + 32 * w + r;
     const bool kok = kj < Nk;
-    const float c = rsqrtf((float)DK) * FA_LOG2E;
+    constexpr bool RAW = !DUAL && !MB;                             // scale of the fp32 scores as in the forward
+    constexpr float sc = FA_RSQ<DK>, c = sc * FA_LOG2E, ce = RAW ? c : 1.f;
     const IOT *qp = (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh, *gp = (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh;
     bf16x8 kf[DK / 16], vf[DK / 16];
     fa_frags<DK, IOT>(kf, (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh + (int64_t)kj * a.k.sn, kok, h, 1.f);
@@ -315,10 +324,10 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
     const FaMB mb = fa_mb(a, b, hh);
     const FaDrop drop = fa_drop(a.dropout_p, a.dropout_seed);
     const int nqt = (N + FA_KT - 1) / FA_KT, qt0 = CAUSAL ? k0 / FA_KT : 0;   // causal: queries before this key block see none of its keys
-    FaTile<DK> fq, fg, fq2;               // q is pre-scaled exactly as the forward's fragments
-    fa_fetch<DK, IOT>(fq, qp, a.q.sn, qt0 * FA_KT, N, c, tid);
+    FaTile<DK> fq, fg, fq2;
+    fa_fetch<DK, IOT>(fq, qp, a.q.sn, qt0 * FA_KT, N, 1.f, tid);
     fa_fetch<DK, IOT>(fg, gp, a.dy.sn, qt0 * FA_KT, N, 1.f, tid);
-    if (DUAL) fa_fetch<DK, IOT>(fq2, q2p, u.q2.sn, qt0 * FA_KT, N, c, tid);
+    if (DUAL) fa_fetch<DK, IOT>(fq2, q2p, u.q2.sn, qt0 * FA_KT, N, 1.f, tid);
     // the tile's row statistics travel with the prefetch too (loaded between the barriers they cost one exposed round trip per tile)
     float nl = 0.f, nd = 0.f;
     auto fetch_stats = [&](int i0) {
@@ -335,9 +344,9 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
         if (DUAL) fa_put<DK, true, true>(Q2s, Q2t, fq2, tid);
         if (tid < FA_KT) { Ls[tid] = nl; Ds[tid] = nd; Hs[tid] = fa_drop_row(drop, bh, i0 + tid); }
         if (qt + 1 < nqt) {
-            fa_fetch<DK, IOT>(fq, qp, a.q.sn, i0 + FA_KT, N, c, tid);
+            fa_fetch<DK, IOT>(fq, qp, a.q.sn, i0 + FA_KT, N, 1.f, tid);
             fa_fetch<DK, IOT>(fg, gp, a.dy.sn, i0 + FA_KT, N, 1.f, tid);
-            if (DUAL) fa_fetch<DK, IOT>(fq2, q2p, u.q2.sn, i0 + FA_KT, N, c, tid);
+            if (DUAL) fa_fetch<DK, IOT>(fq2, q2p, u.q2.sn, i0 + FA_KT, N, 1.f, tid);
             fetch_stats(i0 + FA_KT);
         }
         __syncthreads();
@@ -359,14 +368,15 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
             for (int g = 0; g < 16; ++g) {
                 const int il = 32 * s2 + tile_row(g, h), i = i0 + il;
                 bool ok = kok && i < N && (!CAUSAL || kj <= i);
-                float z = DUAL ? fa_mix(S[g], T2[g], u.a2, u.g_or) : S[g];
-                if (MB) { bool blk; z = fa_apply_mb(z, mb, a, i, kj, Nk, blk); ok = ok && !blk; }
-                const float p = ok ? __builtin_amdgcn_exp2f(z - lrow[g]) : 0.f;
+                const float s1 = DUAL ? S[g] * c : S[g], s2 = DUAL ? T2[g] * c : 0.f;
+                float z = DUAL ? fa_mix(s1, s2, u.a2, u.g_or) : s1;
+                if (MB) { bool blk; z = fa_apply_mb(z, DUAL ? 1.f : c, mb, a, i, kj, Nk, blk); ok = ok && !blk; }
+                const float p = ok ? __builtin_amdgcn_exp2f(fmaf(z, ce, -lrow[g])) : 0.f;
                 float dp = dP[g], pd = p;                         // dropout: dV sees P keep / (1 - p), dP = (dy v^T) keep / (1 - p)
                 if (drop.thresh) { const float kp = fa_drop_keep(drop, Hs[il], kj) ? drop.inv_keep : 0.f; dp *= kp; pd *= kp; }
                 P[g] = pd;
-                const float dz = p * (dp - drow[g]) * FA_LN2;     // Q' = q log2(e)/sqrt(dk)  ->  dK = (dS ln2)^T Q'
-                if (DUAL) { float c1, c2; fa_mix_grad(S[g], T2[g], u.a2, u.g_or, c1, c2); dS[g] = dz * c1; dS2[g] = dz * c2; }
+                const float dz = p * (dp - drow[g]) * sc;         // d logits / sqrt(dk): dK = dS^T Q
+                if (DUAL) { float c1, c2; fa_mix_grad(s1, s2, u.a2, u.g_or, c1, c2); dS[g] = dz * c1; dS2[g] = dz * c2; }
                 else dS[g] = dz;
             }
             bf16x8 lo, hi;

@@ -681,6 +681,13 @@ def _mask_u8(attn_mask, B, H, N, dev, Nk=None):
     return m, (m.stride(0), m.stride(1), m.stride(2))
 
 
+def _refuse_bias_grad(t: Optional[torch.Tensor], what: str) -> None:
+    """the cores return no gradient for an additive bias: one that would take part in autograd is an error, not a silent zero"""
+    if t is not None and torch.is_grad_enabled() and t.requires_grad:
+        raise NotImplementedError(f"{what} requires grad, but the attention cores compute no gradient for it; pass {what}.detach() "
+                                  f"or call under torch.no_grad()")
+
+
 def _bias_f32(bias, B, H, N, dev, Nk=None):
     if bias is None:
         return None, (0, 0, 0)
@@ -800,8 +807,11 @@ def sdpa_core(q, k=None, v=None, attn_mask=None, bias=None, causal=False, dropou
     """q: (B,N,H,dk), k, v: (B,Nk,H,dk) views -- Nk != N is rectangular (cross-)attention: N queries attend to Nk keys -- or packed:
     q = the (B,N,3,H,dk) output of one qkv projection, k = v = None (square; one packed gradient comes back).  Returns (B,N,H*dk).
     attn_mask: 0 = blocked; bias: additive; both broadcastable to (B,H,N,Nk).  causal needs Nk == N (ValueError otherwise).
+    A row with no open key (every key blocked, or a bias of -inf at every key) is 0, as in torch's SDPA.  bias gets no gradient:
+    one that requires grad under grad mode raises NotImplementedError.
     dropout_p > 0: the probabilities are multiplied by keep / (1 - p) (mask = `dropout_keep_mask(seed, B, H, N, Nk)`, seed drawn
     when None)."""
+    _refuse_bias_grad(bias, "sdpa_core: bias")
     if k is not None:
         if k.dim() != 4 or v is None or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2:] != q.shape[2:]:
             raise ValueError(f"sdpa_core: k, v must be (B, Nk, H, dk) with q's B, H, dk; got q {tuple(q.shape)}, k {tuple(k.shape)}, "
@@ -1148,6 +1158,7 @@ class _QuartetFn(torch.autograd.Function):
 @_half_via_fp32
 def quartet_core(q, k, v, q2, k2, mixture, quartet_scale, add_mask, eps, use_quartet, need_weights=False,
                  dropout_p: float = 0.0, seed: Optional[int] = None):
+    _refuse_bias_grad(add_mask, "quartet_core: add_mask")      # add_mask gets no gradient
     if q.shape[0] == 0:                   # q: (B,T,H,dk)
         out = _empty_batch(q, 0, q.shape[1], q.shape[2] * q.shape[3])
         return (out, q.new_zeros((0, q.shape[2], q.shape[1], q.shape[1]), dtype=torch.float32)) if need_weights else out

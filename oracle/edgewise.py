@@ -40,6 +40,18 @@ def _softmax(x: np.ndarray, axis: int = -1) -> np.ndarray:
     return e / e.sum(axis=axis, keepdims=True)
 
 
+def _masked_softmax(S, blocked):
+    """softmax over the keys that `blocked` leaves open.  A row with none open is 0, as torch's SDPA gives -- deliberately not the
+    reference's NaN (the empty-row convention of DESIGN.md)."""
+    if blocked is None:
+        return _softmax(S, -1)
+    Sm = np.where(blocked, -np.inf, S)
+    m = Sm.max(-1, keepdims=True)
+    e = np.where(blocked, 0.0, np.exp(Sm - np.where(np.isfinite(m), m, 0.0)))
+    den = e.sum(-1, keepdims=True)
+    return np.divide(e, den, out=np.zeros_like(e), where=den > 0)
+
+
 def _sigmoid(x):
     return 1.0 / (1.0 + np.exp(-x))
 
@@ -160,9 +172,7 @@ def core_fwd(qv, kv, v0, vL, Wr, br, Wc, bc, beta_not, chain_logit, dense=None, 
     S = np.matmul(qv, np.swapaxes(kv, -1, -2)) * scale          # :500-503  (V,B,H,N,N)
     if blocked is not None:
         blocked = np.broadcast_to(np.asarray(blocked, dtype=bool), S.shape[1:])
-        Sm = np.where(blocked[None], -np.inf, S)
-        e = np.where(blocked[None], 0.0, np.exp(Sm - Sm.max(-1, keepdims=True)))
-        A = e / e.sum(-1, keepdims=True)                          # :504-507
+        A = _masked_softmax(S, blocked[None])                     # :504-507
     else:
         A = _softmax(S, -1)                                       # :507
     T = [A[0]]                                                    # :508-512 prefix products
@@ -211,9 +221,7 @@ def core_fwd(qv, kv, v0, vL, Wr, br, Wc, bc, beta_not, chain_logit, dense=None, 
     Smix = S0 + G[:, :, 0] * O + G[:, :, 1] * (lse - S0) - G[:, :, 2] * (nb * O) \
         + G[:, :, 3] * Cr                                         # :543-547
     if blocked is not None:
-        Sx = np.where(blocked, -np.inf, Smix)                     # :549-550
-        e = np.where(blocked, 0.0, np.exp(Sx - Sx.max(-1, keepdims=True)))
-        P = e / e.sum(-1, keepdims=True)
+        P = _masked_softmax(Smix, blocked)                        # :549-550
     else:
         P = _softmax(Smix, -1)                                    # :551
     Pd = P if drop is None else P * drop                          # :552 attn_drop with the mask made explicit: drop = keep / (1 - p)

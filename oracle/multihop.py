@@ -5,7 +5,8 @@ Restates reference `mop/models/attention_variants.py:163-231` (`MultiHopMSA`) an
 ``softmax(S1 + S2) v1 + sigmoid(w) * A1 A2^(hops-1) v2``.
 Backward is hand-derived and pinned against reference autograd (tests/golden).
 
-attn_mask: broadcastable to (B,H,N,N), 0 = blocked (:202-205, :219-220).
+attn_mask: broadcastable to (B,H,N,N), 0 = blocked (:202-205, :219-220).  A row with every key blocked
+attends to nothing (a zero row, torch SDPA's convention) where the reference gives NaN.
 """
 from __future__ import annotations
 
@@ -14,19 +15,10 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .edgewise import _heads, _sigmoid, _softmax
+from .edgewise import _heads, _masked_softmax, _sigmoid, _softmax
 
 EPS_CHAIN = 1e-6  # :217
 DEFAULT_GATES = dict(and_=1.0, or_=0.0, not_=0.0, chain=0.0, base=1.0)  # :188
-
-
-def _masked_softmax(S, blocked):
-    if blocked is None:
-        return _softmax(S, -1)
-    Sm = np.where(blocked, -np.inf, S)
-    m = Sm.max(-1, keepdims=True)
-    e = np.where(blocked, 0.0, np.exp(Sm - m))
-    return e / e.sum(-1, keepdims=True)
 
 
 def core_fwd(q1, k1, v1, q2, k2, v2, gates, beta_not, hops, chain_logit, blocked=None, drop=None):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from attn_ref import blocked_rows_mask
 from conftest import golden_names, load_golden, ref_bf16_error
 from gpu_util import check_grads, max_abs, module_from_golden, oracle_bf16_noise, rel_err, run_fwd_bwd
 
@@ -663,7 +664,7 @@ def test_fused_dense_head_forward_vs_reference_fixture():
 
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
 @pytest.mark.parametrize("variant", ["lowrank", "dense", "dense_k3"])
-@pytest.mark.parametrize("mask_kind", ["causal", "random"])
+@pytest.mark.parametrize("mask_kind", ["causal", "random", "blocked_rows"])
 def test_masked_edgewise_extension_vs_oracle(variant, mask_kind, prec):
     """attn_mask on EdgewiseMSA: the reference is NaN there (SURVEY.md 8a note); the documented extension (mask on the probabilities
     only, gate features from the unmasked scores; generic path) against the float64 oracle, whose masked backward is pinned by finite
@@ -686,9 +687,12 @@ def test_masked_edgewise_extension_vs_oracle(variant, mask_kind, prec):
         m.chain_value_logit.fill_(-0.5)
     if mask_kind == "causal":
         mask = torch.ones(N, N).tril_()
-    else:
+    elif mask_kind == "random":
         mask = (torch.rand(B, 1, N, N) > 0.4).float()
         mask[..., torch.arange(N), torch.arange(N)] = 1.0            # every query keeps at least one key
+    else:                              # rows with no open key (attend to nothing: a zero row), rows open at key 0 or N - 1 only
+        g = torch.Generator().manual_seed(41)
+        mask = torch.stack([blocked_rows_mask(N, N, g, "cpu") for _ in range(B)]).unsqueeze(1).float()
     params = {k: v.detach().numpy().astype(np.float64) for k, v in m.state_dict().items()}
     x = torch.randn(B, N, D).numpy()
     w = torch.randn(B, N, D).numpy()
