@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPK_VERSION 118 /* 118: mopk_sample_* and MopkSampleArgs (added later without a bump: new exports only, detect with mopk_sample_supported), mopk_decode_attn_rows_*, MopkDecodeAttnRowsArgs, mopk_beam_* and MopkBeamArgs (added later without a bump: new exports only, detect with mopk_decode_attn_rows_supported / mopk_beam_supported), mopk_decode_attn_* and MopkDecodeAttnArgs (added later without a bump: new exports only, detect with mopk_decode_attn_supported), mopk_moe_* and MopkMoeArgs (added later without a bump: new exports only, detect with mopk_moe_supported), MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
+#define MOPK_VERSION 118 /* 118: mopk_decode_attn_ragged_*, MopkDecodeAttnRaggedArgs, mopk_sample_ragged_* and MopkSampleRaggedArgs (added later without a bump: new exports only, detect with mopk_decode_attn_ragged_supported / mopk_sample_ragged_supported), mopk_sample_* and MopkSampleArgs (added later without a bump: new exports only, detect with mopk_sample_supported), mopk_decode_attn_rows_*, MopkDecodeAttnRowsArgs, mopk_beam_* and MopkBeamArgs (added later without a bump: new exports only, detect with mopk_decode_attn_rows_supported / mopk_beam_supported), mopk_decode_attn_* and MopkDecodeAttnArgs (added later without a bump: new exports only, detect with mopk_decode_attn_supported), mopk_moe_* and MopkMoeArgs (added later without a bump: new exports only, detect with mopk_moe_supported), MopkSdpaArgs.Nk appended (rectangular plain SDPA, 0 = N; added later without a bump, the number is pinned by the ABI tests: callers must be built against this header), mopk_token_gate_* (added later without a bump: new exports only, detect with mopk_token_gate_supported), attention dropout on every generic path, MopkCrossViewArgs.{dropout_p,dropout_seed}; 117: mopk_lens_means_{fwd,bwd}; 116: MopkEdgewiseExt.{n_extra,row_extra,col_extra,d_row_extra,d_col_extra}; 115: mask tensors on the fused dual-path kernels; 114: MopkEdgewiseArgs.mask (generic path), fused dense gate head; 113: attention dropout in the fused SDPA / Quartet kernels (dropout_p, dropout_seed, mopk_dropout_keep); 112: mopk_layernorm_*; 0.1.1: MopkEdgewiseArgs.{save_for_backward, ext}, MopkCrossViewArgs, *_fused_supported, y read by the sibling _bwd; 111: mopk_edgewise_reduce_parts */
 
 typedef enum MopkStatus {
     MOPK_OK = 0,
@@ -499,6 +499,23 @@ size_t mopk_decode_attn_rows_workspace_bytes(const MopkDecodeAttnRowsArgs *a);
 int mopk_decode_attn_rows_fwd(const MopkDecodeAttnRowsArgs *a, void *stream);
 
 /* --------------------------------------------------------------------------
+ * Ragged decode attention: prompts of different lengths left-padded in one cache.  (Added under version 118: new exports only;
+ * callers detect it with mopk_decode_attn_ragged_supported.)  Exactly mopk_decode_attn_fwd (rows == NULL) or
+ * mopk_decode_attn_rows_fwd (rows != NULL), except that query row b sees only the keys j >= s_b, s_b = kv_start[b] clamped into
+ * [0, L]: query i of row b sees s_b <= j < L (causal: < L - Tq + i + 1).  Key rows below s_b are not read; a query that sees no
+ * key gets y = 0.  With kv_start[b] = 0 the result is bitwise that of mopk_decode_attn_fwd / mopk_decode_attn_rows_fwd.
+ * kv_start: device int32 (B), 4-byte aligned, required.  Workspace: mopk_decode_attn_ragged_workspace_bytes() (that of base). */
+typedef struct MopkDecodeAttnRaggedArgs {
+    MopkDecodeAttnArgs base;             /* unchanged meaning */
+    const int32_t *rows;                 /* NULL: row b reads its own cache row; else as MopkDecodeAttnRowsArgs.rows */
+    int64_t rows_ld;                     /* as MopkDecodeAttnRowsArgs.rows_ld when rows != NULL */
+    const int32_t *kv_start;             /* device (B) int32, required: query row b sees keys j >= kv_start[b] */
+} MopkDecodeAttnRaggedArgs;
+int mopk_decode_attn_ragged_supported(const MopkDecodeAttnRaggedArgs *a);
+size_t mopk_decode_attn_ragged_workspace_bytes(const MopkDecodeAttnRaggedArgs *a);
+int mopk_decode_attn_ragged_fwd(const MopkDecodeAttnRaggedArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
  * One step of batched beam search (WhisperMoP.beam_search): updates the device beam state in place from the step's last-position
  * logits, with no host synchronisation, so a step can be captured once in a graph.  (Added under version 118: new exports only;
  * callers detect it with mopk_beam_supported.)  Per batch item b that is not done (done[b] == 0):
@@ -579,6 +596,19 @@ typedef struct MopkSampleArgs {
 int mopk_sample_supported(const MopkSampleArgs *a);                  /* 1 if the kernel takes this call (V, dtype, filters, strides) */
 size_t mopk_sample_workspace_bytes(const MopkSampleArgs *a);
 int mopk_sample_step(const MopkSampleArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
+ * Sampling of a ragged batch (prompts left-padded in one cache).  (Added under version 118: new exports only; callers detect it
+ * with mopk_sample_ragged_supported.)  Exactly mopk_sample_step, except that row r draws at position *pos - pos_off[r] instead of
+ * *pos (the hash's pos), so a row's draws depend on its own token index and not on its batch's padding.  With pos_off[r] = 0 the
+ * draw is bitwise that of mopk_sample_step.  pos_off: device int32 (R), 4-byte aligned, required. */
+typedef struct MopkSampleRaggedArgs {
+    MopkSampleArgs base;                 /* unchanged meaning */
+    const int32_t *pos_off;              /* device (R) int32, required: row r draws at *pos - pos_off[r] */
+} MopkSampleRaggedArgs;
+int mopk_sample_ragged_supported(const MopkSampleRaggedArgs *a);
+size_t mopk_sample_ragged_workspace_bytes(const MopkSampleRaggedArgs *a);
+int mopk_sample_ragged_step(const MopkSampleRaggedArgs *a, void *stream);
 
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);

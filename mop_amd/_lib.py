@@ -170,6 +170,12 @@ class DecodeAttnRowsArgs(C.Structure):
     _fields_ = [("base", DecodeAttnArgs), ("rows", _fp), ("rows_ld", C.c_int64)]
 
 
+class DecodeAttnRaggedArgs(C.Structure):
+    """MopkDecodeAttnRaggedArgs: decode attention in which query row b sees only the keys j >= kv_start[b] (left-padded prompts of
+    different lengths), optionally through a row table."""
+    _fields_ = [("base", DecodeAttnArgs), ("rows", _fp), ("rows_ld", C.c_int64), ("kv_start", _fp)]
+
+
 class BeamArgs(C.Structure):
     """MopkBeamArgs: one step of batched beam search over device state (WhisperMoP.beam_search)."""
     _fields_ = [
@@ -189,6 +195,11 @@ class SampleArgs(C.Structure):
         ("logits", _fp), ("logits_sb", C.c_int64), ("logits_sk", C.c_int64), ("pos", _fp), ("tokens", _fp), ("logprobs", _fp),
         ("workspace", _fp),
     ]
+
+
+class SampleRaggedArgs(C.Structure):
+    """MopkSampleRaggedArgs: sampling in which row r draws at position *pos - pos_off[r] (a left-padded ragged batch)."""
+    _fields_ = [("base", SampleArgs), ("pos_off", _fp)]
 
 
 SYMBOLS = {
@@ -250,6 +261,12 @@ SYMBOLS = {
     "mopk_sample_supported": (C.c_int, [C.POINTER(SampleArgs)]),
     "mopk_sample_workspace_bytes": (C.c_size_t, [C.POINTER(SampleArgs)]),
     "mopk_sample_step": (C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
+    "mopk_decode_attn_ragged_supported": (C.c_int, [C.POINTER(DecodeAttnRaggedArgs)]),
+    "mopk_decode_attn_ragged_workspace_bytes": (C.c_size_t, [C.POINTER(DecodeAttnRaggedArgs)]),
+    "mopk_decode_attn_ragged_fwd": (C.c_int, [C.POINTER(DecodeAttnRaggedArgs), C.c_void_p]),
+    "mopk_sample_ragged_supported": (C.c_int, [C.POINTER(SampleRaggedArgs)]),
+    "mopk_sample_ragged_workspace_bytes": (C.c_size_t, [C.POINTER(SampleRaggedArgs)]),
+    "mopk_sample_ragged_step": (C.c_int, [C.POINTER(SampleRaggedArgs), C.c_void_p]),
 }
 
 _lib = None

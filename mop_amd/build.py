@@ -40,6 +40,9 @@ def _hipcc() -> str:
 
 def _jobs():
     jobs = [(s, [], s.replace(".hip", ".o")) for s in PLAIN]
+    # the ragged sampling kernel is built in a unit of its own: beside it, the plain sp_row_kernel would allocate its registers
+    # differently (same instructions, permuted registers), and the plain kernel's code is kept exactly as it was
+    jobs.append(("sample.hip", ["-DMOPK_SAMPLE_RAGGED"], "sample_ragged.o"))
     for s in FUSED + FUSED_INST_ONLY:
         stem = s.replace(".hip", "")
         # fused bf16-MFMA kernels: relaxed fp (reassociation, contraction, approximate reciprocals) but inf/nan kept;

@@ -23,6 +23,12 @@
 // comes from cache row rows[b * rows_ld + j] (clamped into [0, B)) at position j.  Only the staging address changes: one int32 table
 // read per key, the key's dk elements still one run of 16-byte vectors, and every later step is the same code, so an identity table
 // gives bitwise the result of the plain kernels.
+//
+// Ragged variant (mopk_decode_attn_ragged_*, prompts of different lengths left-padded in one cache): START = true adds a per-row
+// first key, s = kv_start[b] clamped into [0, L]; query row b sees keys s <= j < its limit.  A chunk that lies wholly below s writes
+// the empty partial (as a chunk past L does), key rows below s are neither loaded nor scored, and a query with no open key ends as
+// y = 0 in the merge.  With kv_start = 0 every step is the plain code, so the result is bitwise that of the plain kernels; the
+// START = false instantiations compile to the same instructions as before the flag existed (kv_start is an unused argument there).
 #include "common.h"
 
 namespace mopk {
@@ -60,9 +66,10 @@ __device__ __forceinline__ void da_unpack(const uint4 &u, float (&f)[4], float) 
     f[2] = __builtin_bit_cast(float, u.z); f[3] = __builtin_bit_cast(float, u.w);
 }
 
-// launch 1: one (row, chunk) partial; ROWS: keys / values through the row table
-template <typename T, int DK, int TQB, bool ROWS>
-__global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs a, int nsplit, const int32_t *rows, int64_t rows_ld) {
+// launch 1: one (row, chunk) partial; ROWS: keys / values through the row table; START: keys from kv_start[b] on
+template <typename T, int DK, int TQB, bool ROWS, bool START>
+__global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs a, int nsplit, const int32_t *rows, int64_t rows_ld,
+                                                              const int32_t *kv_start) {
     using C = DaCfg<T, DK, TQB>;
     __shared__ uint4 tile[C::CH * C::PITCH];
     __shared__ float4 qs4[TQB * DK / 4];
@@ -81,7 +88,12 @@ __global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs
     float *ml = (float *)a.workspace + part * tq * 2;
     float *acc_out = (float *)a.workspace + (size_t)a.B * a.H * nsplit * tq * 2 + part * tq * DK;
     const int nv = L - c0 < C::CH ? L - c0 : C::CH;             // keys of this chunk any query can see (causal limits are <= L)
-    if (nv <= 0) {
+    int s0 = 0;                                                 // first key any query of this row can see
+    if constexpr (START) {
+        s0 = kv_start[b];
+        s0 = s0 < 0 ? 0 : (s0 > L ? L : s0);
+    }
+    if (nv <= 0 || (START && c0 + C::CH <= s0)) {
         if (tid < tq) { ml[2 * tid] = -INFINITY; ml[2 * tid + 1] = 0.f; }
         return;
     }
@@ -94,7 +106,7 @@ __global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs
     for (int u = 0; u < C::VPT; ++u) {
         const int idx = tid + DA_THREADS * u, row = idx / C::R16, col = idx - row * C::R16;
         kreg[u] = vreg[u] = make_uint4(0u, 0u, 0u, 0u);
-        if (row < nv) {
+        if (row < nv && (!START || c0 + row >= s0)) {
             int64_t kro = 0, vro = 0;                               // element offset of the source row from row b
             if constexpr (ROWS) {
                 int r = rows[(int64_t)b * rows_ld + c0 + row];
@@ -125,7 +137,7 @@ __global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs
         float s[C::QPT];
 #pragma unroll
         for (int qi = 0; qi < C::QPT; ++qi) s[qi] = 0.f;
-        if (j < nv) {
+        if (j < nv && (!START || c0 + j >= s0)) {
 #pragma unroll 4
             for (int c = 0; c < C::R16; ++c) {
                 float kf[C::EPV];
@@ -146,7 +158,7 @@ __global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs
             const int i = g + qi * C::NG;
             if (i < TQB) {
                 const int lim = a.causal ? L - tq + i + 1 : L;          // bottom-right aligned causal limit (global key index)
-                sc[i * C::CH + j] = (i < tq && j < nv && c0 + j < lim) ? s[qi] * scale : -INFINITY;
+                sc[i * C::CH + j] = (i < tq && j < nv && c0 + j < lim && (!START || c0 + j >= s0)) ? s[qi] * scale : -INFINITY;
             }
         }
     }
@@ -268,21 +280,28 @@ int da_check(const MopkDecodeAttnArgs *a) {
     return MOPK_OK;
 }
 
+template <typename T, int DK, int TQB, bool ROWS>
+void da_launch_split(const dim3 &grid, const dim3 &block, hipStream_t st, const MopkDecodeAttnArgs *a, int ns, const int32_t *rows,
+                     int64_t rows_ld, const int32_t *kv_start) {
+    if (kv_start) hipLaunchKernelGGL((da_split_kernel<T, DK, TQB, ROWS, true>), grid, block, 0, st, *a, ns, rows, rows_ld, kv_start);
+    else hipLaunchKernelGGL((da_split_kernel<T, DK, TQB, ROWS, false>), grid, block, 0, st, *a, ns, rows, rows_ld, kv_start);
+}
+
 template <typename T, int DK, bool ROWS>
-void da_launch_dk(const MopkDecodeAttnArgs *a, const int32_t *rows, int64_t rows_ld, hipStream_t st) {
+void da_launch_dk(const MopkDecodeAttnArgs *a, const int32_t *rows, int64_t rows_ld, const int32_t *kv_start, hipStream_t st) {
     const int ns = da_nsplit(a);
     const dim3 grid((unsigned)(a->B * a->H), (unsigned)ns), block(DA_THREADS);
-    if (a->Tq <= 1) hipLaunchKernelGGL((da_split_kernel<T, DK, 1, ROWS>), grid, block, 0, st, *a, ns, rows, rows_ld);
-    else if (a->Tq <= 4) hipLaunchKernelGGL((da_split_kernel<T, DK, 4, ROWS>), grid, block, 0, st, *a, ns, rows, rows_ld);
-    else hipLaunchKernelGGL((da_split_kernel<T, DK, 16, ROWS>), grid, block, 0, st, *a, ns, rows, rows_ld);
+    if (a->Tq <= 1) da_launch_split<T, DK, 1, ROWS>(grid, block, st, a, ns, rows, rows_ld, kv_start);
+    else if (a->Tq <= 4) da_launch_split<T, DK, 4, ROWS>(grid, block, st, a, ns, rows, rows_ld, kv_start);
+    else da_launch_split<T, DK, 16, ROWS>(grid, block, st, a, ns, rows, rows_ld, kv_start);
     hipLaunchKernelGGL(da_merge_kernel<T>, dim3((unsigned)(a->B * a->H)), block, 0, st, *a, ns);
 }
 
 template <typename T, bool ROWS>
-void da_launch(const MopkDecodeAttnArgs *a, const int32_t *rows, int64_t rows_ld, hipStream_t st) {
-    if (a->dk == 32) da_launch_dk<T, 32, ROWS>(a, rows, rows_ld, st);
-    else if (a->dk == 64) da_launch_dk<T, 64, ROWS>(a, rows, rows_ld, st);
-    else da_launch_dk<T, 128, ROWS>(a, rows, rows_ld, st);
+void da_launch(const MopkDecodeAttnArgs *a, const int32_t *rows, int64_t rows_ld, hipStream_t st, const int32_t *kv_start = nullptr) {
+    if (a->dk == 32) da_launch_dk<T, 32, ROWS>(a, rows, rows_ld, kv_start, st);
+    else if (a->dk == 64) da_launch_dk<T, 64, ROWS>(a, rows, rows_ld, kv_start, st);
+    else da_launch_dk<T, 128, ROWS>(a, rows, rows_ld, kv_start, st);
 }
 
 int da_rows_check(const MopkDecodeAttnRowsArgs *a) {
@@ -291,6 +310,19 @@ int da_rows_check(const MopkDecodeAttnRowsArgs *a) {
     if (rc != MOPK_OK) return rc;
     if (a->rows_ld < a->base.cap) return MOPK_ERR_BAD_SHAPE;
     if ((uintptr_t)a->rows & 3) return MOPK_ERR_UNSUPPORTED;
+    return MOPK_OK;
+}
+
+int da_ragged_check(const MopkDecodeAttnRaggedArgs *a) {
+    if (!a) return MOPK_ERR_BAD_ARG;
+    const int rc = da_check(&a->base);
+    if (rc != MOPK_OK) return rc;
+    if (!a->kv_start) return MOPK_ERR_BAD_ARG;
+    if ((uintptr_t)a->kv_start & 3) return MOPK_ERR_UNSUPPORTED;
+    if (a->rows) {
+        if (a->rows_ld < a->base.cap) return MOPK_ERR_BAD_SHAPE;
+        if ((uintptr_t)a->rows & 3) return MOPK_ERR_UNSUPPORTED;
+    }
     return MOPK_OK;
 }
 
@@ -330,6 +362,28 @@ int mopk_decode_attn_rows_fwd(const MopkDecodeAttnRowsArgs *a, void *stream) {
     if (!b->q.ptr || !b->k.ptr || !b->v.ptr || !b->y.ptr || !b->workspace || !a->rows) return MOPK_ERR_BAD_ARG;
     if (b->io_dtype == MOPK_BF16) da_launch<unsigned short, true>(b, a->rows, a->rows_ld, (hipStream_t)stream);
     else da_launch<float, true>(b, a->rows, a->rows_ld, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+}
+
+int mopk_decode_attn_ragged_supported(const MopkDecodeAttnRaggedArgs *a) { return da_ragged_check(a) == MOPK_OK; }
+
+size_t mopk_decode_attn_ragged_workspace_bytes(const MopkDecodeAttnRaggedArgs *a) {
+    return da_ragged_check(a) == MOPK_OK ? mopk_decode_attn_workspace_bytes(&a->base) : 0;
+}
+
+int mopk_decode_attn_ragged_fwd(const MopkDecodeAttnRaggedArgs *a, void *stream) {
+    const int rc = da_ragged_check(a);
+    if (rc != MOPK_OK) return rc;
+    const MopkDecodeAttnArgs *b = &a->base;
+    if (!b->q.ptr || !b->k.ptr || !b->v.ptr || !b->y.ptr || !b->workspace) return MOPK_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->rows) {
+        if (b->io_dtype == MOPK_BF16) da_launch<unsigned short, true>(b, a->rows, a->rows_ld, st, a->kv_start);
+        else da_launch<float, true>(b, a->rows, a->rows_ld, st, a->kv_start);
+    } else {
+        if (b->io_dtype == MOPK_BF16) da_launch<unsigned short, false>(b, nullptr, 0, st, a->kv_start);
+        else da_launch<float, false>(b, nullptr, 0, st, a->kv_start);
+    }
     return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
 }
 

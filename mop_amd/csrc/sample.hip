@@ -10,6 +10,10 @@
 // running total reaches the target, and the window shrinks to that bin; at most four levels reach a single key.  The draw is a
 // Gumbel-max over the kept set with a counter-based hash, so it needs no prefix scan.  Every block reduction has a fixed order:
 // tokens and log-probabilities are bitwise reproducible.
+//
+// Ragged batches (mopk_sample_ragged_*): OFF = true draws row r at position *pos - pos_off[r], the row's own token index in a
+// left-padded batch; nothing else changes.  That instantiation is compiled in a unit of its own (-DMOPK_SAMPLE_RAGGED, a second
+// object of this file), so the OFF = false kernel's code is the same as before the flag existed.
 #include "common.h"
 
 namespace mopk {
@@ -174,8 +178,9 @@ __device__ __forceinline__ uint32_t sp_select(const SpRow<T> &row, uint32_t lo, 
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(SP_THREADS) void sp_row_kernel(MopkSampleArgs a) {
+// OFF: row r draws at *pos - pos_off[r] (a ragged batch); else at *pos
+template <typename T, bool OFF>
+__global__ __launch_bounds__(SP_THREADS) void sp_row_kernel(MopkSampleArgs a, const int32_t *pos_off) {
     __shared__ SpLds s;
     const int tid = threadIdx.x, r = blockIdx.x, V = a.V;
     const int item = r / a.n, sub = r - item * a.n;
@@ -214,7 +219,9 @@ __global__ __launch_bounds__(SP_THREADS) void sp_row_kernel(MopkSampleArgs a) {
             thr = sp_select<true>(row, thr, kmax, P, mz, s);
         }
         // the draw: Gumbel-max over the kept set
-        const uint32_t rh = sp_row_hash(a.seed, r, *a.pos);
+        uint32_t rh;
+        if constexpr (OFF) rh = sp_row_hash(a.seed, r, *a.pos - pos_off[r]);
+        else rh = sp_row_hash(a.seed, r, *a.pos);
 #pragma unroll SP_UNROLL
         for (int v = tid; v < V; v += SP_THREADS) {
             const float z = row.z(v);
@@ -248,6 +255,17 @@ int sp_check(const MopkSampleArgs *a) {
     return MOPK_OK;
 }
 
+#ifdef MOPK_SAMPLE_RAGGED
+int sp_ragged_check(const MopkSampleRaggedArgs *a) {
+    if (!a) return MOPK_ERR_BAD_ARG;
+    const int rc = sp_check(&a->base);
+    if (rc != MOPK_OK) return rc;
+    if (!a->pos_off) return MOPK_ERR_BAD_ARG;
+    if ((uintptr_t)a->pos_off & 3) return MOPK_ERR_UNSUPPORTED;
+    return MOPK_OK;
+}
+#endif
+
 }  // namespace
 }  // namespace mopk
 
@@ -255,6 +273,7 @@ using namespace mopk;
 
 extern "C" {
 
+#ifndef MOPK_SAMPLE_RAGGED
 int mopk_sample_supported(const MopkSampleArgs *a) { return sp_check(a) == MOPK_OK; }
 
 size_t mopk_sample_workspace_bytes(const MopkSampleArgs *a) {
@@ -267,9 +286,29 @@ int mopk_sample_step(const MopkSampleArgs *a, void *stream) {
     if (rc != MOPK_OK) return rc;
     if (!a->logits || !a->pos || !a->tokens || !a->logprobs) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (a->logits_dtype == MOPK_BF16) hipLaunchKernelGGL(sp_row_kernel<unsigned short>, dim3((unsigned)a->R), dim3(SP_THREADS), 0, st, *a);
-    else hipLaunchKernelGGL(sp_row_kernel<float>, dim3((unsigned)a->R), dim3(SP_THREADS), 0, st, *a);
+    if (a->logits_dtype == MOPK_BF16)
+        hipLaunchKernelGGL((sp_row_kernel<unsigned short, false>), dim3((unsigned)a->R), dim3(SP_THREADS), 0, st, *a, nullptr);
+    else hipLaunchKernelGGL((sp_row_kernel<float, false>), dim3((unsigned)a->R), dim3(SP_THREADS), 0, st, *a, nullptr);
     return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
 }
+#else   // the ragged exports: this file compiled a second time with -DMOPK_SAMPLE_RAGGED (mop_amd/build.py)
+int mopk_sample_ragged_supported(const MopkSampleRaggedArgs *a) { return sp_ragged_check(a) == MOPK_OK; }
+
+size_t mopk_sample_ragged_workspace_bytes(const MopkSampleRaggedArgs *a) {
+    return sp_ragged_check(a) == MOPK_OK ? mopk_sample_workspace_bytes(&a->base) : 0;
+}
+
+int mopk_sample_ragged_step(const MopkSampleRaggedArgs *a, void *stream) {
+    const int rc = sp_ragged_check(a);
+    if (rc != MOPK_OK) return rc;
+    const MopkSampleArgs *b = &a->base;
+    if (!b->logits || !b->pos || !b->tokens || !b->logprobs) return MOPK_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (b->logits_dtype == MOPK_BF16)
+        hipLaunchKernelGGL((sp_row_kernel<unsigned short, true>), dim3((unsigned)b->R), dim3(SP_THREADS), 0, st, *b, a->pos_off);
+    else hipLaunchKernelGGL((sp_row_kernel<float, true>), dim3((unsigned)b->R), dim3(SP_THREADS), 0, st, *b, a->pos_off);
+    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+}
+#endif
 
 }  // extern "C"

@@ -10,7 +10,7 @@ are stock PyTorch-ROCm layers.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -194,11 +194,14 @@ class WhisperDecodeCache:
     cross_k / cross_v: per decoder layer, the encoder output projected once to cross-attention keys / values (B, T_audio, H, dh).
     self_k / self_v: per decoder layer, self-attention keys / values (B, max_len, H, dh), filled up to `length`.
     length: the number of cached tokens as a (1,) int32 DEVICE tensor (the kernels read it, so a step's launch arguments do not
-    change from step to step); pos: its host mirror (the host drives the loop, so keeping it costs no sync)."""
+    change from step to step); pos: its host mirror (the host drives the loop, so keeping it costs no sync).
+    kv_start: None (every row's tokens start at column 0), or an int32 (B,) DEVICE tensor for a ragged batch whose prompts are
+    left-padded to one length: row b's tokens start at column kv_start[b] (set it after construction; see decode_step)."""
 
     def __init__(self, cross_k, cross_v, self_k, self_v, length: torch.Tensor, max_len: int):
         self.cross_k, self.cross_v, self.self_k, self.self_v = cross_k, cross_v, self_k, self_v
         self.length, self.pos, self.max_len = length, 0, int(max_len)
+        self.kv_start: Optional[torch.Tensor] = None
 
     @property
     def dtype(self) -> torch.dtype:
@@ -306,7 +309,13 @@ class WhisperMoP(nn.Module):
 
         Equals decode(enc_out, all ids so far)[:, -T_new:] in eval().  Attention runs on ops.decode_attention (the split-KV kernels)
         with the device length; a first chunk of more than 16 tokens runs the square causal ops.sdpa_core and writes its keys /
-        values into the cache.  Positions, the append and the length update are device-indexed: no host sync, graph-capturable."""
+        values into the cache.  Positions, the append and the length update are device-indexed: no host sync, graph-capturable.
+
+        Ragged batches: set cache.kv_start to an int32 (B,) device tensor and pass the prompts left-padded to one length P (any pad
+        token), row b's prompt in columns [kv_start[b], P).  Row b's token in column c then takes position c - kv_start[b] (text_pos),
+        and its queries see only the keys in columns >= kv_start[b] (ops.decode_attention_ragged; a first chunk of more than 16 tokens
+        runs ops.sdpa_core with a key-padding mask), so row b decodes as it would alone; the pad columns are never read.  Every
+        later step appends all rows at the same column.  kv_start None is the uniform batch, run exactly as before."""
         return self._decode_tokens(cache, ids)
 
     def _decode_tokens(self, cache: WhisperDecodeCache, ids: torch.Tensor, rows: Optional[torch.Tensor] = None,
@@ -319,9 +328,13 @@ class WhisperMoP(nn.Module):
             raise ValueError(f"decode_step: {cache.pos} cached + {T} new tokens exceed the cache's max_len = {cache.max_len}")
         H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
         idx = cache.length.to(torch.long) + torch.arange(T, device=ids.device)        # positions of the new tokens
+        ks = cache.kv_start                                                            # ragged: row b's first column
         x = self.wte(ids)
         if self.text_pos is not None:
-            x = x + self.text_pos(idx).unsqueeze(0)
+            if ks is None:
+                x = x + self.text_pos(idx).unsqueeze(0)
+            else:                                                                      # per-row positions, pad columns at 0
+                x = x + self.text_pos((idx.unsqueeze(0) - ks.to(torch.long).unsqueeze(1)).clamp_min(0))
         new_len = cache.length + T
         long_chunk = T > ops.DECODE_MAX_TQ
         prefill = long_chunk and cache.pos == 0
@@ -331,8 +344,12 @@ class WhisperMoP(nn.Module):
             q, k, v = (p(h).view(B, T, H, Dh) for p in (sa.q_proj, sa.k_proj, sa.v_proj))
             cache.self_k[l].index_copy_(1, idx, k.to(cache.dtype))
             cache.self_v[l].index_copy_(1, idx, v.to(cache.dtype))
-            if prefill:
+            if prefill and ks is not None:                                            # key-padding mask (B, 1, 1, T)
+                y = ops.sdpa_core(q, k, v, attn_mask=(idx.unsqueeze(0) >= ks.unsqueeze(1)).view(B, 1, 1, T), causal=True)
+            elif prefill:
                 y = ops.sdpa_core(q, k, v, causal=True)
+            elif ks is not None:
+                y = ops.decode_attention_ragged(q, cache.self_k[l], cache.self_v[l], ks, rows=rows, kv_len=new_len, causal=True)
             elif rows is not None:
                 y = ops.decode_attention_rows(q, cache.self_k[l], cache.self_v[l], rows, kv_len=new_len, causal=True)
             else:
@@ -352,6 +369,44 @@ class WhisperMoP(nn.Module):
         cache.pos += T
         return self.lm_head(self.dec_ln_f(x))
 
+    @staticmethod
+    def _ragged_check(mel: torch.Tensor, prompt_ids, what: str) -> Optional[List[int]]:
+        """None for a (B, T_p) tensor; for a list / tuple of B 1-D integer tensors (a ragged batch), their lengths.  Raises
+        ValueError on a malformed list, before any device work."""
+        if isinstance(prompt_ids, torch.Tensor):
+            return None
+        if not isinstance(prompt_ids, (list, tuple)) or len(prompt_ids) == 0:
+            raise ValueError(f"{what}: prompt_ids must be a (B, T_p) tensor or a non-empty list of B 1-D token tensors")
+        if len(prompt_ids) != mel.shape[0]:
+            raise ValueError(f"{what}: {len(prompt_ids)} prompts for a batch of {mel.shape[0]} mel inputs")
+        for b, p in enumerate(prompt_ids):
+            if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.numel() < 1:
+                raise ValueError(f"{what}: prompt {b} must be a non-empty 1-D tensor, got "
+                                 f"{tuple(p.shape) if isinstance(p, torch.Tensor) else type(p).__name__}")
+            if p.dtype.is_floating_point or p.dtype.is_complex or p.dtype == torch.bool or p.dtype != prompt_ids[0].dtype:
+                raise ValueError(f"{what}: prompts must share one integer dtype, prompt {b} is {p.dtype}")
+            if p.device != mel.device:
+                raise ValueError(f"{what}: prompt {b} is on {p.device}, the mel on {mel.device}")
+        return [int(p.shape[0]) for p in prompt_ids]
+
+    @staticmethod
+    def _ragged_pad(prompt_ids, lens: Optional[List[int]], device):
+        """-> (prompts (B, P), kv_start): a tensor passes through with kv_start None; a ragged list is left-padded with token 0 to
+        P = max(lens), row b's prompt in columns [P - lens[b], P), with kv_start = P - lens as an int32 (B,) device tensor (None
+        when every length is P: the uniform path)"""
+        if lens is None:
+            return prompt_ids, None
+        P = max(lens)
+        if min(lens) == P:
+            return torch.stack(list(prompt_ids)), None
+        padded = torch.zeros(len(lens), P, dtype=prompt_ids[0].dtype, device=device)
+        for b, p in enumerate(prompt_ids):
+            padded[b, P - lens[b]:] = p
+        kv_start = torch.tensor([P - n for n in lens], dtype=torch.int32)
+        if device.type == "cuda":                                      # an asynchronous copy: the host does not wait for it
+            return padded, kv_start.pin_memory().to(device, non_blocking=True)
+        return padded, kv_start
+
     @torch.no_grad()
     def generate(self, mel: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                  graph: bool = False, *, return_logits: bool = False):
@@ -360,14 +415,21 @@ class WhisperMoP(nn.Module):
         Rows that have emitted eos_token_id keep emitting it (torch.where: the loop never syncs the host).  graph=True runs the prompt
         and the first single-token step eagerly, captures one single-token decode_step in a HIP graph (torch.cuda.graph, one stream,
         static id / logit buffers) and replays it for every further token.  return_logits=True also returns the last-position logits
-        that chose each new token, (B, max_new_tokens, vocab)."""
-        B, T_p = prompt_ids.shape
+        that chose each new token, (B, max_new_tokens, vocab).
+
+        prompt_ids may also be a list of B 1-D tensors of different lengths (a ragged batch): they are left-padded in one cache with
+        a per-row start (WhisperDecodeCache.kv_start), each row decodes as it would alone, and the tokens come back as a list of B
+        1-D tensors, prompt b followed by its max_new_tokens tokens (views of one device tensor)."""
+        lens = self._ragged_check(mel, prompt_ids, "generate")
+        B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
         if T_p < 1 or max_new_tokens < 1:
             raise ValueError(f"generate: needs a prompt and at least one new token (T_p = {T_p}, max_new_tokens = {max_new_tokens})")
         if T_p + max_new_tokens > self.cfg.n_text_ctx:
             raise ValueError(f"generate: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel.device)
         enc, _ = self.encode(mel)
         cache = self.init_decode_cache(enc, T_p + max_new_tokens)
+        cache.kv_start = kv_start
         logits = self.decode_step(cache, prompt_ids)[:, -1]
         done = torch.zeros(B, dtype=torch.bool, device=prompt_ids.device) if eos_token_id is not None else None
         toks, steps = [], []
@@ -400,6 +462,8 @@ class WhisperMoP(nn.Module):
             cache.pos += 1
             logits = static_logits
         out = torch.cat([prompt_ids, torch.stack(toks, dim=1).to(prompt_ids.dtype)], dim=1)
+        if lens is not None:
+            out = [out[b, T_p - lens[b]:] for b in range(B)]
         return (out, torch.stack(steps, dim=1)) if return_logits else out
 
     @torch.no_grad()
@@ -418,8 +482,11 @@ class WhisperMoP(nn.Module):
         eos_token_id that is the best live beam.
         Beams never copy cache slots: each step's keys / values are written once into the beam's own row, and the self-attention
         reads a beam's history through the device row table (ops.decode_attention_rows).  graph=True captures one step (decoder
-        step + beam_step) after the first eager one and replays it (torch.cuda.graph, one stream, static buffers)."""
-        B, T_p = prompt_ids.shape
+        step + beam_step) after the first eager one and replays it (torch.cuda.graph, one stream, static buffers).
+        prompt_ids may also be a list of B 1-D tensors of different lengths (see generate): the tokens then come back as a list of B
+        1-D tensors, prompt b followed by max_new_tokens tokens; gen_len counts generated tokens only, as for a tensor."""
+        lens = self._ragged_check(mel, prompt_ids, "beam_search")
+        B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
         K = int(num_beams)
         if not 1 <= K <= ops.BEAM_MAX_K:
             raise ValueError(f"beam_search: num_beams = {num_beams} outside [1, {ops.BEAM_MAX_K}]")
@@ -431,6 +498,7 @@ class WhisperMoP(nn.Module):
             raise ValueError(f"beam_search: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
         cap = T_p + max_new_tokens
         H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel.device)
         enc, _ = self.encode(mel)
         ck, cv = self._cross_kv(enc)
         kw = dict(dtype=ck[0].dtype, device=enc.device)
@@ -438,9 +506,11 @@ class WhisperMoP(nn.Module):
         sv = [torch.zeros(B * K, cap, H, Dh, **kw) for _ in self.decoder]
         length = torch.zeros(1, dtype=torch.int32, device=enc.device)
         prompt_cache = WhisperDecodeCache(ck, cv, [t[::K] for t in sk], [t[::K] for t in sv], length, cap)
+        prompt_cache.kv_start = kv_start
         logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]              # (B, V): shared by the item's beams
         cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
         cache.pos = T_p
+        cache.kv_start = None if kv_start is None else kv_start.repeat_interleave(K)
         st = ops.BeamState(prompt_ids, K, cap, eos_token_id, length_penalty)
         ops.beam_step(logits, st, length)
 
@@ -462,7 +532,10 @@ class WhisperMoP(nn.Module):
             g.replay()
             cache.pos += 1
         tokens, scores = ops.beam_finalize(st, max_new_tokens)
-        return tokens.to(prompt_ids.dtype), scores
+        tokens = tokens.to(prompt_ids.dtype)
+        if lens is not None:
+            tokens = [tokens[b, T_p - lens[b]:] for b in range(B)]
+        return tokens, scores
 
     @torch.no_grad()
     def sample(self, mel: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
@@ -477,8 +550,12 @@ class WhisperMoP(nn.Module):
         cache slot is copied.  The draw at position pos of sample row r is a pure function of (logits, seed, r, pos).  A row that has
         emitted eos_token_id keeps emitting it; sum_logprobs adds log_softmax(logits)[token] of every token up to and including the
         first eos.  graph=True captures one step (decoder step + sample_tokens + the eos / sum update) after the first eager one and
-        replays it (torch.cuda.graph, one stream, static buffers)."""
-        B, T_p = prompt_ids.shape
+        replays it (torch.cuda.graph, one stream, static buffers).
+        prompt_ids may also be a list of B 1-D tensors of different lengths (see generate): the tokens then come back as a list of B
+        (num_samples, P_b + max_new_tokens) tensors, and row r draws at its own token index (ops.sample_tokens_ragged), so its draws
+        are those of a batch in which every prompt has its length."""
+        lens = self._ragged_check(mel, prompt_ids, "sample")
+        B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
         n = int(num_samples)
         if not 1 <= n <= ops.BEAM_MAX_K:
             raise ValueError(f"sample: num_samples = {num_samples} outside [1, {ops.BEAM_MAX_K}]")
@@ -487,6 +564,7 @@ class WhisperMoP(nn.Module):
         if T_p + max_new_tokens > self.cfg.n_text_ctx:
             raise ValueError(f"sample: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
         ops._sample_params(temperature, top_k, top_p, "sample")                 # argument errors before encoding
+        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel.device)
         dev = prompt_ids.device
         length = torch.zeros(1, dtype=torch.int32, device=dev)
         cap = T_p + max_new_tokens
@@ -497,9 +575,11 @@ class WhisperMoP(nn.Module):
         sk = [torch.zeros(B * n, cap, H, Dh, **kw) for _ in self.decoder]
         sv = [torch.zeros(B * n, cap, H, Dh, **kw) for _ in self.decoder]
         prompt_cache = WhisperDecodeCache(ck, cv, [t[::n] for t in sk], [t[::n] for t in sv], length, cap)
+        prompt_cache.kv_start = kv_start
         logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]              # (B, V): shared by the item's samples
         cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
         cache.pos = T_p
+        cache.kv_start = None if kv_start is None else kv_start.repeat_interleave(n)
         i32 = dict(dtype=torch.int32, device=dev)
         r = torch.arange(B * n, **i32)
         table = r.unsqueeze(1).repeat(1, cap)                                   # constant: the prompt from row b * n, then own rows
@@ -513,7 +593,10 @@ class WhisperMoP(nn.Module):
         eos = None if eos_token_id is None else int(eos_token_id)
 
         def draw(lg):
-            ops.sample_tokens(lg, cache.length, temperature, top_k, top_p, seed, out=(tok, lp))
+            if cache.kv_start is None:
+                ops.sample_tokens(lg, cache.length, temperature, top_k, top_p, seed, out=(tok, lp))
+            else:
+                ops.sample_tokens_ragged(lg, cache.length, cache.kv_start, temperature, top_k, top_p, seed, out=(tok, lp))
             if eos is None:
                 sum_lp.add_(lp)
                 ids.copy_(tok.unsqueeze(1))
@@ -541,7 +624,10 @@ class WhisperMoP(nn.Module):
                 cache.pos -= 1                           # capture recorded the step without running it
             g.replay()
             cache.pos += 1
-        return tokens.view(B, n, cap).to(prompt_ids.dtype), sum_lp.view(B, n)
+        tokens = tokens.view(B, n, cap).to(prompt_ids.dtype)
+        if lens is not None:
+            tokens = [tokens[b, :, T_p - lens[b]:] for b in range(B)]
+        return tokens, sum_lp.view(B, n)
 
     @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):

@@ -1652,6 +1652,101 @@ def decode_attention_rows(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
         return y.view(B, Tq, H * dk)
 
 
+# ---- decode attention with a per-row first key (mopk_decode_attn_ragged_*; WhisperMoP decoding of left-padded prompts) ----
+def decode_attention_ragged_torch(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_start: torch.Tensor,
+                                  rows: Optional[torch.Tensor] = None, kv_len: Optional[torch.Tensor] = None, nk: Optional[int] = None,
+                                  causal: bool = False) -> torch.Tensor:
+    """the reference composition of `decode_attention_ragged`: decode_attention_torch (after the row gather of
+    decode_attention_rows_torch when rows is given) with the keys j < kv_start[b] of row b masked out; no host sync"""
+    B, Tq, H, dk = q.shape
+    cap = k_cache.shape[1]
+    if rows is not None:
+        r = rows[:, :cap].to(torch.long).clamp(0, B - 1)
+        j = torch.arange(cap, device=k_cache.device).unsqueeze(0)
+        k_cache, v_cache = k_cache[r, j], v_cache[r, j]
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    s = torch.einsum("bihd,bjhd->bhij", q.to(ct), k_cache.to(ct)) * dk ** -0.5
+    j = torch.arange(cap, device=q.device)
+    L = kv_len.reshape(()).to(torch.long).clamp(0, cap) if kv_len is not None else (cap if nk is None else int(nk))
+    i = torch.arange(Tq, device=q.device)
+    lim = L - Tq + i + 1 if causal else L + 0 * i                           # (Tq,)
+    open_ = (j >= kv_start.reshape(B, 1).to(torch.long)) & (j < L)          # (B, cap): the keys a row may see at all
+    ok = open_.unsqueeze(1) & (j.unsqueeze(0) < lim.unsqueeze(1)).unsqueeze(0)  # (B, Tq, cap)
+    s = s.masked_fill(~ok.unsqueeze(1), float("-inf"))
+    p = torch.softmax(s, dim=-1).nan_to_num(0.0)                            # a query that sees no key gets y = 0, as the kernels
+    v = v_cache.to(ct).masked_fill(~open_.view(B, cap, 1, 1), 0.0)          # rows outside [kv_start, L) may hold anything
+    y = torch.einsum("bhij,bjhd->bihd", p, v)
+    return y.to(q.dtype).reshape(B, Tq, H * dk)
+
+
+def _dag_args(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal) -> L.DecodeAttnRaggedArgs:
+    a = L.DecodeAttnRaggedArgs()
+    a.base = _da_args(q, k_cache, v_cache, kv_len, nk, causal)
+    a.rows, a.rows_ld = (None, 0) if rows is None else (rows.data_ptr(), rows.stride(0))
+    a.kv_start = kv_start.data_ptr()
+    return a
+
+
+def decode_attention_ragged_supported(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_start: torch.Tensor,
+                                      rows: Optional[torch.Tensor] = None, kv_len: Optional[torch.Tensor] = None,
+                                      nk: Optional[int] = None, causal: bool = False) -> bool:
+    """True if mopk_decode_attn_ragged_* take this call: what decode_attention_supported asks, a contiguous CUDA int32 kv_start of
+    B elements, and (with rows) what decode_attention_rows_supported asks of the table"""
+    if not kv_start.is_cuda or kv_start.dtype != torch.int32 or kv_start.numel() != q.shape[0] or not kv_start.is_contiguous():
+        return False
+    if rows is not None and (not rows.is_cuda or rows.dtype != torch.int32 or rows.dim() != 2 or rows.stride(1) != 1):
+        return False
+    if not decode_attention_supported(q, k_cache, v_cache, kv_len, nk, causal):
+        return False
+    return bool(L.lib().mopk_decode_attn_ragged_supported(C.byref(_dag_args(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal))))
+
+
+def decode_attention_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_start: torch.Tensor,
+                            rows: Optional[torch.Tensor] = None, kv_len: Optional[torch.Tensor] = None, nk: Optional[int] = None,
+                            causal: bool = False) -> torch.Tensor:
+    """`decode_attention` (rows None) or `decode_attention_rows` (rows given) in which query row b sees only the keys
+    j >= kv_start[b]: prompts of different lengths left-padded in one cache, row b's prompt in columns [kv_start[b], P).
+    Inference only (no autograd).
+
+    kv_start: int32 (B,) device tensor (values are clamped into [0, L]); q, k_cache, v_cache, rows, kv_len, nk and causal as in
+    decode_attention / decode_attention_rows.  Query i of row b sees kv_start[b] <= j < L (causal: < L - Tq + i + 1); a query that
+    sees no key gets y = 0.  With kv_start = 0 the result is bitwise that of decode_attention / decode_attention_rows.  Returns
+    (B, Tq, H * dk) in q's dtype.  Runs the split-KV HIP kernels when decode_attention_ragged_supported() accepts the call, else
+    decode_attention_ragged_torch(); LAST_PATH["decode_attn_ragged"] records which.  No host synchronisation."""
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError(f"decode_attention_ragged: q must be (B, Tq, H, dk) and k_cache, v_cache (B, cap, H, dk) of one shape; got "
+                         f"q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)}")
+    if k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
+        raise ValueError(f"decode_attention_ragged: k_cache / v_cache {tuple(k_cache.shape)} do not match q's B, H, dk "
+                         f"{tuple(q.shape)}")
+    if kv_start.dim() != 1 or kv_start.shape[0] != q.shape[0] or kv_start.dtype.is_floating_point or kv_start.dtype == torch.bool:
+        raise ValueError(f"decode_attention_ragged: kv_start must be an integer (B,) = ({q.shape[0]},) tensor, got "
+                         f"{tuple(kv_start.shape)} {kv_start.dtype}")
+    if rows is not None and (rows.dim() != 2 or rows.shape[0] != q.shape[0] or rows.shape[1] < k_cache.shape[1]):
+        raise ValueError(f"decode_attention_ragged: rows must be (B, >= cap) = ({q.shape[0]}, >= {k_cache.shape[1]}), "
+                         f"got {tuple(rows.shape)}")
+    if kv_len is not None and nk is not None:
+        raise ValueError("decode_attention_ragged: pass kv_len (device) or nk (host), not both")
+    if nk is not None and not 0 < int(nk) <= k_cache.shape[1]:
+        raise ValueError(f"decode_attention_ragged: nk = {nk} outside [1, cap = {k_cache.shape[1]}]")
+    if kv_len is not None and kv_len.numel() != 1:
+        raise ValueError(f"decode_attention_ragged: kv_len must hold one element, got shape {tuple(kv_len.shape)}")
+    _require_gpu(q, "decode_attention_ragged")
+    with torch.no_grad():
+        if not decode_attention_ragged_supported(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal):
+            LAST_PATH["decode_attn_ragged"] = L.PATH_GENERIC
+            return decode_attention_ragged_torch(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal)
+        lib = L.lib()
+        B, Tq, H, dk = q.shape
+        a = _dag_args(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal)
+        y = torch.empty(B, Tq, H, dk, dtype=q.dtype, device=q.device)
+        ws = _bytes(lib.mopk_decode_attn_ragged_workspace_bytes(C.byref(a)), q.device)
+        a.base.y, a.base.workspace = _v4(y), ws.data_ptr()
+        LAST_PATH["decode_attn_ragged"] = L.PATH_FUSED
+        _launch("mopk_decode_attn_ragged_fwd", a, "decode_attn_ragged")
+        return y.view(B, Tq, H * dk)
+
+
 # ---- batched beam search on device state (mopk_beam_*; WhisperMoP.beam_search) ----
 BEAM_MAX_K = 8
 
@@ -1914,6 +2009,11 @@ def sample_tokens_torch(logits: torch.Tensor, pos: torch.Tensor, temperature: fl
     """the reference composition of `sample_tokens` in torch ops (CPU or GPU, no host sync): the same z, filters, fixed-point top-p
     masses, hash and Gumbel-max, in int64 / fp32 tensors"""
     R, n, inv_t, tp = _sample_check(logits, pos, temperature, top_k, top_p, out, "sample_tokens_torch")
+    return _sample_torch(logits, pos, None, R, n, inv_t, tp, top_k, seed, out)
+
+
+def _sample_torch(logits, pos, pos_off, R, n, inv_t, tp, top_k, seed, out):
+    """sample_tokens_torch's body; pos_off (R,): row r draws at pos - pos_off[r]"""
     x = logits.float()
     if n > 1:
         x = x.repeat_interleave(n, 0)
@@ -1937,7 +2037,10 @@ def sample_tokens_torch(logits: torch.Tensor, pos: torch.Tensor, temperature: fl
             keep = torch.where(live.any(-1, keepdim=True), keep & (z >= tau), keep)
         s = int(seed) & 0xFFFFFFFFFFFFFFFF
         r = torch.arange(R, device=dev, dtype=torch.int64).unsqueeze(1)
-        p = pos.reshape(1, 1).to(torch.int64) & _M32
+        p = pos.reshape(1, 1).to(torch.int64)
+        if pos_off is not None:
+            p = p - pos_off.reshape(R, 1).to(torch.int64)
+        p = p & _M32
         rh = _hash32(_hash32((s & _M32) ^ _mul32(r, 0x9E3779B1)) ^ (s >> 32) ^ _mul32(p, 0x85EBCA77))
         h = _hash32(rh ^ _mul32(torch.arange(V, device=dev, dtype=torch.int64).unsqueeze(0), 0xC2B2AE3D))
         u = ((h >> 9).to(torch.float32) + 0.5) * 2.0 ** -23
@@ -2008,4 +2111,59 @@ def sample_tokens(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 
         a.workspace = _ptr(ws)
         LAST_PATH["sample"] = L.PATH_FUSED
         _launch("mopk_sample_step", a, "sample")
+        return out[0], out[1]
+
+
+# ---- sampling of a left-padded ragged batch (mopk_sample_ragged_*; WhisperMoP.sample with per-row prompt lengths) ----
+def _sample_ragged_check(logits, pos, pos_off, temperature, top_k, top_p, out, what: str):
+    R, n, inv_t, tp = _sample_check(logits, pos, temperature, top_k, top_p, out, what)
+    if pos_off.dim() != 1 or pos_off.shape[0] != R or pos_off.dtype.is_floating_point or pos_off.dtype == torch.bool:
+        raise ValueError(f"{what}: pos_off must be an integer ({R},) tensor (one offset per sampled row), got "
+                         f"{tuple(pos_off.shape)} {pos_off.dtype}")
+    return R, n, inv_t, tp
+
+
+def sample_tokens_ragged_torch(logits: torch.Tensor, pos: torch.Tensor, pos_off: torch.Tensor, temperature: float = 1.0,
+                               top_k: int = 0, top_p: float = 1.0, seed: int = 0, out=None):
+    """the reference composition of `sample_tokens_ragged`: sample_tokens_torch with row r's draw at pos - pos_off[r]"""
+    R, n, inv_t, tp = _sample_ragged_check(logits, pos, pos_off, temperature, top_k, top_p, out, "sample_tokens_ragged_torch")
+    return _sample_torch(logits, pos, pos_off, R, n, inv_t, tp, top_k, seed, out)
+
+
+def sample_tokens_ragged_supported(logits: torch.Tensor, pos: torch.Tensor, pos_off: torch.Tensor, temperature: float = 1.0,
+                                   top_k: int = 0, top_p: float = 1.0, seed: int = 0, out=None) -> bool:
+    """True if mopk_sample_ragged_* take this call: what sample_tokens_supported asks, and a contiguous CUDA int32 pos_off.
+    Raises ValueError on bad arguments."""
+    R, n, inv_t, tp = _sample_ragged_check(logits, pos, pos_off, temperature, top_k, top_p, out, "sample_tokens_ragged_supported")
+    if not pos_off.is_cuda or pos_off.dtype != torch.int32 or not pos_off.is_contiguous():
+        return False
+    if not sample_tokens_supported(logits, pos, temperature, top_k, top_p, seed, out):
+        return False
+    a = L.SampleRaggedArgs()
+    a.base, a.pos_off = _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed), pos_off.data_ptr()
+    return bool(L.lib().mopk_sample_ragged_supported(C.byref(a)))
+
+
+def sample_tokens_ragged(logits: torch.Tensor, pos: torch.Tensor, pos_off: torch.Tensor, temperature: float = 1.0, top_k: int = 0,
+                         top_p: float = 1.0, seed: int = 0, out=None):
+    """`sample_tokens` in which row r draws at position pos - pos_off[r] instead of pos: in a batch of prompts left-padded to one
+    length, pos_off[r] = the row's padding makes a row's draws depend on its own token index only, so a row samples as it would
+    alone.  pos_off: int32 (R,) device tensor, R the number of sampled rows.  With pos_off = 0 the draw is bitwise that of
+    sample_tokens.  Runs the HIP kernel (mopk_sample_ragged_step) when sample_tokens_ragged_supported() accepts the call, else
+    sample_tokens_ragged_torch(); LAST_PATH["sample_ragged"] records which.  No host sync."""
+    R, n, inv_t, tp = _sample_ragged_check(logits, pos, pos_off, temperature, top_k, top_p, out, "sample_tokens_ragged")
+    with torch.no_grad():
+        if not sample_tokens_ragged_supported(logits, pos, pos_off, temperature, top_k, top_p, seed, out):
+            LAST_PATH["sample_ragged"] = L.PATH_GENERIC
+            return sample_tokens_ragged_torch(logits, pos, pos_off, temperature, top_k, top_p, seed, out)
+        if out is None:
+            out = (torch.empty(R, dtype=torch.int32, device=logits.device), torch.empty(R, dtype=torch.float32, device=logits.device))
+        a = L.SampleRaggedArgs()
+        a.base, a.pos_off = _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed), pos_off.data_ptr()
+        a.base.tokens, a.base.logprobs = out[0].data_ptr(), out[1].data_ptr()
+        ws_bytes = L.lib().mopk_sample_ragged_workspace_bytes(C.byref(a))
+        ws = _bytes(ws_bytes, logits.device) if ws_bytes else None
+        a.base.workspace = _ptr(ws)
+        LAST_PATH["sample_ragged"] = L.PATH_FUSED
+        _launch("mopk_sample_ragged_step", a, "sample_ragged")
         return out[0], out[1]

@@ -10,6 +10,8 @@
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload beam-trace
     python tools/bench_whisper_decode.py --workload sample --out profiles/whisper_sample_bench.jsonl   # sampling against greedy
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload sample-trace
+    python tools/bench_whisper_decode.py --workload ragged --batch 8 --out profiles/whisper_ragged_bench.jsonl   # ragged prompts
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload ragged-trace
 
 Model: d = 512, H = 8, 6 + 6 layers, T_a = 1500, vocab 51865 (Whisper-base-like), fp32 parameters under bf16 autocast, prompt 4,
 220 new tokens, B in {1, 8}.  Variants: (a) naive: decode(enc, whole prefix) per token; (b) cached eager: generate(); (c) cached +
@@ -25,6 +27,9 @@ step, and 2 B K L H dk 2 + 4 B K L bytes of K, V and row table per layer and ste
 Sample: temperature 0.7, top_k 50, top_p 0.95, n in {1, 5} samples per item, B in {1, 8}, same model, prompt and length.  Variants:
 (a) generate(graph=True), the greedy baseline; (b) sample eager; (c) sample(graph=True).  sample-trace runs (c) at B = 8, n = 1 and
 n = 5 for rocprofv3; --stats then also prints the sampling kernel (sp_row_kernel).
+Ragged: generate on B prompts of lengths spread over 1 ... 64 (a list: left-padded in one cache, WhisperDecodeCache.kv_start) against a
+uniform (B, 64) prompt, same model and length, eager and graph=True.  ragged-trace runs both with graphs at B = 8 for rocprofv3, so
+the ragged split kernel (da_split_kernel<..., START = true>) can be compared with the plain one (START = false) at the same shape.
 """
 from __future__ import annotations
 
@@ -236,6 +241,48 @@ def bench_core(args):
                                  us=round(ms * 1e3, 2), hbm_byte_bound_us=round(bound_us, 2), steps=args.steps * 20))
 
 
+RAGGED_P = 64
+
+
+def _ragged_prompts(B):
+    """B prompt lengths spread evenly over 1 ... RAGGED_P (B = 1: RAGGED_P)"""
+    import torch
+    lens = [RAGGED_P] if B == 1 else [1 + (RAGGED_P - 1) * b // (B - 1) for b in range(B)]
+    return [torch.randint(0, VOCAB, (n,), device="cuda") for n in lens], lens
+
+
+def bench_ragged(args):
+    import torch
+    m = _base_model()
+    for B in args.batch:
+        mel = torch.randn(B, TA, NMELS, device="cuda")
+        ragged, lens = _ragged_prompts(B)
+        uniform = torch.randint(0, VOCAB, (B, RAGGED_P), device="cuda")
+        outs = {}
+        for name, prompt, graph in (("uniform", uniform, False), ("uniform_graph", uniform, True), ("ragged", ragged, False),
+                                    ("ragged_graph", ragged, True)):
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                ms = _time(lambda: outs.__setitem__(name, m.generate(mel, prompt, NEW, graph=graph)), args.steps, args.warmup)
+            _emit(args, dict(workload="whisper_ragged", variant=name, B=B, T_a=TA, prompt_lens=lens if "ragged" in name else
+                             [RAGGED_P] * B, new_tokens=NEW, d=D, H=H, layers="6+6", vocab=VOCAB, dtype="bf16-autocast",
+                             total_ms=round(ms, 3), ms_per_token=round(ms / NEW, 4), steps=args.steps, warmup=args.warmup))
+        _emit(args, dict(workload="whisper_ragged_agreement", B=B,
+                         graph_equals_eager=all(torch.equal(a, b) for a, b in zip(outs["ragged"], outs["ragged_graph"]))))
+
+
+def bench_ragged_trace(args):
+    import torch
+    m = _base_model()
+    mel = torch.randn(8, TA, NMELS, device="cuda")
+    ragged, _ = _ragged_prompts(8)
+    uniform = torch.randint(0, VOCAB, (8, RAGGED_P), device="cuda")
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        for prompt in (uniform, ragged):
+            for _ in range(2):
+                m.generate(mel, prompt, NEW, graph=True)
+    torch.cuda.synchronize()
+
+
 def bench_core_trace(args):
     import torch
     with torch.no_grad():
@@ -260,8 +307,8 @@ def stats(path):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["generate", "core", "core-trace", "beam", "beam-trace", "sample",
-                                                        "sample-trace"], default="generate")
+    ap.add_argument("--workload", choices=["generate", "core", "core-trace", "beam", "beam-trace", "sample", "sample-trace",
+                                           "ragged", "ragged-trace"], default="generate")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
@@ -273,7 +320,8 @@ def main():
     if args.stats:
         return stats(args.stats)
     {"generate": bench_generate, "core": bench_core, "core-trace": bench_core_trace, "beam": bench_beam,
-     "beam-trace": bench_beam_trace, "sample": bench_sample, "sample-trace": bench_sample_trace}[args.workload](args)
+     "beam-trace": bench_beam_trace, "sample": bench_sample, "sample-trace": bench_sample_trace, "ragged": bench_ragged,
+     "ragged-trace": bench_ragged_trace}[args.workload](args)
 
 
 if __name__ == "__main__":
