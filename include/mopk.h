@@ -280,6 +280,31 @@ int mopk_sdpa_fused_supported(const MopkSdpaArgs *a);
 int mopk_dropout_keep(uint64_t seed, float p, int64_t bh, int64_t i, int64_t j);
 
 /* --------------------------------------------------------------------------
+ * Plain SDPA with per-row lengths: a batch of right-padded sequences (WhisperMoP with audio clips of unequal length).  (Added
+ * under version 118: new exports only, MopkSdpaArgs is unchanged.)  base.mask and base.bias must be NULL.
+ * q_lens[b] / kv_lens[b] are clamped into [0, N] / [0, Nk]; a NULL pointer means the full length.
+ *   query i < q_lens[b] attends to keys j < kv_lens[b] (and j <= i with causal); a query with no open key gives y = 0, dq = 0;
+ *   padding queries (i >= q_lens[b]): y = 0 and dq = 0 are written, and they add nothing to dk, dv whatever dy holds there;
+ *   padding keys (j >= kv_lens[b]): dk = dv = 0 are written;
+ *   nothing beyond a length is used: the result does not depend on what q, k, v, dy hold there (NaN and Inf included);
+ *   dropout: keep(seed, b*H+h, i, j) is indexed by the padded positions, so a seed gives the mask of mopk_sdpa_fwd;
+ *   with every length full (or both pointers NULL) y, dq, dk, dv are bitwise those of mopk_sdpa_fwd / _bwd on base.
+ * Fused path (what mopk_sdpa_fused_supported(&base) takes): the length is a loop bound of the flash kernels, read once per
+ * workgroup -- key tiles beyond kv_lens[b] and query blocks beyond q_lens[b] are skipped, only the last tile is edge-masked, no
+ * mask bytes are read.  Generic path: the lengths block edges in the softmax kernel and zero the gathered padding rows.
+ * Saved / workspace sizes are those of base.  Pass the same lengths to _fwd and _bwd. */
+typedef struct MopkSdpaLensArgs {
+    MopkSdpaArgs base;       /* unchanged meaning; base.mask and base.bias must be NULL */
+    const int32_t *q_lens;   /* device (B) int32, 4-byte aligned, or NULL: query rows i >= q_lens[b] are padding */
+    const int32_t *kv_lens;  /* device (B) int32, 4-byte aligned, or NULL: keys j >= kv_lens[b] are blocked */
+} MopkSdpaLensArgs;
+int mopk_sdpa_lens_supported(const MopkSdpaLensArgs *a);     /* 1 if the fused kernels take this call under MOPK_PATH_AUTO */
+size_t mopk_sdpa_lens_saved_bytes(const MopkSdpaLensArgs *a);
+size_t mopk_sdpa_lens_workspace_bytes(const MopkSdpaLensArgs *a);
+int mopk_sdpa_lens_fwd(const MopkSdpaLensArgs *a, void *stream);
+int mopk_sdpa_lens_bwd(const MopkSdpaLensArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
  * CrossViewMixerMSA attention core.
  * Replaces reference mop/models/attention_variants.py:90-110 (`_compute_logits`: S1, S2, S12, S21, 2x2 mix,
  * transpose cues) and :120-153 (mask, softmax, optional per-key prior sharpening, A v1).
@@ -514,6 +539,21 @@ typedef struct MopkDecodeAttnRaggedArgs {
 int mopk_decode_attn_ragged_supported(const MopkDecodeAttnRaggedArgs *a);
 size_t mopk_decode_attn_ragged_workspace_bytes(const MopkDecodeAttnRaggedArgs *a);
 int mopk_decode_attn_ragged_fwd(const MopkDecodeAttnRaggedArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
+ * Decode attention with per-row key counts: the cross-attention of a decode step over right-padded audio of unequal length.
+ * (Added under version 118: new exports only; callers detect it with mopk_decode_attn_lens_supported.)  Exactly
+ * mopk_decode_attn_fwd with L = kv_lens[b] clamped into [0, base.Nk] for row b of q: chunks beyond L leave at once and the merge
+ * ignores them, key rows >= L are never read, a row with L = 0 gets y = 0.  kv_lens[b] = Nk for every b is bitwise
+ * mopk_decode_attn_fwd.  base.kv_len must be NULL and base.causal 0.  kv_lens: device int32 (B), 4-byte aligned, required.
+ * Workspace: mopk_decode_attn_lens_workspace_bytes() (that of base). */
+typedef struct MopkDecodeAttnLensArgs {
+    MopkDecodeAttnArgs base;             /* base.kv_len NULL, base.causal 0 */
+    const int32_t *kv_lens;              /* device (B) int32, required: row b of q sees keys j < kv_lens[b] */
+} MopkDecodeAttnLensArgs;
+int mopk_decode_attn_lens_supported(const MopkDecodeAttnLensArgs *a);
+size_t mopk_decode_attn_lens_workspace_bytes(const MopkDecodeAttnLensArgs *a);
+int mopk_decode_attn_lens_fwd(const MopkDecodeAttnLensArgs *a, void *stream);
 
 /* --------------------------------------------------------------------------
  * One step of batched beam search (WhisperMoP.beam_search): updates the device beam state in place from the step's last-position

@@ -100,6 +100,11 @@ class SdpaArgs(C.Structure):
     ]
 
 
+class SdpaLensArgs(C.Structure):
+    """MopkSdpaLensArgs: plain SDPA over right-padded rows, query rows i >= q_lens[b] padding, keys j >= kv_lens[b] blocked."""
+    _fields_ = [("base", SdpaArgs), ("q_lens", _fp), ("kv_lens", _fp)]
+
+
 # every symbol include/mopk.h declares: name -> (restype, argtypes)
 class CrossViewArgs(C.Structure):
     _fields_ = [
@@ -174,6 +179,12 @@ class DecodeAttnRaggedArgs(C.Structure):
     """MopkDecodeAttnRaggedArgs: decode attention in which query row b sees only the keys j >= kv_start[b] (left-padded prompts of
     different lengths), optionally through a row table."""
     _fields_ = [("base", DecodeAttnArgs), ("rows", _fp), ("rows_ld", C.c_int64), ("kv_start", _fp)]
+
+
+class DecodeAttnLensArgs(C.Structure):
+    """MopkDecodeAttnLensArgs: decode attention in which row b of q sees the keys j < kv_lens[b] (cross-attention over right-padded
+    audio of unequal length)."""
+    _fields_ = [("base", DecodeAttnArgs), ("kv_lens", _fp)]
 
 
 class BeamArgs(C.Structure):
@@ -267,6 +278,14 @@ SYMBOLS = {
     "mopk_sample_ragged_supported": (C.c_int, [C.POINTER(SampleRaggedArgs)]),
     "mopk_sample_ragged_workspace_bytes": (C.c_size_t, [C.POINTER(SampleRaggedArgs)]),
     "mopk_sample_ragged_step": (C.c_int, [C.POINTER(SampleRaggedArgs), C.c_void_p]),
+    "mopk_sdpa_lens_supported": (C.c_int, [C.POINTER(SdpaLensArgs)]),
+    "mopk_sdpa_lens_saved_bytes": (C.c_size_t, [C.POINTER(SdpaLensArgs)]),
+    "mopk_sdpa_lens_workspace_bytes": (C.c_size_t, [C.POINTER(SdpaLensArgs)]),
+    "mopk_sdpa_lens_fwd": (C.c_int, [C.POINTER(SdpaLensArgs), C.c_void_p]),
+    "mopk_sdpa_lens_bwd": (C.c_int, [C.POINTER(SdpaLensArgs), C.c_void_p]),
+    "mopk_decode_attn_lens_supported": (C.c_int, [C.POINTER(DecodeAttnLensArgs)]),
+    "mopk_decode_attn_lens_workspace_bytes": (C.c_size_t, [C.POINTER(DecodeAttnLensArgs)]),
+    "mopk_decode_attn_lens_fwd": (C.c_int, [C.POINTER(DecodeAttnLensArgs), C.c_void_p]),
 }
 
 _lib = None

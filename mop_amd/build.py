@@ -43,6 +43,9 @@ def _jobs():
     # the ragged sampling kernel is built in a unit of its own: beside it, the plain sp_row_kernel would allocate its registers
     # differently (same instructions, permuted registers), and the plain kernel's code is kept exactly as it was
     jobs.append(("sample.hip", ["-DMOPK_SAMPLE_RAGGED"], "sample_ragged.o"))
+    # so are the per-row-length instantiations of the flash SDPA and of the decode attention (mopk_sdpa_lens_*, mopk_decode_attn_lens_*)
+    jobs.append(("sdpa_flash.hip", ["-DMOPK_SDPA_LENS"], "sdpa_flash_lens.o"))
+    jobs.append(("decode_attn.hip", ["-DMOPK_DECODE_LENS"], "decode_attn_lens.o"))
     for s in FUSED + FUSED_INST_ONLY:
         stem = s.replace(".hip", "")
         # fused bf16-MFMA kernels: relaxed fp (reassociation, contraction, approximate reciprocals) but inf/nan kept;

@@ -18,6 +18,10 @@ size_t sdpa_saved_bytes(const MopkSdpaArgs *a); size_t sdpa_ws_bytes(const MopkS
 int sdpa_fwd(const MopkSdpaArgs *a, hipStream_t st); int sdpa_bwd(const MopkSdpaArgs *a, hipStream_t st);
 int sdpa_flash_supported(const MopkSdpaArgs *a, bool bwd); size_t sdpa_flash_saved_bytes(const MopkSdpaArgs *a); size_t sdpa_flash_ws_bytes(const MopkSdpaArgs *a);
 int sdpa_flash_fwd(const MopkSdpaArgs *a, hipStream_t st); int sdpa_flash_bwd(const MopkSdpaArgs *a, hipStream_t st);
+int sdpa_lens_fwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int32_t *kv_lens, hipStream_t st);
+int sdpa_lens_bwd(const MopkSdpaArgs *a, const int32_t *q_lens, hipStream_t st);
+int sdpa_flash_lens_fwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int32_t *kv_lens, hipStream_t st);
+int sdpa_flash_lens_bwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int32_t *kv_lens, hipStream_t st);
 size_t dp_saved_bytes(const MopkDualPathArgs *a); size_t dp_ws_bytes(const MopkDualPathArgs *a);
 int dp_flash_supported(const MopkDualPathArgs *a, bool bwd); size_t dp_flash_saved_bytes(const MopkDualPathArgs *a); size_t dp_flash_ws_bytes(const MopkDualPathArgs *a);
 int dp_flash_fwd(const MopkDualPathArgs *a, hipStream_t st); int dp_flash_bwd(const MopkDualPathArgs *a, hipStream_t st);
@@ -185,6 +189,36 @@ int mopk_sdpa_bwd(const MopkSdpaArgs *a, void *stream) {      // the fused path 
     if (sdpa_use_flash(a, false)) return sdpa_flash_bwd(a, (hipStream_t)stream);   // same decision as the forward (saved layout)
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
     return sdpa_bwd(a, (hipStream_t)stream);
+}
+// ---- plain SDPA with per-row lengths: the same path decision, sizes and checks as mopk_sdpa_* on base ----
+static int sdpa_lens_check(const MopkSdpaLensArgs *a) {
+    if (!a) return MOPK_ERR_BAD_ARG;
+    int rc = sdpa_check(&a->base); if (rc) return rc;
+    if (a->base.mask || a->base.bias) return MOPK_ERR_BAD_ARG;              // a mask / bias tensor goes with mopk_sdpa_*, not with lengths
+    if (((uintptr_t)a->q_lens & 3) || ((uintptr_t)a->kv_lens & 3)) return MOPK_ERR_UNSUPPORTED;
+    return MOPK_OK;
+}
+int mopk_sdpa_lens_supported(const MopkSdpaLensArgs *a) { return sdpa_lens_check(a) == MOPK_OK && mopk_sdpa_fused_supported(&a->base); }
+size_t mopk_sdpa_lens_saved_bytes(const MopkSdpaLensArgs *a) { return sdpa_lens_check(a) == MOPK_OK ? mopk_sdpa_saved_bytes(&a->base) : 0; }
+size_t mopk_sdpa_lens_workspace_bytes(const MopkSdpaLensArgs *a) { return sdpa_lens_check(a) == MOPK_OK ? mopk_sdpa_workspace_bytes(&a->base) : 0; }
+int mopk_sdpa_lens_fwd(const MopkSdpaLensArgs *l, void *stream) {
+    int rc = sdpa_lens_check(l); if (rc) return rc;
+    const MopkSdpaArgs *a = &l->base;
+    if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !a->saved || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return MOPK_ERR_BAD_ARG;
+    if (sdpa_use_flash(a, false)) return sdpa_flash_lens_fwd(a, l->q_lens, l->kv_lens, (hipStream_t)stream);
+    if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
+    return sdpa_lens_fwd(a, l->q_lens, l->kv_lens, (hipStream_t)stream);
+}
+int mopk_sdpa_lens_bwd(const MopkSdpaLensArgs *l, void *stream) {
+    int rc = sdpa_lens_check(l); if (rc) return rc;
+    const MopkSdpaArgs *a = &l->base;
+    if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !v4ok(a->dy) || !v4ok(a->dq) || !v4ok(a->dk_) || !v4ok(a->dv) ||
+        !a->saved || !a->workspace)
+        return MOPK_ERR_BAD_ARG;
+    if (sdpa_use_flash(a, false)) return sdpa_flash_lens_bwd(a, l->q_lens, l->kv_lens, (hipStream_t)stream);
+    if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
+    return sdpa_lens_bwd(a, l->q_lens, (hipStream_t)stream);
 }
 size_t mopk_crossview_saved_bytes(const MopkCrossViewArgs *a) { return (a && a->B > 0 && a->H > 0 && a->N > 0 && a->dk > 0) ? cv_saved_bytes(a) : 0; }
 size_t mopk_crossview_workspace_bytes(const MopkCrossViewArgs *a) { return (a && a->B > 0 && a->H > 0 && a->N > 0 && a->dk > 0) ? cv_ws_bytes(a) : 0; }

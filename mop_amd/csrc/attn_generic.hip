@@ -52,10 +52,13 @@ struct MaskSpec {
     int causal;
     const uint8_t *mask; int64_t msb, msh, msi;     // 1 = keep
     const float *bias; int64_t bsb, bsh, bsi;       // additive
+    const int32_t *q_lens, *kv_lens;                // per-row lengths (plain SDPA, mopk_sdpa_lens_*): device (B) int32 or nullptr
 };
 __device__ __forceinline__ bool is_blocked(const MaskSpec &m, int b, int h, int i, int j) {
     if (m.causal && j > i) return true;
     if (m.mask && m.mask[b * m.msb + h * m.msh + i * m.msi + j] == 0) return true;
+    if (m.q_lens && i >= m.q_lens[b]) return true;                  // a padding query has no open key: a zero row
+    if (m.kv_lens && j >= m.kv_lens[b]) return true;
     return false;
 }
 // in-place-capable: out = softmax_j(in + bias) over non-blocked j ; one wave per row.  A row with no open key of finite logit (all
@@ -91,6 +94,21 @@ __global__ void softmax_bwd_kernel(const float *P, float *dP, Dm d, float alpha)
     for (int j = lane; j < d.Nk; j += 64) dot += p[j] * g[j];
     dot = wave_sum(dot);
     for (int j = lane; j < d.Nk; j += 64) g[j] = p[j] * (g[j] - dot) * alpha;
+}
+
+// rows n >= lens[b] of a gathered (BH, N, dk) fp32 tensor become 0: what a padding row holds (NaN included) never reaches a GEMM
+__global__ void zero_tail_kernel(float *buf, Dm d, const int32_t *lens) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= d.BH * d.N * d.dk) return;
+    const int n = (idx / d.dk) % d.N; const int64_t bh = idx / ((int64_t)d.dk * d.N);
+    if (n >= lens[bh / d.H]) buf[idx] = 0.f;
+}
+static int zero_tail(float *buf, const Dm &d, const int32_t *lens, hipStream_t st) {
+    if (!lens) return MOPK_OK;
+    const int64_t tot = d.BH * d.N * d.dk;
+    hipLaunchKernelGGL(zero_tail_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, buf, d, lens);
+    MOPK_CHECK_LAUNCH();
+    return MOPK_OK;
 }
 
 static inline GemmDesc gd0(int M, int N, int K, int nb) {
@@ -170,13 +188,16 @@ static SdpaBuf sdpa_carve(void *saved, void *ws, const Dm &d, size_t *ns, size_t
 }
 size_t sdpa_saved_bytes(const MopkSdpaArgs *a) { size_t s; sdpa_carve(nullptr, nullptr, mkdm_nk(a->B, a->H, a->N, sdpa_nk(*a), a->dk), &s, nullptr); return s; }
 size_t sdpa_ws_bytes(const MopkSdpaArgs *a) { size_t w; sdpa_carve(nullptr, nullptr, mkdm_nk(a->B, a->H, a->N, sdpa_nk(*a), a->dk), nullptr, &w); return w; }
-int sdpa_fwd(const MopkSdpaArgs *a, hipStream_t st) {
+// q_lens / kv_lens (mopk_sdpa_lens_*; nullptr = full): the gathered padding rows are zeroed, the softmax kernel blocks the edges
+// beyond a length (P = 0 there, saved for the backward), so y and -- in sdpa_lens_bwd -- dq, dk, dv come out 0 on padding rows
+int sdpa_lens_fwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int32_t *kv_lens, hipStream_t st) {
     const Dm d = mkdm_nk(a->B, a->H, a->N, sdpa_nk(*a), a->dk), dkey = key_rows(d);
     const SdpaBuf b = sdpa_carve(a->saved, a->workspace, d, nullptr, nullptr);
     const bool mf = a->precision == MOPK_PREC_BF16;
     RET_IF(gather(a->io_dtype, a->q, b.q, d, st)); RET_IF(gather(a->io_dtype, a->k, b.k, dkey, st)); RET_IF(gather(a->io_dtype, a->v, b.v, dkey, st));
+    RET_IF(zero_tail(b.q, d, q_lens, st)); RET_IF(zero_tail(b.k, dkey, kv_lens, st)); RET_IF(zero_tail(b.v, dkey, kv_lens, st));
     RET_IF(gemm_nt_scores(b.q, b.k, b.P, d, 1.f / sqrtf((float)d.dk), mf, st));
-    const MaskSpec m{a->causal, a->mask, a->mask_sb, a->mask_sh, a->mask_si, a->bias, a->bias_sb, a->bias_sh, a->bias_si};
+    const MaskSpec m{a->causal, a->mask, a->mask_sb, a->mask_sh, a->mask_si, a->bias, a->bias_sb, a->bias_sh, a->bias_si, q_lens, kv_lens};
     const int64_t rows = d.BH * d.N;
     hipLaunchKernelGGL(masked_softmax_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.P, b.P, d, m);
     if (a->dropout_p > 0.f) drop_map(b.P, b.dP, d, a->dropout_p, a->dropout_seed, st);     // dropped weights in a workspace plane; P stays in `saved`
@@ -184,12 +205,14 @@ int sdpa_fwd(const MopkSdpaArgs *a, hipStream_t st) {
     RET_IF(gemm_map_vec(a->dropout_p > 0.f ? b.dP : b.P, false, b.v, b.y, d, 1.f, 0.f, mf, st));
     return scatter(a->io_dtype, b.y, a->y, d, st);
 }
-int sdpa_bwd(const MopkSdpaArgs *a, hipStream_t st) {
+int sdpa_fwd(const MopkSdpaArgs *a, hipStream_t st) { return sdpa_lens_fwd(a, nullptr, nullptr, st); }
+int sdpa_lens_bwd(const MopkSdpaArgs *a, const int32_t *q_lens, hipStream_t st) {      // the saved q, k, v and P carry the lengths
     const Dm d = mkdm_nk(a->B, a->H, a->N, sdpa_nk(*a), a->dk), dkey = key_rows(d);
     const SdpaBuf b = sdpa_carve(a->saved, a->workspace, d, nullptr, nullptr);
     const bool mf = a->precision == MOPK_PREC_BF16;
     const int64_t rows = d.BH * d.N;
     RET_IF(gather(a->io_dtype, a->dy, b.dy, d, st));
+    RET_IF(zero_tail(b.dy, d, q_lens, st));
     RET_IF(drop_bwd_pair(b.P, b.dy, b.v, b.dP, b.dv, d, a->dropout_p, a->dropout_seed, mf, st));
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.P, b.dP, d, 1.f / sqrtf((float)d.dk));
     MOPK_CHECK_LAUNCH();
@@ -198,6 +221,7 @@ int sdpa_bwd(const MopkSdpaArgs *a, hipStream_t st) {
     RET_IF(scatter(a->io_dtype, b.dq, a->dq, d, st)); RET_IF(scatter(a->io_dtype, b.dk, a->dk_, dkey, st));
     return scatter(a->io_dtype, b.dv, a->dv, dkey, st);
 }
+int sdpa_bwd(const MopkSdpaArgs *a, hipStream_t st) { return sdpa_lens_bwd(a, nullptr, st); }
 
 // =====================================================================  dual path (MultiHopMSA)
 struct DpBuf {

@@ -29,6 +29,13 @@
 // the empty partial (as a chunk past L does), key rows below s are neither loaded nor scored, and a query with no open key ends as
 // y = 0 in the merge.  With kv_start = 0 every step is the plain code, so the result is bitwise that of the plain kernels; the
 // START = false instantiations compile to the same instructions as before the flag existed (kv_start is an unused argument there).
+//
+// Per-row key counts (mopk_decode_attn_lens_*, cross-attention over right-padded audio of unequal length): LENS = true reads the
+// row's own L = kv_lens[b] (clamped into [0, Nk]) where the plain kernel takes one L for the batch; everything after that is the
+// plain code, so a chunk past the row's L writes the empty partial and leaves, key rows >= L are never read, and kv_lens = Nk is
+// bitwise the plain result.  The per-row pointer travels in the kv_start argument (START and LENS are never set together).  These
+// instantiations are built in a unit of their own (-DMOPK_DECODE_LENS, mop_amd/build.py), which leaves the code of the others as
+// it was.
 #include "common.h"
 
 namespace mopk {
@@ -66,8 +73,9 @@ __device__ __forceinline__ void da_unpack(const uint4 &u, float (&f)[4], float) 
     f[2] = __builtin_bit_cast(float, u.z); f[3] = __builtin_bit_cast(float, u.w);
 }
 
-// launch 1: one (row, chunk) partial; ROWS: keys / values through the row table; START: keys from kv_start[b] on
-template <typename T, int DK, int TQB, bool ROWS, bool START>
+// launch 1: one (row, chunk) partial; ROWS: keys / values through the row table; START: keys from kv_start[b] on; LENS: keys up to
+// kv_start[b] (the row's key count in the same argument)
+template <typename T, int DK, int TQB, bool ROWS, bool START, bool LENS = false>
 __global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs a, int nsplit, const int32_t *rows, int64_t rows_ld,
                                                               const int32_t *kv_start) {
     using C = DaCfg<T, DK, TQB>;
@@ -83,6 +91,10 @@ __global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs
     const int tq = a.Tq;
     int L = a.kv_len ? *a.kv_len : a.Nk;
     L = L < 0 ? 0 : (L > a.cap ? a.cap : L);
+    if constexpr (LENS) {
+        const int n = kv_start[b];                                  // uniform: one scalar load per workgroup
+        L = n < 0 ? 0 : (n > L ? L : n);
+    }
     const int c0 = split * C::CH;
     const size_t part = (size_t)bh * nsplit + split;
     float *ml = (float *)a.workspace + part * tq * 2;
@@ -326,6 +338,34 @@ int da_ragged_check(const MopkDecodeAttnRaggedArgs *a) {
     return MOPK_OK;
 }
 
+#ifdef MOPK_DECODE_LENS
+int da_lens_check(const MopkDecodeAttnLensArgs *a) {
+    if (!a) return MOPK_ERR_BAD_ARG;
+    const int rc = da_check(&a->base);
+    if (rc != MOPK_OK) return rc;
+    if (a->base.kv_len || a->base.causal || !a->kv_lens) return MOPK_ERR_BAD_ARG;
+    if ((uintptr_t)a->kv_lens & 3) return MOPK_ERR_UNSUPPORTED;
+    return MOPK_OK;
+}
+
+template <typename T, int DK>
+void da_launch_lens_dk(const MopkDecodeAttnArgs *a, const int32_t *kv_lens, hipStream_t st) {
+    const int ns = da_nsplit(a);
+    const dim3 grid((unsigned)(a->B * a->H), (unsigned)ns), block(DA_THREADS);
+    if (a->Tq <= 1) hipLaunchKernelGGL((da_split_kernel<T, DK, 1, false, false, true>), grid, block, 0, st, *a, ns, (const int32_t *)nullptr, (int64_t)0, kv_lens);
+    else if (a->Tq <= 4) hipLaunchKernelGGL((da_split_kernel<T, DK, 4, false, false, true>), grid, block, 0, st, *a, ns, (const int32_t *)nullptr, (int64_t)0, kv_lens);
+    else hipLaunchKernelGGL((da_split_kernel<T, DK, 16, false, false, true>), grid, block, 0, st, *a, ns, (const int32_t *)nullptr, (int64_t)0, kv_lens);
+    hipLaunchKernelGGL(da_merge_kernel<T>, dim3((unsigned)(a->B * a->H)), block, 0, st, *a, ns);
+}
+
+template <typename T>
+void da_launch_lens(const MopkDecodeAttnArgs *a, const int32_t *kv_lens, hipStream_t st) {
+    if (a->dk == 32) da_launch_lens_dk<T, 32>(a, kv_lens, st);
+    else if (a->dk == 64) da_launch_lens_dk<T, 64>(a, kv_lens, st);
+    else da_launch_lens_dk<T, 128>(a, kv_lens, st);
+}
+#endif
+
 }  // namespace
 }  // namespace mopk
 
@@ -333,6 +373,7 @@ using namespace mopk;
 
 extern "C" {
 
+#ifndef MOPK_DECODE_LENS
 int mopk_decode_attn_supported(const MopkDecodeAttnArgs *a) { return da_check(a) == MOPK_OK; }
 
 size_t mopk_decode_attn_workspace_bytes(const MopkDecodeAttnArgs *a) {
@@ -386,5 +427,26 @@ int mopk_decode_attn_ragged_fwd(const MopkDecodeAttnRaggedArgs *a, void *stream)
     }
     return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
 }
+
+#else  // MOPK_DECODE_LENS: the unit of the per-row key counts
+int mopk_decode_attn_lens_supported(const MopkDecodeAttnLensArgs *a) { return da_lens_check(a) == MOPK_OK; }
+
+size_t mopk_decode_attn_lens_workspace_bytes(const MopkDecodeAttnLensArgs *a) {
+    if (da_lens_check(a) != MOPK_OK) return 0;
+    const MopkDecodeAttnArgs *b = &a->base;
+    return (size_t)b->B * b->H * da_nsplit(b) * b->Tq * (b->dk + 2) * sizeof(float);      // = mopk_decode_attn_workspace_bytes(base)
+}
+
+int mopk_decode_attn_lens_fwd(const MopkDecodeAttnLensArgs *a, void *stream) {
+    const int rc = da_lens_check(a);
+    if (rc != MOPK_OK) return rc;
+    const MopkDecodeAttnArgs *b = &a->base;
+    if (!b->q.ptr || !b->k.ptr || !b->v.ptr || !b->y.ptr || !b->workspace) return MOPK_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (b->io_dtype == MOPK_BF16) da_launch_lens<unsigned short>(b, a->kv_lens, st);
+    else da_launch_lens<float>(b, a->kv_lens, st);
+    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+}
+#endif
 
 }  // extern "C"

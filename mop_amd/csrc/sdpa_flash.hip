@@ -11,6 +11,15 @@
 //   O^T[d, query] += V^T[d, key] . P^T[key, query]
 // with V^T staged in LDS (key columns permuted to the accumulator's k order).  The backward is two kernels (dQ per
 // query block, dK/dV per key block), each recomputing P from the saved row log-sum-exp: deterministic, no atomics.
+//
+// Per-row lengths (LENS = true, mopk_sdpa_lens_*): a batch of right-padded sequences.  q_lens[b] / kv_lens[b] (clamped into [0, N] /
+// [0, Nk]) are read once per workgroup and take the place of N / Nk as the loop bounds and the bounds of every load, exactly as the
+// tail beyond N / Nk is treated: key tiles past kv_lens[b] are not visited (forward, dQ), query tiles past q_lens[b] are not
+// visited (dK/dV), only the last tile is edge-masked (element selects), rows beyond a length are never loaded (so NaN there cannot
+// reach an MFMA), and a workgroup that owns only padding writes its zeros and leaves.  Padding rows are still WRITTEN (y, dq, dk,
+// dv = 0; lse = +inf).  With full lengths every instruction sees the operands of the LENS = false kernel: bitwise equal results.
+// The LENS = true instantiations live in a unit of their own (-DMOPK_SDPA_LENS, mop_amd/build.py), so the code of the others
+// stays what it was.
 #include "flash_common.h"
 
 namespace mopk {
@@ -43,6 +52,13 @@ __device__ __forceinline__ void fa_mix_grad(float s1, float s2, float a2, float 
 }
 // optional explicit mask (uint8, 0 = blocked) and additive fp32 bias, element (b,h,i,j)      (whisper_mop.py:166-170, :202-205)
 struct FaMB { const uint8_t *mask; const float *bias; };
+// per-row lengths (LENS instantiations): device int32 (B) each, or nullptr = full length
+struct FaLens { const int32_t *q, *kv; };
+__device__ __forceinline__ int fa_len(const int32_t *p, int b, int full) {
+    if (!p) return full;
+    const int n = p[b];                                            // b comes from blockIdx: one scalar load per workgroup
+    return n < 0 ? 0 : (n > full ? full : n);
+}
 __device__ __forceinline__ FaMB fa_mb(const MopkSdpaArgs &a, int b, int hh) {
     FaMB m;
     m.mask = a.mask ? a.mask + b * a.mask_sb + hh * a.mask_sh : nullptr;
@@ -64,25 +80,28 @@ __device__ __forceinline__ float fa_apply_mb(float z, float cz, const FaMB &m, c
 }  // namespace
 
 // ------------------------------------------------------------------ forward
-template <int DK, typename IOT, bool CAUSAL, bool DUAL, bool MB>
-__global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kernel(MopkSdpaArgs a, float *lse, FaDual u) {
+template <int DK, typename IOT, bool CAUSAL, bool DUAL, bool MB, bool LENS = false>
+__global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kernel(MopkSdpaArgs a, float *lse, FaDual u, FaLens ln) {
     constexpr int DT = DK / 32, LDK = DK + 8;
     __shared__ __attribute__((aligned(16))) unsigned short Ks[FA_KT * LDK], Vt[DK * FA_LDT], K2s[DUAL ? FA_KT * LDK : 8];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int N = a.N, Nk = CAUSAL ? N : sdpa_nk(a);              // queries, keys (causal calls are square)
+    const int N = a.N, NkA = CAUSAL ? N : sdpa_nk(a);             // queries, keys (causal calls are square)
     int qb, bh;
     fa_block_id((N + FA_QB - 1) / FA_QB, qb, bh);
     const int b = bh / a.H, hh = bh % a.H;
     const int q0 = qb * FA_QB, qi = q0 + 32 * w + r;
     const int wu = __builtin_amdgcn_readfirstlane(w);              // the wave index as a scalar (uniform branches on it)
     const bool qok = qi < N;
+    // LENS: Nq queries and Nk keys of this row are real; qin = this lane's query is one of them (qok still decides what is written)
+    const int Nq = LENS ? fa_len(ln.q, b, N) : N, Nk = LENS ? fa_len(ln.kv, b, NkA) : NkA;
+    const bool qin = LENS ? qi < Nq : qok;
     // logits in base-2 units: the scale c = log2(e) / sqrt(dk) multiplies the fp32 scores (q stays as given).  Plain
     // scores stay raw until the exp2 argument (an fma in place of the subtraction); bias / mask and the dual mix scale them first.
     constexpr bool RAW = !DUAL && !MB;
     constexpr float c = FA_RSQ<DK> * FA_LOG2E, ce = RAW ? c : 1.f;
     const IOT *kp = (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh, *vp = (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh;
     bf16x8 qe[DK / 16];
-    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, 1.f);
+    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qin, h, 1.f);
     bf16x8 q2e[DUAL ? DK / 16 : 1];
     const IOT *k2p = nullptr;
     if (DUAL) {
@@ -96,6 +115,13 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
     f32x16 O[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) O[dt] = fa_zero();
+    if (LENS && q0 >= Nq) {                     // workgroup-uniform: all 128 queries are padding -- write the zeros and leave
+        if (qok) {
+            fa_store_rows<DK, IOT>((IOT *)a.y.ptr + b * a.y.sb + hh * a.y.sh + (int64_t)qi * a.y.sn, O, h, 0.f);
+            if (h == 0) lse[(int64_t)bh * N + qi] = INFINITY;
+        }
+        return;
+    }
     int nkt = (Nk + FA_KT - 1) / FA_KT;
     if (CAUSAL) nkt = min(nkt, (min(q0 + FA_QB, N) + FA_KT - 1) / FA_KT);   // keys beyond the block's last query are never seen
     FaTile<DK> fk, fv, fk2;               // next tile's K / V (/ K2) rows, in flight while the current tile is computed
@@ -169,7 +195,7 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 2 : 3) sdpa_flash_fwd_kerne
     if (qok) {
         // no open key with a finite logit (every key blocked, or an all -inf bias): the row is 0, as torch's SDPA gives, and lse = +inf
         // makes the backward's P = 2^(z - lse) exactly 0 on it.  (The sum over blocked keys still in O and l is finite: 0 * O = 0.)
-        const bool empty = m == FA_NEG;
+        const bool empty = m == FA_NEG || !qin;                   // a padding query (LENS) is a row with no open key
         fa_store_rows<DK, IOT>((IOT *)a.y.ptr + b * a.y.sb + hh * a.y.sh + (int64_t)qi * a.y.sn, O, h, empty ? 0.f : 1.f / l);
         if (h == 0) lse[(int64_t)bh * N + qi] = empty ? INFINITY : m + __builtin_amdgcn_logf(l);     // log2 of the row sum of 2^(logit)
     }
@@ -209,37 +235,43 @@ __global__ void sdpa_flash_delta_kernel(MopkSdpaArgs a, float *delta) {
 }
 
 // dQ: one workgroup per 128 queries, loop over key tiles
-template <int DK, typename IOT, bool CAUSAL, bool DUAL, bool MB>
-__global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_dq_kernel(MopkSdpaArgs a, const float *lse, const float *delta, FaDual u) {
+template <int DK, typename IOT, bool CAUSAL, bool DUAL, bool MB, bool LENS = false>
+__global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_dq_kernel(MopkSdpaArgs a, const float *lse, const float *delta, FaDual u, FaLens ln) {
     constexpr int DT = DK / 32, LDK = DK + 8;
     __shared__ __attribute__((aligned(16))) unsigned short Ks[FA_KT * LDK], Vs[FA_KT * LDK], Kt[DK * FA_LDT];
     __shared__ __attribute__((aligned(16))) unsigned short K2s[DUAL ? FA_KT * LDK : 8], K2t[DUAL ? DK * FA_LDT : 8];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int N = a.N, Nk = CAUSAL ? N : sdpa_nk(a);              // queries, keys (causal calls are square)
+    const int N = a.N, NkA = CAUSAL ? N : sdpa_nk(a);             // queries, keys (causal calls are square)
     int qb, bh;
     fa_block_id((N + FA_QB - 1) / FA_QB, qb, bh);
     const int b = bh / a.H, hh = bh % a.H;
     const int q0 = qb * FA_QB, qi = q0 + 32 * w + r;
     const bool qok = qi < N;
+    const int Nq = LENS ? fa_len(ln.q, b, N) : N, Nk = LENS ? fa_len(ln.kv, b, NkA) : NkA;      // as in the forward
+    const bool qin = LENS ? qi < Nq : qok;
     constexpr bool RAW = !DUAL && !MB;                             // scale of the fp32 scores as in the forward
     constexpr float sc = FA_RSQ<DK>, c = sc * FA_LOG2E, ce = RAW ? c : 1.f;
     const IOT *kp = (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh, *vp = (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh;
     bf16x8 qe[DK / 16], dof[DK / 16];
-    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, 1.f);
-    fa_frags<DK, IOT>(dof, (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh + (int64_t)qi * a.dy.sn, qok, h, 1.f);
+    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qin, h, 1.f);
+    fa_frags<DK, IOT>(dof, (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh + (int64_t)qi * a.dy.sn, qin, h, 1.f);
     bf16x8 q2e[DUAL ? DK / 16 : 1];
     const IOT *k2p = nullptr;
     if (DUAL) {
         fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)u.q2.ptr + b * u.q2.sb + hh * u.q2.sh + (int64_t)qi * u.q2.sn, qok, h, 1.f);
         k2p = (const IOT *)u.k2.ptr + b * u.k2.sb + hh * u.k2.sh;
     }
-    const float Li = qok ? lse[(int64_t)bh * N + qi] : 0.f, di = qok ? delta[(int64_t)bh * N + qi] : 0.f;
+    const float Li = qin ? lse[(int64_t)bh * N + qi] : 0.f, di = qin ? delta[(int64_t)bh * N + qi] : 0.f;
     const FaMB mb = fa_mb(a, b, hh);
     const FaDrop drop = fa_drop(a.dropout_p, a.dropout_seed);
     const uint32_t rowh = fa_drop_row(drop, bh, qi);
     f32x16 dQ[DT], dQ2[DUAL ? DT : 1];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) { dQ[dt] = fa_zero(); if (DUAL) dQ2[dt] = fa_zero(); }
+    if (LENS && q0 >= Nq) {                     // workgroup-uniform: only padding queries -- dq = 0 is written
+        if (qok) fa_store_rows<DK, IOT>((IOT *)a.dq.ptr + b * a.dq.sb + hh * a.dq.sh + (int64_t)qi * a.dq.sn, dQ, h, 1.f);
+        return;
+    }
     int nkt = (Nk + FA_KT - 1) / FA_KT;
     if (CAUSAL) nkt = min(nkt, (min(q0 + FA_QB, N) + FA_KT - 1) / FA_KT);
     FaTile<DK> fk, fv, fk2;
@@ -268,7 +300,7 @@ __global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_d
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
                 const int j = k0 + 32 * s2 + tile_row(g, h);
-                bool ok = qok && j < Nk && (!CAUSAL || j <= qi);
+                bool ok = qin && j < Nk && (!CAUSAL || j <= qi);
                 const float s1 = DUAL ? S[g] * c : S[g], s2 = DUAL ? T2[g] * c : 0.f;
                 float z = DUAL ? fa_mix(s1, s2, u.a2, u.g_or) : s1;
                 if (MB) { bool blk; z = fa_apply_mb(z, DUAL ? 1.f : c, mb, a, qi, j, Nk, blk); ok = ok && !blk; }
@@ -292,26 +324,30 @@ __global__ void __launch_bounds__(FA_NW * 64, (DUAL || MB) ? 2 : 3) sdpa_flash_d
 }
 
 // dK, dV: one workgroup per 128 keys (a lane owns a key), loop over query tiles
-template <int DK, typename IOT, bool CAUSAL, bool DUAL, bool MB>
-__global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kernel(MopkSdpaArgs a, const float *lse, const float *delta, FaDual u) {
+template <int DK, typename IOT, bool CAUSAL, bool DUAL, bool MB, bool LENS = false>
+__global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kernel(MopkSdpaArgs a, const float *lse, const float *delta, FaDual u, FaLens ln) {
     constexpr int DT = DK / 32, LDK = DK + 8;
     __shared__ __attribute__((aligned(16))) unsigned short Qs[FA_KT * LDK], Gs[FA_KT * LDK], Qt[DK * FA_LDT], Gt[DK * FA_LDT];
     __shared__ __attribute__((aligned(16))) unsigned short Q2s[DUAL ? FA_KT * LDK : 8], Q2t[DUAL ? DK * FA_LDT : 8];
     __shared__ __attribute__((aligned(16))) float Ls[FA_KT], Ds[FA_KT];      // 16-byte aligned: the four consecutive rows of a register quad are one ds_read_b128
     __shared__ __attribute__((aligned(16))) uint32_t Hs[FA_KT];              // dropout row hashes of the tile's queries
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int N = a.N, Nk = CAUSAL ? N : sdpa_nk(a);              // queries, keys (causal calls are square)
+    const int NA = a.N, NkA = CAUSAL ? NA : sdpa_nk(a);           // queries, keys (causal calls are square)
     int kb, bh;
-    fa_block_id((Nk + FA_QB - 1) / FA_QB, kb, bh);
+    fa_block_id((NkA + FA_QB - 1) / FA_QB, kb, bh);
     const int b = bh / a.H, hh = bh % a.H;
     const int k0 = kb * FA_QB, kj = k0 + 32 * w + r;
-    const bool kok = kj < Nk;
+    const bool kok = kj < NkA;
+    // LENS: N queries and Nk keys of this row are real (NA / NkA stay the extents of the tensors and of lse / delta); kin = this
+    // lane's key is one of them (kok still decides what is written)
+    const int N = LENS ? fa_len(ln.q, b, NA) : NA, Nk = LENS ? fa_len(ln.kv, b, NkA) : NkA;
+    const bool kin = LENS ? kj < Nk : kok;
     constexpr bool RAW = !DUAL && !MB;                             // scale of the fp32 scores as in the forward
     constexpr float sc = FA_RSQ<DK>, c = sc * FA_LOG2E, ce = RAW ? c : 1.f;
     const IOT *qp = (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh, *gp = (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh;
     bf16x8 kf[DK / 16], vf[DK / 16];
-    fa_frags<DK, IOT>(kf, (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh + (int64_t)kj * a.k.sn, kok, h, 1.f);
-    fa_frags<DK, IOT>(vf, (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh + (int64_t)kj * a.v.sn, kok, h, 1.f);
+    fa_frags<DK, IOT>(kf, (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh + (int64_t)kj * a.k.sn, kin, h, 1.f);
+    fa_frags<DK, IOT>(vf, (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh + (int64_t)kj * a.v.sn, kin, h, 1.f);
     bf16x8 k2f[DUAL ? DK / 16 : 1];
     const IOT *q2p = nullptr;
     if (DUAL) {
@@ -321,6 +357,13 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
     f32x16 dK[DT], dV[DT], dK2[DUAL ? DT : 1];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) { dK[dt] = fa_zero(); dV[dt] = fa_zero(); if (DUAL) dK2[dt] = fa_zero(); }
+    if (LENS && k0 >= Nk) {                     // workgroup-uniform: only padding keys -- dk = dv = 0 are written
+        if (kok) {
+            fa_store_rows<DK, IOT>((IOT *)a.dk_.ptr + b * a.dk_.sb + hh * a.dk_.sh + (int64_t)kj * a.dk_.sn, dK, h, 1.f);
+            fa_store_rows<DK, IOT>((IOT *)a.dv.ptr + b * a.dv.sb + hh * a.dv.sh + (int64_t)kj * a.dv.sn, dV, h, 1.f);
+        }
+        return;
+    }
     const FaMB mb = fa_mb(a, b, hh);
     const FaDrop drop = fa_drop(a.dropout_p, a.dropout_seed);
     const int nqt = (N + FA_KT - 1) / FA_KT, qt0 = CAUSAL ? k0 / FA_KT : 0;   // causal: queries before this key block see none of its keys
@@ -332,8 +375,8 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
     float nl = 0.f, nd = 0.f;
     auto fetch_stats = [&](int i0) {
         const bool ok = tid < FA_KT && i0 + tid < N;
-        nl = ok ? lse[(int64_t)bh * N + i0 + tid] : 0.f;
-        nd = ok ? delta[(int64_t)bh * N + i0 + tid] : 0.f;
+        nl = ok ? lse[(int64_t)bh * NA + i0 + tid] : 0.f;
+        nd = ok ? delta[(int64_t)bh * NA + i0 + tid] : 0.f;
     };
     fetch_stats(qt0 * FA_KT);
     for (int qt = qt0; qt < nqt; ++qt) {
@@ -367,7 +410,7 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
                 const int il = 32 * s2 + tile_row(g, h), i = i0 + il;
-                bool ok = kok && i < N && (!CAUSAL || kj <= i);
+                bool ok = kin && i < N && (!CAUSAL || kj <= i);
                 const float s1 = DUAL ? S[g] * c : S[g], s2 = DUAL ? T2[g] * c : 0.f;
                 float z = DUAL ? fa_mix(s1, s2, u.a2, u.g_or) : s1;
                 if (MB) { bool blk; z = fa_apply_mb(z, DUAL ? 1.f : c, mb, a, i, kj, Nk, blk); ok = ok && !blk; }
@@ -395,6 +438,7 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
 }
 
 // ------------------------------------------------------------------ host side
+#ifndef MOPK_SDPA_LENS
 static bool fa_aligned(const MopkView4 &v, int es) {
     const int64_t al = 16 / es;
     return ((uintptr_t)v.ptr & 15) == 0 && v.sb % al == 0 && v.sh % al == 0 && v.sn % al == 0;
@@ -412,8 +456,8 @@ size_t sdpa_flash_saved_bytes(const MopkSdpaArgs *a) { return (size_t)a->B * a->
 size_t sdpa_flash_ws_bytes(const MopkSdpaArgs *a) { return (size_t)a->B * a->H * a->N * sizeof(float) + 256; }      // delta
 
 #define FA_LAUNCH4(KERNEL, DK_, IOT_, DUAL_, MB_, GRID, ...)                                                   \
-    do { if (a->causal) hipLaunchKernelGGL((KERNEL<DK_, IOT_, true, DUAL_, MB_>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__);   \
-         else hipLaunchKernelGGL((KERNEL<DK_, IOT_, false, DUAL_, MB_>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__); } while (0)
+    do { if (a->causal) hipLaunchKernelGGL((KERNEL<DK_, IOT_, true, DUAL_, MB_>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__, FaLens{});   \
+         else hipLaunchKernelGGL((KERNEL<DK_, IOT_, false, DUAL_, MB_>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__, FaLens{}); } while (0)
 #define FA_DISPATCH5(KERNEL, DUAL_, MB_, GRID, ...)                                                            \
     do {                                                                                                       \
         if (a->io_dtype == MOPK_BF16) { if (a->dk == 64) FA_LAUNCH4(KERNEL, 64, unsigned short, DUAL_, MB_, GRID, __VA_ARGS__);   \
@@ -660,5 +704,44 @@ int dp_flash_bwd(const MopkDualPathArgs *a, hipStream_t st) {
     MOPK_CHECK_LAUNCH();
     return MOPK_OK;
 }
+
+#else   // MOPK_SDPA_LENS: the unit of the LENS = true instantiations (plain SDPA only: no mask / bias tensor, no dual path)
+int sdpa_flash_supported(const MopkSdpaArgs *a, bool bwd);
+
+#define FA_LENS_LAUNCH2(KERNEL, DK_, IOT_, GRID, ...)                                                          \
+    do { if (a->causal) hipLaunchKernelGGL((KERNEL<DK_, IOT_, true, false, false, true>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__);   \
+         else hipLaunchKernelGGL((KERNEL<DK_, IOT_, false, false, false, true>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__); } while (0)
+#define FA_LENS_DISPATCH(KERNEL, GRID, ...)                                                                    \
+    do {                                                                                                       \
+        if (a->io_dtype == MOPK_BF16) { if (a->dk == 64) FA_LENS_LAUNCH2(KERNEL, 64, unsigned short, GRID, __VA_ARGS__);   \
+                                        else FA_LENS_LAUNCH2(KERNEL, 32, unsigned short, GRID, __VA_ARGS__); }            \
+        else { if (a->dk == 64) FA_LENS_LAUNCH2(KERNEL, 64, float, GRID, __VA_ARGS__);                          \
+               else FA_LENS_LAUNCH2(KERNEL, 32, float, GRID, __VA_ARGS__); }                                    \
+    } while (0)
+
+int sdpa_flash_lens_fwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int32_t *kv_lens, hipStream_t st) {
+    if (a->mask || a->bias || !sdpa_flash_supported(a, false)) return MOPK_ERR_UNSUPPORTED;
+    const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H);
+    const FaLens ln{q_lens, kv_lens};
+    FA_LENS_DISPATCH(sdpa_flash_fwd_kernel, grid, *a, (float *)a->saved, FaDual{}, ln);
+    MOPK_CHECK_LAUNCH();
+    return MOPK_OK;
+}
+int sdpa_flash_lens_bwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int32_t *kv_lens, hipStream_t st) {
+    if (a->mask || a->bias || !sdpa_flash_supported(a, true)) return MOPK_ERR_UNSUPPORTED;
+    const int64_t rows = (int64_t)a->B * a->H * a->N;
+    float *delta = (float *)a->workspace;       // delta of a padding row is dy . 0: never read by the LENS kernels
+    if (a->io_dtype == MOPK_BF16) hipLaunchKernelGGL((sdpa_flash_delta_kernel<unsigned short>), dim3((rows * (a->dk / 8) + 255) / 256), dim3(256), 0, st, *a, delta);
+    else hipLaunchKernelGGL((sdpa_flash_delta_kernel<float>), dim3((rows * (a->dk / 8) + 255) / 256), dim3(256), 0, st, *a, delta);
+    MOPK_CHECK_LAUNCH();
+    const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H), kgrid(((sdpa_nk(*a) + FA_QB - 1) / FA_QB) * a->B * a->H);
+    const FaLens ln{q_lens, kv_lens};
+    FA_LENS_DISPATCH(sdpa_flash_dq_kernel, grid, *a, (const float *)a->saved, (const float *)delta, FaDual{}, ln);
+    MOPK_CHECK_LAUNCH();
+    FA_LENS_DISPATCH(sdpa_flash_dkv_kernel, kgrid, *a, (const float *)a->saved, (const float *)delta, FaDual{}, ln);
+    MOPK_CHECK_LAUNCH();
+    return MOPK_OK;
+}
+#endif  // MOPK_SDPA_LENS
 
 }  // namespace mopk

@@ -5,7 +5,7 @@ from .components import (MLP, MSA, Block, DropPath, FuseExcInh, Kernels3, PatchE
                          ViewsLinear, ViTEncoder)
 from .quartet_attn_patch import CausalSelfAttention, TransformerConfig  # noqa: F401
 from .vit_mop import ViT_MoP  # noqa: F401
-from .whisper_mop import (DecoderBlock, EncoderBlock, FuseExcInh2D, Kernels2D, MoP2D,  # noqa: F401
+from .whisper_mop import (DecoderBlock, EncodedAudio, EncoderBlock, FuseExcInh2D, Kernels2D, MoP2D,  # noqa: F401
                           MultiheadCrossAttention, MultiheadSelfAttention, ViewsConv2D, WhisperConfig, WhisperDecodeCache, WhisperMoP,
                           create_whisper_baseline, create_whisper_mop)
 from .vit_edgewise import BlockEdgewise, ViTEdgewise  # noqa: F401

@@ -10,7 +10,7 @@ are stock PyTorch-ROCm layers.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -37,6 +37,26 @@ class WhisperConfig:
     n_views: int = 5
     n_kernels: int = 3
     kernel_size: int = 5
+
+
+class EncodedAudio(NamedTuple):
+    """encoder output of a batch of clips of different lengths (`WhisperMoP.encode` on a list of mel tensors).
+    out: (B, T, D), right-padded to T = the longest clip; rows t >= lens[b] of item b are unspecified (finite, never read).
+    lens: int32 (B,) device tensor of the clips' frame counts, or None when every clip has T frames (the uniform batch).
+    `decode`, `init_decode_cache` and `DecoderBlock.forward` take it wherever they take the plain (B, T, D) tensor."""
+    out: torch.Tensor
+    lens: Optional[torch.Tensor]
+
+
+class _Batch(NamedTuple):
+    """what the prompt checks need to know of the audio batch when the mel is a list: shape[0] and device"""
+    shape: Tuple[int, ...]
+    device: torch.device
+
+
+def _enc_parts(enc):
+    """(out, lens) of an EncodedAudio; (enc, None) of a plain tensor"""
+    return (enc.out, enc.lens) if isinstance(enc, EncodedAudio) else (enc, None)
 
 
 class ViewsConv2D(nn.Module):
@@ -100,18 +120,23 @@ class MultiheadSelfAttention(nn.Module):
         self.attn_drop = nn.Dropout(dropout)
         self.resid_drop = nn.Dropout(dropout)
 
-    def forward(self, x: torch.Tensor, attn_bias: Optional[torch.Tensor] = None):
+    def forward(self, x: torch.Tensor, attn_bias: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None):
+        """lens: int32 (B,) device tensor for right-padded rows (tokens t >= lens[b] are padding: neither queries nor keys), or None"""
         pdrop = float(self.attn_drop.p) if self.training else 0.0      # dropout on the probabilities (:172), inside the kernels
         B, T, D = x.shape
         H, Dh = self.n_head, self.head_dim
         q, k, v = (p(x).view(B, T, H, Dh) for p in (self.q_proj, self.k_proj, self.v_proj))
-        y = ops.sdpa_core(q, k, v, bias=attn_bias, causal=self.causal, dropout_p=pdrop)
+        if lens is None:
+            y = ops.sdpa_core(q, k, v, bias=attn_bias, causal=self.causal, dropout_p=pdrop)
+        else:
+            y = ops.sdpa_core(q, k, v, bias=attn_bias, causal=self.causal, dropout_p=pdrop, q_lens=lens, kv_lens=lens)
         return self.resid_drop(self.o_proj(y))
 
 
 class MultiheadCrossAttention(nn.Module):
     """queries from x_q, keys / values from x_kv; softmax(q k^T / sqrt(dh) [+ attn_mask]) v in libmopk with Nk = T_kv keys
-    (reference :180-221).  attn_mask is ADDITIVE in the reference (:213-214), so it is passed to the core as its bias."""
+    (reference :180-221).  attn_mask is ADDITIVE in the reference (:213-214), so it is passed to the core as its bias.
+    x_kv may be an `EncodedAudio`: item b's queries then see only the keys j < lens[b]."""
 
     def __init__(self, dim_q: int, dim_kv: int, n_head: int, dropout: float, bias: bool):
         super().__init__()
@@ -127,13 +152,17 @@ class MultiheadCrossAttention(nn.Module):
 
     def forward(self, x_q: torch.Tensor, x_kv: torch.Tensor, attn_mask: Optional[torch.Tensor] = None):
         pdrop = float(self.attn_drop.p) if self.training else 0.0      # dropout on the probabilities (:217), inside the kernels
+        x_kv, kv_lens = _enc_parts(x_kv)
         B, Tq, _ = x_q.shape
         Tk = x_kv.shape[1]
         H, Dh = self.n_head, self.head_dim
         q = self.q_proj(x_q).view(B, Tq, H, Dh)
         k = self.k_proj(x_kv).view(B, Tk, H, Dh)
         v = self.v_proj(x_kv).view(B, Tk, H, Dh)
-        y = ops.sdpa_core(q, k, v, bias=attn_mask, dropout_p=pdrop)
+        if kv_lens is None:
+            y = ops.sdpa_core(q, k, v, bias=attn_mask, dropout_p=pdrop)
+        else:
+            y = ops.sdpa_core(q, k, v, bias=attn_mask, dropout_p=pdrop, kv_lens=kv_lens)
         return self.resid_drop(self.o_proj(y))
 
 
@@ -160,8 +189,8 @@ class EncoderBlock(nn.Module):
         self.mlp = MLP(D, cfg.dropout, cfg.bias)
         self.mop = MoP2D(cfg.n_views, cfg.n_kernels, cfg.kernel_size)
 
-    def forward(self, x, mel2d):
-        x = x + self.attn(self.ln1(x))
+    def forward(self, x, mel2d, lens=None):
+        x = x + (self.attn(self.ln1(x)) if lens is None else self.attn(self.ln1(x), lens=lens))
         gate_t, _, _ = self.mop(mel2d)
         x = x * gate_t
         x = x + self.mlp(self.ln2(x))
@@ -182,6 +211,7 @@ class DecoderBlock(nn.Module):
         self.mlp = MLP(D, cfg.dropout, cfg.bias)
 
     def forward(self, x: torch.Tensor, enc: torch.Tensor) -> torch.Tensor:
+        """enc: (B, T_audio, D), or an EncodedAudio for clips of different lengths"""
         x = x + self.self_attn(self.ln1(x))
         x = x + self.cross_attn(self.ln2(x), enc)
         x = x + self.mlp(self.ln3(x))
@@ -196,12 +226,16 @@ class WhisperDecodeCache:
     length: the number of cached tokens as a (1,) int32 DEVICE tensor (the kernels read it, so a step's launch arguments do not
     change from step to step); pos: its host mirror (the host drives the loop, so keeping it costs no sync).
     kv_start: None (every row's tokens start at column 0), or an int32 (B,) DEVICE tensor for a ragged batch whose prompts are
-    left-padded to one length: row b's tokens start at column kv_start[b] (set it after construction; see decode_step)."""
+    left-padded to one length: row b's tokens start at column kv_start[b] (set it after construction; see decode_step).
+    audio_lens: None (every item's cross keys are all T_audio rows), or an int32 (items,) DEVICE tensor for clips of different
+    lengths right-padded to T_audio: item b's queries see the cross keys j < audio_lens[b] (set after construction, as kv_start;
+    init_decode_cache sets it from an EncodedAudio).  One entry per row of cross_k, i.e. per item where beams / samples share it."""
 
     def __init__(self, cross_k, cross_v, self_k, self_v, length: torch.Tensor, max_len: int):
         self.cross_k, self.cross_v, self.self_k, self.self_v = cross_k, cross_v, self_k, self_v
         self.length, self.pos, self.max_len = length, 0, int(max_len)
         self.kv_start: Optional[torch.Tensor] = None
+        self.audio_lens: Optional[torch.Tensor] = None
 
     @property
     def dtype(self) -> torch.dtype:
@@ -244,8 +278,71 @@ class WhisperMoP(nn.Module):
     def _pos(self, T: int, device: torch.device) -> torch.Tensor:
         return torch.arange(T, device=device, dtype=torch.long).unsqueeze(0)
 
+    def _audio_check(self, mel, what: str) -> Optional[List[int]]:
+        """None for a (B, T_audio, n_mels) tensor; for a list / tuple of B 2-D (T_b, n_mels) tensors (clips of different lengths),
+        their frame counts.  Raises ValueError on a malformed list, before any device work."""
+        if isinstance(mel, torch.Tensor):
+            return None
+        if not isinstance(mel, (list, tuple)) or len(mel) == 0:
+            raise ValueError(f"{what}: mel must be a (B, T_audio, n_mels) tensor or a non-empty list of B (T_b, n_mels) tensors")
+        for b, m in enumerate(mel):
+            if not isinstance(m, torch.Tensor) or m.dim() != 2:
+                raise ValueError(f"{what}: mel {b} must be a 2-D (T_b, n_mels) tensor, got "
+                                 f"{tuple(m.shape) if isinstance(m, torch.Tensor) else type(m).__name__}")
+            if m.shape[1] != self.cfg.n_mels:
+                raise ValueError(f"{what}: mel {b} has {m.shape[1]} mel bins, the model n_mels = {self.cfg.n_mels}")
+            if not 1 <= m.shape[0] <= self.cfg.n_audio_ctx:
+                raise ValueError(f"{what}: mel {b} has {m.shape[0]} frames, outside [1, n_audio_ctx = {self.cfg.n_audio_ctx}]")
+            if m.dtype != mel[0].dtype or not m.dtype.is_floating_point:
+                raise ValueError(f"{what}: mels must share one floating dtype, mel {b} is {m.dtype}")
+            if m.device != mel[0].device:
+                raise ValueError(f"{what}: mel {b} is on {m.device}, mel 0 on {mel[0].device}")
+        return [int(m.shape[0]) for m in mel]
+
+    @staticmethod
+    def _audio_pad(mel, lens: Optional[List[int]]):
+        """-> (mel (B, T, n_mels), audio_lens): a tensor passes through with audio_lens None; a list is right-padded with ZEROS to
+        T = max(lens) (MoP2D's convolutions have no bias and pad with zeros, so a zero tail is what a clip sees when it is alone),
+        with audio_lens an int32 (B,) device tensor (None when every length is T: the uniform path)"""
+        if lens is None:
+            return mel, None
+        T = max(lens)
+        if min(lens) == T:
+            return torch.stack(list(mel)), None
+        padded = torch.zeros(len(lens), T, mel[0].shape[1], dtype=mel[0].dtype, device=mel[0].device)
+        for b, m in enumerate(mel):
+            padded[b, :lens[b]] = m
+        audio_lens = torch.tensor(lens, dtype=torch.int32)
+        if padded.device.type == "cuda":                               # an asynchronous copy: the host does not wait for it
+            return padded, audio_lens.pin_memory().to(padded.device, non_blocking=True)
+        return padded, audio_lens
+
+    def _batch_check(self, mel, prompt_ids, what: str):
+        """the argument checks generate / beam_search / sample share -> (audio batch info, prompt lengths or None); ValueErrors
+        before any device work"""
+        alens = self._audio_check(mel, what)
+        info = mel if alens is None else _Batch((len(alens),), mel[0].device)
+        lens = self._ragged_check(info, prompt_ids, what)
+        if alens is not None and lens is None and prompt_ids.shape[0] != len(alens):
+            raise ValueError(f"{what}: {prompt_ids.shape[0]} prompts for a batch of {len(alens)} mel inputs")
+        return info, lens
+
     def encode(self, mel: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """mel (B, T_audio, n_mels) -> enc_out (B, T_audio, D), gates (B, L_enc, T_audio)."""
+        """mel (B, T_audio, n_mels) -> enc_out (B, T_audio, D), gates (B, L_enc, T_audio).
+
+        mel may also be a list of B (T_b, n_mels) tensors, 1 <= T_b <= n_audio_ctx (clips of different lengths).  They are
+        right-padded with zeros to T = max T_b; every encoder self-attention then runs with per-row lengths (ops.sdpa_core(q_lens,
+        kv_lens): padding frames are neither queries nor keys), so item b comes out as it would alone.  Returns (EncodedAudio(out,
+        lens), gates): rows >= lens[b] of out and columns >= lens[b] of gates are unspecified.  A list of equal lengths runs the
+        tensor path (lens None)."""
+        alens = self._audio_check(mel, "encode")
+        if alens is not None:
+            mel, audio_lens = self._audio_pad(mel, alens)
+            x, gates = self._encode(mel, audio_lens)
+            return EncodedAudio(x, audio_lens), gates
+        return self._encode(mel, None)
+
+    def _encode(self, mel: torch.Tensor, audio_lens: Optional[torch.Tensor]):
         B, T_a, F_ = mel.shape
         assert F_ == self.cfg.n_mels, "mel dim mismatch"
         x = self.audio_proj(mel)
@@ -255,13 +352,13 @@ class WhisperMoP(nn.Module):
         mel2d = mel.unsqueeze(1).contiguous()                        # (B,1,T,F), as the reference's two transposes give
         gate_layers = []
         for blk in self.encoder:
-            x, gate_t = blk(x, mel2d)
+            x, gate_t = blk(x, mel2d) if audio_lens is None else blk(x, mel2d, audio_lens)
             gate_layers.append(gate_t)
         x = self.enc_ln_f(x)
         return x, torch.stack(gate_layers, dim=1)
 
     def decode(self, enc_out: torch.Tensor, dec_input_ids: torch.Tensor) -> torch.Tensor:
-        """enc_out (B, T_audio, D), dec_input_ids (B, T_text) -> logits (B, T_text, vocab)."""
+        """enc_out (B, T_audio, D) or an EncodedAudio, dec_input_ids (B, T_text) -> logits (B, T_text, vocab)."""
         B, T_t = dec_input_ids.shape
         x = self.wte(dec_input_ids)
         if self.text_pos is not None:
@@ -272,6 +369,11 @@ class WhisperMoP(nn.Module):
         return self.lm_head(self.dec_ln_f(x))
 
     def forward(self, mel: torch.Tensor, dec_input_ids: torch.Tensor, targets: Optional[torch.Tensor] = None):
+        """mel: (B, T_audio, n_mels), or a list of B (T_b, n_mels) clips of different lengths (see encode): every item's logits
+        are then those of the item alone, and the gates' columns >= T_b are unspecified."""
+        alens = self._audio_check(mel, "forward")
+        if alens is not None and dec_input_ids.shape[0] != len(alens):
+            raise ValueError(f"forward: {dec_input_ids.shape[0]} rows of dec_input_ids for a batch of {len(alens)} mel inputs")
         enc_out, gates = self.encode(mel)
         logits = self.decode(enc_out, dec_input_ids)
         loss = None
@@ -287,13 +389,16 @@ class WhisperMoP(nn.Module):
         under bf16 autocast)."""
         if not 0 < int(max_len) <= self.cfg.n_text_ctx:
             raise ValueError(f"init_decode_cache: max_len = {max_len} outside [1, n_text_ctx = {self.cfg.n_text_ctx}]")
+        enc_out, audio_lens = _enc_parts(enc_out)                     # an EncodedAudio sets the cache's audio_lens
         B = enc_out.shape[0]
         H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
         ck, cv = self._cross_kv(enc_out)
         kw = dict(dtype=ck[0].dtype, device=enc_out.device)
         sk = [torch.zeros(B, int(max_len), H, Dh, **kw) for _ in self.decoder]
         sv = [torch.zeros(B, int(max_len), H, Dh, **kw) for _ in self.decoder]
-        return WhisperDecodeCache(ck, cv, sk, sv, torch.zeros(1, dtype=torch.int32, device=enc_out.device), max_len)
+        cache = WhisperDecodeCache(ck, cv, sk, sv, torch.zeros(1, dtype=torch.int32, device=enc_out.device), max_len)
+        cache.audio_lens = audio_lens
+        return cache
 
     def _cross_kv(self, enc_out: torch.Tensor):
         """every decoder layer's cross-attention keys / values, (B, T_audio, H, dh) each, projected once"""
@@ -315,7 +420,10 @@ class WhisperMoP(nn.Module):
         token), row b's prompt in columns [kv_start[b], P).  Row b's token in column c then takes position c - kv_start[b] (text_pos),
         and its queries see only the keys in columns >= kv_start[b] (ops.decode_attention_ragged; a first chunk of more than 16 tokens
         runs ops.sdpa_core with a key-padding mask), so row b decodes as it would alone; the pad columns are never read.  Every
-        later step appends all rows at the same column.  kv_start None is the uniform batch, run exactly as before."""
+        later step appends all rows at the same column.  kv_start None is the uniform batch, run exactly as before.
+
+        Clips of different lengths: with cache.audio_lens set (int32 (B,) device tensor), row b's cross-attention sees the keys
+        j < audio_lens[b] only (ops.decode_attention_lens; a chunk of more than 16 tokens runs ops.sdpa_core with kv_lens)."""
         return self._decode_tokens(cache, ids)
 
     def _decode_tokens(self, cache: WhisperDecodeCache, ids: torch.Tensor, rows: Optional[torch.Tensor] = None,
@@ -329,6 +437,7 @@ class WhisperMoP(nn.Module):
         H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
         idx = cache.length.to(torch.long) + torch.arange(T, device=ids.device)        # positions of the new tokens
         ks = cache.kv_start                                                            # ragged: row b's first column
+        al = cache.audio_lens                                                          # ragged audio: cross keys of item b
         x = self.wte(ids)
         if self.text_pos is not None:
             if ks is None:
@@ -358,7 +467,9 @@ class WhisperMoP(nn.Module):
             q = ca.q_proj(blk.ln2(x)).view(B, T, H, Dh)
             ck, cv = cache.cross_k[l], cache.cross_v[l]
             if long_chunk:
-                y = ops.sdpa_core(q, ck, cv)
+                y = ops.sdpa_core(q, ck, cv) if al is None else ops.sdpa_core(q, ck, cv, kv_lens=al)
+            elif al is not None:                                                       # one length per item = per row of q here
+                y = ops.decode_attention_lens(q.view(B // beams, beams * T, H, Dh), ck, cv, al, nk=ck.shape[1]).view(B, T, H * Dh)
             elif beams > 1:
                 y = ops.decode_attention(q.view(B // beams, beams * T, H, Dh), ck, cv, nk=ck.shape[1]).view(B, T, H * Dh)
             else:
@@ -419,14 +530,16 @@ class WhisperMoP(nn.Module):
 
         prompt_ids may also be a list of B 1-D tensors of different lengths (a ragged batch): they are left-padded in one cache with
         a per-row start (WhisperDecodeCache.kv_start), each row decodes as it would alone, and the tokens come back as a list of B
-        1-D tensors, prompt b followed by its max_new_tokens tokens (views of one device tensor)."""
-        lens = self._ragged_check(mel, prompt_ids, "generate")
+        1-D tensors, prompt b followed by its max_new_tokens tokens (views of one device tensor).
+        mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode; it combines with a prompt list): every
+        row decodes as it would alone."""
+        mel_info, lens = self._batch_check(mel, prompt_ids, "generate")
         B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
         if T_p < 1 or max_new_tokens < 1:
             raise ValueError(f"generate: needs a prompt and at least one new token (T_p = {T_p}, max_new_tokens = {max_new_tokens})")
         if T_p + max_new_tokens > self.cfg.n_text_ctx:
             raise ValueError(f"generate: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
-        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel.device)
+        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
         enc, _ = self.encode(mel)
         cache = self.init_decode_cache(enc, T_p + max_new_tokens)
         cache.kv_start = kv_start
@@ -484,8 +597,10 @@ class WhisperMoP(nn.Module):
         reads a beam's history through the device row table (ops.decode_attention_rows).  graph=True captures one step (decoder
         step + beam_step) after the first eager one and replays it (torch.cuda.graph, one stream, static buffers).
         prompt_ids may also be a list of B 1-D tensors of different lengths (see generate): the tokens then come back as a list of B
-        1-D tensors, prompt b followed by max_new_tokens tokens; gen_len counts generated tokens only, as for a tensor."""
-        lens = self._ragged_check(mel, prompt_ids, "beam_search")
+        1-D tensors, prompt b followed by max_new_tokens tokens; gen_len counts generated tokens only, as for a tensor.
+        mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode): an item's beams share its cross cache and
+        its length."""
+        mel_info, lens = self._batch_check(mel, prompt_ids, "beam_search")
         B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
         K = int(num_beams)
         if not 1 <= K <= ops.BEAM_MAX_K:
@@ -498,19 +613,20 @@ class WhisperMoP(nn.Module):
             raise ValueError(f"beam_search: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
         cap = T_p + max_new_tokens
         H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
-        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel.device)
-        enc, _ = self.encode(mel)
+        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
+        enc, audio_lens = _enc_parts(self.encode(mel)[0])
         ck, cv = self._cross_kv(enc)
         kw = dict(dtype=ck[0].dtype, device=enc.device)
         sk = [torch.zeros(B * K, cap, H, Dh, **kw) for _ in self.decoder]
         sv = [torch.zeros(B * K, cap, H, Dh, **kw) for _ in self.decoder]
         length = torch.zeros(1, dtype=torch.int32, device=enc.device)
         prompt_cache = WhisperDecodeCache(ck, cv, [t[::K] for t in sk], [t[::K] for t in sv], length, cap)
-        prompt_cache.kv_start = kv_start
+        prompt_cache.kv_start, prompt_cache.audio_lens = kv_start, audio_lens
         logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]              # (B, V): shared by the item's beams
         cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
         cache.pos = T_p
         cache.kv_start = None if kv_start is None else kv_start.repeat_interleave(K)
+        cache.audio_lens = audio_lens                                           # per item: its beams share the cross cache
         st = ops.BeamState(prompt_ids, K, cap, eos_token_id, length_penalty)
         ops.beam_step(logits, st, length)
 
@@ -553,8 +669,10 @@ class WhisperMoP(nn.Module):
         replays it (torch.cuda.graph, one stream, static buffers).
         prompt_ids may also be a list of B 1-D tensors of different lengths (see generate): the tokens then come back as a list of B
         (num_samples, P_b + max_new_tokens) tensors, and row r draws at its own token index (ops.sample_tokens_ragged), so its draws
-        are those of a batch in which every prompt has its length."""
-        lens = self._ragged_check(mel, prompt_ids, "sample")
+        are those of a batch in which every prompt has its length.
+        mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode): an item's samples share its cross cache
+        and its length."""
+        mel_info, lens = self._batch_check(mel, prompt_ids, "sample")
         B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
         n = int(num_samples)
         if not 1 <= n <= ops.BEAM_MAX_K:
@@ -564,22 +682,23 @@ class WhisperMoP(nn.Module):
         if T_p + max_new_tokens > self.cfg.n_text_ctx:
             raise ValueError(f"sample: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
         ops._sample_params(temperature, top_k, top_p, "sample")                 # argument errors before encoding
-        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel.device)
+        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
         dev = prompt_ids.device
         length = torch.zeros(1, dtype=torch.int32, device=dev)
         cap = T_p + max_new_tokens
         H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
-        enc, _ = self.encode(mel)
+        enc, audio_lens = _enc_parts(self.encode(mel)[0])
         ck, cv = self._cross_kv(enc)
         kw = dict(dtype=ck[0].dtype, device=enc.device)
         sk = [torch.zeros(B * n, cap, H, Dh, **kw) for _ in self.decoder]
         sv = [torch.zeros(B * n, cap, H, Dh, **kw) for _ in self.decoder]
         prompt_cache = WhisperDecodeCache(ck, cv, [t[::n] for t in sk], [t[::n] for t in sv], length, cap)
-        prompt_cache.kv_start = kv_start
+        prompt_cache.kv_start, prompt_cache.audio_lens = kv_start, audio_lens
         logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]              # (B, V): shared by the item's samples
         cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
         cache.pos = T_p
         cache.kv_start = None if kv_start is None else kv_start.repeat_interleave(n)
+        cache.audio_lens = audio_lens                                           # per item: its samples share the cross cache
         i32 = dict(dtype=torch.int32, device=dev)
         r = torch.arange(B * n, **i32)
         table = r.unsqueeze(1).repeat(1, cap)                                   # constant: the prompt from row b * n, then own rows
@@ -631,7 +750,8 @@ class WhisperMoP(nn.Module):
 
     @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):
-        """per-layer time gates of the encoder, (B, L_enc, T_audio)."""
+        """per-layer time gates of the encoder, (B, L_enc, T_audio); for a list of clips (see encode) the columns >= T_b of item b
+        are unspecified."""
         _, gates = self.encode(mel)
         return gates
 

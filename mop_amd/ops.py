@@ -768,6 +768,88 @@ class _SdpaFn(torch.autograd.Function):
         return dq, dk_, dv, None, None, None, None, None, None
 
 
+def _sdpa_lens_args(q, k, v, y, lens, causal, prec, path, drop) -> L.SdpaLensArgs:
+    """the MopkSdpaLensArgs fields forward and backward share; lens: (q_lens or None, kv_lens or None), int32 (B,) device tensors"""
+    a = L.SdpaLensArgs()
+    a.base = _sdpa_args(q, k, v, y, (None, (0, 0, 0)), (None, (0, 0, 0)), causal, prec, path, drop)
+    a.q_lens, a.kv_lens = _ptr(lens[0]), _ptr(lens[1])
+    return a
+
+
+class _SdpaLensFn(torch.autograd.Function):
+    """_SdpaFn over right-padded rows (mopk_sdpa_lens_*): no mask / bias tensor, per-row lengths read by the kernels"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, q_lens, kv_lens, causal, prec, path, drop=(0.0, 0)):
+        _require_gpu(q, "SDPA")
+        lib = L.lib()
+        ctx.packed = k is None                     # packed (B,N,3,H,dk) projection, as in _SdpaFn
+        if ctx.packed:
+            q, k, v = q.contiguous().unbind(2)
+        q, k, v = _heads_view(q), _heads_view(k), _heads_view(v)
+        B, N, H, dk = q.shape
+        dev = q.device
+        lens = (q_lens, kv_lens)
+        y = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
+        a = _sdpa_lens_args(q, k, v, y, lens, causal, prec, path, drop)
+        if path == L.PATH_AUTO:       # resolve once so forward, backward and the size queries agree
+            path = L.PATH_FUSED if lib.mopk_sdpa_lens_supported(C.byref(a)) else L.PATH_GENERIC
+            a.base.path = path
+        LAST_PATH["sdpa_fwd"] = path
+        saved = _bytes(lib.mopk_sdpa_lens_saved_bytes(C.byref(a)), dev)
+        ws = _bytes(lib.mopk_sdpa_lens_workspace_bytes(C.byref(a)), dev)
+        a.base.saved, a.base.workspace = saved.data_ptr(), ws.data_ptr()
+        _launch("mopk_sdpa_lens_fwd", a, "sdpa_fwd")
+        ctx.save_for_backward(q, k, v, y, saved)
+        ctx.meta = (causal, prec, path, lens, drop)
+        return y.view(B, N, H * dk)
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = L.lib()
+        q, k, v, y, saved = ctx.saved_tensors
+        causal, prec, path, lens, drop = ctx.meta
+        B, N, H, dk = q.shape
+        Nk = k.shape[1]
+        dev = q.device
+        dy = dy.contiguous().to(q.dtype).view(B, N, H, dk)
+        a = _sdpa_lens_args(q, k, v, y, lens, causal, prec, path, drop)
+        a.base.dy = _v4(dy)
+        if ctx.packed:
+            dqkv = torch.empty(B, N, 3, H, dk, dtype=q.dtype, device=dev)
+            dq, dk_, dv = dqkv.unbind(2)
+        else:
+            dq = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
+            dk_, dv = (torch.empty(B, Nk, H, dk, dtype=q.dtype, device=dev) for _ in range(2))
+        a.base.dq, a.base.dk_, a.base.dv = _v4(dq), _v4(dk_), _v4(dv)
+        LAST_PATH["sdpa_bwd"] = path
+        ws = _bytes(lib.mopk_sdpa_lens_workspace_bytes(C.byref(a)), dev)
+        a.base.saved, a.base.workspace = saved.data_ptr(), ws.data_ptr()
+        _launch("mopk_sdpa_lens_bwd", a, "sdpa_bwd")
+        if ctx.packed:
+            return dqkv, None, None, None, None, None, None, None, None
+        return dq, dk_, dv, None, None, None, None, None, None
+
+
+def _check_lens(t, B: int, dev, what: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != B:
+        raise ValueError(f"sdpa_core: {what} must be an int32 (B,) = ({B},) tensor, got "
+                         f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.device != dev:
+        raise ValueError(f"sdpa_core: {what} is on {t.device}, q on {dev}")
+
+
+def sdpa_lens_mask(q_lens, kv_lens, B: int, N: int, Nk: int, device) -> torch.Tensor:
+    """the lengths as a (B, 1, N or 1, Nk or 1) bool mask, True = open: query i < q_lens[b] sees key j < kv_lens[b] (torch ops on the
+    device, no host sync)"""
+    m = torch.ones(B, 1, 1, 1, dtype=torch.bool, device=device)
+    if q_lens is not None:
+        m = m & (torch.arange(N, device=device).view(1, 1, N, 1) < q_lens.view(B, 1, 1, 1))
+    if kv_lens is not None:
+        m = m & (torch.arange(Nk, device=device).view(1, 1, 1, Nk) < kv_lens.view(B, 1, 1, 1))
+    return m
+
+
 def dropout_seed() -> int:
     """a fresh 63-bit seed for the in-kernel dropout mask, drawn from torch's CPU generator (so `torch.manual_seed` makes runs
     reproducible, like it does for `nn.Dropout`)"""
@@ -803,14 +885,22 @@ def dropout_keep_mask(seed: int, p: float, B: int, H: int, N: int, Nk: Optional[
 
 
 @_half_via_fp32
-def sdpa_core(q, k=None, v=None, attn_mask=None, bias=None, causal=False, dropout_p: float = 0.0, seed: Optional[int] = None):
+def sdpa_core(q, k=None, v=None, attn_mask=None, bias=None, causal=False, dropout_p: float = 0.0, seed: Optional[int] = None,
+              q_lens=None, kv_lens=None):
     """q: (B,N,H,dk), k, v: (B,Nk,H,dk) views -- Nk != N is rectangular (cross-)attention: N queries attend to Nk keys -- or packed:
     q = the (B,N,3,H,dk) output of one qkv projection, k = v = None (square; one packed gradient comes back).  Returns (B,N,H*dk).
     attn_mask: 0 = blocked; bias: additive; both broadcastable to (B,H,N,Nk).  causal needs Nk == N (ValueError otherwise).
     A row with no open key (every key blocked, or a bias of -inf at every key) is 0, as in torch's SDPA.  bias gets no gradient:
     one that requires grad under grad mode raises NotImplementedError.
     dropout_p > 0: the probabilities are multiplied by keep / (1 - p) (mask = `dropout_keep_mask(seed, B, H, N, Nk)`, seed drawn
-    when None)."""
+    when None).
+    q_lens / kv_lens: int32 (B,) tensors on q's device for a batch of right-padded rows (values are clamped into [0, N] / [0, Nk]).
+    Query i < q_lens[b] attends to keys j < kv_lens[b]; padding query rows give y = 0 and get no gradient, padding keys get
+    dk = dv = 0, and padding queries add nothing to dk, dv.  Without attn_mask / bias the kernels read the lengths themselves
+    (mopk_sdpa_lens_*: loop bounds, not a mask): rows beyond a length are never loaded, so the result does not depend on what q, k,
+    v or the incoming gradient hold there (NaN included), and full lengths are bitwise the call without lengths.  With an attn_mask
+    or bias tensor the lengths are folded into the mask (torch ops, no sync) and the call takes the mask route, which multiplies
+    padding rows by zero weights: they must then be finite.  No host synchronisation either way."""
     _refuse_bias_grad(bias, "sdpa_core: bias")
     if k is not None:
         if k.dim() != 4 or v is None or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2:] != q.shape[2:]:
@@ -820,12 +910,24 @@ def sdpa_core(q, k=None, v=None, attn_mask=None, bias=None, causal=False, dropou
             raise ValueError("sdpa_core: k, v have no keys (Nk = 0)")
         if causal and k.shape[1] != q.shape[1]:
             raise ValueError(f"sdpa_core: causal attention needs as many keys as queries (N = {q.shape[1]}, Nk = {k.shape[1]})")
+    if q_lens is not None or kv_lens is not None:
+        for t, what in ((q_lens, "q_lens"), (kv_lens, "kv_lens")):
+            if t is not None:
+                _check_lens(t, q.shape[0], q.device, what)
     if q.shape[0] == 0:
         if k is None:
             return _empty_batch(q, 0, q.shape[1], q.shape[-2] * q.shape[-1])
         return _empty_batch(q, 0, q.shape[1], q.shape[2] * q.shape[3]) + (k.sum() + v.sum()) * 0
     drop = _drop(dropout_p, seed)
-    return _SdpaFn.apply(q, k, v, attn_mask, bias, causal, _prec_for(q.dtype), _PATH, drop)
+    if q_lens is None and kv_lens is None:
+        return _SdpaFn.apply(q, k, v, attn_mask, bias, causal, _prec_for(q.dtype), _PATH, drop)
+    if attn_mask is None and bias is None:
+        return _SdpaLensFn.apply(q, k, v, q_lens, kv_lens, causal, _prec_for(q.dtype), _PATH, drop)
+    B, N, Nk = q.shape[0], q.shape[1], (q.shape[1] if k is None else k.shape[1])
+    m = sdpa_lens_mask(q_lens, kv_lens, B, N, Nk, q.device)
+    if attn_mask is not None:
+        m = m & (attn_mask.to(q.device) != 0)
+    return _SdpaFn.apply(q, k, v, m, bias, causal, _prec_for(q.dtype), _PATH, drop)
 
 
 _ANCHOR_MODES = {"fixed": 0, "argmax_row_sum": 1}          # any other string -> row 0 (reference :141-145)
@@ -1744,6 +1846,82 @@ def decode_attention_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
         a.base.y, a.base.workspace = _v4(y), ws.data_ptr()
         LAST_PATH["decode_attn_ragged"] = L.PATH_FUSED
         _launch("mopk_decode_attn_ragged_fwd", a, "decode_attn_ragged")
+        return y.view(B, Tq, H * dk)
+
+
+# ---- decode attention with a per-row key count (mopk_decode_attn_lens_*; WhisperMoP cross-attention over ragged audio) ----
+def decode_attention_lens_torch(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_lens: torch.Tensor,
+                                nk: Optional[int] = None) -> torch.Tensor:
+    """the reference composition of `decode_attention_lens`: non-causal decode_attention_torch with the keys j >= kv_lens[b] of row b
+    masked out; no host sync"""
+    B, Tq, H, dk = q.shape
+    cap = k_cache.shape[1]
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    s = torch.einsum("bihd,bjhd->bhij", q.to(ct), k_cache.to(ct)) * dk ** -0.5
+    j = torch.arange(cap, device=q.device)
+    L_ = kv_lens.reshape(B, 1).to(torch.long).clamp(0, cap if nk is None else int(nk))
+    open_ = j.unsqueeze(0) < L_                                             # (B, cap)
+    s = s.masked_fill(~open_.view(B, 1, 1, cap), float("-inf"))
+    p = torch.softmax(s, dim=-1).nan_to_num(0.0)                            # a row that sees no key gets y = 0, as the kernels
+    v = v_cache.to(ct).masked_fill(~open_.view(B, cap, 1, 1), 0.0)          # rows past kv_lens[b] may hold anything
+    y = torch.einsum("bhij,bjhd->bihd", p, v)
+    return y.to(q.dtype).reshape(B, Tq, H * dk)
+
+
+def _dal_args(q, k_cache, v_cache, kv_lens, nk) -> L.DecodeAttnLensArgs:
+    a = L.DecodeAttnLensArgs()
+    a.base = _da_args(q, k_cache, v_cache, None, nk, False)
+    a.kv_lens = kv_lens.data_ptr()
+    return a
+
+
+def decode_attention_lens_supported(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_lens: torch.Tensor,
+                                    nk: Optional[int] = None) -> bool:
+    """True if mopk_decode_attn_lens_* take this call: what decode_attention_supported asks, and a contiguous CUDA int32 kv_lens of
+    B elements"""
+    if not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.numel() != q.shape[0] or not kv_lens.is_contiguous():
+        return False
+    if not decode_attention_supported(q, k_cache, v_cache, None, nk, False):
+        return False
+    return bool(L.lib().mopk_decode_attn_lens_supported(C.byref(_dal_args(q, k_cache, v_cache, kv_lens, nk))))
+
+
+def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_lens: torch.Tensor,
+                          nk: Optional[int] = None) -> torch.Tensor:
+    """non-causal `decode_attention` in which row b of q sees only the keys j < kv_lens[b]: the cross-attention of a decode step over
+    audio of different lengths right-padded in one cache.  Inference only (no autograd).
+
+    q: (B, Tq, H, dk); k_cache, v_cache: (B, cap, H, dk) views; kv_lens: int32 (B,) device tensor, clamped into [0, nk] (nk: host
+    int, else cap).  A row is a row of q: beams or samples of one item that share its cache go in as one row of beams * T queries,
+    with one length.  Key rows >= kv_lens[b] are never read; a row with kv_lens[b] = 0 gets y = 0; kv_lens = nk everywhere is
+    bitwise decode_attention(q, k_cache, v_cache, nk=nk).  Returns (B, Tq, H * dk) in q's dtype.  Runs the split-KV HIP kernels when
+    decode_attention_lens_supported() accepts the call, else decode_attention_lens_torch(); LAST_PATH["decode_attn_lens"] records
+    which.  No host synchronisation."""
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError(f"decode_attention_lens: q must be (B, Tq, H, dk) and k_cache, v_cache (B, cap, H, dk) of one shape; got "
+                         f"q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)}")
+    if k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
+        raise ValueError(f"decode_attention_lens: k_cache / v_cache {tuple(k_cache.shape)} do not match q's B, H, dk "
+                         f"{tuple(q.shape)}")
+    if (not isinstance(kv_lens, torch.Tensor) or kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0]
+            or kv_lens.dtype.is_floating_point or kv_lens.dtype == torch.bool):
+        raise ValueError(f"decode_attention_lens: kv_lens must be an integer (B,) = ({q.shape[0]},) tensor, got "
+                         f"{(tuple(kv_lens.shape), kv_lens.dtype) if isinstance(kv_lens, torch.Tensor) else type(kv_lens).__name__}")
+    if nk is not None and not 0 < int(nk) <= k_cache.shape[1]:
+        raise ValueError(f"decode_attention_lens: nk = {nk} outside [1, cap = {k_cache.shape[1]}]")
+    _require_gpu(q, "decode_attention_lens")
+    with torch.no_grad():
+        if not decode_attention_lens_supported(q, k_cache, v_cache, kv_lens, nk):
+            LAST_PATH["decode_attn_lens"] = L.PATH_GENERIC
+            return decode_attention_lens_torch(q, k_cache, v_cache, kv_lens, nk)
+        lib = L.lib()
+        B, Tq, H, dk = q.shape
+        a = _dal_args(q, k_cache, v_cache, kv_lens, nk)
+        y = torch.empty(B, Tq, H, dk, dtype=q.dtype, device=q.device)
+        ws = _bytes(lib.mopk_decode_attn_lens_workspace_bytes(C.byref(a)), q.device)
+        a.base.y, a.base.workspace = _v4(y), ws.data_ptr()
+        LAST_PATH["decode_attn_lens"] = L.PATH_FUSED
+        _launch("mopk_decode_attn_lens_fwd", a, "decode_attn_lens")
         return y.view(B, Tq, H * dk)
 
 
