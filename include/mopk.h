@@ -345,6 +345,36 @@ int mopk_crossview_bwd(const MopkCrossViewArgs *a, void *stream);
  * Reads only B, V, H, dk and the four *_part pointers of `a`. */
 int mopk_edgewise_reduce_parts(const MopkEdgewiseArgs *a, float *dsqk, float *dvs0, float *dvsL, float *dlogit, void *stream);
 
+/* Small-parameter prologue / epilogue of a share_qkv EdgewiseMSA layer with the low-rank head (added without a version bump: new
+ * exports only).  The layer's small parameters -- q_scale, k_scale, v_scale (V,H,1,dk) :374-378, the head's Wr, br, Wc, bc and
+ * chain_value_logit :451 -- are stored in `io_dtype` (one dtype for all of them, contiguous); the core reads float32 copies.
+ *   _params_fwd: ONE launch writes `pack`, n_pack = V H dk + 2 H dk + 2 (4r C) + 2 (4r) + 1 floats laid out as
+ *     sqk (V,H,dk) | vs0 (H,dk) | vsL (H,dk) | Wr (4r,C) | br | Wc | bc | logit, with sqk = rnd(rnd(q_scale k_scale) inv),
+ *     inv = (float)(1 / sqrt(dk)), rnd = round-to-nearest-even to io_dtype, every product a separate float32 multiply: the values
+ *     `(q_scale * k_scale) * inv` has when evaluated tensor by tensor in io_dtype.  vs0 / vsL = v_scale[0] / v_scale[V-1].
+ *   _params_bwd: ONE launch after mopk_edgewise_lowrank_bwd, in place of mopk_edgewise_reduce_parts.  Sums the per-batch partials
+ *     in that function's order, then finishes the chain rule with the roundings a tensor-by-tensor evaluation in io_dtype has:
+ *     g = rnd(dsqk), g2 = rnd(g inv), dq_scale = rnd(g2 k_scale), dk_scale = rnd(g2 q_scale); dv_scale[0] = rnd(dvs0),
+ *     dv_scale[V-1] = rnd(dvsL), rows between zero; gWr .. gbc = rnd(dWr .. dbc) (the float32 values _bwd left), glogit = rnd(dlogit).
+ *     Every output is a separate contiguous array of the parameter's shape.
+ * Neither allocates nor synchronises (safe under stream capture). */
+typedef struct MopkEdgewiseParamArgs {
+    int32_t B, V, H, dk, r;
+    int32_t C;               /* input channels of the head: 2V + 2 */
+    int32_t io_dtype;        /* MopkDtype of the parameters and of their gradients */
+    const void *q_scale, *k_scale, *v_scale;       /* (V,H,1,dk) */
+    const void *Wr, *br, *Wc, *bc;                 /* (4r,C), (4r), (4r,C), (4r) */
+    const void *chain_logit;                       /* 1 */
+    float *pack;                                   /* _fwd out: n_pack floats */
+    /* ---- _params_bwd only ---- */
+    const float *dsqk_part, *dvs0_part, *dvsL_part, *dlogit_part;   /* as in MopkEdgewiseArgs: (B,V,H,dk), (B,H,dk) x 2, (B,H) */
+    const float *dWr, *dbr, *dWc, *dbc;            /* float32, fully reduced (MopkEdgewiseArgs.dWr ..) */
+    void *gq_scale, *gk_scale, *gv_scale;          /* out, io_dtype: (V,H,1,dk) */
+    void *gWr, *gbr, *gWc, *gbc, *glogit;          /* out, io_dtype */
+} MopkEdgewiseParamArgs;
+int mopk_edgewise_params_fwd(const MopkEdgewiseParamArgs *p, void *stream);
+int mopk_edgewise_params_bwd(const MopkEdgewiseParamArgs *p, void *stream);
+
 /* -------------------------------------------------------------------------- */
 /* LayerNorm prologue / residual epilogue of the attention path.
  *

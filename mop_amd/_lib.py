@@ -56,6 +56,20 @@ class EdgewiseArgs(C.Structure):
     ]
 
 
+class EdgewiseParamArgs(C.Structure):
+    """MopkEdgewiseParamArgs: the small parameters of a share_qkv EdgewiseMSA layer on their way to the core and their gradients back."""
+    _fields_ = [
+        ("B", C.c_int32), ("V", C.c_int32), ("H", C.c_int32), ("dk", C.c_int32), ("r", C.c_int32), ("C", C.c_int32),
+        ("io_dtype", C.c_int32),
+        ("q_scale", _fp), ("k_scale", _fp), ("v_scale", _fp), ("Wr", _fp), ("br", _fp), ("Wc", _fp), ("bc", _fp),
+        ("chain_logit", _fp), ("pack", _fp),
+        ("dsqk_part", _fp), ("dvs0_part", _fp), ("dvsL_part", _fp), ("dlogit_part", _fp),
+        ("dWr", _fp), ("dbr", _fp), ("dWc", _fp), ("dbc", _fp),
+        ("gq_scale", _fp), ("gk_scale", _fp), ("gv_scale", _fp), ("gWr", _fp), ("gbr", _fp), ("gWc", _fp), ("gbc", _fp),
+        ("glogit", _fp),
+    ]
+
+
 class DualPathArgs(C.Structure):
     _fields_ = [
         ("B", C.c_int32), ("H", C.c_int32), ("N", C.c_int32), ("dk", C.c_int32), ("hops", C.c_int32),
@@ -223,6 +237,8 @@ SYMBOLS = {
     "mopk_edgewise_lowrank_fwd": (C.c_int, [C.POINTER(EdgewiseArgs), C.c_void_p]),
     "mopk_edgewise_lowrank_bwd": (C.c_int, [C.POINTER(EdgewiseArgs), C.c_void_p]),
     "mopk_edgewise_reduce_parts": (C.c_int, [C.POINTER(EdgewiseArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mopk_edgewise_params_fwd": (C.c_int, [C.POINTER(EdgewiseParamArgs), C.c_void_p]),
+    "mopk_edgewise_params_bwd": (C.c_int, [C.POINTER(EdgewiseParamArgs), C.c_void_p]),
     "mopk_edgewise_fwd": (C.c_int, [C.POINTER(EdgewiseArgs), C.c_void_p]),
     "mopk_edgewise_bwd": (C.c_int, [C.POINTER(EdgewiseArgs), C.c_void_p]),
     "mopk_dualpath_saved_bytes": (C.c_size_t, [C.POINTER(DualPathArgs)]),

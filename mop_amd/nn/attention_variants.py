@@ -219,6 +219,16 @@ class EdgewiseMSA(nn.Module):
             vs0, vsL = self.v_scale[0, :, 0], self.v_scale[min(V - 1, n_s - 1), :, 0]     # :556
         elif self.share_qkv:
             qkv = self.qkv(x).view(B, N, 1, 3, H, dk)
+            # plain low-rank layer: the small parameters go to the core as they are stored -- one kernel builds sqk, vs0, vsL and the
+            # head's float32 copies, one kernel after the core's backward turns its partial sums into the parameters' gradients
+            # (ops.edgewise_lowrank_core_shared: same bits as the expressions below, about twenty small launches fewer per step)
+            head = (eh.row_proj.weight.squeeze(-1), eh.row_proj.bias, eh.col_proj.weight.squeeze(-1), eh.col_proj.bias) if not dense else ()
+            if not dense and attn_mask is None and not self.use_lens_bank and ops.edgewise_shared_params_supported(
+                    qkv, (self.q_scale, self.k_scale, self.v_scale, *head, self.chain_value_logit)):
+                y = ops.edgewise_lowrank_core_shared(qkv, self.q_scale, self.k_scale, self.v_scale, *head, self.chain_value_logit,
+                                                     float(self.beta_not), V,
+                                                     dropout_p=float(self.attn_drop.p) if self.training else 0.0)      # :552
+                return self._project(y, residual)
             sqk = (self.q_scale * self.k_scale).squeeze(2) * inv          # (V,H,dk)
             vs0, vsL = self.v_scale[0, :, 0], self.v_scale[V - 1, :, 0]   # (H,dk)
         else:

@@ -196,6 +196,88 @@ def set_save_chain_state(on: bool) -> None:
     _SAVE_CHAIN_STATE = bool(on)
 
 
+def _ew_lowrank_fwd(ctx, qkv, f, beta_not, V, prec, path, want_bwd, drop, lens_w=None, lens_dil=()):
+    """the low-rank core's forward launch, shared by _EdgewiseLowrankFn and _EdgewiseSharedFn.  f: the float32 small tensors by name
+    (sqk, vs0, vsL, Wr, br, Wc, bc, logit).  Returns y (B,N,H,dk) and the tensors the backward launch needs (qkv, saved, *f, *extras);
+    sets ctx.meta / ctx.lens_*."""
+    _require_gpu(qkv, "EdgewiseMSA")
+    lib = L.lib()
+    B, N, Vq, _, H, dk = qkv.shape
+    dev = qkv.device
+    n_extra = 0 if lens_w is None else int(lens_w.shape[0] * lens_w.shape[1])
+    r = f["Wr"].shape[0] // 4
+    y = torch.empty(B, N, H, dk, dtype=qkv.dtype, device=dev)
+    a = _ew_args(qkv, y, V, r, prec, path, beta_not, drop, (f["sqk"], f["vs0"], f["vsL"], f["logit"]),
+                 (f["Wr"], f["br"], f["Wc"], f["bc"]))
+    extras = ()
+    ctx.lens_dil, ctx.lens_dtype = tuple(lens_dil), (None if lens_w is None else lens_w.dtype)
+    if n_extra:
+        lens_w = _f32c(lens_w)
+        row_x, col_x = lens_means_hip(qkv, f["sqk"], lens_w, lens_dil)
+        extras = (row_x, col_x, lens_w)
+        ext = _extra_ext(n_extra, row_x, col_x)
+        a.ext = C.pointer(ext)
+        if path == L.PATH_GENERIC or not lib.mopk_edgewise_fused_supported(C.byref(a)):
+            raise NotImplementedError("extra feature channels are an input of the fused Edgewise kernels only")
+        path = L.PATH_FUSED
+    if path == L.PATH_AUTO:   # AUTO: fused gfx950 kernels when they cover the shape, generic otherwise
+        path = L.PATH_FUSED if lib.mopk_edgewise_fused_supported(C.byref(a)) else L.PATH_GENERIC
+    a.path = path
+    # training forward of the fused path also exports the chain state its backward would otherwise recompute
+    a.save_for_backward = int(bool(want_bwd) and path == L.PATH_FUSED and _SAVE_CHAIN_STATE)
+    LAST_PATH["edgewise_fwd"] = path
+    saved = _bytes(lib.mopk_edgewise_saved_bytes(C.byref(a)), dev)
+    ws = _bytes(256 if path == L.PATH_FUSED else lib.mopk_edgewise_workspace_bytes(C.byref(a)), dev)
+    a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
+    if _KEEP_WS:
+        LAST_PATH["_fwd_ws"] = ws  # diagnostics only (stamp builds read it back): pins the buffer until the next call
+    _launch("mopk_edgewise_lowrank_fwd", a, "edgewise_fwd")
+    ctx.meta = (beta_not, V, prec, path, r, int(a.save_for_backward), drop)
+    return y, (qkv, saved, *f.values(), *extras)
+
+
+def _ew_lowrank_bwd(ctx, dy, core_saved, head_grads):
+    """the low-rank core's backward launch on what _ew_lowrank_fwd returned.  head_grads: float32 (dWr, dbr, dWc, dbc) to write.  Returns the argument struct (its *_part pointers
+    are what the batch reduction reads), dqkv, the gradients of the extra channels (or None) and the tensors that own the
+    partial sums (keep them alive until the reduction is launched)."""
+    lib = L.lib()
+    qkv, saved, sqk, vs0, vsL, Wr, br, Wc, bc, logit, *extras = core_saved
+    beta_not, V, prec, path, r, sfb, drop = ctx.meta
+    B, N, Vq, _, H, dk = qkv.shape
+    dev = qkv.device
+    dy = dy.contiguous()
+    if dy.dtype != qkv.dtype:
+        dy = dy.to(qkv.dtype)
+    # a.y = dy: unused by bwd, must be non-null
+    a = _ew_args(qkv, dy, V, r, prec, path, beta_not, drop, (sqk, vs0, vsL, logit), (Wr, br, Wc, bc))
+    a.save_for_backward = sfb
+    a.dy = L.View4(dy.data_ptr(), N * H * dk, dk, H * dk)
+    # unshared: only v of view 0 and V-1 receive gradient -> zero-fill the rest
+    dqkv = (torch.empty_like(qkv) if Vq == 1 else torch.zeros_like(qkv))
+    _ew_views(a, dqkv, "d")
+    n_extra = extras[0].shape[2] if extras else 0
+    d_extras = None
+    if n_extra:
+        d_extras = (torch.empty_like(extras[0]), torch.empty_like(extras[1]))
+        ext = _extra_ext(n_extra, extras[0], extras[1])
+        ext.d_row_extra, ext.d_col_extra = d_extras[0].data_ptr(), d_extras[1].data_ptr()
+        a.ext = C.pointer(ext)
+    # per-batch partials of the small gradients
+    n_sqk, n_vs = V * H * dk, H * dk
+    parts = torch.empty(B * (n_sqk + 2 * n_vs + H), dtype=torch.float32, device=dev)
+    dsqk_p, dvs0_p, dvsL_p, dlg_p = torch.split(parts, [B * n_sqk, B * n_vs, B * n_vs, B * H])
+    a.dsqk_part, a.dvs0_part, a.dvsL_part = dsqk_p.data_ptr(), dvs0_p.data_ptr(), dvsL_p.data_ptr()
+    a.dWr, a.dbr, a.dWc, a.dbc = map(torch.Tensor.data_ptr, head_grads)
+    a.dlogit_part = dlg_p.data_ptr()
+    LAST_PATH["edgewise_bwd"] = path
+    ws = _bytes(lib.mopk_edgewise_workspace_bytes(C.byref(a)), dev)
+    if _KEEP_WS:
+        LAST_PATH["_bwd_ws"] = ws  # diagnostics only (stamp builds read it back): pins the buffer until the next call
+    a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
+    _launch("mopk_edgewise_lowrank_bwd", a, "edgewise_bwd")
+    return a, dqkv, d_extras, parts
+
+
 class _EdgewiseLowrankFn(torch.autograd.Function):
     """y = EdgewiseMSA core(qkv, ...) ; reference attention_variants.py:500-562."""
 
@@ -205,87 +287,29 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
         """lens_w (L,V,3,3) + lens_dil: the S lens bank.  Its planes reach the head as E = L V extra feature channels given by their
         row / column means (Wr / Wc then have 2V + 2 + E input channels): fused path only (MopkEdgewiseExt.n_extra)."""
         _require_gpu(qkv, "EdgewiseMSA")
-        lib = L.lib()
         B, N, Vq, _, H, dk = qkv.shape
-        qkv = qkv.contiguous()
-        dev = qkv.device
-        n_extra = 0 if lens_w is None else int(lens_w.shape[0] * lens_w.shape[1])
         f = dict(zip(("sqk", "vs0", "vsL", "Wr", "br", "Wc", "bc", "logit"),
                      _f32_pack([sqk, vs0, vsL, Wr, br, Wc, bc, logit.reshape(1)])))
         ctx.small_dtype = sqk.dtype if len({t.dtype for t in (sqk, vs0, vsL, Wr, br, Wc, bc, logit)}) == 1 else None
-        r = f["Wr"].shape[0] // 4
-        y = torch.empty(B, N, H, dk, dtype=qkv.dtype, device=dev)
-        a = _ew_args(qkv, y, V, r, prec, path, beta_not, drop, (f["sqk"], f["vs0"], f["vsL"], f["logit"]),
-                     (f["Wr"], f["br"], f["Wc"], f["bc"]))
-        extras = ()
-        ctx.lens_dil, ctx.lens_dtype = tuple(lens_dil), (None if lens_w is None else lens_w.dtype)
-        if n_extra:
-            lens_w = _f32c(lens_w)
-            row_x, col_x = lens_means_hip(qkv, f["sqk"], lens_w, lens_dil)
-            extras = (row_x, col_x, lens_w)
-            ext = _extra_ext(n_extra, row_x, col_x)
-            a.ext = C.pointer(ext)
-            if path == L.PATH_GENERIC or not lib.mopk_edgewise_fused_supported(C.byref(a)):
-                raise NotImplementedError("extra feature channels are an input of the fused Edgewise kernels only")
-            path = L.PATH_FUSED
-        if path == L.PATH_AUTO:   # AUTO: fused gfx950 kernels when they cover the shape, generic otherwise
-            path = L.PATH_FUSED if lib.mopk_edgewise_fused_supported(C.byref(a)) else L.PATH_GENERIC
-        a.path = path
-        # training forward of the fused path also exports the chain state its backward would otherwise recompute
-        a.save_for_backward = int(bool(want_bwd) and path == L.PATH_FUSED and _SAVE_CHAIN_STATE)
-        LAST_PATH["edgewise_fwd"] = path
-        saved = _bytes(lib.mopk_edgewise_saved_bytes(C.byref(a)), dev)
-        ws = _bytes(256 if path == L.PATH_FUSED else lib.mopk_edgewise_workspace_bytes(C.byref(a)), dev)
-        a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        if _KEEP_WS:
-            LAST_PATH["_fwd_ws"] = ws  # diagnostics only (stamp builds read it back): pins the buffer until the next call
-        _launch("mopk_edgewise_lowrank_fwd", a, "edgewise_fwd")
-        ctx.save_for_backward(qkv, saved, *f.values(), *extras)
-        ctx.meta = (beta_not, V, prec, path, r, int(a.save_for_backward), drop)
+        y, core_saved = _ew_lowrank_fwd(ctx, qkv.contiguous(), f, beta_not, V, prec, path, want_bwd, drop, lens_w, lens_dil)
+        ctx.save_for_backward(*core_saved)
         return y.view(B, N, H * dk)
 
     @staticmethod
     def backward(ctx, dy):
         lib = L.lib()
-        qkv, saved, sqk, vs0, vsL, Wr, br, Wc, bc, logit, *extras = ctx.saved_tensors
-        beta_not, V, prec, path, r, sfb, drop = ctx.meta
+        qkv, _, sqk, *_rest = ctx.saved_tensors
+        extras = ctx.saved_tensors[10:]
+        V, r = ctx.meta[1], ctx.meta[4]
         B, N, Vq, _, H, dk = qkv.shape
-        dev = qkv.device
-        dy = dy.contiguous()
-        if dy.dtype != qkv.dtype:
-            dy = dy.to(qkv.dtype)
-        # a.y = dy: unused by bwd, must be non-null
-        a = _ew_args(qkv, dy, V, r, prec, path, beta_not, drop, (sqk, vs0, vsL, logit), (Wr, br, Wc, bc))
-        a.save_for_backward = sfb
-        a.dy = L.View4(dy.data_ptr(), N * H * dk, dk, H * dk)
-        # unshared: only v of view 0 and V-1 receive gradient -> zero-fill the rest
-        dqkv = (torch.empty_like(qkv) if Vq == 1 else torch.zeros_like(qkv))
-        _ew_views(a, dqkv, "d")
-        f32 = dict(dtype=torch.float32, device=dev)
         n_extra = extras[0].shape[2] if extras else 0
         C_ = 2 * V + 2 + n_extra
-        d_extras = None
-        if n_extra:
-            d_extras = (torch.empty_like(extras[0]), torch.empty_like(extras[1]))
-            ext = _extra_ext(n_extra, extras[0], extras[1])
-            ext.d_row_extra, ext.d_col_extra = d_extras[0].data_ptr(), d_extras[1].data_ptr()
-            a.ext = C.pointer(ext)
-        # per-batch partials of the small gradients, and ONE buffer for their final values (reduced by the library in a single
-        # launch, cast to the parameters' dtype in a single kernel, handed to autograd as views)
+        # ONE buffer for the final values of the small gradients (reduced by the library in a single launch, cast to the
+        # parameters' dtype in a single kernel, handed to autograd as views)
         n_sqk, n_vs, n_w, n_b = V * H * dk, H * dk, 4 * r * C_, 4 * r
-        parts = torch.empty(B * (n_sqk + 2 * n_vs + H), **f32)
-        dsqk_p, dvs0_p, dvsL_p, dlg_p = torch.split(parts, [B * n_sqk, B * n_vs, B * n_vs, B * H])
-        small = torch.empty(n_sqk + 2 * n_vs + 2 * n_w + 2 * n_b + 1, **f32)
+        small = torch.empty(n_sqk + 2 * n_vs + 2 * n_w + 2 * n_b + 1, dtype=torch.float32, device=qkv.device)
         dsqk, dvs0, dvsL, dWr, dbr, dWc, dbc, dlg = torch.split(small, [n_sqk, n_vs, n_vs, n_w, n_b, n_w, n_b, 1])
-        a.dsqk_part, a.dvs0_part, a.dvsL_part = dsqk_p.data_ptr(), dvs0_p.data_ptr(), dvsL_p.data_ptr()
-        a.dWr, a.dbr, a.dWc, a.dbc = dWr.data_ptr(), dbr.data_ptr(), dWc.data_ptr(), dbc.data_ptr()
-        a.dlogit_part = dlg_p.data_ptr()
-        LAST_PATH["edgewise_bwd"] = path
-        ws = _bytes(lib.mopk_edgewise_workspace_bytes(C.byref(a)), dev)
-        if _KEEP_WS:
-            LAST_PATH["_bwd_ws"] = ws  # diagnostics only (stamp builds read it back): pins the buffer until the next call
-        a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        _launch("mopk_edgewise_lowrank_bwd", a, "edgewise_bwd")
+        a, dqkv, d_extras, parts = _ew_lowrank_bwd(ctx, dy, ctx.saved_tensors, (dWr, dbr, dWc, dbc))
         L.check(lib.mopk_edgewise_reduce_parts(C.byref(a), dsqk.data_ptr(), dvs0.data_ptr(), dvsL.data_ptr(), dlg.data_ptr(),
                                                _stream()), "mopk_edgewise_reduce_parts")
         dlens = None
@@ -298,6 +322,56 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
             dsqk, dvs0, dvsL, dWr, dbr, dWc, dbc, dlg = torch.split(small, [n_sqk, n_vs, n_vs, n_w, n_b, n_w, n_b, 1])
         return (dqkv, dsqk.view(V, H, dk), dvs0.view(H, dk), dvsL.view(H, dk), dWr.view(4 * r, C_), dbr, dWc.view(4 * r, C_), dbc,
                 dlg.reshape(()), None, None, None, None, None, None, dlens, None)
+
+
+def _ew_param_args(B, q_scale, k_scale, v_scale, Wr, br, Wc, bc, logit) -> L.EdgewiseParamArgs:
+    """the MopkEdgewiseParamArgs fields mopk_edgewise_params_fwd and _bwd share: shapes and the parameters themselves"""
+    V, H, _, dk = q_scale.shape
+    p = L.EdgewiseParamArgs()
+    p.B, p.V, p.H, p.dk, p.r, p.C, p.io_dtype = B, V, H, dk, Wr.shape[0] // 4, Wr.shape[1], _io_dtype(q_scale)
+    p.q_scale, p.k_scale, p.v_scale, p.Wr, p.br, p.Wc, p.bc, p.chain_logit = map(
+        torch.Tensor.data_ptr, (q_scale, k_scale, v_scale, Wr, br, Wc, bc, logit))
+    return p
+
+
+class _EdgewiseSharedFn(torch.autograd.Function):
+    """_EdgewiseLowrankFn for a share_qkv layer, taking the layer's small parameters as they are stored: q_scale, k_scale, v_scale
+    (V,H,1,dk), the head's Wr, br, Wc, bc and chain_logit, all of one dtype (float32 / bfloat16).  The float32 copies the core
+    reads (sqk = q_scale k_scale / sqrt(dk), v_scale[0], v_scale[V-1], ...) come from ONE launch, mopk_edgewise_params_fwd, and the
+    parameters' gradients from ONE launch after the core's backward, mopk_edgewise_params_bwd (batch reduction + chain rule +
+    cast, each gradient a tensor of its own) -- both bit-identical to the tensor expressions of EdgewiseMSA.forward feeding
+    _EdgewiseLowrankFn, which cost about twenty small launches per step."""
+
+    @staticmethod
+    def forward(ctx, qkv, q_scale, k_scale, v_scale, Wr, br, Wc, bc, logit, beta_not, V, prec, path, want_bwd, drop=(0.0, 0)):
+        _require_gpu(qkv, "EdgewiseMSA")
+        B, N, Vq, _, H, dk = qkv.shape
+        params = tuple(t.contiguous() for t in (q_scale, k_scale, v_scale, Wr, br, Wc, bc, logit))
+        sizes = [V * H * dk, H * dk, H * dk, Wr.numel(), br.numel(), Wc.numel(), bc.numel(), 1]
+        pack = torch.empty(sum(sizes), dtype=torch.float32, device=qkv.device)
+        p = _ew_param_args(B, *params)
+        p.pack = pack.data_ptr()
+        _launch("mopk_edgewise_params_fwd", p)
+        shapes = ((V, H, dk), (H, dk), (H, dk), Wr.shape, br.shape, Wc.shape, bc.shape, (1,))
+        f = {k: t.view(sh) for k, t, sh in zip(("sqk", "vs0", "vsL", "Wr", "br", "Wc", "bc", "logit"), torch.split(pack, sizes), shapes)}
+        y, core_saved = _ew_lowrank_fwd(ctx, qkv.contiguous(), f, beta_not, V, prec, path, want_bwd, drop)
+        ctx.save_for_backward(*core_saved, *params)
+        return y.view(B, N, H * dk)
+
+    @staticmethod
+    def backward(ctx, dy):
+        core_saved, params = ctx.saved_tensors[:10], ctx.saved_tensors[10:]
+        qkv = core_saved[0]
+        n_w, n_b = params[3].numel(), params[4].numel()
+        head = torch.empty(2 * n_w + 2 * n_b, dtype=torch.float32, device=qkv.device)
+        a, dqkv, _, parts = _ew_lowrank_bwd(ctx, dy, core_saved, torch.split(head, [n_w, n_b, n_w, n_b]))
+        grads = tuple(torch.empty_like(t) for t in params)     # one tensor per parameter: autograd keeps them without a copy
+        p = _ew_param_args(qkv.shape[0], *params)
+        p.dsqk_part, p.dvs0_part, p.dvsL_part, p.dlogit_part = a.dsqk_part, a.dvs0_part, a.dvsL_part, a.dlogit_part
+        p.dWr, p.dbr, p.dWc, p.dbc = a.dWr, a.dbr, a.dWc, a.dbc
+        p.gq_scale, p.gk_scale, p.gv_scale, p.gWr, p.gbr, p.gWc, p.gbc, p.glogit = map(torch.Tensor.data_ptr, grads)
+        _launch("mopk_edgewise_params_bwd", p)
+        return (dqkv, *grads, None, None, None, None, None, None)
 
 
 class EdgewiseVariant:
@@ -653,6 +727,34 @@ def edgewise_lowrank_core(qkv, sqk, vs0, vsL, Wr, br, Wc, bc, chain_logit, beta_
         t is not None and t.requires_grad for t in (qkv, sqk, vs0, vsL, Wr, br, Wc, bc, chain_logit, lens_w))
     return _EdgewiseLowrankFn.apply(qkv, sqk, vs0, vsL, Wr, br, Wc, bc, chain_logit, beta_not,
                                     n_views, prec, _PATH if path is None else path, want_bwd, drop, lens_w, tuple(lens_dilations))
+
+
+def edgewise_shared_params_supported(qkv, params) -> bool:
+    """True when `edgewise_lowrank_core_shared` takes this call: GPU tensors, float32 / bfloat16 qkv of the share_qkv layout
+    (B,N,1,3,H,dk) with B > 0, and the small parameters all of one dtype that is float32 or bfloat16"""
+    dtypes = {t.dtype for t in params}
+    return (qkv.is_cuda and qkv.dim() == 6 and qkv.shape[2] == 1 and qkv.shape[0] > 0 and qkv.dtype in (torch.float32, torch.bfloat16)
+            and len(dtypes) == 1 and next(iter(dtypes)) in (torch.float32, torch.bfloat16) and all(t.is_cuda for t in params))
+
+
+def edgewise_lowrank_core_shared(qkv, q_scale, k_scale, v_scale, Wr, br, Wc, bc, chain_logit, beta_not: float,
+                                 n_views: int, precision: Optional[int] = None, path: Optional[int] = None,
+                                 dropout_p: float = 0.0, seed: Optional[int] = None):
+    """`edgewise_lowrank_core` of a share_qkv layer, fed with the layer's parameters as they are stored instead of the tensors
+    derived from them: qkv (B,N,1,3,H,dk); q_scale, k_scale, v_scale (V,H,1,dk) with V = n_views.  Computes what
+    `edgewise_lowrank_core(qkv, (q_scale * k_scale).squeeze(2) / sqrt(dk), v_scale[0, :, 0], v_scale[V - 1, :, 0], ...)` computes,
+    bit for bit in the output and in every gradient, with one small kernel before the core and one after its backward in place of
+    the tensor expressions (see _EdgewiseSharedFn).  Callers check `edgewise_shared_params_supported` first."""
+    params = (q_scale, k_scale, v_scale, Wr, br, Wc, bc, chain_logit)
+    if not edgewise_shared_params_supported(qkv, params):
+        raise NotImplementedError("edgewise_lowrank_core_shared: needs a GPU share_qkv call whose small parameters have one dtype "
+                                  "(float32 / bfloat16); use edgewise_lowrank_core")
+    if tuple(q_scale.shape) != (n_views, qkv.shape[4], 1, qkv.shape[5]) or k_scale.shape != q_scale.shape or v_scale.shape != q_scale.shape:
+        raise ValueError(f"q_scale / k_scale / v_scale must be (n_views, H, 1, dk), got {tuple(q_scale.shape)}")
+    drop = _drop(dropout_p, seed)
+    prec = _prec_for(qkv.dtype) if precision is None else precision
+    want_bwd = torch.is_grad_enabled() and any(t.requires_grad for t in (qkv, *params))
+    return _EdgewiseSharedFn.apply(qkv, *params, beta_not, n_views, prec, _PATH if path is None else path, want_bwd, drop)
 
 
 # --------------------------------------------------------------------------------------
