@@ -437,7 +437,6 @@ class WhisperMoP(nn.Module):
         H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
         idx = cache.length.to(torch.long) + torch.arange(T, device=ids.device)        # positions of the new tokens
         ks = cache.kv_start                                                            # ragged: row b's first column
-        al = cache.audio_lens                                                          # ragged audio: cross keys of item b
         x = self.wte(ids)
         if self.text_pos is not None:
             if ks is None:
@@ -453,32 +452,44 @@ class WhisperMoP(nn.Module):
             q, k, v = (p(h).view(B, T, H, Dh) for p in (sa.q_proj, sa.k_proj, sa.v_proj))
             cache.self_k[l].index_copy_(1, idx, k.to(cache.dtype))
             cache.self_v[l].index_copy_(1, idx, v.to(cache.dtype))
-            if prefill and ks is not None:                                            # key-padding mask (B, 1, 1, T)
-                y = ops.sdpa_core(q, k, v, attn_mask=(idx.unsqueeze(0) >= ks.unsqueeze(1)).view(B, 1, 1, T), causal=True)
-            elif prefill:
-                y = ops.sdpa_core(q, k, v, causal=True)
-            elif ks is not None:
-                y = ops.decode_attention_ragged(q, cache.self_k[l], cache.self_v[l], ks, rows=rows, kv_len=new_len, causal=True)
-            elif rows is not None:
-                y = ops.decode_attention_rows(q, cache.self_k[l], cache.self_v[l], rows, kv_len=new_len, causal=True)
-            else:
-                y = ops.decode_attention(q, cache.self_k[l], cache.self_v[l], kv_len=new_len, causal=True)
+            y = self._self_attention(cache, l, q, k, v, idx, new_len, rows, prefill)
             x = x + sa.o_proj(y)
             q = ca.q_proj(blk.ln2(x)).view(B, T, H, Dh)
-            ck, cv = cache.cross_k[l], cache.cross_v[l]
-            if long_chunk:
-                y = ops.sdpa_core(q, ck, cv) if al is None else ops.sdpa_core(q, ck, cv, kv_lens=al)
-            elif al is not None:                                                       # one length per item = per row of q here
-                y = ops.decode_attention_lens(q.view(B // beams, beams * T, H, Dh), ck, cv, al, nk=ck.shape[1]).view(B, T, H * Dh)
-            elif beams > 1:
-                y = ops.decode_attention(q.view(B // beams, beams * T, H, Dh), ck, cv, nk=ck.shape[1]).view(B, T, H * Dh)
-            else:
-                y = ops.decode_attention(q, ck, cv, nk=ck.shape[1])
+            y = self._cross_attention(cache, l, q, beams, long_chunk)
             x = x + ca.o_proj(y)
             x = x + blk.mlp.proj(F.gelu(blk.mlp.fc(blk.ln3(x)), approximate="tanh"))
         cache.length.add_(T)
         cache.pos += T
         return self.lm_head(self.dec_ln_f(x))
+
+    @staticmethod
+    def _self_attention(cache: WhisperDecodeCache, l: int, q, k, v, idx, new_len, rows, prefill: bool) -> torch.Tensor:
+        """layer l's causal self-attention of a decode step, after the step's k / v were appended: prefill (a first chunk of more
+        than 16 tokens) runs the square core on the chunk, every other step the decode core the cache asks for"""
+        ks = cache.kv_start
+        if prefill and ks is not None:                                                # key-padding mask (B, 1, 1, T)
+            B, T = q.shape[:2]
+            return ops.sdpa_core(q, k, v, attn_mask=(idx.unsqueeze(0) >= ks.unsqueeze(1)).view(B, 1, 1, T), causal=True)
+        if prefill:
+            return ops.sdpa_core(q, k, v, causal=True)
+        if ks is not None:
+            return ops.decode_attention_ragged(q, cache.self_k[l], cache.self_v[l], ks, rows=rows, kv_len=new_len, causal=True)
+        if rows is not None:
+            return ops.decode_attention_rows(q, cache.self_k[l], cache.self_v[l], rows, kv_len=new_len, causal=True)
+        return ops.decode_attention(q, cache.self_k[l], cache.self_v[l], kv_len=new_len, causal=True)
+
+    @staticmethod
+    def _cross_attention(cache: WhisperDecodeCache, l: int, q, beams: int, long_chunk: bool) -> torch.Tensor:
+        """layer l's cross-attention of a decode step over the item's cached audio keys / values"""
+        B, T, H, Dh = q.shape
+        ck, cv, al = cache.cross_k[l], cache.cross_v[l], cache.audio_lens
+        if long_chunk:
+            return ops.sdpa_core(q, ck, cv) if al is None else ops.sdpa_core(q, ck, cv, kv_lens=al)
+        if al is not None:                                                            # one length per item = per row of q here
+            return ops.decode_attention_lens(q.view(B // beams, beams * T, H, Dh), ck, cv, al, nk=ck.shape[1]).view(B, T, H * Dh)
+        if beams > 1:
+            return ops.decode_attention(q.view(B // beams, beams * T, H, Dh), ck, cv, nk=ck.shape[1]).view(B, T, H * Dh)
+        return ops.decode_attention(q, ck, cv, nk=ck.shape[1])
 
     @staticmethod
     def _ragged_check(mel: torch.Tensor, prompt_ids, what: str) -> Optional[List[int]]:
@@ -518,6 +529,69 @@ class WhisperMoP(nn.Module):
             return padded, kv_start.pin_memory().to(device, non_blocking=True)
         return padded, kv_start
 
+    def _decode_check(self, mel, prompt_ids, max_new_tokens: int, what: str, count=None, min_vocab: int = 0):
+        """the argument checks generate / beam_search / sample share, on top of _batch_check -> (audio batch info, prompt lengths
+        or None, B, T_p, rows per item).  count: (argument name, value) of beam_search's num_beams / sample's num_samples.
+        ValueErrors before any device work"""
+        mel_info, lens = self._batch_check(mel, prompt_ids, what)
+        B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
+        rep = 1 if count is None else int(count[1])
+        if not 1 <= rep <= ops.BEAM_MAX_K:
+            raise ValueError(f"{what}: {count[0]} = {count[1]} outside [1, {ops.BEAM_MAX_K}]")
+        if self.cfg.vocab_size < min_vocab:
+            raise ValueError(f"{what}: needs vocab_size >= {min_vocab}, got {self.cfg.vocab_size}")
+        if T_p < 1 or max_new_tokens < 1:
+            raise ValueError(f"{what}: needs a prompt and at least one new token (T_p = {T_p}, max_new_tokens = {max_new_tokens})")
+        if T_p + max_new_tokens > self.cfg.n_text_ctx:
+            raise ValueError(f"{what}: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        return mel_info, lens, B, T_p, rep
+
+    def _replicated_cache(self, mel, mel_info, prompt_ids, lens: Optional[List[int]], cap: int, rep: int):
+        """encode, run the prompt once per item and set up the cache of rep rows per item (beams / samples) for the steps after it
+        -> (prompt_ids (B, T_p) padded, prompt logits (B, V) shared by the item's rows, the step cache).  The prompt's keys / values
+        land in cache row b * rep (a prompt cache over the rows [::rep] of the same buffers); the step cache starts at pos = T_p,
+        with the padding's kv_start per row and the audio lengths per item (an item's rows share its cross cache)."""
+        H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
+        B, T_p = prompt_ids.shape
+        enc, audio_lens = _enc_parts(self.encode(mel)[0])
+        ck, cv = self._cross_kv(enc)
+        kw = dict(dtype=ck[0].dtype, device=enc.device)
+        sk = [torch.zeros(B * rep, cap, H, Dh, **kw) for _ in self.decoder]
+        sv = [torch.zeros(B * rep, cap, H, Dh, **kw) for _ in self.decoder]
+        length = torch.zeros(1, dtype=torch.int32, device=enc.device)
+        prompt_cache = WhisperDecodeCache(ck, cv, [t[::rep] for t in sk], [t[::rep] for t in sv], length, cap)
+        prompt_cache.kv_start, prompt_cache.audio_lens = kv_start, audio_lens
+        logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]
+        cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
+        cache.pos = T_p
+        cache.kv_start = None if kv_start is None else kv_start.repeat_interleave(rep)
+        cache.audio_lens = audio_lens
+        return prompt_ids, logits, cache
+
+    @staticmethod
+    def _step_loop(cache: WhisperDecodeCache, step, n_steps: int, graph: bool, feed=None) -> None:
+        """run step() n_steps times on the cache.  graph: the first step runs eagerly (and warms every kernel up), the second is
+        captured in a HIP graph (torch.cuda.graph, one stream, static buffers) and replayed for every further one.  feed(t), if
+        given, runs before step t and outside the graph: it puts the step's input where step() reads it (a static buffer for
+        t >= 1 when graph is set)."""
+        g = None
+        for t in range(n_steps):
+            if feed is not None:
+                feed(t)
+            if not graph or t == 0:
+                step()
+                continue
+            if g is None:
+                g = torch.cuda.CUDAGraph()
+                with torch.autocast(device_type="cuda", dtype=torch.get_autocast_dtype("cuda"),
+                                    enabled=torch.is_autocast_enabled("cuda"), cache_enabled=False):
+                    with torch.cuda.graph(g):
+                        step()
+                cache.pos -= 1                           # capture recorded the step without running it
+            g.replay()
+            cache.pos += 1
+
     @torch.no_grad()
     def generate(self, mel: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int, eos_token_id: Optional[int] = None,
                  graph: bool = False, *, return_logits: bool = False):
@@ -533,12 +607,7 @@ class WhisperMoP(nn.Module):
         1-D tensors, prompt b followed by its max_new_tokens tokens (views of one device tensor).
         mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode; it combines with a prompt list): every
         row decodes as it would alone."""
-        mel_info, lens = self._batch_check(mel, prompt_ids, "generate")
-        B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
-        if T_p < 1 or max_new_tokens < 1:
-            raise ValueError(f"generate: needs a prompt and at least one new token (T_p = {T_p}, max_new_tokens = {max_new_tokens})")
-        if T_p + max_new_tokens > self.cfg.n_text_ctx:
-            raise ValueError(f"generate: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        mel_info, lens, B, T_p, _ = self._decode_check(mel, prompt_ids, max_new_tokens, "generate")
         prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
         enc, _ = self.encode(mel)
         cache = self.init_decode_cache(enc, T_p + max_new_tokens)
@@ -546,8 +615,10 @@ class WhisperMoP(nn.Module):
         logits = self.decode_step(cache, prompt_ids)[:, -1]
         done = torch.zeros(B, dtype=torch.bool, device=prompt_ids.device) if eos_token_id is not None else None
         toks, steps = [], []
-        g = static_ids = static_logits = None
-        for t in range(max_new_tokens):
+        ids = None
+
+        def pick():                                  # the next token of every row from the last logits; never inside the graph
+            nonlocal done
             if return_logits:
                 steps.append(logits.clone())
             nxt = logits.argmax(-1)
@@ -555,25 +626,23 @@ class WhisperMoP(nn.Module):
                 nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)
                 done = done | (nxt == eos_token_id)
             toks.append(nxt)
-            if t == max_new_tokens - 1:
-                break
-            ids = nxt.unsqueeze(1)
-            if not graph or t == 0:                  # the first single-token step runs eagerly (and warms every kernel up)
-                logits = self.decode_step(cache, ids)[:, -1]
-                continue
-            if g is None:
-                static_ids = ids.clone()
-                g = torch.cuda.CUDAGraph()
-                with torch.autocast(device_type="cuda", dtype=torch.get_autocast_dtype("cuda"),
-                                    enabled=torch.is_autocast_enabled("cuda"), cache_enabled=False):
-                    with torch.cuda.graph(g):
-                        static_logits = self.decode_step(cache, static_ids)[:, -1]
-                cache.pos -= 1                           # capture recorded the step without running it
+            return nxt.unsqueeze(1)
+
+        def feed(t):
+            nonlocal ids
+            if graph and t > 1:
+                ids.copy_(pick())
+            elif graph and t == 1:                   # the buffer the captured step reads from then on
+                ids = pick().clone()
             else:
-                static_ids.copy_(ids)
-            g.replay()
-            cache.pos += 1
-            logits = static_logits
+                ids = pick()
+
+        def step():                                  # captured: logits becomes the graph's static output
+            nonlocal logits
+            logits = self.decode_step(cache, ids)[:, -1]
+
+        self._step_loop(cache, step, max_new_tokens - 1, graph, feed)
+        pick()
         out = torch.cat([prompt_ids, torch.stack(toks, dim=1).to(prompt_ids.dtype)], dim=1)
         if lens is not None:
             out = [out[b, T_p - lens[b]:] for b in range(B)]
@@ -600,53 +669,16 @@ class WhisperMoP(nn.Module):
         1-D tensors, prompt b followed by max_new_tokens tokens; gen_len counts generated tokens only, as for a tensor.
         mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode): an item's beams share its cross cache and
         its length."""
-        mel_info, lens = self._batch_check(mel, prompt_ids, "beam_search")
-        B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
-        K = int(num_beams)
-        if not 1 <= K <= ops.BEAM_MAX_K:
-            raise ValueError(f"beam_search: num_beams = {num_beams} outside [1, {ops.BEAM_MAX_K}]")
-        if self.cfg.vocab_size < 2:
-            raise ValueError(f"beam_search: needs vocab_size >= 2, got {self.cfg.vocab_size}")
-        if T_p < 1 or max_new_tokens < 1:
-            raise ValueError(f"beam_search: needs a prompt and at least one new token (T_p = {T_p}, max_new_tokens = {max_new_tokens})")
-        if T_p + max_new_tokens > self.cfg.n_text_ctx:
-            raise ValueError(f"beam_search: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        mel_info, lens, B, T_p, K = self._decode_check(mel, prompt_ids, max_new_tokens, "beam_search", ("num_beams", num_beams), 2)
         cap = T_p + max_new_tokens
-        H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
-        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
-        enc, audio_lens = _enc_parts(self.encode(mel)[0])
-        ck, cv = self._cross_kv(enc)
-        kw = dict(dtype=ck[0].dtype, device=enc.device)
-        sk = [torch.zeros(B * K, cap, H, Dh, **kw) for _ in self.decoder]
-        sv = [torch.zeros(B * K, cap, H, Dh, **kw) for _ in self.decoder]
-        length = torch.zeros(1, dtype=torch.int32, device=enc.device)
-        prompt_cache = WhisperDecodeCache(ck, cv, [t[::K] for t in sk], [t[::K] for t in sv], length, cap)
-        prompt_cache.kv_start, prompt_cache.audio_lens = kv_start, audio_lens
-        logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]              # (B, V): shared by the item's beams
-        cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
-        cache.pos = T_p
-        cache.kv_start = None if kv_start is None else kv_start.repeat_interleave(K)
-        cache.audio_lens = audio_lens                                           # per item: its beams share the cross cache
+        prompt_ids, logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, K)
         st = ops.BeamState(prompt_ids, K, cap, eos_token_id, length_penalty)
-        ops.beam_step(logits, st, length)
+        ops.beam_step(logits, st, cache.length)
 
         def step():
             ops.beam_step(self._decode_tokens(cache, st.next_ids, rows=st.rows, beams=K)[:, -1], st, cache.length)
 
-        g = None
-        for t in range(1, max_new_tokens):
-            if not graph or t == 1:                  # the first full step runs eagerly (and warms every kernel up)
-                step()
-                continue
-            if g is None:
-                g = torch.cuda.CUDAGraph()
-                with torch.autocast(device_type="cuda", dtype=torch.get_autocast_dtype("cuda"),
-                                    enabled=torch.is_autocast_enabled("cuda"), cache_enabled=False):
-                    with torch.cuda.graph(g):
-                        step()
-                cache.pos -= 1                           # capture recorded the step without running it
-            g.replay()
-            cache.pos += 1
+        self._step_loop(cache, step, max_new_tokens - 1, graph)
         tokens, scores = ops.beam_finalize(st, max_new_tokens)
         tokens = tokens.to(prompt_ids.dtype)
         if lens is not None:
@@ -672,33 +704,11 @@ class WhisperMoP(nn.Module):
         are those of a batch in which every prompt has its length.
         mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode): an item's samples share its cross cache
         and its length."""
-        mel_info, lens = self._batch_check(mel, prompt_ids, "sample")
-        B, T_p = prompt_ids.shape if lens is None else (len(lens), max(lens))
-        n = int(num_samples)
-        if not 1 <= n <= ops.BEAM_MAX_K:
-            raise ValueError(f"sample: num_samples = {num_samples} outside [1, {ops.BEAM_MAX_K}]")
-        if T_p < 1 or max_new_tokens < 1:
-            raise ValueError(f"sample: needs a prompt and at least one new token (T_p = {T_p}, max_new_tokens = {max_new_tokens})")
-        if T_p + max_new_tokens > self.cfg.n_text_ctx:
-            raise ValueError(f"sample: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        mel_info, lens, B, T_p, n = self._decode_check(mel, prompt_ids, max_new_tokens, "sample", ("num_samples", num_samples))
         ops._sample_params(temperature, top_k, top_p, "sample")                 # argument errors before encoding
-        prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
-        dev = prompt_ids.device
-        length = torch.zeros(1, dtype=torch.int32, device=dev)
         cap = T_p + max_new_tokens
-        H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
-        enc, audio_lens = _enc_parts(self.encode(mel)[0])
-        ck, cv = self._cross_kv(enc)
-        kw = dict(dtype=ck[0].dtype, device=enc.device)
-        sk = [torch.zeros(B * n, cap, H, Dh, **kw) for _ in self.decoder]
-        sv = [torch.zeros(B * n, cap, H, Dh, **kw) for _ in self.decoder]
-        prompt_cache = WhisperDecodeCache(ck, cv, [t[::n] for t in sk], [t[::n] for t in sv], length, cap)
-        prompt_cache.kv_start, prompt_cache.audio_lens = kv_start, audio_lens
-        logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]              # (B, V): shared by the item's samples
-        cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
-        cache.pos = T_p
-        cache.kv_start = None if kv_start is None else kv_start.repeat_interleave(n)
-        cache.audio_lens = audio_lens                                           # per item: its samples share the cross cache
+        prompt_ids, logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, n)
+        dev = prompt_ids.device
         i32 = dict(dtype=torch.int32, device=dev)
         r = torch.arange(B * n, **i32)
         table = r.unsqueeze(1).repeat(1, cap)                                   # constant: the prompt from row b * n, then own rows
@@ -729,20 +739,7 @@ class WhisperMoP(nn.Module):
             draw(self._decode_tokens(cache, ids, rows=table, beams=n)[:, -1])
 
         draw(logits)
-        g = None
-        for t in range(1, max_new_tokens):
-            if not graph or t == 1:                  # the first full step runs eagerly (and warms every kernel up)
-                step()
-                continue
-            if g is None:
-                g = torch.cuda.CUDAGraph()
-                with torch.autocast(device_type="cuda", dtype=torch.get_autocast_dtype("cuda"),
-                                    enabled=torch.is_autocast_enabled("cuda"), cache_enabled=False):
-                    with torch.cuda.graph(g):
-                        step()
-                cache.pos -= 1                           # capture recorded the step without running it
-            g.replay()
-            cache.pos += 1
+        self._step_loop(cache, step, max_new_tokens - 1, graph)
         tokens = tokens.view(B, n, cap).to(prompt_ids.dtype)
         if lens is not None:
             tokens = [tokens[b, :, T_p - lens[b]:] for b in range(B)]

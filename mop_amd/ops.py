@@ -1707,52 +1707,157 @@ def moe_route(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.Tens
 
 
 # ---- attention of a few new queries against a key / value cache (mopk_decode_attn_*; WhisperMoP incremental decoding) ----
+# Four public ops share one validator (_da_check), one torch composition (_da_torch), one acceptance test (_da_accept) and one
+# launch tail (_da_run).  An op is its public name; kw below is whichever of kv_len, nk, rows, kv_start, kv_lens it takes.
 DECODE_MAX_TQ = 16
+_NA = object()                  # _da_check: "the op has no such argument" (None is a value a caller can pass)
+_DA_OPS = {                     # op -> (args class, export stem, LAST_PATH key)
+    "decode_attention": (L.DecodeAttnArgs, "mopk_decode_attn", "decode_attn"),
+    "decode_attention_rows": (L.DecodeAttnRowsArgs, "mopk_decode_attn_rows", "decode_attn_rows"),
+    "decode_attention_ragged": (L.DecodeAttnRaggedArgs, "mopk_decode_attn_ragged", "decode_attn_ragged"),
+    "decode_attention_lens": (L.DecodeAttnLensArgs, "mopk_decode_attn_lens", "decode_attn_lens"),
+}
 
 
-def decode_attention_torch(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: Optional[torch.Tensor] = None,
-                           nk: Optional[int] = None, causal: bool = False) -> torch.Tensor:
-    """the reference composition of `decode_attention` in torch ops (fp32 arithmetic, float64 for float64 tensors); the valid length
-    stays on the device (a mask over the whole cache), so there is no host sync either"""
+def _not_row_ints(t: torch.Tensor, B: int) -> bool:
+    return t.dim() != 1 or t.shape[0] != B or t.dtype.is_floating_point or t.dtype == torch.bool
+
+
+def _da_check(op: str, q, k_cache, v_cache, kv_len=None, nk=None, rows=_NA, kv_start=_NA, kv_lens=_NA, rows_optional=False) -> None:
+    """the four ops' argument checks, in one order: shapes, kv_start, kv_lens, rows, kv_len against nk, nk, kv_len.  _NA: the op has
+    no such argument; rows_optional: rows may be None (the ragged op)"""
+    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError(f"{op}: q must be (B, Tq, H, dk) and k_cache, v_cache (B, cap, H, dk) of one shape; got q "
+                         f"{tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)}")
+    if k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
+        raise ValueError(f"{op}: k_cache / v_cache {tuple(k_cache.shape)} do not match q's B, H, dk {tuple(q.shape)}")
+    B, cap = q.shape[0], k_cache.shape[1]
+    if kv_start is not _NA and _not_row_ints(kv_start, B):
+        raise ValueError(f"{op}: kv_start must be an integer (B,) = ({B},) tensor, got {tuple(kv_start.shape)} {kv_start.dtype}")
+    if kv_lens is not _NA and (not isinstance(kv_lens, torch.Tensor) or _not_row_ints(kv_lens, B)):
+        raise ValueError(f"{op}: kv_lens must be an integer (B,) = ({B},) tensor, got "
+                         f"{(tuple(kv_lens.shape), kv_lens.dtype) if isinstance(kv_lens, torch.Tensor) else type(kv_lens).__name__}")
+    if rows is None and rows_optional:
+        rows = _NA
+    if rows is not _NA and (rows.dim() != 2 or rows.shape[0] != B or rows.shape[1] < cap):
+        raise ValueError(f"{op}: rows must be (B, >= cap) = ({B}, >= {cap}), got {tuple(rows.shape)}")
+    if kv_len is not None and nk is not None:
+        raise ValueError(f"{op}: pass kv_len (device) or nk (host), not both")
+    if nk is not None and not 0 < int(nk) <= cap:
+        raise ValueError(f"{op}: nk = {nk} outside [1, cap = {cap}]")
+    if kv_len is not None and kv_len.numel() != 1:
+        raise ValueError(f"{op}: kv_len must hold one element, got shape {tuple(kv_len.shape)}")
+
+
+def _da_torch(q, k_cache, v_cache, kv_len=None, nk=None, causal=False, rows=None, kv_start=None, kv_lens=None) -> torch.Tensor:
+    """the reference composition of the four ops in torch ops (fp32 arithmetic, float64 for float64 tensors).  Row b's key j comes
+    from cache row rows[b, j] (clamped into [0, B)); it is open if kv_start[b] <= j < min(L, kv_lens[b]), with L = kv_len (device),
+    else nk, else cap.  Every length stays on the device (masks over the whole cache), so there is no host sync either."""
     B, Tq, H, dk = q.shape
     cap = k_cache.shape[1]
+    if rows is not None:
+        r = rows[:, :cap].to(torch.long).clamp(0, B - 1)
+        j = torch.arange(cap, device=k_cache.device).unsqueeze(0)
+        k_cache, v_cache = k_cache[r, j], v_cache[r, j]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
     s = torch.einsum("bihd,bjhd->bhij", q.to(ct), k_cache.to(ct)) * dk ** -0.5
     j = torch.arange(cap, device=q.device)
     L = kv_len.reshape(()).to(torch.long).clamp(0, cap) if kv_len is not None else (cap if nk is None else int(nk))
     i = torch.arange(Tq, device=q.device)
     lim = L - Tq + i + 1 if causal else L + 0 * i                           # (Tq,): host ints never become device copies
-    ok = j.unsqueeze(0) < lim.unsqueeze(1)                                  # (Tq, cap)
-    s = s.masked_fill(~ok, float("-inf"))
+    open_ = (j < L).unsqueeze(0)                                            # (1 or B, cap): the keys a row may see at all
+    if kv_start is not None:
+        open_ = open_ & (j >= kv_start.reshape(B, 1).to(torch.long))
+    if kv_lens is not None:
+        open_ = open_ & (j < kv_lens.reshape(B, 1).to(torch.long).clamp_min(0))     # j < L is in open_ already
+    ok = open_.unsqueeze(1) & (j.unsqueeze(0) < lim.unsqueeze(1)).unsqueeze(0)  # (1 or B, Tq, cap)
+    s = s.masked_fill(~ok.unsqueeze(1), float("-inf"))
     p = torch.softmax(s, dim=-1).nan_to_num(0.0)                            # a query that sees no key gets y = 0, as the kernels
-    v = v_cache.to(ct).masked_fill(~(j < L).view(1, cap, 1, 1), 0.0)       # rows past L may hold anything
+    v = v_cache.to(ct).masked_fill(~open_.view(-1, cap, 1, 1), 0.0)         # rows that are not open may hold anything
     y = torch.einsum("bhij,bjhd->bihd", p, v)
     return y.to(q.dtype).reshape(B, Tq, H * dk)
 
 
-def _da_args(q, k_cache, v_cache, kv_len, nk, causal) -> L.DecodeAttnArgs:
+def _da_args(op: str, q, k_cache, v_cache, kv_len=None, nk=None, causal=False, rows=None, kv_start=None, kv_lens=None):
+    """the op's args struct, without y and the workspace"""
     B, Tq, H, dk = q.shape
-    a = L.DecodeAttnArgs()
-    a.B, a.H, a.Tq, a.dk, a.cap = B, H, Tq, dk, k_cache.shape[1]
-    a.Nk = a.cap if (nk is None and kv_len is None) else (0 if nk is None else int(nk))
-    a.io_dtype, a.causal = _io_dtype(q), int(bool(causal))
-    a.q, a.k, a.v = _v4(q), _v4(k_cache), _v4(v_cache)
-    a.kv_len = _ptr(kv_len)
+    base = L.DecodeAttnArgs()
+    base.B, base.H, base.Tq, base.dk, base.cap = B, H, Tq, dk, k_cache.shape[1]
+    base.Nk = base.cap if (nk is None and kv_len is None) else (0 if nk is None else int(nk))
+    base.io_dtype, base.causal = _io_dtype(q), int(bool(causal))
+    base.q, base.k, base.v = _v4(q), _v4(k_cache), _v4(v_cache)
+    base.kv_len = _ptr(kv_len)
+    if op == "decode_attention":
+        return base
+    a = _DA_OPS[op][0]()
+    a.base = base                                                           # a copy: from here on the fields are a.base's
+    if rows is not None:
+        a.rows, a.rows_ld = rows.data_ptr(), rows.stride(0)
+    if kv_start is not None:
+        a.kv_start = kv_start.data_ptr()
+    if kv_lens is not None:
+        a.kv_lens = kv_lens.data_ptr()
     return a
+
+
+def _row_i32_ok(t: torch.Tensor, B: int) -> bool:
+    """a per-row vector the kernels read: int32, CUDA, contiguous, B elements"""
+    return t.is_cuda and t.dtype == torch.int32 and t.numel() == B and t.is_contiguous()
+
+
+def _da_accept(op: str, q, k_cache, v_cache, kv_len=None, nk=None, causal=False, rows=None, kv_start=None, kv_lens=None):
+    """the args struct of a call that the op's kernels take, None of one they refuse.  The tensor side is tested here; the library's
+    query for the op decides the rest (each variant's query runs the plain op's check on its base first, so that is not asked twice)"""
+    if kv_start is not None and not _row_i32_ok(kv_start, q.shape[0]):
+        return None
+    if kv_lens is not None and not _row_i32_ok(kv_lens, q.shape[0]):
+        return None
+    if rows is not None and (not rows.is_cuda or rows.dtype != torch.int32 or rows.dim() != 2 or rows.stride(1) != 1):
+        return None
+    ts = (q, k_cache, v_cache)
+    if any(not t.is_cuda or t.dtype != q.dtype or t.dtype not in (torch.float32, torch.bfloat16) or t.stride(-1) != 1 for t in ts):
+        return None
+    if kv_len is not None and (not kv_len.is_cuda or kv_len.dtype != torch.int32 or kv_len.numel() != 1):
+        return None
+    if q.numel() == 0 or k_cache.shape[1] == 0:
+        return None
+    a = _da_args(op, q, k_cache, v_cache, kv_len, nk, causal, rows, kv_start, kv_lens)
+    return a if getattr(L.lib(), _DA_OPS[op][1] + "_supported")(C.byref(a)) else None
+
+
+def _da_run(op: str, q, k_cache, v_cache, causal=False, rows_optional=False, **kw) -> torch.Tensor:
+    """a public op's body: validate, then the HIP kernels on the args struct _da_accept built (the one struct serves the library's
+    _supported query, its workspace query and the launch), or _da_torch for a call the kernels refuse"""
+    _da_check(op, q, k_cache, v_cache, rows_optional=rows_optional, **kw)
+    _require_gpu(q, op)
+    _, stem, key = _DA_OPS[op]
+    with torch.no_grad():
+        a = _da_accept(op, q, k_cache, v_cache, causal=causal, **kw)
+        if a is None:
+            LAST_PATH[key] = L.PATH_GENERIC
+            return _da_torch(q, k_cache, v_cache, causal=causal, **kw)
+        B, Tq, H, dk = q.shape
+        y = torch.empty(B, Tq, H, dk, dtype=q.dtype, device=q.device)
+        ws = _bytes(getattr(L.lib(), stem + "_workspace_bytes")(C.byref(a)), q.device)
+        base = a if op == "decode_attention" else a.base
+        base.y, base.workspace = _v4(y), ws.data_ptr()
+        LAST_PATH[key] = L.PATH_FUSED
+        _launch(stem + "_fwd", a, key)
+        return y.view(B, Tq, H * dk)
+
+
+def decode_attention_torch(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: Optional[torch.Tensor] = None,
+                           nk: Optional[int] = None, causal: bool = False) -> torch.Tensor:
+    """the reference composition of `decode_attention` in torch ops (fp32 arithmetic, float64 for float64 tensors); the valid length
+    stays on the device (a mask over the whole cache), so there is no host sync either"""
+    return _da_torch(q, k_cache, v_cache, kv_len, nk, causal)
 
 
 def decode_attention_supported(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: Optional[torch.Tensor] = None,
                                nk: Optional[int] = None, causal: bool = False) -> bool:
     """True if mopk_decode_attn_* take this call: GPU tensors of one dtype (fp32 / bf16), 1 <= Tq <= 16, dk in {32, 64, 128}, unit
     inner strides, 16-byte aligned cache views, an int32 kv_len (the library's own query decides the rest)"""
-    ts = (q, k_cache, v_cache)
-    if any(not t.is_cuda or t.dtype != q.dtype or t.dtype not in (torch.float32, torch.bfloat16) or t.stride(-1) != 1 for t in ts):
-        return False
-    if kv_len is not None and (not kv_len.is_cuda or kv_len.dtype != torch.int32 or kv_len.numel() != 1):
-        return False
-    if q.numel() == 0 or k_cache.shape[1] == 0:
-        return False
-    return bool(L.lib().mopk_decode_attn_supported(C.byref(_da_args(q, k_cache, v_cache, kv_len, nk, causal))))
+    return _da_accept("decode_attention", q, k_cache, v_cache, kv_len, nk, causal) is not None
 
 
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_len: Optional[torch.Tensor] = None,
@@ -1765,31 +1870,7 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     bottom-right aligned: query i sees keys j < L - Tq + i + 1.  Returns (B, Tq, H * dk) in q's dtype.  Runs the split-KV HIP kernel
     pair when decode_attention_supported() accepts the call, else decode_attention_torch(); LAST_PATH["decode_attn"] records which
     (PATH_FUSED / PATH_GENERIC).  No host synchronisation."""
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise ValueError(f"decode_attention: q must be (B, Tq, H, dk) and k_cache, v_cache (B, cap, H, dk) of one shape; got q "
-                         f"{tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)}")
-    if k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
-        raise ValueError(f"decode_attention: k_cache / v_cache {tuple(k_cache.shape)} do not match q's B, H, dk {tuple(q.shape)}")
-    if kv_len is not None and nk is not None:
-        raise ValueError("decode_attention: pass kv_len (device) or nk (host), not both")
-    if nk is not None and not 0 < int(nk) <= k_cache.shape[1]:
-        raise ValueError(f"decode_attention: nk = {nk} outside [1, cap = {k_cache.shape[1]}]")
-    if kv_len is not None and kv_len.numel() != 1:
-        raise ValueError(f"decode_attention: kv_len must hold one element, got shape {tuple(kv_len.shape)}")
-    _require_gpu(q, "decode_attention")
-    with torch.no_grad():
-        if not decode_attention_supported(q, k_cache, v_cache, kv_len, nk, causal):
-            LAST_PATH["decode_attn"] = L.PATH_GENERIC
-            return decode_attention_torch(q, k_cache, v_cache, kv_len, nk, causal)
-        lib = L.lib()
-        B, Tq, H, dk = q.shape
-        a = _da_args(q, k_cache, v_cache, kv_len, nk, causal)
-        y = torch.empty(B, Tq, H, dk, dtype=q.dtype, device=q.device)
-        ws = _bytes(lib.mopk_decode_attn_workspace_bytes(C.byref(a)), q.device)
-        a.y, a.workspace = _v4(y), ws.data_ptr()
-        LAST_PATH["decode_attn"] = L.PATH_FUSED
-        _launch("mopk_decode_attn_fwd", a, "decode_attn")
-        return y.view(B, Tq, H * dk)
+    return _da_run("decode_attention", q, k_cache, v_cache, causal, kv_len=kv_len, nk=nk)
 
 
 # ---- decode attention through a source-row table (mopk_decode_attn_rows_*; WhisperMoP beam search) ----
@@ -1797,28 +1878,14 @@ def decode_attention_rows_torch(q: torch.Tensor, k_cache: torch.Tensor, v_cache:
                                 kv_len: Optional[torch.Tensor] = None, causal: bool = False) -> torch.Tensor:
     """the reference composition of `decode_attention_rows`: gather key / value j of row b from cache row rows[b, j] (clamped into
     [0, B)), then decode_attention_torch"""
-    B, cap = k_cache.shape[:2]
-    r = rows[:, :cap].to(torch.long).clamp(0, B - 1)
-    j = torch.arange(cap, device=k_cache.device).unsqueeze(0)
-    return decode_attention_torch(q, k_cache[r, j], v_cache[r, j], kv_len, None, causal)
-
-
-def _dar_args(q, k_cache, v_cache, rows, kv_len, causal) -> L.DecodeAttnRowsArgs:
-    a = L.DecodeAttnRowsArgs()
-    a.base = _da_args(q, k_cache, v_cache, kv_len, None, causal)
-    a.rows, a.rows_ld = rows.data_ptr(), rows.stride(0)
-    return a
+    return _da_torch(q, k_cache, v_cache, kv_len, None, causal, rows=rows)
 
 
 def decode_attention_rows_supported(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, rows: torch.Tensor,
                                     kv_len: Optional[torch.Tensor] = None, causal: bool = False) -> bool:
     """True if mopk_decode_attn_rows_* take this call: what decode_attention_supported asks, and a CUDA int32 (B, >= cap) table with
     unit inner stride"""
-    if not rows.is_cuda or rows.dtype != torch.int32 or rows.dim() != 2 or rows.stride(1) != 1:
-        return False
-    if not decode_attention_supported(q, k_cache, v_cache, kv_len, None, causal):
-        return False
-    return bool(L.lib().mopk_decode_attn_rows_supported(C.byref(_dar_args(q, k_cache, v_cache, rows, kv_len, causal))))
+    return _da_accept("decode_attention_rows", q, k_cache, v_cache, kv_len, None, causal, rows=rows) is not None
 
 
 def decode_attention_rows(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, rows: torch.Tensor,
@@ -1830,30 +1897,7 @@ def decode_attention_rows(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     kv_len as in decode_attention (else L = cap).  With rows[b, j] = b the result is bitwise that of decode_attention.  Returns
     (B, Tq, H * dk) in q's dtype.  Runs the row-indirect split-KV HIP kernels when decode_attention_rows_supported() accepts the call,
     else decode_attention_rows_torch(); LAST_PATH["decode_attn_rows"] records which.  No host synchronisation."""
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise ValueError(f"decode_attention_rows: q must be (B, Tq, H, dk) and k_cache, v_cache (B, cap, H, dk) of one shape; got q "
-                         f"{tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)}")
-    if k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
-        raise ValueError(f"decode_attention_rows: k_cache / v_cache {tuple(k_cache.shape)} do not match q's B, H, dk {tuple(q.shape)}")
-    if rows.dim() != 2 or rows.shape[0] != q.shape[0] or rows.shape[1] < k_cache.shape[1]:
-        raise ValueError(f"decode_attention_rows: rows must be (B, >= cap) = ({q.shape[0]}, >= {k_cache.shape[1]}), "
-                         f"got {tuple(rows.shape)}")
-    if kv_len is not None and kv_len.numel() != 1:
-        raise ValueError(f"decode_attention_rows: kv_len must hold one element, got shape {tuple(kv_len.shape)}")
-    _require_gpu(q, "decode_attention_rows")
-    with torch.no_grad():
-        if not decode_attention_rows_supported(q, k_cache, v_cache, rows, kv_len, causal):
-            LAST_PATH["decode_attn_rows"] = L.PATH_GENERIC
-            return decode_attention_rows_torch(q, k_cache, v_cache, rows, kv_len, causal)
-        lib = L.lib()
-        B, Tq, H, dk = q.shape
-        a = _dar_args(q, k_cache, v_cache, rows, kv_len, causal)
-        y = torch.empty(B, Tq, H, dk, dtype=q.dtype, device=q.device)
-        ws = _bytes(lib.mopk_decode_attn_rows_workspace_bytes(C.byref(a)), q.device)
-        a.base.y, a.base.workspace = _v4(y), ws.data_ptr()
-        LAST_PATH["decode_attn_rows"] = L.PATH_FUSED
-        _launch("mopk_decode_attn_rows_fwd", a, "decode_attn_rows")
-        return y.view(B, Tq, H * dk)
+    return _da_run("decode_attention_rows", q, k_cache, v_cache, causal, rows=rows, kv_len=kv_len)
 
 
 # ---- decode attention with a per-row first key (mopk_decode_attn_ragged_*; WhisperMoP decoding of left-padded prompts) ----
@@ -1862,33 +1906,7 @@ def decode_attention_ragged_torch(q: torch.Tensor, k_cache: torch.Tensor, v_cach
                                   causal: bool = False) -> torch.Tensor:
     """the reference composition of `decode_attention_ragged`: decode_attention_torch (after the row gather of
     decode_attention_rows_torch when rows is given) with the keys j < kv_start[b] of row b masked out; no host sync"""
-    B, Tq, H, dk = q.shape
-    cap = k_cache.shape[1]
-    if rows is not None:
-        r = rows[:, :cap].to(torch.long).clamp(0, B - 1)
-        j = torch.arange(cap, device=k_cache.device).unsqueeze(0)
-        k_cache, v_cache = k_cache[r, j], v_cache[r, j]
-    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
-    s = torch.einsum("bihd,bjhd->bhij", q.to(ct), k_cache.to(ct)) * dk ** -0.5
-    j = torch.arange(cap, device=q.device)
-    L = kv_len.reshape(()).to(torch.long).clamp(0, cap) if kv_len is not None else (cap if nk is None else int(nk))
-    i = torch.arange(Tq, device=q.device)
-    lim = L - Tq + i + 1 if causal else L + 0 * i                           # (Tq,)
-    open_ = (j >= kv_start.reshape(B, 1).to(torch.long)) & (j < L)          # (B, cap): the keys a row may see at all
-    ok = open_.unsqueeze(1) & (j.unsqueeze(0) < lim.unsqueeze(1)).unsqueeze(0)  # (B, Tq, cap)
-    s = s.masked_fill(~ok.unsqueeze(1), float("-inf"))
-    p = torch.softmax(s, dim=-1).nan_to_num(0.0)                            # a query that sees no key gets y = 0, as the kernels
-    v = v_cache.to(ct).masked_fill(~open_.view(B, cap, 1, 1), 0.0)          # rows outside [kv_start, L) may hold anything
-    y = torch.einsum("bhij,bjhd->bihd", p, v)
-    return y.to(q.dtype).reshape(B, Tq, H * dk)
-
-
-def _dag_args(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal) -> L.DecodeAttnRaggedArgs:
-    a = L.DecodeAttnRaggedArgs()
-    a.base = _da_args(q, k_cache, v_cache, kv_len, nk, causal)
-    a.rows, a.rows_ld = (None, 0) if rows is None else (rows.data_ptr(), rows.stride(0))
-    a.kv_start = kv_start.data_ptr()
-    return a
+    return _da_torch(q, k_cache, v_cache, kv_len, nk, causal, rows=rows, kv_start=kv_start)
 
 
 def decode_attention_ragged_supported(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_start: torch.Tensor,
@@ -1896,13 +1914,7 @@ def decode_attention_ragged_supported(q: torch.Tensor, k_cache: torch.Tensor, v_
                                       nk: Optional[int] = None, causal: bool = False) -> bool:
     """True if mopk_decode_attn_ragged_* take this call: what decode_attention_supported asks, a contiguous CUDA int32 kv_start of
     B elements, and (with rows) what decode_attention_rows_supported asks of the table"""
-    if not kv_start.is_cuda or kv_start.dtype != torch.int32 or kv_start.numel() != q.shape[0] or not kv_start.is_contiguous():
-        return False
-    if rows is not None and (not rows.is_cuda or rows.dtype != torch.int32 or rows.dim() != 2 or rows.stride(1) != 1):
-        return False
-    if not decode_attention_supported(q, k_cache, v_cache, kv_len, nk, causal):
-        return False
-    return bool(L.lib().mopk_decode_attn_ragged_supported(C.byref(_dag_args(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal))))
+    return _da_accept("decode_attention_ragged", q, k_cache, v_cache, kv_len, nk, causal, rows=rows, kv_start=kv_start) is not None
 
 
 def decode_attention_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_start: torch.Tensor,
@@ -1917,38 +1929,7 @@ def decode_attention_ragged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
     sees no key gets y = 0.  With kv_start = 0 the result is bitwise that of decode_attention / decode_attention_rows.  Returns
     (B, Tq, H * dk) in q's dtype.  Runs the split-KV HIP kernels when decode_attention_ragged_supported() accepts the call, else
     decode_attention_ragged_torch(); LAST_PATH["decode_attn_ragged"] records which.  No host synchronisation."""
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise ValueError(f"decode_attention_ragged: q must be (B, Tq, H, dk) and k_cache, v_cache (B, cap, H, dk) of one shape; got "
-                         f"q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)}")
-    if k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
-        raise ValueError(f"decode_attention_ragged: k_cache / v_cache {tuple(k_cache.shape)} do not match q's B, H, dk "
-                         f"{tuple(q.shape)}")
-    if kv_start.dim() != 1 or kv_start.shape[0] != q.shape[0] or kv_start.dtype.is_floating_point or kv_start.dtype == torch.bool:
-        raise ValueError(f"decode_attention_ragged: kv_start must be an integer (B,) = ({q.shape[0]},) tensor, got "
-                         f"{tuple(kv_start.shape)} {kv_start.dtype}")
-    if rows is not None and (rows.dim() != 2 or rows.shape[0] != q.shape[0] or rows.shape[1] < k_cache.shape[1]):
-        raise ValueError(f"decode_attention_ragged: rows must be (B, >= cap) = ({q.shape[0]}, >= {k_cache.shape[1]}), "
-                         f"got {tuple(rows.shape)}")
-    if kv_len is not None and nk is not None:
-        raise ValueError("decode_attention_ragged: pass kv_len (device) or nk (host), not both")
-    if nk is not None and not 0 < int(nk) <= k_cache.shape[1]:
-        raise ValueError(f"decode_attention_ragged: nk = {nk} outside [1, cap = {k_cache.shape[1]}]")
-    if kv_len is not None and kv_len.numel() != 1:
-        raise ValueError(f"decode_attention_ragged: kv_len must hold one element, got shape {tuple(kv_len.shape)}")
-    _require_gpu(q, "decode_attention_ragged")
-    with torch.no_grad():
-        if not decode_attention_ragged_supported(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal):
-            LAST_PATH["decode_attn_ragged"] = L.PATH_GENERIC
-            return decode_attention_ragged_torch(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal)
-        lib = L.lib()
-        B, Tq, H, dk = q.shape
-        a = _dag_args(q, k_cache, v_cache, kv_start, rows, kv_len, nk, causal)
-        y = torch.empty(B, Tq, H, dk, dtype=q.dtype, device=q.device)
-        ws = _bytes(lib.mopk_decode_attn_ragged_workspace_bytes(C.byref(a)), q.device)
-        a.base.y, a.base.workspace = _v4(y), ws.data_ptr()
-        LAST_PATH["decode_attn_ragged"] = L.PATH_FUSED
-        _launch("mopk_decode_attn_ragged_fwd", a, "decode_attn_ragged")
-        return y.view(B, Tq, H * dk)
+    return _da_run("decode_attention_ragged", q, k_cache, v_cache, causal, True, kv_start=kv_start, rows=rows, kv_len=kv_len, nk=nk)
 
 
 # ---- decode attention with a per-row key count (mopk_decode_attn_lens_*; WhisperMoP cross-attention over ragged audio) ----
@@ -1956,36 +1937,14 @@ def decode_attention_lens_torch(q: torch.Tensor, k_cache: torch.Tensor, v_cache:
                                 nk: Optional[int] = None) -> torch.Tensor:
     """the reference composition of `decode_attention_lens`: non-causal decode_attention_torch with the keys j >= kv_lens[b] of row b
     masked out; no host sync"""
-    B, Tq, H, dk = q.shape
-    cap = k_cache.shape[1]
-    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
-    s = torch.einsum("bihd,bjhd->bhij", q.to(ct), k_cache.to(ct)) * dk ** -0.5
-    j = torch.arange(cap, device=q.device)
-    L_ = kv_lens.reshape(B, 1).to(torch.long).clamp(0, cap if nk is None else int(nk))
-    open_ = j.unsqueeze(0) < L_                                             # (B, cap)
-    s = s.masked_fill(~open_.view(B, 1, 1, cap), float("-inf"))
-    p = torch.softmax(s, dim=-1).nan_to_num(0.0)                            # a row that sees no key gets y = 0, as the kernels
-    v = v_cache.to(ct).masked_fill(~open_.view(B, cap, 1, 1), 0.0)          # rows past kv_lens[b] may hold anything
-    y = torch.einsum("bhij,bjhd->bihd", p, v)
-    return y.to(q.dtype).reshape(B, Tq, H * dk)
-
-
-def _dal_args(q, k_cache, v_cache, kv_lens, nk) -> L.DecodeAttnLensArgs:
-    a = L.DecodeAttnLensArgs()
-    a.base = _da_args(q, k_cache, v_cache, None, nk, False)
-    a.kv_lens = kv_lens.data_ptr()
-    return a
+    return _da_torch(q, k_cache, v_cache, None, nk, False, kv_lens=kv_lens)
 
 
 def decode_attention_lens_supported(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_lens: torch.Tensor,
                                     nk: Optional[int] = None) -> bool:
     """True if mopk_decode_attn_lens_* take this call: what decode_attention_supported asks, and a contiguous CUDA int32 kv_lens of
     B elements"""
-    if not kv_lens.is_cuda or kv_lens.dtype != torch.int32 or kv_lens.numel() != q.shape[0] or not kv_lens.is_contiguous():
-        return False
-    if not decode_attention_supported(q, k_cache, v_cache, None, nk, False):
-        return False
-    return bool(L.lib().mopk_decode_attn_lens_supported(C.byref(_dal_args(q, k_cache, v_cache, kv_lens, nk))))
+    return _da_accept("decode_attention_lens", q, k_cache, v_cache, None, nk, False, kv_lens=kv_lens) is not None
 
 
 def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, kv_lens: torch.Tensor,
@@ -1999,32 +1958,7 @@ def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     bitwise decode_attention(q, k_cache, v_cache, nk=nk).  Returns (B, Tq, H * dk) in q's dtype.  Runs the split-KV HIP kernels when
     decode_attention_lens_supported() accepts the call, else decode_attention_lens_torch(); LAST_PATH["decode_attn_lens"] records
     which.  No host synchronisation."""
-    if q.dim() != 4 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
-        raise ValueError(f"decode_attention_lens: q must be (B, Tq, H, dk) and k_cache, v_cache (B, cap, H, dk) of one shape; got "
-                         f"q {tuple(q.shape)}, k {tuple(k_cache.shape)}, v {tuple(v_cache.shape)}")
-    if k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
-        raise ValueError(f"decode_attention_lens: k_cache / v_cache {tuple(k_cache.shape)} do not match q's B, H, dk "
-                         f"{tuple(q.shape)}")
-    if (not isinstance(kv_lens, torch.Tensor) or kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0]
-            or kv_lens.dtype.is_floating_point or kv_lens.dtype == torch.bool):
-        raise ValueError(f"decode_attention_lens: kv_lens must be an integer (B,) = ({q.shape[0]},) tensor, got "
-                         f"{(tuple(kv_lens.shape), kv_lens.dtype) if isinstance(kv_lens, torch.Tensor) else type(kv_lens).__name__}")
-    if nk is not None and not 0 < int(nk) <= k_cache.shape[1]:
-        raise ValueError(f"decode_attention_lens: nk = {nk} outside [1, cap = {k_cache.shape[1]}]")
-    _require_gpu(q, "decode_attention_lens")
-    with torch.no_grad():
-        if not decode_attention_lens_supported(q, k_cache, v_cache, kv_lens, nk):
-            LAST_PATH["decode_attn_lens"] = L.PATH_GENERIC
-            return decode_attention_lens_torch(q, k_cache, v_cache, kv_lens, nk)
-        lib = L.lib()
-        B, Tq, H, dk = q.shape
-        a = _dal_args(q, k_cache, v_cache, kv_lens, nk)
-        y = torch.empty(B, Tq, H, dk, dtype=q.dtype, device=q.device)
-        ws = _bytes(lib.mopk_decode_attn_lens_workspace_bytes(C.byref(a)), q.device)
-        a.base.y, a.base.workspace = _v4(y), ws.data_ptr()
-        LAST_PATH["decode_attn_lens"] = L.PATH_FUSED
-        _launch("mopk_decode_attn_lens_fwd", a, "decode_attn_lens")
-        return y.view(B, Tq, H * dk)
+    return _da_run("decode_attention_lens", q, k_cache, v_cache, kv_lens=kv_lens, nk=nk)
 
 
 # ---- batched beam search on device state (mopk_beam_*; WhisperMoP.beam_search) ----
@@ -2344,6 +2278,20 @@ def _sample_args(logits: torch.Tensor, pos: torch.Tensor, R: int, n: int, inv_t,
     return a
 
 
+def _sample_launch(stem: str, key: str, a, logits: torch.Tensor, R: int, out):
+    """the tail sample_tokens and sample_tokens_ragged share: out buffers, workspace and launch of `stem`_step on the args `a`"""
+    if out is None:
+        out = (torch.empty(R, dtype=torch.int32, device=logits.device), torch.empty(R, dtype=torch.float32, device=logits.device))
+    base = getattr(a, "base", a)
+    base.tokens, base.logprobs = out[0].data_ptr(), out[1].data_ptr()
+    ws_bytes = getattr(L.lib(), stem + "_workspace_bytes")(C.byref(a))
+    ws = _bytes(ws_bytes, logits.device) if ws_bytes else None
+    base.workspace = _ptr(ws)
+    LAST_PATH[key] = L.PATH_FUSED
+    _launch(stem + "_step", a, key)
+    return out[0], out[1]
+
+
 def sample_tokens_supported(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                             seed: int = 0, out=None) -> bool:
     """True if mopk_sample_* take this call: CUDA fp32 / bf16 logits with unit inner stride, an int32 device pos, contiguous CUDA
@@ -2382,16 +2330,7 @@ def sample_tokens(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 
         if not sample_tokens_supported(logits, pos, temperature, top_k, top_p, seed, out):
             LAST_PATH["sample"] = L.PATH_GENERIC
             return sample_tokens_torch(logits, pos, temperature, top_k, top_p, seed, out)
-        if out is None:
-            out = (torch.empty(R, dtype=torch.int32, device=logits.device), torch.empty(R, dtype=torch.float32, device=logits.device))
-        a = _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed)
-        a.tokens, a.logprobs = out[0].data_ptr(), out[1].data_ptr()
-        ws_bytes = L.lib().mopk_sample_workspace_bytes(C.byref(a))
-        ws = _bytes(ws_bytes, logits.device) if ws_bytes else None
-        a.workspace = _ptr(ws)
-        LAST_PATH["sample"] = L.PATH_FUSED
-        _launch("mopk_sample_step", a, "sample")
-        return out[0], out[1]
+        return _sample_launch("mopk_sample", "sample", _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed), logits, R, out)
 
 
 # ---- sampling of a left-padded ragged batch (mopk_sample_ragged_*; WhisperMoP.sample with per-row prompt lengths) ----
@@ -2436,14 +2375,6 @@ def sample_tokens_ragged(logits: torch.Tensor, pos: torch.Tensor, pos_off: torch
         if not sample_tokens_ragged_supported(logits, pos, pos_off, temperature, top_k, top_p, seed, out):
             LAST_PATH["sample_ragged"] = L.PATH_GENERIC
             return sample_tokens_ragged_torch(logits, pos, pos_off, temperature, top_k, top_p, seed, out)
-        if out is None:
-            out = (torch.empty(R, dtype=torch.int32, device=logits.device), torch.empty(R, dtype=torch.float32, device=logits.device))
         a = L.SampleRaggedArgs()
         a.base, a.pos_off = _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed), pos_off.data_ptr()
-        a.base.tokens, a.base.logprobs = out[0].data_ptr(), out[1].data_ptr()
-        ws_bytes = L.lib().mopk_sample_ragged_workspace_bytes(C.byref(a))
-        ws = _bytes(ws_bytes, logits.device) if ws_bytes else None
-        a.base.workspace = _ptr(ws)
-        LAST_PATH["sample_ragged"] = L.PATH_FUSED
-        _launch("mopk_sample_ragged_step", a, "sample_ragged")
-        return out[0], out[1]
+        return _sample_launch("mopk_sample_ragged", "sample_ragged", a, logits, R, out)
