@@ -680,6 +680,44 @@ int mopk_sample_ragged_supported(const MopkSampleRaggedArgs *a);
 size_t mopk_sample_ragged_workspace_bytes(const MopkSampleRaggedArgs *a);
 int mopk_sample_ragged_step(const MopkSampleRaggedArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * Whisper's logit rules on last-position logits (WhisperMoP.generate / beam_search / sample with logit_rules; inference only).
+ * (Added under version 118: new exports only; callers detect it with mopk_logit_rules_supported.)  Row r (0 <= r < R) reads x at
+ * logits + r * logits_ld elements and writes out + r * out_ld (F32 or BF16, element-aligned); every written entry is the input's
+ * bits or -inf ("blocked").  g = hist[r * hist_ld + T0 ...] holds the n = clamp(*pos - T0, 0, T - T0) tokens generated so far
+ * (*pos in device memory: one set of launch arguments serves every decoding step).  In this order:
+ *   1. mask[v] & 1: blocked (the never-emit list; callers fold the no-timestamps token in when tb >= 0);
+ *   2. n == 0 and mask[v] & 2: blocked (blank / eot at the first generated position);
+ *   3. tb >= 0 (timestamp tokens are v >= tb), with last = n >= 1 && g[n-1] >= tb and pen = n < 2 || g[n-2] >= tb:
+ *      last && pen: x[tb:] blocked; last && !pen: x[:eos] blocked;
+ *      t = the last g[i] >= tb, if any: x[tb:lim] blocked, lim = t when last && !pen, else t + 1 (timestamps never decrease);
+ *      n == 0: x[:tb] blocked, and x[tb + max_initial + 1:] when max_initial >= 0;
+ *      then, over what is left, in fp32: L = m + logf(sum expf(x[tb:] - m)), m = max x[tb:], M = max x[:tb] (-inf for an empty
+ *      side); L > M: x[:tb] blocked.
+ * A row that the caller's lists block completely comes out all -inf: no guard.  One workgroup of 1024 threads per row: one wave
+ * scans g, one streaming pass merges (m, sum, M) in a fixed order, one writes the result; bitwise reproducible, no workspace, no
+ * host synchronisation.  out may be logits (the same rows); any other overlap is undefined. */
+typedef struct MopkLogitRulesArgs {
+    int32_t R;                           /* rows */
+    int32_t V;                           /* vocabulary, >= 2 */
+    int32_t dtype;                       /* MopkDtype of logits and out: F32 or BF16 */
+    int32_t T;                           /* columns of hist (g is never read past them) */
+    int32_t T0;                          /* first generated column, 0 <= T0 <= T */
+    int32_t tb;                          /* first timestamp token, or -1: rule 3 off */
+    int32_t eos;                         /* 0 <= eos < tb when tb >= 0 (unused otherwise) */
+    int32_t max_initial;                 /* max_initial_timestamp_index, or -1: off */
+    const void *logits;
+    int64_t logits_ld;                   /* element stride between rows, >= V */
+    void *out;
+    int64_t out_ld;                      /* >= V */
+    const int32_t *hist;                 /* device (R rows of T) int32 */
+    int64_t hist_ld;                     /* element stride between hist rows, >= T */
+    const int32_t *pos;                  /* device: one int32 */
+    const uint8_t *mask;                 /* device (V): bit 0 rule 1, bit 1 rule 2 */
+} MopkLogitRulesArgs;
+int mopk_logit_rules_supported(const MopkLogitRulesArgs *a);         /* 1 if the kernel takes this call (V, dtype, strides, ids) */
+int mopk_logit_rules(const MopkLogitRulesArgs *a, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

@@ -227,6 +227,16 @@ class SampleRaggedArgs(C.Structure):
     _fields_ = [("base", SampleArgs), ("pos_off", _fp)]
 
 
+class LogitRulesArgs(C.Structure):
+    """MopkLogitRulesArgs: Whisper's suppression and timestamp rules on last-position logits (WhisperMoP's logit_rules)."""
+    _fields_ = [
+        ("R", C.c_int32), ("V", C.c_int32), ("dtype", C.c_int32), ("T", C.c_int32), ("T0", C.c_int32), ("tb", C.c_int32),
+        ("eos", C.c_int32), ("max_initial", C.c_int32),
+        ("logits", _fp), ("logits_ld", C.c_int64), ("out", _fp), ("out_ld", C.c_int64), ("hist", _fp), ("hist_ld", C.c_int64),
+        ("pos", _fp), ("mask", _fp),
+    ]
+
+
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),
@@ -302,6 +312,8 @@ SYMBOLS = {
     "mopk_decode_attn_lens_supported": (C.c_int, [C.POINTER(DecodeAttnLensArgs)]),
     "mopk_decode_attn_lens_workspace_bytes": (C.c_size_t, [C.POINTER(DecodeAttnLensArgs)]),
     "mopk_decode_attn_lens_fwd": (C.c_int, [C.POINTER(DecodeAttnLensArgs), C.c_void_p]),
+    "mopk_logit_rules_supported": (C.c_int, [C.POINTER(LogitRulesArgs)]),
+    "mopk_logit_rules": (C.c_int, [C.POINTER(LogitRulesArgs), C.c_void_p]),
 }
 
 _lib = None

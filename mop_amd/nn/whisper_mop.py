@@ -546,6 +546,24 @@ class WhisperMoP(nn.Module):
             raise ValueError(f"{what}: T_p + max_new_tokens = {T_p + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
         return mel_info, lens, B, T_p, rep
 
+    def _rules_check(self, rules, eos_token_id, what: str) -> None:
+        """the argument checks of a decoding with logit rules (None: nothing to check); ValueErrors before any device work"""
+        if rules is None:
+            return
+        if not isinstance(rules, ops.LogitRules):
+            raise ValueError(f"{what}: logit rules must be an ops.LogitRules, got {type(rules).__name__}")
+        if rules.vocab_size != self.cfg.vocab_size:
+            raise ValueError(f"{what}: the logit rules were built for vocab_size = {rules.vocab_size}, the model has "
+                             f"{self.cfg.vocab_size}")
+        if rules.eos_token_id is not None and eos_token_id is not None and int(eos_token_id) != rules.eos_token_id:
+            raise ValueError(f"{what}: eos_token_id = {eos_token_id}, the logit rules' eos_token_id = {rules.eos_token_id}")
+
+    def with_logit_rules(self, logit_rules: Optional["ops.LogitRules"]) -> "RuledDecoding":
+        """this model's decoders under Whisper's logit rules: with_logit_rules(rules).generate / .beam_search / .sample take the
+        arguments of generate / beam_search / sample and apply ops.logit_rules(rules) to every step's last-position logits, on the
+        device and inside the captured step, before the argmax / beam step / draw.  None: the plain decoders."""
+        return RuledDecoding(self, logit_rules)
+
     def _replicated_cache(self, mel, mel_info, prompt_ids, lens: Optional[List[int]], cap: int, rep: int):
         """encode, run the prompt once per item and set up the cache of rep rows per item (beams / samples) for the steps after it
         -> (prompt_ids (B, T_p) padded, prompt logits (B, V) shared by the item's rows, the step cache).  The prompt's keys / values
@@ -606,13 +624,25 @@ class WhisperMoP(nn.Module):
         a per-row start (WhisperDecodeCache.kv_start), each row decodes as it would alone, and the tokens come back as a list of B
         1-D tensors, prompt b followed by its max_new_tokens tokens (views of one device tensor).
         mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode; it combines with a prompt list): every
-        row decodes as it would alone."""
+        row decodes as it would alone.
+        Whisper's logit rules: with_logit_rules(rules).generate(...) takes the same arguments."""
+        return self._generate(mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, None)
+
+    def _generate(self, mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, logit_rules):
+        """generate's body.  logit_rules: every step's last-position logits pass ops.logit_rules before the argmax, inside the
+        captured step, over a (B, cap) int32 device history kept for them only; None runs exactly the code without them"""
         mel_info, lens, B, T_p, _ = self._decode_check(mel, prompt_ids, max_new_tokens, "generate")
+        self._rules_check(logit_rules, eos_token_id, "generate")
         prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
         enc, _ = self.encode(mel)
         cache = self.init_decode_cache(enc, T_p + max_new_tokens)
         cache.kv_start = kv_start
         logits = self.decode_step(cache, prompt_ids)[:, -1]
+        hist = None
+        if logit_rules is not None:
+            hist = torch.zeros(B, T_p + max_new_tokens, dtype=torch.int32, device=prompt_ids.device)
+            hist[:, :T_p] = prompt_ids
+            logits = ops.logit_rules(logits, hist, cache.length, T_p, logit_rules, out=logits)
         done = torch.zeros(B, dtype=torch.bool, device=prompt_ids.device) if eos_token_id is not None else None
         toks, steps = [], []
         ids = None
@@ -626,6 +656,8 @@ class WhisperMoP(nn.Module):
                 nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)
                 done = done | (nxt == eos_token_id)
             toks.append(nxt)
+            if hist is not None:
+                hist[:, cache.pos] = nxt             # the host drives the loop: it knows the column
             return nxt.unsqueeze(1)
 
         def feed(t):
@@ -640,6 +672,8 @@ class WhisperMoP(nn.Module):
         def step():                                  # captured: logits becomes the graph's static output
             nonlocal logits
             logits = self.decode_step(cache, ids)[:, -1]
+            if hist is not None:
+                logits = ops.logit_rules(logits, hist, cache.length, T_p, logit_rules, out=logits)
 
         self._step_loop(cache, step, max_new_tokens - 1, graph, feed)
         pick()
@@ -668,15 +702,28 @@ class WhisperMoP(nn.Module):
         prompt_ids may also be a list of B 1-D tensors of different lengths (see generate): the tokens then come back as a list of B
         1-D tensors, prompt b followed by max_new_tokens tokens; gen_len counts generated tokens only, as for a tensor.
         mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode): an item's beams share its cross cache and
-        its length."""
+        its length.
+        Whisper's logit rules: with_logit_rules(rules).beam_search(...) takes the same arguments."""
+        return self._beam_search(mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph, None)
+
+    def _beam_search(self, mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph, logit_rules):
+        """beam_search's body.  logit_rules: every step's logits pass ops.logit_rules before ops.beam_step, inside the captured
+        step, with the beams' own histories (the first step's shared prompt logits with the rows [::K] of them); None runs exactly
+        the code without them"""
         mel_info, lens, B, T_p, K = self._decode_check(mel, prompt_ids, max_new_tokens, "beam_search", ("num_beams", num_beams), 2)
+        self._rules_check(logit_rules, eos_token_id, "beam_search")
         cap = T_p + max_new_tokens
         prompt_ids, logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, K)
         st = ops.BeamState(prompt_ids, K, cap, eos_token_id, length_penalty)
+        if logit_rules is not None:
+            logits = ops.logit_rules(logits, st.hist[::K], cache.length, T_p, logit_rules, out=logits)
         ops.beam_step(logits, st, cache.length)
 
         def step():
-            ops.beam_step(self._decode_tokens(cache, st.next_ids, rows=st.rows, beams=K)[:, -1], st, cache.length)
+            lg = self._decode_tokens(cache, st.next_ids, rows=st.rows, beams=K)[:, -1]
+            if logit_rules is not None:
+                lg = ops.logit_rules(lg, st.hist, cache.length, T_p, logit_rules, out=lg)
+            ops.beam_step(lg, st, cache.length)
 
         self._step_loop(cache, step, max_new_tokens - 1, graph)
         tokens, scores = ops.beam_finalize(st, max_new_tokens)
@@ -703,9 +750,19 @@ class WhisperMoP(nn.Module):
         (num_samples, P_b + max_new_tokens) tensors, and row r draws at its own token index (ops.sample_tokens_ragged), so its draws
         are those of a batch in which every prompt has its length.
         mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode): an item's samples share its cross cache
-        and its length."""
+        and its length.
+        Whisper's logit rules: with_logit_rules(rules).sample(...) takes the same arguments; sum_logprobs is then the log-softmax
+        of the FILTERED row (Whisper's convention: its filters precede the log-probabilities)."""
+        return self._sample(mel, prompt_ids, max_new_tokens, temperature, top_k, top_p, num_samples, eos_token_id, seed, graph, None)
+
+    def _sample(self, mel, prompt_ids, max_new_tokens, temperature, top_k, top_p, num_samples, eos_token_id, seed, graph,
+                logit_rules):
+        """sample's body.  logit_rules: every step's logits pass ops.logit_rules before the draw, inside the captured step, with
+        the samples' own token rows as history (the first draw's shared prompt logits with the rows [::num_samples] of them); the
+        log-probabilities are those of the filtered row.  None runs exactly the code without them"""
         mel_info, lens, B, T_p, n = self._decode_check(mel, prompt_ids, max_new_tokens, "sample", ("num_samples", num_samples))
         ops._sample_params(temperature, top_k, top_p, "sample")                 # argument errors before encoding
+        self._rules_check(logit_rules, eos_token_id, "sample")
         cap = T_p + max_new_tokens
         prompt_ids, logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, n)
         dev = prompt_ids.device
@@ -722,6 +779,8 @@ class WhisperMoP(nn.Module):
         eos = None if eos_token_id is None else int(eos_token_id)
 
         def draw(lg):
+            if logit_rules is not None:
+                lg = ops.logit_rules(lg, tokens if lg.shape[0] == B * n else tokens[::n], cache.length, T_p, logit_rules, out=lg)
             if cache.kv_start is None:
                 ops.sample_tokens(lg, cache.length, temperature, top_k, top_p, seed, out=(tok, lp))
             else:
@@ -751,6 +810,41 @@ class WhisperMoP(nn.Module):
         are unspecified."""
         _, gates = self.encode(mel)
         return gates
+
+
+class RuledDecoding:
+    """`WhisperMoP.with_logit_rules(rules)`: the model's three decoders with Whisper's logit rules (ops.LogitRules: the never-emit
+    list, blank suppression at the first generated position, the timestamp grammar) applied to every step's last-position logits
+    by ops.logit_rules, one HIP launch inside the step.  The decoders' own signatures do not change; each method here takes the
+    arguments of the method it names.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
+    (ValueError).  logit_rules None runs the plain decoder: no extra launch, no extra buffer."""
+
+    def __init__(self, model: WhisperMoP, logit_rules: Optional["ops.LogitRules"]):
+        self.model, self.logit_rules = model, logit_rules
+        model._rules_check(logit_rules, None, "with_logit_rules")
+
+    @torch.no_grad()
+    def generate(self, mel, prompt_ids, max_new_tokens: int, eos_token_id: Optional[int] = None, graph: bool = False, *,
+                 return_logits: bool = False):
+        """WhisperMoP.generate under the rules: the filter runs before the argmax, over a (B, cap) int32 device history kept for
+        it; return_logits returns the FILTERED logits, the ones that chose the token"""
+        return self.model._generate(mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, self.logit_rules)
+
+    @torch.no_grad()
+    def beam_search(self, mel, prompt_ids, max_new_tokens: int, num_beams: int, eos_token_id: Optional[int] = None,
+                    length_penalty: float = 1.0, graph: bool = False):
+        """WhisperMoP.beam_search under the rules: the filter runs before ops.beam_step, on the beams' own histories, so the
+        candidates' log-probabilities are those of the filtered rows"""
+        return self.model._beam_search(mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph,
+                                       self.logit_rules)
+
+    @torch.no_grad()
+    def sample(self, mel, prompt_ids, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+               num_samples: int = 1, eos_token_id: Optional[int] = None, seed: int = 0, graph: bool = False):
+        """WhisperMoP.sample under the rules: the filter runs before the draw; sum_logprobs adds the log-softmax of the FILTERED
+        row (Whisper's convention: its filters precede the log-probabilities)"""
+        return self.model._sample(mel, prompt_ids, max_new_tokens, temperature, top_k, top_p, num_samples, eos_token_id, seed,
+                                  graph, self.logit_rules)
 
 
 def create_whisper_mop(cfg: WhisperConfig) -> WhisperMoP:

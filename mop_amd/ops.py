@@ -2378,3 +2378,207 @@ def sample_tokens_ragged(logits: torch.Tensor, pos: torch.Tensor, pos_off: torch
         a = L.SampleRaggedArgs()
         a.base, a.pos_off = _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed), pos_off.data_ptr()
         return _sample_launch("mopk_sample_ragged", "sample_ragged", a, logits, R, out)
+
+
+# ---- Whisper's logit rules on last-position logits (mopk_logit_rules*; WhisperMoP decoding with logit rules) ----
+class LogitRules:
+    """Whisper's logit rules (the logit filters of OpenAI Whisper's decoding.py) for a vocabulary of `vocab_size` tokens.
+
+    suppress_tokens: ids never emitted.  suppress_at_begin: ids blocked only at the first generated position (Whisper: blank and
+    eot).  timestamp_begin: tb, the first timestamp token (None switches the timestamp rules off); eos_token_id is then required and
+    must be < tb.  no_timestamps_token_id: blocked whenever tb is set.  max_initial_timestamp_index: the first timestamp is at most
+    tb + this.  `logit_rules` documents the rules.  The constructor validates everything (ValueError) before any device work and
+    builds the (V,) uint8 table once (bit 0: never emitted, the no-timestamps token included; bit 1: blocked at the first position);
+    table(device) returns its copy on a device, made once per device (pass `device` to make it at construction).
+    A row that these lists block completely comes out all -inf: there is no guard."""
+
+    def __init__(self, vocab_size: int, suppress_tokens=(), suppress_at_begin=(), timestamp_begin: Optional[int] = None,
+                 eos_token_id: Optional[int] = None, no_timestamps_token_id: Optional[int] = None,
+                 max_initial_timestamp_index: Optional[int] = None, device=None):
+        def _int(x, name):
+            if isinstance(x, bool) or int(x) != x:
+                raise ValueError(f"LogitRules: {name} must be an integer, got {x!r}")
+            return int(x)
+
+        V = _int(vocab_size, "vocab_size")
+        if V < 2:
+            raise ValueError(f"LogitRules: vocab_size must be >= 2, got {V}")
+
+        def _id(x, name):
+            x = _int(x, name)
+            if not 0 <= x < V:
+                raise ValueError(f"LogitRules: {name} = {x} outside [0, vocab_size = {V})")
+            return x
+
+        self.vocab_size = V
+        self.suppress_tokens = tuple(_id(t, "suppress_tokens id") for t in suppress_tokens)
+        self.suppress_at_begin = tuple(_id(t, "suppress_at_begin id") for t in suppress_at_begin)
+        self.timestamp_begin = None if timestamp_begin is None else _id(timestamp_begin, "timestamp_begin")
+        self.eos_token_id = None if eos_token_id is None else _id(eos_token_id, "eos_token_id")
+        self.no_timestamps_token_id = None if no_timestamps_token_id is None else _id(no_timestamps_token_id,
+                                                                                      "no_timestamps_token_id")
+        self.max_initial_timestamp_index = None if max_initial_timestamp_index is None else _int(
+            max_initial_timestamp_index, "max_initial_timestamp_index")
+        if self.max_initial_timestamp_index is not None and self.max_initial_timestamp_index < 0:
+            raise ValueError(f"LogitRules: max_initial_timestamp_index must be >= 0, got {max_initial_timestamp_index}")
+        if self.timestamp_begin is not None:
+            if self.eos_token_id is None:
+                raise ValueError("LogitRules: timestamp_begin needs eos_token_id")
+            if not self.eos_token_id < self.timestamp_begin:
+                raise ValueError(f"LogitRules: needs eos_token_id < timestamp_begin, got {self.eos_token_id} >= {self.timestamp_begin}")
+        mask = torch.zeros(V, dtype=torch.uint8)
+        never = list(self.suppress_tokens)
+        if self.timestamp_begin is not None and self.no_timestamps_token_id is not None:
+            never.append(self.no_timestamps_token_id)
+        if never:
+            mask[torch.tensor(never, dtype=torch.long)] |= 1
+        if self.suppress_at_begin:
+            mask[torch.tensor(self.suppress_at_begin, dtype=torch.long)] |= 2
+        self._tables = {torch.device("cpu"): mask}
+        if device is not None:
+            self.table(device)
+
+    def table(self, device) -> torch.Tensor:
+        """the (V,) uint8 table on `device` (copied there once, without a host sync)"""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self._tables.get(device)
+        if t is None:
+            cpu = self._tables[torch.device("cpu")]
+            t = cpu.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else cpu.to(device)
+            self._tables[device] = t
+        return t
+
+
+def _lr_check(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: LogitRules, out, what: str) -> None:
+    """validate a logit-rules call before any device work"""
+    if not isinstance(rules, LogitRules):
+        raise ValueError(f"{what}: rules must be a LogitRules, got {type(rules).__name__}")
+    if logits.dim() != 2 or logits.shape[0] < 1 or not logits.dtype.is_floating_point:
+        raise ValueError(f"{what}: logits must be a floating (rows, V) tensor, got {tuple(logits.shape)} {logits.dtype}")
+    if logits.shape[1] != rules.vocab_size:
+        raise ValueError(f"{what}: logits have V = {logits.shape[1]}, the rules were built for vocab_size = {rules.vocab_size}")
+    if hist.dim() != 2 or hist.shape[0] != logits.shape[0] or hist.dtype.is_floating_point or hist.dtype == torch.bool:
+        raise ValueError(f"{what}: hist must be an integer ({logits.shape[0]}, T) tensor, got {tuple(hist.shape)} {hist.dtype}")
+    if isinstance(t0, bool) or int(t0) != t0 or not 0 <= t0 <= hist.shape[1]:
+        raise ValueError(f"{what}: t0 must be an integer in [0, T = {hist.shape[1]}], got {t0}")
+    if pos.numel() != 1 or pos.dtype.is_floating_point:
+        raise ValueError(f"{what}: pos must hold one integer, got shape {tuple(pos.shape)} {pos.dtype}")
+    if out is not None and (out.shape != logits.shape or out.dtype != logits.dtype or out.device != logits.device):
+        raise ValueError(f"{what}: out must match logits ({tuple(logits.shape)} {logits.dtype}), got {tuple(out.shape)} {out.dtype}")
+
+
+def logit_rules_torch(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: LogitRules, out=None):
+    """the restatement of `logit_rules` in torch ops (CPU or GPU, vectorised over rows, no host sync): the same rules in the same
+    order, rule 3e in fp32 as documented there (L = m + log(sum(exp(x - m))))"""
+    _lr_check(logits, hist, pos, t0, rules, out, "logit_rules_torch")
+    R, V = logits.shape
+    dev, T, t0 = logits.device, hist.shape[1], int(t0)
+    mask = rules.table(dev)
+    n = (pos.reshape(()).to(torch.long) - t0).clamp(0, T - t0)
+    first = n == 0
+    blocked = ((mask & 1) != 0) | (first & ((mask & 2) != 0))                      # rules 1 and 2
+    blocked = blocked.unsqueeze(0).expand(R, V)
+    tb = rules.timestamp_begin
+    if tb is not None:
+        g = F.pad(hist[:, t0:].to(torch.long), (0, 1))                             # one spare column: the gathers below stay inside
+        j = torch.arange(g.shape[1], device=dev)
+        at = lambda i: g.index_select(1, i.clamp_min(0).reshape(1)).squeeze(1)     # noqa: E731  g[:, i] at a device index
+        last = (n >= 1) & (at(n - 1) >= tb)
+        pen = (n < 2) | (at(n - 2) >= tb)
+        pair, lone = last & pen, last & ~pen
+        li = torch.where((g >= tb) & (j < n), j, -1).max(1).values                 # the last timestamp in sequence order
+        t = g.gather(1, li.clamp_min(0).unsqueeze(1)).squeeze(1)
+        text_lo = torch.where(lone, rules.eos_token_id, 0)                         # 3b: x[:eos]
+        ts_lo = torch.where(li >= 0, torch.where(lone, t, t + 1), tb)              # 3c: x[tb:lim]
+        ts_lo = torch.where(pair, V, ts_lo)                                        # 3b: x[tb:]
+        text_lo = torch.where(first, tb, text_lo)                                  # 3d: x[:tb]
+        k = rules.max_initial_timestamp_index
+        ts_hi = torch.where(first, V - 1 if k is None else min(tb + k, V - 1), V - 1)
+        v = torch.arange(V, device=dev).unsqueeze(0)
+        text = v < tb
+        blocked = blocked | torch.where(text, v < text_lo.unsqueeze(1), (v < ts_lo.unsqueeze(1)) | (v > ts_hi))
+        x = logits.float().masked_fill(blocked, float("-inf"))                     # 3e, on the row as masked so far
+        m = x[:, tb:].max(1).values
+        m0 = torch.where(m == float("-inf"), torch.zeros_like(m), m)
+        lse = m + torch.log(torch.exp(x[:, tb:] - m0.unsqueeze(1)).sum(1))          # -inf for an all-blocked side
+        blocked = blocked | ((lse > x[:, :tb].max(1).values).unsqueeze(1) & text)
+    y = logits.masked_fill(blocked, float("-inf"))
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
+def _lr_args(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: LogitRules, out) -> L.LogitRulesArgs:
+    a = L.LogitRulesArgs()
+    a.R, a.V, a.T, a.T0 = logits.shape[0], logits.shape[1], hist.shape[1], int(t0)
+    a.dtype = L.MOPK_BF16 if logits.dtype == torch.bfloat16 else L.MOPK_F32
+    a.tb = -1 if rules.timestamp_begin is None else rules.timestamp_begin
+    a.eos = 0 if rules.eos_token_id is None else rules.eos_token_id
+    k = rules.max_initial_timestamp_index
+    a.max_initial = -1 if k is None else min(k, a.V)
+    a.logits, a.logits_ld, a.out, a.out_ld = logits.data_ptr(), logits.stride(0), out.data_ptr(), out.stride(0)
+    a.hist, a.hist_ld, a.pos, a.mask = hist.data_ptr(), hist.stride(0), pos.data_ptr(), rules.table(logits.device).data_ptr()
+    return a
+
+
+def logit_rules_supported(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: LogitRules, out=None) -> bool:
+    """True if mopk_logit_rules takes this call: CUDA fp32 / bf16 logits (and out) with unit inner stride and a row stride >= V
+    (one row: any), a CUDA int32 hist with unit inner stride and a row stride >= T, an int32 device pos (the library's own query
+    decides the rest).  Raises ValueError on bad arguments."""
+    _lr_check(logits, hist, pos, t0, rules, out, "logit_rules_supported")
+    o = logits if out is None else out
+    R, V = logits.shape
+    for t in (logits, o):
+        if not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16) or t.stride(1) != 1 or (R > 1 and t.stride(0) < V):
+            return False
+    if not hist.is_cuda or hist.dtype != torch.int32 or (hist.shape[1] > 1 and hist.stride(1) != 1):
+        return False
+    if R > 1 and hist.stride(0) < hist.shape[1]:
+        return False
+    if not pos.is_cuda or pos.dtype != torch.int32:
+        return False
+    a = _lr_args(logits, hist, pos, t0, rules, o)
+    if R == 1:                                                                     # a single row: its strides are never used
+        a.logits_ld = a.out_ld = V
+        a.hist_ld = hist.shape[1]
+    return bool(L.lib().mopk_logit_rules_supported(C.byref(a)))
+
+
+def logit_rules(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: LogitRules, out=None):
+    """apply Whisper's logit rules to last-position logits -> the filtered logits, (R, V) in the logits' dtype: every entry is
+    the input's bits, or -inf ("blocked").  Inference only.
+
+    logits: (R, V) fp32 or bf16, any row stride.  hist: (R, T) int32 token histories (any row stride: a caller may pass
+    hist[::K]).  pos: (1,) int32 device tensor, the column of the token being chosen; t0: the first generated column (the same for
+    every row: ragged prompts are left-padded).  Per row, g = hist[r, t0:pos] are the n = pos - t0 tokens generated so far, and,
+    in this order:
+    1. every id of rules.suppress_tokens is blocked;
+    2. n == 0: every id of rules.suppress_at_begin is blocked;
+    3. with tb = rules.timestamp_begin set (timestamp tokens are the ids >= tb):
+       a. rules.no_timestamps_token_id, if given, is blocked;
+       b. last = n >= 1 and g[n-1] >= tb, pen = n < 2 or g[n-2] >= tb.  last and pen: x[tb:] is blocked (a pair is complete, text
+          follows); last and not pen: x[:eos] is blocked (a lone timestamp after text is followed by a timestamp or eos);
+       c. t = the last g[i] >= tb, if any: x[tb:lim] is blocked, lim = t if last and not pen, else t + 1 (never decreasing);
+       d. n == 0: x[:tb] is blocked (the first token is a timestamp), and x[tb + k + 1:] with k = max_initial_timestamp_index;
+       e. on the row as masked so far, in fp32: m = max x[tb:], L = m + log(sum(exp(x[tb:] - m))), M = max x[:tb] (an all-blocked
+          side gives -inf); L > M: x[:tb] is blocked (the softmax normaliser cancels on both sides).
+    A row that the caller's lists block completely comes out all -inf: there is no guard.  out: a static result buffer; it may be
+    `logits` itself.  Runs the HIP kernel (mopk_logit_rules: one launch) when logit_rules_supported() accepts the call, else
+    logit_rules_torch(); LAST_PATH["logit_rules"] records which.  No host sync; bitwise reproducible."""
+    _lr_check(logits, hist, pos, t0, rules, out, "logit_rules")
+    with torch.no_grad():
+        if not logit_rules_supported(logits, hist, pos, t0, rules, out):
+            LAST_PATH["logit_rules"] = L.PATH_GENERIC
+            return logit_rules_torch(logits, hist, pos, t0, rules, out)
+        if out is None:
+            out = torch.empty_like(logits, memory_format=torch.contiguous_format)
+        a = _lr_args(logits, hist, pos, t0, rules, out)
+        if logits.shape[0] == 1:
+            a.logits_ld = a.out_ld = logits.shape[1]
+            a.hist_ld = hist.shape[1]
+        LAST_PATH["logit_rules"] = L.PATH_FUSED
+        _launch("mopk_logit_rules", a, "logit_rules")
+        return out

@@ -12,6 +12,8 @@
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload sample-trace
     python tools/bench_whisper_decode.py --workload ragged --batch 8 --out profiles/whisper_ragged_bench.jsonl   # ragged prompts
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload ragged-trace
+    python tools/bench_whisper_decode.py --workload rules --out profiles/whisper_rules_bench.jsonl   # Whisper's logit rules
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_whisper_decode.py --workload rules-trace
 
 Model: d = 512, H = 8, 6 + 6 layers, T_a = 1500, vocab 51865 (Whisper-base-like), fp32 parameters under bf16 autocast, prompt 4,
 220 new tokens, B in {1, 8}.  Variants: (a) naive: decode(enc, whole prefix) per token; (b) cached eager: generate(); (c) cached +
@@ -30,6 +32,10 @@ n = 5 for rocprofv3; --stats then also prints the sampling kernel (sp_row_kernel
 Ragged: generate on B prompts of lengths spread over 1 ... 64 (a list: left-padded in one cache, WhisperDecodeCache.kv_start) against a
 uniform (B, 64) prompt, same model and length, eager and graph=True.  ragged-trace runs both with graphs at B = 8 for rocprofv3, so
 the ragged split kernel (da_split_kernel<..., START = true>) can be compared with the plain one (START = false) at the same shape.
+Rules: generate(graph=True) on the same model, prompt and length, B in {1, 8}: (a) no_rules; (b) rules_hip: with_logit_rules (Whisper's
+multilingual ids: timestamps from 50364, eot 50257, 88 suppressed ids) on the HIP kernel; (c) rules_torch: the same with
+ops.logit_rules forced onto ops.logit_rules_torch.  rules-trace runs (b) at B = 8 for rocprofv3; --stats then also prints the rules
+kernel (lr_row_kernel) next to the time to stream one bf16 row twice at the HBM rate.
 """
 from __future__ import annotations
 
@@ -283,6 +289,57 @@ def bench_ragged_trace(args):
     torch.cuda.synchronize()
 
 
+RULES_TB, RULES_EOS = 50364, 50257
+
+
+def _whisper_rules():
+    """a rule set of Whisper's size: timestamps from 50364, eot 50257, the specials 50258 ... 50363 and 88 - 106 other ids never
+    emitted, blank (220) and eot blocked at the first position, a first timestamp of at most 1 s (index 50)"""
+    from mop_amd.nn import LogitRules
+    never = list(range(1, 1000, 12)) + [i for i in range(50258, RULES_TB - 1) if i != 50363]
+    return LogitRules(VOCAB, suppress_tokens=never, suppress_at_begin=[220, RULES_EOS], timestamp_begin=RULES_TB,
+                      eos_token_id=RULES_EOS, no_timestamps_token_id=50363, max_initial_timestamp_index=50, device="cuda")
+
+
+def bench_rules(args):
+    import torch
+    from mop_amd import ops
+    m = _base_model()
+    d = m.with_logit_rules(_whisper_rules())
+    hip = ops.logit_rules
+    for B in args.batch:
+        mel = torch.randn(B, TA, NMELS, device="cuda")
+        prompt = torch.randint(0, RULES_EOS, (B, TP), device="cuda")
+        outs = {}
+        for name, fn, op in (("no_rules", lambda: m.generate(mel, prompt, NEW, graph=True), hip),
+                             ("rules_hip", lambda: d.generate(mel, prompt, NEW, graph=True), hip),
+                             ("rules_torch", lambda: d.generate(mel, prompt, NEW, graph=True), ops.logit_rules_torch)):
+            ops.logit_rules = op
+            try:
+                with torch.autocast("cuda", dtype=torch.bfloat16):
+                    ms = _time(lambda: outs.__setitem__(name, fn()), args.steps, args.warmup)
+            finally:
+                ops.logit_rules = hip
+            _emit(args, dict(workload="whisper_rules", variant=name, B=B, T_a=TA, T_p=TP, new_tokens=NEW, d=D, H=H, layers="6+6",
+                             vocab=VOCAB, dtype="bf16-autocast", total_ms=round(ms, 3), ms_per_token=round(ms / NEW, 4),
+                             steps=args.steps, warmup=args.warmup))
+        stamps = (outs["rules_hip"][:, TP:] >= RULES_TB).float().mean().item()
+        _emit(args, dict(workload="whisper_rules_agreement", B=B, timestamp_share=round(stamps, 3),
+                         rows_equal_hip_vs_torch=(outs["rules_hip"] == outs["rules_torch"]).all(1).float().mean().item()))
+
+
+def bench_rules_trace(args):
+    import torch
+    m = _base_model()
+    d = m.with_logit_rules(_whisper_rules())
+    mel = torch.randn(8, TA, NMELS, device="cuda")
+    prompt = torch.randint(0, RULES_EOS, (8, TP), device="cuda")
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        for _ in range(2):
+            d.generate(mel, prompt, NEW)
+    torch.cuda.synchronize()
+
+
 def bench_core_trace(args):
     import torch
     with torch.no_grad():
@@ -298,17 +355,19 @@ def stats(path):
     rows = list(csv.DictReader(open(path)))
     for r in rows:
         if "da_" in r["Name"] or "sdpa" in r["Name"] or "attention" in r["Name"].lower() or "fmha" in r["Name"].lower() \
-                or "bs_" in r["Name"] or "sp_row" in r["Name"]:
+                or "bs_" in r["Name"] or "sp_row" in r["Name"] or "lr_row" in r["Name"]:
             print(f"{float(r['AverageNs']) / 1e3:9.2f} us  x{r['Calls']:>5}  {r['Name'][:150]}")
     B, K, L = 8, 5, TP + NEW // 2
     print(f"beam bounds at B = {B}, K = {K}: logits {B * K * VOCAB * 2 / HBM_BPS * 1e6:.2f} us; row-indirect attention per layer at "
           f"L = {L}: {(2 * B * K * L * H * 64 * 2 + 4 * B * K * L) / HBM_BPS * 1e6:.2f} us")
+    print(f"logit rules: one bf16 row of {VOCAB} streamed twice (read + write) at the HBM rate: {2 * VOCAB * 2 / HBM_BPS * 1e6:.3f} us; "
+          f"{B} rows: {B * 2 * VOCAB * 2 / HBM_BPS * 1e6:.3f} us")
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=["generate", "core", "core-trace", "beam", "beam-trace", "sample", "sample-trace",
-                                           "ragged", "ragged-trace"], default="generate")
+                                           "ragged", "ragged-trace", "rules", "rules-trace"], default="generate")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
@@ -321,7 +380,7 @@ def main():
         return stats(args.stats)
     {"generate": bench_generate, "core": bench_core, "core-trace": bench_core_trace, "beam": bench_beam,
      "beam-trace": bench_beam_trace, "sample": bench_sample, "sample-trace": bench_sample_trace, "ragged": bench_ragged,
-     "ragged-trace": bench_ragged_trace}[args.workload](args)
+     "ragged-trace": bench_ragged_trace, "rules": bench_rules, "rules-trace": bench_rules_trace}[args.workload](args)
 
 
 if __name__ == "__main__":
