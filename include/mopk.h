@@ -718,6 +718,56 @@ typedef struct MopkLogitRulesArgs {
 int mopk_logit_rules_supported(const MopkLogitRulesArgs *a);         /* 1 if the kernel takes this call (V, dtype, strides, ids) */
 int mopk_logit_rules(const MopkLogitRulesArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * Token-level timestamps (WhisperMoP.align_tokens; inference only): Whisper's alignment filter and its dynamic time warping.
+ * (Added under version 118: new exports only; callers detect them with the _supported queries.)
+ *
+ * mopk_alignment_cost: probs (B, S, N, M) fp32, the cross-attention probabilities of S heads (rows: tokens, columns: audio frames),
+ * element (b, s, i, j) at probs + b * probs_sb + s * probs_ss + i * probs_sn + j.  nt = clamp(n_tokens[b], 0, N), nf =
+ * clamp(n_frames[b], 0, M): item b uses the rows i < nt and the columns j < nf only; nothing else is loaded.  Per head and column:
+ * mu = sum_i p / nt, sd = sqrt(sum_i (p - mu)^2 / nt) (two passes, fp32), z = (p - mu) / sd (no guard for sd = 0); z is
+ * median-filtered along j over `width` columns, reflect-padded by width / 2 inside the item's own nf columns (skipped when
+ * nf <= width / 2); cost[b, i, j] = -(sum_s filtered) / S, heads added in index order.  cost outside the window is not written.
+ * One workgroup of 1024 threads per (column tile, item) keeps one head's slab in LDS; no atomics, fixed reduction orders: bitwise
+ * reproducible.  Takes odd width <= 9 and N <= 1024.
+ *
+ * mopk_dtw_align: Whisper's dtw_cpu over rows [row0, clamp(n_rows[b], 0, N)) and columns [0, clamp(n_cols[b], 0, M)) of cost
+ * (B, N, M) fp32 (element (b, i, j) at cost + b * cost_sb + i * cost_ld + j).  1-based with a +inf border and D[0,0] = 0:
+ * c0 = D[i-1,j-1], c1 = D[i-1,j], c2 = D[i,j-1]; c0 < c1 && c0 < c2: step 0 (diagonal); else c1 < c0 && c1 < c2: step 1 (up); else
+ * step 2 (left); D[i,j] = x[i-1,j-1] + c, one fp32 add.  The path is walked back from the last cell (the first row goes left to
+ * column 0 and the first column up to the first row, which is what the rules give for finite costs).  starts[b, i] / ends[b, i]
+ * (B, N) int32: the first and last column of the path in row i; -1 for rows outside the range and for an item without rows or
+ * columns.  One workgroup per item, one thread per row over the anti-diagonals, a step code per cell in the workspace
+ * (mopk_dtw_workspace_bytes), the walk back on the device; no host synchronisation.  Takes N - row0 <= 1024. */
+typedef struct MopkAlignCostArgs {
+    int32_t B, S, N, M;
+    int32_t width;                       /* median filter width, odd */
+    int32_t reserved;                    /* 0 */
+    const float *probs;
+    int64_t probs_sb, probs_ss, probs_sn;   /* element strides of item, head and row; unit column stride */
+    const int32_t *n_tokens;             /* device (B) */
+    const int32_t *n_frames;             /* device (B) */
+    float *cost;                         /* (B, N, M) out */
+    int64_t cost_sb, cost_ld;            /* element strides of item and row, cost_ld >= M */
+} MopkAlignCostArgs;
+int mopk_alignment_cost_supported(const MopkAlignCostArgs *a);       /* 1 if the kernel takes this call (N, width, alignment) */
+int mopk_alignment_cost(const MopkAlignCostArgs *a, void *stream);
+
+typedef struct MopkDtwArgs {
+    int32_t B, N, M;
+    int32_t row0;                        /* first row of every item's range, 0 <= row0 < N */
+    const float *cost;
+    int64_t cost_sb, cost_ld;            /* element strides of item and row, cost_ld >= M */
+    const int32_t *n_rows;               /* device (B): the range's end row */
+    const int32_t *n_cols;               /* device (B) */
+    int32_t *starts;                     /* (B, N) out, contiguous */
+    int32_t *ends;                       /* (B, N) out, contiguous */
+    void *workspace;                     /* mopk_dtw_workspace_bytes(): one step code per cell */
+} MopkDtwArgs;
+int mopk_dtw_align_supported(const MopkDtwArgs *a);                  /* 1 if the kernel takes this call (N - row0, alignment) */
+size_t mopk_dtw_workspace_bytes(const MopkDtwArgs *a);               /* from B, N, M, row0 alone (no pointer is looked at) */
+int mopk_dtw_align(const MopkDtwArgs *a, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

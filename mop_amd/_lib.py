@@ -237,6 +237,24 @@ class LogitRulesArgs(C.Structure):
     ]
 
 
+class AlignCostArgs(C.Structure):
+    """MopkAlignCostArgs: Whisper's alignment filter (z-normalise, median-filter, average the heads) on cross-attention maps."""
+    _fields_ = [
+        ("B", C.c_int32), ("S", C.c_int32), ("N", C.c_int32), ("M", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
+        ("probs", _fp), ("probs_sb", C.c_int64), ("probs_ss", C.c_int64), ("probs_sn", C.c_int64),
+        ("n_tokens", _fp), ("n_frames", _fp), ("cost", _fp), ("cost_sb", C.c_int64), ("cost_ld", C.c_int64),
+    ]
+
+
+class DtwArgs(C.Structure):
+    """MopkDtwArgs: Whisper's dynamic time warping over per-item windows of a cost matrix, walked back on the device."""
+    _fields_ = [
+        ("B", C.c_int32), ("N", C.c_int32), ("M", C.c_int32), ("row0", C.c_int32),
+        ("cost", _fp), ("cost_sb", C.c_int64), ("cost_ld", C.c_int64), ("n_rows", _fp), ("n_cols", _fp),
+        ("starts", _fp), ("ends", _fp), ("workspace", _fp),
+    ]
+
+
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),
@@ -314,6 +332,11 @@ SYMBOLS = {
     "mopk_decode_attn_lens_fwd": (C.c_int, [C.POINTER(DecodeAttnLensArgs), C.c_void_p]),
     "mopk_logit_rules_supported": (C.c_int, [C.POINTER(LogitRulesArgs)]),
     "mopk_logit_rules": (C.c_int, [C.POINTER(LogitRulesArgs), C.c_void_p]),
+    "mopk_alignment_cost_supported": (C.c_int, [C.POINTER(AlignCostArgs)]),
+    "mopk_alignment_cost": (C.c_int, [C.POINTER(AlignCostArgs), C.c_void_p]),
+    "mopk_dtw_align_supported": (C.c_int, [C.POINTER(DtwArgs)]),
+    "mopk_dtw_workspace_bytes": (C.c_size_t, [C.POINTER(DtwArgs)]),
+    "mopk_dtw_align": (C.c_int, [C.POINTER(DtwArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -48,6 +48,15 @@ class EncodedAudio(NamedTuple):
     lens: Optional[torch.Tensor]
 
 
+class TokenAlignment(NamedTuple):
+    """token-level timestamps of a batch (`WhisperMoP.align_tokens`), in encoder frames, all on the device.
+    starts / ends: int32 (B, T): the first and last audio frame of token t of item b; -1 for the prompt, for the final token and
+    for the padding.  n_tokens: int32 (B,), the lengths of the token sequences."""
+    starts: torch.Tensor
+    ends: torch.Tensor
+    n_tokens: torch.Tensor
+
+
 class _Batch(NamedTuple):
     """what the prompt checks need to know of the audio batch when the mel is a list: shape[0] and device"""
     shape: Tuple[int, ...]
@@ -803,6 +812,101 @@ class WhisperMoP(nn.Module):
         if lens is not None:
             tokens = [tokens[b, :, T_p - lens[b]:] for b in range(B)]
         return tokens, sum_lp.view(B, n)
+
+    # ---- token-level timestamps; inference only ----
+    def _align_check(self, mel, tokens, prompt_len, alignment_heads, medfilt_width):
+        """align_tokens' argument checks -> (audio batch info, token lengths, (layer, head) pairs); ValueErrors before any device
+        work"""
+        what = "align_tokens"
+        alens = self._audio_check(mel, what)
+        info = mel if alens is None else _Batch((len(alens),), mel[0].device)
+        if isinstance(tokens, torch.Tensor):
+            if tokens.dim() != 2 or tokens.dtype.is_floating_point or tokens.dtype.is_complex or tokens.dtype == torch.bool:
+                raise ValueError(f"{what}: tokens must be an integer (B, T) tensor or a list of B 1-D token tensors, got "
+                                 f"{tuple(tokens.shape)} {tokens.dtype}")
+            if tokens.shape[0] != info.shape[0]:
+                raise ValueError(f"{what}: {tokens.shape[0]} token sequences for a batch of {info.shape[0]} mel inputs")
+            if tokens.device != info.device:
+                raise ValueError(f"{what}: tokens are on {tokens.device}, the mel on {info.device}")
+            lens = [int(tokens.shape[1])] * tokens.shape[0]
+        else:
+            lens = self._ragged_check(info, tokens, what)
+        if isinstance(prompt_len, bool) or not isinstance(prompt_len, int) or prompt_len < 0:
+            raise ValueError(f"{what}: prompt_len must be a non-negative int (one for the batch), got {prompt_len!r}")
+        if min(lens) < prompt_len + 2:
+            raise ValueError(f"{what}: every sequence needs the prompt, one token to align and a final token: the shortest has "
+                             f"{min(lens)} tokens, prompt_len = {prompt_len}")
+        if max(lens) > self.cfg.n_text_ctx:
+            raise ValueError(f"{what}: a sequence of {max(lens)} tokens exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        if isinstance(medfilt_width, bool) or not isinstance(medfilt_width, int) or medfilt_width < 1 or medfilt_width % 2 == 0:
+            raise ValueError(f"{what}: medfilt_width must be a positive odd int, got {medfilt_width!r}")
+        Ld, H = self.cfg.n_layer_dec, self.cfg.n_head
+        if alignment_heads is None:                                   # Whisper's default: every head of the upper half of the layers
+            heads = [(l, h) for l in range(Ld // 2, Ld) for h in range(H)]
+        else:
+            heads = [tuple(p) for p in alignment_heads]
+            if not heads:
+                raise ValueError(f"{what}: alignment_heads is empty")
+            for p in heads:
+                if len(p) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in p) or not (0 <= p[0] < Ld and 0 <= p[1] < H):
+                    raise ValueError(f"{what}: alignment head {p} is not a (decoder layer < {Ld}, head < {H}) pair")
+        return info, lens, heads
+
+    @torch.no_grad()
+    def align_tokens(self, mel, tokens, prompt_len: int, alignment_heads=None, medfilt_width: int = 7, *, return_cost: bool = False):
+        """token-level timestamps, as Whisper's find_alignment computes them -> TokenAlignment(starts, ends, n_tokens), all on the
+        device; no host sync.
+
+        mel: as for generate (a tensor, or a list of clips of different lengths).  tokens: a (B, T) integer tensor, or a list of B
+        1-D tensors of different lengths (right-padded here): each is the full sequence, the prompt of prompt_len tokens (one int
+        for the batch), the generated tokens and a final token.  alignment_heads: a list of (decoder layer, head) pairs; None takes
+        every head of the upper half of the decoder layers.
+        One teacher-forced decoder pass collects the selected layers' cross-attention queries; their probabilities over the item's
+        audio frames are formed in fp32 (softmax(q k^T / sqrt(dh)), frames >= the clip's length blocked), ops.alignment_cost
+        z-normalises them over the tokens, median-filters them over the frames (medfilt_width) and averages the heads, and
+        ops.dtw_align warps the rows [prompt_len, n_tokens - 1) of the negated map (Whisper drops the prompt and the final token)
+        onto the item's frames.  starts / ends (B, T) int32 are each token's first and last ENCODER frame (this model has no
+        convolutional downsampling: a frame is a mel frame), -1 outside the aligned rows.  return_cost=True also returns the
+        (B, T, T_audio) cost matrix the warping ran on."""
+        info, lens, heads = self._align_check(mel, tokens, prompt_len, alignment_heads, medfilt_width)
+        dev, B, T = info.device, len(lens), max(lens)
+        if isinstance(tokens, torch.Tensor):
+            ids = tokens
+        else:
+            ids = torch.zeros(B, T, dtype=tokens[0].dtype, device=dev)
+            for b, t in enumerate(tokens):
+                ids[b, :lens[b]] = t
+        n_tokens = torch.tensor(lens, dtype=torch.int32)
+        if dev.type == "cuda":                                         # an asynchronous copy: the host does not wait for it
+            n_tokens = n_tokens.pin_memory().to(dev, non_blocking=True)
+        enc = self.encode(mel)[0]
+        enc_out, audio_lens = _enc_parts(enc)
+        Ta = enc_out.shape[1]
+        layers = sorted({l for l, _ in heads})
+        queries, hooks = {}, []
+        for l in layers:                                               # cross_attn.q_proj(ln2(x)) of the selected layers
+            hooks.append(self.decoder[l].cross_attn.q_proj.register_forward_hook(
+                lambda mod, args, out, l=l: queries.__setitem__(l, out)))
+        try:
+            self.decode(enc, ids)
+        finally:
+            for h in hooks:
+                h.remove()
+        H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        ck, _ = self._cross_kv(enc_out)
+        q = torch.stack([queries[l].view(B, T, H, Dh)[:, :, h] for l, h in heads], dim=1).float()          # (B, S, T, dh)
+        k = torch.stack([ck[l][:, :, h] for l, h in heads], dim=1).float()                                 # (B, S, Ta, dh)
+        qk = torch.matmul(q, k.transpose(2, 3)) * Dh ** -0.5
+        if audio_lens is None:
+            n_frames = torch.full((B,), Ta, dtype=torch.int32, device=dev)
+        else:
+            n_frames = audio_lens
+            qk = qk.masked_fill((torch.arange(Ta, device=dev).unsqueeze(0) >= audio_lens.unsqueeze(1)).view(B, 1, 1, Ta), float("-inf"))
+        probs = torch.softmax(qk, dim=-1)
+        cost = ops.alignment_cost(probs, n_tokens, n_frames, medfilt_width)
+        starts, ends = ops.dtw_align(cost, n_tokens - 1, n_frames, row0=prompt_len)
+        out = TokenAlignment(starts, ends, n_tokens)
+        return (out, cost) if return_cost else out
 
     @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):

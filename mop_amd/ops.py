@@ -2582,3 +2582,231 @@ def logit_rules(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0:
         LAST_PATH["logit_rules"] = L.PATH_FUSED
         _launch("mopk_logit_rules", a, "logit_rules")
         return out
+
+
+# --------------------------------------------------------------------------------------
+# Token-level timestamps (WhisperMoP.align_tokens): Whisper's alignment filter and its dynamic time warping
+ALIGN_MAX_WIDTH = 9            # the filter kernel's odd median widths end here
+ALIGN_MAX_ROWS = 1024          # rows of a map the filter kernel holds in LDS / rows of one DTW (one thread each)
+
+
+def _lens_i32_check(t, B: int, dev, name: str, what: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.shape != (B,) or t.dtype.is_floating_point or t.dtype in (torch.bool,) or t.dtype.is_complex:
+        raise ValueError(f"{what}: {name} must be an integer ({B},) tensor, got "
+                         f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.device != dev:
+        raise ValueError(f"{what}: {name} is on {t.device}, the map on {dev}")
+
+
+def _ac_check(probs, n_tokens, n_frames, medfilt_width, what: str) -> None:
+    """validate an alignment_cost call before any device work"""
+    if not isinstance(probs, torch.Tensor) or probs.dim() != 4 or probs.dtype != torch.float32 or 0 in probs.shape:
+        raise ValueError(f"{what}: probs must be a non-empty fp32 (B, S, N, M) tensor, got "
+                         f"{(tuple(probs.shape), probs.dtype) if isinstance(probs, torch.Tensor) else type(probs).__name__}")
+    if probs.shape[3] > 1 and probs.stride(3) != 1:
+        raise ValueError(f"{what}: probs must have a unit inner stride, got strides {probs.stride()}")
+    if isinstance(medfilt_width, bool) or int(medfilt_width) != medfilt_width or medfilt_width < 1 or medfilt_width % 2 == 0:
+        raise ValueError(f"{what}: medfilt_width must be a positive odd integer, got {medfilt_width}")
+    _lens_i32_check(n_tokens, probs.shape[0], probs.device, "n_tokens", what)
+    _lens_i32_check(n_frames, probs.shape[0], probs.device, "n_frames", what)
+
+
+def alignment_cost_torch(probs: torch.Tensor, n_tokens: torch.Tensor, n_frames: torch.Tensor, medfilt_width: int = 7) -> torch.Tensor:
+    """the restatement of `alignment_cost` in torch ops (CPU or GPU, vectorised over the batch, no host sync): per head, mean and
+    population standard deviation over the item's rows (torch.where keeps everything outside the window out of them), z, a gather
+    of the reflect-padded windows, sort, the middle element; the heads are added in index order"""
+    _ac_check(probs, n_tokens, n_frames, medfilt_width, "alignment_cost_torch")
+    B, S, N, M = probs.shape
+    dev, h = probs.device, int(medfilt_width) // 2
+    nt = n_tokens.to(torch.long).clamp(0, N)
+    nf = n_frames.to(torch.long).clamp(0, M)
+    rows = (torch.arange(N, device=dev).unsqueeze(0) < nt.unsqueeze(1)).unsqueeze(2)           # (B, N, 1)
+    cnt = nt.to(torch.float32).view(B, 1, 1)
+    src = torch.arange(M, device=dev).view(1, M, 1) + torch.arange(-h, h + 1, device=dev).view(1, 1, -1)   # (1, M, width)
+    last = (nf - 1).view(B, 1, 1)
+    src = torch.where(src < 0, -src, src)
+    src = torch.where(src > last, 2 * last - src, src).clamp(0, M - 1)                         # columns >= nf: anything inside
+    filt = (nf > h).view(B, 1, 1)
+    total = torch.zeros(B, N, M, dtype=torch.float32, device=dev)
+    for s in range(S):
+        p = probs[:, s]
+        mu = torch.where(rows, p, 0.0).sum(1, keepdim=True) / cnt
+        d = torch.where(rows, p - mu, 0.0)
+        sd = ((d * d).sum(1, keepdim=True) / cnt).sqrt()
+        z = (p - mu) / sd
+        if h > 0:
+            win = torch.stack([z.gather(2, src[:, :, e].unsqueeze(1).expand(B, N, M)) for e in range(2 * h + 1)], dim=3)
+            z = torch.where(filt, win.sort(dim=3).values[..., h], z)
+        total = total + z
+    return -(total / S)
+
+
+def _ac_args(probs, n_tokens, n_frames, medfilt_width, cost) -> L.AlignCostArgs:
+    a = L.AlignCostArgs()
+    a.B, a.S, a.N, a.M = probs.shape
+    a.width, a.reserved = int(medfilt_width), 0
+    a.probs, a.probs_sb, a.probs_ss, a.probs_sn = probs.data_ptr(), probs.stride(0), probs.stride(1), probs.stride(2)
+    a.n_tokens, a.n_frames = n_tokens.data_ptr(), n_frames.data_ptr()
+    a.cost = 0 if cost is None else cost.data_ptr()
+    a.cost_sb, a.cost_ld = a.N * a.M, a.M
+    return a
+
+
+def alignment_cost_supported(probs: torch.Tensor, n_tokens: torch.Tensor, n_frames: torch.Tensor, medfilt_width: int = 7) -> bool:
+    """True if mopk_alignment_cost takes this call: CUDA tensors, int32 lengths, an odd width <= 9 and N <= 1024 (the library's own
+    query decides the rest).  Raises ValueError on bad arguments."""
+    _ac_check(probs, n_tokens, n_frames, medfilt_width, "alignment_cost_supported")
+    if not probs.is_cuda or n_tokens.dtype != torch.int32 or n_frames.dtype != torch.int32:
+        return False
+    if medfilt_width > ALIGN_MAX_WIDTH or probs.shape[2] > ALIGN_MAX_ROWS:
+        return False
+    a = _ac_args(probs, n_tokens, n_frames, medfilt_width, None)
+    a.cost = a.probs                                                               # a stand-in: only its alignment is looked at
+    return bool(L.lib().mopk_alignment_cost_supported(C.byref(a)))
+
+
+def alignment_cost(probs: torch.Tensor, n_tokens: torch.Tensor, n_frames: torch.Tensor, medfilt_width: int = 7) -> torch.Tensor:
+    """Whisper's alignment filter (timing.py, find_alignment) -> cost (B, N, M) fp32, the input of `dtw_align`.  Inference only.
+
+    probs: (B, S, N, M) fp32 cross-attention probabilities of S heads, rows are tokens and columns audio frames; unit inner stride,
+    the other strides are free.  n_tokens, n_frames: int32 (B,) device tensors, clamped into [0, N] and [0, M]: item b uses the rows
+    i < n_tokens[b] and the columns j < n_frames[b] only, nothing outside them is read (NaN there does not matter).  Per item, head
+    and column: mu and the population standard deviation sd over the item's rows (two passes), z = (p - mu) / sd (no guard for
+    sd = 0, as in Whisper); z is median-filtered along the columns with window medfilt_width, reflect-padded by medfilt_width // 2
+    inside the item's own n_frames[b] columns (skipped when n_frames[b] <= medfilt_width // 2, as in Whisper);
+    cost[b, i, j] = -mean over the heads, added in index order.  Entries outside the item's window are unspecified.
+    Runs the HIP kernel (mopk_alignment_cost: one launch) when alignment_cost_supported() accepts the call, else
+    alignment_cost_torch(); LAST_PATH["alignment_cost"] records which.  No host sync; bitwise reproducible."""
+    _ac_check(probs, n_tokens, n_frames, medfilt_width, "alignment_cost")
+    with torch.no_grad():
+        if not alignment_cost_supported(probs, n_tokens, n_frames, medfilt_width):
+            LAST_PATH["alignment_cost"] = L.PATH_GENERIC
+            return alignment_cost_torch(probs, n_tokens, n_frames, medfilt_width)
+        B, S, N, M = probs.shape
+        cost = torch.empty(B, N, M, dtype=torch.float32, device=probs.device)
+        LAST_PATH["alignment_cost"] = L.PATH_FUSED
+        _launch("mopk_alignment_cost", _ac_args(probs, n_tokens, n_frames, medfilt_width, cost), "alignment_cost")
+        return cost
+
+
+def _dtw_check(cost, n_rows, n_cols, row0, what: str) -> None:
+    """validate a dtw_align call before any device work"""
+    if not isinstance(cost, torch.Tensor) or cost.dim() != 3 or cost.dtype != torch.float32 or 0 in cost.shape:
+        raise ValueError(f"{what}: cost must be a non-empty fp32 (B, N, M) tensor, got "
+                         f"{(tuple(cost.shape), cost.dtype) if isinstance(cost, torch.Tensor) else type(cost).__name__}")
+    if cost.shape[2] > 1 and cost.stride(2) != 1:
+        raise ValueError(f"{what}: cost must have a unit inner stride, got strides {cost.stride()}")
+    if isinstance(row0, bool) or int(row0) != row0 or not 0 <= row0 < cost.shape[1]:
+        raise ValueError(f"{what}: row0 must be an integer in [0, N = {cost.shape[1]}), got {row0}")
+    _lens_i32_check(n_rows, cost.shape[0], cost.device, "n_rows", what)
+    _lens_i32_check(n_cols, cost.shape[0], cost.device, "n_cols", what)
+
+
+def dtw_align_torch(cost: torch.Tensor, n_rows: torch.Tensor, n_cols: torch.Tensor, row0: int = 0):
+    """the restatement of `dtw_align` in torch ops (CPU or GPU, vectorised over the batch, no host sync): one step per
+    anti-diagonal over the whole (N - row0, M) rectangle (a cell depends on smaller indices only, so every item's window comes out
+    as it would alone), then one step per cell of the longest possible path for the walk back"""
+    _dtw_check(cost, n_rows, n_cols, row0, "dtw_align_torch")
+    B, N, M = cost.shape
+    dev, row0 = cost.device, int(row0)
+    R = N - row0
+    inf = float("inf")
+    D = torch.full((B, R + 1, M + 1), inf, dtype=torch.float32, device=dev)
+    D[:, 0, 0] = 0.0
+    trace = torch.full((B, R, M), 2, dtype=torch.int8, device=dev)
+    x = cost[:, row0:]
+    for d in range(R + M - 1):
+        i = torch.arange(max(0, d - M + 1), min(R - 1, d) + 1, device=dev)
+        j = d - i
+        c0, c1, c2 = D[:, i, j], D[:, i, j + 1], D[:, i + 1, j]
+        diag = (c0 < c1) & (c0 < c2)
+        up = ~diag & (c1 < c0) & (c1 < c2)
+        c = torch.where(diag, c0, torch.where(up, c1, c2))
+        D[:, i + 1, j + 1] = x[:, i, j] + c
+        trace[:, i, j] = torch.where(diag, 0, torch.where(up, 1, 2)).to(torch.int8)
+    nr = n_rows.to(torch.long).clamp(0, N) - row0
+    nc = n_cols.to(torch.long).clamp(0, M)
+    live = (nr > 0) & (nc > 0)
+    i, j = (nr - 1).clamp_min(0), (nc - 1).clamp_min(0)
+    starts = torch.full((B, R), -1, dtype=torch.long, device=dev)
+    ends = torch.full((B, R), -1, dtype=torch.long, device=dev)
+    bi = torch.arange(B, device=dev)
+    for _ in range(R + M - 1):
+        cur_s, cur_e = starts[bi, i], ends[bi, i]
+        ends[bi, i] = torch.where(live & (cur_e < 0), j, cur_e)
+        starts[bi, i] = torch.where(live, j, cur_s)
+        code = trace[bi, i, j].to(torch.long)
+        code = torch.where(i == 0, 2, torch.where(j == 0, 1, code))               # the first row goes left, the first column up
+        live = live & ((i > 0) | (j > 0))
+        i = torch.where(live & (code != 2), i - 1, i)
+        j = torch.where(live & (code != 1), j - 1, j)
+    out_s = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+    out_e = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+    out_s[:, row0:] = starts.to(torch.int32)
+    out_e[:, row0:] = ends.to(torch.int32)
+    return out_s, out_e
+
+
+def _dtw_args(cost, n_rows, n_cols, row0) -> L.DtwArgs:
+    a = L.DtwArgs()
+    a.B, a.N, a.M = cost.shape
+    a.row0 = int(row0)
+    a.cost, a.cost_sb, a.cost_ld = cost.data_ptr(), cost.stride(0), cost.stride(1)
+    if a.B == 1:                                                                   # a single item: its stride is never used
+        a.cost_sb = a.N * a.cost_ld
+    a.n_rows, a.n_cols = n_rows.data_ptr(), n_cols.data_ptr()
+    return a
+
+
+def dtw_workspace_bytes(B: int, N: int, M: int, row0: int = 0) -> int:
+    """bytes of step codes one dtw_align call of this shape allocates (mopk_dtw_workspace_bytes; needs no GPU)"""
+    a = L.DtwArgs()
+    a.B, a.N, a.M, a.row0 = int(B), int(N), int(M), int(row0)
+    return int(L.lib().mopk_dtw_workspace_bytes(C.byref(a)))
+
+
+def dtw_align_supported(cost: torch.Tensor, n_rows: torch.Tensor, n_cols: torch.Tensor, row0: int = 0) -> bool:
+    """True if mopk_dtw_align takes this call: CUDA tensors, int32 lengths, a row stride >= M, item stride >= 0 and
+    N - row0 <= 1024 rows (the library's own query decides the rest).  Raises ValueError on bad arguments."""
+    _dtw_check(cost, n_rows, n_cols, row0, "dtw_align_supported")
+    if not cost.is_cuda or n_rows.dtype != torch.int32 or n_cols.dtype != torch.int32:
+        return False
+    B, N, M = cost.shape
+    if N - row0 > ALIGN_MAX_ROWS or (N > 1 and cost.stride(1) < M):
+        return False
+    a = _dtw_args(cost, n_rows, n_cols, row0)
+    if N == 1:
+        a.cost_ld = M
+    a.starts = a.ends = a.n_rows                                                   # stand-ins: only their alignment is looked at
+    return bool(L.lib().mopk_dtw_align_supported(C.byref(a)))
+
+
+def dtw_align(cost: torch.Tensor, n_rows: torch.Tensor, n_cols: torch.Tensor, row0: int = 0):
+    """Whisper's dynamic time warping (timing.py, dtw_cpu) with the walk back on the device -> (starts, ends), both (B, N) int32.
+    Inference only.
+
+    cost: (B, N, M) fp32, unit inner stride.  n_rows, n_cols: int32 (B,) device tensors, clamped into [0, N] and [0, M]: item b's
+    DTW runs over the rows [row0, n_rows[b]) and the columns [0, n_cols[b]); nothing outside them is read.  Whisper's rules
+    exactly, with one fp32 add per cell (1-based, a +inf border, D[0,0] = 0): c0 = D[i-1,j-1], c1 = D[i-1,j], c2 = D[i,j-1];
+    c0 < c1 and c0 < c2: the diagonal; else c1 < c0 and c1 < c2: up; else left; D[i,j] = x[i-1,j-1] + c.  The path is walked back
+    from the last cell; starts[b, i] / ends[b, i] are its first and last column in row i, so starts[i+1] is ends[i] or
+    ends[i] + 1, the first row starts at column 0 and the last row ends at n_cols[b] - 1.  Rows outside the range get -1, and so do
+    all rows of an item with no rows or no columns.
+    Runs the HIP kernel (mopk_dtw_align: one launch, one workspace of a step code per cell) when dtw_align_supported() accepts the
+    call, else dtw_align_torch(); LAST_PATH["dtw_align"] records which.  No host sync, no device-to-host copy."""
+    _dtw_check(cost, n_rows, n_cols, row0, "dtw_align")
+    with torch.no_grad():
+        if not dtw_align_supported(cost, n_rows, n_cols, row0):
+            LAST_PATH["dtw_align"] = L.PATH_GENERIC
+            return dtw_align_torch(cost, n_rows, n_cols, row0)
+        B, N, M = cost.shape
+        a = _dtw_args(cost, n_rows, n_cols, row0)
+        if N == 1:
+            a.cost_ld = M
+        starts = torch.empty(B, N, dtype=torch.int32, device=cost.device)
+        ends = torch.empty(B, N, dtype=torch.int32, device=cost.device)
+        ws = _bytes(L.lib().mopk_dtw_workspace_bytes(C.byref(a)), cost.device)
+        a.starts, a.ends, a.workspace = starts.data_ptr(), ends.data_ptr(), ws.data_ptr()
+        LAST_PATH["dtw_align"] = L.PATH_FUSED
+        _launch("mopk_dtw_align", a, "dtw_align")
+        return starts, ends
