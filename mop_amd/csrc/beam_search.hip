@@ -17,6 +17,7 @@
 // Ranking: larger score first, ties to the smaller flat index -- the same comparison in every list and merge, so the result does not
 // depend on how the vocabulary is sliced or on thread timing.
 #include "common.h"
+#include "row_helpers.h"
 
 namespace mopk {
 namespace {
@@ -28,18 +29,15 @@ constexpr int BS_TARGET_WG = 512;       // launch-A workgroups aimed for (two pe
 constexpr int BS_COLS = 256;            // history columns per reorder block
 constexpr int BS_SENT = 0x7fffffff;     // sentinel index: ranks after every real candidate
 
-// (as, ai) ranks before (bs, bi): larger score, ties to the smaller index
-__device__ __forceinline__ bool bs_before(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
-
 // insert into a sorted register list of NC entries (dropped when it ranks after the last one)
 template <int NC>
 __device__ __forceinline__ void bs_insert(float (&ls)[NC], int (&li)[NC], float s, int i) {
-    if (!bs_before(s, i, ls[NC - 1], li[NC - 1])) return;
+    if (!row_before(s, i, ls[NC - 1], li[NC - 1])) return;
     ls[NC - 1] = s;
     li[NC - 1] = i;
 #pragma unroll
     for (int j = NC - 1; j > 0; --j) {
-        if (bs_before(ls[j], li[j], ls[j - 1], li[j - 1])) {
+        if (row_before(ls[j], li[j], ls[j - 1], li[j - 1])) {
             const float ts = ls[j]; ls[j] = ls[j - 1]; ls[j - 1] = ts;
             const int ti = li[j]; li[j] = li[j - 1]; li[j - 1] = ti;
         }
@@ -66,7 +64,7 @@ __device__ __forceinline__ void bs_block_merge(const float (&ls)[NC], const int 
             int hi = ai[0], gi = bi[0];
 #pragma unroll
             for (int o = 0; o < NC; ++o) {
-                const bool ta = bs_before(hs, hi, gs, gi);
+                const bool ta = row_before(hs, hi, gs, gi);
                 ms[o] = ta ? hs : gs;
                 mi[o] = ta ? hi : gi;
                 if (o + 1 < NC) {
@@ -79,31 +77,6 @@ __device__ __forceinline__ void bs_block_merge(const float (&ls)[NC], const int 
         }
         __syncthreads();
     }
-}
-
-__device__ __forceinline__ void bs_unpack(const uint4 &u, float (&f)[8], unsigned short) {
-    const unsigned int w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __builtin_bit_cast(float, w[i] << 16);
-        f[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ void bs_unpack(const uint4 &u, float (&f)[4], float) {
-    f[0] = __builtin_bit_cast(float, u.x); f[1] = __builtin_bit_cast(float, u.y);
-    f[2] = __builtin_bit_cast(float, u.z); f[3] = __builtin_bit_cast(float, u.w);
-}
-
-// online (max, sum-exp): -inf entries add nothing
-__device__ __forceinline__ void bs_lse_add(float &m, float &l, float f) {
-    if (f > m) { l = l * expf(m - f) + 1.f; m = f; }             // m = -inf: l = 0 * 0 + 1
-    else if (f != -INFINITY) l += expf(f - m);
-}
-__device__ __forceinline__ void bs_lse_merge(float &m, float &l, float m2, float l2) {
-    const float M = fmaxf(m, m2);
-    if (M == -INFINITY) return;
-    l = (m == -INFINITY ? 0.f : l * expf(m - M)) + (m2 == -INFINITY ? 0.f : l2 * expf(m2 - M));
-    m = M;
 }
 
 struct BsWs {                                                   // workspace layout, rows = B * K
@@ -144,11 +117,11 @@ __global__ __launch_bounds__(BS_A_THREADS) void bs_rows_kernel(MopkBeamArgs a, i
     const uint4 *xv = (const uint4 *)(x + head);
     for (int u = u0 + tid; u < u1; u += BS_A_THREADS) {
         float f[EPV];
-        bs_unpack(xv[u], f, T());
+        row_unpack(xv[u], f, T());
         float fm = f[0];
 #pragma unroll
         for (int e = 0; e < EPV; ++e) {
-            bs_lse_add(m, l, f[e]);
+            row_lse_add(m, l, f[e]);
             fm = fmaxf(fm, f[e]);
         }
         if (fm < ls[LN - 1]) continue;                          // the common case once the list is full: nothing to insert
@@ -163,7 +136,7 @@ __global__ __launch_bounds__(BS_A_THREADS) void bs_rows_kernel(MopkBeamArgs a, i
     for (int t = tid; t < nh + nt; t += BS_A_THREADS) {
         const int e = t < nh ? t : tail0 + (t - nh);
         const float f = ld_as_f32<T>(x + e);
-        bs_lse_add(m, l, f);
+        row_lse_add(m, l, f);
         bs_insert(ls, li, f, e);
     }
 
@@ -174,7 +147,7 @@ __global__ __launch_bounds__(BS_A_THREADS) void bs_rows_kernel(MopkBeamArgs a, i
     for (int n = BS_A_THREADS / 2; n >= 1; n >>= 1) {
         if (tid < n) {
             float mm = rm[tid], ll = rl[tid];
-            bs_lse_merge(mm, ll, rm[tid + n], rl[tid + n]);
+            row_lse_merge(mm, ll, rm[tid + n], rl[tid + n]);
             rm[tid] = mm;
             rl[tid] = ll;
         }

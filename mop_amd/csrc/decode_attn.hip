@@ -37,6 +37,7 @@
 // instantiations are built in a unit of their own (-DMOPK_DECODE_LENS, mop_amd/build.py), which leaves the code of the others as
 // it was.
 #include "common.h"
+#include "row_helpers.h"
 
 namespace mopk {
 namespace {
@@ -59,19 +60,6 @@ struct DaCfg {
     static_assert(CH * R16 % DA_THREADS == 0, "staging must divide evenly");
     static_assert(KG >= 1, "PV phase needs one key group");
 };
-
-__device__ __forceinline__ void da_unpack(const uint4 &u, float (&f)[8], unsigned short) {
-    const unsigned int w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __builtin_bit_cast(float, w[i] << 16);
-        f[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ void da_unpack(const uint4 &u, float (&f)[4], float) {
-    f[0] = __builtin_bit_cast(float, u.x); f[1] = __builtin_bit_cast(float, u.y);
-    f[2] = __builtin_bit_cast(float, u.z); f[3] = __builtin_bit_cast(float, u.w);
-}
 
 // launch 1: one (row, chunk) partial; ROWS: keys / values through the row table; START: keys from kv_start[b] on; LENS: keys up to
 // kv_start[b] (the row's key count in the same argument)
@@ -153,7 +141,7 @@ __global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs
 #pragma unroll 4
             for (int c = 0; c < C::R16; ++c) {
                 float kf[C::EPV];
-                da_unpack(tile[j * C::PITCH + c], kf, T());
+                row_unpack(tile[j * C::PITCH + c], kf, T());
 #pragma unroll
                 for (int qi = 0; qi < C::QPT; ++qi) {
                     const int i = g + qi * C::NG;
@@ -212,11 +200,11 @@ __global__ __launch_bounds__(DA_THREADS) void da_split_kernel(MopkDecodeAttnArgs
                 const uint4 *vp = tile + j * C::PITCH + s * (8 / C::EPV);
                 float vf[8];
                 if constexpr (C::EPV == 8) {
-                    da_unpack(vp[0], vf, T());
+                    row_unpack(vp[0], vf, T());
                 } else {
                     float lo[4], hi[4];
-                    da_unpack(vp[0], lo, T());
-                    da_unpack(vp[1], hi, T());
+                    row_unpack(vp[0], lo, T());
+                    row_unpack(vp[1], hi, T());
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
                 }

@@ -10,6 +10,7 @@
 // the kept text tokens; every block reduction has a fixed order, so the result is bitwise reproducible.  Pass 2 streams it again
 // (it is in L2) and writes each entry's own bits or -inf; a thread rewrites only elements that it read itself, so out may be logits.
 #include "common.h"
+#include "row_helpers.h"
 
 namespace mopk {
 namespace {
@@ -17,17 +18,6 @@ namespace {
 constexpr int LR_THREADS = 1024;
 constexpr int LR_WAVES = LR_THREADS / WAVE;
 #define LR_UNROLL 16                                            // loads in flight per thread: each pass is bound by L2 latency
-
-__device__ __forceinline__ void lr_lse_add(float &m, float &l, float f) {
-    if (f > m) { l = l * expf(m - f) + 1.f; m = f; }
-    else if (f != -INFINITY) l += expf(f - m);
-}
-__device__ __forceinline__ void lr_lse_merge(float &m, float &l, float m2, float l2) {
-    const float M = fmaxf(m, m2);
-    if (M == -INFINITY) return;
-    l = (m == -INFINITY ? 0.f : l * expf(m - M)) + (m2 == -INFINITY ? 0.f : l2 * expf(m2 - M));
-    m = M;
-}
 
 template <typename T> __device__ __forceinline__ T lr_ninf();
 template <> __device__ __forceinline__ float lr_ninf<float>() { return -INFINITY; }
@@ -93,13 +83,13 @@ __global__ __launch_bounds__(LR_THREADS) void lr_row_kernel(MopkLogitRulesArgs a
         for (int v = tid; v < V; v += LR_THREADS) {
             const float f = ld_as_f32<T>(x + v);
             if (!row.blocked(v, a.mask[v])) {
-                if (v >= row.tb) lr_lse_add(m, l, f);
+                if (v >= row.tb) row_lse_add(m, l, f);
                 else mt = fmaxf(mt, f);
             }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            lr_lse_merge(m, l, __shfl_xor(m, o, 64), __shfl_xor(l, o, 64));
+            row_lse_merge(m, l, __shfl_xor(m, o, 64), __shfl_xor(l, o, 64));
             mt = fmaxf(mt, __shfl_xor(mt, o, 64));
         }
         const int w = tid / WAVE;
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(LR_THREADS) void lr_row_kernel(MopkLogitRulesArgs a
         l = s.wl[0];
         mt = s.wt[0];
         for (int i = 1; i < LR_WAVES; ++i) {
-            lr_lse_merge(m, l, s.wm[i], s.wl[i]);
+            row_lse_merge(m, l, s.wm[i], s.wl[i]);
             mt = fmaxf(mt, s.wt[i]);
         }
         const float L = m == -INFINITY ? -INFINITY : m + logf(l);

@@ -15,6 +15,7 @@
 // left-padded batch; nothing else changes.  That instantiation is compiled in a unit of its own (-DMOPK_SAMPLE_RAGGED, a second
 // object of this file), so the OFF = false kernel's code is the same as before the flag existed.
 #include "common.h"
+#include "row_helpers.h"
 
 namespace mopk {
 namespace {
@@ -41,19 +42,6 @@ __device__ __forceinline__ uint32_t sp_key(float z) {
 }
 __device__ __forceinline__ uint64_t sp_mass(float z, float mz) { return (uint64_t)(expf(z - mz) * SP_MASS_SCALE); }
 
-__device__ __forceinline__ void sp_lse_add(float &m, float &l, float f) {
-    if (f > m) { l = l * expf(m - f) + 1.f; m = f; }
-    else if (f != -INFINITY) l += expf(f - m);
-}
-__device__ __forceinline__ void sp_lse_merge(float &m, float &l, float m2, float l2) {
-    const float M = fmaxf(m, m2);
-    if (M == -INFINITY) return;
-    l = (m == -INFINITY ? 0.f : l * expf(m - M)) + (m2 == -INFINITY ? 0.f : l2 * expf(m2 - M));
-    m = M;
-}
-// (as, ai) ranks before (bs, bi): larger score, ties to the smaller index
-__device__ __forceinline__ bool sp_before(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
-
 struct SpLds {
     uint64_t hist[SP_BINS];
     float wf[SP_WAVES], wg[SP_WAVES];
@@ -67,13 +55,13 @@ struct SpLds {
 // block-wide reductions: shuffles inside a wave, then the SP_WAVES wave results in wave order (every thread gets the result)
 __device__ __forceinline__ void sp_block_lse(float &m, float &l, SpLds &s) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sp_lse_merge(m, l, __shfl_xor(m, o, 64), __shfl_xor(l, o, 64));
+    for (int o = 32; o > 0; o >>= 1) row_lse_merge(m, l, __shfl_xor(m, o, 64), __shfl_xor(l, o, 64));
     const int w = threadIdx.x / WAVE;
     if ((threadIdx.x & 63) == 0) { s.wf[w] = m; s.wg[w] = l; }
     __syncthreads();
     m = s.wf[0];
     l = s.wg[0];
-    for (int i = 1; i < SP_WAVES; ++i) sp_lse_merge(m, l, s.wf[i], s.wg[i]);
+    for (int i = 1; i < SP_WAVES; ++i) row_lse_merge(m, l, s.wf[i], s.wg[i]);
     __syncthreads();
 }
 __device__ __forceinline__ void sp_block_best(float &sc, int &v, SpLds &s) {
@@ -81,7 +69,7 @@ __device__ __forceinline__ void sp_block_best(float &sc, int &v, SpLds &s) {
     for (int o = 32; o > 0; o >>= 1) {
         const float s2 = __shfl_xor(sc, o, 64);
         const int v2 = __shfl_xor(v, o, 64);
-        if (sp_before(s2, v2, sc, v)) { sc = s2; v = v2; }
+        if (row_before(s2, v2, sc, v)) { sc = s2; v = v2; }
     }
     const int w = threadIdx.x / WAVE;
     if ((threadIdx.x & 63) == 0) { s.wf[w] = sc; s.wi[w] = v; }
@@ -89,7 +77,7 @@ __device__ __forceinline__ void sp_block_best(float &sc, int &v, SpLds &s) {
     sc = s.wf[0];
     v = s.wi[0];
     for (int i = 1; i < SP_WAVES; ++i)
-        if (sp_before(s.wf[i], s.wi[i], sc, v)) { sc = s.wf[i]; v = s.wi[i]; }
+        if (row_before(s.wf[i], s.wi[i], sc, v)) { sc = s.wf[i]; v = s.wi[i]; }
     __syncthreads();
 }
 __device__ __forceinline__ uint64_t sp_block_sum(uint64_t x, SpLds &s) {
@@ -193,7 +181,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_row_kernel(MopkSampleArgs a, co
 #pragma unroll SP_UNROLL
     for (int v = tid; v < V; v += SP_THREADS) {
         const float f = row.x_at(v);
-        sp_lse_add(m0, l0, f);
+        row_lse_add(m0, l0, f);
         if (row.greedy) {
             if (f > best || bv == 0x7fffffff) { best = f; bv = v; }       // v rises: the first maximum of this thread
         } else {
@@ -227,7 +215,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_row_kernel(MopkSampleArgs a, co
             const float z = row.z(v);
             if (sp_key(z) >= thr) {
                 const float sc = z + sp_gumbel(rh, v);
-                if (sp_before(sc, v, best, bv)) { best = sc; bv = v; }
+                if (row_before(sc, v, best, bv)) { best = sc; bv = v; }
             }
         }
     }

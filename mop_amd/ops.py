@@ -1961,6 +1961,20 @@ def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     return _da_run("decode_attention_lens", q, k_cache, v_cache, kv_lens=kv_lens, nk=nk)
 
 
+# ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, alignment_cost, dtw_align ----
+# Each is its _*_check (every ValueError, once per call), its _*_accept (the tensor-side tests, then the args struct, built once,
+# if the library's _supported query takes it, else None), then the torch restatement, or the outputs into that struct and _row_launch.
+def _row_launch(a, sym: str, key: str, dev=None, ws_sym: Optional[str] = None) -> None:
+    """the tail the six ops share: the library's workspace query `ws_sym` where the op has one (the buffer goes into the struct,
+    into its base for a struct that wraps one), LAST_PATH, and the launch of `sym` on the accepted struct `a`"""
+    if ws_sym is not None:
+        n = getattr(L.lib(), ws_sym)(C.byref(a))
+        ws = _bytes(n, dev) if n else None
+        getattr(a, "base", a).workspace = _ptr(ws)
+    LAST_PATH[key] = L.PATH_FUSED
+    _launch(sym, a, key)
+
+
 # ---- batched beam search on device state (mopk_beam_*; WhisperMoP.beam_search) ----
 BEAM_MAX_K = 8
 
@@ -2020,14 +2034,20 @@ def _beam_args(logits: torch.Tensor, st: BeamState, pos: torch.Tensor) -> L.Beam
     return a
 
 
+def _beam_accept(logits: torch.Tensor, state: BeamState, pos: torch.Tensor):
+    """the args struct (without the workspace) of a call that mopk_beam_* take, None of one they refuse"""
+    if not logits.is_cuda or logits.dtype not in (torch.float32, torch.bfloat16) or logits.stride(-1) != 1:
+        return None
+    if not pos.is_cuda or pos.dtype != torch.int32 or pos.numel() != 1:
+        return None
+    a = _beam_args(logits, state, pos)
+    return a if L.lib().mopk_beam_supported(C.byref(a)) else None
+
+
 def beam_step_supported(logits: torch.Tensor, state: BeamState, pos: torch.Tensor) -> bool:
     """True if mopk_beam_* take this call: CUDA fp32 / bf16 logits with unit inner stride, 1 <= K <= 8, V >= 2, an int32 device pos
     (the library's own query decides the rest)"""
-    if not logits.is_cuda or logits.dtype not in (torch.float32, torch.bfloat16) or logits.stride(-1) != 1:
-        return False
-    if not pos.is_cuda or pos.dtype != torch.int32 or pos.numel() != 1:
-        return False
-    return bool(L.lib().mopk_beam_supported(C.byref(_beam_args(logits, state, pos))))
+    return _beam_accept(logits, state, pos) is not None
 
 
 def _beam_check(logits: torch.Tensor, state: BeamState, pos: torch.Tensor, what: str):
@@ -2134,15 +2154,11 @@ def beam_step(logits: torch.Tensor, state: BeamState, pos: torch.Tensor) -> None
     _beam_check(logits, state, pos, "beam_step")
     _require_gpu(logits, "beam_step")
     with torch.no_grad():
-        if not beam_step_supported(logits, state, pos):
+        a = _beam_accept(logits, state, pos)
+        if a is None:
             LAST_PATH["beam_step"] = L.PATH_GENERIC
             return beam_step_torch(logits, state, pos)
-        lib = L.lib()
-        a = _beam_args(logits, state, pos)
-        ws = _bytes(lib.mopk_beam_workspace_bytes(C.byref(a)), logits.device)
-        a.workspace = ws.data_ptr()
-        LAST_PATH["beam_step"] = L.PATH_FUSED
-        _launch("mopk_beam_step", a, "beam_step")
+        _row_launch(a, "mopk_beam_step", "beam_step", logits.device, "mopk_beam_workspace_bytes")
 
 
 def beam_finalize(state: BeamState, n_new: int):
@@ -2278,32 +2294,46 @@ def _sample_args(logits: torch.Tensor, pos: torch.Tensor, R: int, n: int, inv_t,
     return a
 
 
-def _sample_launch(stem: str, key: str, a, logits: torch.Tensor, R: int, out):
-    """the tail sample_tokens and sample_tokens_ragged share: out buffers, workspace and launch of `stem`_step on the args `a`"""
-    if out is None:
-        out = (torch.empty(R, dtype=torch.int32, device=logits.device), torch.empty(R, dtype=torch.float32, device=logits.device))
-    base = getattr(a, "base", a)
-    base.tokens, base.logprobs = out[0].data_ptr(), out[1].data_ptr()
-    ws_bytes = getattr(L.lib(), stem + "_workspace_bytes")(C.byref(a))
-    ws = _bytes(ws_bytes, logits.device) if ws_bytes else None
-    base.workspace = _ptr(ws)
-    LAST_PATH[key] = L.PATH_FUSED
-    _launch(stem + "_step", a, key)
-    return out[0], out[1]
+def _sample_accept(logits, pos, chk, top_k, seed, out, pos_off=None):
+    """the args struct of a call that mopk_sample_* (with pos_off: mopk_sample_ragged_*, whose query starts with the plain op's check
+    on the same base, so that one is not asked as well) take, None of one they refuse.  chk: _sample_check's (R, n, inv_t, tp)."""
+    if not logits.is_cuda or logits.dtype not in (torch.float32, torch.bfloat16) or logits.stride(-1) != 1:
+        return None
+    if not pos.is_cuda or pos.dtype != torch.int32:
+        return None
+    if out is not None and not all(t.is_cuda and t.is_contiguous() for t in out):
+        return None
+    a = _sample_args(logits, pos, *chk, top_k, seed)
+    if pos_off is None:
+        return a if L.lib().mopk_sample_supported(C.byref(a)) else None
+    if not pos_off.is_cuda or pos_off.dtype != torch.int32 or not pos_off.is_contiguous():
+        return None
+    r = L.SampleRaggedArgs()
+    r.base, r.pos_off = a, pos_off.data_ptr()                                      # a copy: from here on the fields are r.base's
+    return r if L.lib().mopk_sample_ragged_supported(C.byref(r)) else None
+
+
+def _sample_run(stem: str, key: str, logits, pos, pos_off, chk, top_k, seed, out):
+    """the body sample_tokens and sample_tokens_ragged (pos_off given) share, after their check"""
+    with torch.no_grad():
+        a = _sample_accept(logits, pos, chk, top_k, seed, out, pos_off)
+        if a is None:
+            LAST_PATH[key] = L.PATH_GENERIC
+            return _sample_torch(logits, pos, pos_off, *chk, top_k, seed, out)
+        if out is None:
+            out = tuple(torch.empty(chk[0], dtype=dt, device=logits.device) for dt in (torch.int32, torch.float32))
+        base = getattr(a, "base", a)
+        base.tokens, base.logprobs = out[0].data_ptr(), out[1].data_ptr()
+        _row_launch(a, stem + "_step", key, logits.device, stem + "_workspace_bytes")
+        return out[0], out[1]
 
 
 def sample_tokens_supported(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                             seed: int = 0, out=None) -> bool:
     """True if mopk_sample_* take this call: CUDA fp32 / bf16 logits with unit inner stride, an int32 device pos, contiguous CUDA
     out buffers (the library's own query decides the rest: 2 <= V <= 2^24).  Raises ValueError on bad arguments."""
-    R, n, inv_t, tp = _sample_check(logits, pos, temperature, top_k, top_p, out, "sample_tokens_supported")
-    if not logits.is_cuda or logits.dtype not in (torch.float32, torch.bfloat16) or logits.stride(-1) != 1:
-        return False
-    if not pos.is_cuda or pos.dtype != torch.int32:
-        return False
-    if out is not None and not all(t.is_cuda and t.is_contiguous() for t in out):
-        return False
-    return bool(L.lib().mopk_sample_supported(C.byref(_sample_args(logits, pos, R, n, inv_t, tp, top_k, seed))))
+    chk = _sample_check(logits, pos, temperature, top_k, top_p, out, "sample_tokens_supported")
+    return _sample_accept(logits, pos, chk, top_k, seed, out) is not None
 
 
 def sample_tokens(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
@@ -2325,12 +2355,8 @@ def sample_tokens(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 
     - logprobs[r] = log_softmax(float(x))[token] on the unscaled, unfiltered row (Whisper's sum_logprobs convention).
     out: static (tokens, logprobs) buffers, written in place (graph capture).  Runs the HIP kernel (mopk_sample_step) when
     sample_tokens_supported() accepts the call, else sample_tokens_torch(); LAST_PATH["sample"] records which.  No host sync."""
-    R, n, inv_t, tp = _sample_check(logits, pos, temperature, top_k, top_p, out, "sample_tokens")
-    with torch.no_grad():
-        if not sample_tokens_supported(logits, pos, temperature, top_k, top_p, seed, out):
-            LAST_PATH["sample"] = L.PATH_GENERIC
-            return sample_tokens_torch(logits, pos, temperature, top_k, top_p, seed, out)
-        return _sample_launch("mopk_sample", "sample", _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed), logits, R, out)
+    chk = _sample_check(logits, pos, temperature, top_k, top_p, out, "sample_tokens")
+    return _sample_run("mopk_sample", "sample", logits, pos, None, chk, top_k, seed, out)
 
 
 # ---- sampling of a left-padded ragged batch (mopk_sample_ragged_*; WhisperMoP.sample with per-row prompt lengths) ----
@@ -2353,14 +2379,8 @@ def sample_tokens_ragged_supported(logits: torch.Tensor, pos: torch.Tensor, pos_
                                    top_k: int = 0, top_p: float = 1.0, seed: int = 0, out=None) -> bool:
     """True if mopk_sample_ragged_* take this call: what sample_tokens_supported asks, and a contiguous CUDA int32 pos_off.
     Raises ValueError on bad arguments."""
-    R, n, inv_t, tp = _sample_ragged_check(logits, pos, pos_off, temperature, top_k, top_p, out, "sample_tokens_ragged_supported")
-    if not pos_off.is_cuda or pos_off.dtype != torch.int32 or not pos_off.is_contiguous():
-        return False
-    if not sample_tokens_supported(logits, pos, temperature, top_k, top_p, seed, out):
-        return False
-    a = L.SampleRaggedArgs()
-    a.base, a.pos_off = _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed), pos_off.data_ptr()
-    return bool(L.lib().mopk_sample_ragged_supported(C.byref(a)))
+    chk = _sample_ragged_check(logits, pos, pos_off, temperature, top_k, top_p, out, "sample_tokens_ragged_supported")
+    return _sample_accept(logits, pos, chk, top_k, seed, out, pos_off) is not None
 
 
 def sample_tokens_ragged(logits: torch.Tensor, pos: torch.Tensor, pos_off: torch.Tensor, temperature: float = 1.0, top_k: int = 0,
@@ -2370,14 +2390,8 @@ def sample_tokens_ragged(logits: torch.Tensor, pos: torch.Tensor, pos_off: torch
     alone.  pos_off: int32 (R,) device tensor, R the number of sampled rows.  With pos_off = 0 the draw is bitwise that of
     sample_tokens.  Runs the HIP kernel (mopk_sample_ragged_step) when sample_tokens_ragged_supported() accepts the call, else
     sample_tokens_ragged_torch(); LAST_PATH["sample_ragged"] records which.  No host sync."""
-    R, n, inv_t, tp = _sample_ragged_check(logits, pos, pos_off, temperature, top_k, top_p, out, "sample_tokens_ragged")
-    with torch.no_grad():
-        if not sample_tokens_ragged_supported(logits, pos, pos_off, temperature, top_k, top_p, seed, out):
-            LAST_PATH["sample_ragged"] = L.PATH_GENERIC
-            return sample_tokens_ragged_torch(logits, pos, pos_off, temperature, top_k, top_p, seed, out)
-        a = L.SampleRaggedArgs()
-        a.base, a.pos_off = _sample_args(logits, pos, R, n, inv_t, tp, top_k, seed), pos_off.data_ptr()
-        return _sample_launch("mopk_sample_ragged", "sample_ragged", a, logits, R, out)
+    chk = _sample_ragged_check(logits, pos, pos_off, temperature, top_k, top_p, out, "sample_tokens_ragged")
+    return _sample_run("mopk_sample_ragged", "sample_ragged", logits, pos, pos_off, chk, top_k, seed, out)
 
 
 # ---- Whisper's logit rules on last-position logits (mopk_logit_rules*; WhisperMoP decoding with logit rules) ----
@@ -2521,7 +2535,26 @@ def _lr_args(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: in
     a.max_initial = -1 if k is None else min(k, a.V)
     a.logits, a.logits_ld, a.out, a.out_ld = logits.data_ptr(), logits.stride(0), out.data_ptr(), out.stride(0)
     a.hist, a.hist_ld, a.pos, a.mask = hist.data_ptr(), hist.stride(0), pos.data_ptr(), rules.table(logits.device).data_ptr()
+    if a.R == 1:                                                                   # a single row: its strides are never used
+        a.logits_ld = a.out_ld = a.V
+        a.hist_ld = a.T
     return a
+
+
+def _lr_accept(logits, hist, pos, t0, rules, out):
+    """the args struct of a call that mopk_logit_rules takes, None of one it refuses; out None: `logits` stands in for the result"""
+    o = logits if out is None else out
+    R, V = logits.shape
+    for t in (logits, o):
+        if not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16) or t.stride(1) != 1 or (R > 1 and t.stride(0) < V):
+            return None
+    T = hist.shape[1]
+    if not hist.is_cuda or hist.dtype != torch.int32 or (T > 1 and hist.stride(1) != 1) or (R > 1 and hist.stride(0) < T):
+        return None
+    if not pos.is_cuda or pos.dtype != torch.int32:
+        return None
+    a = _lr_args(logits, hist, pos, t0, rules, o)
+    return a if L.lib().mopk_logit_rules_supported(C.byref(a)) else None
 
 
 def logit_rules_supported(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: LogitRules, out=None) -> bool:
@@ -2529,22 +2562,7 @@ def logit_rules_supported(logits: torch.Tensor, hist: torch.Tensor, pos: torch.T
     (one row: any), a CUDA int32 hist with unit inner stride and a row stride >= T, an int32 device pos (the library's own query
     decides the rest).  Raises ValueError on bad arguments."""
     _lr_check(logits, hist, pos, t0, rules, out, "logit_rules_supported")
-    o = logits if out is None else out
-    R, V = logits.shape
-    for t in (logits, o):
-        if not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16) or t.stride(1) != 1 or (R > 1 and t.stride(0) < V):
-            return False
-    if not hist.is_cuda or hist.dtype != torch.int32 or (hist.shape[1] > 1 and hist.stride(1) != 1):
-        return False
-    if R > 1 and hist.stride(0) < hist.shape[1]:
-        return False
-    if not pos.is_cuda or pos.dtype != torch.int32:
-        return False
-    a = _lr_args(logits, hist, pos, t0, rules, o)
-    if R == 1:                                                                     # a single row: its strides are never used
-        a.logits_ld = a.out_ld = V
-        a.hist_ld = hist.shape[1]
-    return bool(L.lib().mopk_logit_rules_supported(C.byref(a)))
+    return _lr_accept(logits, hist, pos, t0, rules, out) is not None
 
 
 def logit_rules(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: LogitRules, out=None):
@@ -2570,17 +2588,14 @@ def logit_rules(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0:
     logit_rules_torch(); LAST_PATH["logit_rules"] records which.  No host sync; bitwise reproducible."""
     _lr_check(logits, hist, pos, t0, rules, out, "logit_rules")
     with torch.no_grad():
-        if not logit_rules_supported(logits, hist, pos, t0, rules, out):
+        a = _lr_accept(logits, hist, pos, t0, rules, out)
+        if a is None:
             LAST_PATH["logit_rules"] = L.PATH_GENERIC
             return logit_rules_torch(logits, hist, pos, t0, rules, out)
         if out is None:
             out = torch.empty_like(logits, memory_format=torch.contiguous_format)
-        a = _lr_args(logits, hist, pos, t0, rules, out)
-        if logits.shape[0] == 1:
-            a.logits_ld = a.out_ld = logits.shape[1]
-            a.hist_ld = hist.shape[1]
-        LAST_PATH["logit_rules"] = L.PATH_FUSED
-        _launch("mopk_logit_rules", a, "logit_rules")
+            a.out, a.out_ld = out.data_ptr(), out.stride(0)                        # in place of the stand-in
+        _row_launch(a, "mopk_logit_rules", "logit_rules")
         return out
 
 
@@ -2641,28 +2656,32 @@ def alignment_cost_torch(probs: torch.Tensor, n_tokens: torch.Tensor, n_frames: 
     return -(total / S)
 
 
-def _ac_args(probs, n_tokens, n_frames, medfilt_width, cost) -> L.AlignCostArgs:
+def _ac_args(probs, n_tokens, n_frames, medfilt_width) -> L.AlignCostArgs:
     a = L.AlignCostArgs()
     a.B, a.S, a.N, a.M = probs.shape
     a.width, a.reserved = int(medfilt_width), 0
     a.probs, a.probs_sb, a.probs_ss, a.probs_sn = probs.data_ptr(), probs.stride(0), probs.stride(1), probs.stride(2)
     a.n_tokens, a.n_frames = n_tokens.data_ptr(), n_frames.data_ptr()
-    a.cost = 0 if cost is None else cost.data_ptr()
     a.cost_sb, a.cost_ld = a.N * a.M, a.M
     return a
+
+
+def _ac_accept(probs, n_tokens, n_frames, medfilt_width):
+    """the args struct of a call that mopk_alignment_cost takes, None of one it refuses; a.cost holds a stand-in"""
+    if not probs.is_cuda or n_tokens.dtype != torch.int32 or n_frames.dtype != torch.int32:
+        return None
+    if medfilt_width > ALIGN_MAX_WIDTH or probs.shape[2] > ALIGN_MAX_ROWS:
+        return None
+    a = _ac_args(probs, n_tokens, n_frames, medfilt_width)
+    a.cost = a.probs                                                               # a stand-in: only its alignment is looked at
+    return a if L.lib().mopk_alignment_cost_supported(C.byref(a)) else None
 
 
 def alignment_cost_supported(probs: torch.Tensor, n_tokens: torch.Tensor, n_frames: torch.Tensor, medfilt_width: int = 7) -> bool:
     """True if mopk_alignment_cost takes this call: CUDA tensors, int32 lengths, an odd width <= 9 and N <= 1024 (the library's own
     query decides the rest).  Raises ValueError on bad arguments."""
     _ac_check(probs, n_tokens, n_frames, medfilt_width, "alignment_cost_supported")
-    if not probs.is_cuda or n_tokens.dtype != torch.int32 or n_frames.dtype != torch.int32:
-        return False
-    if medfilt_width > ALIGN_MAX_WIDTH or probs.shape[2] > ALIGN_MAX_ROWS:
-        return False
-    a = _ac_args(probs, n_tokens, n_frames, medfilt_width, None)
-    a.cost = a.probs                                                               # a stand-in: only its alignment is looked at
-    return bool(L.lib().mopk_alignment_cost_supported(C.byref(a)))
+    return _ac_accept(probs, n_tokens, n_frames, medfilt_width) is not None
 
 
 def alignment_cost(probs: torch.Tensor, n_tokens: torch.Tensor, n_frames: torch.Tensor, medfilt_width: int = 7) -> torch.Tensor:
@@ -2679,13 +2698,13 @@ def alignment_cost(probs: torch.Tensor, n_tokens: torch.Tensor, n_frames: torch.
     alignment_cost_torch(); LAST_PATH["alignment_cost"] records which.  No host sync; bitwise reproducible."""
     _ac_check(probs, n_tokens, n_frames, medfilt_width, "alignment_cost")
     with torch.no_grad():
-        if not alignment_cost_supported(probs, n_tokens, n_frames, medfilt_width):
+        a = _ac_accept(probs, n_tokens, n_frames, medfilt_width)
+        if a is None:
             LAST_PATH["alignment_cost"] = L.PATH_GENERIC
             return alignment_cost_torch(probs, n_tokens, n_frames, medfilt_width)
-        B, S, N, M = probs.shape
-        cost = torch.empty(B, N, M, dtype=torch.float32, device=probs.device)
-        LAST_PATH["alignment_cost"] = L.PATH_FUSED
-        _launch("mopk_alignment_cost", _ac_args(probs, n_tokens, n_frames, medfilt_width, cost), "alignment_cost")
+        cost = torch.empty(a.B, a.N, a.M, dtype=torch.float32, device=probs.device)
+        a.cost = cost.data_ptr()                                                   # in place of the stand-in
+        _row_launch(a, "mopk_alignment_cost", "alignment_cost")
         return cost
 
 
@@ -2752,6 +2771,8 @@ def _dtw_args(cost, n_rows, n_cols, row0) -> L.DtwArgs:
     a.B, a.N, a.M = cost.shape
     a.row0 = int(row0)
     a.cost, a.cost_sb, a.cost_ld = cost.data_ptr(), cost.stride(0), cost.stride(1)
+    if a.N == 1:                                                                   # a single row: its stride is never used
+        a.cost_ld = a.M
     if a.B == 1:                                                                   # a single item: its stride is never used
         a.cost_sb = a.N * a.cost_ld
     a.n_rows, a.n_cols = n_rows.data_ptr(), n_cols.data_ptr()
@@ -2765,20 +2786,23 @@ def dtw_workspace_bytes(B: int, N: int, M: int, row0: int = 0) -> int:
     return int(L.lib().mopk_dtw_workspace_bytes(C.byref(a)))
 
 
+def _dtw_accept(cost, n_rows, n_cols, row0):
+    """the args struct of a call that mopk_dtw_align takes, None of one it refuses; a.starts and a.ends hold stand-ins"""
+    if not cost.is_cuda or n_rows.dtype != torch.int32 or n_cols.dtype != torch.int32:
+        return None
+    B, N, M = cost.shape
+    if N - row0 > ALIGN_MAX_ROWS or (N > 1 and cost.stride(1) < M):
+        return None
+    a = _dtw_args(cost, n_rows, n_cols, row0)
+    a.starts = a.ends = a.n_rows                                                   # stand-ins: only their alignment is looked at
+    return a if L.lib().mopk_dtw_align_supported(C.byref(a)) else None
+
+
 def dtw_align_supported(cost: torch.Tensor, n_rows: torch.Tensor, n_cols: torch.Tensor, row0: int = 0) -> bool:
     """True if mopk_dtw_align takes this call: CUDA tensors, int32 lengths, a row stride >= M, item stride >= 0 and
     N - row0 <= 1024 rows (the library's own query decides the rest).  Raises ValueError on bad arguments."""
     _dtw_check(cost, n_rows, n_cols, row0, "dtw_align_supported")
-    if not cost.is_cuda or n_rows.dtype != torch.int32 or n_cols.dtype != torch.int32:
-        return False
-    B, N, M = cost.shape
-    if N - row0 > ALIGN_MAX_ROWS or (N > 1 and cost.stride(1) < M):
-        return False
-    a = _dtw_args(cost, n_rows, n_cols, row0)
-    if N == 1:
-        a.cost_ld = M
-    a.starts = a.ends = a.n_rows                                                   # stand-ins: only their alignment is looked at
-    return bool(L.lib().mopk_dtw_align_supported(C.byref(a)))
+    return _dtw_accept(cost, n_rows, n_cols, row0) is not None
 
 
 def dtw_align(cost: torch.Tensor, n_rows: torch.Tensor, n_cols: torch.Tensor, row0: int = 0):
@@ -2796,17 +2820,12 @@ def dtw_align(cost: torch.Tensor, n_rows: torch.Tensor, n_cols: torch.Tensor, ro
     call, else dtw_align_torch(); LAST_PATH["dtw_align"] records which.  No host sync, no device-to-host copy."""
     _dtw_check(cost, n_rows, n_cols, row0, "dtw_align")
     with torch.no_grad():
-        if not dtw_align_supported(cost, n_rows, n_cols, row0):
+        a = _dtw_accept(cost, n_rows, n_cols, row0)
+        if a is None:
             LAST_PATH["dtw_align"] = L.PATH_GENERIC
             return dtw_align_torch(cost, n_rows, n_cols, row0)
-        B, N, M = cost.shape
-        a = _dtw_args(cost, n_rows, n_cols, row0)
-        if N == 1:
-            a.cost_ld = M
-        starts = torch.empty(B, N, dtype=torch.int32, device=cost.device)
-        ends = torch.empty(B, N, dtype=torch.int32, device=cost.device)
-        ws = _bytes(L.lib().mopk_dtw_workspace_bytes(C.byref(a)), cost.device)
-        a.starts, a.ends, a.workspace = starts.data_ptr(), ends.data_ptr(), ws.data_ptr()
-        LAST_PATH["dtw_align"] = L.PATH_FUSED
-        _launch("mopk_dtw_align", a, "dtw_align")
+        starts = torch.empty(a.B, a.N, dtype=torch.int32, device=cost.device)
+        ends = torch.empty(a.B, a.N, dtype=torch.int32, device=cost.device)
+        a.starts, a.ends = starts.data_ptr(), ends.data_ptr()                      # in place of the stand-ins
+        _row_launch(a, "mopk_dtw_align", "dtw_align", cost.device, "mopk_dtw_workspace_bytes")
         return starts, ends

@@ -64,6 +64,22 @@ def test_dtw_kernel_strides_lengths_and_empty_items(row0):
     assert ops.LAST_PATH["dtw_align"] == _lib.PATH_FUSED and torch.equal(s3, s) and torch.equal(e3, e)
 
 
+def test_dtw_kernel_single_row_and_single_item_strides():
+    """N == 1: the row stride is never used, B == 1: the item stride is never used; values the kernel would refuse (a row stride
+    below M) or misread (an item stride of 0) for more rows / items pass"""
+    from mop_amd import ops
+    cost, nr, nc = dtw_case(1, 7, 3, B=2, n_cols=[7, 5])
+    view = cost.cuda().as_strided((2, 1, 7), (7, 1, 1))
+    s, e = _dtw_both(view, nr.cuda(), nc.cuda(), what="N == 1, row stride 1")
+    print(f"dtw N == 1, row stride 1: path {ops.LAST_PATH['dtw_align']}")
+    assert s.tolist() == [[0], [0]] and e.tolist() == [[6], [4]]
+    cost, nr, nc = dtw_case(3, 7, 4, n_rows=[3], n_cols=[6])
+    view = cost.cuda().as_strided((1, 3, 7), (0, 7, 1))
+    s, e = _dtw_both(view, nr.cuda(), nc.cuda(), what="B == 1, item stride 0")
+    print(f"dtw B == 1, item stride 0: path {ops.LAST_PATH['dtw_align']}")
+    check_boundaries(s[0].cpu(), e[0].cpu(), 0, 3, 6)
+
+
 @pytest.mark.parametrize("N,M", [(6, 9), (9, 6), (40, 70), (130, 200)])
 def test_dtw_kernel_finds_the_planted_staircase(N, M):
     cost, starts, ends = staircase(N, M, N + M)

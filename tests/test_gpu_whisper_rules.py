@@ -87,6 +87,30 @@ def test_strides_aliasing_and_the_device_position(dtype):
     assert not torch.equal(results[T0], results[T0 + 2]) and not torch.equal(results[T0 + 2], plain)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_single_row_with_degenerate_row_strides(dtype):
+    """R = 1: the row strides of logits, out and hist are never used, so any value passes (0 and 1 here, which the kernels would
+    refuse for more rows), with the result allocated by the op and with out = logits"""
+    from mop_amd import _lib, ops
+    V, tb, eos, T = 1027, 900, 890, 8                        # one full pass of the kernel's 1024 threads plus a tail
+    kw = rule_sets(V, tb, eos)["full"]
+    rules = ops.LogitRules(V, **kw)
+    x, hist, pos = build_case(V, tb, eos, 1, dtype, ["x", tb + 3, tb + 3, "x"], 41, "cuda", cap=T)
+    assert ref_rules(x, hist.cpu(), int(pos), T0, V, **kw)[1][0] >= NEAR_TIE        # the case itself is no near tie of rule 3e
+    for stride in (0, 1):
+        view, hview = x.clone().as_strided((1, V), (stride, 1)), hist.as_strided((1, T), (stride, 1))
+        ref = ops.logit_rules_torch(view, hview, pos, T0, rules)
+        assert bool(torch.isneginf(ref[0, tb:tb + 3]).all()) and not bool(torch.isneginf(ref[0, tb + 4:V - 2]).any())
+        got = ops.logit_rules(view, hview, pos, T0, rules)
+        print(f"single row, {dtype}, row stride {stride}, out=None: path {ops.LAST_PATH['logit_rules']}")
+        assert ops.LAST_PATH["logit_rules"] == _lib.PATH_FUSED
+        assert got.data_ptr() != view.data_ptr() and got.stride() == (V, 1) and torch.equal(got, ref)
+        same = ops.logit_rules(view, hview, pos, T0, rules, out=view)
+        print(f"single row, {dtype}, row stride {stride}, out=logits: path {ops.LAST_PATH['logit_rules']}")
+        assert ops.LAST_PATH["logit_rules"] == _lib.PATH_FUSED
+        assert same.data_ptr() == view.data_ptr() and torch.equal(view, ref)
+
+
 def test_kernel_is_bitwise_reproducible():
     from mop_amd import _lib, ops
     V, tb, eos = SHAPES["v51865"]
