@@ -768,6 +768,43 @@ int mopk_dtw_align_supported(const MopkDtwArgs *a);                  /* 1 if the
 size_t mopk_dtw_workspace_bytes(const MopkDtwArgs *a);               /* from B, N, M, row0 alone (no pointer is looked at) */
 int mopk_dtw_align(const MopkDtwArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * Whisper's segment and seek arithmetic on decoded token rows (WhisperMoP.transcribe; the rules of OpenAI Whisper's
+ * transcribe.py).  (Added under version 118: new exports only; callers detect it with mopk_timestamp_segments_supported.)
+ * Row r (0 <= r < R) reads tokens + r * tokens_ld + T0 ...: S = T - T0 generated columns.  e = the first column that holds eos
+ * (S if none), g = the n = e tokens before it, ts[i] = g[i] >= tb (a timestamp token: tb + i is frame i * f of the window),
+ * w = max(window[r], 1).
+ *   1. n == 0: no segment, advance = w.
+ *   2. single_end = n >= 2 && !ts[n-2] && ts[n-1];  C = { i : 1 <= i < n, ts[i-1] && ts[i] }, ascending.
+ *   3. C not empty: the cuts are C, then n if single_end.  With p the cut before (0 at first), cut c closes the segment of the
+ *      token columns [T0 + p, T0 + c): start = (g[p] - tb) * f (0 when g[p] is no timestamp: p = 0 only), end = (g[c-1] - tb) * f.
+ *      advance = w if single_end, else (g[max C - 1] - tb) * f; the tokens after the last cut are in no segment.
+ *   4. C empty: one segment [T0, T0 + n), start = 0, end = w, or (s - tb) * f when a timestamp exists and the last one, s, is
+ *      not tb itself; advance = w.
+ *   5. advance is clamped into [1, w].
+ * starts / ends / tok_begin / tok_end (R, S) int32, contiguous: row r's n_segments[r] segments in order, -1 behind them (written by
+ * the same launch).  The products are taken in 32 bits (callers keep (id - tb) * f below 2^31).  One workgroup per row, one
+ * thread per generated column: wave ballots and one LDS exchange per block reduction and for the exclusive scan that numbers
+ * the cuts; every output word has one writer; integers only, no atomics, no workspace, no host synchronisation.
+ * Takes T - T0 <= 1024. */
+typedef struct MopkTimestampSegmentsArgs {
+    int32_t R;                           /* rows */
+    int32_t T;                           /* columns of tokens */
+    int32_t T0;                          /* first generated column, 0 <= T0 < T */
+    int32_t tb;                          /* first timestamp token */
+    int32_t eos;                         /* 0 <= eos < tb */
+    int32_t f;                           /* frames per timestamp step, >= 1 */
+    const int32_t *tokens;               /* device (R rows of T) int32 */
+    int64_t tokens_ld;                   /* element stride between rows, >= T */
+    const int32_t *window;               /* device (R): frames of row r's window */
+    int32_t *starts, *ends;              /* (R, T - T0) out: frames relative to the window start */
+    int32_t *tok_begin, *tok_end;        /* (R, T - T0) out: columns of tokens, the end exclusive */
+    int32_t *n_segments;                 /* (R) out */
+    int32_t *advance;                    /* (R) out: frames to move the window by, in [1, w] */
+} MopkTimestampSegmentsArgs;
+int mopk_timestamp_segments_supported(const MopkTimestampSegmentsArgs *a);   /* 1 if the kernel takes this call (T - T0, alignment) */
+int mopk_timestamp_segments(const MopkTimestampSegmentsArgs *a, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

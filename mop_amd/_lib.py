@@ -255,6 +255,15 @@ class DtwArgs(C.Structure):
     ]
 
 
+class TimestampSegmentsArgs(C.Structure):
+    """MopkTimestampSegmentsArgs: Whisper's segment and seek arithmetic on decoded token rows (WhisperMoP.transcribe)."""
+    _fields_ = [
+        ("R", C.c_int32), ("T", C.c_int32), ("T0", C.c_int32), ("tb", C.c_int32), ("eos", C.c_int32), ("f", C.c_int32),
+        ("tokens", _fp), ("tokens_ld", C.c_int64), ("window", _fp), ("starts", _fp), ("ends", _fp),
+        ("tok_begin", _fp), ("tok_end", _fp), ("n_segments", _fp), ("advance", _fp),
+    ]
+
+
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),
@@ -337,6 +346,8 @@ SYMBOLS = {
     "mopk_dtw_align_supported": (C.c_int, [C.POINTER(DtwArgs)]),
     "mopk_dtw_workspace_bytes": (C.c_size_t, [C.POINTER(DtwArgs)]),
     "mopk_dtw_align": (C.c_int, [C.POINTER(DtwArgs), C.c_void_p]),
+    "mopk_timestamp_segments_supported": (C.c_int, [C.POINTER(TimestampSegmentsArgs)]),
+    "mopk_timestamp_segments": (C.c_int, [C.POINTER(TimestampSegmentsArgs), C.c_void_p]),
 }
 
 _lib = None

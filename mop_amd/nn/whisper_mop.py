@@ -57,6 +57,16 @@ class TokenAlignment(NamedTuple):
     n_tokens: torch.Tensor
 
 
+class Transcript(NamedTuple):
+    """one clip's long-form transcription (`WhisperMoP.transcribe`), all on the device.  starts / ends: int32 (n,), the segments'
+    first and last frame, in frames of the CLIP; tokens: (m,) in prompt_ids' dtype, the segments' tokens end to end, timestamp
+    tokens included; offsets: int32 (n + 1,): segment i's tokens are tokens[offsets[i]:offsets[i + 1]]."""
+    starts: torch.Tensor
+    ends: torch.Tensor
+    tokens: torch.Tensor
+    offsets: torch.Tensor
+
+
 class _Batch(NamedTuple):
     """what the prompt checks need to know of the audio batch when the mel is a list: shape[0] and device"""
     shape: Tuple[int, ...]
@@ -907,6 +917,110 @@ class WhisperMoP(nn.Module):
         starts, ends = ops.dtw_align(cost, n_tokens - 1, n_frames, row0=prompt_len)
         out = TokenAlignment(starts, ends, n_tokens)
         return (out, cost) if return_cost else out
+
+    # ---- long-form transcription; inference only ----
+    def _transcribe_check(self, mel, prompt_ids, logit_rules, max_new_tokens, window, frames_per_timestamp, num_beams,
+                          length_penalty):
+        """transcribe's argument checks -> (the clips as a list of (T_b, n_mels) tensors, the window in frames).  What transcribe
+        adds is checked here; the clips' first windows and the prompt, one row per clip, then pass _decode_check, as every
+        window's decoder call will.  ValueErrors before any device work"""
+        what = "transcribe"
+        n_ctx = self.cfg.n_audio_ctx
+        if isinstance(mel, torch.Tensor):
+            if mel.dim() != 3:
+                raise ValueError(f"{what}: mel must be a (B, T, n_mels) tensor or a non-empty list of B (T_b, n_mels) tensors, got "
+                                 f"{tuple(mel.shape)}")
+            mel = list(mel.unbind(0))
+        if window is None:
+            window = n_ctx
+        if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= n_ctx:
+            raise ValueError(f"{what}: window must be an int in [1, n_audio_ctx = {n_ctx}], got {window!r}")
+        for name, v in (("frames_per_timestamp", frames_per_timestamp), ("max_new_tokens", max_new_tokens), ("num_beams", num_beams)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{what}: {name} must be an int >= 1, got {v!r}")
+        if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or length_penalty != length_penalty:
+            raise ValueError(f"{what}: length_penalty must be a number, got {length_penalty!r}")
+        if not isinstance(logit_rules, ops.LogitRules) or logit_rules.timestamp_begin is None:
+            raise ValueError(f"{what}: logit_rules must be an ops.LogitRules with timestamp_begin set (the segments are cut at "
+                             f"the timestamp tokens), got {type(logit_rules).__name__}")
+        self._rules_check(logit_rules, None, what)
+        if (not isinstance(prompt_ids, torch.Tensor) or prompt_ids.dim() not in (1, 2) or prompt_ids.dtype.is_floating_point
+                or prompt_ids.dtype.is_complex or prompt_ids.dtype == torch.bool):
+            raise ValueError(f"{what}: prompt_ids must be an integer (T_p,) or (B, T_p) tensor, got "
+                             f"{(tuple(prompt_ids.shape), prompt_ids.dtype) if isinstance(prompt_ids, torch.Tensor) else type(prompt_ids).__name__}")
+        first = [m[:window] if isinstance(m, torch.Tensor) and m.dim() == 2 else m for m in mel] if isinstance(mel, (list, tuple)) else mel
+        B = len(first) if isinstance(first, (list, tuple)) else 0
+        prompts = prompt_ids if prompt_ids.dim() == 2 else prompt_ids.unsqueeze(0).expand(B, -1)
+        mel_info = self._decode_check(first, prompts, max_new_tokens, what, ("num_beams", num_beams), 2 if num_beams > 1 else 0)[0]
+        if prompt_ids.device != mel_info.device:
+            raise ValueError(f"{what}: prompt_ids are on {prompt_ids.device}, the mel on {mel_info.device}")
+        return list(mel), window
+
+    @torch.no_grad()
+    def transcribe(self, mel, prompt_ids: torch.Tensor, logit_rules: "ops.LogitRules", max_new_tokens: int, *,
+                   window: Optional[int] = None, frames_per_timestamp: int = 1, num_beams: int = 1, length_penalty: float = 1.0,
+                   graph: bool = False) -> List[Transcript]:
+        """long-form transcription, Whisper's transcribe loop over windows for a batch of clips -> a list of B Transcript(starts,
+        ends, tokens, offsets), all on the device.
+
+        mel: a list of B (T_b, n_mels) clips, T_b >= 1 and NOT bounded by n_audio_ctx, or a (B, T, n_mels) tensor.  window: the
+        frames decoded at a time, at most n_audio_ctx (the default).  prompt_ids: a (T_p,) tensor, or (B, T_p): the same
+        start-of-transcript sequence opens every window of an item.  logit_rules: an ops.LogitRules with timestamp_begin set; the
+        eos token is its eos_token_id.  frames_per_timestamp: see ops.timestamp_segments.
+        Each item keeps a host integer seek_b, 0 at first.  While any seek_b < T_b: the windows mel_b[seek_b:seek_b + window] of
+        the items still running go, as a list of clips of different lengths, through with_logit_rules(logit_rules).generate (or
+        .beam_search with num_beams > 1; graph is passed on); ops.timestamp_segments cuts the decoded rows into segments and
+        gives each row's advance, in one launch; ONE (A, 3) int32 copy to pinned host memory brings advance, n_segments and the
+        number of tokens the segments span back (the only synchronisation the loop adds to the decoders' own: with graph=True
+        every window's decoder call opens its capture with a device synchronise; the host needs the third to size the token
+        views); seek_b += advance, and the window's segments join item b's transcript, their frames shifted by the window's
+        seek_b.  advance >= 1, so the loop ends after at most T_b windows.  The tokens behind a
+        window's last cut are in no segment: the next window starts at that cut and decodes them again.
+        Out of scope: conditioning a window on the previous window's text, the temperature fallback, the no-speech skip, word
+        grouping, and sampling."""
+        clips, W = self._transcribe_check(mel, prompt_ids, logit_rules, max_new_tokens, window, frames_per_timestamp, num_beams,
+                                           length_penalty)
+        dev, B, dec = clips[0].device, len(clips), self.with_logit_rules(logit_rules)
+        tb, eos = logit_rules.timestamp_begin, logit_rules.eos_token_id
+        T_p = prompt_ids.shape[-1]
+        total = [int(c.shape[0]) for c in clips]
+        seek, n_tok = [0] * B, [0] * B
+        parts = [([], [], [], []) for _ in range(B)]                   # per item: starts, ends, tokens, offsets of each window
+        while True:
+            act = [b for b in range(B) if seek[b] < total[b]]
+            if not act:
+                break
+            wins = [clips[b][seek[b]:seek[b] + W] for b in act]
+            if prompt_ids.dim() == 1:
+                prompts = prompt_ids.unsqueeze(0).expand(len(act), -1)
+            else:
+                prompts = prompt_ids if len(act) == B else torch.stack([prompt_ids[b] for b in act])
+            if num_beams > 1:
+                rows, _ = dec.beam_search(wins, prompts, max_new_tokens, num_beams, eos, length_penalty, graph)
+            else:
+                rows = dec.generate(wins, prompts, max_new_tokens, eos, graph)
+            lens = torch.tensor([int(w.shape[0]) for w in wins], dtype=torch.int32)
+            meta = torch.empty(len(act), 3, dtype=torch.int32)
+            if dev.type == "cuda":                                     # an asynchronous copy: the host does not wait for it
+                lens, meta = lens.pin_memory().to(dev, non_blocking=True), meta.pin_memory()
+            seg = ops.timestamp_segments(rows.to(torch.int32), T_p, lens, tb, eos, frames_per_timestamp)
+            last = seg.tok_end.gather(1, (seg.n_segments - 1).clamp_min(0).long().unsqueeze(1)).squeeze(1)
+            spanned = torch.where(seg.n_segments > 0, last - T_p, 0)   # a window's segments are contiguous from column T_p on
+            meta.copy_(torch.stack((seg.advance, seg.n_segments, spanned.to(torch.int32)), dim=1))      # the one synchronisation
+            for a, (adv, n, m) in enumerate(meta.tolist()):
+                b = act[a]
+                st, en, tk, off = parts[b]
+                st.append(seg.starts[a, :n] + seek[b])
+                en.append(seg.ends[a, :n] + seek[b])
+                tk.append(rows[a, T_p:T_p + m])
+                off.append(seg.tok_begin[a, :n] + (n_tok[b] - T_p))
+                seek[b] += adv
+                n_tok[b] += m
+        out = []
+        for b, (st, en, tk, off) in enumerate(parts):
+            off.append(torch.full((1,), n_tok[b], dtype=torch.int32, device=dev))
+            out.append(Transcript(torch.cat(st), torch.cat(en), torch.cat(tk), torch.cat(off)))
+        return out
 
     @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):

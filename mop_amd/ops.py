@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -1961,11 +1961,12 @@ def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     return _da_run("decode_attention_lens", q, k_cache, v_cache, kv_lens=kv_lens, nk=nk)
 
 
-# ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, alignment_cost, dtw_align ----
+# ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, alignment_cost, dtw_align,
+# timestamp_segments ----
 # Each is its _*_check (every ValueError, once per call), its _*_accept (the tensor-side tests, then the args struct, built once,
 # if the library's _supported query takes it, else None), then the torch restatement, or the outputs into that struct and _row_launch.
 def _row_launch(a, sym: str, key: str, dev=None, ws_sym: Optional[str] = None) -> None:
-    """the tail the six ops share: the library's workspace query `ws_sym` where the op has one (the buffer goes into the struct,
+    """the tail these ops share: the library's workspace query `ws_sym` where the op has one (the buffer goes into the struct,
     into its base for a struct that wraps one), LAST_PATH, and the launch of `sym` on the accepted struct `a`"""
     if ws_sym is not None:
         n = getattr(L.lib(), ws_sym)(C.byref(a))
@@ -2605,12 +2606,12 @@ ALIGN_MAX_WIDTH = 9            # the filter kernel's odd median widths end here
 ALIGN_MAX_ROWS = 1024          # rows of a map the filter kernel holds in LDS / rows of one DTW (one thread each)
 
 
-def _lens_i32_check(t, B: int, dev, name: str, what: str) -> None:
+def _lens_i32_check(t, B: int, dev, name: str, what: str, beside: str = "the map") -> None:
     if not isinstance(t, torch.Tensor) or t.shape != (B,) or t.dtype.is_floating_point or t.dtype in (torch.bool,) or t.dtype.is_complex:
         raise ValueError(f"{what}: {name} must be an integer ({B},) tensor, got "
                          f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
     if t.device != dev:
-        raise ValueError(f"{what}: {name} is on {t.device}, the map on {dev}")
+        raise ValueError(f"{what}: {name} is on {t.device}, {beside} on {dev}")
 
 
 def _ac_check(probs, n_tokens, n_frames, medfilt_width, what: str) -> None:
@@ -2829,3 +2830,162 @@ def dtw_align(cost: torch.Tensor, n_rows: torch.Tensor, n_cols: torch.Tensor, ro
         a.starts, a.ends = starts.data_ptr(), ends.data_ptr()                      # in place of the stand-ins
         _row_launch(a, "mopk_dtw_align", "dtw_align", cost.device, "mopk_dtw_workspace_bytes")
         return starts, ends
+
+
+# --------------------------------------------------------------------------------------
+# Long-form transcription (WhisperMoP.transcribe): Whisper's segment and seek arithmetic on decoded token rows
+SEGMENTS_MAX_COLS = 1024       # generated columns of a row (one thread each)
+
+
+class TimestampSegments(NamedTuple):
+    """the segments of a batch of decoded windows (`timestamp_segments`), all int32 on the tokens' device.
+    starts / ends (R, S): the segments' first and last frame, relative to the window start; tok_begin / tok_end (R, S): the columns
+    of `tokens` a segment spans, the end exclusive; all -1 at j >= n_segments[r].  n_segments (R,).  advance (R,): how far the
+    next window moves, in [1, max(window[r], 1)]."""
+    starts: torch.Tensor
+    ends: torch.Tensor
+    tok_begin: torch.Tensor
+    tok_end: torch.Tensor
+    n_segments: torch.Tensor
+    advance: torch.Tensor
+
+
+def _ts_check(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp, what: str) -> None:
+    """validate a timestamp_segments call before any device work"""
+    def _is_int(x):
+        return not isinstance(x, bool) and isinstance(x, int)
+
+    if (not isinstance(tokens, torch.Tensor) or tokens.dim() != 2 or 0 in tokens.shape or tokens.dtype.is_floating_point
+            or tokens.dtype.is_complex or tokens.dtype == torch.bool):
+        raise ValueError(f"{what}: tokens must be a non-empty integer (R, T) tensor, got "
+                         f"{(tuple(tokens.shape), tokens.dtype) if isinstance(tokens, torch.Tensor) else type(tokens).__name__}")
+    if not _is_int(t0) or not 0 <= t0 < tokens.shape[1]:
+        raise ValueError(f"{what}: t0 must be an int in [0, T = {tokens.shape[1]}), got {t0!r}")
+    _lens_i32_check(window, tokens.shape[0], tokens.device, "window", what, "the tokens")
+    if not _is_int(timestamp_begin) or not _is_int(eos_token_id) or not 0 <= eos_token_id < timestamp_begin < 2 ** 31:
+        raise ValueError(f"{what}: needs ints 0 <= eos_token_id < timestamp_begin < 2^31, got eos_token_id = {eos_token_id!r}, "
+                         f"timestamp_begin = {timestamp_begin!r}")
+    if not _is_int(frames_per_timestamp) or not 1 <= frames_per_timestamp < 2 ** 31:
+        raise ValueError(f"{what}: frames_per_timestamp must be an int >= 1, got {frames_per_timestamp!r}")
+
+
+def timestamp_segments_torch(tokens: torch.Tensor, t0: int, window: torch.Tensor, timestamp_begin: int, eos_token_id: int,
+                             frames_per_timestamp: int = 1) -> TimestampSegments:
+    """the restatement of `timestamp_segments` in torch ops (CPU or GPU, vectorised over rows, no host sync): the flags per
+    column, a cumulative sum that numbers the cuts, and scatters into buffers with one spare column that takes every write of a
+    column that has none to make"""
+    _ts_check(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp, "timestamp_segments_torch")
+    R, T = tokens.shape
+    dev, S, tb, f = tokens.device, T - t0, timestamp_begin, frames_per_timestamp
+    g = tokens[:, t0:].to(torch.long)
+    j = torch.arange(S, device=dev).unsqueeze(0)
+    w = window.to(torch.long).clamp_min(1)
+    n = torch.where(g == eos_token_id, j, S).min(1).values
+    ts = (j < n.unsqueeze(1)) & (g >= tb)
+    cut = torch.zeros_like(ts)
+    cut[:, 1:] = ts[:, 1:] & ts[:, :-1]
+    at = lambda i: g.gather(1, i.clamp(0, S - 1).unsqueeze(1)).squeeze(1)          # noqa: E731  g[r, i[r]]
+    frame = lambda x: ((x - tb) * f).to(torch.int32).to(torch.long)                # noqa: E731  the product in 32 bits
+    single_end = (n >= 2) & (at(n - 2) < tb) & (at(n - 1) >= tb)                   # rule 2
+    nC = cut.sum(1)
+    has = nC > 0
+    nseg = torch.where(has, nC + single_end, (n > 0).long())
+    rank = cut.cumsum(1) - cut.long()                                              # the exclusive scan: cut c closes segment rank
+    col = (t0 + j).expand(R, S)
+    starts, ends, tok_begin, tok_end = (torch.full((R, S + 1), -1, dtype=torch.long, device=dev) for _ in range(4))
+    prev = F.pad(g, (1, 0))[:, :S]
+    close = torch.where(cut, rank, S)                                              # rule 4: a cut closes its segment ...
+    ends.scatter_(1, close, frame(prev))
+    tok_end.scatter_(1, close, col)
+    opens = torch.where(cut & (rank + 1 < nseg.unsqueeze(1)), rank + 1, S)         # ... and opens the next one, if there is one
+    starts.scatter_(1, opens, frame(g))
+    tok_begin.scatter_(1, opens, col)
+    some = nseg > 0
+    starts[:, 0] = torch.where(some, torch.where(has & ts[:, 0], frame(g[:, 0]), 0), -1)
+    tok_begin[:, 0] = torch.where(some, t0, -1)
+    tail = torch.where(has & single_end, nC, S).unsqueeze(1)                       # the cut at n
+    ends.scatter_(1, tail, frame(at(n - 1)).unsqueeze(1))
+    tok_end.scatter_(1, tail, (t0 + n).unsqueeze(1))
+    li = torch.where(ts, j, -1).max(1).values                                      # rule 5: the last timestamp
+    s = at(li)
+    one = ~has & some
+    ends[:, 0] = torch.where(one, torch.where((li >= 0) & (s != tb), frame(s), w), ends[:, 0])
+    tok_end[:, 0] = torch.where(one, t0 + n, tok_end[:, 0])
+    max_c = torch.where(cut, j, -1).max(1).values
+    adv = torch.where(has & ~single_end, frame(at(max_c - 1)), w)
+    adv = torch.minimum(adv.clamp_min(1), w)                                       # rule 6
+    i32 = lambda t: t.to(torch.int32)                                              # noqa: E731
+    return TimestampSegments(i32(starts[:, :S]), i32(ends[:, :S]), i32(tok_begin[:, :S]), i32(tok_end[:, :S]), i32(nseg), i32(adv))
+
+
+def _ts_args(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp) -> L.TimestampSegmentsArgs:
+    a = L.TimestampSegmentsArgs()
+    a.R, a.T = tokens.shape
+    a.T0, a.tb, a.eos, a.f = t0, timestamp_begin, eos_token_id, frames_per_timestamp
+    a.tokens, a.tokens_ld, a.window = tokens.data_ptr(), tokens.stride(0), window.data_ptr()
+    if a.R == 1:                                                                   # a single row: its stride is never used
+        a.tokens_ld = a.T
+    return a
+
+
+def _ts_accept(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp):
+    """the args struct of a call that mopk_timestamp_segments takes, None of one it refuses; the outputs hold stand-ins"""
+    R, T = tokens.shape
+    if not tokens.is_cuda or tokens.dtype != torch.int32 or (T > 1 and tokens.stride(1) != 1) or (R > 1 and tokens.stride(0) < T):
+        return None
+    if window.dtype != torch.int32 or (R > 1 and window.stride(0) != 1) or T - t0 > SEGMENTS_MAX_COLS:
+        return None
+    a = _ts_args(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp)
+    a.starts = a.ends = a.tok_begin = a.tok_end = a.n_segments = a.advance = a.window  # stand-ins: only their alignment is looked at
+    return a if L.lib().mopk_timestamp_segments_supported(C.byref(a)) else None
+
+
+def timestamp_segments_supported(tokens: torch.Tensor, t0: int, window: torch.Tensor, timestamp_begin: int, eos_token_id: int,
+                                 frames_per_timestamp: int = 1) -> bool:
+    """True if mopk_timestamp_segments takes this call: CUDA int32 tokens with unit inner stride and a row stride >= T (one row:
+    any), a contiguous int32 window, T - t0 <= 1024 (the library's own query decides the rest).  Raises ValueError on bad
+    arguments."""
+    _ts_check(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp, "timestamp_segments_supported")
+    return _ts_accept(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp) is not None
+
+
+def timestamp_segments(tokens: torch.Tensor, t0: int, window: torch.Tensor, timestamp_begin: int, eos_token_id: int,
+                       frames_per_timestamp: int = 1) -> TimestampSegments:
+    """Whisper's segment and seek arithmetic (transcribe.py) for a batch of decoded windows -> TimestampSegments(starts, ends,
+    tok_begin, tok_end, n_segments, advance), all int32 on the tokens' device.  Inference only.
+
+    tokens: (R, T) int32 decoder outputs, the prompt in front; unit inner stride, any row stride >= T (one row: any).  t0: the
+    first generated column (the same for every row: ragged prompts are left-padded).  window: (R,) int32 device tensor, the frames
+    of row r's window, used as w = max(window[r], 1).  tb = timestamp_begin, eos = eos_token_id, 0 <= eos < tb: a token is a
+    timestamp when its id is >= tb, and tb + i means frame i * f of the window, f = frames_per_timestamp (this model has no
+    convolutional stem: a frame is a mel frame; OpenAI's 20 ms timestamps over 10 ms frames are f = 2).  Per row, e = the first
+    column >= t0 that holds eos (T if none), g = tokens[r, t0:e] are its n = e - t0 tokens, ts[i] = g[i] >= tb, and:
+    1. n == 0: no segment; advance = w;
+    2. single_end = n >= 2 and not ts[n-2] and ts[n-1];
+    3. C = the i in [1, n) with ts[i-1] and ts[i], ascending;
+    4. C not empty: the cuts are C, then n if single_end; with p the cut before (0 at first), cut c makes the segment of the
+       columns tok_begin = t0 + p, tok_end = t0 + c (exclusive), start = (g[p] - tb) * f (0 when g[p] is no timestamp: p = 0 only,
+       and never under the logit rules), end = (g[c-1] - tb) * f; advance = w if single_end, else (g[max C - 1] - tb) * f; the
+       tokens after the last cut are in no segment (the next window decodes them again);
+    5. C empty: one segment [t0, t0 + n), start = 0, end = w, or (s - tb) * f when a timestamp exists and the last one, s, is not
+       tb itself; advance = w;
+    6. advance is clamped into [1, w].
+    Three deviations from Whisper: rule 6 (Whisper has neither clamp; the lower one keeps a loop moving, the upper one guards
+    against a timestamp beyond the window, and under the logit rules only the upper one can act), the start = 0 of rule 4, and
+    rule 1 (Whisper adds an empty segment there and drops it later).  starts / ends / tok_begin / tok_end are (R, T - t0) with
+    -1 at j >= n_segments[r]; the products are taken in 32 bits.
+    Runs the HIP kernel (mopk_timestamp_segments: one launch, the -1 tail included) when timestamp_segments_supported() accepts
+    the call, else timestamp_segments_torch(); LAST_PATH["timestamp_segments"] records which.  No host sync, no workspace;
+    bitwise reproducible."""
+    _ts_check(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp, "timestamp_segments")
+    with torch.no_grad():
+        a = _ts_accept(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp)
+        if a is None:
+            LAST_PATH["timestamp_segments"] = L.PATH_GENERIC
+            return timestamp_segments_torch(tokens, t0, window, timestamp_begin, eos_token_id, frames_per_timestamp)
+        seg = torch.empty(4, a.R, a.T - a.T0, dtype=torch.int32, device=tokens.device)
+        row = torch.empty(2, a.R, dtype=torch.int32, device=tokens.device)
+        a.starts, a.ends, a.tok_begin, a.tok_end = (seg[k].data_ptr() for k in range(4))        # in place of the stand-ins
+        a.n_segments, a.advance = row[0].data_ptr(), row[1].data_ptr()
+        _row_launch(a, "mopk_timestamp_segments", "timestamp_segments")
+        return TimestampSegments(seg[0], seg[1], seg[2], seg[3], row[0], row[1])
