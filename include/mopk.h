@@ -805,6 +805,48 @@ typedef struct MopkTimestampSegmentsArgs {
 int mopk_timestamp_segments_supported(const MopkTimestampSegmentsArgs *a);   /* 1 if the kernel takes this call (T - T0, alignment) */
 int mopk_timestamp_segments(const MopkTimestampSegmentsArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * Whisper's log-mel spectrogram of a batch of waveforms (audio.py's log_mel_spectrogram; the stage in front of the encoder).
+ * (Added under version 118: new exports only; callers detect it with mopk_log_mel_supported.)
+ * Clip b holds len_b = min(lens[b], L) samples (L without lens) and T_b = len_b / hop frames; T = L / hop rows are written.
+ * Frame t covers the samples [t * hop - n_fft/2, t * hop + n_fft/2) of the clip reflected at ITS OWN two ends (index -i reads i,
+ * index len_b - 1 + i reads len_b - 1 - i).  With w the periodic Hann window and F the filters:
+ *   P[t,k] = | sum_n w[n] * frame_t[n] * e^{-2 pi i n k / n_fft} |^2, k = 0 .. n_fft/2;   M[t,m] = sum_k F[m,k] * P[t,k];
+ *   G = log10(max(M, 1e-10));   G = max(G, max over the clip's own t < T_b and all m of G, minus 8);   out = (G + 4) / 4.
+ * Rows t >= T_b of out are written as zeros by the same call.  All arithmetic is fp32.
+ * Two launches.  (1) One workgroup per (tile of MOPK_LOG_MEL_TILE_FRAMES frames, clip): the windowed frames and the twiddles
+ * sit in LDS, the DFT is a (32 x n_fft) . (n_fft x 2 . 32) product per 32 bins on the f32-input MFMA (twiddle n * k mod n_fft:
+ * an exact integer index into the table), the power and the filterbank product stay in LDS and registers, G goes to out (fp32)
+ * or to the workspace (bf16 out), and the tile's maximum to one workspace word of its own.  (2) Every workgroup reduces its
+ * clip's tile maxima in a fixed order (no atomics: bit-repeatable), clamps, scales and writes the zero tail.
+ * No host synchronisation.  The first call raises the kernel's LDS limit (not inside a stream capture: run once before).
+ * Takes n_fft even in [16, 512], 1 <= hop <= n_fft, 1 <= n_mels <= 128, L >= max(hop, n_fft/2 + 1), B <= 65535.  A device
+ * length below n_fft/2 + 1 cannot be refused here: such a clip reads zeros where the reflection leaves it (never out of bounds). */
+#define MOPK_LOG_MEL_TILE_FRAMES 32
+#define MOPK_LOG_MEL_F16 2               /* audio_dtype only: IEEE half samples (beside MOPK_F32 and MOPK_BF16) */
+typedef struct MopkLogMelArgs {
+    int32_t B;                           /* clips */
+    int32_t L;                           /* samples per row of audio */
+    int32_t n_fft;
+    int32_t hop;
+    int32_t n_mels;
+    int32_t audio_dtype;                 /* MOPK_F32, MOPK_BF16 or MOPK_LOG_MEL_F16 */
+    int32_t out_dtype;                   /* MOPK_F32 or MOPK_BF16 */
+    int32_t reserved;
+    const void *audio;                   /* device (B rows of L), unit inner stride */
+    int64_t audio_ld;                    /* element stride between rows, >= L */
+    const int32_t *lens;                 /* device (B) sample counts, clamped into [0, L]; NULL: every clip has L */
+    const float *filters;                /* device (n_mels, n_fft/2 + 1) fp32, contiguous */
+    const int32_t *bands;                /* device (n_mels, 2): filters[m][k] == 0 outside lo <= k < hi; NULL: 0 .. n_fft/2 + 1 */
+    const float *twiddle;                /* device (n_fft, 2): cos and sin of 2 pi i / n_fft */
+    const float *window;                 /* device (n_fft): 0.5 - 0.5 cos(2 pi n / n_fft) */
+    void *out;                           /* (B, L / hop, n_mels) out, contiguous */
+    void *workspace;                     /* mopk_log_mel_workspace_bytes() */
+} MopkLogMelArgs;
+int mopk_log_mel_supported(const MopkLogMelArgs *a);             /* 1 if the kernel takes this call (shape, dtypes, alignment) */
+size_t mopk_log_mel_workspace_bytes(const MopkLogMelArgs *a);    /* from the shape and out_dtype alone (no pointer is looked at) */
+int mopk_log_mel(const MopkLogMelArgs *a, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

@@ -264,6 +264,20 @@ class TimestampSegmentsArgs(C.Structure):
     ]
 
 
+class LogMelArgs(C.Structure):
+    """MopkLogMelArgs: Whisper's log-mel spectrogram of a batch of waveforms (LogMelFrontend)."""
+    _fields_ = [
+        ("B", C.c_int32), ("L", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32),
+        ("audio_dtype", C.c_int32), ("out_dtype", C.c_int32), ("reserved", C.c_int32),
+        ("audio", _fp), ("audio_ld", C.c_int64), ("lens", _fp), ("filters", _fp), ("bands", _fp), ("twiddle", _fp),
+        ("window", _fp), ("out", _fp), ("workspace", _fp),
+    ]
+
+
+LOG_MEL_TILE_FRAMES = 32   # MOPK_LOG_MEL_TILE_FRAMES
+LOG_MEL_F16 = 2            # MOPK_LOG_MEL_F16
+
+
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),
@@ -348,6 +362,9 @@ SYMBOLS = {
     "mopk_dtw_align": (C.c_int, [C.POINTER(DtwArgs), C.c_void_p]),
     "mopk_timestamp_segments_supported": (C.c_int, [C.POINTER(TimestampSegmentsArgs)]),
     "mopk_timestamp_segments": (C.c_int, [C.POINTER(TimestampSegmentsArgs), C.c_void_p]),
+    "mopk_log_mel_supported": (C.c_int, [C.POINTER(LogMelArgs)]),
+    "mopk_log_mel_workspace_bytes": (C.c_size_t, [C.POINTER(LogMelArgs)]),
+    "mopk_log_mel": (C.c_int, [C.POINTER(LogMelArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -1023,11 +1023,83 @@ class WhisperMoP(nn.Module):
         return out
 
     @torch.no_grad()
+    def transcribe_audio(self, audio, frontend: "LogMelFrontend", prompt_ids: torch.Tensor, logit_rules: "ops.LogitRules",
+                         max_new_tokens: int, **transcribe_kwargs) -> List[Transcript]:
+        """`transcribe` from waveforms: audio (a (B, L) tensor or a list of B 1-D clips, see LogMelFrontend.forward) goes through
+        frontend, the mel it returns through transcribe(mel, prompt_ids, logit_rules, max_new_tokens, **transcribe_kwargs).
+        A segment's frames times frontend.frame_seconds are seconds.  ValueError when frontend.n_mels is not the model's."""
+        if not isinstance(frontend, LogMelFrontend) or frontend.n_mels != self.cfg.n_mels:
+            raise ValueError(f"transcribe_audio: frontend must be a LogMelFrontend with n_mels = {self.cfg.n_mels} (the model's), got "
+                             f"{getattr(frontend, 'n_mels', type(frontend).__name__)!r}")
+        return self.transcribe(frontend(audio), prompt_ids, logit_rules, max_new_tokens, **transcribe_kwargs)
+
+    @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):
         """per-layer time gates of the encoder, (B, L_enc, T_audio); for a list of clips (see encode) the columns >= T_b of item b
         are unspecified."""
         _, gates = self.encode(mel)
         return gates
+
+
+class LogMelFrontend(nn.Module):
+    """waveform -> Whisper's log-mel spectrogram (ops.log_mel: the HIP STFT kernel), the stage in front of `WhisperMoP.encode`,
+    `generate`, `beam_search`, `sample`, `align_tokens` and `transcribe`.  The Slaney mel filterbank (ops.mel_filterbank) is a
+    non-persistent buffer.  Out of scope: resampling (audio must be at sample_rate), Whisper's 30 s zero padding, file decoding."""
+
+    def __init__(self, n_mels: int = 80, sample_rate: int = 16000, n_fft: int = 400, hop_length: int = 160):
+        super().__init__()
+        for name, v in (("n_mels", n_mels), ("sample_rate", sample_rate), ("n_fft", n_fft), ("hop_length", hop_length)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"LogMelFrontend: {name} must be an int >= 1, got {v!r}")
+        if n_fft % 2 or hop_length > n_fft:
+            raise ValueError(f"LogMelFrontend: needs an even n_fft and hop_length <= n_fft, got n_fft = {n_fft}, hop_length = {hop_length}")
+        self.n_mels, self.sample_rate, self.n_fft, self.hop_length = n_mels, sample_rate, n_fft, hop_length
+        self.register_buffer("filters", ops.mel_filterbank(sample_rate, n_fft, n_mels), persistent=False)
+
+    @property
+    def frame_seconds(self) -> float:
+        """the duration of one mel frame"""
+        return self.hop_length / self.sample_rate
+
+    @property
+    def min_samples(self) -> int:
+        """the shortest clip: one frame, and a reflection that stays inside the clip"""
+        return max(self.hop_length, self.n_fft // 2 + 1)
+
+    @torch.no_grad()
+    def forward(self, audio):
+        """audio: a (B, L) tensor of samples -> (B, L // hop_length, n_mels) fp32; or a list of B 1-D clips of different lengths
+        -> a list of B (T_b, n_mels) tensors, T_b = L_b // hop_length, views of one padded buffer (what the model's entry points
+        take as a list).  The clips are padded into one (B, L_max) buffer and their lengths go to the device as one pinned
+        asynchronous copy; every clip is reflected at its own ends and clamped against its own maximum."""
+        what = "LogMelFrontend"
+        if isinstance(audio, torch.Tensor):
+            if audio.dim() != 2:
+                raise ValueError(f"{what}: audio must be a (B, L) tensor or a non-empty list of B 1-D clips, got {tuple(audio.shape)}")
+            return ops.log_mel(audio, self.filters, self.n_fft, self.hop_length)
+        if not isinstance(audio, (list, tuple)) or len(audio) == 0:
+            raise ValueError(f"{what}: audio must be a (B, L) tensor or a non-empty list of B 1-D clips")
+        for b, x in enumerate(audio):
+            if not isinstance(x, torch.Tensor) or x.dim() != 1:
+                raise ValueError(f"{what}: clip {b} must be a 1-D tensor of samples, got "
+                                 f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+            if x.dtype != audio[0].dtype or not x.dtype.is_floating_point:
+                raise ValueError(f"{what}: clips must share one floating dtype, clip {b} is {x.dtype}")
+            if x.device != audio[0].device:
+                raise ValueError(f"{what}: clip {b} is on {x.device}, clip 0 on {audio[0].device}")
+            if x.shape[0] < self.min_samples:
+                raise ValueError(f"{what}: clip {b} has {x.shape[0]} samples, fewer than max(hop_length, n_fft/2 + 1) = {self.min_samples}")
+        n = [int(x.shape[0]) for x in audio]
+        padded = torch.zeros(len(n), max(n), dtype=audio[0].dtype, device=audio[0].device)
+        for b, x in enumerate(audio):
+            padded[b, :n[b]] = x
+        lens = None
+        if min(n) != max(n):
+            lens = torch.tensor(n, dtype=torch.int32)
+            if padded.device.type == "cuda":                           # an asynchronous copy: the host does not wait for it
+                lens = lens.pin_memory().to(padded.device, non_blocking=True)
+        mel = ops.log_mel(padded, self.filters, self.n_fft, self.hop_length, lens)
+        return [mel[b, :n[b] // self.hop_length] for b in range(len(n))]
 
 
 class RuledDecoding:

@@ -2989,3 +2989,200 @@ def timestamp_segments(tokens: torch.Tensor, t0: int, window: torch.Tensor, time
         a.n_segments, a.advance = row[0].data_ptr(), row[1].data_ptr()
         _row_launch(a, "mopk_timestamp_segments", "timestamp_segments")
         return TimestampSegments(seg[0], seg[1], seg[2], seg[3], row[0], row[1])
+
+
+# --------------------------------------------------------------------------------------
+# Audio frontend (LogMelFrontend): Whisper's log-mel spectrogram of a batch of waveforms
+LOG_MEL_TILE_FRAMES = L.LOG_MEL_TILE_FRAMES     # frames per workgroup of the tile kernel
+LOG_MEL_MIN_FFT, LOG_MEL_MAX_FFT, LOG_MEL_MAX_MELS = 16, 512, 128
+_LM_TABLES = {}                # (n_fft, device, dtype) -> (twiddle (n_fft, 2), window (n_fft,))
+_LM_BANDS = {}                 # id(filters) -> (weak reference, version, bands (n_mels, 2) int32)
+
+
+def _slaney_hz_to_mel(f: float) -> float:
+    return 15.0 + math.log(f / 1000.0) / (math.log(6.4) / 27.0) if f >= 1000.0 else f / (200.0 / 3.0)
+
+
+def _slaney_mel_to_hz(m: float) -> float:
+    return 1000.0 * math.exp((math.log(6.4) / 27.0) * (m - 15.0)) if m >= 15.0 else m * (200.0 / 3.0)
+
+
+def mel_filterbank(sample_rate: int, n_fft: int, n_mels: int, device=None) -> torch.Tensor:
+    """the Slaney-scale, area-normalised triangular mel filterbank (librosa.filters.mel's default, the matrix Whisper ships as
+    mel_filters.npz) -> (n_mels, n_fft/2 + 1) fp32.  The mel scale is linear below 1 kHz (200/3 Hz per mel) and logarithmic above
+    (step log(6.4)/27); n_mels + 2 points f_0 .. f_{n_mels+1} are spaced evenly in mel over [0, sample_rate/2]; row m is the
+    triangle over [f_m, f_{m+2}] with its peak at f_{m+1}, scaled by 2 / (f_{m+2} - f_m).  Computed in float64 on the host."""
+    for name, v in (("sample_rate", sample_rate), ("n_fft", n_fft), ("n_mels", n_mels)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"mel_filterbank: {name} must be an int >= 1, got {v!r}")
+    if n_fft % 2:
+        raise ValueError(f"mel_filterbank: n_fft must be even, got {n_fft}")
+    top = _slaney_hz_to_mel(sample_rate / 2.0)
+    pts = torch.tensor([_slaney_mel_to_hz(top * i / (n_mels + 1)) for i in range(n_mels + 2)], dtype=torch.float64)
+    freqs = torch.arange(n_fft // 2 + 1, dtype=torch.float64) * (sample_rate / 2.0 / (n_fft // 2))
+    d = pts[1:] - pts[:-1]
+    r = pts.unsqueeze(1) - freqs.unsqueeze(0)
+    w = torch.minimum(-r[:-2] / d[:-1].unsqueeze(1), r[2:] / d[1:].unsqueeze(1)).clamp_min(0.0)
+    w = w * (2.0 / (pts[2:] - pts[:-2])).unsqueeze(1)
+    return w.to(torch.float32).to(device) if device is not None else w.to(torch.float32)
+
+
+def _lm_tables(n_fft: int, device, dtype):
+    """(twiddle (n_fft, 2): cos and sin of 2 pi i / n_fft, window (n_fft,): periodic Hann), computed once per (n_fft, device,
+    dtype) in float64 and rounded to dtype"""
+    key = (n_fft, str(device), dtype)
+    if key not in _LM_TABLES:
+        ang = torch.arange(n_fft, dtype=torch.float64) * (2.0 * math.pi / n_fft)
+        tw = torch.stack((torch.cos(ang), torch.sin(ang)), dim=1)
+        _LM_TABLES[key] = (tw.to(dtype).to(device).contiguous(), (0.5 - 0.5 * torch.cos(ang)).to(dtype).to(device).contiguous())
+    return _LM_TABLES[key]
+
+
+def _lm_bands(filters: torch.Tensor) -> torch.Tensor:
+    """(n_mels, 2) int32 on the filters' device: row m of the filters is zero outside [lo, hi) (an empty row: lo = hi = 0).  Built
+    with a few torch ops and no host sync, then kept for as long as the same tensor object is passed in unchanged (its version
+    counter), so a frontend that holds its filters pays for it once.  A tensor made under torch.inference_mode has no version
+    counter and could change unseen, so its table is derived on every call"""
+    import weakref
+    version = None if filters.is_inference() else filters._version
+    hit = _LM_BANDS.get(id(filters))
+    if version is not None and hit is not None and hit[0]() is filters and hit[1] == version:
+        return hit[2]
+    nz = filters != 0
+    nb = filters.shape[1]
+    lo = nz.to(torch.int32).argmax(1)
+    hi = nb - nz.flip(1).to(torch.int32).argmax(1)
+    some = nz.any(1)
+    bands = torch.stack((torch.where(some, lo, 0), torch.where(some, hi, 0)), dim=1).to(torch.int32).contiguous()
+    for k in [k for k, v in _LM_BANDS.items() if v[0]() is None]:
+        del _LM_BANDS[k]
+    if version is not None:
+        _LM_BANDS[id(filters)] = (weakref.ref(filters), version, bands)
+    return bands
+
+
+def _lm_check(audio, filters, n_fft, hop_length, lens, out_dtype, what: str) -> None:
+    """validate a log_mel call before any device work"""
+    if (not isinstance(audio, torch.Tensor) or audio.dim() != 2 or 0 in audio.shape
+            or audio.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.float64)):
+        raise ValueError(f"{what}: audio must be a non-empty (B, L) tensor of float32, bfloat16, float16 or float64 samples, got "
+                         f"{(tuple(audio.shape), audio.dtype) if isinstance(audio, torch.Tensor) else type(audio).__name__}")
+    if isinstance(n_fft, bool) or not isinstance(n_fft, int) or n_fft < 2 or n_fft % 2:
+        raise ValueError(f"{what}: n_fft must be an even int >= 2, got {n_fft!r}")
+    if isinstance(hop_length, bool) or not isinstance(hop_length, int) or not 1 <= hop_length <= n_fft:
+        raise ValueError(f"{what}: hop_length must be an int in [1, n_fft = {n_fft}], got {hop_length!r}")
+    if (not isinstance(filters, torch.Tensor) or filters.dim() != 2 or filters.shape[0] < 1 or filters.shape[1] != n_fft // 2 + 1
+            or filters.dtype not in (torch.float32, torch.float64)):
+        raise ValueError(f"{what}: filters must be a float32 (or float64) (n_mels, n_fft/2 + 1 = {n_fft // 2 + 1}) tensor, got "
+                         f"{(tuple(filters.shape), filters.dtype) if isinstance(filters, torch.Tensor) else type(filters).__name__}")
+    if filters.device != audio.device:
+        raise ValueError(f"{what}: filters are on {filters.device}, the audio on {audio.device}")
+    need = max(hop_length, n_fft // 2 + 1)
+    if audio.shape[1] < need:
+        raise ValueError(f"{what}: a clip needs at least max(hop_length, n_fft/2 + 1) = {need} samples (one frame, and a "
+                         f"reflection that stays inside it), got L = {audio.shape[1]}")
+    if lens is not None:
+        if not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or lens.shape != (audio.shape[0],):
+            raise ValueError(f"{what}: lens must be an int32 ({audio.shape[0]},) tensor of sample counts, got "
+                             f"{(tuple(lens.shape), lens.dtype) if isinstance(lens, torch.Tensor) else type(lens).__name__}")
+        if lens.device != audio.device:
+            raise ValueError(f"{what}: lens is on {lens.device}, the audio on {audio.device}")
+    allowed = (torch.float32, torch.bfloat16) + ((torch.float64,) if audio.dtype == torch.float64 else ())
+    if out_dtype not in allowed:
+        raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16 (torch.float64 for float64 audio), got {out_dtype!r}")
+
+
+def log_mel_torch(audio: torch.Tensor, filters: torch.Tensor, n_fft: int = 400, hop_length: int = 160,
+                  lens: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """the restatement of `log_mel` in torch ops (CPU or GPU, no host sync, no FFT library): the frames are gathered at their
+    reflected sample indices into a (B, T, n_fft) matrix, windowed, and multiplied with the cos and sin bases read from the same
+    (n * k) mod n_fft twiddle table the kernel uses; power, filterbank product, log10, the per-clip clamp over the valid frames,
+    the scale, zeros behind T_b.  Computes in float32, in float64 for float64 audio."""
+    _lm_check(audio, filters, n_fft, hop_length, lens, out_dtype, "log_mel_torch")
+    cd = torch.float64 if audio.dtype == torch.float64 else torch.float32
+    dev, (B, Lm), N, nb = audio.device, audio.shape, n_fft, n_fft // 2 + 1
+    T = Lm // hop_length
+    tw, win = _lm_tables(N, dev, cd)
+    ln = torch.full((B,), Lm, dtype=torch.long, device=dev) if lens is None else lens.long().clamp(0, Lm)
+    n = torch.arange(N, device=dev)
+    idx = (torch.arange(T, device=dev).unsqueeze(1) * hop_length + n.unsqueeze(0) - N // 2).abs().unsqueeze(0)   # (1, T, n_fft)
+    lb = ln.view(B, 1, 1)
+    idx = torch.where(idx >= lb, 2 * (lb - 1) - idx, idx)
+    inside = (idx >= 0) & (idx < lb)
+    frames = audio.to(cd).gather(1, idx.clamp(0, Lm - 1).reshape(B, T * N)).view(B, T, N)
+    frames = torch.where(inside, frames, 0.0) * win
+    kk = (n.unsqueeze(1) * torch.arange(nb, device=dev).unsqueeze(0)) % N
+    re, im = frames @ tw[:, 0][kk], frames @ tw[:, 1][kk]
+    g = ((re * re + im * im) @ filters.to(cd).t()).clamp_min(1e-10).log10()
+    valid = (torch.arange(T, device=dev).unsqueeze(0) < (ln // hop_length).unsqueeze(1)).unsqueeze(2)            # (B, T, 1)
+    top = torch.where(valid, g, float("-inf")).amax(dim=(1, 2), keepdim=True)
+    out = (torch.maximum(g, top - 8.0) + 4.0) / 4.0
+    return torch.where(valid, out, 0.0).to(out_dtype)
+
+
+def _lm_args(audio, filters, n_fft, hop_length, lens, out_dtype, tables, bands) -> L.LogMelArgs:
+    a = L.LogMelArgs()
+    a.B, a.L = audio.shape
+    a.n_fft, a.hop, a.n_mels = n_fft, hop_length, filters.shape[0]
+    a.audio_dtype = {torch.float32: L.MOPK_F32, torch.bfloat16: L.MOPK_BF16, torch.float16: L.LOG_MEL_F16}[audio.dtype]
+    a.out_dtype = L.MOPK_BF16 if out_dtype == torch.bfloat16 else L.MOPK_F32
+    a.audio, a.audio_ld = audio.data_ptr(), audio.stride(0) if a.B > 1 else a.L       # a single row: its stride is never used
+    a.lens, a.filters, a.bands = _ptr(lens), filters.data_ptr(), _ptr(bands)
+    a.twiddle, a.window = tables[0].data_ptr(), tables[1].data_ptr()
+    return a
+
+
+def _lm_accept(audio, filters, n_fft, hop_length, lens, out_dtype):
+    """the args struct (without the output and the workspace) of a call that mopk_log_mel takes, None of one it refuses"""
+    B, Lm = audio.shape
+    if not audio.is_cuda or audio.dtype == torch.float64 or (Lm > 1 and audio.stride(1) != 1) or (B > 1 and audio.stride(0) < Lm):
+        return None
+    if filters.dtype != torch.float32 or not filters.is_contiguous() or out_dtype == torch.float64:
+        return None
+    if lens is not None and B > 1 and lens.stride(0) != 1:
+        return None
+    if not (LOG_MEL_MIN_FFT <= n_fft <= LOG_MEL_MAX_FFT and filters.shape[0] <= LOG_MEL_MAX_MELS):
+        return None
+    a = _lm_args(audio, filters, n_fft, hop_length, lens, out_dtype, _lm_tables(n_fft, audio.device, torch.float32), _lm_bands(filters))
+    a.out = a.filters                                                              # a stand-in: only its alignment is looked at
+    return a if L.lib().mopk_log_mel_supported(C.byref(a)) else None
+
+
+def log_mel_supported(audio: torch.Tensor, filters: torch.Tensor, n_fft: int = 400, hop_length: int = 160,
+                      lens: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32) -> bool:
+    """True if mopk_log_mel takes this call: CUDA float32 / bfloat16 / float16 audio with unit inner stride and a row stride >= L,
+    contiguous float32 filters, n_fft even in [16, 512], n_mels <= 128, a contiguous lens, out_dtype float32 or bfloat16 (the
+    library's own query decides the rest).  Raises ValueError on bad arguments."""
+    _lm_check(audio, filters, n_fft, hop_length, lens, out_dtype, "log_mel_supported")
+    return _lm_accept(audio, filters, n_fft, hop_length, lens, out_dtype) is not None
+
+
+def log_mel(audio: torch.Tensor, filters: torch.Tensor, n_fft: int = 400, hop_length: int = 160,
+            lens: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Whisper's log_mel_spectrogram for a batch of clips -> (B, T, n_mels) in out_dtype, T = L // hop_length: what
+    WhisperMoP.encode / transcribe take.  Inference only.
+
+    audio: (B, L) float32 / bfloat16 / float16 samples, unit inner stride, any row stride >= L.  filters: (n_mels, n_fft/2 + 1)
+    float32 (`mel_filterbank`).  lens: int32 (B,) DEVICE tensor of sample counts (None: L), clamped into [0, L]; clip b has
+    len_b samples and T_b = len_b // hop_length frames.  Frame t covers the samples [t * hop - n_fft/2, t * hop + n_fft/2) of the
+    clip reflected at its own two ends (torch.stft(center=True, pad_mode="reflect") without its last frame); with w the periodic
+    Hann window: P[t,k] = |sum_n w[n] frame_t[n] e^{-2 pi i n k / n_fft}|^2, M = P . filters^T, G = log10(max(M, 1e-10)),
+    G = max(G, max_{t < T_b, m} G - 8) per clip, out = (G + 4) / 4; rows t >= T_b are zeros.  L >= max(hop_length, n_fft/2 + 1)
+    is checked here; lengths that only the device knows are the caller's to keep in that range (the kernel reads zeros where a
+    reflection leaves a shorter clip).
+    Runs the HIP kernels (mopk_log_mel: two launches, fp32 on the f32-input MFMA) when log_mel_supported() accepts the call, else
+    log_mel_torch(); LAST_PATH["log_mel"] records which.  No host sync; bitwise reproducible.  The twiddle table and the window
+    are built once per (n_fft, device).  The filters' band table (the non-zero span of each row) costs about ten small torch
+    launches before the two, once per filters tensor OBJECT: a call with the same unchanged tensor (a LogMelFrontend's buffer) is
+    two launches, a call with a fresh tensor such as `filters.cuda()`, or with one made under torch.inference_mode, pays them
+    again.  Samples are taken to be finite: a NaN or Inf sample lands on the clip's floor here, where log_mel_torch gives NaN."""
+    _lm_check(audio, filters, n_fft, hop_length, lens, out_dtype, "log_mel")
+    with torch.no_grad():
+        a = _lm_accept(audio, filters, n_fft, hop_length, lens, out_dtype)
+        if a is None:
+            LAST_PATH["log_mel"] = L.PATH_GENERIC
+            return log_mel_torch(audio, filters, n_fft, hop_length, lens, out_dtype)
+        out = torch.empty(a.B, a.L // a.hop, a.n_mels, dtype=out_dtype, device=audio.device)
+        a.out = out.data_ptr()                                                     # in place of the stand-in
+        _row_launch(a, "mopk_log_mel", "log_mel", audio.device, "mopk_log_mel_workspace_bytes")
+        return out
