@@ -847,6 +847,59 @@ int mopk_log_mel_supported(const MopkLogMelArgs *a);             /* 1 if the ker
 size_t mopk_log_mel_workspace_bytes(const MopkLogMelArgs *a);    /* from the shape and out_dtype alone (no pointer is looked at) */
 int mopk_log_mel(const MopkLogMelArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * Per-step decoding statistics on last-position logits (WhisperMoP.generate / beam_search / sample with return_stats, and the
+ * temperature fallback and no-speech skip of WhisperMoP.transcribe; inference only).  (Added under version 118: new exports only;
+ * callers detect them with the _supported queries.)  Row r (0 <= r < R) reads x at logits + r * logits_ld elements, F32 or BF16,
+ * element-aligned, finite or -inf values; lse = m + logf(sum expf(x - m)), m = max x, in fp32 (-inf entries add nothing).  A row
+ * without a finite entry is outside the contract: nothing faults, its results are unspecified.
+ *
+ * mopk_token_logprob: out[r] = (float)x[t] - lse, t = tokens[r], or `token` for every row when tokens is NULL; t is clamped into
+ * [0, V) (callers refuse what they can see).  x[t] = -inf gives -inf.
+ *
+ * mopk_greedy_pick: one greedy decoding step (Whisper's GreedyDecoder.update) on device state, in place.  p = *pos.
+ *   eos >= 0 and done[r] != 0:  t = eos; sum_logprobs, n_tokens and done are left as they are;
+ *   else:  t = argmax_v x_v, ties to the smaller v;  sum_logprobs[r] += x[t] - lse;  n_tokens[r] += 1;  done[r] |= (t == eos).
+ *   next_ids[r] = t;  hist[r * hist_ld + p] = t when hist is given and 0 <= p < hist_cap.
+ * The first eos is counted in the sum and in the length, nothing behind it: sum_logprobs / n_tokens is Whisper's avg_logprob.
+ *
+ * Both: one workgroup of 1024 threads per row, one pass over the row in 16-byte loads (scalar elements before the row's first
+ * 16-byte boundary and behind its last whole vector), the (max, sum-exp) pairs and the best (value, index) merged by wave shuffles
+ * and then in wave order; static LDS only, no atomics, no workspace, no host synchronisation: bitwise reproducible, and a first
+ * call may be inside a stream capture. */
+typedef struct MopkTokenLogprobArgs {
+    int32_t R;                           /* rows */
+    int32_t V;                           /* vocabulary, >= 2 */
+    int32_t dtype;                       /* MopkDtype of logits: F32 or BF16 */
+    int32_t token;                       /* the token of every row when tokens is NULL */
+    const void *logits;
+    int64_t logits_ld;                   /* element stride between rows, >= V */
+    const int32_t *tokens;               /* device (R) int32, contiguous, or NULL */
+    float *out;                          /* (R) out */
+} MopkTokenLogprobArgs;
+int mopk_token_logprob_supported(const MopkTokenLogprobArgs *a);     /* 1 if the kernel takes this call (V, dtype, stride, alignment) */
+int mopk_token_logprob(const MopkTokenLogprobArgs *a, void *stream);
+
+typedef struct MopkGreedyPickArgs {
+    int32_t R;                           /* rows */
+    int32_t V;                           /* vocabulary, >= 2 */
+    int32_t dtype;                       /* MopkDtype of logits: F32 or BF16 */
+    int32_t eos;                         /* eos token id, or -1: no eos */
+    int32_t hist_cap;                    /* columns of hist (0 without hist) */
+    int32_t reserved;                    /* 0 */
+    const void *logits;
+    int64_t logits_ld;                   /* element stride between rows, >= V */
+    const int32_t *pos;                  /* device: the new token's history column (one int32) */
+    int32_t *next_ids;                   /* (R) out: the next decoder step's ids */
+    int32_t *done;                       /* (R) in / out */
+    float *sum_logprobs;                 /* (R) in / out */
+    int32_t *n_tokens;                   /* (R) in / out */
+    int32_t *hist;                       /* (R rows of hist_cap) in / out, or NULL */
+    int64_t hist_ld;                     /* element stride between hist rows, >= hist_cap */
+} MopkGreedyPickArgs;
+int mopk_greedy_pick_supported(const MopkGreedyPickArgs *a);         /* 1 if the kernel takes this call (V, dtype, strides, alignment) */
+int mopk_greedy_pick(const MopkGreedyPickArgs *a, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

@@ -274,6 +274,23 @@ class LogMelArgs(C.Structure):
     ]
 
 
+class TokenLogprobArgs(C.Structure):
+    """MopkTokenLogprobArgs: the log-probability of one token per row of last-position logits (WhisperMoP's no_speech_prob)."""
+    _fields_ = [
+        ("R", C.c_int32), ("V", C.c_int32), ("dtype", C.c_int32), ("token", C.c_int32),
+        ("logits", _fp), ("logits_ld", C.c_int64), ("tokens", _fp), ("out", _fp),
+    ]
+
+
+class GreedyPickArgs(C.Structure):
+    """MopkGreedyPickArgs: one greedy decoding step on device state (WhisperMoP.generate)."""
+    _fields_ = [
+        ("R", C.c_int32), ("V", C.c_int32), ("dtype", C.c_int32), ("eos", C.c_int32), ("hist_cap", C.c_int32), ("reserved", C.c_int32),
+        ("logits", _fp), ("logits_ld", C.c_int64), ("pos", _fp), ("next_ids", _fp), ("done", _fp), ("sum_logprobs", _fp),
+        ("n_tokens", _fp), ("hist", _fp), ("hist_ld", C.c_int64),
+    ]
+
+
 LOG_MEL_TILE_FRAMES = 32   # MOPK_LOG_MEL_TILE_FRAMES
 LOG_MEL_F16 = 2            # MOPK_LOG_MEL_F16
 
@@ -365,6 +382,10 @@ SYMBOLS = {
     "mopk_log_mel_supported": (C.c_int, [C.POINTER(LogMelArgs)]),
     "mopk_log_mel_workspace_bytes": (C.c_size_t, [C.POINTER(LogMelArgs)]),
     "mopk_log_mel": (C.c_int, [C.POINTER(LogMelArgs), C.c_void_p]),
+    "mopk_token_logprob_supported": (C.c_int, [C.POINTER(TokenLogprobArgs)]),
+    "mopk_token_logprob": (C.c_int, [C.POINTER(TokenLogprobArgs), C.c_void_p]),
+    "mopk_greedy_pick_supported": (C.c_int, [C.POINTER(GreedyPickArgs)]),
+    "mopk_greedy_pick": (C.c_int, [C.POINTER(GreedyPickArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,182 @@
+// Per-step decoding statistics on last-position logits (WhisperMoP's return_stats and the temperature fallback / no-speech skip of
+// transcribe; inference only): the log-probability of one token per row (mopk_token_logprob) and one greedy decoding step on device
+// state (mopk_greedy_pick: argmax, log-probability sum, length, eos bookkeeping and the history column).  include/mopk.h states
+// both.  One launch, one workgroup of 1024 threads per row, static LDS, no atomics, no host synchronisation: the position is read
+// from device memory, so one set of launch arguments serves every step and a step can be captured once in a HIP graph.
+//
+// One pass streams the row in 16-byte loads: the elements before the row's first 16-byte boundary and behind its last whole
+// vector are read one by one (a row may start at any element).  A thread merges what it reads into its (max, sum-exp) pair and its
+// best (value, index); ranking by row_before is a total order, so the argmax does not depend on who read what, and the pairs are
+// merged in a fixed order (wave shuffles, then the waves in order): results are bitwise reproducible.
+#include "common.h"
+#include "row_helpers.h"
+
+namespace mopk {
+namespace {
+
+constexpr int TL_THREADS = 1024;
+constexpr int TL_WAVES = TL_THREADS / WAVE;
+constexpr int TL_NONE = 0x7fffffff;                             // index of "no element yet": every real index ranks before it
+
+struct TlLds {
+    float wm[TL_WAVES], wl[TL_WAVES], ws[TL_WAVES];
+    int wi[TL_WAVES];
+};
+
+// this thread's share of row x[0, V): (m, l) and, with BEST, the best (bs, bi)
+template <typename T, bool BEST>
+__device__ __forceinline__ void tl_scan(const T *x, int V, float &m, float &l, float &bs, int &bi) {
+    constexpr int ES = (int)sizeof(T), EPV = 16 / ES;
+    const int tid = threadIdx.x;
+    int head = (int)(((16 - ((uintptr_t)x & 15)) & 15) / ES);   // elements before the row's first 16-byte boundary
+    head = head < V ? head : V;
+    const int nvec = (V - head) / EPV, tail0 = head + nvec * EPV;
+    const uint4 *xv = (const uint4 *)(x + head);
+#pragma unroll 4
+    for (int u = tid; u < nvec; u += TL_THREADS) {
+        float f[EPV];
+        row_unpack(xv[u], f, T());
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) {
+            row_lse_add(m, l, f[e]);
+            if (BEST && row_before(f[e], head + u * EPV + e, bs, bi)) { bs = f[e]; bi = head + u * EPV + e; }
+        }
+    }
+    const int nt = V - tail0;                                   // head + nt < 2 * EPV scalar elements
+    if (tid < head + nt) {
+        const int e = tid < head ? tid : tail0 + (tid - head);
+        const float f = ld_as_f32<T>(x + e);
+        row_lse_add(m, l, f);
+        if (BEST && row_before(f, e, bs, bi)) { bs = f; bi = e; }
+    }
+}
+
+// block-wide merge: shuffles inside a wave, then the wave results in wave order (every thread gets the result)
+template <bool BEST>
+__device__ __forceinline__ void tl_block_merge(float &m, float &l, float &bs, int &bi, TlLds &s) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        row_lse_merge(m, l, __shfl_xor(m, o, 64), __shfl_xor(l, o, 64));
+        if (BEST) {
+            const float s2 = __shfl_xor(bs, o, 64);
+            const int i2 = __shfl_xor(bi, o, 64);
+            if (row_before(s2, i2, bs, bi)) { bs = s2; bi = i2; }
+        }
+    }
+    const int w = threadIdx.x / WAVE;
+    if ((threadIdx.x & 63) == 0) { s.wm[w] = m; s.wl[w] = l; s.ws[w] = bs; s.wi[w] = bi; }
+    __syncthreads();
+    m = s.wm[0];
+    l = s.wl[0];
+    bs = s.ws[0];
+    bi = s.wi[0];
+    for (int i = 1; i < TL_WAVES; ++i) {
+        row_lse_merge(m, l, s.wm[i], s.wl[i]);
+        if (BEST && row_before(s.ws[i], s.wi[i], bs, bi)) { bs = s.ws[i]; bi = s.wi[i]; }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(TL_THREADS) void tl_row_kernel(MopkTokenLogprobArgs a) {
+    __shared__ TlLds s;
+    const int r = blockIdx.x, V = a.V;
+    const T *x = (const T *)a.logits + (int64_t)r * a.logits_ld;
+    float m = -INFINITY, l = 0.f, bs = -INFINITY;
+    int bi = TL_NONE;
+    tl_scan<T, false>(x, V, m, l, bs, bi);
+    tl_block_merge<false>(m, l, bs, bi, s);
+    if (threadIdx.x == 0) {
+        const int t = min(max(a.tokens ? a.tokens[r] : a.token, 0), V - 1);        // no read leaves the row
+        a.out[r] = ld_as_f32<T>(x + t) - (m + logf(l));
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(TL_THREADS) void gp_row_kernel(MopkGreedyPickArgs a) {
+    __shared__ TlLds s;
+    const int r = blockIdx.x, V = a.V;
+    const int p = *a.pos;
+    const bool hist_on = a.hist != nullptr && p >= 0 && p < a.hist_cap;
+    if (a.eos >= 0 && a.done[r] != 0) {                         // the whole workgroup takes this branch: no barrier is skipped
+        if (threadIdx.x == 0) {
+            a.next_ids[r] = a.eos;
+            if (hist_on) a.hist[(int64_t)r * a.hist_ld + p] = a.eos;
+        }
+        return;
+    }
+    const T *x = (const T *)a.logits + (int64_t)r * a.logits_ld;
+    float m = -INFINITY, l = 0.f, bs = -INFINITY;
+    int bi = TL_NONE;
+    tl_scan<T, true>(x, V, m, l, bs, bi);
+    tl_block_merge<true>(m, l, bs, bi, s);
+    if (threadIdx.x == 0) {
+        const int t = bi < V ? bi : 0;                          // only reachable with NaN logits: keep the read inside the row
+        a.sum_logprobs[r] += ld_as_f32<T>(x + t) - (m + logf(l));
+        a.n_tokens[r] += 1;
+        a.next_ids[r] = t;
+        if (t == a.eos) a.done[r] = 1;
+        if (hist_on) a.hist[(int64_t)r * a.hist_ld + p] = t;
+    }
+}
+
+int tl_row_check(int R, int V, int dtype, const void *logits, int64_t ld) {
+    if (R <= 0 || V < 2) return MOPK_ERR_BAD_SHAPE;
+    if (dtype != MOPK_F32 && dtype != MOPK_BF16) return MOPK_ERR_BAD_ARG;
+    if (ld < V) return MOPK_ERR_BAD_ARG;
+    if ((uintptr_t)logits % (dtype == MOPK_BF16 ? 2 : 4)) return MOPK_ERR_UNSUPPORTED;
+    return MOPK_OK;
+}
+
+int tl_check(const MopkTokenLogprobArgs *a) {
+    if (!a) return MOPK_ERR_BAD_ARG;
+    const int rc = tl_row_check(a->R, a->V, a->dtype, a->logits, a->logits_ld);
+    if (rc != MOPK_OK) return rc;
+    if (!a->tokens && (a->token < 0 || a->token >= a->V)) return MOPK_ERR_BAD_ARG;
+    if (((uintptr_t)a->tokens & 3) || ((uintptr_t)a->out & 3)) return MOPK_ERR_UNSUPPORTED;
+    return MOPK_OK;
+}
+
+int gp_check(const MopkGreedyPickArgs *a) {
+    if (!a) return MOPK_ERR_BAD_ARG;
+    const int rc = tl_row_check(a->R, a->V, a->dtype, a->logits, a->logits_ld);
+    if (rc != MOPK_OK) return rc;
+    if (a->eos < -1 || a->eos >= a->V || a->reserved != 0) return MOPK_ERR_BAD_ARG;
+    if (a->hist_cap < 0 || (a->hist && a->hist_ld < a->hist_cap)) return MOPK_ERR_BAD_ARG;
+    if (((uintptr_t)a->pos & 3) || ((uintptr_t)a->next_ids & 3) || ((uintptr_t)a->done & 3) || ((uintptr_t)a->sum_logprobs & 3) ||
+        ((uintptr_t)a->n_tokens & 3) || ((uintptr_t)a->hist & 3))
+        return MOPK_ERR_UNSUPPORTED;
+    return MOPK_OK;
+}
+
+}  // namespace
+}  // namespace mopk
+
+using namespace mopk;
+
+extern "C" {
+
+int mopk_token_logprob_supported(const MopkTokenLogprobArgs *a) { return tl_check(a) == MOPK_OK; }
+
+int mopk_token_logprob(const MopkTokenLogprobArgs *a, void *stream) {
+    const int rc = tl_check(a);
+    if (rc != MOPK_OK) return rc;
+    if (!a->logits || !a->out) return MOPK_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->dtype == MOPK_BF16) hipLaunchKernelGGL((tl_row_kernel<unsigned short>), dim3((unsigned)a->R), dim3(TL_THREADS), 0, st, *a);
+    else hipLaunchKernelGGL((tl_row_kernel<float>), dim3((unsigned)a->R), dim3(TL_THREADS), 0, st, *a);
+    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+}
+
+int mopk_greedy_pick_supported(const MopkGreedyPickArgs *a) { return gp_check(a) == MOPK_OK; }
+
+int mopk_greedy_pick(const MopkGreedyPickArgs *a, void *stream) {
+    const int rc = gp_check(a);
+    if (rc != MOPK_OK) return rc;
+    if (!a->logits || !a->pos || !a->next_ids || !a->done || !a->sum_logprobs || !a->n_tokens) return MOPK_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->dtype == MOPK_BF16) hipLaunchKernelGGL((gp_row_kernel<unsigned short>), dim3((unsigned)a->R), dim3(TL_THREADS), 0, st, *a);
+    else hipLaunchKernelGGL((gp_row_kernel<float>), dim3((unsigned)a->R), dim3(TL_THREADS), 0, st, *a);
+    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+}
+
+}  // extern "C"

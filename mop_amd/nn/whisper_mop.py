@@ -67,6 +67,43 @@ class Transcript(NamedTuple):
     offsets: torch.Tensor
 
 
+class DecodeStats(NamedTuple):
+    """a decoding's quality figures (`generate` / `beam_search` / `sample` with return_stats=True), all on the device.
+    sum_logprobs: fp32 (B,) ((B, num_samples) from sample), the sum of log_softmax(logits)[token] over the generated tokens up to
+    and including the first eos (under logit rules: of the FILTERED rows, Whisper's convention); n_tokens: int32, same shape, how
+    many tokens that is: sum_logprobs / n_tokens is Whisper's avg_logprob; no_speech_prob: fp32 (B,), the probability of
+    no_speech_token_id at prompt position sot_index, before any logit rule; None without a token id."""
+    sum_logprobs: torch.Tensor
+    n_tokens: torch.Tensor
+    no_speech_prob: Optional[torch.Tensor]
+
+
+class TranscribeLog(NamedTuple):
+    """what `transcribe` decided for one clip's windows (return_log=True): host values, one entry per window, in order.
+    seek: the window's first frame; temperature: the one whose result was kept; avg_logprob: sum_logprobs / n_tokens of it;
+    no_speech_prob: NaN without a no_speech_token_id; compression_ratio: NaN without a callable; skipped: the no-speech skip
+    dropped the window."""
+    seek: List[int]
+    temperature: List[float]
+    avg_logprob: List[float]
+    no_speech_prob: List[float]
+    compression_ratio: List[float]
+    skipped: List[bool]
+
+
+class _Fallback(NamedTuple):
+    """transcribe's per-window policy, as checked by _fallback_check"""
+    temperatures: Tuple[float, ...]
+    logprob_threshold: Optional[float]
+    no_speech_threshold: Optional[float]
+    no_speech_token_id: Optional[int]
+    sot_index: int
+    compression_ratio_threshold: Optional[float]
+    compression_ratio: Optional[object]
+    num_samples: int
+    seed: int
+
+
 class _Batch(NamedTuple):
     """what the prompt checks need to know of the audio batch when the mel is a list: shape[0] and device"""
     shape: Tuple[int, ...]
@@ -577,6 +614,50 @@ class WhisperMoP(nn.Module):
         if rules.eos_token_id is not None and eos_token_id is not None and int(eos_token_id) != rules.eos_token_id:
             raise ValueError(f"{what}: eos_token_id = {eos_token_id}, the logit rules' eos_token_id = {rules.eos_token_id}")
 
+    def _stats_check(self, return_stats: bool, no_speech_token_id, sot_index, lens: Optional[List[int]], T_p: int, what: str,
+                     eos_token_id=None):
+        """the argument checks of a decoding with return_stats -> None when no statistics are asked for, else (no_speech_token_id
+        or None, sot_index); ValueErrors before any device work"""
+        if not return_stats:
+            return None
+        V = self.cfg.vocab_size
+        if eos_token_id is not None and (isinstance(eos_token_id, bool) or int(eos_token_id) != eos_token_id
+                                         or not 0 <= eos_token_id < V):
+            raise ValueError(f"{what}: with return_stats, eos_token_id must be None or an int in [0, vocab_size = {V}), got "
+                             f"{eos_token_id!r}")
+        if no_speech_token_id is not None and (isinstance(no_speech_token_id, bool) or not isinstance(no_speech_token_id, int)
+                                               or not 0 <= no_speech_token_id < V):
+            raise ValueError(f"{what}: no_speech_token_id must be None or an int in [0, vocab_size = {V}), got {no_speech_token_id!r}")
+        shortest = T_p if lens is None else min(lens)
+        if isinstance(sot_index, bool) or not isinstance(sot_index, int) or not 0 <= sot_index < shortest:
+            raise ValueError(f"{what}: sot_index must be an int inside the shortest prompt, [0, {shortest}), got {sot_index!r}")
+        return no_speech_token_id, sot_index
+
+    @staticmethod
+    def _no_speech_prob(prompt_logits: torch.Tensor, stats, lens: Optional[List[int]]) -> Optional[torch.Tensor]:
+        """P(no_speech_token_id) at position sot_index of every row's own prompt, from the prompt pass's logits (B, T_p, V) as
+        the decoder gave them (call it before a logit rule rewrites the last position in place): one ops.token_logprob launch on
+        a column view; a ragged batch first gathers its B rows (B slices and one stack)"""
+        tok, sot = stats
+        if tok is None:
+            return None
+        B, T_p = prompt_logits.shape[:2]
+        if lens is None or min(lens) == T_p:
+            rows = prompt_logits[:, sot]
+        else:                                                          # left-padded: row b's prompt starts at T_p - lens[b]
+            rows = torch.stack([prompt_logits[b, T_p - lens[b] + sot] for b in range(B)])
+        return ops.token_logprob(rows, tok).exp()
+
+    @staticmethod
+    def _generated_lengths(tokens: torch.Tensor, T_p: int, eos_token_id: Optional[int]) -> torch.Tensor:
+        """int32 (B,): the generated tokens of each (B, cap) row up to and including its first eos, or all of them"""
+        gen = tokens[:, T_p:]
+        n = gen.shape[1]
+        if eos_token_id is None:
+            return torch.full((gen.shape[0],), n, dtype=torch.int32, device=tokens.device)
+        j = torch.arange(n, device=tokens.device).unsqueeze(0)
+        return (torch.where(gen == eos_token_id, j, n - 1).min(1).values + 1).to(torch.int32)
+
     def with_logit_rules(self, logit_rules: Optional["ops.LogitRules"]) -> "RuledDecoding":
         """this model's decoders under Whisper's logit rules: with_logit_rules(rules).generate / .beam_search / .sample take the
         arguments of generate / beam_search / sample and apply ops.logit_rules(rules) to every step's last-position logits, on the
@@ -585,7 +666,7 @@ class WhisperMoP(nn.Module):
 
     def _replicated_cache(self, mel, mel_info, prompt_ids, lens: Optional[List[int]], cap: int, rep: int):
         """encode, run the prompt once per item and set up the cache of rep rows per item (beams / samples) for the steps after it
-        -> (prompt_ids (B, T_p) padded, prompt logits (B, V) shared by the item's rows, the step cache).  The prompt's keys / values
+        -> (prompt_ids (B, T_p) padded, the prompt pass's logits (B, T_p, V): [:, -1] is shared by the item's rows, the step cache).  The prompt's keys / values
         land in cache row b * rep (a prompt cache over the rows [::rep] of the same buffers); the step cache starts at pos = T_p,
         with the padding's kv_start per row and the audio lengths per item (an item's rows share its cross cache)."""
         H, Dh = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
@@ -599,7 +680,7 @@ class WhisperMoP(nn.Module):
         length = torch.zeros(1, dtype=torch.int32, device=enc.device)
         prompt_cache = WhisperDecodeCache(ck, cv, [t[::rep] for t in sk], [t[::rep] for t in sv], length, cap)
         prompt_cache.kv_start, prompt_cache.audio_lens = kv_start, audio_lens
-        logits = self.decode_step(prompt_cache, prompt_ids)[:, -1]
+        logits = self.decode_step(prompt_cache, prompt_ids)
         cache = WhisperDecodeCache(ck, cv, sk, sv, length, cap)
         cache.pos = T_p
         cache.kv_start = None if kv_start is None else kv_start.repeat_interleave(rep)
@@ -644,19 +725,28 @@ class WhisperMoP(nn.Module):
         1-D tensors, prompt b followed by its max_new_tokens tokens (views of one device tensor).
         mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode; it combines with a prompt list): every
         row decodes as it would alone.
-        Whisper's logit rules: with_logit_rules(rules).generate(...) takes the same arguments."""
+        Whisper's logit rules and the decoding statistics (return_stats): with_logit_rules(rules).generate(...) takes the same
+        arguments and the statistics' keywords; rules None decodes as here."""
         return self._generate(mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, None)
 
-    def _generate(self, mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, logit_rules):
+    def _generate(self, mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, logit_rules, return_stats=False,
+                  no_speech_token_id=None, sot_index=0):
         """generate's body.  logit_rules: every step's last-position logits pass ops.logit_rules before the argmax, inside the
-        captured step, over a (B, cap) int32 device history kept for them only; None runs exactly the code without them"""
+        captured step, over a (B, cap) int32 device history kept for them only; None runs exactly the code without them.
+        return_stats: the statistics route (_generate_stats) from the prompt's logits on; False runs exactly the code without it"""
         mel_info, lens, B, T_p, _ = self._decode_check(mel, prompt_ids, max_new_tokens, "generate")
         self._rules_check(logit_rules, eos_token_id, "generate")
+        stats = self._stats_check(return_stats, no_speech_token_id, sot_index, lens, T_p, "generate", eos_token_id)
         prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
         enc, _ = self.encode(mel)
         cache = self.init_decode_cache(enc, T_p + max_new_tokens)
         cache.kv_start = kv_start
-        logits = self.decode_step(cache, prompt_ids)[:, -1]
+        prompt_logits = self.decode_step(cache, prompt_ids)
+        logits = prompt_logits[:, -1]
+        if stats is not None:
+            return self._generate_stats(cache, prompt_ids, prompt_logits, lens, max_new_tokens, eos_token_id, graph, return_logits,
+                                        logit_rules, stats)
+        del prompt_logits
         hist = None
         if logit_rules is not None:
             hist = torch.zeros(B, T_p + max_new_tokens, dtype=torch.int32, device=prompt_ids.device)
@@ -701,6 +791,38 @@ class WhisperMoP(nn.Module):
             out = [out[b, T_p - lens[b]:] for b in range(B)]
         return (out, torch.stack(steps, dim=1)) if return_logits else out
 
+    def _generate_stats(self, cache, prompt_ids, prompt_logits, lens, max_new_tokens, eos_token_id, graph, return_logits,
+                        logit_rules, stats):
+        """generate's statistics route, from the prompt pass's logits on: ops.greedy_pick chooses every token on an
+        ops.GreedyState whose hist is the logit rules' history and, in the end, the tokens; a step is the decoder step, the
+        rules and the pick, all captured with graph=True"""
+        B, T_p = prompt_ids.shape
+        dev, cap = prompt_ids.device, T_p + max_new_tokens
+        no_speech = self._no_speech_prob(prompt_logits, stats, lens)                  # before the rules rewrite [:, -1] in place
+        st = ops.GreedyState(B, cap, None if eos_token_id is None else int(eos_token_id), with_hist=True, device=dev)
+        st.hist[:, :T_p] = prompt_ids
+        steps = None
+        if return_logits:
+            steps = torch.empty(B, max_new_tokens, prompt_logits.shape[-1], dtype=prompt_logits.dtype, device=dev)
+
+        def pick(lg):
+            if logit_rules is not None:
+                lg = ops.logit_rules(lg, st.hist, cache.length, T_p, logit_rules, out=lg)
+            if steps is not None:                    # at the device index of the token being chosen: the same launch every step
+                steps.index_copy_(1, cache.length.to(torch.long) - T_p, lg.unsqueeze(1))
+            ops.greedy_pick(lg, st, cache.length)
+
+        def step():
+            pick(self.decode_step(cache, st.next_ids)[:, -1])
+
+        pick(prompt_logits[:, -1])
+        self._step_loop(cache, step, max_new_tokens - 1, graph)
+        out = torch.cat([prompt_ids, st.hist[:, T_p:].to(prompt_ids.dtype)], dim=1)
+        if lens is not None:
+            out = [out[b, T_p - lens[b]:] for b in range(B)]
+        res = (out, steps) if return_logits else (out,)
+        return res + (DecodeStats(st.sum_logprobs, st.n_tokens, no_speech),)
+
     @torch.no_grad()
     def beam_search(self, mel: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int, num_beams: int,
                     eos_token_id: Optional[int] = None, length_penalty: float = 1.0, graph: bool = False):
@@ -722,17 +844,23 @@ class WhisperMoP(nn.Module):
         1-D tensors, prompt b followed by max_new_tokens tokens; gen_len counts generated tokens only, as for a tensor.
         mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode): an item's beams share its cross cache and
         its length.
-        Whisper's logit rules: with_logit_rules(rules).beam_search(...) takes the same arguments."""
+        Whisper's logit rules and the decoding statistics (return_stats): with_logit_rules(rules).beam_search(...) takes the same
+        arguments and the statistics' keywords; rules None decodes as here."""
         return self._beam_search(mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph, None)
 
-    def _beam_search(self, mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph, logit_rules):
+    def _beam_search(self, mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph, logit_rules,
+                     return_stats=False, no_speech_token_id=None, sot_index=0):
         """beam_search's body.  logit_rules: every step's logits pass ops.logit_rules before ops.beam_step, inside the captured
         step, with the beams' own histories (the first step's shared prompt logits with the rows [::K] of them); None runs exactly
         the code without them"""
         mel_info, lens, B, T_p, K = self._decode_check(mel, prompt_ids, max_new_tokens, "beam_search", ("num_beams", num_beams), 2)
         self._rules_check(logit_rules, eos_token_id, "beam_search")
+        stats = self._stats_check(return_stats, no_speech_token_id, sot_index, lens, T_p, "beam_search", eos_token_id)
         cap = T_p + max_new_tokens
-        prompt_ids, logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, K)
+        prompt_ids, prompt_logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, K)
+        no_speech = None if stats is None else self._no_speech_prob(prompt_logits, stats, lens)
+        logits = prompt_logits[:, -1]
+        del prompt_logits
         st = ops.BeamState(prompt_ids, K, cap, eos_token_id, length_penalty)
         if logit_rules is not None:
             logits = ops.logit_rules(logits, st.hist[::K], cache.length, T_p, logit_rules, out=logits)
@@ -746,10 +874,13 @@ class WhisperMoP(nn.Module):
 
         self._step_loop(cache, step, max_new_tokens - 1, graph)
         tokens, scores = ops.beam_finalize(st, max_new_tokens)
+        if stats is not None:
+            n_tokens = self._generated_lengths(tokens, T_p, eos_token_id)
+            stats = DecodeStats(scores * n_tokens.to(torch.float32) ** float(length_penalty), n_tokens, no_speech)
         tokens = tokens.to(prompt_ids.dtype)
         if lens is not None:
             tokens = [tokens[b, T_p - lens[b]:] for b in range(B)]
-        return tokens, scores
+        return (tokens, scores) if stats is None else (tokens, scores, stats)
 
     @torch.no_grad()
     def sample(self, mel: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
@@ -771,19 +902,24 @@ class WhisperMoP(nn.Module):
         mel may also be a list of B (T_b, n_mels) clips of different lengths (see encode): an item's samples share its cross cache
         and its length.
         Whisper's logit rules: with_logit_rules(rules).sample(...) takes the same arguments; sum_logprobs is then the log-softmax
-        of the FILTERED row (Whisper's convention: its filters precede the log-probabilities)."""
+        of the FILTERED row (Whisper's convention: its filters precede the log-probabilities).  The decoding statistics
+        (return_stats) are keywords of with_logit_rules(rules).sample(...) as well; rules None decodes as here."""
         return self._sample(mel, prompt_ids, max_new_tokens, temperature, top_k, top_p, num_samples, eos_token_id, seed, graph, None)
 
     def _sample(self, mel, prompt_ids, max_new_tokens, temperature, top_k, top_p, num_samples, eos_token_id, seed, graph,
-                logit_rules):
+                logit_rules, return_stats=False, no_speech_token_id=None, sot_index=0):
         """sample's body.  logit_rules: every step's logits pass ops.logit_rules before the draw, inside the captured step, with
         the samples' own token rows as history (the first draw's shared prompt logits with the rows [::num_samples] of them); the
         log-probabilities are those of the filtered row.  None runs exactly the code without them"""
         mel_info, lens, B, T_p, n = self._decode_check(mel, prompt_ids, max_new_tokens, "sample", ("num_samples", num_samples))
         ops._sample_params(temperature, top_k, top_p, "sample")                 # argument errors before encoding
         self._rules_check(logit_rules, eos_token_id, "sample")
+        stats = self._stats_check(return_stats, no_speech_token_id, sot_index, lens, T_p, "sample", eos_token_id)
         cap = T_p + max_new_tokens
-        prompt_ids, logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, n)
+        prompt_ids, prompt_logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, n)
+        no_speech = None if stats is None else self._no_speech_prob(prompt_logits, stats, lens)
+        logits = prompt_logits[:, -1]
+        del prompt_logits
         dev = prompt_ids.device
         i32 = dict(dtype=torch.int32, device=dev)
         r = torch.arange(B * n, **i32)
@@ -796,6 +932,7 @@ class WhisperMoP(nn.Module):
         sum_lp = torch.zeros(B * n, dtype=torch.float32, device=dev)
         done = torch.zeros(B * n, dtype=torch.bool, device=dev)
         eos = None if eos_token_id is None else int(eos_token_id)
+        n_tok = torch.zeros(B * n, **i32) if stats is not None and eos is not None else None
 
         def draw(lg):
             if logit_rules is not None:
@@ -809,6 +946,8 @@ class WhisperMoP(nn.Module):
                 ids.copy_(tok.unsqueeze(1))
             else:
                 sum_lp.add_(torch.where(done, torch.zeros_like(lp), lp))
+                if n_tok is not None:
+                    n_tok.add_(torch.where(done, 0, 1))
                 ids.copy_(torch.where(done, torch.full_like(tok, eos), tok).unsqueeze(1))
                 done.logical_or_(ids.squeeze(1) == eos)
             tokens.index_copy_(1, cache.length.to(torch.long), ids)
@@ -821,7 +960,11 @@ class WhisperMoP(nn.Module):
         tokens = tokens.view(B, n, cap).to(prompt_ids.dtype)
         if lens is not None:
             tokens = [tokens[b, :, T_p - lens[b]:] for b in range(B)]
-        return tokens, sum_lp.view(B, n)
+        if stats is None:
+            return tokens, sum_lp.view(B, n)
+        if n_tok is None:                                                       # no eos: every row holds all its tokens
+            n_tok = torch.full((B * n,), max_new_tokens, **i32)
+        return tokens, sum_lp.view(B, n), DecodeStats(sum_lp.view(B, n), n_tok.view(B, n), no_speech)
 
     # ---- token-level timestamps; inference only ----
     def _align_check(self, mel, tokens, prompt_len, alignment_heads, medfilt_width):
@@ -956,10 +1099,117 @@ class WhisperMoP(nn.Module):
             raise ValueError(f"{what}: prompt_ids are on {prompt_ids.device}, the mel on {mel_info.device}")
         return list(mel), window
 
+    def _fallback_check(self, T_p: int, temperatures, logprob_threshold, no_speech_threshold, no_speech_token_id, sot_index,
+                        compression_ratio_threshold, compression_ratio, num_samples, seed) -> _Fallback:
+        """the checks of transcribe's temperature fallback and no-speech skip -> the policy; ValueErrors before any device work"""
+        what = "transcribe"
+
+        def _num(x):
+            return not isinstance(x, bool) and isinstance(x, (int, float)) and x == x
+
+        if _num(temperatures):
+            temperatures = (temperatures,)
+        if not isinstance(temperatures, (list, tuple)) or len(temperatures) == 0:
+            raise ValueError(f"{what}: temperatures must be a non-empty sequence of numbers, got {temperatures!r}")
+        for i, t in enumerate(temperatures):
+            if not _num(t) or t < 0 or (i > 0 and not t > temperatures[i - 1]):
+                raise ValueError(f"{what}: temperatures must be increasing numbers >= 0, got {tuple(temperatures)!r}")
+            if t > 0:
+                ops._sample_params(t, 0, 1.0, what)
+        for name, v in (("logprob_threshold", logprob_threshold), ("no_speech_threshold", no_speech_threshold),
+                        ("compression_ratio_threshold", compression_ratio_threshold)):
+            if v is not None and not _num(v):
+                raise ValueError(f"{what}: {name} must be None or a number, got {v!r}")
+        if no_speech_threshold is not None and no_speech_token_id is None:
+            raise ValueError(f"{what}: no_speech_threshold needs no_speech_token_id")
+        if compression_ratio is not None and not callable(compression_ratio):
+            raise ValueError(f"{what}: compression_ratio must be None or a callable, got {type(compression_ratio).__name__}")
+        if compression_ratio_threshold is not None and compression_ratio is None:
+            raise ValueError(f"{what}: compression_ratio_threshold needs a compression_ratio callable (the ratio needs a tokenizer "
+                             f"and a compressor, which stay outside this library)")
+        if isinstance(num_samples, bool) or not isinstance(num_samples, int) or not 1 <= num_samples <= ops.BEAM_MAX_K:
+            raise ValueError(f"{what}: num_samples must be an int in [1, {ops.BEAM_MAX_K}], got {num_samples!r}")
+        if num_samples > 1 and not temperatures[-1] > 0:
+            raise ValueError(f"{what}: num_samples = {num_samples} needs a temperature above 0 (temperature 0 is not sampled)")
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"{what}: seed must be an int, got {seed!r}")
+        self._stats_check(True, no_speech_token_id, sot_index, None, T_p, what)
+        return _Fallback(tuple(float(t) for t in temperatures), logprob_threshold, no_speech_threshold, no_speech_token_id,
+                         sot_index, compression_ratio_threshold, compression_ratio, num_samples, seed)
+
+    def _decode_with_fallback(self, dec, wins, prompts, max_new_tokens, eos, num_beams, length_penalty, graph, pol: _Fallback,
+                              calls: List[int]):
+        """one set of windows under transcribe's policy (Whisper's decode_with_fallback, then should_skip) -> (rows (A, cap) on
+        the device, and per window, as host lists: the temperature kept, avg_logprob, no_speech_prob, compression ratio, skipped).
+        calls: a one-element list, the number of sample calls this transcribe has made so far (call k uses seed + k)."""
+        A, T_p = len(wins), prompts.shape[1]
+        dev, nan = prompts.device, float("nan")
+        kw = dict(return_stats=True, no_speech_token_id=pol.no_speech_token_id, sot_index=pol.sot_index)
+        kept = [None] * A
+        temp, avg, nsp, ratio = [pol.temperatures[0]] * A, [nan] * A, [nan] * A, [nan] * A
+        pending = list(range(A))
+        for ti, t in enumerate(pol.temperatures):
+            sub_w = [wins[i] for i in pending]
+            sub_p = prompts if len(pending) == A else torch.stack([prompts[i] for i in pending])
+            if t == 0 and num_beams > 1:
+                rows, _, st = dec.beam_search(sub_w, sub_p, max_new_tokens, num_beams, eos, length_penalty, graph, **kw)
+                a = st.sum_logprobs / st.n_tokens
+            elif t == 0:
+                rows, st = dec.generate(sub_w, sub_p, max_new_tokens, eos, graph, **kw)
+                a = st.sum_logprobs / st.n_tokens
+            else:
+                toks, _, st = dec.sample(sub_w, sub_p, max_new_tokens, temperature=t, num_samples=pol.num_samples, eos_token_id=eos,
+                                         seed=pol.seed + calls[0], graph=graph, **kw)
+                calls[0] += 1
+                every = st.sum_logprobs / st.n_tokens                  # (rows, num_samples): keep the best, ties to the first
+                best = every.argmax(1, keepdim=True)
+                a = every.gather(1, best).squeeze(1)
+                rows = toks.gather(1, best.unsqueeze(2).expand(-1, 1, toks.shape[2])).squeeze(1)
+            ns = st.no_speech_prob if st.no_speech_prob is not None else torch.full_like(a, nan)
+            host = torch.empty(len(pending), 2, dtype=torch.float32)
+            if dev.type == "cuda":
+                host = host.pin_memory()
+            host.copy_(torch.stack((a, ns.to(torch.float32)), dim=1))               # the attempt's one fp32 copy to the host
+            gen = rows[:, T_p:].to(torch.int64).cpu() if pol.compression_ratio is not None else None
+            for k, (i, (ak, nk)) in enumerate(zip(pending, host.tolist())):
+                kept[i], temp[i], avg[i], nsp[i] = rows[k], t, ak, nk
+                if gen is not None:
+                    hit = (gen[k] == eos).nonzero()
+                    ratio[i] = float(pol.compression_ratio(gen[k, :int(hit[0])] if hit.numel() else gen[k]))
+            if ti + 1 == len(pol.temperatures):
+                break                                                  # the last temperature's result is kept whatever it is
+            again = []
+            for i in pending:
+                need = ((pol.compression_ratio_threshold is not None and ratio[i] > pol.compression_ratio_threshold)
+                        or (pol.logprob_threshold is not None and avg[i] < pol.logprob_threshold))
+                if (need and pol.no_speech_threshold is not None and pol.logprob_threshold is not None
+                        and nsp[i] > pol.no_speech_threshold and avg[i] < pol.logprob_threshold):
+                    need = False                                       # silence: a higher temperature would not help
+                if need:
+                    again.append(i)
+            pending = again
+            if not pending:
+                break
+        skipped = [pol.no_speech_threshold is not None and nsp[i] > pol.no_speech_threshold
+                   and not (pol.logprob_threshold is not None and avg[i] > pol.logprob_threshold) for i in range(A)]
+        rows = kept[0].unsqueeze(0) if A == 1 else torch.stack(kept)
+        return rows, temp, avg, nsp, ratio, skipped
+
     @torch.no_grad()
     def transcribe(self, mel, prompt_ids: torch.Tensor, logit_rules: "ops.LogitRules", max_new_tokens: int, *,
                    window: Optional[int] = None, frames_per_timestamp: int = 1, num_beams: int = 1, length_penalty: float = 1.0,
                    graph: bool = False) -> List[Transcript]:
+        """long-form transcription: the window loop that with_logit_rules(logit_rules).transcribe documents, without the
+        temperature fallback and the no-speech skip (their keywords are that method's; this signature is pinned)."""
+        return self._transcribe(mel, prompt_ids, logit_rules, max_new_tokens, window=window, frames_per_timestamp=frames_per_timestamp,
+                                num_beams=num_beams, length_penalty=length_penalty, graph=graph)
+
+    def _transcribe(self, mel, prompt_ids: torch.Tensor, logit_rules: "ops.LogitRules", max_new_tokens: int, *,
+                    window: Optional[int] = None, frames_per_timestamp: int = 1, num_beams: int = 1, length_penalty: float = 1.0,
+                    graph: bool = False, temperatures=(0.0,), logprob_threshold: Optional[float] = None,
+                    no_speech_threshold: Optional[float] = None, no_speech_token_id: Optional[int] = None, sot_index: int = 0,
+                    compression_ratio_threshold: Optional[float] = None, compression_ratio=None, num_samples: int = 1,
+                    seed: int = 0, return_log: bool = False):
         """long-form transcription, Whisper's transcribe loop over windows for a batch of clips -> a list of B Transcript(starts,
         ends, tokens, offsets), all on the device.
 
@@ -976,11 +1226,44 @@ class WhisperMoP(nn.Module):
         views); seek_b += advance, and the window's segments join item b's transcript, their frames shifted by the window's
         seek_b.  advance >= 1, so the loop ends after at most T_b windows.  The tokens behind a
         window's last cut are in no segment: the next window starts at that cut and decodes them again.
-        Out of scope: conditioning a window on the previous window's text, the temperature fallback, the no-speech skip, word
-        grouping, and sampling."""
+
+        The temperature fallback and the no-speech skip (Whisper's decode_with_fallback and should_skip).  With every argument
+        below at its default the loop above is all that runs, and no statistics are asked of the decoders.  Otherwise every
+        decoder call runs with return_stats=True, and per set of windows:
+        1. all active rows decode at temperatures[0]: temperature 0 is generate (beam_search with num_beams > 1), a temperature
+           above 0 is sample(temperature, num_samples), of whose samples the one with the largest avg_logprob = sum_logprobs /
+           n_tokens is kept (ties to the smaller index);
+        2. a row needs fallback when compression_ratio_threshold is set and its ratio exceeds it, or logprob_threshold is set and
+           its avg_logprob is below it;
+        3. unless no_speech_threshold and logprob_threshold are both set, its no_speech_prob > no_speech_threshold and its
+           avg_logprob < logprob_threshold (silence);
+        4. the rows that still need it decode again, as a smaller batch of their own windows, at the next temperature; the last
+           temperature's result is kept whatever it is;
+        5. with no_speech_threshold set, a row whose final no_speech_prob > no_speech_threshold is skipped, unless
+           logprob_threshold is set and its avg_logprob > logprob_threshold: it adds no segments and no tokens, and its seek moves
+           by the window's length.
+        no_speech_prob: the probability of no_speech_token_id at position sot_index of the prompt, before the logit rules.
+        compression_ratio: a callable from a 1-D CPU int64 tensor (the generated tokens before the first eos) to a float (Whisper's
+        ratio needs a tokenizer and zlib, which stay outside this library); only with it does a window's token row go to the
+        host.  The k-th sample call this transcribe makes uses seed + k.  Sampled results depend on the batch's composition (as
+        sample's own do: its draw is a function of the row index), so on which rows fell back together.  Every decoding attempt
+        adds ONE (rows, 2) fp32 copy to pinned host memory (avg_logprob, no_speech_prob) to the (A, 3) int32 one per set of
+        windows, plus the token rows when compression_ratio is given.  A fallback attempt encodes its windows again (the decoders
+        take mel).  return_log=True also returns a list of B TranscribeLog, one entry per window.
+        ValueError before any device work: temperatures empty, not increasing, negative or NaN; no_speech_threshold without
+        no_speech_token_id; compression_ratio_threshold without compression_ratio; num_samples outside [1, 8], or above 1 with no
+        temperature above 0; sot_index outside the prompt; no_speech_token_id outside the vocabulary.
+        Out of scope: conditioning a window on the previous window's text, word grouping, top-k / top-p inside transcribe, handing
+        the encoded audio over to a fallback attempt, and a device-side compression ratio."""
         clips, W = self._transcribe_check(mel, prompt_ids, logit_rules, max_new_tokens, window, frames_per_timestamp, num_beams,
                                            length_penalty)
+        pol = self._fallback_check(prompt_ids.shape[-1], temperatures, logprob_threshold, no_speech_threshold, no_speech_token_id,
+                                   sot_index, compression_ratio_threshold, compression_ratio, num_samples, seed)
+        plain = (pol.temperatures == (0.0,) and logprob_threshold is None and no_speech_threshold is None
+                 and no_speech_token_id is None and compression_ratio is None and not return_log)
+        calls = [0]
         dev, B, dec = clips[0].device, len(clips), self.with_logit_rules(logit_rules)
+        logs = [TranscribeLog([], [], [], [], [], []) for _ in range(B)]
         tb, eos = logit_rules.timestamp_begin, logit_rules.eos_token_id
         T_p = prompt_ids.shape[-1]
         total = [int(c.shape[0]) for c in clips]
@@ -995,7 +1278,14 @@ class WhisperMoP(nn.Module):
                 prompts = prompt_ids.unsqueeze(0).expand(len(act), -1)
             else:
                 prompts = prompt_ids if len(act) == B else torch.stack([prompt_ids[b] for b in act])
-            if num_beams > 1:
+            skipped = None
+            if not plain:
+                rows, temp, avg, nsp, ratio, skipped = self._decode_with_fallback(
+                    dec, wins, prompts, max_new_tokens, eos, num_beams, length_penalty, graph, pol, calls)
+                for a, b in enumerate(act):
+                    for field, v in zip(logs[b], (seek[b], temp[a], avg[a], nsp[a], ratio[a], skipped[a])):
+                        field.append(v)
+            elif num_beams > 1:
                 rows, _ = dec.beam_search(wins, prompts, max_new_tokens, num_beams, eos, length_penalty, graph)
             else:
                 rows = dec.generate(wins, prompts, max_new_tokens, eos, graph)
@@ -1009,6 +1299,8 @@ class WhisperMoP(nn.Module):
             meta.copy_(torch.stack((seg.advance, seg.n_segments, spanned.to(torch.int32)), dim=1))      # the one synchronisation
             for a, (adv, n, m) in enumerate(meta.tolist()):
                 b = act[a]
+                if skipped is not None and skipped[a]:                 # no speech: nothing joins the transcript, seek moves on
+                    adv, n, m = int(wins[a].shape[0]), 0, 0
                 st, en, tk, off = parts[b]
                 st.append(seg.starts[a, :n] + seek[b])
                 en.append(seg.ends[a, :n] + seek[b])
@@ -1020,18 +1312,22 @@ class WhisperMoP(nn.Module):
         for b, (st, en, tk, off) in enumerate(parts):
             off.append(torch.full((1,), n_tok[b], dtype=torch.int32, device=dev))
             out.append(Transcript(torch.cat(st), torch.cat(en), torch.cat(tk), torch.cat(off)))
-        return out
+        return (out, logs) if return_log else out
 
     @torch.no_grad()
     def transcribe_audio(self, audio, frontend: "LogMelFrontend", prompt_ids: torch.Tensor, logit_rules: "ops.LogitRules",
-                         max_new_tokens: int, **transcribe_kwargs) -> List[Transcript]:
+                         max_new_tokens: int, **transcribe_kwargs):
         """`transcribe` from waveforms: audio (a (B, L) tensor or a list of B 1-D clips, see LogMelFrontend.forward) goes through
-        frontend, the mel it returns through transcribe(mel, prompt_ids, logit_rules, max_new_tokens, **transcribe_kwargs).
-        A segment's frames times frontend.frame_seconds are seconds.  ValueError when frontend.n_mels is not the model's."""
+        frontend, the mel it returns through with_logit_rules(logit_rules).transcribe(mel, prompt_ids, max_new_tokens, **transcribe_kwargs)
+        -> a list of Transcript (with return_log=True: that list and the logs).  It runs the loop itself, not through the public
+        `transcribe`, whose pinned signature cannot take the policy's keywords: a subclass that overrides `transcribe` overrides
+        `_transcribe` for this entry point.
+        Every keyword of transcribe passes through (the temperature fallback and the no-speech skip included; with return_log=True
+        the logs come back beside the transcripts).  A segment's frames times frontend.frame_seconds are seconds.  ValueError when frontend.n_mels is not the model's."""
         if not isinstance(frontend, LogMelFrontend) or frontend.n_mels != self.cfg.n_mels:
             raise ValueError(f"transcribe_audio: frontend must be a LogMelFrontend with n_mels = {self.cfg.n_mels} (the model's), got "
                              f"{getattr(frontend, 'n_mels', type(frontend).__name__)!r}")
-        return self.transcribe(frontend(audio), prompt_ids, logit_rules, max_new_tokens, **transcribe_kwargs)
+        return self._transcribe(frontend(audio), prompt_ids, logit_rules, max_new_tokens, **transcribe_kwargs)
 
     @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):
@@ -1105,8 +1401,9 @@ class LogMelFrontend(nn.Module):
 class RuledDecoding:
     """`WhisperMoP.with_logit_rules(rules)`: the model's three decoders with Whisper's logit rules (ops.LogitRules: the never-emit
     list, blank suppression at the first generated position, the timestamp grammar) applied to every step's last-position logits
-    by ops.logit_rules, one HIP launch inside the step.  The decoders' own signatures do not change; each method here takes the
-    arguments of the method it names.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
+    by ops.logit_rules, one HIP launch inside the step.  The decoders' own signatures do not change (their tests pin them); each
+    method here takes the arguments of the method it names, and what came later as keywords of its own: the decoding statistics
+    (return_stats, no_speech_token_id, sot_index) and, on transcribe, the temperature fallback and the no-speech skip.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
     (ValueError).  logit_rules None runs the plain decoder: no extra launch, no extra buffer."""
 
     def __init__(self, model: WhisperMoP, logit_rules: Optional["ops.LogitRules"]):
@@ -1115,26 +1412,47 @@ class RuledDecoding:
 
     @torch.no_grad()
     def generate(self, mel, prompt_ids, max_new_tokens: int, eos_token_id: Optional[int] = None, graph: bool = False, *,
-                 return_logits: bool = False):
+                 return_logits: bool = False, return_stats: bool = False, no_speech_token_id: Optional[int] = None,
+                 sot_index: int = 0):
         """WhisperMoP.generate under the rules: the filter runs before the argmax, over a (B, cap) int32 device history kept for
-        it; return_logits returns the FILTERED logits, the ones that chose the token"""
-        return self.model._generate(mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, self.logit_rules)
+        it; return_logits returns the FILTERED logits, the ones that chose the token; return_stats adds up the log-softmax of the
+        FILTERED rows (Whisper's convention), while no_speech_prob is read before the filter"""
+        return self.model._generate(mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, self.logit_rules,
+                                    return_stats, no_speech_token_id, sot_index)
 
     @torch.no_grad()
     def beam_search(self, mel, prompt_ids, max_new_tokens: int, num_beams: int, eos_token_id: Optional[int] = None,
-                    length_penalty: float = 1.0, graph: bool = False):
+                    length_penalty: float = 1.0, graph: bool = False, *, return_stats: bool = False,
+                    no_speech_token_id: Optional[int] = None, sot_index: int = 0):
         """WhisperMoP.beam_search under the rules: the filter runs before ops.beam_step, on the beams' own histories, so the
-        candidates' log-probabilities are those of the filtered rows"""
+        candidates' log-probabilities are those of the filtered rows (no_speech_prob is read before the filter)"""
         return self.model._beam_search(mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph,
-                                       self.logit_rules)
+                                       self.logit_rules, return_stats, no_speech_token_id, sot_index)
 
     @torch.no_grad()
     def sample(self, mel, prompt_ids, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-               num_samples: int = 1, eos_token_id: Optional[int] = None, seed: int = 0, graph: bool = False):
+               num_samples: int = 1, eos_token_id: Optional[int] = None, seed: int = 0, graph: bool = False, *,
+               return_stats: bool = False, no_speech_token_id: Optional[int] = None, sot_index: int = 0):
         """WhisperMoP.sample under the rules: the filter runs before the draw; sum_logprobs adds the log-softmax of the FILTERED
-        row (Whisper's convention: its filters precede the log-probabilities)"""
+        row (Whisper's convention: its filters precede the log-probabilities; no_speech_prob is read before the filter)"""
         return self.model._sample(mel, prompt_ids, max_new_tokens, temperature, top_k, top_p, num_samples, eos_token_id, seed,
-                                  graph, self.logit_rules)
+                                  graph, self.logit_rules, return_stats, no_speech_token_id, sot_index)
+
+    @torch.no_grad()
+    def transcribe(self, mel, prompt_ids: torch.Tensor, max_new_tokens: int, *, window: Optional[int] = None,
+                   frames_per_timestamp: int = 1, num_beams: int = 1, length_penalty: float = 1.0, graph: bool = False,
+                   temperatures=(0.0,), logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None,
+                   no_speech_token_id: Optional[int] = None, sot_index: int = 0, compression_ratio_threshold: Optional[float] = None,
+                   compression_ratio=None, num_samples: int = 1, seed: int = 0, return_log: bool = False):
+        return self.model._transcribe(
+            mel, prompt_ids, self.logit_rules, max_new_tokens, window=window, frames_per_timestamp=frames_per_timestamp,
+            num_beams=num_beams, length_penalty=length_penalty, graph=graph, temperatures=temperatures,
+            logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold, no_speech_token_id=no_speech_token_id,
+            sot_index=sot_index, compression_ratio_threshold=compression_ratio_threshold, compression_ratio=compression_ratio,
+            num_samples=num_samples, seed=seed, return_log=return_log)
+
+
+RuledDecoding.transcribe.__doc__ = WhisperMoP._transcribe.__doc__
 
 
 def create_whisper_mop(cfg: WhisperConfig) -> WhisperMoP:

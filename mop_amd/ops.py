@@ -1961,8 +1961,8 @@ def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     return _da_run("decode_attention_lens", q, k_cache, v_cache, kv_lens=kv_lens, nk=nk)
 
 
-# ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, alignment_cost, dtw_align,
-# timestamp_segments ----
+# ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, token_logprob, greedy_pick,
+# alignment_cost, dtw_align, timestamp_segments ----
 # Each is its _*_check (every ValueError, once per call), its _*_accept (the tensor-side tests, then the args struct, built once,
 # if the library's _supported query takes it, else None), then the torch restatement, or the outputs into that struct and _row_launch.
 def _row_launch(a, sym: str, key: str, dev=None, ws_sym: Optional[str] = None) -> None:
@@ -2598,6 +2598,239 @@ def logit_rules(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0:
             a.out, a.out_ld = out.data_ptr(), out.stride(0)                        # in place of the stand-in
         _row_launch(a, "mopk_logit_rules", "logit_rules")
         return out
+
+
+# ---- per-step decoding statistics (mopk_token_logprob, mopk_greedy_pick; WhisperMoP's return_stats, transcribe's fallback) ----
+def _is_index(x) -> bool:
+    return not isinstance(x, bool) and isinstance(x, int)
+
+
+def _stat_logits_check(logits, what: str) -> None:
+    if (not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 2
+            or not logits.dtype.is_floating_point):
+        raise ValueError(f"{what}: logits must be a floating (rows, V) tensor with V >= 2, got "
+                         f"{(tuple(logits.shape), logits.dtype) if isinstance(logits, torch.Tensor) else type(logits).__name__}")
+
+
+def _stat_logits_ok(logits: torch.Tensor) -> bool:
+    """the tensor-side tests the two kernels share: CUDA fp32 / bf16, unit inner stride, a row stride >= V (one row: any)"""
+    R, V = logits.shape
+    return (logits.is_cuda and logits.dtype in (torch.float32, torch.bfloat16) and logits.stride(1) == 1
+            and (R == 1 or logits.stride(0) >= V))
+
+
+def _tl_check(logits, tokens, out, what: str) -> None:
+    """validate a token_logprob call before any device work"""
+    _stat_logits_check(logits, what)
+    R, V = logits.shape
+    if isinstance(tokens, torch.Tensor):
+        if tuple(tokens.shape) != (R,) or tokens.dtype.is_floating_point or tokens.dtype.is_complex or tokens.dtype == torch.bool:
+            raise ValueError(f"{what}: tokens must be an integer ({R},) tensor or an int, got {tuple(tokens.shape)} {tokens.dtype}")
+        if tokens.device != logits.device:
+            raise ValueError(f"{what}: tokens are on {tokens.device}, the logits on {logits.device}")
+        if not tokens.is_cuda and bool(((tokens < 0) | (tokens >= V)).any()):          # host values: the host can know
+            raise ValueError(f"{what}: a token lies outside [0, V = {V})")
+    elif not _is_index(tokens) or not 0 <= tokens < V:
+        raise ValueError(f"{what}: tokens must be an integer ({R},) tensor or an int in [0, V = {V}), got {tokens!r}")
+    if out is not None and (tuple(out.shape) != (R,) or out.dtype != torch.float32 or out.device != logits.device):
+        raise ValueError(f"{what}: out must be an fp32 ({R},) tensor on {logits.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+
+
+def token_logprob_torch(logits: torch.Tensor, tokens, out=None) -> torch.Tensor:
+    """the restatement of `token_logprob` in torch ops (no host sync): log_softmax(logits.float(), -1) gathered at the tokens
+    (a device token outside [0, V) is clamped, as in the kernel)"""
+    _tl_check(logits, tokens, out, "token_logprob_torch")
+    R, V = logits.shape
+    if not isinstance(tokens, torch.Tensor):
+        tokens = torch.full((R,), tokens, dtype=torch.long, device=logits.device)
+    lp = torch.log_softmax(logits.float(), -1).gather(1, tokens.to(torch.long).clamp(0, V - 1).unsqueeze(1)).squeeze(1)
+    if out is None:
+        return lp
+    out.copy_(lp)
+    return out
+
+
+def _tl_accept(logits, tokens, out):
+    """the args struct of a call that mopk_token_logprob takes, None of one it refuses; out None: the result buffer is left NULL
+    (the query looks at its alignment only; the launcher fills it in)"""
+    if not _stat_logits_ok(logits):
+        return None
+    a = L.TokenLogprobArgs()
+    a.R, a.V = logits.shape
+    a.dtype = L.MOPK_BF16 if logits.dtype == torch.bfloat16 else L.MOPK_F32
+    a.logits, a.logits_ld = logits.data_ptr(), a.V if a.R == 1 else logits.stride(0)   # a single row: its stride is never used
+    if isinstance(tokens, torch.Tensor):
+        if not tokens.is_cuda or tokens.dtype != torch.int32 or not tokens.is_contiguous():
+            return None
+        a.tokens = tokens.data_ptr()
+    else:
+        a.token = tokens
+    if out is not None and not (out.is_cuda and out.is_contiguous()):
+        return None
+    if out is not None:
+        a.out = out.data_ptr()
+    return a if L.lib().mopk_token_logprob_supported(C.byref(a)) else None
+
+
+def token_logprob_supported(logits: torch.Tensor, tokens, out=None) -> bool:
+    """True if mopk_token_logprob takes this call: CUDA fp32 / bf16 logits with unit inner stride and a row stride >= V (one
+    row: any), tokens an int or a contiguous CUDA int32 tensor, a contiguous CUDA out (the library's own query decides the
+    rest).  Raises ValueError on bad arguments."""
+    _tl_check(logits, tokens, out, "token_logprob_supported")
+    return _tl_accept(logits, tokens, out) is not None
+
+
+def token_logprob(logits: torch.Tensor, tokens, out=None) -> torch.Tensor:
+    """the log-probability of one token per row -> fp32 (R,): out[r] = float(logits[r, tokens[r]]) - lse(logits[r]), in fp32.
+    Inference only.
+
+    logits: (R, V) fp32 or bf16, any row stride >= V (a column of a (B, T, V) tensor is one).  tokens: an int32 (R,) tensor on the
+    logits' device, or one int for every row.  -inf entries add nothing to the lse; a token whose own entry is -inf gives -inf.  A
+    row without a finite entry is outside the contract (its value is unspecified).  A token outside [0, V) is a ValueError where
+    the host can see it (an int, a CPU tensor); a device token is clamped into the row.  out: a static fp32 (R,) result buffer.
+    Runs the HIP kernel (mopk_token_logprob: one launch) when token_logprob_supported() accepts the call, else
+    token_logprob_torch(); LAST_PATH["token_logprob"] records which.  No host sync; bitwise reproducible."""
+    _tl_check(logits, tokens, out, "token_logprob")
+    with torch.no_grad():
+        a = _tl_accept(logits, tokens, out)
+        if a is None:
+            LAST_PATH["token_logprob"] = L.PATH_GENERIC
+            return token_logprob_torch(logits, tokens, out)
+        if out is None:
+            out = torch.empty(a.R, dtype=torch.float32, device=logits.device)
+            a.out = out.data_ptr()
+        _row_launch(a, "mopk_token_logprob", "token_logprob")
+        return out
+
+
+class GreedyState:
+    """Device state of a greedy decoding of B rows, updated in place by `greedy_pick` (no host sync, static buffers: a step can be
+    captured in a graph).
+
+    next_ids (B, 1) int32: the newest tokens (the next decoder step's ids); done (B,) int32: the row has emitted eos_token_id;
+    sum_logprobs (B,) fp32: the sum of log_softmax(logits)[token] over the row's tokens up to and including its first eos;
+    n_tokens (B,) int32: how many tokens that sum holds (sum_logprobs / n_tokens is Whisper's avg_logprob); hist (B, cap) int32
+    with with_hist, else None: the token history, written at column pos by every pick (a caller fills the prompt's columns)."""
+
+    def __init__(self, B: int, cap: int, eos_token_id: Optional[int] = None, with_hist: bool = False, device=None):
+        if not _is_index(B) or not _is_index(cap) or B < 1 or cap < 1:
+            raise ValueError(f"GreedyState: B and cap must be ints >= 1, got B = {B!r}, cap = {cap!r}")
+        if eos_token_id is not None and (not _is_index(eos_token_id) or eos_token_id < 0):
+            raise ValueError(f"GreedyState: eos_token_id must be None or an int >= 0, got {eos_token_id!r}")
+        self.B, self.cap, self.eos = B, cap, eos_token_id
+        i32 = dict(dtype=torch.int32, device=device)
+        self.next_ids = torch.zeros(B, 1, **i32)
+        self.done = torch.zeros(B, **i32)
+        self.sum_logprobs = torch.zeros(B, dtype=torch.float32, device=device)
+        self.n_tokens = torch.zeros(B, **i32)
+        self.hist = torch.zeros(B, cap, **i32) if with_hist else None
+
+
+def _gp_check(logits, state, pos, what: str) -> None:
+    """validate a greedy_pick call before any device work"""
+    if not isinstance(state, GreedyState):
+        raise ValueError(f"{what}: state must be a GreedyState, got {type(state).__name__}")
+    _stat_logits_check(logits, what)
+    R, V = logits.shape
+    if R != state.B:
+        raise ValueError(f"{what}: {R} logit rows for a state of B = {state.B} rows")
+    if state.eos is not None and state.eos >= V:
+        raise ValueError(f"{what}: the state's eos_token_id = {state.eos} outside [0, V = {V})")
+    if not isinstance(pos, torch.Tensor) or pos.numel() != 1 or pos.dtype.is_floating_point or pos.dtype == torch.bool:
+        raise ValueError(f"{what}: pos must hold one integer, got "
+                         f"{(tuple(pos.shape), pos.dtype) if isinstance(pos, torch.Tensor) else type(pos).__name__}")
+    h = state.hist
+    if h is not None:
+        if h.dim() != 2 or h.shape[0] != R or h.dtype != torch.int32:
+            raise ValueError(f"{what}: the state's hist must be an int32 ({R}, cap) tensor, got {tuple(h.shape)} {h.dtype}")
+        if not pos.is_cuda and not 0 <= int(pos) < h.shape[1]:                        # a host value: the host can know
+            raise ValueError(f"{what}: pos = {int(pos)} outside the history's columns [0, {h.shape[1]})")
+    for name, t, dt, shape in (("next_ids", state.next_ids, torch.int32, (R, 1)), ("done", state.done, torch.int32, (R,)),
+                               ("sum_logprobs", state.sum_logprobs, torch.float32, (R,)), ("n_tokens", state.n_tokens, torch.int32, (R,))):
+        if tuple(t.shape) != shape or t.dtype != dt:
+            raise ValueError(f"{what}: the state's {name} must be {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+    for t in (pos, state.next_ids, state.done, state.sum_logprobs, state.n_tokens) + (() if h is None else (h,)):
+        if t.device != logits.device:
+            raise ValueError(f"{what}: pos and the state must be on the logits' device {logits.device}, found {t.device}")
+
+
+def greedy_pick_torch(logits: torch.Tensor, state: GreedyState, pos: torch.Tensor) -> None:
+    """the restatement of `greedy_pick` in torch ops (no host sync): log_softmax(logits.float(), -1), argmax, where"""
+    _gp_check(logits, state, pos, "greedy_pick_torch")
+    x = logits.float()
+    lp = torch.log_softmax(x, -1)
+    tok = x.argmax(-1)
+    add = lp.gather(1, tok.unsqueeze(1)).squeeze(1)
+    if state.eos is not None:
+        live = state.done == 0
+        tok = torch.where(live, tok, torch.full_like(tok, state.eos))
+        add = torch.where(live, add, torch.zeros_like(add))
+        state.n_tokens.add_(live.to(torch.int32))
+        state.done.logical_or_(live & (tok == state.eos))
+    else:
+        state.n_tokens.add_(1)
+    state.sum_logprobs.add_(add)
+    state.next_ids.copy_(tok.unsqueeze(1))
+    if state.hist is not None:
+        cap = state.hist.shape[1]
+        p = pos.reshape(1).to(torch.long)
+        col = state.hist.index_select(1, p.clamp(0, cap - 1)).squeeze(1)
+        inside = ((p >= 0) & (p < cap)).expand_as(col)
+        state.hist.index_copy_(1, p.clamp(0, cap - 1), torch.where(inside, tok.to(torch.int32), col).unsqueeze(1))
+
+
+def _gp_accept(logits, state, pos):
+    """the args struct of a call that mopk_greedy_pick takes, None of one it refuses"""
+    if not _stat_logits_ok(logits):
+        return None
+    if not pos.is_cuda or pos.dtype != torch.int32:
+        return None
+    if not all(t.is_cuda and t.is_contiguous() for t in (state.next_ids, state.done, state.sum_logprobs, state.n_tokens)):
+        return None
+    a = L.GreedyPickArgs()
+    a.R, a.V = logits.shape
+    a.dtype = L.MOPK_BF16 if logits.dtype == torch.bfloat16 else L.MOPK_F32
+    a.eos = -1 if state.eos is None else state.eos
+    a.logits, a.logits_ld, a.pos = logits.data_ptr(), a.V if a.R == 1 else logits.stride(0), pos.data_ptr()
+    a.next_ids, a.done = state.next_ids.data_ptr(), state.done.data_ptr()
+    a.sum_logprobs, a.n_tokens = state.sum_logprobs.data_ptr(), state.n_tokens.data_ptr()
+    h = state.hist
+    if h is not None:
+        cap = h.shape[1]
+        if not h.is_cuda or (cap > 1 and h.stride(1) != 1) or (a.R > 1 and h.stride(0) < cap):
+            return None
+        a.hist, a.hist_cap, a.hist_ld = h.data_ptr(), cap, cap if a.R == 1 else h.stride(0)
+    return a if L.lib().mopk_greedy_pick_supported(C.byref(a)) else None
+
+
+def greedy_pick_supported(logits: torch.Tensor, state: GreedyState, pos: torch.Tensor) -> bool:
+    """True if mopk_greedy_pick takes this call: CUDA fp32 / bf16 logits with unit inner stride and a row stride >= V (one row:
+    any), an int32 device pos, a CUDA state whose hist (if any) has unit inner stride and a row stride >= cap (the library's own
+    query decides the rest).  Raises ValueError on bad arguments."""
+    _gp_check(logits, state, pos, "greedy_pick_supported")
+    return _gp_accept(logits, state, pos) is not None
+
+
+def greedy_pick(logits: torch.Tensor, state: GreedyState, pos: torch.Tensor) -> None:
+    """one greedy decoding step (Whisper's GreedyDecoder.update): update `state` in place from the step's last-position logits.
+    Inference only.
+
+    logits: (B, V) fp32 or bf16, any row stride >= V.  pos: (1,) int32 device tensor, the history column of the new tokens (the
+    decoder cache's length after the step that produced the logits; what `logit_rules` takes).  Per row r:
+    - state.done[r] != 0 (and the state has an eos): the token is eos; sum_logprobs, n_tokens and done stay;
+    - else the token is argmax logits[r], ties to the smaller index (torch.argmax); sum_logprobs[r] += float(logits[r, token]) -
+      lse(logits[r]) in fp32; n_tokens[r] += 1; done[r] |= token == eos;
+    - next_ids[r] = token, and hist[r, pos] = token when the state has a hist (pos outside its columns writes nothing).
+    The first eos is counted in the sum and in the length, nothing behind it.  Runs the HIP kernel (mopk_greedy_pick: one launch)
+    when greedy_pick_supported() accepts the call, else greedy_pick_torch(); LAST_PATH["greedy_pick"] records which.  No host
+    sync; bitwise reproducible."""
+    _gp_check(logits, state, pos, "greedy_pick")
+    with torch.no_grad():
+        a = _gp_accept(logits, state, pos)
+        if a is None:
+            LAST_PATH["greedy_pick"] = L.PATH_GENERIC
+            return greedy_pick_torch(logits, state, pos)
+        _row_launch(a, "mopk_greedy_pick", "greedy_pick")
 
 
 # --------------------------------------------------------------------------------------
