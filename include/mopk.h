@@ -806,6 +806,67 @@ int mopk_timestamp_segments_supported(const MopkTimestampSegmentsArgs *a);   /* 
 int mopk_timestamp_segments(const MopkTimestampSegmentsArgs *a, void *stream);
 
 /* --------------------------------------------------------------------------
+ * Conditioning a window on the previous text (WhisperMoP.transcribe with condition_on_previous_text / initial_prompt; Whisper's
+ * all_tokens[prompt_reset_since:] and its n_ctx // 2 - 1 cap).  (Added under version 118: new exports only; callers detect them
+ * with the _supported queries.)  The state: hist (B, n) int32, contiguous, and hist_len (B) int32: hist[b, :hist_len[b]] holds
+ * the last tokens of clip b's transcript since its last reset, n is the cap.  Everywhere L = hist_len[b] clamped into [0, n].
+ *
+ * mopk_prompt_history_update, in place.  Row a (0 <= a < A) reads tokens + a * tokens_ld + T0 ...; b = item[a]; a row with b outside
+ * [0, B) is skipped.  m = n_take[a] clamped into [0, T - T0].
+ *   mode[a] == 0: c = hist[b, :L] followed by tokens[a, T0 : T0 + m];  keep = min(n, L + m);  hist[b, :keep] = the last keep
+ *                 entries of c;  hist_len[b] = keep.  hist[b, keep:] is left as it is.
+ *   mode[a] == 1: hist_len[b] = 0 (hist is left as it is).
+ *   any other value: clip b is left untouched.
+ * The item values of one call must be distinct (two rows of one clip race; every access stays inside the buffers).  One workgroup
+ * per row, one thread per history entry: thread j reads the entry that ends up at hist[b, j] into a register, a barrier follows
+ * the last read, then every thread writes (the shift is in place).  Takes n <= 1024 and T - T0 <= 1024.
+ *
+ * mopk_window_prompts builds the left-padded prompt matrix ids (A, width) and kv_start (A) of a set of windows.  Row a: b = item[a]
+ * (outside [0, B): the row has no history and reads the sot row of the nearest clip), room = width - Ts,
+ *   h = min(L, room - 1) if L > 0 and room >= 2, else 0;   length = Ts + (h > 0 ? 1 + h : 0);   kv_start[a] = width - length;
+ *   ids[a] = kv_start[a] zeros, then prev and hist[b, L - h : L] when h > 0, then the Ts tokens sot + b * sot_ld ...
+ * (sot_ld == 0: one sot sequence for every clip).  One workgroup per row strides over the columns; thread 0 writes kv_start.
+ * Takes width <= 2048.
+ * Both: integers only, every word has one writer, no atomics, no workspace, no host synchronisation. */
+typedef struct MopkPromptHistoryArgs {
+    int32_t A;                           /* rows of tokens */
+    int32_t B;                           /* clips */
+    int32_t n;                           /* history cap, >= 1 */
+    int32_t T;                           /* columns of tokens */
+    int32_t T0;                          /* first generated column, 0 <= T0 < T */
+    int32_t reserved;
+    int32_t *hist;                       /* device (B, n) int32, contiguous, in place */
+    int32_t *hist_len;                   /* device (B), in place */
+    const int32_t *tokens;               /* device (A rows of T) int32 */
+    int64_t tokens_ld;                   /* element stride between rows, >= T */
+    const int32_t *n_take;               /* device (A): tokens of row a that join the history */
+    const int32_t *item;                 /* device (A): the clip of row a, distinct */
+    const int32_t *mode;                 /* device (A): 0 append, 1 reset, else leave */
+} MopkPromptHistoryArgs;
+int mopk_prompt_history_update_supported(const MopkPromptHistoryArgs *a);    /* 1 if the kernel takes this call (n, T - T0, alignment) */
+int mopk_prompt_history_update(const MopkPromptHistoryArgs *a, void *stream);
+
+typedef struct MopkWindowPromptsArgs {
+    int32_t A;                           /* rows of ids */
+    int32_t B;                           /* clips */
+    int32_t n;                           /* history cap, >= 1 */
+    int32_t width;                       /* columns of ids, >= Ts */
+    int32_t Ts;                          /* tokens of the sot sequence, >= 1 */
+    int32_t prev;                        /* the token in front of the history (Whisper's sot_prev) */
+    int32_t out_i64;                     /* ids holds int64 (1) or int32 (0) */
+    int32_t sot_i64;                     /* sot holds int64 (1) or int32 (0) */
+    const int32_t *hist;                 /* device (B, n) int32, contiguous */
+    const int32_t *hist_len;             /* device (B) */
+    const int32_t *item;                 /* device (A): the clip of row a */
+    const void *sot;                     /* device (Ts), or (B rows of Ts) with sot_ld */
+    int64_t sot_ld;                      /* element stride between the clips' sot rows, >= Ts, or 0: one row for all */
+    void *ids;                           /* (A, width) out, contiguous */
+    int32_t *kv_start;                   /* (A) out */
+} MopkWindowPromptsArgs;
+int mopk_window_prompts_supported(const MopkWindowPromptsArgs *a);           /* 1 if the kernel takes this call (width, alignment) */
+int mopk_window_prompts(const MopkWindowPromptsArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
  * Whisper's log-mel spectrogram of a batch of waveforms (audio.py's log_mel_spectrogram; the stage in front of the encoder).
  * (Added under version 118: new exports only; callers detect it with mopk_log_mel_supported.)
  * Clip b holds len_b = min(lens[b], L) samples (L without lens) and T_b = len_b / hop frames; T = L / hop rows are written.

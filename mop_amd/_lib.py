@@ -264,6 +264,23 @@ class TimestampSegmentsArgs(C.Structure):
     ]
 
 
+class PromptHistoryArgs(C.Structure):
+    """MopkPromptHistoryArgs: the in-place update of the per-clip token history (WhisperMoP.transcribe's conditioning)."""
+    _fields_ = [
+        ("A", C.c_int32), ("B", C.c_int32), ("n", C.c_int32), ("T", C.c_int32), ("T0", C.c_int32), ("reserved", C.c_int32),
+        ("hist", _fp), ("hist_len", _fp), ("tokens", _fp), ("tokens_ld", C.c_int64), ("n_take", _fp), ("item", _fp), ("mode", _fp),
+    ]
+
+
+class WindowPromptsArgs(C.Structure):
+    """MopkWindowPromptsArgs: the left-padded prompt matrix of a set of windows, built from the token history."""
+    _fields_ = [
+        ("A", C.c_int32), ("B", C.c_int32), ("n", C.c_int32), ("width", C.c_int32), ("Ts", C.c_int32), ("prev", C.c_int32),
+        ("out_i64", C.c_int32), ("sot_i64", C.c_int32),
+        ("hist", _fp), ("hist_len", _fp), ("item", _fp), ("sot", _fp), ("sot_ld", C.c_int64), ("ids", _fp), ("kv_start", _fp),
+    ]
+
+
 class LogMelArgs(C.Structure):
     """MopkLogMelArgs: Whisper's log-mel spectrogram of a batch of waveforms (LogMelFrontend)."""
     _fields_ = [
@@ -379,6 +396,10 @@ SYMBOLS = {
     "mopk_dtw_align": (C.c_int, [C.POINTER(DtwArgs), C.c_void_p]),
     "mopk_timestamp_segments_supported": (C.c_int, [C.POINTER(TimestampSegmentsArgs)]),
     "mopk_timestamp_segments": (C.c_int, [C.POINTER(TimestampSegmentsArgs), C.c_void_p]),
+    "mopk_prompt_history_update_supported": (C.c_int, [C.POINTER(PromptHistoryArgs)]),
+    "mopk_prompt_history_update": (C.c_int, [C.POINTER(PromptHistoryArgs), C.c_void_p]),
+    "mopk_window_prompts_supported": (C.c_int, [C.POINTER(WindowPromptsArgs)]),
+    "mopk_window_prompts": (C.c_int, [C.POINTER(WindowPromptsArgs), C.c_void_p]),
     "mopk_log_mel_supported": (C.c_int, [C.POINTER(LogMelArgs)]),
     "mopk_log_mel_workspace_bytes": (C.c_size_t, [C.POINTER(LogMelArgs)]),
     "mopk_log_mel": (C.c_int, [C.POINTER(LogMelArgs), C.c_void_p]),

@@ -104,6 +104,26 @@ class _Fallback(NamedTuple):
     seed: int
 
 
+class _Conditioning(NamedTuple):
+    """transcribe's conditioning on the previous text, as checked by _condition_check"""
+    on: bool                             # condition_on_previous_text
+    n: int                               # the history cap
+    prev: int                            # sot_prev_token_id
+    seeds: Optional[List[torch.Tensor]]  # per clip: the initial prompt, or None
+    reset_temperature: float
+
+
+class _PreparedPrompts(NamedTuple):
+    """a ragged prompt batch that is already padded (transcribe builds it on the device with ops.window_prompts), for the decoders'
+    private entry points in place of the list form: ids (B, P) left-padded, kv_start int32 (B,) or None when every row fills P,
+    lens: the rows' lengths on the host, max(lens) == P; every row ends with the same sot_len tokens, inside which sot_index
+    counts.  The tokens come back as one (B, P + max_new_tokens) tensor, the padding included."""
+    ids: torch.Tensor
+    kv_start: Optional[torch.Tensor]
+    lens: List[int]
+    sot_len: int
+
+
 class _Batch(NamedTuple):
     """what the prompt checks need to know of the audio batch when the mel is a list: shape[0] and device"""
     shape: Tuple[int, ...]
@@ -553,6 +573,10 @@ class WhisperMoP(nn.Module):
         ValueError on a malformed list, before any device work."""
         if isinstance(prompt_ids, torch.Tensor):
             return None
+        if isinstance(prompt_ids, _PreparedPrompts):
+            if len(prompt_ids.lens) != mel.shape[0]:
+                raise ValueError(f"{what}: {len(prompt_ids.lens)} prompts for a batch of {mel.shape[0]} mel inputs")
+            return list(prompt_ids.lens)
         if not isinstance(prompt_ids, (list, tuple)) or len(prompt_ids) == 0:
             raise ValueError(f"{what}: prompt_ids must be a (B, T_p) tensor or a non-empty list of B 1-D token tensors")
         if len(prompt_ids) != mel.shape[0]:
@@ -572,6 +596,8 @@ class WhisperMoP(nn.Module):
         """-> (prompts (B, P), kv_start): a tensor passes through with kv_start None; a ragged list is left-padded with token 0 to
         P = max(lens), row b's prompt in columns [P - lens[b], P), with kv_start = P - lens as an int32 (B,) device tensor (None
         when every length is P: the uniform path)"""
+        if isinstance(prompt_ids, _PreparedPrompts):
+            return prompt_ids.ids, prompt_ids.kv_start
         if lens is None:
             return prompt_ids, None
         P = max(lens)
@@ -632,6 +658,15 @@ class WhisperMoP(nn.Module):
         if isinstance(sot_index, bool) or not isinstance(sot_index, int) or not 0 <= sot_index < shortest:
             raise ValueError(f"{what}: sot_index must be an int inside the shortest prompt, [0, {shortest}), got {sot_index!r}")
         return no_speech_token_id, sot_index
+
+    @staticmethod
+    def _prepared(prompt_ids, stats, lens, T_p: int):
+        """(stats, lens) as the decoders go on using them.  A _PreparedPrompts batch holds the sot sequence in the last sot_len
+        columns of every row: its no-speech column is T_p - sot_len + sot_index for all rows, and its tokens are not cut into a
+        list (lens None from here on)"""
+        if not isinstance(prompt_ids, _PreparedPrompts):
+            return stats, lens
+        return (None if stats is None else (stats[0], T_p - prompt_ids.sot_len + stats[1])), None
 
     @staticmethod
     def _no_speech_prob(prompt_logits: torch.Tensor, stats, lens: Optional[List[int]]) -> Optional[torch.Tensor]:
@@ -737,6 +772,7 @@ class WhisperMoP(nn.Module):
         mel_info, lens, B, T_p, _ = self._decode_check(mel, prompt_ids, max_new_tokens, "generate")
         self._rules_check(logit_rules, eos_token_id, "generate")
         stats = self._stats_check(return_stats, no_speech_token_id, sot_index, lens, T_p, "generate", eos_token_id)
+        stats, lens = self._prepared(prompt_ids, stats, lens, T_p)
         prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
         enc, _ = self.encode(mel)
         cache = self.init_decode_cache(enc, T_p + max_new_tokens)
@@ -856,6 +892,7 @@ class WhisperMoP(nn.Module):
         mel_info, lens, B, T_p, K = self._decode_check(mel, prompt_ids, max_new_tokens, "beam_search", ("num_beams", num_beams), 2)
         self._rules_check(logit_rules, eos_token_id, "beam_search")
         stats = self._stats_check(return_stats, no_speech_token_id, sot_index, lens, T_p, "beam_search", eos_token_id)
+        stats, lens = self._prepared(prompt_ids, stats, lens, T_p)
         cap = T_p + max_new_tokens
         prompt_ids, prompt_logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, K)
         no_speech = None if stats is None else self._no_speech_prob(prompt_logits, stats, lens)
@@ -915,6 +952,7 @@ class WhisperMoP(nn.Module):
         ops._sample_params(temperature, top_k, top_p, "sample")                 # argument errors before encoding
         self._rules_check(logit_rules, eos_token_id, "sample")
         stats = self._stats_check(return_stats, no_speech_token_id, sot_index, lens, T_p, "sample", eos_token_id)
+        stats, lens = self._prepared(prompt_ids, stats, lens, T_p)
         cap = T_p + max_new_tokens
         prompt_ids, prompt_logits, cache = self._replicated_cache(mel, mel_info, prompt_ids, lens, cap, n)
         no_speech = None if stats is None else self._no_speech_prob(prompt_logits, stats, lens)
@@ -1137,11 +1175,77 @@ class WhisperMoP(nn.Module):
         return _Fallback(tuple(float(t) for t in temperatures), logprob_threshold, no_speech_threshold, no_speech_token_id,
                          sot_index, compression_ratio_threshold, compression_ratio, num_samples, seed)
 
+    def _condition_check(self, B: int, T_p: int, max_new_tokens: int, condition_on_previous_text, initial_prompt, sot_prev_token_id,
+                         max_prompt_tokens, prompt_reset_temperature) -> Optional[_Conditioning]:
+        """the checks of transcribe's conditioning on the previous text -> None with every keyword at its default (the loop then
+        runs as it does without them), else the policy; ValueErrors before any device work"""
+        what = "transcribe"
+
+        def _int(x):
+            return not isinstance(x, bool) and isinstance(x, int)
+
+        if not isinstance(condition_on_previous_text, bool):
+            raise ValueError(f"{what}: condition_on_previous_text must be a bool, got {condition_on_previous_text!r}")
+        t = prompt_reset_temperature
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or t != t:
+            raise ValueError(f"{what}: prompt_reset_temperature must be a number, got {t!r}")
+        if sot_prev_token_id is not None and (not _int(sot_prev_token_id) or not 0 <= sot_prev_token_id < self.cfg.vocab_size):
+            raise ValueError(f"{what}: sot_prev_token_id must be an int in [0, vocab_size = {self.cfg.vocab_size}), got "
+                             f"{sot_prev_token_id!r}")
+        if max_prompt_tokens is not None and (not _int(max_prompt_tokens) or max_prompt_tokens < 1):
+            raise ValueError(f"{what}: max_prompt_tokens must be None or an int >= 1, got {max_prompt_tokens!r}")
+        seeds = None
+        if initial_prompt is not None:
+            seeds = [initial_prompt] * B if isinstance(initial_prompt, torch.Tensor) else initial_prompt
+            if not isinstance(seeds, (list, tuple)) or len(seeds) != B:
+                raise ValueError(f"{what}: initial_prompt must be a 1-D integer tensor or a list of {B} of them (one per clip), got "
+                                 f"{type(initial_prompt).__name__}"
+                                 + (f" of {len(seeds)}" if isinstance(seeds, (list, tuple)) else ""))
+            for b, p in enumerate(seeds):
+                if (not isinstance(p, torch.Tensor) or p.dim() != 1 or p.dtype.is_floating_point or p.dtype.is_complex
+                        or p.dtype == torch.bool):
+                    raise ValueError(f"{what}: initial_prompt {b} must be a 1-D integer tensor, got "
+                                     f"{(tuple(p.shape), p.dtype) if isinstance(p, torch.Tensor) else type(p).__name__}")
+            seeds = list(seeds)
+        if not condition_on_previous_text and seeds is None:
+            return None
+        if sot_prev_token_id is None:
+            raise ValueError(f"{what}: condition_on_previous_text and initial_prompt need sot_prev_token_id (the token in front of "
+                             f"the previous text)")
+        n = self.cfg.n_text_ctx // 2 - 1 if max_prompt_tokens is None else max_prompt_tokens
+        if n < 1:
+            raise ValueError(f"{what}: n_text_ctx = {self.cfg.n_text_ctx} leaves no room for previous text "
+                             f"(n_text_ctx // 2 - 1 = {n})")
+        if T_p + 1 + n + max_new_tokens > self.cfg.n_text_ctx:
+            raise ValueError(f"{what}: T_p + 1 + max_prompt_tokens + max_new_tokens = {T_p} + 1 + {n} + {max_new_tokens} = "
+                             f"{T_p + 1 + n + max_new_tokens} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        return _Conditioning(condition_on_previous_text, n, sot_prev_token_id, seeds, float(t))
+
+    @staticmethod
+    def _history_init(cond: _Conditioning, B: int, dev):
+        """the token history of B clips -> (hist (B, n) int32, hist_len (B,) int32 on the device, the host's mirror of
+        hist_len): empty, or seeded with the last n tokens of each clip's initial prompt"""
+        hist = torch.zeros(B, cond.n, dtype=torch.int32, device=dev)
+        len_b = [0] * B
+        if cond.seeds is None:
+            return hist, torch.zeros(B, dtype=torch.int32, device=dev), len_b
+        for b, p in enumerate(cond.seeds):
+            len_b[b] = min(cond.n, int(p.shape[0]))
+            if len_b[b]:
+                hist[b, :len_b[b]] = p[p.shape[0] - len_b[b]:].to(device=dev, dtype=torch.int32)
+        hist_len = torch.tensor(len_b, dtype=torch.int32)
+        if dev.type == "cuda":                                         # an asynchronous copy: the host does not wait for it
+            hist_len = hist_len.pin_memory().to(dev, non_blocking=True)
+        return hist, hist_len, len_b
+
     def _decode_with_fallback(self, dec, wins, prompts, max_new_tokens, eos, num_beams, length_penalty, graph, pol: _Fallback,
-                              calls: List[int]):
+                              calls: List[int], build=None):
         """one set of windows under transcribe's policy (Whisper's decode_with_fallback, then should_skip) -> (rows (A, cap) on
         the device, and per window, as host lists: the temperature kept, avg_logprob, no_speech_prob, compression ratio, skipped).
-        calls: a one-element list, the number of sample calls this transcribe has made so far (call k uses seed + k)."""
+        calls: a one-element list, the number of sample calls this transcribe has made so far (call k uses seed + k).
+        build: with conditioning on the previous text, build(window indices) makes the _PreparedPrompts of exactly the rows of
+        an attempt; its rows come back at the attempt's own width and are cut to the sot sequence and the generated tokens, so
+        the rows of every attempt are (T_p + max_new_tokens) wide, T_p the sot sequence's length."""
         A, T_p = len(wins), prompts.shape[1]
         dev, nan = prompts.device, float("nan")
         kw = dict(return_stats=True, no_speech_token_id=pol.no_speech_token_id, sot_index=pol.sot_index)
@@ -1150,7 +1254,10 @@ class WhisperMoP(nn.Module):
         pending = list(range(A))
         for ti, t in enumerate(pol.temperatures):
             sub_w = [wins[i] for i in pending]
-            sub_p = prompts if len(pending) == A else torch.stack([prompts[i] for i in pending])
+            if build is not None:
+                sub_p = build(pending)
+            else:
+                sub_p = prompts if len(pending) == A else torch.stack([prompts[i] for i in pending])
             if t == 0 and num_beams > 1:
                 rows, _, st = dec.beam_search(sub_w, sub_p, max_new_tokens, num_beams, eos, length_penalty, graph, **kw)
                 a = st.sum_logprobs / st.n_tokens
@@ -1165,6 +1272,8 @@ class WhisperMoP(nn.Module):
                 best = every.argmax(1, keepdim=True)
                 a = every.gather(1, best).squeeze(1)
                 rows = toks.gather(1, best.unsqueeze(2).expand(-1, 1, toks.shape[2])).squeeze(1)
+            if build is not None:
+                rows = rows[:, sub_p.ids.shape[1] - T_p:]
             ns = st.no_speech_prob if st.no_speech_prob is not None else torch.full_like(a, nan)
             host = torch.empty(len(pending), 2, dtype=torch.float32)
             if dev.type == "cuda":
@@ -1209,7 +1318,9 @@ class WhisperMoP(nn.Module):
                     graph: bool = False, temperatures=(0.0,), logprob_threshold: Optional[float] = None,
                     no_speech_threshold: Optional[float] = None, no_speech_token_id: Optional[int] = None, sot_index: int = 0,
                     compression_ratio_threshold: Optional[float] = None, compression_ratio=None, num_samples: int = 1,
-                    seed: int = 0, return_log: bool = False):
+                    seed: int = 0, return_log: bool = False, condition_on_previous_text: bool = False, initial_prompt=None,
+                    sot_prev_token_id: Optional[int] = None, max_prompt_tokens: Optional[int] = None,
+                    prompt_reset_temperature: float = 0.5):
         """long-form transcription, Whisper's transcribe loop over windows for a batch of clips -> a list of B Transcript(starts,
         ends, tokens, offsets), all on the device.
 
@@ -1253,16 +1364,58 @@ class WhisperMoP(nn.Module):
         ValueError before any device work: temperatures empty, not increasing, negative or NaN; no_speech_threshold without
         no_speech_token_id; compression_ratio_threshold without compression_ratio; num_samples outside [1, 8], or above 1 with no
         temperature above 0; sot_index outside the prompt; no_speech_token_id outside the vocabulary.
-        Out of scope: conditioning a window on the previous window's text, word grouping, top-k / top-p inside transcribe, handing
-        the encoded audio over to a fallback attempt, and a device-side compression ratio."""
+
+        Conditioning on the previous text (Whisper's condition_on_previous_text and initial_prompt).  With the five keywords
+        below at their defaults every window is decoded from prompt_ids alone, by the loop above: no history is allocated and
+        no launch is added.  With condition_on_previous_text=True or an initial_prompt, clip b keeps a token history on the
+        device, hist (B, n) int32 and hist_len (B,), n = max_prompt_tokens, or n_text_ctx // 2 - 1 when that is None (Whisper's
+        n_ctx // 2 - 1), and a window of clip b with a history of len_b > 0 tokens is decoded from [sot_prev_token_id, the
+        history, prompt_ids].  sot_prev_token_id (Whisper's <|startofprev|>) is required then.  initial_prompt: a 1-D integer
+        tensor for all clips, or a list of B 1-D tensors (an empty one: none for that clip); its last n tokens seed the history,
+        and it never appears in the Transcript.
+        Before EVERY decoder call, a fallback attempt on some of the rows included, ops.window_prompts builds the prompt matrix
+        of exactly that call's rows in one launch, at width = T_p + the largest 1 + len_b among its rows with history (T_p when
+        none has any: the host keeps len_b as a mirror of hist_len, updated from the token count the (A, 3) copy brings), and
+        the decoders take it as a ragged batch, left-padded with a per-row start, or as a uniform one when every row fills the
+        width: exactly what their public list form does with the same prompts, so the result equals a host loop over the public
+        decoders bit for bit.  prompt_ids sits in the last T_p columns of every row, so no_speech_prob is read at the one column
+        width - T_p + sot_index.  After each set of windows ONE ops.prompt_history_update launch gives every row one of:
+        - a skipped window (no speech) leaves its clip's history as it is (Whisper continues before its reset check);
+        - with condition_on_previous_text False, or a kept temperature above prompt_reset_temperature, the history is cleared
+          (Whisper's prompt_reset_since; so without condition_on_previous_text an initial_prompt conditions each clip's first
+          window only);
+        - else the tokens that join the transcript, timestamp tokens included, are appended and the newest n kept.
+        No host synchronisation is added: the rows' clips and modes ride in the pinned upload that carries the windows'
+        lengths, the clips of a decoder call in one of their own, and the (A, 3) download is unchanged.  With graph=True each
+        decoder call captures anew at its own width.
+        ValueError before any device work: sot_prev_token_id missing or outside the vocabulary; n < 1; T_p + 1 + n +
+        max_new_tokens > n_text_ctx; an initial_prompt that is neither form; a prompt_reset_temperature that is not a number.
+        Out of scope: word grouping, top-k / top-p inside transcribe, handing the encoded audio over to a fallback attempt, a
+        device-side compression ratio, and a vocabulary projection of the prompt pass restricted to the columns that are read."""
         clips, W = self._transcribe_check(mel, prompt_ids, logit_rules, max_new_tokens, window, frames_per_timestamp, num_beams,
                                            length_penalty)
         pol = self._fallback_check(prompt_ids.shape[-1], temperatures, logprob_threshold, no_speech_threshold, no_speech_token_id,
                                    sot_index, compression_ratio_threshold, compression_ratio, num_samples, seed)
+        cond = self._condition_check(len(clips), prompt_ids.shape[-1], max_new_tokens, condition_on_previous_text, initial_prompt,
+                                     sot_prev_token_id, max_prompt_tokens, prompt_reset_temperature)
         plain = (pol.temperatures == (0.0,) and logprob_threshold is None and no_speech_threshold is None
                  and no_speech_token_id is None and compression_ratio is None and not return_log)
         calls = [0]
         dev, B, dec = clips[0].device, len(clips), self.with_logit_rules(logit_rules)
+        build = None
+        if cond is not None:
+            hist, hist_len, len_b = self._history_init(cond, B, dev)
+
+            def build(idx):                                            # the prompts of one decoder call: its rows' clips idx
+                have = [len_b[b] for b in idx]
+                width = T_p + max((1 + n for n in have if n > 0), default=0)
+                item = torch.tensor(idx, dtype=torch.int32)
+                if dev.type == "cuda":                                 # an asynchronous copy: the host does not wait for it
+                    item = item.pin_memory().to(dev, non_blocking=True)
+                dt = prompt_ids.dtype if prompt_ids.dtype in (torch.int32, torch.int64) else torch.int64
+                ids, kv_start = ops.window_prompts(hist, hist_len, item, prompt_ids, cond.prev, width, dt)
+                lens_p = [T_p + (1 + n if n > 0 else 0) for n in have]
+                return _PreparedPrompts(ids.to(prompt_ids.dtype), None if min(lens_p) == width else kv_start, lens_p, T_p)
         logs = [TranscribeLog([], [], [], [], [], []) for _ in range(B)]
         tb, eos = logit_rules.timestamp_begin, logit_rules.eos_token_id
         T_p = prompt_ids.shape[-1]
@@ -1281,26 +1434,44 @@ class WhisperMoP(nn.Module):
             skipped = None
             if not plain:
                 rows, temp, avg, nsp, ratio, skipped = self._decode_with_fallback(
-                    dec, wins, prompts, max_new_tokens, eos, num_beams, length_penalty, graph, pol, calls)
+                    dec, wins, prompts, max_new_tokens, eos, num_beams, length_penalty, graph, pol, calls,
+                    None if build is None else lambda pending: build([act[i] for i in pending]))
                 for a, b in enumerate(act):
                     for field, v in zip(logs[b], (seek[b], temp[a], avg[a], nsp[a], ratio[a], skipped[a])):
                         field.append(v)
-            elif num_beams > 1:
-                rows, _ = dec.beam_search(wins, prompts, max_new_tokens, num_beams, eos, length_penalty, graph)
             else:
-                rows = dec.generate(wins, prompts, max_new_tokens, eos, graph)
+                if build is not None:
+                    prompts = build(act)
+                if num_beams > 1:
+                    rows, _ = dec.beam_search(wins, prompts, max_new_tokens, num_beams, eos, length_penalty, graph)
+                else:
+                    rows = dec.generate(wins, prompts, max_new_tokens, eos, graph)
+                if build is not None:                                  # the sot sequence and the generated tokens
+                    rows = rows[:, prompts.ids.shape[1] - T_p:]
             lens = torch.tensor([int(w.shape[0]) for w in wins], dtype=torch.int32)
+            if build is not None:                                      # per row: 2 leave the history, 1 clear it, 0 append
+                kept_t = temp if skipped is not None else [0.0] * len(act)
+                modes = [2 if skipped is not None and skipped[a] else int(not cond.on or kept_t[a] > cond.reset_temperature)
+                         for a in range(len(act))]
+                lens = torch.stack((lens, torch.tensor(act, dtype=torch.int32), torch.tensor(modes, dtype=torch.int32)))
             meta = torch.empty(len(act), 3, dtype=torch.int32)
             if dev.type == "cuda":                                     # an asynchronous copy: the host does not wait for it
                 lens, meta = lens.pin_memory().to(dev, non_blocking=True), meta.pin_memory()
-            seg = ops.timestamp_segments(rows.to(torch.int32), T_p, lens, tb, eos, frames_per_timestamp)
+            if build is not None:
+                lens, item, mode = lens[0], lens[1], lens[2]
+            rows32 = rows.to(torch.int32)
+            seg = ops.timestamp_segments(rows32, T_p, lens, tb, eos, frames_per_timestamp)
             last = seg.tok_end.gather(1, (seg.n_segments - 1).clamp_min(0).long().unsqueeze(1)).squeeze(1)
             spanned = torch.where(seg.n_segments > 0, last - T_p, 0)   # a window's segments are contiguous from column T_p on
             meta.copy_(torch.stack((seg.advance, seg.n_segments, spanned.to(torch.int32)), dim=1))      # the one synchronisation
+            if build is not None:
+                ops.prompt_history_update(hist, hist_len, rows32, T_p, spanned.to(torch.int32), item, mode)
             for a, (adv, n, m) in enumerate(meta.tolist()):
                 b = act[a]
                 if skipped is not None and skipped[a]:                 # no speech: nothing joins the transcript, seek moves on
                     adv, n, m = int(wins[a].shape[0]), 0, 0
+                if build is not None and modes[a] != 2:                # the host's mirror of hist_len
+                    len_b[b] = min(cond.n, len_b[b] + m) if modes[a] == 0 else 0
                 st, en, tk, off = parts[b]
                 st.append(seg.starts[a, :n] + seek[b])
                 en.append(seg.ends[a, :n] + seek[b])
@@ -1403,7 +1574,8 @@ class RuledDecoding:
     list, blank suppression at the first generated position, the timestamp grammar) applied to every step's last-position logits
     by ops.logit_rules, one HIP launch inside the step.  The decoders' own signatures do not change (their tests pin them); each
     method here takes the arguments of the method it names, and what came later as keywords of its own: the decoding statistics
-    (return_stats, no_speech_token_id, sot_index) and, on transcribe, the temperature fallback and the no-speech skip.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
+    (return_stats, no_speech_token_id, sot_index) and, on transcribe, the temperature fallback, the no-speech skip and the
+    conditioning on the previous text.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
     (ValueError).  logit_rules None runs the plain decoder: no extra launch, no extra buffer."""
 
     def __init__(self, model: WhisperMoP, logit_rules: Optional["ops.LogitRules"]):
@@ -1443,13 +1615,17 @@ class RuledDecoding:
                    frames_per_timestamp: int = 1, num_beams: int = 1, length_penalty: float = 1.0, graph: bool = False,
                    temperatures=(0.0,), logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None,
                    no_speech_token_id: Optional[int] = None, sot_index: int = 0, compression_ratio_threshold: Optional[float] = None,
-                   compression_ratio=None, num_samples: int = 1, seed: int = 0, return_log: bool = False):
+                   compression_ratio=None, num_samples: int = 1, seed: int = 0, return_log: bool = False,
+                   condition_on_previous_text: bool = False, initial_prompt=None, sot_prev_token_id: Optional[int] = None,
+                   max_prompt_tokens: Optional[int] = None, prompt_reset_temperature: float = 0.5):
         return self.model._transcribe(
             mel, prompt_ids, self.logit_rules, max_new_tokens, window=window, frames_per_timestamp=frames_per_timestamp,
             num_beams=num_beams, length_penalty=length_penalty, graph=graph, temperatures=temperatures,
             logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold, no_speech_token_id=no_speech_token_id,
             sot_index=sot_index, compression_ratio_threshold=compression_ratio_threshold, compression_ratio=compression_ratio,
-            num_samples=num_samples, seed=seed, return_log=return_log)
+            num_samples=num_samples, seed=seed, return_log=return_log, condition_on_previous_text=condition_on_previous_text,
+            initial_prompt=initial_prompt, sot_prev_token_id=sot_prev_token_id, max_prompt_tokens=max_prompt_tokens,
+            prompt_reset_temperature=prompt_reset_temperature)
 
 
 RuledDecoding.transcribe.__doc__ = WhisperMoP._transcribe.__doc__

@@ -1962,7 +1962,7 @@ def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
 
 
 # ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, token_logprob, greedy_pick,
-# alignment_cost, dtw_align, timestamp_segments ----
+# alignment_cost, dtw_align, timestamp_segments, prompt_history_update, window_prompts ----
 # Each is its _*_check (every ValueError, once per call), its _*_accept (the tensor-side tests, then the args struct, built once,
 # if the library's _supported query takes it, else None), then the torch restatement, or the outputs into that struct and _row_launch.
 def _row_launch(a, sym: str, key: str, dev=None, ws_sym: Optional[str] = None) -> None:
@@ -3222,6 +3222,233 @@ def timestamp_segments(tokens: torch.Tensor, t0: int, window: torch.Tensor, time
         a.n_segments, a.advance = row[0].data_ptr(), row[1].data_ptr()
         _row_launch(a, "mopk_timestamp_segments", "timestamp_segments")
         return TimestampSegments(seg[0], seg[1], seg[2], seg[3], row[0], row[1])
+
+
+# --------------------------------------------------------------------------------------
+# Conditioning on the previous text (WhisperMoP.transcribe): the per-clip token history on the device, and the prompts built from it
+PROMPT_HISTORY_MAX = 1024      # history entries of a clip (one thread each), and generated columns of a row
+WINDOW_PROMPTS_MAX_WIDTH = 2048
+
+
+class WindowPrompts(NamedTuple):
+    """the prompts of a set of windows (`window_prompts`): ids (A, width), left-padded with zeros, and kv_start (A,) int32, the
+    first column of each row's own prompt (what WhisperDecodeCache.kv_start takes)"""
+    ids: torch.Tensor
+    kv_start: torch.Tensor
+
+
+def _is_int(x) -> bool:
+    return not isinstance(x, bool) and isinstance(x, int)
+
+
+def _hist_state_check(hist, hist_len, what: str) -> None:
+    if not isinstance(hist, torch.Tensor) or hist.dim() != 2 or 0 in hist.shape or hist.dtype != torch.int32 or not hist.is_contiguous():
+        raise ValueError(f"{what}: hist must be a non-empty contiguous int32 (B, n) tensor, got "
+                         f"{(tuple(hist.shape), hist.dtype, hist.stride()) if isinstance(hist, torch.Tensor) else type(hist).__name__}")
+    B = hist.shape[0]
+    if (not isinstance(hist_len, torch.Tensor) or hist_len.shape != (B,) or hist_len.dtype != torch.int32
+            or not hist_len.is_contiguous()):
+        raise ValueError(f"{what}: hist_len must be a contiguous int32 ({B},) tensor, got "
+                         f"{(tuple(hist_len.shape), hist_len.dtype) if isinstance(hist_len, torch.Tensor) else type(hist_len).__name__}")
+    if hist_len.device != hist.device:
+        raise ValueError(f"{what}: hist_len is on {hist_len.device}, hist on {hist.device}")
+
+
+def _ph_check(hist, hist_len, tokens, t0, n_take, item, mode, what: str) -> None:
+    """validate a prompt_history_update call before any device work"""
+    _hist_state_check(hist, hist_len, what)
+    if (not isinstance(tokens, torch.Tensor) or tokens.dim() != 2 or 0 in tokens.shape or tokens.dtype.is_floating_point
+            or tokens.dtype.is_complex or tokens.dtype == torch.bool):
+        raise ValueError(f"{what}: tokens must be a non-empty integer (A, T) tensor, got "
+                         f"{(tuple(tokens.shape), tokens.dtype) if isinstance(tokens, torch.Tensor) else type(tokens).__name__}")
+    if tokens.device != hist.device:
+        raise ValueError(f"{what}: tokens are on {tokens.device}, hist on {hist.device}")
+    if not _is_int(t0) or not 0 <= t0 < tokens.shape[1]:
+        raise ValueError(f"{what}: t0 must be an int in [0, T = {tokens.shape[1]}), got {t0!r}")
+    for name, t in (("n_take", n_take), ("item", item), ("mode", mode)):
+        _lens_i32_check(t, tokens.shape[0], hist.device, name, what, "hist")
+
+
+def _item_lookup(item: torch.Tensor, B: int):
+    """per clip b: whether a row a has item[a] == b, and the first such row"""
+    match = item.to(torch.long).unsqueeze(0) == torch.arange(B, device=item.device).unsqueeze(1)         # (B, A)
+    return match.any(1), match.to(torch.int32).argmax(1)
+
+
+def prompt_history_update_torch(hist: torch.Tensor, hist_len: torch.Tensor, tokens: torch.Tensor, t0: int, n_take: torch.Tensor,
+                                item: torch.Tensor, mode: torch.Tensor) -> None:
+    """the restatement of `prompt_history_update` in torch ops (CPU or GPU, no host sync): every clip looks up the row that names
+    it, gathers its new history from (hist, tokens) and keeps its old one where no row, or a row of another mode, does"""
+    _ph_check(hist, hist_len, tokens, t0, n_take, item, mode, "prompt_history_update_torch")
+    (B, n), S = hist.shape, tokens.shape[1] - t0
+    has, a = _item_lookup(item, B)
+    md = torch.where(has, mode.to(torch.long)[a], 2)
+    L = hist_len.to(torch.long).clamp(0, n)
+    m = n_take.to(torch.long)[a].clamp(0, S)
+    keep = (L + m).clamp_max(n)
+    j = torch.arange(n, device=hist.device).unsqueeze(0)
+    src = (L + m - keep).unsqueeze(1) + j                                          # entry j of the last keep of (hist, tokens)
+    old = hist.gather(1, src.clamp(0, n - 1))
+    new = tokens[:, t0:].to(torch.int32)[a].gather(1, (src - L.unsqueeze(1)).clamp(0, S - 1))
+    write = (j < keep.unsqueeze(1)) & (md == 0).unsqueeze(1)
+    hist.copy_(torch.where(write, torch.where(src < L.unsqueeze(1), old, new), hist))
+    hist_len.copy_(torch.where(md == 0, keep, torch.where(md == 1, 0, hist_len.to(torch.long))).to(torch.int32))
+
+
+def _ph_accept(hist, hist_len, tokens, t0, n_take, item, mode):
+    """the args struct of a call that mopk_prompt_history_update takes, None of one it refuses"""
+    A, T = tokens.shape
+    if not hist.is_cuda or tokens.dtype != torch.int32 or (T > 1 and tokens.stride(1) != 1) or (A > 1 and tokens.stride(0) < T):
+        return None
+    if any(t.dtype != torch.int32 or (A > 1 and t.stride(0) != 1) for t in (n_take, item, mode)):
+        return None
+    if hist.shape[1] > PROMPT_HISTORY_MAX or T - t0 > PROMPT_HISTORY_MAX:
+        return None
+    a = L.PromptHistoryArgs()
+    a.A, a.T, a.T0 = A, T, t0
+    a.B, a.n = hist.shape
+    a.hist, a.hist_len, a.tokens, a.tokens_ld = hist.data_ptr(), hist_len.data_ptr(), tokens.data_ptr(), tokens.stride(0)
+    if A == 1:                                                                     # a single row: its stride is never used
+        a.tokens_ld = T
+    a.n_take, a.item, a.mode = n_take.data_ptr(), item.data_ptr(), mode.data_ptr()
+    return a if L.lib().mopk_prompt_history_update_supported(C.byref(a)) else None
+
+
+def prompt_history_update_supported(hist: torch.Tensor, hist_len: torch.Tensor, tokens: torch.Tensor, t0: int,
+                                    n_take: torch.Tensor, item: torch.Tensor, mode: torch.Tensor) -> bool:
+    """True if mopk_prompt_history_update takes this call: CUDA tensors, int32 tokens with unit inner stride and a row stride >= T
+    (one row: any), contiguous int32 n_take / item / mode, n <= 1024 and T - t0 <= 1024 (the library's own query decides the
+    rest).  Raises ValueError on bad arguments."""
+    _ph_check(hist, hist_len, tokens, t0, n_take, item, mode, "prompt_history_update_supported")
+    return _ph_accept(hist, hist_len, tokens, t0, n_take, item, mode) is not None
+
+
+def prompt_history_update(hist: torch.Tensor, hist_len: torch.Tensor, tokens: torch.Tensor, t0: int, n_take: torch.Tensor,
+                          item: torch.Tensor, mode: torch.Tensor) -> None:
+    """add the tokens a set of decoded windows contributes to their clips' token histories, or clear them, IN PLACE (Whisper's
+    all_tokens[prompt_reset_since:], capped: what conditions the next window).  Inference only.
+
+    hist (B, n) int32 contiguous and hist_len (B,) int32: hist[b, :hist_len[b]] holds the last tokens of clip b's transcript since
+    its last reset; n is the cap.  tokens: (A, T) int32 decoded rows, unit inner stride, any row stride >= T; t0: the first
+    generated column.  n_take, item, mode: (A,) int32 device tensors.  Per row a, with b = item[a], L = hist_len[b] clamped into
+    [0, n] and m = n_take[a] clamped into [0, T - t0]:
+    mode[a] == 0: c = hist[b, :L] followed by tokens[a, t0:t0+m]; keep = min(n, L + m); hist[b, :keep] = the last keep entries of
+                  c; hist_len[b] = keep (hist[b, keep:] keeps its old words);
+    mode[a] == 1: hist_len[b] = 0;
+    any other value: clip b is left untouched.
+    A row whose item lies outside [0, B) is skipped.  The item values of a call must be distinct: two rows of one clip race in the
+    kernel (inside the buffers), and the torch path lets the first one win.
+    Runs the HIP kernel (mopk_prompt_history_update: one launch, one workgroup per row, the entries held in registers across a
+    barrier) when prompt_history_update_supported() accepts the call, else prompt_history_update_torch();
+    LAST_PATH["prompt_history_update"] records which.  No host sync, no workspace; bitwise reproducible."""
+    _ph_check(hist, hist_len, tokens, t0, n_take, item, mode, "prompt_history_update")
+    with torch.no_grad():
+        a = _ph_accept(hist, hist_len, tokens, t0, n_take, item, mode)
+        if a is None:
+            LAST_PATH["prompt_history_update"] = L.PATH_GENERIC
+            return prompt_history_update_torch(hist, hist_len, tokens, t0, n_take, item, mode)
+        _row_launch(a, "mopk_prompt_history_update", "prompt_history_update")
+
+
+def _wp_check(hist, hist_len, item, sot, sot_prev_token_id, width, out_dtype, what: str) -> None:
+    """validate a window_prompts call before any device work"""
+    _hist_state_check(hist, hist_len, what)
+    B = hist.shape[0]
+    if (not isinstance(item, torch.Tensor) or item.dim() != 1 or item.numel() == 0 or item.dtype.is_floating_point
+            or item.dtype.is_complex or item.dtype == torch.bool):
+        raise ValueError(f"{what}: item must be a non-empty integer (A,) tensor, got "
+                         f"{(tuple(item.shape), item.dtype) if isinstance(item, torch.Tensor) else type(item).__name__}")
+    if (not isinstance(sot, torch.Tensor) or sot.dim() not in (1, 2) or 0 in sot.shape or sot.dtype.is_floating_point
+            or sot.dtype.is_complex or sot.dtype == torch.bool or (sot.dim() == 2 and sot.shape[0] != B)):
+        raise ValueError(f"{what}: sot must be an integer (T_s,) or ({B}, T_s) tensor, got "
+                         f"{(tuple(sot.shape), sot.dtype) if isinstance(sot, torch.Tensor) else type(sot).__name__}")
+    for name, t in (("item", item), ("sot", sot)):
+        if t.device != hist.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, hist on {hist.device}")
+    if not _is_int(sot_prev_token_id) or not 0 <= sot_prev_token_id < 2 ** 31:
+        raise ValueError(f"{what}: sot_prev_token_id must be an int in [0, 2^31), got {sot_prev_token_id!r}")
+    if not _is_int(width) or width < sot.shape[-1]:
+        raise ValueError(f"{what}: width must be an int >= T_s = {sot.shape[-1]}, got {width!r}")
+    if out_dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: out_dtype must be torch.int32 or torch.int64, got {out_dtype!r}")
+
+
+def window_prompts_torch(hist: torch.Tensor, hist_len: torch.Tensor, item: torch.Tensor, sot: torch.Tensor,
+                         sot_prev_token_id: int, width: int, out_dtype: torch.dtype = torch.int64) -> WindowPrompts:
+    """the restatement of `window_prompts` in torch ops (CPU or GPU, vectorised over rows, no host sync): every column finds its
+    place relative to the row's first own column and gathers from the history or the sot sequence"""
+    _wp_check(hist, hist_len, item, sot, sot_prev_token_id, width, out_dtype, "window_prompts_torch")
+    (B, n), T_s = hist.shape, sot.shape[-1]
+    it = item.to(torch.long)
+    b = it.clamp(0, B - 1)
+    Ln = torch.where((it >= 0) & (it < B), hist_len.to(torch.long)[b].clamp(0, n), 0)
+    room = width - T_s
+    h = Ln.clamp_max(room - 1) if room >= 2 else torch.zeros_like(Ln)
+    pre = torch.where(h > 0, 1 + h, 0).unsqueeze(1)
+    ks = width - T_s - pre
+    rel = torch.arange(width, device=hist.device).unsqueeze(0) - ks
+    rows = sot.to(torch.long)
+    rows = rows[b] if sot.dim() == 2 else rows.unsqueeze(0).expand(b.shape[0], -1)
+    from_sot = rows.gather(1, (rel - pre).clamp(0, T_s - 1))
+    from_hist = hist.to(torch.long)[b].gather(1, ((Ln - h).unsqueeze(1) + rel - 1).clamp(0, n - 1))
+    ids = torch.where(rel >= pre, from_sot, torch.where(rel >= 1, from_hist, torch.where(rel == 0, sot_prev_token_id, 0)))
+    return WindowPrompts(ids.to(out_dtype), ks.squeeze(1).to(torch.int32))
+
+
+def _wp_accept(hist, hist_len, item, sot, sot_prev_token_id, width, out_dtype):
+    """the args struct of a call that mopk_window_prompts takes, None of one it refuses; the outputs hold stand-ins"""
+    A, T_s = item.shape[0], sot.shape[-1]
+    if not hist.is_cuda or item.dtype != torch.int32 or (A > 1 and item.stride(0) != 1) or sot.dtype not in (torch.int32, torch.int64):
+        return None
+    if (T_s > 1 and sot.stride(-1) != 1) or (sot.dim() == 2 and sot.shape[0] > 1 and sot.stride(0) < T_s) or width > WINDOW_PROMPTS_MAX_WIDTH:
+        return None
+    a = L.WindowPromptsArgs()
+    a.A, a.width, a.Ts, a.prev = A, width, T_s, sot_prev_token_id
+    a.B, a.n = hist.shape
+    a.out_i64, a.sot_i64 = int(out_dtype == torch.int64), int(sot.dtype == torch.int64)
+    a.hist, a.hist_len, a.item, a.sot = hist.data_ptr(), hist_len.data_ptr(), item.data_ptr(), sot.data_ptr()
+    a.sot_ld = 0 if sot.dim() == 1 else (T_s if sot.shape[0] == 1 else sot.stride(0))
+    a.ids = a.kv_start = 8                                                         # stand-ins: only their alignment is looked at
+    return a if L.lib().mopk_window_prompts_supported(C.byref(a)) else None
+
+
+def window_prompts_supported(hist: torch.Tensor, hist_len: torch.Tensor, item: torch.Tensor, sot: torch.Tensor,
+                             sot_prev_token_id: int, width: int, out_dtype: torch.dtype = torch.int64) -> bool:
+    """True if mopk_window_prompts takes this call: CUDA tensors, a contiguous int32 item, an int32 or int64 sot with unit inner
+    stride, width <= 2048 (the library's own query decides the rest).  Raises ValueError on bad arguments."""
+    _wp_check(hist, hist_len, item, sot, sot_prev_token_id, width, out_dtype, "window_prompts_supported")
+    return _wp_accept(hist, hist_len, item, sot, sot_prev_token_id, width, out_dtype) is not None
+
+
+def window_prompts(hist: torch.Tensor, hist_len: torch.Tensor, item: torch.Tensor, sot: torch.Tensor, sot_prev_token_id: int,
+                   width: int, out_dtype: torch.dtype = torch.int64) -> WindowPrompts:
+    """the prompt matrix of a set of windows, each conditioned on its clip's token history (Whisper's
+    [sot_prev] + prompt_tokens[-(n_ctx // 2 - 1):] + sot_sequence) -> WindowPrompts(ids (A, width) of out_dtype, kv_start (A,)
+    int32), left-padded as the decoders take a ragged batch.  Inference only.
+
+    hist, hist_len: the state `prompt_history_update` keeps.  item: (A,) int32 device tensor, the clip of row a.  sot: the
+    start-of-transcript sequence, an integer (T_s,) tensor, or (B, T_s) indexed by item[a].  width >= T_s is the host's choice
+    (the output's shape cannot depend on device values): T_s + 1 + the longest history among the rows holds every row in full.
+    Per row a, with b = item[a], L = hist_len[b] clamped into [0, n] and room = width - T_s:
+    h = min(L, room - 1) if L > 0 and room >= 2, else 0 (a narrower width keeps the NEWEST h tokens; one too narrow for
+    sot_prev_token_id and one token drops the history);  length = T_s + (1 + h if h > 0 else 0);
+    ids[a] = width - length zeros, then [sot_prev_token_id, hist[b, L-h:L]] when h > 0, then the sot sequence;
+    kv_start[a] = width - length.
+    An item outside [0, B) makes a row without history (with a (B, T_s) sot: under the nearest clip's sequence).
+    Runs the HIP kernel (mopk_window_prompts: one launch writes both outputs, every word once) when window_prompts_supported()
+    accepts the call, else window_prompts_torch(); LAST_PATH["window_prompts"] records which.  No host sync, no workspace;
+    bitwise reproducible."""
+    _wp_check(hist, hist_len, item, sot, sot_prev_token_id, width, out_dtype, "window_prompts")
+    with torch.no_grad():
+        a = _wp_accept(hist, hist_len, item, sot, sot_prev_token_id, width, out_dtype)
+        if a is None:
+            LAST_PATH["window_prompts"] = L.PATH_GENERIC
+            return window_prompts_torch(hist, hist_len, item, sot, sot_prev_token_id, width, out_dtype)
+        ids = torch.empty(a.A, width, dtype=out_dtype, device=hist.device)
+        ks = torch.empty(a.A, dtype=torch.int32, device=hist.device)
+        a.ids, a.kv_start = ids.data_ptr(), ks.data_ptr()                          # in place of the stand-ins
+        _row_launch(a, "mopk_window_prompts", "window_prompts")
+        return WindowPrompts(ids, ks)
 
 
 # --------------------------------------------------------------------------------------
