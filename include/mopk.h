@@ -867,6 +867,82 @@ int mopk_window_prompts_supported(const MopkWindowPromptsArgs *a);           /* 
 int mopk_window_prompts(const MopkWindowPromptsArgs *a, void *stream);
 
 /* --------------------------------------------------------------------------
+ * Word timestamps (WhisperMoP.align_words and transcribe(word_timestamps=True); Whisper's find_alignment and add_word_timestamps
+ * with the tokenizer's part as a table over the vocabulary).  (Added under version 118: new exports only; callers detect them with
+ * the _supported queries.)
+ *
+ * mopk_alignment_rows turns decoded window rows into the inputs of the alignment pass.  Row r reads g[j] = tokens[r, T0 + j],
+ * S = T - T0 generated columns, m = n_take[r] clamped into [0, S]; the text tokens are the g[j] < eos with j < m, in order, n_text
+ * of them.  W = Tp + 2 + S.
+ *   ids[r]      = the Tp tokens sot + r * sot_ld ... (sot_ld == 0: one sequence for every row), nots, the text tokens, then eos to
+ *                 the end of the row (at least once);
+ *   n_tokens[r] = Tp + 2 + n_text;
+ *   col[r, i]   = T0 + j of text token i for i < n_text, else -1 (W columns).
+ * One workgroup per row, one thread per generated column: a stable compaction by wave ballots and one LDS exchange of the waves'
+ * counts; the block then strides over what the compaction did not write.  Takes S <= 1024.
+ *
+ * mopk_word_spans groups a row of text tokens into words and times them.  Row r: n = n_text[r] clamped into [0, N]; c_i =
+ * table[tokens[r, i] clamped into [0, V)] (bit 0 begins a word, bit 1 prepend punctuation, bit 2 append punctuation, bit 3 sentence
+ * end); times[r, i] is the frame at which token i begins and times[r, n] the closing frame.
+ *   1. token i begins a word when i == 0 or c_i & 1; word k covers [o_k, o_{k+1}), o_K = n; s_k = times[o_k], e_k = times[o_{k+1}],
+ *      p_k = the fp32 mean of its tokens' probabilities (summed in token order); P_k / A_k / E_k: the word has exactly one token and
+ *      that token has bit 1 / 2 / 3.
+ *   2. d_k = e_k - s_k; m2 = twice the median of the d_k != 0 (odd count: twice the middle value; even: the sum of the two middle
+ *      values; none: 0); max_dur = m2, or min(m2, 2 * median_cap) with median_cap >= 0.
+ *   3. k >= 1 with d_k > max_dur: E_k: e_k = s_k + max_dur; else E_{k-1}: s_k = e_k - max_dur (original values on the right).
+ *   4. pass 1: a word with P_k and k < K - 1 dies; its tokens go in front of the nearest later word that does not die here.
+ *   5. pass 2: a word k >= 1 that survived pass 1, has A_k and received nothing in pass 1 dies when word k - 1 survived pass 1; its
+ *      tokens go to the back of the nearest earlier word that survives both passes (one exists then).
+ *   6. the survivors, in order, keep their own s, e, p; their token ranges [tok_begin, tok_end) are the unions with what they
+ *      absorbed, contiguous, a partition of [0, n).  starts / ends / tok_begin / tok_end (R, N) int32 and probs (R, N) fp32,
+ *      contiguous; behind the n_words[r] survivors the integers are -1 and probs 0 (written by the same launch).
+ * One workgroup per row, one thread per token and then per word: the word and the survivor numbering are ballot scans with one LDS
+ * exchange each, the per-word values live in LDS, and for the median every word ranks its own duration against the others (ties to
+ * the smaller index).  Takes N <= 1024.
+ * Both: every output word has one writer, no atomics, no workspace, no host synchronisation. */
+typedef struct MopkAlignmentRowsArgs {
+    int32_t R;                           /* rows */
+    int32_t T;                           /* columns of tokens */
+    int32_t T0;                          /* first generated column, 0 <= T0 < T */
+    int32_t Tp;                          /* tokens of the sot sequence, >= 1 */
+    int32_t nots;                        /* the token behind the sot sequence (Whisper's <|notimestamps|>) */
+    int32_t eos;                         /* text tokens are below it; it closes and pads the row */
+    int32_t out_i64;                     /* ids holds int64 (1) or int32 (0) */
+    int32_t sot_i64;                     /* sot holds int64 (1) or int32 (0) */
+    const int32_t *tokens;               /* device (R rows of T) int32 */
+    int64_t tokens_ld;                   /* element stride between rows, >= T */
+    const int32_t *n_take;               /* device (R): generated tokens of row r that are inside its segments */
+    const void *sot;                     /* device (Tp), or (R rows of Tp) with sot_ld */
+    int64_t sot_ld;                      /* element stride between the rows' sot sequences, >= Tp, or 0: one for all */
+    void *ids;                           /* (R, Tp + 2 + T - T0) out, contiguous */
+    int32_t *n_tokens;                   /* (R) out */
+    int32_t *col;                        /* (R, Tp + 2 + T - T0) out, contiguous */
+} MopkAlignmentRowsArgs;
+int mopk_alignment_rows_supported(const MopkAlignmentRowsArgs *a);           /* 1 if the kernel takes this call (T - T0, alignment) */
+int mopk_alignment_rows(const MopkAlignmentRowsArgs *a, void *stream);
+
+typedef struct MopkWordSpansArgs {
+    int32_t R;                           /* rows */
+    int32_t N;                           /* text tokens per row */
+    int32_t V;                           /* entries of table */
+    int32_t median_cap;                  /* frames, >= 0, or -1: no cap */
+    const int32_t *tokens;               /* device (R rows of N) int32 */
+    int64_t tokens_ld;                   /* element stride between rows, >= N */
+    const int32_t *times;                /* device (R rows of N + 1) int32 */
+    int64_t times_ld;                    /* element stride between rows, >= N + 1 */
+    const float *probs;                  /* device (R rows of N) fp32 */
+    int64_t probs_ld;                    /* element stride between rows, >= N */
+    const int32_t *n_text;               /* device (R) */
+    const uint8_t *table;                /* device (V) */
+    int32_t *starts, *ends;              /* (R, N) out: frames */
+    float *out_probs;                    /* (R, N) out */
+    int32_t *tok_begin, *tok_end;        /* (R, N) out: indices into the row's text tokens, the end exclusive */
+    int32_t *n_words;                    /* (R) out */
+} MopkWordSpansArgs;
+int mopk_word_spans_supported(const MopkWordSpansArgs *a);                   /* 1 if the kernel takes this call (N, alignment) */
+int mopk_word_spans(const MopkWordSpansArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
  * Whisper's log-mel spectrogram of a batch of waveforms (audio.py's log_mel_spectrogram; the stage in front of the encoder).
  * (Added under version 118: new exports only; callers detect it with mopk_log_mel_supported.)
  * Clip b holds len_b = min(lens[b], L) samples (L without lens) and T_b = len_b / hop frames; T = L / hop rows are written.

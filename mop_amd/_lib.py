@@ -281,6 +281,26 @@ class WindowPromptsArgs(C.Structure):
     ]
 
 
+class AlignmentRowsArgs(C.Structure):
+    """MopkAlignmentRowsArgs: decoded window rows turned into the padded ids of the alignment pass (transcribe's word timestamps)."""
+    _fields_ = [
+        ("R", C.c_int32), ("T", C.c_int32), ("T0", C.c_int32), ("Tp", C.c_int32), ("nots", C.c_int32), ("eos", C.c_int32),
+        ("out_i64", C.c_int32), ("sot_i64", C.c_int32),
+        ("tokens", _fp), ("tokens_ld", C.c_int64), ("n_take", _fp), ("sot", _fp), ("sot_ld", C.c_int64), ("ids", _fp),
+        ("n_tokens", _fp), ("col", _fp),
+    ]
+
+
+class WordSpansArgs(C.Structure):
+    """MopkWordSpansArgs: aligned text tokens grouped into timed words (Whisper's add_word_timestamps)."""
+    _fields_ = [
+        ("R", C.c_int32), ("N", C.c_int32), ("V", C.c_int32), ("median_cap", C.c_int32),
+        ("tokens", _fp), ("tokens_ld", C.c_int64), ("times", _fp), ("times_ld", C.c_int64), ("probs", _fp), ("probs_ld", C.c_int64),
+        ("n_text", _fp), ("table", _fp), ("starts", _fp), ("ends", _fp), ("out_probs", _fp), ("tok_begin", _fp), ("tok_end", _fp),
+        ("n_words", _fp),
+    ]
+
+
 class LogMelArgs(C.Structure):
     """MopkLogMelArgs: Whisper's log-mel spectrogram of a batch of waveforms (LogMelFrontend)."""
     _fields_ = [
@@ -400,6 +420,10 @@ SYMBOLS = {
     "mopk_prompt_history_update": (C.c_int, [C.POINTER(PromptHistoryArgs), C.c_void_p]),
     "mopk_window_prompts_supported": (C.c_int, [C.POINTER(WindowPromptsArgs)]),
     "mopk_window_prompts": (C.c_int, [C.POINTER(WindowPromptsArgs), C.c_void_p]),
+    "mopk_alignment_rows_supported": (C.c_int, [C.POINTER(AlignmentRowsArgs)]),
+    "mopk_alignment_rows": (C.c_int, [C.POINTER(AlignmentRowsArgs), C.c_void_p]),
+    "mopk_word_spans_supported": (C.c_int, [C.POINTER(WordSpansArgs)]),
+    "mopk_word_spans": (C.c_int, [C.POINTER(WordSpansArgs), C.c_void_p]),
     "mopk_log_mel_supported": (C.c_int, [C.POINTER(LogMelArgs)]),
     "mopk_log_mel_workspace_bytes": (C.c_size_t, [C.POINTER(LogMelArgs)]),
     "mopk_log_mel": (C.c_int, [C.POINTER(LogMelArgs), C.c_void_p]),

@@ -57,6 +57,40 @@ class TokenAlignment(NamedTuple):
     n_tokens: torch.Tensor
 
 
+class WordAlignment(NamedTuple):
+    """word-level timestamps of a batch (`WhisperMoP.align_words`), all on the device, N = T - prompt_len - 2 columns.
+    starts / ends: int32 (B, N), the words' first frame and the frame the next word starts at; probs: fp32 (B, N), the mean
+    probability of a word's own tokens; tok_begin / tok_end: int32 (B, N), the positions of the full token sequence a word spans
+    (the end exclusive); n_words: int32 (B,).  At j >= n_words[b] the integers are -1 and probs is 0."""
+    starts: torch.Tensor
+    ends: torch.Tensor
+    probs: torch.Tensor
+    tok_begin: torch.Tensor
+    tok_end: torch.Tensor
+    n_words: torch.Tensor
+
+
+class TranscriptWords(NamedTuple):
+    """one clip's words (`transcribe(word_timestamps=True)`), all on the device, one entry per word in order.  starts / ends:
+    int32, in frames of the CLIP; probs: fp32; tok_begin / tok_end: int32 indices into Transcript.tokens, the end exclusive (the
+    timestamp tokens between two segments fall inside no word); segment: int64, the index of the segment the word begins in."""
+    starts: torch.Tensor
+    ends: torch.Tensor
+    probs: torch.Tensor
+    tok_begin: torch.Tensor
+    tok_end: torch.Tensor
+    segment: torch.Tensor
+
+
+class _Words(NamedTuple):
+    """transcribe's word timestamps, as checked by _words_check"""
+    rules: "ops.WordRules"
+    heads: List[Tuple[int, int]]
+    medfilt_width: int
+    median_cap: Optional[int]
+    nots: int                            # logit_rules.no_timestamps_token_id
+
+
 class Transcript(NamedTuple):
     """one clip's long-form transcription (`WhisperMoP.transcribe`), all on the device.  starts / ends: int32 (n,), the segments'
     first and last frame, in frames of the CLIP; tokens: (m,) in prompt_ids' dtype, the segments' tokens end to end, timestamp
@@ -1005,10 +1039,9 @@ class WhisperMoP(nn.Module):
         return tokens, sum_lp.view(B, n), DecodeStats(sum_lp.view(B, n), n_tok.view(B, n), no_speech)
 
     # ---- token-level timestamps; inference only ----
-    def _align_check(self, mel, tokens, prompt_len, alignment_heads, medfilt_width):
+    def _align_check(self, mel, tokens, prompt_len, alignment_heads, medfilt_width, what: str = "align_tokens"):
         """align_tokens' argument checks -> (audio batch info, token lengths, (layer, head) pairs); ValueErrors before any device
         work"""
-        what = "align_tokens"
         alens = self._audio_check(mel, what)
         info = mel if alens is None else _Batch((len(alens),), mel[0].device)
         if isinstance(tokens, torch.Tensor):
@@ -1029,6 +1062,10 @@ class WhisperMoP(nn.Module):
                              f"{min(lens)} tokens, prompt_len = {prompt_len}")
         if max(lens) > self.cfg.n_text_ctx:
             raise ValueError(f"{what}: a sequence of {max(lens)} tokens exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+        return info, lens, self._align_heads_check(alignment_heads, medfilt_width, what)
+
+    def _align_heads_check(self, alignment_heads, medfilt_width, what: str):
+        """the tests of the alignment heads and the median width -> the (layer, head) pairs"""
         if isinstance(medfilt_width, bool) or not isinstance(medfilt_width, int) or medfilt_width < 1 or medfilt_width % 2 == 0:
             raise ValueError(f"{what}: medfilt_width must be a positive odd int, got {medfilt_width!r}")
         Ld, H = self.cfg.n_layer_dec, self.cfg.n_head
@@ -1041,7 +1078,7 @@ class WhisperMoP(nn.Module):
             for p in heads:
                 if len(p) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in p) or not (0 <= p[0] < Ld and 0 <= p[1] < H):
                     raise ValueError(f"{what}: alignment head {p} is not a (decoder layer < {Ld}, head < {H}) pair")
-        return info, lens, heads
+        return heads
 
     @torch.no_grad()
     def align_tokens(self, mel, tokens, prompt_len: int, alignment_heads=None, medfilt_width: int = 7, *, return_cost: bool = False):
@@ -1060,7 +1097,15 @@ class WhisperMoP(nn.Module):
         convolutional downsampling: a frame is a mel frame), -1 outside the aligned rows.  return_cost=True also returns the
         (B, T, T_audio) cost matrix the warping ran on."""
         info, lens, heads = self._align_check(mel, tokens, prompt_len, alignment_heads, medfilt_width)
-        dev, B, T = info.device, len(lens), max(lens)
+        ids, n_tokens = self._align_ids(tokens, lens, info.device)
+        starts, ends, cost, _ = self._align(mel, ids, n_tokens, prompt_len, heads, medfilt_width)
+        out = TokenAlignment(starts, ends, n_tokens)
+        return (out, cost) if return_cost else out
+
+    @staticmethod
+    def _align_ids(tokens, lens: List[int], dev):
+        """the padded (B, T) ids and the device lengths of align_tokens' token argument (a tensor, or a list right-padded here)"""
+        B, T = len(lens), max(lens)
         if isinstance(tokens, torch.Tensor):
             ids = tokens
         else:
@@ -1070,6 +1115,15 @@ class WhisperMoP(nn.Module):
         n_tokens = torch.tensor(lens, dtype=torch.int32)
         if dev.type == "cuda":                                         # an asynchronous copy: the host does not wait for it
             n_tokens = n_tokens.pin_memory().to(dev, non_blocking=True)
+        return ids, n_tokens
+
+    def _align(self, mel, ids: torch.Tensor, n_tokens: torch.Tensor, prompt_len: int, heads, medfilt_width: int,
+               token_probs: bool = False, eot: Optional[int] = None):
+        """the alignment pass of align_tokens, align_words and transcribe's word timestamps, on padded ids (B, T) and device
+        lengths n_tokens (B,) int32 -> (starts, ends, cost, tok_probs).  tok_probs is None, or with token_probs the fp32 (B, T)
+        probability the same teacher-forced pass gives token p + 1 at position p, over the columns below eot (all when None): a
+        token at or above eot is read as eot - 1; column T - 1 is unspecified."""
+        dev, (B, T) = ids.device, ids.shape
         enc = self.encode(mel)[0]
         enc_out, audio_lens = _enc_parts(enc)
         Ta = enc_out.shape[1]
@@ -1079,7 +1133,7 @@ class WhisperMoP(nn.Module):
             hooks.append(self.decoder[l].cross_attn.q_proj.register_forward_hook(
                 lambda mod, args, out, l=l: queries.__setitem__(l, out)))
         try:
-            self.decode(enc, ids)
+            logits = self.decode(enc, ids)
         finally:
             for h in hooks:
                 h.remove()
@@ -1096,8 +1150,62 @@ class WhisperMoP(nn.Module):
         probs = torch.softmax(qk, dim=-1)
         cost = ops.alignment_cost(probs, n_tokens, n_frames, medfilt_width)
         starts, ends = ops.dtw_align(cost, n_tokens - 1, n_frames, row0=prompt_len)
-        out = TokenAlignment(starts, ends, n_tokens)
-        return (out, cost) if return_cost else out
+        tok_probs = None
+        if token_probs:
+            Vr = logits.shape[-1] if eot is None else eot
+            nxt = F.pad(ids[:, 1:], (0, 1)).to(torch.int32).clamp(0, Vr - 1).reshape(B * T)
+            tok_probs = ops.token_logprob(logits.view(B * T, -1)[:, :Vr], nxt).exp().view(B, T)
+        return starts, ends, cost, tok_probs
+
+    @torch.no_grad()
+    def align_words(self, mel, tokens, prompt_len: int, word_rules: "ops.WordRules", alignment_heads=None, medfilt_width: int = 7,
+                    median_word_frames: Optional[int] = None, *, eot_token_id: Optional[int] = None) -> WordAlignment:
+        """word-level timestamps, as Whisper's find_alignment and add_word_timestamps compute them -> WordAlignment(starts, ends,
+        probs, tok_begin, tok_end, n_words), all on the device; no host sync.
+
+        mel, tokens, alignment_heads, medfilt_width: as for align_tokens.  Each sequence of n tokens is prompt_len prompt tokens,
+        one lead-in token (Whisper's <|notimestamps|>), the text and a final token: the words are formed from
+        tokens[prompt_len + 1 : n - 1], and the longest sequence must hold at least one text token.  word_rules: the ops.WordRules
+        of the model's vocabulary.  median_word_frames: ops.word_spans' median_cap (Whisper's 0.7 s; None: no cap).
+        The alignment pass is align_tokens' own; text token i begins at times[i] = starts[prompt_len + i], i in [0, n_text], with
+        starts what align_tokens returns for the same call (Whisper's convention: the cross-attention row at position p times
+        token p + 1), and its probability is exp(ops.token_logprob(logits[:, p, :eot_token_id], tokens[:, p + 1])) at
+        p = prompt_len + i, from the same teacher-forced pass, over the columns below eot_token_id as Whisper restricts them
+        (over all columns when it is None).  Text tokens are expected below eot_token_id, as Whisper's are; the ids live on the
+        device, so one at or above it is not refused: its probability is read at column eot_token_id - 1 (the clamp of
+        ops.token_logprob) and is meaningless.  ops.word_spans then groups and times the words; tok_begin / tok_end are shifted to
+        positions of the full sequence."""
+        what = "align_words"
+        info, lens, heads = self._align_check(mel, tokens, prompt_len, alignment_heads, medfilt_width, what)
+        if not isinstance(word_rules, ops.WordRules) or word_rules.vocab_size != self.cfg.vocab_size:
+            raise ValueError(f"{what}: word_rules must be an ops.WordRules of the model's vocabulary ({self.cfg.vocab_size}), got "
+                             f"{getattr(word_rules, 'vocab_size', type(word_rules).__name__)!r}")
+        if max(lens) < prompt_len + 3:
+            raise ValueError(f"{what}: no sequence holds a text token between the lead-in and the final token: the longest has "
+                             f"{max(lens)} tokens, prompt_len = {prompt_len}")
+        cap = self._median_cap_check(median_word_frames, what)
+        if eot_token_id is not None and (isinstance(eot_token_id, bool) or not isinstance(eot_token_id, int)
+                                         or not 2 <= eot_token_id <= self.cfg.vocab_size):
+            raise ValueError(f"{what}: eot_token_id must be None or an int in [2, vocab_size = {self.cfg.vocab_size}], got {eot_token_id!r}")
+        ids, n_tokens = self._align_ids(tokens, lens, info.device)
+        w = self._word_pass(mel, ids, n_tokens, prompt_len, heads, medfilt_width, word_rules, cap, eot_token_id)
+        shift = lambda t: torch.where(t >= 0, t + (prompt_len + 1), t)                 # noqa: E731
+        return WordAlignment(w.starts, w.ends, w.probs, shift(w.tok_begin), shift(w.tok_end), w.n_words)
+
+    @staticmethod
+    def _median_cap_check(median_word_frames, what: str) -> Optional[int]:
+        if median_word_frames is not None and (isinstance(median_word_frames, bool) or not isinstance(median_word_frames, int)
+                                               or not 0 <= median_word_frames < 2 ** 30):
+            raise ValueError(f"{what}: median_word_frames must be None or an int in [0, 2^30) of frames, got {median_word_frames!r}")
+        return median_word_frames
+
+    def _word_pass(self, mel, ids, n_tokens, prompt_len: int, heads, medfilt_width: int, word_rules, cap, eot) -> "ops.WordSpans":
+        """the alignment pass and ops.word_spans on padded ids: the words of ids[:, prompt_len + 1 : n - 1], token indices relative
+        to prompt_len + 1"""
+        T = ids.shape[1]
+        starts, _, _, tok_probs = self._align(mel, ids, n_tokens, prompt_len, heads, medfilt_width, True, eot)
+        text = ids.to(torch.int32)[:, prompt_len + 1:T - 1]
+        return ops.word_spans(text, starts[:, prompt_len:T - 1], tok_probs[:, prompt_len:T - 2], n_tokens - (prompt_len + 2), word_rules, cap)
 
     # ---- long-form transcription; inference only ----
     def _transcribe_check(self, mel, prompt_ids, logit_rules, max_new_tokens, window, frames_per_timestamp, num_beams,
@@ -1318,8 +1426,9 @@ class WhisperMoP(nn.Module):
                     graph: bool = False, temperatures=(0.0,), logprob_threshold: Optional[float] = None,
                     no_speech_threshold: Optional[float] = None, no_speech_token_id: Optional[int] = None, sot_index: int = 0,
                     compression_ratio_threshold: Optional[float] = None, compression_ratio=None, num_samples: int = 1,
-                    seed: int = 0, return_log: bool = False, condition_on_previous_text: bool = False, initial_prompt=None,
-                    sot_prev_token_id: Optional[int] = None, max_prompt_tokens: Optional[int] = None,
+                    seed: int = 0, return_log: bool = False, word_timestamps: bool = False, word_rules=None, alignment_heads=None,
+                    medfilt_width: int = 7, median_word_frames: Optional[int] = None, condition_on_previous_text: bool = False,
+                    initial_prompt=None, sot_prev_token_id: Optional[int] = None, max_prompt_tokens: Optional[int] = None,
                     prompt_reset_temperature: float = 0.5):
         """long-form transcription, Whisper's transcribe loop over windows for a batch of clips -> a list of B Transcript(starts,
         ends, tokens, offsets), all on the device.
@@ -1390,14 +1499,38 @@ class WhisperMoP(nn.Module):
         decoder call captures anew at its own width.
         ValueError before any device work: sot_prev_token_id missing or outside the vocabulary; n < 1; T_p + 1 + n +
         max_new_tokens > n_text_ctx; an initial_prompt that is neither form; a prompt_reset_temperature that is not a number.
-        Out of scope: word grouping, top-k / top-p inside transcribe, handing the encoded audio over to a fallback attempt, a
-        device-side compression ratio, and a vocabulary projection of the prompt pass restricted to the columns that are read."""
+
+        Word timestamps (Whisper's word_timestamps=True).  With word_timestamps False the four keywords behind it are not
+        looked at, and the loop runs the launches and copies described above.  With it, word_rules must be the ops.WordRules of
+        the model's vocabulary and logit_rules.no_timestamps_token_id must be set; alignment_heads and medfilt_width are
+        align_tokens', median_word_frames is ops.word_spans' median_cap (transcribe_audio fills in Whisper's 0.7 s).  Per set of
+        windows, ops.alignment_rows turns the decoded rows and the device count of the tokens their segments span into the
+        alignment pass' ids = [prompt_ids, no-timestamps token, the text tokens (no timestamp tokens, no eos), eos] in one
+        launch BEFORE the download, which becomes (A, 4) and carries each row's number of text tokens: no synchronisation is
+        added.  The host cuts ids to T_p + 2 + the longest text (the width align_tokens' list form pads to); ONE alignment
+        pass (align_words' own, probabilities over the columns below eos) runs over the rows that were not skipped and have
+        text, with their windows as the clips, and ONE ops.word_spans call groups and times their words.  The words join the
+        clip's list with their frames shifted by the window's seek and their token ranges mapped through alignment_rows' col
+        into Transcript.tokens.  A window's word count stays on the device: the padded rows are compacted after the loop by one
+        boolean selection per clip (a synchronisation each, outside the loop), and one torch.searchsorted per clip against
+        Transcript.offsets gives each word's segment.  Returns (transcripts, words), or (transcripts, logs, words) with
+        return_log=True; words is a list of B TranscriptWords, and the transcripts equal those of the same call without word
+        timestamps.
+        ValueError before any device work: word_rules missing or of another vocabulary; no_timestamps_token_id unset; T_p +
+        max_new_tokens + 2 > n_text_ctx; malformed heads, width or median_word_frames.
+        Out of scope: Whisper's pause and segment-boundary heuristics on the words (last_speech_timestamp, preferring the
+        segment-level start / end), hallucination_silence_threshold, word splitting on unicode code points, an alignment pass
+        fused so that it never materialises the probability maps, top-k / top-p inside transcribe, handing the encoded audio over
+        to a fallback attempt or to the alignment pass, a device-side compression ratio, and a vocabulary projection of the prompt
+        pass restricted to the columns that are read."""
         clips, W = self._transcribe_check(mel, prompt_ids, logit_rules, max_new_tokens, window, frames_per_timestamp, num_beams,
                                            length_penalty)
         pol = self._fallback_check(prompt_ids.shape[-1], temperatures, logprob_threshold, no_speech_threshold, no_speech_token_id,
                                    sot_index, compression_ratio_threshold, compression_ratio, num_samples, seed)
         cond = self._condition_check(len(clips), prompt_ids.shape[-1], max_new_tokens, condition_on_previous_text, initial_prompt,
                                      sot_prev_token_id, max_prompt_tokens, prompt_reset_temperature)
+        wt = self._words_check(prompt_ids.shape[-1], max_new_tokens, logit_rules, word_timestamps, word_rules, alignment_heads,
+                               medfilt_width, median_word_frames)
         plain = (pol.temperatures == (0.0,) and logprob_threshold is None and no_speech_threshold is None
                  and no_speech_token_id is None and compression_ratio is None and not return_log)
         calls = [0]
@@ -1422,6 +1555,7 @@ class WhisperMoP(nn.Module):
         total = [int(c.shape[0]) for c in clips]
         seek, n_tok = [0] * B, [0] * B
         parts = [([], [], [], []) for _ in range(B)]                   # per item: starts, ends, tokens, offsets of each window
+        wparts = [([], [], [], [], [], []) for _ in range(B)]          # per item: starts, ends, probs, tok_begin, tok_end, live
         while True:
             act = [b for b in range(B) if seek[b] < total[b]]
             if not act:
@@ -1454,7 +1588,7 @@ class WhisperMoP(nn.Module):
                 modes = [2 if skipped is not None and skipped[a] else int(not cond.on or kept_t[a] > cond.reset_temperature)
                          for a in range(len(act))]
                 lens = torch.stack((lens, torch.tensor(act, dtype=torch.int32), torch.tensor(modes, dtype=torch.int32)))
-            meta = torch.empty(len(act), 3, dtype=torch.int32)
+            meta = torch.empty(len(act), 3 if wt is None else 4, dtype=torch.int32)
             if dev.type == "cuda":                                     # an asynchronous copy: the host does not wait for it
                 lens, meta = lens.pin_memory().to(dev, non_blocking=True), meta.pin_memory()
             if build is not None:
@@ -1463,10 +1597,21 @@ class WhisperMoP(nn.Module):
             seg = ops.timestamp_segments(rows32, T_p, lens, tb, eos, frames_per_timestamp)
             last = seg.tok_end.gather(1, (seg.n_segments - 1).clamp_min(0).long().unsqueeze(1)).squeeze(1)
             spanned = torch.where(seg.n_segments > 0, last - T_p, 0)   # a window's segments are contiguous from column T_p on
-            meta.copy_(torch.stack((seg.advance, seg.n_segments, spanned.to(torch.int32)), dim=1))      # the one synchronisation
+            cols = (seg.advance, seg.n_segments, spanned.to(torch.int32))
+            if wt is not None:
+                sot = prompt_ids if prompt_ids.dim() == 1 or len(act) == B else torch.stack([prompt_ids[b] for b in act])
+                if sot.dtype not in (torch.int32, torch.int64):
+                    sot = sot.to(torch.int64)
+                ar = ops.alignment_rows(rows32, T_p, cols[2], sot, wt.nots, eos, torch.int32)
+                cols += (ar.n_tokens - (T_p + 2),)
+            meta.copy_(torch.stack(cols, dim=1))                       # the one synchronisation
             if build is not None:
                 ops.prompt_history_update(hist, hist_len, rows32, T_p, spanned.to(torch.int32), item, mode)
-            for a, (adv, n, m) in enumerate(meta.tolist()):
+            meta = meta.tolist()
+            if wt is not None:
+                self._window_words(wt, ar, [r[3] for r in meta], skipped, wins, [seek[b] for b in act], [n_tok[b] for b in act],
+                                   [wparts[b] for b in act], T_p, eos)
+            for a, (adv, n, m) in enumerate(r[:3] for r in meta):
                 b = act[a]
                 if skipped is not None and skipped[a]:                 # no speech: nothing joins the transcript, seek moves on
                     adv, n, m = int(wins[a].shape[0]), 0, 0
@@ -1483,7 +1628,67 @@ class WhisperMoP(nn.Module):
         for b, (st, en, tk, off) in enumerate(parts):
             off.append(torch.full((1,), n_tok[b], dtype=torch.int32, device=dev))
             out.append(Transcript(torch.cat(st), torch.cat(en), torch.cat(tk), torch.cat(off)))
-        return (out, logs) if return_log else out
+        if wt is None:
+            return (out, logs) if return_log else out
+        words = []
+        for b, wp in enumerate(wparts):
+            if wp[0]:
+                live = torch.cat(wp[5])
+                st, en, pr, tb_, te_ = (torch.cat(x)[live] for x in wp[:5])
+            else:                                                      # no window of this clip had text
+                st, en, tb_, te_ = (torch.empty(0, dtype=torch.int32, device=dev) for _ in range(4))
+                pr = torch.empty(0, dtype=torch.float32, device=dev)
+            words.append(TranscriptWords(st, en, pr, tb_, te_, torch.searchsorted(out[b].offsets, tb_, right=True) - 1))
+        return (out, logs, words) if return_log else (out, words)
+
+    def _words_check(self, T_p: int, max_new_tokens: int, logit_rules, word_timestamps, word_rules, alignment_heads, medfilt_width,
+                     median_word_frames) -> Optional[_Words]:
+        """the checks of transcribe's word timestamps -> what the loop needs, None without them; ValueErrors before any device
+        work"""
+        what = "transcribe"
+        if not isinstance(word_timestamps, bool):
+            raise ValueError(f"{what}: word_timestamps must be a bool, got {word_timestamps!r}")
+        if not word_timestamps:
+            return None
+        if not isinstance(word_rules, ops.WordRules) or word_rules.vocab_size != self.cfg.vocab_size:
+            raise ValueError(f"{what}: word_timestamps needs word_rules, an ops.WordRules of the model's vocabulary "
+                             f"({self.cfg.vocab_size}), got {getattr(word_rules, 'vocab_size', type(word_rules).__name__)!r}")
+        if logit_rules.no_timestamps_token_id is None:
+            raise ValueError(f"{what}: word_timestamps needs logit_rules.no_timestamps_token_id (the alignment pass decodes the "
+                             f"text behind it)")
+        if T_p + max_new_tokens + 2 > self.cfg.n_text_ctx:
+            raise ValueError(f"{what}: word_timestamps aligns up to T_p + max_new_tokens + 2 = {T_p + max_new_tokens + 2} tokens, "
+                             f"beyond n_text_ctx = {self.cfg.n_text_ctx}")
+        heads = self._align_heads_check(alignment_heads, medfilt_width, what)
+        return _Words(word_rules, heads, medfilt_width, self._median_cap_check(median_word_frames, what),
+                      logit_rules.no_timestamps_token_id)
+
+    def _window_words(self, wt: _Words, ar, n_text: List[int], skipped, wins, seeks: List[int], n_toks: List[int], wparts, T_p: int,
+                      eos: int) -> None:
+        """the words of one set of windows: one alignment pass and one ops.word_spans call over the rows that were not skipped
+        and have text; each row's padded results and a mask of its live words are appended to its clip's wparts"""
+        sel = [a for a in range(len(n_text)) if n_text[a] > 0 and not (skipped is not None and skipped[a])]
+        if not sel:
+            return
+        dev = ar.ids.device
+        width = T_p + 2 + max(n_text[a] for a in sel)
+        ids, n_tokens, col = ar.ids, ar.n_tokens, ar.col
+        shift = torch.tensor([[seeks[a] for a in sel], [n_toks[a] - T_p for a in sel], sel], dtype=torch.int32)
+        if dev.type == "cuda":                                         # an asynchronous copy: the host does not wait for it
+            shift = shift.pin_memory().to(dev, non_blocking=True)
+        if len(sel) < len(n_text):
+            pick = shift[2].long()
+            ids, n_tokens, col = ids[pick], n_tokens[pick], col[pick]
+        w = self._word_pass([wins[a] for a in sel], ids[:, :width], n_tokens, T_p, wt.heads, wt.medfilt_width, wt.rules,
+                            wt.median_cap, eos)
+        live = w.tok_begin >= 0
+        seek, base = shift[0].unsqueeze(1), shift[1].unsqueeze(1)
+        at = lambda t: col.gather(1, t.clamp_min(0).long())                            # noqa: E731  text token -> column of the row
+        for k, v in enumerate((torch.where(live, w.starts + seek, -1), torch.where(live, w.ends + seek, -1), w.probs,
+                               torch.where(live, at(w.tok_begin) + base, -1), torch.where(live, at(w.tok_end - 1) + 1 + base, -1),
+                               live)):
+            for i, a in enumerate(sel):
+                wparts[a][k].append(v[i])
 
     @torch.no_grad()
     def transcribe_audio(self, audio, frontend: "LogMelFrontend", prompt_ids: torch.Tensor, logit_rules: "ops.LogitRules",
@@ -1494,10 +1699,13 @@ class WhisperMoP(nn.Module):
         `transcribe`, whose pinned signature cannot take the policy's keywords: a subclass that overrides `transcribe` overrides
         `_transcribe` for this entry point.
         Every keyword of transcribe passes through (the temperature fallback and the no-speech skip included; with return_log=True
-        the logs come back beside the transcripts).  A segment's frames times frontend.frame_seconds are seconds.  ValueError when frontend.n_mels is not the model's."""
+        the logs come back beside the transcripts; with word_timestamps=True the words too, and a median_word_frames the caller
+        leaves out becomes round(0.7 / frontend.frame_seconds), Whisper's 0.7 s).  A segment's frames times frontend.frame_seconds are seconds.  ValueError when frontend.n_mels is not the model's."""
         if not isinstance(frontend, LogMelFrontend) or frontend.n_mels != self.cfg.n_mels:
             raise ValueError(f"transcribe_audio: frontend must be a LogMelFrontend with n_mels = {self.cfg.n_mels} (the model's), got "
                              f"{getattr(frontend, 'n_mels', type(frontend).__name__)!r}")
+        if transcribe_kwargs.get("word_timestamps") and transcribe_kwargs.get("median_word_frames") is None:
+            transcribe_kwargs["median_word_frames"] = round(0.7 / frontend.frame_seconds)       # Whisper's 0.7 s cap
         return self._transcribe(frontend(audio), prompt_ids, logit_rules, max_new_tokens, **transcribe_kwargs)
 
     @torch.no_grad()
@@ -1574,8 +1782,8 @@ class RuledDecoding:
     list, blank suppression at the first generated position, the timestamp grammar) applied to every step's last-position logits
     by ops.logit_rules, one HIP launch inside the step.  The decoders' own signatures do not change (their tests pin them); each
     method here takes the arguments of the method it names, and what came later as keywords of its own: the decoding statistics
-    (return_stats, no_speech_token_id, sot_index) and, on transcribe, the temperature fallback, the no-speech skip and the
-    conditioning on the previous text.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
+    (return_stats, no_speech_token_id, sot_index) and, on transcribe, the temperature fallback, the no-speech skip, the
+    conditioning on the previous text and the word timestamps.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
     (ValueError).  logit_rules None runs the plain decoder: no extra launch, no extra buffer."""
 
     def __init__(self, model: WhisperMoP, logit_rules: Optional["ops.LogitRules"]):
@@ -1616,8 +1824,10 @@ class RuledDecoding:
                    temperatures=(0.0,), logprob_threshold: Optional[float] = None, no_speech_threshold: Optional[float] = None,
                    no_speech_token_id: Optional[int] = None, sot_index: int = 0, compression_ratio_threshold: Optional[float] = None,
                    compression_ratio=None, num_samples: int = 1, seed: int = 0, return_log: bool = False,
-                   condition_on_previous_text: bool = False, initial_prompt=None, sot_prev_token_id: Optional[int] = None,
-                   max_prompt_tokens: Optional[int] = None, prompt_reset_temperature: float = 0.5):
+                   word_timestamps: bool = False, word_rules=None, alignment_heads=None, medfilt_width: int = 7,
+                   median_word_frames: Optional[int] = None, condition_on_previous_text: bool = False, initial_prompt=None,
+                   sot_prev_token_id: Optional[int] = None, max_prompt_tokens: Optional[int] = None,
+                   prompt_reset_temperature: float = 0.5):
         return self.model._transcribe(
             mel, prompt_ids, self.logit_rules, max_new_tokens, window=window, frames_per_timestamp=frames_per_timestamp,
             num_beams=num_beams, length_penalty=length_penalty, graph=graph, temperatures=temperatures,
@@ -1625,7 +1835,8 @@ class RuledDecoding:
             sot_index=sot_index, compression_ratio_threshold=compression_ratio_threshold, compression_ratio=compression_ratio,
             num_samples=num_samples, seed=seed, return_log=return_log, condition_on_previous_text=condition_on_previous_text,
             initial_prompt=initial_prompt, sot_prev_token_id=sot_prev_token_id, max_prompt_tokens=max_prompt_tokens,
-            prompt_reset_temperature=prompt_reset_temperature)
+            prompt_reset_temperature=prompt_reset_temperature, word_timestamps=word_timestamps, word_rules=word_rules,
+            alignment_heads=alignment_heads, medfilt_width=medfilt_width, median_word_frames=median_word_frames)
 
 
 RuledDecoding.transcribe.__doc__ = WhisperMoP._transcribe.__doc__

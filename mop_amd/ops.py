@@ -1962,7 +1962,7 @@ def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
 
 
 # ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, token_logprob, greedy_pick,
-# alignment_cost, dtw_align, timestamp_segments, prompt_history_update, window_prompts ----
+# alignment_cost, dtw_align, timestamp_segments, prompt_history_update, window_prompts, alignment_rows, word_spans ----
 # Each is its _*_check (every ValueError, once per call), its _*_accept (the tensor-side tests, then the args struct, built once,
 # if the library's _supported query takes it, else None), then the torch restatement, or the outputs into that struct and _row_launch.
 def _row_launch(a, sym: str, key: str, dev=None, ws_sym: Optional[str] = None) -> None:
@@ -3449,6 +3449,362 @@ def window_prompts(hist: torch.Tensor, hist_len: torch.Tensor, item: torch.Tenso
         a.ids, a.kv_start = ids.data_ptr(), ks.data_ptr()                          # in place of the stand-ins
         _row_launch(a, "mopk_window_prompts", "window_prompts")
         return WindowPrompts(ids, ks)
+
+
+# --------------------------------------------------------------------------------------
+# Word timestamps (WhisperMoP.align_words, transcribe(word_timestamps=True)): the tokenizer's part as a table over the vocabulary,
+# decoded window rows turned into alignment inputs, and Whisper's word grouping and timing on the aligned text tokens
+ALIGNMENT_ROWS_MAX_COLS = 1024 # generated columns of a row (one thread each)
+WORD_SPANS_MAX_TOKENS = 1024   # text tokens of a row (one thread each)
+WORD_BEGIN, WORD_PREPEND, WORD_APPEND, WORD_SENTENCE_END = 1, 2, 4, 8      # the bits of WordRules.table
+
+
+class WordRules:
+    """what Whisper's word grouping (split_tokens_on_spaces, merge_punctuations, the sentence-end truncation of
+    add_word_timestamps) reads from a tokenizer, as a (V,) uint8 table over the token ids: bit 0 (1) the token begins a word,
+    bit 1 (2) it is prepend punctuation, bit 2 (4) append punctuation, bit 3 (8) a sentence-end mark.
+
+    word_begin, prepend_punct, append_punct, sentence_end: each an iterable of token ids or a bool (V,) tensor.  The constructor
+    validates everything (ValueError) before any device work and builds `table` once, on `device` (default: the CPU);
+    `on(device)` returns the table's copy on a device, made once per device.  `from_pieces` builds the rules from the decoded
+    text of every token."""
+
+    def __init__(self, vocab_size: int, word_begin, prepend_punct=(), append_punct=(), sentence_end=(), device=None):
+        if isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1:
+            raise ValueError(f"WordRules: vocab_size must be an int >= 1, got {vocab_size!r}")
+        V = vocab_size
+        mask = torch.zeros(V, dtype=torch.uint8)
+        for bit, name, arg in ((WORD_BEGIN, "word_begin", word_begin), (WORD_PREPEND, "prepend_punct", prepend_punct),
+                               (WORD_APPEND, "append_punct", append_punct), (WORD_SENTENCE_END, "sentence_end", sentence_end)):
+            if isinstance(arg, torch.Tensor):
+                if arg.dtype != torch.bool or arg.shape != (V,):
+                    raise ValueError(f"WordRules: a tensor {name} must be bool ({V},), got {(tuple(arg.shape), arg.dtype)}")
+                mask |= arg.to("cpu", torch.uint8) * bit
+                continue
+            if isinstance(arg, (str, bytes)) or not hasattr(arg, "__iter__"):
+                raise ValueError(f"WordRules: {name} must be an iterable of token ids or a bool ({V},) tensor, got {type(arg).__name__}")
+            ids = []
+            for x in arg:
+                if isinstance(x, bool) or not isinstance(x, int):
+                    raise ValueError(f"WordRules: {name} id must be an int, got {x!r}")
+                if not 0 <= x < V:
+                    raise ValueError(f"WordRules: {name} id = {x} outside [0, vocab_size = {V})")
+                ids.append(x)
+            if ids:
+                mask[torch.tensor(ids, dtype=torch.long)] |= bit
+        self.vocab_size = V
+        self._tables = {torch.device("cpu"): mask}
+        self.table = self.on("cpu" if device is None else device)
+
+    def on(self, device) -> torch.Tensor:
+        """the (V,) uint8 table on `device` (copied there once, without a host sync)"""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self._tables.get(device)
+        if t is None:
+            cpu = self._tables[torch.device("cpu")]
+            t = cpu.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else cpu.to(device)
+            self._tables[device] = t
+        return t
+
+    @classmethod
+    def from_pieces(cls, pieces, prepend="\"'“¿([{-", append="\"'.。,，!！?？:：”)]}、", sentence_end=".。!！?？", device=None):
+        """the rules of a vocabulary whose token v decodes to the text pieces[v] (None: a token without text, no bit), after
+        Whisper's split_tokens_on_spaces and merge_punctuations:
+        begin: the piece starts with " ", or piece.strip() is one character of string.punctuation;
+        prepend: the piece starts with " " and piece.strip() is in `prepend`;  append: the piece itself, unstripped, is in `append`
+        and not empty;  sentence end: the piece is a single character of `sentence_end`.
+        Languages that Whisper splits on unicode code points rather than on spaces are not covered."""
+        import string
+        pieces = list(pieces)
+        if any(p is not None and not isinstance(p, str) for p in pieces):
+            raise ValueError("WordRules.from_pieces: every piece must be a str or None")
+        if not all(isinstance(s, str) for s in (prepend, append, sentence_end)):
+            raise ValueError("WordRules.from_pieces: prepend, append and sentence_end must be str")
+        sets = ([], [], [], [])
+        for v, p in enumerate(pieces):
+            if p is None:
+                continue
+            core = p.strip()
+            if p.startswith(" ") or (len(core) == 1 and core in string.punctuation):
+                sets[0].append(v)
+            if p.startswith(" ") and core in prepend:               # str containment, as Whisper tests it: " " counts
+                sets[1].append(v)
+            if p and p in append:
+                sets[2].append(v)
+            if len(p) == 1 and p in sentence_end:
+                sets[3].append(v)
+        return cls(len(pieces), *sets, device=device)
+
+
+class AlignmentRows(NamedTuple):
+    """the alignment inputs of a set of decoded windows (`alignment_rows`), W = T_p + 2 + (T - t0) columns: ids (R, W), each row
+    [sot, no-timestamps token, text tokens, eos ...]; n_tokens (R,) int32 = T_p + 2 + the row's text tokens; col (R, W) int32, the
+    column of `tokens` text token i came from, -1 behind the row's text tokens"""
+    ids: torch.Tensor
+    n_tokens: torch.Tensor
+    col: torch.Tensor
+
+
+class WordSpans(NamedTuple):
+    """the words of a batch of aligned token rows (`word_spans`): starts / ends (R, N) int32 frames, probs (R, N) fp32,
+    tok_begin / tok_end (R, N) int32 indices into the row's text tokens (the end exclusive), n_words (R,) int32; at
+    j >= n_words[r] the integers are -1 and probs is 0"""
+    starts: torch.Tensor
+    ends: torch.Tensor
+    probs: torch.Tensor
+    tok_begin: torch.Tensor
+    tok_end: torch.Tensor
+    n_words: torch.Tensor
+
+
+def _int_matrix_check(t, name: str, what: str, shape=None) -> None:
+    if (not isinstance(t, torch.Tensor) or t.dim() != 2 or 0 in t.shape or t.dtype.is_floating_point or t.dtype.is_complex
+            or t.dtype == torch.bool or (shape is not None and tuple(t.shape) != shape)):
+        raise ValueError(f"{what}: {name} must be a non-empty integer {'(R, T)' if shape is None else shape} tensor, got "
+                         f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+
+
+def _ar_check(tokens, t0, n_take, sot, no_timestamps_token_id, eos_token_id, dtype, what: str) -> None:
+    """validate an alignment_rows call before any device work"""
+    _int_matrix_check(tokens, "tokens", what)
+    R, T = tokens.shape
+    if not _is_int(t0) or not 0 <= t0 < T:
+        raise ValueError(f"{what}: t0 must be an int in [0, T = {T}), got {t0!r}")
+    _lens_i32_check(n_take, R, tokens.device, "n_take", what, "the tokens")
+    if (not isinstance(sot, torch.Tensor) or sot.dim() not in (1, 2) or 0 in sot.shape or sot.dtype not in (torch.int32, torch.int64)
+            or (sot.dim() == 2 and sot.shape[0] != R)):
+        raise ValueError(f"{what}: sot must be an int32 or int64 (T_p,) or ({R}, T_p) tensor, got "
+                         f"{(tuple(sot.shape), sot.dtype) if isinstance(sot, torch.Tensor) else type(sot).__name__}")
+    if sot.device != tokens.device:
+        raise ValueError(f"{what}: sot is on {sot.device}, the tokens on {tokens.device}")
+    for name, x in (("no_timestamps_token_id", no_timestamps_token_id), ("eos_token_id", eos_token_id)):
+        if not _is_int(x) or not 0 <= x < 2 ** 31:
+            raise ValueError(f"{what}: {name} must be an int in [0, 2^31), got {x!r}")
+    if dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: dtype must be torch.int32 or torch.int64, got {dtype!r}")
+
+
+def alignment_rows_torch(tokens: torch.Tensor, t0: int, n_take: torch.Tensor, sot: torch.Tensor, no_timestamps_token_id: int,
+                         eos_token_id: int, dtype: torch.dtype = torch.int64) -> AlignmentRows:
+    """the restatement of `alignment_rows` in torch ops (CPU or GPU, vectorised over rows, no host sync): a cumulative sum numbers
+    the text tokens, and scatters into buffers with one spare column that takes the write of every column that has none to make"""
+    _ar_check(tokens, t0, n_take, sot, no_timestamps_token_id, eos_token_id, dtype, "alignment_rows_torch")
+    R, T = tokens.shape
+    dev, S, Tp = tokens.device, T - t0, sot.shape[-1]
+    W = Tp + 2 + S
+    g = tokens[:, t0:].to(torch.long)
+    j = torch.arange(S, device=dev).unsqueeze(0)
+    text = (j < n_take.to(torch.long).clamp(0, S).unsqueeze(1)) & (g < eos_token_id)
+    pos = text.cumsum(1) - text.long()
+    ids = torch.full((R, W + 1), eos_token_id, dtype=torch.long, device=dev)
+    ids[:, :Tp] = sot.to(torch.long)
+    ids[:, Tp] = no_timestamps_token_id
+    ids.scatter_(1, torch.where(text, Tp + 1 + pos, W), g)
+    col = torch.full((R, W + 1), -1, dtype=torch.long, device=dev)
+    col.scatter_(1, torch.where(text, pos, W), (t0 + j).expand(R, S))
+    return AlignmentRows(ids[:, :W].to(dtype), (Tp + 2 + text.sum(1)).to(torch.int32), col[:, :W].to(torch.int32))
+
+
+def _ar_accept(tokens, t0, n_take, sot, no_timestamps_token_id, eos_token_id, dtype):
+    """the args struct of a call that mopk_alignment_rows takes, None of one it refuses; the outputs hold stand-ins"""
+    R, T = tokens.shape
+    Tp = sot.shape[-1]
+    if not tokens.is_cuda or tokens.dtype != torch.int32 or (T > 1 and tokens.stride(1) != 1) or (R > 1 and tokens.stride(0) < T):
+        return None
+    if n_take.dtype != torch.int32 or (R > 1 and n_take.stride(0) != 1) or T - t0 > ALIGNMENT_ROWS_MAX_COLS:
+        return None
+    if (Tp > 1 and sot.stride(-1) != 1) or (sot.dim() == 2 and R > 1 and sot.stride(0) < Tp):
+        return None
+    a = L.AlignmentRowsArgs()
+    a.R, a.T, a.T0, a.Tp, a.nots, a.eos = R, T, t0, Tp, no_timestamps_token_id, eos_token_id
+    a.out_i64, a.sot_i64 = int(dtype == torch.int64), int(sot.dtype == torch.int64)
+    a.tokens, a.tokens_ld, a.n_take, a.sot = tokens.data_ptr(), (T if R == 1 else tokens.stride(0)), n_take.data_ptr(), sot.data_ptr()
+    a.sot_ld = 0 if sot.dim() == 1 else (Tp if R == 1 else sot.stride(0))
+    a.ids = a.n_tokens = a.col = 8                                                 # stand-ins: only their alignment is looked at
+    return a if L.lib().mopk_alignment_rows_supported(C.byref(a)) else None
+
+
+def alignment_rows_supported(tokens: torch.Tensor, t0: int, n_take: torch.Tensor, sot: torch.Tensor, no_timestamps_token_id: int,
+                             eos_token_id: int, dtype: torch.dtype = torch.int64) -> bool:
+    """True if mopk_alignment_rows takes this call: CUDA int32 tokens with unit inner stride and a row stride >= T (one row: any),
+    a contiguous int32 n_take, a sot with unit inner stride, T - t0 <= 1024 (the library's own query decides the rest).  Raises
+    ValueError on bad arguments."""
+    _ar_check(tokens, t0, n_take, sot, no_timestamps_token_id, eos_token_id, dtype, "alignment_rows_supported")
+    return _ar_accept(tokens, t0, n_take, sot, no_timestamps_token_id, eos_token_id, dtype) is not None
+
+
+def alignment_rows(tokens: torch.Tensor, t0: int, n_take: torch.Tensor, sot: torch.Tensor, no_timestamps_token_id: int,
+                   eos_token_id: int, dtype: torch.dtype = torch.int64) -> AlignmentRows:
+    """the inputs of the alignment pass behind word timestamps, from the decoded rows of a set of windows (the text_tokens of
+    Whisper's find_alignment: no timestamp tokens, no eos, the <|notimestamps|> lead-in) -> AlignmentRows(ids, n_tokens, col).
+    Inference only.
+
+    tokens: (R, T) int32 decoder outputs, the rows `timestamp_segments` takes (unit inner stride, any row stride >= T); t0: the
+    first generated column.  n_take: (R,) int32 device tensor, how many generated tokens of row r lie inside its segments, clamped
+    into [0, T - t0].  sot: the prompt the alignment pass runs under, an int32 or int64 (T_p,) tensor or (R, T_p), one per row.
+    With g = tokens[r, t0:] and W = T_p + 2 + (T - t0):
+    ids[r] = sot_r, no_timestamps_token_id, the g[j] < eos_token_id among j < n_take[r] in order (n_text[r] of them), then
+    eos_token_id to the end of the row;  n_tokens[r] = T_p + 2 + n_text[r];  col[r, i] = t0 + j of text token i for i < n_text[r],
+    else -1.  ids has `dtype` (int32 or int64), n_tokens and col are int32.
+    Runs the HIP kernel (mopk_alignment_rows: one launch, a stable compaction by wave ballots) when alignment_rows_supported()
+    accepts the call, else alignment_rows_torch(); LAST_PATH["alignment_rows"] records which.  No host sync, no workspace; bitwise
+    reproducible."""
+    _ar_check(tokens, t0, n_take, sot, no_timestamps_token_id, eos_token_id, dtype, "alignment_rows")
+    with torch.no_grad():
+        a = _ar_accept(tokens, t0, n_take, sot, no_timestamps_token_id, eos_token_id, dtype)
+        if a is None:
+            LAST_PATH["alignment_rows"] = L.PATH_GENERIC
+            return alignment_rows_torch(tokens, t0, n_take, sot, no_timestamps_token_id, eos_token_id, dtype)
+        W = a.Tp + 2 + a.T - a.T0
+        ids = torch.empty(a.R, W, dtype=dtype, device=tokens.device)
+        col = torch.empty(a.R, W, dtype=torch.int32, device=tokens.device)
+        n_tokens = torch.empty(a.R, dtype=torch.int32, device=tokens.device)
+        a.ids, a.n_tokens, a.col = ids.data_ptr(), n_tokens.data_ptr(), col.data_ptr()     # in place of the stand-ins
+        _row_launch(a, "mopk_alignment_rows", "alignment_rows")
+        return AlignmentRows(ids, n_tokens, col)
+
+
+def _ws_check(tokens, times, probs, n_text, word_rules, median_cap, what: str) -> None:
+    """validate a word_spans call before any device work"""
+    _int_matrix_check(tokens, "tokens", what)
+    R, N = tokens.shape
+    _int_matrix_check(times, "times", what, (R, N + 1))
+    if not isinstance(probs, torch.Tensor) or tuple(probs.shape) != (R, N) or probs.dtype != torch.float32:
+        raise ValueError(f"{what}: probs must be an fp32 ({R}, {N}) tensor, got "
+                         f"{(tuple(probs.shape), probs.dtype) if isinstance(probs, torch.Tensor) else type(probs).__name__}")
+    for name, t in (("times", times), ("probs", probs)):
+        if t.device != tokens.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, the tokens on {tokens.device}")
+    _lens_i32_check(n_text, R, tokens.device, "n_text", what, "the tokens")
+    if not isinstance(word_rules, WordRules):
+        raise ValueError(f"{what}: word_rules must be a WordRules, got {type(word_rules).__name__}")
+    if median_cap is not None and (not _is_int(median_cap) or not 0 <= median_cap < 2 ** 30):
+        raise ValueError(f"{what}: median_cap must be None or an int in [0, 2^30), got {median_cap!r}")
+
+
+def word_spans_torch(tokens: torch.Tensor, times: torch.Tensor, probs: torch.Tensor, n_text: torch.Tensor, word_rules: WordRules,
+                     median_cap: Optional[int] = None) -> WordSpans:
+    """the restatement of `word_spans` in torch ops (CPU or GPU, vectorised over rows, no host sync): cumulative sums number the
+    words and the survivors, a sort finds the median, and scatters into buffers with one spare column place the results.  A
+    word's probability is the difference of a float64 running sum, rounded to fp32 once."""
+    _ws_check(tokens, times, probs, n_text, word_rules, median_cap, "word_spans_torch")
+    R, N = tokens.shape
+    dev, V = tokens.device, word_rules.vocab_size
+    table = word_rules.on(dev).to(torch.long)
+    n = n_text.to(torch.long).clamp(0, N).unsqueeze(1)
+    i = torch.arange(N, device=dev).unsqueeze(0)                                   # a token index, and later a word index
+    c = torch.where(i < n, table[tokens.to(torch.long).clamp(0, V - 1)], 0)
+    begin = (i < n) & ((i == 0) | ((c & WORD_BEGIN) != 0))                         # rule 1
+    K = begin.sum(1, keepdim=True)
+    o = n.expand(R, N + 2).clone()                                                 # o[k] = n at k >= K
+    o.scatter_(1, torch.where(begin, begin.cumsum(1) - 1, N + 1), i.expand(R, N))
+    o0, o1 = o[:, :N], o[:, 1:N + 1]
+    word = i < K
+    tm = times.to(torch.long)
+    s, e = tm.gather(1, o0), tm.gather(1, o1)
+    cs = F.pad(torch.where(i < n, probs, 0).to(torch.float64).cumsum(1), (1, 0))
+    p = ((cs.gather(1, o1) - cs.gather(1, o0)) / (o1 - o0).clamp_min(1)).to(torch.float32)
+    fl = torch.where(word & (o1 - o0 == 1), c.gather(1, o0.clamp_max(N - 1)), 0)
+    P, A, E = ((fl & b) != 0 for b in (WORD_PREPEND, WORD_APPEND, WORD_SENTENCE_END))
+    d = torch.where(word, e - s, 0)
+    nz = word & (d != 0)                                                           # rule 2
+    M = nz.sum(1, keepdim=True)
+    srt = torch.where(nz, d, torch.iinfo(torch.long).max).sort(1).values
+    m2 = torch.where(M > 0, srt.gather(1, ((M - 1) // 2).clamp_min(0)) + srt.gather(1, (M // 2).clamp_max(N - 1)), 0)
+    max_dur = m2 if median_cap is None else m2.clamp_max(2 * median_cap)
+    before = lambda t: F.pad(t, (1, 0))[:, :N]                                     # noqa: E731  the flag of word k - 1
+    long_ = word & (i >= 1) & (d > max_dur)                                        # rule 3
+    e2 = torch.where(long_ & E, s + max_dur, e)
+    s2 = torch.where(long_ & ~E & before(E), e - max_dur, s)
+    die1 = P & (i < K - 1)                                                         # rule 4
+    die2 = word & (i >= 1) & ~die1 & A & ~before(die1)                             # rule 5
+    surv = word & ~die1 & ~die2                                                    # rule 6
+    idx = surv.cumsum(1) - surv.long()
+    nw = surv.sum(1, keepdim=True)
+    tb = n.expand(R, N + 2).clone()                                                # tb[j] = n at j >= n_words
+    tb.scatter_(1, torch.where(word & ~before(die1) & (surv | die1), idx, N + 1), o0)
+    to = torch.where(surv, idx, N)
+    starts, ends = (torch.full((R, N + 1), -1, dtype=torch.long, device=dev).scatter_(1, to, v)[:, :N] for v in (s2, e2))
+    out_p = torch.zeros(R, N + 1, dtype=torch.float32, device=dev).scatter_(1, to, p)[:, :N]
+    live = i < nw
+    i32 = lambda t: t.to(torch.int32)                                              # noqa: E731
+    return WordSpans(i32(starts), i32(ends), out_p, i32(torch.where(live, tb[:, :N], -1)), i32(torch.where(live, tb[:, 1:N + 1], -1)),
+                     i32(nw.squeeze(1)))
+
+
+def _ws_accept(tokens, times, probs, n_text, word_rules, median_cap):
+    """the args struct of a call that mopk_word_spans takes, None of one it refuses; the outputs hold stand-ins"""
+    R, N = tokens.shape
+    if not tokens.is_cuda or tokens.dtype != torch.int32 or times.dtype != torch.int32 or N > WORD_SPANS_MAX_TOKENS:
+        return None
+    if (N > 1 and (tokens.stride(1) != 1 or probs.stride(1) != 1)) or times.stride(1) != 1:
+        return None
+    if R > 1 and (tokens.stride(0) < N or probs.stride(0) < N or times.stride(0) < N + 1):
+        return None
+    if n_text.dtype != torch.int32 or (R > 1 and n_text.stride(0) != 1):
+        return None
+    a = L.WordSpansArgs()
+    a.R, a.N, a.V, a.median_cap = R, N, word_rules.vocab_size, (-1 if median_cap is None else median_cap)
+    a.tokens, a.times, a.probs = tokens.data_ptr(), times.data_ptr(), probs.data_ptr()
+    a.tokens_ld, a.times_ld, a.probs_ld = (N, N + 1, N) if R == 1 else (tokens.stride(0), times.stride(0), probs.stride(0))
+    a.n_text, a.table = n_text.data_ptr(), word_rules.on(tokens.device).data_ptr()
+    a.starts = a.ends = a.out_probs = a.tok_begin = a.tok_end = a.n_words = 8      # stand-ins: only their alignment is looked at
+    return a if L.lib().mopk_word_spans_supported(C.byref(a)) else None
+
+
+def word_spans_supported(tokens: torch.Tensor, times: torch.Tensor, probs: torch.Tensor, n_text: torch.Tensor,
+                         word_rules: WordRules, median_cap: Optional[int] = None) -> bool:
+    """True if mopk_word_spans takes this call: CUDA tensors, int32 tokens and times and fp32 probs with unit inner strides and
+    row strides that hold a row (one row: any), a contiguous int32 n_text, N <= 1024 (the library's own query decides the rest).
+    Raises ValueError on bad arguments."""
+    _ws_check(tokens, times, probs, n_text, word_rules, median_cap, "word_spans_supported")
+    return _ws_accept(tokens, times, probs, n_text, word_rules, median_cap) is not None
+
+
+def word_spans(tokens: torch.Tensor, times: torch.Tensor, probs: torch.Tensor, n_text: torch.Tensor, word_rules: WordRules,
+               median_cap: Optional[int] = None) -> WordSpans:
+    """Whisper's word grouping and timing (find_alignment's split into words, then add_word_timestamps' duration bound and
+    merge_punctuations) on a batch of aligned token rows -> WordSpans(starts, ends, probs, tok_begin, tok_end, n_words).
+    Inference only.
+
+    tokens: (R, N) int32 text tokens (ids are clamped into [0, V) for the table lookup).  times: (R, N + 1) int32, times[r, i]
+    the frame at which text token i begins, times[r, n] the closing frame.  probs: (R, N) fp32 token probabilities.  n_text: (R,)
+    int32 device tensor, used as n = clamp(n_text[r], 0, N).  word_rules: the WordRules of the vocabulary.  median_cap: an int
+    >= 0 in frames, or None for no cap (Whisper's 0.7 s is 70 at 10 ms frames).  Unit inner strides, free row strides.  Per row:
+    1. token i begins a word when i == 0 or its table entry has bit 0; word k covers the tokens [o_k, o_{k+1}), o_K = n;
+       s_k = times[o_k], e_k = times[o_{k+1}] (a word ends where the next one starts), p_k = the fp32 mean of its tokens'
+       probabilities; the word is prepend / append / sentence-end (P_k / A_k / E_k) when it has exactly one token and that token
+       has the bit;
+    2. d_k = e_k - s_k; m2 = twice numpy.median of the d_k != 0 (odd count: twice the middle value; even: the sum of the two
+       middle values; none: 0); max_dur = m2, or min(m2, 2 * median_cap); integers throughout;
+    3. for k >= 1 with d_k > max_dur: if E_k, e_k = s_k + max_dur; else if E_{k-1}, s_k = e_k - max_dur (original values on the
+       right-hand sides);
+    4. pass 1 (Whisper's right-to-left pass): a word with P_k and k < K - 1 dies; its tokens go in front of the nearest later
+       word that does not die in this pass;
+    5. pass 2 (left-to-right): a word k >= 1 that survived pass 1, has A_k and received nothing in pass 1 dies, unless every
+       earlier word died in pass 1; its tokens go to the back of the nearest earlier word that survives both passes;
+    6. the survivors, in order, keep their own s, e, p (Whisper merges text and tokens, not times or probabilities); their token
+       ranges [tok_begin, tok_end) include what they absorbed, are contiguous and partition [0, n).
+    Two deviations from Whisper: pass 2 does not test `not previous.word.endswith(" ")` (a property of the merged text, not of a
+    token id), and punctuation words of more than one token are not recognised.
+    Runs the HIP kernel (mopk_word_spans: one launch, one workgroup per row, ballot scans for the word and survivor numbering,
+    the per-word values in LDS, the median by ranking) when word_spans_supported() accepts the call, else word_spans_torch()
+    (N > 1024 among others); LAST_PATH["word_spans"] records which.  No host sync, no workspace; bitwise reproducible."""
+    _ws_check(tokens, times, probs, n_text, word_rules, median_cap, "word_spans")
+    with torch.no_grad():
+        a = _ws_accept(tokens, times, probs, n_text, word_rules, median_cap)
+        if a is None:
+            LAST_PATH["word_spans"] = L.PATH_GENERIC
+            return word_spans_torch(tokens, times, probs, n_text, word_rules, median_cap)
+        seg = torch.empty(4, a.R, a.N, dtype=torch.int32, device=tokens.device)
+        out_p = torch.empty(a.R, a.N, dtype=torch.float32, device=tokens.device)
+        n_words = torch.empty(a.R, dtype=torch.int32, device=tokens.device)
+        a.starts, a.ends, a.tok_begin, a.tok_end = (seg[k].data_ptr() for k in range(4))        # in place of the stand-ins
+        a.out_probs, a.n_words = out_p.data_ptr(), n_words.data_ptr()
+        _row_launch(a, "mopk_word_spans", "word_spans")
+        return WordSpans(seg[0], seg[1], out_p, seg[2], seg[3], n_words)
 
 
 # --------------------------------------------------------------------------------------
