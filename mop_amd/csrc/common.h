@@ -48,6 +48,36 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// Natural logarithm of an argument that is known to be a NORMAL positive float: x >= 2^-126, finite or +inf (NaN stays NaN).
+// __logf() guards v_log_f32 against subnormal arguments (compare, two selects, v_ldexp_f32: five instructions around the
+// logarithm) and ends in fma(log2 x, ln 2, 0 or -32 ln 2); with the guard never taken that is this product, bit for bit.
+// The product is made opaque, so -ffast-math cannot contract it into a consumer's add or re-associate it with a consumer's
+// multiply: callers get the value __logf() gave them.  Every call site states why its argument cannot be subnormal.
+__device__ __forceinline__ float log_pos(float x) {
+    float v = __builtin_amdgcn_logf(x) * 0.6931471805599453f;
+    asm("" : "+v"(v));
+    return v;
+}
+// max(a, b) as ONE v_max_f32.  fmaxf() quiets signalling NaNs first (a `v_max_f32 x, x, x` in front of every operand the
+// compiler cannot prove canonical: loop-carried values, matrix-core results); the hardware instruction returns the other
+// operand for a quiet NaN exactly like fmaxf(), so the results differ only for a SIGNALLING NaN operand, which no
+// arithmetic instruction produces.  The compiler pads no hazards of an asm statement: BOTH OPERANDS MUST COME FROM AN
+// ORDINARY VALU INSTRUCTION (or from another vmax) -- never straight from an MFMA or from v_exp / v_log / v_rcp -- and the
+// result must go to ordinary VALU code, not into an MFMA operand.
+__device__ __forceinline__ float vmax(float a, float b) {
+    asm("v_max_f32 %0, %0, %1" : "+v"(a) : "v"(b));
+    return a;
+}
+// max(m, x[0], .., x[15]) as eight v_max3_f32 in ONE statement (between two dependent asm statements the compiler pads a wait
+// state; inside one the hardware interlocks).  NaN handling and operand contract as vmax.
+__device__ __forceinline__ float vmax16(float m, const f32x16 &x) {
+    asm("v_max3_f32 %0, %0, %1, %2\n\tv_max3_f32 %0, %0, %3, %4\n\tv_max3_f32 %0, %0, %5, %6\n\tv_max3_f32 %0, %0, %7, %8\n\t"
+        "v_max3_f32 %0, %0, %9, %10\n\tv_max3_f32 %0, %0, %11, %12\n\tv_max3_f32 %0, %0, %13, %14\n\tv_max3_f32 %0, %0, %15, %16"
+        : "+v"(m)
+        : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]), "v"(x[8]), "v"(x[9]), "v"(x[10]),
+          "v"(x[11]), "v"(x[12]), "v"(x[13]), "v"(x[14]), "v"(x[15]));
+    return m;
+}
 // key / value length of a plain SDPA call: N queries attend to Nk keys (cross-attention); Nk = 0 means N (square)
 __host__ __device__ inline int sdpa_nk(const MopkSdpaArgs &a) { return a.Nk > 0 ? a.Nk : a.N; }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }

@@ -187,10 +187,11 @@ __global__ void __launch_bounds__(NT * 64, NT <= 3 ? 2 : 1) ew_fused_fwd_kernel(
 #pragma unroll
                 for (int g = 0; g < 16; ++g) S[g] = (32 * t + tile_row(g, h) >= N) ? NEG : S[g];     // select (no per-lane branch around a vector element write)
             }
-            float tm = NEG;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) tm = fmaxf(tm, S[g]);
-            const float mn = fmaxf(m, tm);
+            // tile maximum without a canonicalising move per element (vmax16, common.h).  Its operands may not come straight from the
+            // matrix core, so the tile's FIRST reader is the compiler's own fmaxf: that one is held back until the MFMA chain has
+            // written S, and the statement below depends on its result
+            const float tm = vmax16(fmaxf(NEG, S[0]), S);
+            const float mn = vmax(m, tm);
             float sm = 0.f;
 #pragma unroll
             for (int g = 0; g < 16; ++g) sm += __builtin_amdgcn_exp2f(S[g] - mn);
@@ -221,7 +222,7 @@ __global__ void __launch_bounds__(NT * 64, NT <= 3 ? 2 : 1) ew_fused_fwd_kernel(
         float c[16];
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-            const float v = __logf(X[g] + EPSC);
+            const float v = log_pos(X[g] + EPSC);     // X >= 0 (a sum of products of softmax weights): argument >= EPSC = 1e-6
             X[g] = v;
             rs += (32 * t + tile_row(g, h) < N) ? v : 0.f;
             c[g] = qok ? v : 0.f;
@@ -748,9 +749,9 @@ __global__ void __launch_bounds__(NT * 64, NT <= 3 ? 2 : 1) ew_fused_fwd_kernel(
             const bool tr1 = ctrim && t == NT - 1;              // trimmed chunk: the neighbour is re-read (its keys are padding, masked below)
             const bf16x8 cl = __builtin_bit_cast(bf16x8, cfp[(2 * t) * 64]), ch = __builtin_bit_cast(bf16x8, cfp[(2 * t + (tr1 ? 0 : 1)) * 64]);
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                cw[p] = pack_h2(__logf(bf2f((unsigned short)cl[2 * p]) + EPSC), __logf(bf2f((unsigned short)cl[2 * p + 1]) + EPSC));
-                cw[4 + p] = pack_h2(__logf(bf2f((unsigned short)ch[2 * p]) + EPSC), __logf(bf2f((unsigned short)ch[2 * p + 1]) + EPSC));
+            for (int p = 0; p < 4; ++p) {             // the export holds C-> >= 0 rounded to bf16: every argument >= EPSC
+                cw[p] = pack_h2(log_pos(bf2f((unsigned short)cl[2 * p]) + EPSC), log_pos(bf2f((unsigned short)cl[2 * p + 1]) + EPSC));
+                cw[4 + p] = pack_h2(log_pos(bf2f((unsigned short)ch[2 * p]) + EPSC), log_pos(bf2f((unsigned short)ch[2 * p + 1]) + EPSC));
             }
         } else {
         switch (t) {
@@ -778,11 +779,11 @@ __global__ void __launch_bounds__(NT * 64, NT <= 3 ? 2 : 1) ew_fused_fwd_kernel(
                     const float d = Sv[g] - S0[g];
                     const float e = __expf(-fabsf(d - mx[g]));
                     se[g] = d > mx[g] ? fmaf(se[g], e, 1.f) : se[g] + e;
-                    mx[g] = fmaxf(mx[g], d);
+                    mx[g] = vmax(mx[g], d);          // d comes from the subtraction above, mx from the previous round: vmax's contract holds
                 }
             }
 #pragma unroll
-            for (int g = 0; g < 16; ++g) L[g] = mx[g] + __logf(se[g]);   // lse_v S_v - S_0
+            for (int g = 0; g < 16; ++g) L[g] = mx[g] + log_pos(se[g]);  // lse_v S_v - S_0; se starts at 1 and only grows: argument >= 1
         }
         if (SAVE) {                       // L x log2(e) in fp32, accumulator order (the backward's S_L slab: [wave][4 t + q][lane] x 16 B)
             f32x4 *lp = (f32x4 *)(svb + SL.oL + (size_t)w * 2 * NT * 8 * 64 * 4) + lane;
@@ -800,7 +801,7 @@ __global__ void __launch_bounds__(NT * 64, NT <= 3 ? 2 : 1) ew_fused_fwd_kernel(
 #pragma unroll
             for (int p = 0; p < 8; ++p) {
                 Crv[2 * p] = h2_lo(cw[p]); Crv[2 * p + 1] = h2_hi(cw[p]);
-                Clv[p] = __logf(bf2f((unsigned short)cbl[p]) + EPSC); Clv[8 + p] = __logf(bf2f((unsigned short)cbh[p]) + EPSC);
+                Clv[p] = log_pos(bf2f((unsigned short)cbl[p]) + EPSC); Clv[8 + p] = log_pos(bf2f((unsigned short)cbh[p]) + EPSC);    // C<- >= 0 from the export: argument >= EPSC
             }
             // rolled over the four register quarters (unrolled, hipcc overlaps them and spills 700 registers); the quarter's registers
             // are picked with a wave-uniform index into the accumulator vectors (register-indexed moves)
@@ -921,6 +922,7 @@ __global__ void __launch_bounds__(NT * 64, NT <= 3 ? 2 : 1) ew_fused_fwd_kernel(
         {
             f32x16 G = G3d;
             if constexpr (HEAD == 0) G = gate_tile(t, 3);
+            f32x16 sv;
 #pragma unroll
             for (int p = 0; p < 8; ++p) {
                 float s0 = fmaf(G[2 * p], h2_lo(cw[p]), S0[2 * p]);
@@ -929,9 +931,10 @@ __global__ void __launch_bounds__(NT * 64, NT <= 3 ? 2 : 1) ew_fused_fwd_kernel(
                     s0 = (32 * t + tile_row(2 * p, h) >= N) ? -INFINITY : s0;
                     s1 = (32 * t + tile_row(2 * p + 1, h) >= N) ? -INFINITY : s1;
                 }
-                mxrow = fmaxf(mxrow, fmaxf(s0, s1));
+                sv[2 * p] = s0; sv[2 * p + 1] = s1;
                 cw[p] = pack_h2(s0, s1);
             }
+            mxrow = vmax16(mxrow, sv);              // every element comes from an fma or a select: vmax's contract holds
             if (SAVE) {                   // Smix as packed fp16 (the backward's S_SM slab)
                 typedef __attribute__((ext_vector_type(4))) unsigned int u4;
                 u4 *sp = (u4 *)(svb + SL.oSm + (size_t)w * NT * 8 * 64 * 4) + lane;

@@ -670,7 +670,7 @@ __global__ void __launch_bounds__(NT * 64, NT <= 3 ? 2 : 1) ew_fused_bwd_kernel(
             const u32x4 *pc = slot(S_CF);
             Cr = unpack_tile_bf(as_b8(pc[(2 * t) * 64]), as_b8(trim_val(2 * t + 1, pc[trim_idx(2 * t + 1) * 64])));
 #pragma unroll
-            for (int g = 0; g < 16; ++g) Cr[g] = __logf(Cr[g] + EPSC);
+            for (int g = 0; g < 16; ++g) Cr[g] = __logf(Cr[g] + EPSC);       // (log_pos() gives the same bits with 80 instructions fewer per tile, and launch A runs 0.03 ms SLOWER with it: DESIGN 5.2)
         }
         f32x16 dbt = zero16();
 #pragma unroll
@@ -1135,40 +1135,82 @@ __global__ void __launch_bounds__(NT * 64, NT <= 3 ? 2 : 1) ew_fused_bwd_kernel(
         __syncthreads();
         gemm_rows_glob(gL, R, DYT);                    // (C->^T dy)[j][d]
         __syncthreads();
-        const IOT *v0p = (const IOT *)a.v0.ptr + b * a.v0.sb + hh * a.v0.sh;
-        const IOT *vLp = (const IOT *)a.vL.ptr + b * a.vL.sb + hh * a.vL.sh;
-        IOT *d0p = (IOT *)a.dv0.ptr + b * a.dv0.sb + hh * a.dv0.sh;
-        IOT *dLp = (IOT *)a.dvL.ptr + b * a.dvL.sb + hh * a.dvL.sh;
-        const bool same = a.dv0.ptr == a.dvL.ptr;
+        // Epilogue on [key][d] rows.  The result tiles hold lanes <-> channel d, registers <-> keys: written out that way, every element of
+        // v0 / vL / dv0 / dvL is a 2-byte access with a 64-bit row address of its own (160 of them per lane).  Each wave turns its tiles
+        // through a private staging area in R (free: the barrier behind the second product has passed) into rows of DK floats, and a
+        // lane then owns 8-channel chunks of key rows: per chunk one 16-byte read of v0 and of vL and one 16-byte write of dv0 / dvL
+        // for bf16 I/O (two for fp32), from row pointers formed once per row.  The values written are the same bits as before; the
+        // per-channel sums for the value scales are accumulated in this layout (4 rows per lane, then a tree over the lanes of a chunk).
+        constexpr int LDT = DK + 4, CH = DK / 8, RPP = 64 / CH, NPASS = 32 / RPP;   // staging row stride (floats) | chunks per row | rows per pass | passes
+        static_assert(NT * 32 * LDT * 4 <= Cfg::R_BYTES, "P8: the staging rows live in R");
+        float *stg = (float *)R + w * 32 * LDT;
+        const int c8 = 8 * (lane % CH), kr = lane / CH;
+        auto rows_of = [&](float (&e)[NPASS][8], const f32x16 (&g)[DT]) {      // e[i] = channels c8 .. c8 + 7 of key row kr + RPP i of the wave's tile
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const int d = 32 * dt + r;                 // lanes <-> d, registers <-> keys of tile w
-            float s0 = 0.f, sL = 0.f;
-            if (d < DK) {
-                const float f0 = vs0[d], fL = vsL[d] * wv;
-                // the v0 / vL values of this lane's 16 keys are requested together from rows that exist (padded keys read row 0 and
-                // are masked): guarded, each pair of loads sat in its own exec-masked branch with a full wait (32 per lane)
-                float x0[16], xL[16];
+            for (int dt = 0; dt < DT; ++dt)
+                if (32 * dt + r < DK) {
 #pragma unroll
-                for (int g = 0; g < 16; ++g) {
-                    const int j = 32 * w + tile_row(g, h), jc = j < N ? j : 0;
-                    x0[g] = ld_as_f32(v0p + (int64_t)jc * a.v0.sn + d);
-                    xL[g] = ld_as_f32(vLp + (int64_t)jc * a.vL.sn + d);
+                    for (int gg = 0; gg < 16; ++gg) stg[tile_row(gg, h) * LDT + 32 * dt + r] = g[dt][gg];
                 }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
 #pragma unroll
-                for (int g = 0; g < 16; ++g) {
-                    const int j = 32 * w + tile_row(g, h);
-                    const float e0 = g0[dt][g], eL = gL[dt][g] * wv;
-                    s0 += keep_if(j < N, e0 * x0[g]);
-                    sL += keep_if(j < N, eL * xL[g]);
-                    if (j < N) {
-                        if (same) st_from_f32(d0p + (int64_t)j * a.dv0.sn + d, e0 * f0 + gL[dt][g] * fL);
-                        else { st_from_f32(d0p + (int64_t)j * a.dv0.sn + d, e0 * f0); st_from_f32(dLp + (int64_t)j * a.dvL.sn + d, gL[dt][g] * fL); }
-                    }
-                }
-                s0 += __shfl_xor(s0, 32, 64); sL += __shfl_xor(sL, 32, 64);
-                if (h == 0) { redbuf[w * DK + d] = s0; redbuf[(NT + w) * DK + d] = sL; }
+            for (int i = 0; i < NPASS; ++i) {
+                const float4 lo = *(const float4 *)&stg[(kr + RPP * i) * LDT + c8], hi = *(const float4 *)&stg[(kr + RPP * i) * LDT + c8 + 4];
+                e[i][0] = lo.x; e[i][1] = lo.y; e[i][2] = lo.z; e[i][3] = lo.w; e[i][4] = hi.x; e[i][5] = hi.y; e[i][6] = hi.z; e[i][7] = hi.w;
             }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        };
+        float e0[NPASS][8], eL[NPASS][8];
+        rows_of(e0, g0);
+        rows_of(eL, gL);
+        const bool same = a.dv0.ptr == a.dvL.ptr;
+        const int j0 = 32 * w + kr;                    // this lane's first key row; the others follow RPP rows apart
+        const IOT *v0p = (const IOT *)a.v0.ptr + b * a.v0.sb + hh * a.v0.sh + c8, *v0r = v0p + (int64_t)j0 * a.v0.sn;
+        const IOT *vLp = (const IOT *)a.vL.ptr + b * a.vL.sb + hh * a.vL.sh + c8, *vLr = vLp + (int64_t)j0 * a.vL.sn;
+        IOT *d0r = (IOT *)a.dv0.ptr + b * a.dv0.sb + hh * a.dv0.sh + c8 + (int64_t)j0 * a.dv0.sn;
+        IOT *dLr = (IOT *)a.dvL.ptr + b * a.dvL.sb + hh * a.dvL.sh + c8 + (int64_t)j0 * a.dvL.sn;
+        float f0[8], fL[8], s0[8], sL[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) { f0[c] = vs0[c8 + c]; fL[c] = vsL[c8 + c] * wv; s0[c] = 0.f; sL[c] = 0.f; }
+        // the v0 / vL chunks of all rows are requested together from rows that exist (a padded key reads row 0 and is masked)
+        float x0[NPASS][8], xL[NPASS][8];
+#pragma unroll
+        for (int i = 0; i < NPASS; ++i) {
+            const bool ok = j0 + RPP * i < N;
+            ld8_as_f32(x0[i], ok ? v0r + (int64_t)(RPP * i) * a.v0.sn : v0p);
+            ld8_as_f32(xL[i], ok ? vLr + (int64_t)(RPP * i) * a.vL.sn : vLp);
+        }
+#pragma unroll
+        for (int i = 0; i < NPASS; ++i) {
+            const bool ok = j0 + RPP * i < N;
+            float o0[8], oL[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const float m0 = e0[i][c] * f0[c];
+                s0[c] += keep_if(ok, e0[i][c] * x0[i][c]);
+                sL[c] += keep_if(ok, (eL[i][c] * wv) * xL[i][c]);
+                o0[c] = same ? __builtin_fmaf(eL[i][c], fL[c], m0) : m0;        // one tensor takes both value gradients (share_qkv)
+                oL[c] = eL[i][c] * fL[c];
+            }
+            if (ok) {
+                IOT *p0 = d0r + (int64_t)(RPP * i) * a.dv0.sn;
+                store4<IOT>(p0, o0[0], o0[1], o0[2], o0[3]); store4<IOT>(p0 + 4, o0[4], o0[5], o0[6], o0[7]);
+                if (!same) {
+                    IOT *pL = dLr + (int64_t)(RPP * i) * a.dvL.sn;
+                    store4<IOT>(pL, oL[0], oL[1], oL[2], oL[3]); store4<IOT>(pL + 4, oL[4], oL[5], oL[6], oL[7]);
+                }
+            }
+        }
+        // per-channel sums of the wave: over the lanes that hold the same chunk (lane % CH), a fixed tree
+#pragma unroll
+        for (int o = CH; o < 64; o <<= 1)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) { s0[c] += __shfl_xor(s0[c], o, 64); sL[c] += __shfl_xor(sL[c], o, 64); }
+        if (lane < CH) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) { redbuf[w * DK + c8 + c] = s0[c]; redbuf[(NT + w) * DK + c8 + c] = sL[c]; }
         }
         __syncthreads();
         if (tid < DK) {
