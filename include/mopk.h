@@ -1037,6 +1037,45 @@ typedef struct MopkGreedyPickArgs {
 int mopk_greedy_pick_supported(const MopkGreedyPickArgs *a);         /* 1 if the kernel takes this call (V, dtype, strides, alignment) */
 int mopk_greedy_pick(const MopkGreedyPickArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * Repetition penalty and no-repeat n-gram blocking on last-position logits (WhisperMoP decoding with repeat rules; inference
+ * only).  (Added under version 118: new exports only; callers detect it with mopk_repeat_rules_supported.)  The conventions are
+ * mopk_logit_rules': row r (0 <= r < R) reads x at logits + r * logits_ld elements and writes out + r * out_ld (F32 or BF16,
+ * element-aligned); g = hist[r * hist_ld + T0 ...] holds the n = clamp(*pos - T0, 0, T - T0) tokens generated so far (*pos in
+ * device memory: one set of launch arguments serves every decoding step).  Tokens before T0 (the prompt) never count.  In this
+ * order:
+ *   0. out[v] = x[v], bit for bit;
+ *   1. penalty != 1: every distinct v in g with 0 <= v < V and exempt[v] == 0 gets, in fp32, f = (float)x[v],
+ *      out[v] = f < 0 ? f * penalty : f * inv_penalty, rounded to the dtype (BF16: to nearest even).
+ *      -inf stays -inf and NaN stays NaN.  inv_penalty is the caller's fp32 1 / penalty: the product may differ from a true quotient by one ulp;
+ *   2. ngram = s >= 1 and n >= s - 1: for every i in [0, n - s] with g[i : i + s - 1] == g[n - s + 1 : n] (raw int32 values),
+ *      v = g[i + s - 1]; 0 <= v < V and exempt[v] == 0: out[v] = -inf, whether or not step 1 touched it.
+ * Every other entry of out is the input's bits; a row that the rules block completely comes out all -inf: no guard.
+ * One workgroup of 1024 threads per row, one launch; g is staged in LDS once (T - T0 <= 4096).  out == logits (the same rows):
+ * the kernel touches only the entries that it changes; every x[g[i]] is read before a barrier and written after it, so duplicate
+ * tokens write equal values, and the bans are written behind a second barrier.  Any other overlap is undefined.  Bitwise
+ * reproducible, no workspace, no host synchronisation. */
+typedef struct MopkRepeatRulesArgs {
+    int32_t R;                           /* rows */
+    int32_t V;                           /* vocabulary, >= 2 */
+    int32_t dtype;                       /* MopkDtype of logits and out: F32 or BF16 */
+    int32_t T;                           /* columns of hist (g is never read past them) */
+    int32_t T0;                          /* first generated column, 0 <= T0 <= T, T - T0 <= 4096 */
+    int32_t ngram;                       /* no_repeat_ngram_size, >= 0 (0: off) */
+    float penalty;                       /* repetition_penalty, finite and > 0 (1: off) */
+    float inv_penalty;                   /* the caller's fp32 1 / penalty */
+    const void *logits;
+    int64_t logits_ld;                   /* element stride between rows, >= V */
+    void *out;
+    int64_t out_ld;                      /* >= V */
+    const int32_t *hist;                 /* device (R rows of T) int32 */
+    int64_t hist_ld;                     /* element stride between hist rows, >= T */
+    const int32_t *pos;                  /* device: one int32 */
+    const uint8_t *exempt;               /* device (V): non-zero entries are never penalised or banned */
+} MopkRepeatRulesArgs;
+int mopk_repeat_rules_supported(const MopkRepeatRulesArgs *a);       /* 1 if the kernel takes this call (V, dtype, strides, T - T0) */
+int mopk_repeat_rules(const MopkRepeatRulesArgs *a, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

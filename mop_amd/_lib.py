@@ -237,6 +237,16 @@ class LogitRulesArgs(C.Structure):
     ]
 
 
+class RepeatRulesArgs(C.Structure):
+    """MopkRepeatRulesArgs: repetition penalty and no-repeat n-gram blocking on last-position logits (WhisperMoP's repeat_rules)."""
+    _fields_ = [
+        ("R", C.c_int32), ("V", C.c_int32), ("dtype", C.c_int32), ("T", C.c_int32), ("T0", C.c_int32), ("ngram", C.c_int32),
+        ("penalty", C.c_float), ("inv_penalty", C.c_float),
+        ("logits", _fp), ("logits_ld", C.c_int64), ("out", _fp), ("out_ld", C.c_int64), ("hist", _fp), ("hist_ld", C.c_int64),
+        ("pos", _fp), ("exempt", _fp),
+    ]
+
+
 class AlignCostArgs(C.Structure):
     """MopkAlignCostArgs: Whisper's alignment filter (z-normalise, median-filter, average the heads) on cross-attention maps."""
     _fields_ = [
@@ -409,6 +419,8 @@ SYMBOLS = {
     "mopk_decode_attn_lens_fwd": (C.c_int, [C.POINTER(DecodeAttnLensArgs), C.c_void_p]),
     "mopk_logit_rules_supported": (C.c_int, [C.POINTER(LogitRulesArgs)]),
     "mopk_logit_rules": (C.c_int, [C.POINTER(LogitRulesArgs), C.c_void_p]),
+    "mopk_repeat_rules_supported": (C.c_int, [C.POINTER(RepeatRulesArgs)]),
+    "mopk_repeat_rules": (C.c_int, [C.POINTER(RepeatRulesArgs), C.c_void_p]),
     "mopk_alignment_cost_supported": (C.c_int, [C.POINTER(AlignCostArgs)]),
     "mopk_alignment_cost": (C.c_int, [C.POINTER(AlignCostArgs), C.c_void_p]),
     "mopk_dtw_align_supported": (C.c_int, [C.POINTER(DtwArgs)]),

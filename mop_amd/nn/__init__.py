@@ -9,7 +9,7 @@ from .whisper_mop import (DecoderBlock, EncodedAudio, EncoderBlock, FuseExcInh2D
                           MultiheadCrossAttention, MultiheadSelfAttention, ViewsConv2D, WhisperConfig, WhisperDecodeCache, WhisperMoP,
                           create_whisper_baseline, create_whisper_mop, LogMelFrontend, RuledDecoding, TokenAlignment, Transcript,
                           DecodeStats, TranscribeLog, WordAlignment, TranscriptWords)
-from ..ops import LogitRules, WordRules  # noqa: F401  (the rule set of WhisperMoP.with_logit_rules, the word table of align_words)
+from ..ops import LogitRules, RepeatRules, WordRules  # noqa: F401  (the rule sets of WhisperMoP.with_logit_rules, the word table of align_words)
 from .vit_edgewise import BlockEdgewise, ViTEdgewise  # noqa: F401
 # GPT line (mop/models/gpt_mop.py).  The Quartet MLP / Block / TinyTransformerLM live in .quartet_attn_patch; MLP and Block here stay
 # the ViT ones, as in the reference's mop.models.

@@ -674,6 +674,28 @@ class WhisperMoP(nn.Module):
         if rules.eos_token_id is not None and eos_token_id is not None and int(eos_token_id) != rules.eos_token_id:
             raise ValueError(f"{what}: eos_token_id = {eos_token_id}, the logit rules' eos_token_id = {rules.eos_token_id}")
 
+    def _repeat_check(self, rules, what: str):
+        """the argument checks of a decoding with repeat rules -> the rules, or None for None and for neutral rules (which then
+        cost no launch and no buffer); ValueErrors before any device work"""
+        if rules is None:
+            return None
+        if not isinstance(rules, ops.RepeatRules):
+            raise ValueError(f"{what}: repeat rules must be an ops.RepeatRules, got {type(rules).__name__}")
+        if rules.vocab_size != self.cfg.vocab_size:
+            raise ValueError(f"{what}: the repeat rules were built for vocab_size = {rules.vocab_size}, the model has "
+                             f"{self.cfg.vocab_size}")
+        return None if rules.neutral else rules
+
+    @staticmethod
+    def _filter(lg, hist, pos, t0: int, logit_rules, repeat_rules):
+        """a step's last-position logits through the rules, in place: ops.repeat_rules first, then ops.logit_rules, so the
+        timestamp grammar's rule 3e and every log-probability see the penalised row; hist: the rows' int32 token histories"""
+        if repeat_rules is not None:
+            lg = ops.repeat_rules(lg, hist, pos, t0, repeat_rules, out=lg)
+        if logit_rules is not None:
+            lg = ops.logit_rules(lg, hist, pos, t0, logit_rules, out=lg)
+        return lg
+
     def _stats_check(self, return_stats: bool, no_speech_token_id, sot_index, lens: Optional[List[int]], T_p: int, what: str,
                      eos_token_id=None):
         """the argument checks of a decoding with return_stats -> None when no statistics are asked for, else (no_speech_token_id
@@ -727,11 +749,15 @@ class WhisperMoP(nn.Module):
         j = torch.arange(n, device=tokens.device).unsqueeze(0)
         return (torch.where(gen == eos_token_id, j, n - 1).min(1).values + 1).to(torch.int32)
 
-    def with_logit_rules(self, logit_rules: Optional["ops.LogitRules"]) -> "RuledDecoding":
+    def with_logit_rules(self, logit_rules: Optional["ops.LogitRules"],
+                         repeat_rules: Optional["ops.RepeatRules"] = None) -> "RuledDecoding":
         """this model's decoders under Whisper's logit rules: with_logit_rules(rules).generate / .beam_search / .sample take the
         arguments of generate / beam_search / sample and apply ops.logit_rules(rules) to every step's last-position logits, on the
-        device and inside the captured step, before the argmax / beam step / draw.  None: the plain decoders."""
-        return RuledDecoding(self, logit_rules)
+        device and inside the captured step, before the argmax / beam step / draw.  None: the plain decoders.
+        repeat_rules: an ops.RepeatRules (a repetition penalty and / or no-repeat n-gram blocking over the generated tokens),
+        applied by ops.repeat_rules to the same logits BEFORE the logit rules; it works with logit_rules None too.  None or
+        neutral rules add no launch and no buffer."""
+        return RuledDecoding(self, logit_rules, repeat_rules)
 
     def _replicated_cache(self, mel, mel_info, prompt_ids, lens: Optional[List[int]], cap: int, rep: int):
         """encode, run the prompt once per item and set up the cache of rep rows per item (beams / samples) for the steps after it
@@ -799,12 +825,14 @@ class WhisperMoP(nn.Module):
         return self._generate(mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, None)
 
     def _generate(self, mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, logit_rules, return_stats=False,
-                  no_speech_token_id=None, sot_index=0):
+                  no_speech_token_id=None, sot_index=0, repeat_rules=None):
         """generate's body.  logit_rules: every step's last-position logits pass ops.logit_rules before the argmax, inside the
         captured step, over a (B, cap) int32 device history kept for them only; None runs exactly the code without them.
-        return_stats: the statistics route (_generate_stats) from the prompt's logits on; False runs exactly the code without it"""
+        repeat_rules: the logits pass ops.repeat_rules before that, over the same history (kept for them alone when logit_rules
+        is None).  return_stats: the statistics route (_generate_stats) from the prompt's logits on; False runs exactly the code without it"""
         mel_info, lens, B, T_p, _ = self._decode_check(mel, prompt_ids, max_new_tokens, "generate")
         self._rules_check(logit_rules, eos_token_id, "generate")
+        repeat_rules = self._repeat_check(repeat_rules, "generate")
         stats = self._stats_check(return_stats, no_speech_token_id, sot_index, lens, T_p, "generate", eos_token_id)
         stats, lens = self._prepared(prompt_ids, stats, lens, T_p)
         prompt_ids, kv_start = self._ragged_pad(prompt_ids, lens, mel_info.device)
@@ -815,13 +843,13 @@ class WhisperMoP(nn.Module):
         logits = prompt_logits[:, -1]
         if stats is not None:
             return self._generate_stats(cache, prompt_ids, prompt_logits, lens, max_new_tokens, eos_token_id, graph, return_logits,
-                                        logit_rules, stats)
+                                        logit_rules, stats, repeat_rules)
         del prompt_logits
         hist = None
-        if logit_rules is not None:
+        if logit_rules is not None or repeat_rules is not None:
             hist = torch.zeros(B, T_p + max_new_tokens, dtype=torch.int32, device=prompt_ids.device)
             hist[:, :T_p] = prompt_ids
-            logits = ops.logit_rules(logits, hist, cache.length, T_p, logit_rules, out=logits)
+            logits = self._filter(logits, hist, cache.length, T_p, logit_rules, repeat_rules)
         done = torch.zeros(B, dtype=torch.bool, device=prompt_ids.device) if eos_token_id is not None else None
         toks, steps = [], []
         ids = None
@@ -852,7 +880,7 @@ class WhisperMoP(nn.Module):
             nonlocal logits
             logits = self.decode_step(cache, ids)[:, -1]
             if hist is not None:
-                logits = ops.logit_rules(logits, hist, cache.length, T_p, logit_rules, out=logits)
+                logits = self._filter(logits, hist, cache.length, T_p, logit_rules, repeat_rules)
 
         self._step_loop(cache, step, max_new_tokens - 1, graph, feed)
         pick()
@@ -862,7 +890,7 @@ class WhisperMoP(nn.Module):
         return (out, torch.stack(steps, dim=1)) if return_logits else out
 
     def _generate_stats(self, cache, prompt_ids, prompt_logits, lens, max_new_tokens, eos_token_id, graph, return_logits,
-                        logit_rules, stats):
+                        logit_rules, stats, repeat_rules=None):
         """generate's statistics route, from the prompt pass's logits on: ops.greedy_pick chooses every token on an
         ops.GreedyState whose hist is the logit rules' history and, in the end, the tokens; a step is the decoder step, the
         rules and the pick, all captured with graph=True"""
@@ -876,8 +904,7 @@ class WhisperMoP(nn.Module):
             steps = torch.empty(B, max_new_tokens, prompt_logits.shape[-1], dtype=prompt_logits.dtype, device=dev)
 
         def pick(lg):
-            if logit_rules is not None:
-                lg = ops.logit_rules(lg, st.hist, cache.length, T_p, logit_rules, out=lg)
+            lg = self._filter(lg, st.hist, cache.length, T_p, logit_rules, repeat_rules)
             if steps is not None:                    # at the device index of the token being chosen: the same launch every step
                 steps.index_copy_(1, cache.length.to(torch.long) - T_p, lg.unsqueeze(1))
             ops.greedy_pick(lg, st, cache.length)
@@ -919,12 +946,13 @@ class WhisperMoP(nn.Module):
         return self._beam_search(mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph, None)
 
     def _beam_search(self, mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph, logit_rules,
-                     return_stats=False, no_speech_token_id=None, sot_index=0):
+                     return_stats=False, no_speech_token_id=None, sot_index=0, repeat_rules=None):
         """beam_search's body.  logit_rules: every step's logits pass ops.logit_rules before ops.beam_step, inside the captured
         step, with the beams' own histories (the first step's shared prompt logits with the rows [::K] of them); None runs exactly
-        the code without them"""
+        the code without them.  repeat_rules: ops.repeat_rules before that, on the same histories"""
         mel_info, lens, B, T_p, K = self._decode_check(mel, prompt_ids, max_new_tokens, "beam_search", ("num_beams", num_beams), 2)
         self._rules_check(logit_rules, eos_token_id, "beam_search")
+        repeat_rules = self._repeat_check(repeat_rules, "beam_search")
         stats = self._stats_check(return_stats, no_speech_token_id, sot_index, lens, T_p, "beam_search", eos_token_id)
         stats, lens = self._prepared(prompt_ids, stats, lens, T_p)
         cap = T_p + max_new_tokens
@@ -933,14 +961,12 @@ class WhisperMoP(nn.Module):
         logits = prompt_logits[:, -1]
         del prompt_logits
         st = ops.BeamState(prompt_ids, K, cap, eos_token_id, length_penalty)
-        if logit_rules is not None:
-            logits = ops.logit_rules(logits, st.hist[::K], cache.length, T_p, logit_rules, out=logits)
+        logits = self._filter(logits, st.hist[::K], cache.length, T_p, logit_rules, repeat_rules)
         ops.beam_step(logits, st, cache.length)
 
         def step():
             lg = self._decode_tokens(cache, st.next_ids, rows=st.rows, beams=K)[:, -1]
-            if logit_rules is not None:
-                lg = ops.logit_rules(lg, st.hist, cache.length, T_p, logit_rules, out=lg)
+            lg = self._filter(lg, st.hist, cache.length, T_p, logit_rules, repeat_rules)
             ops.beam_step(lg, st, cache.length)
 
         self._step_loop(cache, step, max_new_tokens - 1, graph)
@@ -978,13 +1004,15 @@ class WhisperMoP(nn.Module):
         return self._sample(mel, prompt_ids, max_new_tokens, temperature, top_k, top_p, num_samples, eos_token_id, seed, graph, None)
 
     def _sample(self, mel, prompt_ids, max_new_tokens, temperature, top_k, top_p, num_samples, eos_token_id, seed, graph,
-                logit_rules, return_stats=False, no_speech_token_id=None, sot_index=0):
+                logit_rules, return_stats=False, no_speech_token_id=None, sot_index=0, repeat_rules=None):
         """sample's body.  logit_rules: every step's logits pass ops.logit_rules before the draw, inside the captured step, with
         the samples' own token rows as history (the first draw's shared prompt logits with the rows [::num_samples] of them); the
-        log-probabilities are those of the filtered row.  None runs exactly the code without them"""
+        log-probabilities are those of the filtered row.  None runs exactly the code without them.  repeat_rules:
+        ops.repeat_rules before that, on the same rows"""
         mel_info, lens, B, T_p, n = self._decode_check(mel, prompt_ids, max_new_tokens, "sample", ("num_samples", num_samples))
         ops._sample_params(temperature, top_k, top_p, "sample")                 # argument errors before encoding
         self._rules_check(logit_rules, eos_token_id, "sample")
+        repeat_rules = self._repeat_check(repeat_rules, "sample")
         stats = self._stats_check(return_stats, no_speech_token_id, sot_index, lens, T_p, "sample", eos_token_id)
         stats, lens = self._prepared(prompt_ids, stats, lens, T_p)
         cap = T_p + max_new_tokens
@@ -1007,8 +1035,7 @@ class WhisperMoP(nn.Module):
         n_tok = torch.zeros(B * n, **i32) if stats is not None and eos is not None else None
 
         def draw(lg):
-            if logit_rules is not None:
-                lg = ops.logit_rules(lg, tokens if lg.shape[0] == B * n else tokens[::n], cache.length, T_p, logit_rules, out=lg)
+            lg = self._filter(lg, tokens if lg.shape[0] == B * n else tokens[::n], cache.length, T_p, logit_rules, repeat_rules)
             if cache.kv_start is None:
                 ops.sample_tokens(lg, cache.length, temperature, top_k, top_p, seed, out=(tok, lp))
             else:
@@ -1427,9 +1454,9 @@ class WhisperMoP(nn.Module):
                     no_speech_threshold: Optional[float] = None, no_speech_token_id: Optional[int] = None, sot_index: int = 0,
                     compression_ratio_threshold: Optional[float] = None, compression_ratio=None, num_samples: int = 1,
                     seed: int = 0, return_log: bool = False, word_timestamps: bool = False, word_rules=None, alignment_heads=None,
-                    medfilt_width: int = 7, median_word_frames: Optional[int] = None, condition_on_previous_text: bool = False,
-                    initial_prompt=None, sot_prev_token_id: Optional[int] = None, max_prompt_tokens: Optional[int] = None,
-                    prompt_reset_temperature: float = 0.5):
+                    medfilt_width: int = 7, median_word_frames: Optional[int] = None, repeat_rules=None,
+                    condition_on_previous_text: bool = False, initial_prompt=None, sot_prev_token_id: Optional[int] = None,
+                    max_prompt_tokens: Optional[int] = None, prompt_reset_temperature: float = 0.5):
         """long-form transcription, Whisper's transcribe loop over windows for a batch of clips -> a list of B Transcript(starts,
         ends, tokens, offsets), all on the device.
 
@@ -1518,6 +1545,13 @@ class WhisperMoP(nn.Module):
         timestamps.
         ValueError before any device work: word_rules missing or of another vocabulary; no_timestamps_token_id unset; T_p +
         max_new_tokens + 2 > n_text_ctx; malformed heads, width or median_word_frames.
+
+        Repetition (repeat_rules; on RuledDecoding.transcribe they come from with_logit_rules(logit_rules, repeat_rules)): an
+        ops.RepeatRules of the model's vocabulary.  Every decoder call of every window and of every fallback temperature applies
+        them before the logit rules, over the window's generated tokens only (never the prompt, so never the previous window's
+        text).  Build them with ops.RepeatRules.for_whisper(logit_rules, ...): it exempts eos and the timestamp tokens, which the
+        segments need to repeat (one segment's end and the next one's start are the same token).  The alignment pass of the word
+        timestamps decodes nothing and is not affected.
         Out of scope: Whisper's pause and segment-boundary heuristics on the words (last_speech_timestamp, preferring the
         segment-level start / end), hallucination_silence_threshold, word splitting on unicode code points, an alignment pass
         fused so that it never materialises the probability maps, top-k / top-p inside transcribe, handing the encoded audio over
@@ -1534,7 +1568,7 @@ class WhisperMoP(nn.Module):
         plain = (pol.temperatures == (0.0,) and logprob_threshold is None and no_speech_threshold is None
                  and no_speech_token_id is None and compression_ratio is None and not return_log)
         calls = [0]
-        dev, B, dec = clips[0].device, len(clips), self.with_logit_rules(logit_rules)
+        dev, B, dec = clips[0].device, len(clips), self.with_logit_rules(logit_rules, repeat_rules)
         build = None
         if cond is not None:
             hist, hist_len, len_b = self._history_init(cond, B, dev)
@@ -1784,11 +1818,18 @@ class RuledDecoding:
     method here takes the arguments of the method it names, and what came later as keywords of its own: the decoding statistics
     (return_stats, no_speech_token_id, sot_index) and, on transcribe, the temperature fallback, the no-speech skip, the
     conditioning on the previous text and the word timestamps.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
-    (ValueError).  logit_rules None runs the plain decoder: no extra launch, no extra buffer."""
+    (ValueError).  logit_rules None runs the plain decoder: no extra launch, no extra buffer.
+    repeat_rules (ops.RepeatRules; for Whisper build them with ops.RepeatRules.for_whisper(logit_rules, ...), which exempts eos
+    and the timestamps): a repetition penalty and / or no-repeat n-gram blocking over each row's generated tokens, by
+    ops.repeat_rules, one more HIP launch inside the step and BEFORE the logit rules, so everything said above about the filtered
+    row (the timestamp grammar's rule 3e, return_logits, the log-probabilities) holds for the row after both filters, while
+    no_speech_prob is still read before any filter.  transcribe applies them to every window and every fallback temperature.
+    None or neutral rules: no extra launch, no extra buffer."""
 
-    def __init__(self, model: WhisperMoP, logit_rules: Optional["ops.LogitRules"]):
-        self.model, self.logit_rules = model, logit_rules
+    def __init__(self, model: WhisperMoP, logit_rules: Optional["ops.LogitRules"], repeat_rules: Optional["ops.RepeatRules"] = None):
+        self.model, self.logit_rules, self.repeat_rules = model, logit_rules, repeat_rules
         model._rules_check(logit_rules, None, "with_logit_rules")
+        model._repeat_check(repeat_rules, "with_logit_rules")
 
     @torch.no_grad()
     def generate(self, mel, prompt_ids, max_new_tokens: int, eos_token_id: Optional[int] = None, graph: bool = False, *,
@@ -1798,7 +1839,7 @@ class RuledDecoding:
         it; return_logits returns the FILTERED logits, the ones that chose the token; return_stats adds up the log-softmax of the
         FILTERED rows (Whisper's convention), while no_speech_prob is read before the filter"""
         return self.model._generate(mel, prompt_ids, max_new_tokens, eos_token_id, graph, return_logits, self.logit_rules,
-                                    return_stats, no_speech_token_id, sot_index)
+                                    return_stats, no_speech_token_id, sot_index, self.repeat_rules)
 
     @torch.no_grad()
     def beam_search(self, mel, prompt_ids, max_new_tokens: int, num_beams: int, eos_token_id: Optional[int] = None,
@@ -1807,7 +1848,7 @@ class RuledDecoding:
         """WhisperMoP.beam_search under the rules: the filter runs before ops.beam_step, on the beams' own histories, so the
         candidates' log-probabilities are those of the filtered rows (no_speech_prob is read before the filter)"""
         return self.model._beam_search(mel, prompt_ids, max_new_tokens, num_beams, eos_token_id, length_penalty, graph,
-                                       self.logit_rules, return_stats, no_speech_token_id, sot_index)
+                                       self.logit_rules, return_stats, no_speech_token_id, sot_index, self.repeat_rules)
 
     @torch.no_grad()
     def sample(self, mel, prompt_ids, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
@@ -1816,7 +1857,7 @@ class RuledDecoding:
         """WhisperMoP.sample under the rules: the filter runs before the draw; sum_logprobs adds the log-softmax of the FILTERED
         row (Whisper's convention: its filters precede the log-probabilities; no_speech_prob is read before the filter)"""
         return self.model._sample(mel, prompt_ids, max_new_tokens, temperature, top_k, top_p, num_samples, eos_token_id, seed,
-                                  graph, self.logit_rules, return_stats, no_speech_token_id, sot_index)
+                                  graph, self.logit_rules, return_stats, no_speech_token_id, sot_index, self.repeat_rules)
 
     @torch.no_grad()
     def transcribe(self, mel, prompt_ids: torch.Tensor, max_new_tokens: int, *, window: Optional[int] = None,
@@ -1836,7 +1877,8 @@ class RuledDecoding:
             num_samples=num_samples, seed=seed, return_log=return_log, condition_on_previous_text=condition_on_previous_text,
             initial_prompt=initial_prompt, sot_prev_token_id=sot_prev_token_id, max_prompt_tokens=max_prompt_tokens,
             prompt_reset_temperature=prompt_reset_temperature, word_timestamps=word_timestamps, word_rules=word_rules,
-            alignment_heads=alignment_heads, medfilt_width=medfilt_width, median_word_frames=median_word_frames)
+            alignment_heads=alignment_heads, medfilt_width=medfilt_width, median_word_frames=median_word_frames,
+            repeat_rules=self.repeat_rules)
 
 
 RuledDecoding.transcribe.__doc__ = WhisperMoP._transcribe.__doc__

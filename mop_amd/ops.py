@@ -1961,7 +1961,7 @@ def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     return _da_run("decode_attention_lens", q, k_cache, v_cache, kv_lens=kv_lens, nk=nk)
 
 
-# ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, token_logprob, greedy_pick,
+# ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, repeat_rules, token_logprob, greedy_pick,
 # alignment_cost, dtw_align, timestamp_segments, prompt_history_update, window_prompts, alignment_rows, word_spans ----
 # Each is its _*_check (every ValueError, once per call), its _*_accept (the tensor-side tests, then the args struct, built once,
 # if the library's _supported query takes it, else None), then the torch restatement, or the outputs into that struct and _row_launch.
@@ -2466,10 +2466,11 @@ class LogitRules:
         return t
 
 
-def _lr_check(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: LogitRules, out, what: str) -> None:
-    """validate a logit-rules call before any device work"""
-    if not isinstance(rules, LogitRules):
-        raise ValueError(f"{what}: rules must be a LogitRules, got {type(rules).__name__}")
+def _lr_check(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules, out, what: str, kind=None) -> None:
+    """validate a logit-rules call (or, with kind = RepeatRules, a repeat-rules call: the same arguments) before any device work"""
+    kind = LogitRules if kind is None else kind
+    if not isinstance(rules, kind):
+        raise ValueError(f"{what}: rules must be a {kind.__name__}, got {type(rules).__name__}")
     if logits.dim() != 2 or logits.shape[0] < 1 or not logits.dtype.is_floating_point:
         raise ValueError(f"{what}: logits must be a floating (rows, V) tensor, got {tuple(logits.shape)} {logits.dtype}")
     if logits.shape[1] != rules.vocab_size:
@@ -2542,17 +2543,22 @@ def _lr_args(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: in
     return a
 
 
-def _lr_accept(logits, hist, pos, t0, rules, out):
-    """the args struct of a call that mopk_logit_rules takes, None of one it refuses; out None: `logits` stands in for the result"""
-    o = logits if out is None else out
+def _lr_tensors_ok(logits, o, hist, pos) -> bool:
+    """the tensor-side tests that logit_rules and repeat_rules share: CUDA fp32 / bf16 rows, a CUDA int32 history and position"""
     R, V = logits.shape
     for t in (logits, o):
         if not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16) or t.stride(1) != 1 or (R > 1 and t.stride(0) < V):
-            return None
+            return False
     T = hist.shape[1]
     if not hist.is_cuda or hist.dtype != torch.int32 or (T > 1 and hist.stride(1) != 1) or (R > 1 and hist.stride(0) < T):
-        return None
-    if not pos.is_cuda or pos.dtype != torch.int32:
+        return False
+    return pos.is_cuda and pos.dtype == torch.int32
+
+
+def _lr_accept(logits, hist, pos, t0, rules, out):
+    """the args struct of a call that mopk_logit_rules takes, None of one it refuses; out None: `logits` stands in for the result"""
+    o = logits if out is None else out
+    if not _lr_tensors_ok(logits, o, hist, pos):
         return None
     a = _lr_args(logits, hist, pos, t0, rules, o)
     return a if L.lib().mopk_logit_rules_supported(C.byref(a)) else None
@@ -2597,6 +2603,186 @@ def logit_rules(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0:
             out = torch.empty_like(logits, memory_format=torch.contiguous_format)
             a.out, a.out_ld = out.data_ptr(), out.stride(0)                        # in place of the stand-in
         _row_launch(a, "mopk_logit_rules", "logit_rules")
+        return out
+
+
+# ---- repetition penalty and no-repeat n-gram blocking on last-position logits (mopk_repeat_rules*; WhisperMoP decoding) ----
+REPEAT_MAX_GENERATED = 4096                                                        # T - t0 the kernel stages in LDS
+
+
+class RepeatRules:
+    """The two per-step controls against repetition loops for a vocabulary of `vocab_size` tokens: `repetition_penalty` (HF's
+    RepetitionPenaltyLogitsProcessor; 1.0 is off) and `no_repeat_ngram_size` (HF's NoRepeatNGramLogitsProcessor; 0 is off), both
+    over the GENERATED tokens only.  `repeat_rules` documents them.
+
+    exempt_tokens: ids that are never penalised or banned; exempt_from: every id >= it is exempt too (None: none).  The
+    constructor validates everything (ValueError) before any device work, builds the (V,) uint8 exemption table once (1: exempt)
+    and stores inv_penalty, the fp32 value of 1 / repetition_penalty, computed once on the host; table(device) returns the
+    table's copy on a device, made once per device (pass `device` to make it at construction).  neutral: penalty 1.0 and
+    n-gram size 0, rules that change nothing."""
+
+    def __init__(self, vocab_size: int, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, exempt_tokens=(),
+                 exempt_from: Optional[int] = None, device=None):
+        def _int(x, name):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or int(x) != x:
+                raise ValueError(f"RepeatRules: {name} must be an integer, got {x!r}")
+            return int(x)
+
+        V = _int(vocab_size, "vocab_size")
+        if V < 2:
+            raise ValueError(f"RepeatRules: vocab_size must be >= 2, got {V}")
+        p = repetition_penalty
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p) or not p > 0:
+            raise ValueError(f"RepeatRules: repetition_penalty must be a finite number > 0, got {p!r}")
+        p32 = torch.tensor(float(p), dtype=torch.float32)
+        inv = 1.0 / p32                                                            # fp32, once, on the host
+        if not (math.isfinite(p32.item()) and p32.item() > 0 and math.isfinite(inv.item()) and inv.item() > 0):
+            raise ValueError(f"RepeatRules: repetition_penalty = {p!r} or its reciprocal is not a positive finite fp32 number")
+        s = _int(no_repeat_ngram_size, "no_repeat_ngram_size")
+        if s < 0:
+            raise ValueError(f"RepeatRules: no_repeat_ngram_size must be >= 0, got {s}")
+        ids = []
+        for t in exempt_tokens:
+            t = _int(t, "exempt_tokens id")
+            if not 0 <= t < V:
+                raise ValueError(f"RepeatRules: exempt_tokens id = {t} outside [0, vocab_size = {V})")
+            ids.append(t)
+        if exempt_from is not None:
+            exempt_from = _int(exempt_from, "exempt_from")
+            if not 0 <= exempt_from <= V:
+                raise ValueError(f"RepeatRules: exempt_from = {exempt_from} outside [0, vocab_size = {V}]")
+        self.vocab_size, self.no_repeat_ngram_size = V, s
+        self.repetition_penalty, self.inv_penalty = p32.item(), inv.item()         # both as their fp32 values
+        self.exempt_tokens, self.exempt_from = tuple(ids), exempt_from
+        self.neutral = self.repetition_penalty == 1.0 and s == 0
+        table = torch.zeros(V, dtype=torch.uint8)
+        if ids:
+            table[torch.tensor(ids, dtype=torch.long)] = 1
+        if exempt_from is not None:
+            table[exempt_from:] = 1
+        self._tables = {torch.device("cpu"): table}
+        if device is not None:
+            self.table(device)
+
+    table = LogitRules.table
+
+    @classmethod
+    def for_whisper(cls, logit_rules: LogitRules, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                    extra_exempt=()) -> "RepeatRules":
+        """the repeat rules that go with a Whisper `logit_rules`: logit_rules.eos_token_id (when set) and every timestamp token,
+        the ids >= logit_rules.timestamp_begin (when set), are exempt, and so are the ids of extra_exempt.  The timestamps must
+        be: a segment's closing <|t|> and the next segment's opening <|t|> are legitimately the same token twice, and
+        ops.timestamp_segments cuts the segments at exactly such pairs; a penalty or a ban on them would break the grammar that
+        transcribe relies on.  Use this constructor for with_logit_rules(...).transcribe."""
+        if not isinstance(logit_rules, LogitRules):
+            raise ValueError(f"RepeatRules.for_whisper: logit_rules must be a LogitRules, got {type(logit_rules).__name__}")
+        exempt = list(extra_exempt)
+        if logit_rules.eos_token_id is not None:
+            exempt.append(logit_rules.eos_token_id)
+        return cls(logit_rules.vocab_size, repetition_penalty, no_repeat_ngram_size, exempt, logit_rules.timestamp_begin)
+
+
+def _rr_check(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: RepeatRules, out, what: str) -> None:
+    """validate a repeat-rules call before any device work: logit_rules' arguments with a RepeatRules"""
+    _lr_check(logits, hist, pos, t0, rules, out, what, RepeatRules)
+
+
+def repeat_rules_torch(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: RepeatRules, out=None):
+    """the restatement of `repeat_rules` in torch ops (CPU or GPU, vectorised over rows, no host sync): the same steps in the
+    same order, the penalty in fp32 with the same two constants, so it agrees with the kernel bit for bit"""
+    _rr_check(logits, hist, pos, t0, rules, out, "repeat_rules_torch")
+    R, V = logits.shape
+    dev, T, t0 = logits.device, hist.shape[1], int(t0)
+    s, G = rules.no_repeat_ngram_size, T - t0
+    y = logits
+    if G > 0 and not rules.neutral:
+        n = (pos.reshape(()).to(torch.long) - t0).clamp(0, G)
+        g = hist[:, t0:].to(torch.long)                                            # (R, G), raw values
+        j = torch.arange(G, device=dev)
+        gc = g.clamp(0, V - 1)
+        ok = (j < n) & (g >= 0) & (g < V) & (rules.table(dev)[gc] == 0)            # positions whose token can be changed
+        if rules.repetition_penalty != 1.0:
+            seen = torch.zeros(R, V, dtype=torch.int32, device=dev).scatter_add_(1, gc, ok.to(torch.int32)) > 0
+            x = logits.float()
+            pen = torch.where(x < 0, x * rules.repetition_penalty, x * rules.inv_penalty).to(logits.dtype)
+            y = torch.where(seen, pen, y)
+        W = G - s + 1                                                              # n-gram windows that fit
+        if s >= 1 and W >= 1:
+            same = (torch.arange(W, device=dev) <= n - s).unsqueeze(0).expand(R, W)
+            for k in range(s - 1):                                                 # window i against ctx = g[n - s + 1 : n]
+                ctx = g.index_select(1, (n - s + 1 + k).clamp(0, G - 1).reshape(1))
+                same = same & (g[:, k:k + W] == ctx)
+            hit = (same & ok[:, s - 1:]).to(torch.int32)
+            ban = torch.zeros(R, V, dtype=torch.int32, device=dev).scatter_add_(1, gc[:, s - 1:], hit) > 0
+            y = y.masked_fill(ban, float("-inf"))
+    if out is None:
+        return y.clone() if y is logits else y
+    if out is not y:
+        out.copy_(y)
+    return out
+
+
+def _rr_args(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: RepeatRules, out) -> L.RepeatRulesArgs:
+    a = L.RepeatRulesArgs()
+    a.R, a.V, a.T, a.T0 = logits.shape[0], logits.shape[1], hist.shape[1], int(t0)
+    a.dtype = L.MOPK_BF16 if logits.dtype == torch.bfloat16 else L.MOPK_F32
+    a.ngram, a.penalty, a.inv_penalty = rules.no_repeat_ngram_size, rules.repetition_penalty, rules.inv_penalty
+    a.logits, a.logits_ld, a.out, a.out_ld = logits.data_ptr(), logits.stride(0), out.data_ptr(), out.stride(0)
+    a.hist, a.hist_ld, a.pos, a.exempt = hist.data_ptr(), hist.stride(0), pos.data_ptr(), rules.table(logits.device).data_ptr()
+    if a.R == 1:                                                                   # a single row: its strides are never used
+        a.logits_ld = a.out_ld = a.V
+        a.hist_ld = a.T
+    return a
+
+
+def _rr_accept(logits, hist, pos, t0, rules, out):
+    """the args struct of a call that mopk_repeat_rules takes, None of one it refuses; out None: `logits` stands in for the result"""
+    if not _lr_tensors_ok(logits, logits if out is None else out, hist, pos):
+        return None
+    a = _rr_args(logits, hist, pos, t0, rules, logits if out is None else out)
+    return a if L.lib().mopk_repeat_rules_supported(C.byref(a)) else None
+
+
+def repeat_rules_supported(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: RepeatRules, out=None) -> bool:
+    """True if mopk_repeat_rules takes this call: the tensors that logit_rules_supported asks for, and T - t0 <= 4096 generated
+    columns (the library's own query decides that and the rest).  Raises ValueError on bad arguments."""
+    _rr_check(logits, hist, pos, t0, rules, out, "repeat_rules_supported")
+    return _rr_accept(logits, hist, pos, t0, rules, out) is not None
+
+
+def repeat_rules(logits: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor, t0: int, rules: RepeatRules, out=None):
+    """apply a repetition penalty and no-repeat n-gram blocking to last-position logits -> the logits, (R, V) in their dtype.
+    Inference only.  The arguments are those of `logit_rules`: logits (R, V) fp32 or bf16, any row stride; hist (R, T) int32
+    token histories, any row stride (hist[::K]); pos a (1,) int32 device tensor, the column of the token being chosen; t0 the
+    first generated column, the same for every row.
+
+    Per row, n = clamp(pos - t0, 0, T - t0) and g = hist[r, t0 : t0 + n]: only the generated tokens count (the prompt may be
+    left padding or the previous window's text).  With p = rules.repetition_penalty and s = rules.no_repeat_ngram_size, in this
+    order:
+    0. out[r] = logits[r], bit for bit;
+    1. p != 1: every distinct v in g with 0 <= v < V that is not exempt gets, in fp32, x = float(logits[r, v]) and
+       out[r, v] = x * p if x < 0 else x * rules.inv_penalty, rounded to the logits' dtype (bf16: to nearest even).  A token that
+       occurs several times is penalised once; -inf stays -inf and NaN stays NaN.  This is HF's RepetitionPenaltyLogitsProcessor
+       with its division written as a multiplication by the fp32 reciprocal that the host computed once (so that the kernel and
+       the torch restatement agree bitwise): the result may differ from a true division by one ulp;
+    2. s >= 1 and n >= s - 1: with ctx = g[n - s + 1 : n] (s - 1 tokens compared as raw int32 values; empty for s = 1), every i in
+       [0, n - s] with g[i : i + s - 1] == ctx names v = g[i + s - 1]; 0 <= v < V and not exempt: out[r, v] = -inf, whether or
+       not step 1 penalised it.  This is HF's NoRepeatNGramLogitsProcessor restricted to the generated part.
+    Every other entry is the input's bits.  A row that the rules block completely comes out all -inf: there is no guard.  Neutral
+    rules are a valid call: the result equals the input.  out: a static result buffer; it may be `logits` itself, and the kernel
+    then reads and writes only the entries it changes.  Runs the HIP kernel (mopk_repeat_rules: one launch, one workgroup per
+    row) when repeat_rules_supported() accepts the call (T - t0 <= 4096), else repeat_rules_torch(); LAST_PATH["repeat_rules"]
+    records which.  No host sync; bitwise reproducible."""
+    _rr_check(logits, hist, pos, t0, rules, out, "repeat_rules")
+    with torch.no_grad():
+        a = _rr_accept(logits, hist, pos, t0, rules, out)
+        if a is None:
+            LAST_PATH["repeat_rules"] = L.PATH_GENERIC
+            return repeat_rules_torch(logits, hist, pos, t0, rules, out)
+        if out is None:
+            out = torch.empty_like(logits, memory_format=torch.contiguous_format)
+            a.out, a.out_ld = out.data_ptr(), out.stride(0)                        # in place of the stand-in
+        _row_launch(a, "mopk_repeat_rules", "repeat_rules")
         return out
 
 
