@@ -28,12 +28,17 @@ def weight_grad_splits(rows: int, out_features: int) -> int:
     return s
 
 
+def _acc_dtype(t: torch.Tensor) -> torch.dtype:
+    """the dtype partial sums are added in: float32, which float64 tensors must not be rounded to"""
+    return torch.float64 if t.dtype == torch.float64 else torch.float32
+
+
 def _weight_grad(dy2: torch.Tensor, x2: torch.Tensor, n_out: int) -> torch.Tensor:
     rows = x2.shape[0]
     s = weight_grad_splits(rows, n_out)
     if s > 1:
         part = torch.bmm(dy2.reshape(s, rows // s, n_out).transpose(1, 2), x2.reshape(s, rows // s, x2.shape[1]))
-        return part.sum(0, dtype=torch.float32).to(dy2.dtype)
+        return part.sum(0, dtype=_acc_dtype(dy2)).to(dy2.dtype)
     return dy2.t() @ x2
 
 
@@ -50,7 +55,7 @@ class _ResidualLinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         n_out, n_in = weight.shape
-        dy2 = dy.reshape(-1, n_out)
+        dy2 = dy.reshape(-1, n_out).contiguous()     # a stride-0 (expanded) gradient would take other GEMM kernels: other bits
         dx = dw = None
         if ctx.needs_input_grad[1]:
             dx = (dy2 @ weight).view(x.shape)
@@ -76,7 +81,7 @@ class _TokenLinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         n_out, n_in = weight.shape
-        dy2 = dy.reshape(-1, n_out)
+        dy2 = dy.reshape(-1, n_out).contiguous()     # a stride-0 (expanded) gradient would take other GEMM kernels: other bits
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = (dy2 @ weight).view(x.shape)
@@ -86,11 +91,11 @@ class _TokenLinearFn(torch.autograd.Function):
             s = weight_grad_splits(rows, n_out)
             if s > 1:
                 part = torch.bmm(dy2.reshape(s, rows // s, n_out).transpose(1, 2), x2.reshape(s, rows // s, n_in))
-                dw = part.sum(0, dtype=torch.float32).to(weight.dtype)
+                dw = part.sum(0, dtype=_acc_dtype(dy2)).to(weight.dtype)
             else:
                 dw = dy2.t() @ x2
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy2.sum(0, dtype=torch.float32).to(dy.dtype)
+            db = dy2.sum(0, dtype=_acc_dtype(dy2)).to(dy.dtype)
         return dx, dw, db
 
 

@@ -7,11 +7,13 @@ tensor or a missing library raises -- there is no fallback path.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
@@ -78,6 +80,37 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
+
+
+def _once_differentiable(backward):
+    """torch's once_differentiable for a backward made of kernel launches, whose outputs carry no graph: differentiating them again
+    raises instead of contributing nothing.  torch hangs its error node on the outputs only when an incoming gradient requires
+    grad, but these gradients depend on the saved inputs as well (a gradient penalty on d y.sum() / dx meets a gradient of ones),
+    so under create_graph -- grad mode is on inside a backward only then -- one incoming gradient goes on as a leaf that requires
+    grad (the same storage, no copy)."""
+    marked = once_differentiable(backward)
+
+    @functools.wraps(backward)
+    def wrapper(ctx, *grads):
+        if torch.is_grad_enabled() and not any(isinstance(g, torch.Tensor) and g.requires_grad for g in grads):
+            grads = list(grads)
+            for i, g in enumerate(grads):
+                if isinstance(g, torch.Tensor):
+                    grads[i] = g.detach().requires_grad_()
+                    break
+        return marked(ctx, *grads)
+    return wrapper
+
+
+def _grad_in(dy: torch.Tensor, dtype: torch.dtype, shape=None) -> torch.Tensor:
+    """an incoming gradient as the kernels read it: contiguous, of the core's dtype and on a 16-byte boundary, viewed as `shape`.
+    Autograd may hand a backward an expanded (stride-0) tensor, a slice of a wider buffer, another dtype, or a contiguous tensor
+    whose storage offset puts it off the boundary (`.contiguous()` returns that one unchanged); each is copied into a fresh
+    tensor (the allocator's blocks are aligned), anything else is passed on as it is."""
+    if dy.dtype != dtype or not dy.is_contiguous() or dy.data_ptr() % 16:
+        src, dy = dy, torch.empty(dy.shape, dtype=dtype, device=dy.device)
+        dy.copy_(src)
+    return dy if shape is None or tuple(shape) == tuple(dy.shape) else dy.view(shape)
 
 
 def _f32_pack(ts):
@@ -245,9 +278,7 @@ def _ew_lowrank_bwd(ctx, dy, core_saved, head_grads):
     beta_not, V, prec, path, r, sfb, drop = ctx.meta
     B, N, Vq, _, H, dk = qkv.shape
     dev = qkv.device
-    dy = dy.contiguous()
-    if dy.dtype != qkv.dtype:
-        dy = dy.to(qkv.dtype)
+    dy = _grad_in(dy, qkv.dtype)
     # a.y = dy: unused by bwd, must be non-null
     a = _ew_args(qkv, dy, V, r, prec, path, beta_not, drop, (sqk, vs0, vsL, logit), (Wr, br, Wc, bc))
     a.save_for_backward = sfb
@@ -296,10 +327,12 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
         return y.view(B, N, H * dk)
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy):
         lib = L.lib()
-        qkv, _, sqk, *_rest = ctx.saved_tensors
-        extras = ctx.saved_tensors[10:]
+        saved_all = ctx.saved_tensors          # read once: a non-reentrant checkpoint unpacks (recomputes) on every access
+        qkv, _, sqk, *_rest = saved_all
+        extras = saved_all[10:]
         V, r = ctx.meta[1], ctx.meta[4]
         B, N, Vq, _, H, dk = qkv.shape
         n_extra = extras[0].shape[2] if extras else 0
@@ -309,7 +342,7 @@ class _EdgewiseLowrankFn(torch.autograd.Function):
         n_sqk, n_vs, n_w, n_b = V * H * dk, H * dk, 4 * r * C_, 4 * r
         small = torch.empty(n_sqk + 2 * n_vs + 2 * n_w + 2 * n_b + 1, dtype=torch.float32, device=qkv.device)
         dsqk, dvs0, dvsL, dWr, dbr, dWc, dbc, dlg = torch.split(small, [n_sqk, n_vs, n_vs, n_w, n_b, n_w, n_b, 1])
-        a, dqkv, d_extras, parts = _ew_lowrank_bwd(ctx, dy, ctx.saved_tensors, (dWr, dbr, dWc, dbc))
+        a, dqkv, d_extras, parts = _ew_lowrank_bwd(ctx, dy, saved_all, (dWr, dbr, dWc, dbc))
         L.check(lib.mopk_edgewise_reduce_parts(C.byref(a), dsqk.data_ptr(), dvs0.data_ptr(), dvsL.data_ptr(), dlg.data_ptr(),
                                                _stream()), "mopk_edgewise_reduce_parts")
         dlens = None
@@ -359,8 +392,10 @@ class _EdgewiseSharedFn(torch.autograd.Function):
         return y.view(B, N, H * dk)
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy):
-        core_saved, params = ctx.saved_tensors[:10], ctx.saved_tensors[10:]
+        saved_all = ctx.saved_tensors          # read once: a non-reentrant checkpoint unpacks (recomputes) on every access
+        core_saved, params = saved_all[:10], saved_all[10:]
         qkv = core_saved[0]
         n_w, n_b = params[3].numel(), params[4].numel()
         head = torch.empty(2 * n_w + 2 * n_b, dtype=torch.float32, device=qkv.device)
@@ -446,6 +481,7 @@ class _EdgewiseGeneralFn(torch.autograd.Function):
         return y.view(B, N, H * dk)
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy):
         lib = L.lib()
         qkv, saved, *rest = ctx.saved_tensors
@@ -454,9 +490,7 @@ class _EdgewiseGeneralFn(torch.autograd.Function):
         path = ctx.fwd_path
         B, N, Vq, _, H, dk = qkv.shape
         dev = qkv.device
-        dy = dy.contiguous()
-        if dy.dtype != qkv.dtype:
-            dy = dy.to(qkv.dtype)
+        dy = _grad_in(dy, qkv.dtype)
         small, head = (f["sqk"], f["vs0"], f["vsL"], f["logit"]), (f["h0"], f["h1"], f["h2"], f["h3"])
         a = _ew_args(qkv, dy, V, r, prec, path, beta_not, ctx.drop, small, None if var.dense else head, ctx.mask)
         a.save_for_backward = int(path == L.PATH_FUSED)
@@ -844,6 +878,7 @@ class _SdpaFn(torch.autograd.Function):
         return y.view(B, N, H * dk)
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy):
         lib = L.lib()
         q, k, v, y, saved = ctx.saved_tensors
@@ -851,7 +886,7 @@ class _SdpaFn(torch.autograd.Function):
         B, N, H, dk = q.shape
         Nk = k.shape[1]
         dev = q.device
-        dy = dy.contiguous().to(q.dtype).view(B, N, H, dk)
+        dy = _grad_in(dy, q.dtype, (B, N, H, dk))
         a = _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop)
         a.dy = _v4(dy)
         if ctx.packed:
@@ -907,6 +942,7 @@ class _SdpaLensFn(torch.autograd.Function):
         return y.view(B, N, H * dk)
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy):
         lib = L.lib()
         q, k, v, y, saved = ctx.saved_tensors
@@ -914,7 +950,7 @@ class _SdpaLensFn(torch.autograd.Function):
         B, N, H, dk = q.shape
         Nk = k.shape[1]
         dev = q.device
-        dy = dy.contiguous().to(q.dtype).view(B, N, H, dk)
+        dy = _grad_in(dy, q.dtype, (B, N, H, dk))
         a = _sdpa_lens_args(q, k, v, y, lens, causal, prec, path, drop)
         a.base.dy = _v4(dy)
         if ctx.packed:
@@ -1075,13 +1111,14 @@ class _CrossViewFn(torch.autograd.Function):
         return y.view(B, N, H * dk)
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy):
         lib = L.lib()
         *ts, mx, saved = ctx.saved_tensors
         cfg, causal, prec, mask, drop = ctx.meta
         B, N, H, dk = ts[0].shape
         dev = ts[0].device
-        dy = dy.contiguous().to(ts[0].dtype).view(B, N, H, dk)
+        dy = _grad_in(dy, ts[0].dtype, (B, N, H, dk))
         a = _cv_args(ts, mx, dy, cfg, mask, causal, prec, drop)          # a.y = dy: unused by bwd, must be non-null
         a.dy = _v4(dy)
         outs = [torch.empty(B, N, H, dk, dtype=ts[0].dtype, device=dev) for _ in range(5)]
@@ -1113,9 +1150,10 @@ def crossview_core(q1, k1, v1, q2, k2, mix, t1=0.0, t2=0.0, prior_weight=0.0, an
         return _empty_batch(q1, 0, q1.shape[1], q1.shape[2] * q1.shape[3])
     prec = _prec_for(q1.dtype)
     drop = _drop(dropout_p, seed)
-    if _cv_folds(t1, t2, prior_weight, prec, q1.shape[-1]):
+    if _cv_folds(t1, t2, prior_weight, prec, q1.shape[-1]) and not any(t.data_ptr() % 16 for t in (q1, k1, v1, q2, k2)):
         # the 2x2 mix folds into two mixed key tensors (autograd carries d mix, d k1, d k2) and the core is the fused two-score
-        # attention (dual-path kernels without the transport term)
+        # attention (dual-path kernels without the transport term), which reads 16-byte vectors: views off that boundary take the
+        # generic kernels below
         k1p, k2p = _cv_mixed_keys(mix.to(k1.dtype), k1, k2)
         zero = q1.new_zeros((), dtype=torch.float32)
         LAST_PATH["crossview_fwd"] = L.PATH_FUSED
@@ -1210,12 +1248,13 @@ class _DualPathFn(torch.autograd.Function):
         return y.view(B, N, H * dk)
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy):
         *ts, lg, y, saved = ctx.saved_tensors
         gates, beta_not, hops, causal, prec, path, mask, drop = ctx.meta
         B, N, H, dk = ts[0].shape
         dev = ts[0].device
-        dy = dy.contiguous().to(ts[0].dtype).view(B, N, H, dk)
+        dy = _grad_in(dy, ts[0].dtype, (B, N, H, dk))
         mk = torch.zeros if hops == 0 else torch.empty          # hops == 0: dv2 is never written
         if ctx.packed:
             packs = [mk(B, N, 3, H, dk, dtype=ts[0].dtype, device=dev) for _ in range(2)]
@@ -1250,6 +1289,7 @@ class _CrossViewFoldedFn(torch.autograd.Function):
         return y.view(B, N, H * dk)
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy):
         qkv1, qkv2, mix, k1p, k2p, lg, y, saved = ctx.saved_tensors
         causal, prec, path, mask, drop = ctx.meta
@@ -1257,7 +1297,7 @@ class _CrossViewFoldedFn(torch.autograd.Function):
         q2, k2, _ = qkv2.unbind(2)
         B, N, H, dk = q1.shape
         dev = q1.device
-        dy = dy.contiguous().to(q1.dtype).view(B, N, H, dk)
+        dy = _grad_in(dy, q1.dtype, (B, N, H, dk))
         d1, d2 = torch.empty_like(qkv1), torch.zeros_like(qkv2)            # v2 receives no gradient (:98)
         dk1p, dk2p = torch.empty(B, N, H, dk, dtype=q1.dtype, device=dev), torch.empty(B, N, H, dk, dtype=q1.dtype, device=dev)
         dv2 = torch.zeros(B, N, H, dk, dtype=q1.dtype, device=dev)          # hops == 0: never written
@@ -1331,6 +1371,7 @@ class _QuartetFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy, *unused):
         lib = L.lib()
         eps, use_quartet, prec, path, am, drop = ctx.meta
@@ -1339,7 +1380,7 @@ class _QuartetFn(torch.autograd.Function):
         ts, sc = ts[:n], ts[n:]
         B, T, H, dh = ts[0].shape
         dev = ts[0].device
-        dy = dy.contiguous().to(ts[0].dtype).view(B, T, H, dh)
+        dy = _grad_in(dy, ts[0].dtype, (B, T, H, dh))
         a = _qt_args(ts, sc, y, am, eps, prec, path, drop)
         a.dy = _v4(dy)
         gs = [torch.empty(B, T, H, dh, dtype=ts[0].dtype, device=dev) for _ in range(n)]
@@ -1373,10 +1414,11 @@ def quartet_core(q, k, v, q2, k2, mixture, quartet_scale, add_mask, eps, use_qua
 
 # ---- LayerNorm prologue / residual epilogue around the cores (mopk_layernorm_*) ----
 def layernorm_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
-    """shapes the HIP prologue covers (anything else: the caller keeps torch's LayerNorm)"""
+    """calls the HIP prologue covers (anything else: the caller keeps torch's LayerNorm): the shapes and dtypes, and an input the
+    kernels can read with 16-byte loads -- a contiguous x is passed as it is, so it has to sit on a 16-byte boundary"""
     d = x.shape[-1]
     return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and weight.dtype in (torch.float32, torch.bfloat16)
-            and d % 8 == 0 and d <= 4096 and x.numel() > 0)
+            and d % 8 == 0 and d <= 4096 and x.numel() > 0 and (not x.is_contiguous() or x.data_ptr() % 16 == 0))
 
 
 def _ln_args(xc, w, mean, rstd, y, eps) -> L.LayerNormArgs:
@@ -1408,6 +1450,7 @@ class _LayerNormFn(torch.autograd.Function):
         return y
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, *grads):
         xc, w, mean, rstd = ctx.saved_tensors
         eps, has_bias, with_residual, wdt, bdt = ctx.meta
@@ -1415,9 +1458,9 @@ class _LayerNormFn(torch.autograd.Function):
         d = xc.shape[-1]
         if dy is None:                                    # only the residual branch carries a gradient
             return (dres, None, None, None, None, None)
-        dy = dy.contiguous()
+        dy = _grad_in(dy, dy.dtype)
         if dres is not None:
-            dres = dres.to(xc.dtype).contiguous()
+            dres = _grad_in(dres, xc.dtype)
         dx = torch.empty_like(xc)
         dg = torch.empty(d, dtype=torch.float32, device=xc.device)
         db = torch.empty(d, dtype=torch.float32, device=xc.device) if has_bias else None
@@ -1515,12 +1558,13 @@ class _TokenGateFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dout):
         lib = L.lib()
         x, a, uc, gate = ctx.saved_tensors
         g = _tg_args(x, a)
         odt = torch.float32 if g.o_dtype == L.MOPK_F32 else torch.bfloat16
-        dout = dout.to(odt).contiguous()
+        dout = _grad_in(dout, odt)
         dr = torch.empty(x.shape, dtype=odt, device=x.device)
         du = torch.empty(3, x.shape[2], dtype=torch.float32, device=x.device)
         g.u, g.gate, g.dout, g.dr, g.du = uc.data_ptr(), gate.data_ptr(), dout.data_ptr(), dr.data_ptr(), du.data_ptr()
@@ -1610,6 +1654,8 @@ def moe_supported(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.
         return False
     a = _moe_args(None, gate_w, gate_b, w1s, w2s, *dt, M=x.numel() // D)
     a.x_dtype = _io_dtype(x)
+    if x.is_contiguous():       # passed to the kernels as it is (a strided x is copied first): the query sees its alignment
+        a.x = x.data_ptr()
     return bool(L.lib().mopk_moe_supported(C.byref(a)))
 
 
@@ -1643,12 +1689,13 @@ class _MoeFn(torch.autograd.Function):
         return y.view(x.shape)
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dy):
         x2, gate_w, gate_b, u, h, route, *ws = ctx.saved_tensors
         n_exp, odt, prec, xshape, xdt, has_res = ctx.meta
         w1s, w2s = ws[:n_exp], ws[n_exp:]
         D = x2.shape[1]
-        dyc = dy.reshape(-1, D).to(odt).contiguous()
+        dyc = _grad_in(dy, odt, (-1, D))
         a = _moe_args(x2, gate_w.detach(), None if gate_b is None else gate_b.detach(), w1s, w2s, odt, prec)
         dx = torch.empty(x2.shape, dtype=xdt, device=x2.device)
         dw1 = [torch.empty_like(w) for w in w1s]

@@ -19,7 +19,8 @@ Kernel-read or kernel-written buffers that do NOT come from the four patched fun
     Quartet cores, and `uc` of the token gate for a non-float32 u;
   * `x.contiguous()` of a row-strided LayerNorm input (ops.layernorm_residual cannot pass a row stride: the kernels' x_ld / y_ld
     are covered through the C ABI in test_layernorm_kernels_with_a_row_stride), `reshape(-1, D).contiguous()` of a strided MoE input, `q.contiguous()` of
-    a packed projection that is not contiguous, and `dy.contiguous()` / `dy.to(dtype)` of an incoming gradient that is neither;
+    a packed projection that is not contiguous (an incoming gradient that is not contiguous, aligned and of the core's dtype is
+    copied by ops._grad_in into a torch.empty buffer, a guarded one here: tests/test_gpu_autograd_contract.py runs those forms);
   * the mixed keys k1', k2' of the folded CrossView core (`_cv_mixed_keys`: arithmetic + .contiguous()) and the zero chain logit
     of ops.crossview_core (`new_zeros`);
   * what autograd itself allocates (accumulated .grad tensors are the guarded tensors the Functions return, but sums such as
