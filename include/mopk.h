@@ -1076,6 +1076,36 @@ typedef struct MopkRepeatRulesArgs {
 int mopk_repeat_rules_supported(const MopkRepeatRulesArgs *a);       /* 1 if the kernel takes this call (V, dtype, strides, T - T0) */
 int mopk_repeat_rules(const MopkRepeatRulesArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * Language probabilities on last-position logits (WhisperMoP.detect_language, and transcribe with `languages`; inference only):
+ * Whisper's detect_language after the decoder pass.  (Added under version 118: new exports only; callers detect it with
+ * mopk_language_probs_supported.)  Row r (0 <= r < R) reads x_i = (float)logits[r * logits_ld + ids[i]], 0 <= i < n, F32 or BF16,
+ * element-aligned, finite or -inf values; each ids[i] is clamped into [0, V) before the read, so no read leaves the row (callers
+ * refuse what they can see).  In fp32:
+ *   lse = m + logf(sum_i expf(x_i - m)), m = max_i x_i (-inf entries add nothing);
+ *   probs[r * probs_ld + i] = expf(x_i - lse), which is 0 for x_i = -inf;
+ *   tokens[r] = ids[i*], i* the largest x_i, ties to the smaller token id (what an argmax over the masked vocabulary gives).
+ * A row without a finite language entry is outside the contract: nothing faults, its values are unspecified.  Entries of probs
+ * behind column n of a row are not written.
+ * One launch, one workgroup of 256 threads per row; a thread gathers up to four entries and keeps them in registers, the
+ * (max, sum-exp) pairs and the best (value, id) are merged by wave shuffles and then in wave order; static LDS only, no atomics,
+ * no workspace, no host synchronisation: bitwise reproducible, and a first call may be inside a stream capture. */
+#define MOPK_LANGUAGE_MAX_N 1024
+typedef struct MopkLanguageProbsArgs {
+    int32_t R;                           /* rows */
+    int32_t V;                           /* vocabulary, >= 2 */
+    int32_t dtype;                       /* MopkDtype of logits: F32 or BF16 */
+    int32_t n;                           /* languages, 1 <= n <= MOPK_LANGUAGE_MAX_N */
+    const void *logits;
+    int64_t logits_ld;                   /* element stride between rows, >= V */
+    const int32_t *ids;                  /* device (n) int32, contiguous: the language tokens */
+    float *probs;                        /* (R, n) out */
+    int64_t probs_ld;                    /* element stride between probs rows, >= n */
+    int32_t *tokens;                     /* (R) out: the most probable language token of each row */
+} MopkLanguageProbsArgs;
+int mopk_language_probs_supported(const MopkLanguageProbsArgs *a);   /* 1 if the kernel takes this call (V, n, dtype, strides, alignment) */
+int mopk_language_probs(const MopkLanguageProbsArgs *a, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

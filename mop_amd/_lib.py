@@ -338,6 +338,15 @@ class GreedyPickArgs(C.Structure):
     ]
 
 
+class LanguageProbsArgs(C.Structure):
+    """MopkLanguageProbsArgs: the softmax over the language tokens' logits and its argmax (WhisperMoP.detect_language)."""
+    _fields_ = [
+        ("R", C.c_int32), ("V", C.c_int32), ("dtype", C.c_int32), ("n", C.c_int32),
+        ("logits", _fp), ("logits_ld", C.c_int64), ("ids", _fp), ("probs", _fp), ("probs_ld", C.c_int64), ("tokens", _fp),
+    ]
+
+
+LANGUAGE_MAX_N = 1024      # MOPK_LANGUAGE_MAX_N
 LOG_MEL_TILE_FRAMES = 32   # MOPK_LOG_MEL_TILE_FRAMES
 LOG_MEL_F16 = 2            # MOPK_LOG_MEL_F16
 
@@ -443,6 +452,8 @@ SYMBOLS = {
     "mopk_token_logprob": (C.c_int, [C.POINTER(TokenLogprobArgs), C.c_void_p]),
     "mopk_greedy_pick_supported": (C.c_int, [C.POINTER(GreedyPickArgs)]),
     "mopk_greedy_pick": (C.c_int, [C.POINTER(GreedyPickArgs), C.c_void_p]),
+    "mopk_language_probs_supported": (C.c_int, [C.POINTER(LanguageProbsArgs)]),
+    "mopk_language_probs": (C.c_int, [C.POINTER(LanguageProbsArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -112,6 +112,14 @@ class DecodeStats(NamedTuple):
     no_speech_prob: Optional[torch.Tensor]
 
 
+class LanguageDetection(NamedTuple):
+    """the language of a batch of clips (`WhisperMoP.detect_language`, and the last element of what `transcribe` returns with
+    `languages`), on the device.  tokens: int32 (B,), each clip's most probable language token; probs: fp32 (B, n), the
+    probabilities of the n language tokens in the ops.LanguageTokens' order (a softmax over them alone)."""
+    tokens: torch.Tensor
+    probs: torch.Tensor
+
+
 class TranscribeLog(NamedTuple):
     """what `transcribe` decided for one clip's windows (return_log=True): host values, one entry per window, in order.
     seek: the window's first frame; temperature: the one whose result was kept; avg_logprob: sum_logprobs / n_tokens of it;
@@ -1234,6 +1242,58 @@ class WhisperMoP(nn.Module):
         text = ids.to(torch.int32)[:, prompt_len + 1:T - 1]
         return ops.word_spans(text, starts[:, prompt_len:T - 1], tok_probs[:, prompt_len:T - 2], n_tokens - (prompt_len + 2), word_rules, cap)
 
+    # ---- language detection; inference only ----
+    def _language_check(self, mel, sot_ids, languages, what: str) -> torch.Tensor:
+        """detect_language's argument checks -> the decoder's ids, (B, T_s) on the mel's device; ValueErrors before any device
+        work"""
+        V = self.cfg.vocab_size
+        if not isinstance(languages, ops.LanguageTokens):
+            raise ValueError(f"{what}: languages must be an ops.LanguageTokens, got {type(languages).__name__}")
+        if languages.vocab_size != V:
+            raise ValueError(f"{what}: the languages were built for vocab_size = {languages.vocab_size}, the model has {V}")
+        alens = self._audio_check(mel, what)
+        if alens is None:
+            if mel.dim() != 3 or mel.shape[0] < 1 or mel.shape[2] != self.cfg.n_mels or not 1 <= mel.shape[1] <= self.cfg.n_audio_ctx:
+                raise ValueError(f"{what}: mel must be a (B, T, n_mels = {self.cfg.n_mels}) tensor with 1 <= T <= n_audio_ctx = "
+                                 f"{self.cfg.n_audio_ctx} or a non-empty list of B (T_b, n_mels) tensors, got {tuple(mel.shape)}")
+            B, dev = mel.shape[0], mel.device
+        else:
+            B, dev = len(alens), mel[0].device
+        if isinstance(sot_ids, torch.Tensor):
+            if (sot_ids.dim() not in (1, 2) or sot_ids.dtype.is_floating_point or sot_ids.dtype.is_complex
+                    or sot_ids.dtype == torch.bool or sot_ids.shape[-1] < 1):
+                raise ValueError(f"{what}: sot_ids must be an int or an integer (T_s,) or (B, T_s) tensor with T_s >= 1, got "
+                                 f"{tuple(sot_ids.shape)} {sot_ids.dtype}")
+            if sot_ids.dim() == 2 and sot_ids.shape[0] != B:
+                raise ValueError(f"{what}: {sot_ids.shape[0]} rows of sot_ids for a batch of {B} mel inputs")
+            if sot_ids.shape[-1] > self.cfg.n_text_ctx:
+                raise ValueError(f"{what}: T_s = {sot_ids.shape[-1]} exceeds n_text_ctx = {self.cfg.n_text_ctx}")
+            if sot_ids.device != dev:
+                raise ValueError(f"{what}: sot_ids are on {sot_ids.device}, the mel on {dev}")
+            if not sot_ids.is_cuda and bool(((sot_ids < 0) | (sot_ids >= V)).any()):   # host values: the host can know
+                raise ValueError(f"{what}: an id of sot_ids lies outside [0, vocab_size = {V})")
+            return sot_ids if sot_ids.dim() == 2 else sot_ids.unsqueeze(0).expand(B, -1)
+        if isinstance(sot_ids, bool) or not isinstance(sot_ids, int) or not 0 <= sot_ids < V:
+            raise ValueError(f"{what}: sot_ids must be an int in [0, vocab_size = {V}) or an integer (T_s,) or (B, T_s) tensor, got "
+                             f"{sot_ids!r}")
+        return torch.full((B, 1), sot_ids, dtype=torch.long, device=dev)
+
+    @torch.no_grad()
+    def detect_language(self, mel, sot_ids, languages: "ops.LanguageTokens") -> LanguageDetection:
+        """Whisper's detect_language -> LanguageDetection(tokens (B,) int32, probs (B, n) fp32), on the device.
+
+        mel: as for `encode`, a (B, T, n_mels) tensor or a list of B clips of different lengths, 1 <= T_b <= n_audio_ctx.
+        sot_ids: the tokens in front of the language token, an int, a (T_s,) tensor for every clip or a (B, T_s) integer tensor,
+        T_s >= 1 (Whisper's is [<|startoftranscript|>]).  languages: the ops.LanguageTokens of the model's vocabulary.
+        The result is ops.language_probs(decode(encode(mel)[0], ids)[:, -1], languages): one encoder pass, one teacher-forced
+        decoder pass over the T_s tokens (no cache), and one launch that masks everything but the language tokens at the last
+        position, takes the softmax over them and their argmax (ties to the smaller token id).  No host synchronisation.
+        ValueError before any device work: languages of another type or vocabulary, T_s > n_text_ctx, an id outside the
+        vocabulary where the host can see it (an int, a CPU tensor), sot_ids on another device than the mel."""
+        ids = self._language_check(mel, sot_ids, languages, "detect_language")
+        res = ops.language_probs(self.decode(self.encode(mel)[0], ids)[:, -1], languages)
+        return LanguageDetection(res.tokens, res.probs)
+
     # ---- long-form transcription; inference only ----
     def _transcribe_check(self, mel, prompt_ids, logit_rules, max_new_tokens, window, frames_per_timestamp, num_beams,
                           length_penalty):
@@ -1454,8 +1514,8 @@ class WhisperMoP(nn.Module):
                     no_speech_threshold: Optional[float] = None, no_speech_token_id: Optional[int] = None, sot_index: int = 0,
                     compression_ratio_threshold: Optional[float] = None, compression_ratio=None, num_samples: int = 1,
                     seed: int = 0, return_log: bool = False, word_timestamps: bool = False, word_rules=None, alignment_heads=None,
-                    medfilt_width: int = 7, median_word_frames: Optional[int] = None, repeat_rules=None,
-                    condition_on_previous_text: bool = False, initial_prompt=None, sot_prev_token_id: Optional[int] = None,
+                    medfilt_width: int = 7, median_word_frames: Optional[int] = None, languages=None, language_index: int = 1,
+                    repeat_rules=None, condition_on_previous_text: bool = False, initial_prompt=None, sot_prev_token_id: Optional[int] = None,
                     max_prompt_tokens: Optional[int] = None, prompt_reset_temperature: float = 0.5):
         """long-form transcription, Whisper's transcribe loop over windows for a batch of clips -> a list of B Transcript(starts,
         ends, tokens, offsets), all on the device.
@@ -1552,8 +1612,22 @@ class WhisperMoP(nn.Module):
         text).  Build them with ops.RepeatRules.for_whisper(logit_rules, ...): it exempts eos and the timestamp tokens, which the
         segments need to repeat (one segment's end and the next one's start are the same token).  The alignment pass of the word
         timestamps decodes nothing and is not affected.
-        Out of scope: Whisper's pause and segment-boundary heuristics on the words (last_speech_timestamp, preferring the
-        segment-level start / end), hallucination_silence_threshold, word splitting on unicode code points, an alignment pass
+
+        Language detection (Whisper's language=None).  With languages None nothing changes: no launch, no buffer, no copy, and
+        language_index is not looked at.  With languages an ops.LanguageTokens of the model's vocabulary, prompt_ids' column
+        language_index (1 <= language_index < T_p; Whisper's start-of-transcript sequence has the language token at 1) is a
+        placeholder: before the window loop ONE detect_language call runs over the B clips' first windows mel_b[:window], as one
+        batch of clips of different lengths, from prompt_ids[..., :language_index]; prompt_ids is expanded to a (B, T_p) copy
+        on the device, and a device-side copy writes the detected tokens into its column language_index (no value comes to the
+        host, and no host synchronisation is added beyond what a device (B, T_p) prompt tensor costs).  The loop then runs exactly
+        as if the caller had passed that matrix: every window, fallback attempt, conditioned prompt and alignment pass opens with
+        the detected language.  The LanguageDetection is appended as the LAST element of what is returned: (transcripts,
+        detection), (transcripts, logs, detection), (transcripts, words, detection) or (transcripts, logs, words, detection).
+        ValueError before any device work: languages of another type or vocabulary; language_index outside [1, T_p).
+        Out of scope: reusing the detection's encoder output for the first window (Whisper encodes twice too), detection on
+        anything but the first window, a vocabulary projection restricted to the language rows, Whisper's pause and
+        segment-boundary heuristics on the words (last_speech_timestamp, preferring the segment-level start / end),
+        hallucination_silence_threshold, word splitting on unicode code points, an alignment pass
         fused so that it never materialises the probability maps, top-k / top-p inside transcribe, handing the encoded audio over
         to a fallback attempt or to the alignment pass, a device-side compression ratio, and a vocabulary projection of the prompt
         pass restricted to the columns that are read."""
@@ -1565,6 +1639,15 @@ class WhisperMoP(nn.Module):
                                      sot_prev_token_id, max_prompt_tokens, prompt_reset_temperature)
         wt = self._words_check(prompt_ids.shape[-1], max_new_tokens, logit_rules, word_timestamps, word_rules, alignment_heads,
                                medfilt_width, median_word_frames)
+        detection = None
+        if languages is not None:
+            if (isinstance(language_index, bool) or not isinstance(language_index, int)
+                    or not 1 <= language_index < prompt_ids.shape[-1]):
+                raise ValueError(f"transcribe: language_index must be an int in [1, T_p = {prompt_ids.shape[-1]}) (the language "
+                                 f"token's column of prompt_ids, behind the tokens it is detected from), got {language_index!r}")
+            detection = self.detect_language([c[:W] for c in clips], prompt_ids[..., :language_index], languages)
+            prompt_ids = (prompt_ids if prompt_ids.dim() == 2 else prompt_ids.unsqueeze(0).expand(len(clips), -1)).clone()
+            prompt_ids[:, language_index] = detection.tokens       # a device-side copy: the host never sees the language
         plain = (pol.temperatures == (0.0,) and logprob_threshold is None and no_speech_threshold is None
                  and no_speech_token_id is None and compression_ratio is None and not return_log)
         calls = [0]
@@ -1662,8 +1745,11 @@ class WhisperMoP(nn.Module):
         for b, (st, en, tk, off) in enumerate(parts):
             off.append(torch.full((1,), n_tok[b], dtype=torch.int32, device=dev))
             out.append(Transcript(torch.cat(st), torch.cat(en), torch.cat(tk), torch.cat(off)))
+        tail = () if detection is None else (detection,)
         if wt is None:
-            return (out, logs) if return_log else out
+            if return_log:
+                return (out, logs) + tail
+            return (out,) + tail if tail else out
         words = []
         for b, wp in enumerate(wparts):
             if wp[0]:
@@ -1673,7 +1759,7 @@ class WhisperMoP(nn.Module):
                 st, en, tb_, te_ = (torch.empty(0, dtype=torch.int32, device=dev) for _ in range(4))
                 pr = torch.empty(0, dtype=torch.float32, device=dev)
             words.append(TranscriptWords(st, en, pr, tb_, te_, torch.searchsorted(out[b].offsets, tb_, right=True) - 1))
-        return (out, logs, words) if return_log else (out, words)
+        return ((out, logs, words) if return_log else (out, words)) + tail
 
     def _words_check(self, T_p: int, max_new_tokens: int, logit_rules, word_timestamps, word_rules, alignment_heads, medfilt_width,
                      median_word_frames) -> Optional[_Words]:
@@ -1734,7 +1820,7 @@ class WhisperMoP(nn.Module):
         `_transcribe` for this entry point.
         Every keyword of transcribe passes through (the temperature fallback and the no-speech skip included; with return_log=True
         the logs come back beside the transcripts; with word_timestamps=True the words too, and a median_word_frames the caller
-        leaves out becomes round(0.7 / frontend.frame_seconds), Whisper's 0.7 s).  A segment's frames times frontend.frame_seconds are seconds.  ValueError when frontend.n_mels is not the model's."""
+        leaves out becomes round(0.7 / frontend.frame_seconds), Whisper's 0.7 s; with languages the LanguageDetection comes back last).  A segment's frames times frontend.frame_seconds are seconds.  ValueError when frontend.n_mels is not the model's."""
         if not isinstance(frontend, LogMelFrontend) or frontend.n_mels != self.cfg.n_mels:
             raise ValueError(f"transcribe_audio: frontend must be a LogMelFrontend with n_mels = {self.cfg.n_mels} (the model's), got "
                              f"{getattr(frontend, 'n_mels', type(frontend).__name__)!r}")
@@ -1817,7 +1903,7 @@ class RuledDecoding:
     by ops.logit_rules, one HIP launch inside the step.  The decoders' own signatures do not change (their tests pin them); each
     method here takes the arguments of the method it names, and what came later as keywords of its own: the decoding statistics
     (return_stats, no_speech_token_id, sot_index) and, on transcribe, the temperature fallback, the no-speech skip, the
-    conditioning on the previous text and the word timestamps.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
+    conditioning on the previous text, the word timestamps and the language detection.  rules.eos_token_id, when set, must equal a call's eos_token_id when that is given too
     (ValueError).  logit_rules None runs the plain decoder: no extra launch, no extra buffer.
     repeat_rules (ops.RepeatRules; for Whisper build them with ops.RepeatRules.for_whisper(logit_rules, ...), which exempts eos
     and the timestamps): a repetition penalty and / or no-repeat n-gram blocking over each row's generated tokens, by
@@ -1866,9 +1952,9 @@ class RuledDecoding:
                    no_speech_token_id: Optional[int] = None, sot_index: int = 0, compression_ratio_threshold: Optional[float] = None,
                    compression_ratio=None, num_samples: int = 1, seed: int = 0, return_log: bool = False,
                    word_timestamps: bool = False, word_rules=None, alignment_heads=None, medfilt_width: int = 7,
-                   median_word_frames: Optional[int] = None, condition_on_previous_text: bool = False, initial_prompt=None,
-                   sot_prev_token_id: Optional[int] = None, max_prompt_tokens: Optional[int] = None,
-                   prompt_reset_temperature: float = 0.5):
+                   median_word_frames: Optional[int] = None, languages=None, language_index: int = 1,
+                   condition_on_previous_text: bool = False, initial_prompt=None, sot_prev_token_id: Optional[int] = None,
+                   max_prompt_tokens: Optional[int] = None, prompt_reset_temperature: float = 0.5):
         return self.model._transcribe(
             mel, prompt_ids, self.logit_rules, max_new_tokens, window=window, frames_per_timestamp=frames_per_timestamp,
             num_beams=num_beams, length_penalty=length_penalty, graph=graph, temperatures=temperatures,
@@ -1878,7 +1964,7 @@ class RuledDecoding:
             initial_prompt=initial_prompt, sot_prev_token_id=sot_prev_token_id, max_prompt_tokens=max_prompt_tokens,
             prompt_reset_temperature=prompt_reset_temperature, word_timestamps=word_timestamps, word_rules=word_rules,
             alignment_heads=alignment_heads, medfilt_width=medfilt_width, median_word_frames=median_word_frames,
-            repeat_rules=self.repeat_rules)
+            languages=languages, language_index=language_index, repeat_rules=self.repeat_rules)
 
 
 RuledDecoding.transcribe.__doc__ = WhisperMoP._transcribe.__doc__

@@ -2008,7 +2008,7 @@ def decode_attention_lens(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     return _da_run("decode_attention_lens", q, k_cache, v_cache, kv_lens=kv_lens, nk=nk)
 
 
-# ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, repeat_rules, token_logprob, greedy_pick,
+# ---- the ops after the decoder's logits: beam_step, sample_tokens[_ragged], logit_rules, repeat_rules, token_logprob, language_probs, greedy_pick,
 # alignment_cost, dtw_align, timestamp_segments, prompt_history_update, window_prompts, alignment_rows, word_spans ----
 # Each is its _*_check (every ValueError, once per call), its _*_accept (the tensor-side tests, then the args struct, built once,
 # if the library's _supported query takes it, else None), then the torch restatement, or the outputs into that struct and _row_launch.
@@ -2934,6 +2934,161 @@ def token_logprob(logits: torch.Tensor, tokens, out=None) -> torch.Tensor:
             a.out = out.data_ptr()
         _row_launch(a, "mopk_token_logprob", "token_logprob")
         return out
+
+
+# ---- language probabilities on last-position logits (mopk_language_probs; WhisperMoP.detect_language) ----
+class LanguageTokens:
+    """The language tokens of a vocabulary of `vocab_size` tokens (the tokenizer's share of Whisper's detect_language).
+
+    token_ids: 1 <= n <= 1024 distinct integer ids, each in [0, vocab_size); their order is the column order of the probabilities
+    that `language_probs` returns.  The constructor validates everything (ValueError) before any device work and builds the (n,)
+    int32 table once; table(device) returns its copy on a device, made once per device (pass `device` to make it at construction)."""
+
+    def __init__(self, vocab_size: int, token_ids, device=None):
+        def _int(x, name):
+            try:
+                ok = not isinstance(x, bool) and int(x) == x
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"LanguageTokens: {name} must be an integer, got {x!r}")
+            return int(x)
+
+        V = _int(vocab_size, "vocab_size")
+        if V < 2:
+            raise ValueError(f"LanguageTokens: vocab_size must be >= 2, got {V}")
+        if isinstance(token_ids, torch.Tensor):
+            token_ids = token_ids.reshape(-1).tolist()
+        try:
+            ids = tuple(_int(t, "a token id") for t in token_ids)
+        except TypeError:
+            raise ValueError(f"LanguageTokens: token_ids must be a sequence of integers, got {type(token_ids).__name__}") from None
+        if not 1 <= len(ids) <= L.LANGUAGE_MAX_N:
+            raise ValueError(f"LanguageTokens: needs 1 <= n <= {L.LANGUAGE_MAX_N} language tokens, got {len(ids)}")
+        for t in ids:
+            if not 0 <= t < V:
+                raise ValueError(f"LanguageTokens: token id {t} outside [0, vocab_size = {V})")
+        if len(set(ids)) != len(ids):
+            raise ValueError("LanguageTokens: the token ids must be distinct")
+        self.vocab_size, self.token_ids, self.n = V, ids, len(ids)
+        self._tables = {torch.device("cpu"): torch.tensor(ids, dtype=torch.int32)}
+        if device is not None:
+            self.table(device)
+
+    table = LogitRules.table
+
+    @classmethod
+    def for_whisper(cls, vocab_size: int, sot_token_id: int, n_languages: int, device=None) -> "LanguageTokens":
+        """Whisper's layout: the n_languages language tokens follow <|startoftranscript|>, ids sot + 1 ... sot + n_languages"""
+        for name, x in (("sot_token_id", sot_token_id), ("n_languages", n_languages)):
+            if not _is_index(x):
+                raise ValueError(f"LanguageTokens.for_whisper: {name} must be an int, got {x!r}")
+        if n_languages < 1:
+            raise ValueError(f"LanguageTokens.for_whisper: n_languages must be >= 1, got {n_languages}")
+        return cls(vocab_size, range(sot_token_id + 1, sot_token_id + 1 + n_languages), device)
+
+
+class LanguageProbs(NamedTuple):
+    """what `language_probs` returns: probs (R, n) fp32, the softmax over the language tokens' logits in the LanguageTokens'
+    order; tokens (R,) int32, the most probable language token of each row"""
+    probs: torch.Tensor
+    tokens: torch.Tensor
+
+
+def _lp_check(logits, languages, out_probs, out_tokens, what: str) -> None:
+    """validate a language_probs call before any device work"""
+    if not isinstance(languages, LanguageTokens):
+        raise ValueError(f"{what}: languages must be a LanguageTokens, got {type(languages).__name__}")
+    _stat_logits_check(logits, what)
+    R, V = logits.shape
+    if V != languages.vocab_size:
+        raise ValueError(f"{what}: logits have V = {V}, the languages were built for vocab_size = {languages.vocab_size}")
+    n = languages.n
+    if out_probs is not None and (not isinstance(out_probs, torch.Tensor) or tuple(out_probs.shape) != (R, n)
+                                  or out_probs.dtype != torch.float32 or out_probs.device != logits.device):
+        raise ValueError(f"{what}: out_probs must be an fp32 ({R}, {n}) tensor on {logits.device}, got "
+                         f"{(tuple(out_probs.shape), out_probs.dtype, out_probs.device) if isinstance(out_probs, torch.Tensor) else type(out_probs).__name__}")
+    if out_tokens is not None and (not isinstance(out_tokens, torch.Tensor) or tuple(out_tokens.shape) != (R,)
+                                   or out_tokens.dtype != torch.int32 or out_tokens.device != logits.device):
+        raise ValueError(f"{what}: out_tokens must be an int32 ({R},) tensor on {logits.device}, got "
+                         f"{(tuple(out_tokens.shape), out_tokens.dtype, out_tokens.device) if isinstance(out_tokens, torch.Tensor) else type(out_tokens).__name__}")
+
+
+def language_probs_torch(logits: torch.Tensor, languages: LanguageTokens, out_probs=None, out_tokens=None) -> LanguageProbs:
+    """the restatement of `language_probs` in torch ops (CPU or GPU, no host sync): the language columns gathered and widened to
+    fp32, exp(x - logsumexp(x)), and of the columns that hold the row's maximum the smallest token id"""
+    _lp_check(logits, languages, out_probs, out_tokens, "language_probs_torch")
+    ids = languages.table(logits.device)
+    x = logits.index_select(1, ids.to(torch.long)).float()                         # (R, n)
+    probs = (x - torch.logsumexp(x, 1, keepdim=True)).exp()
+    best = x == x.max(1, keepdim=True).values
+    tokens = torch.where(best, ids.unsqueeze(0), torch.full_like(ids, 0x7fffffff).unsqueeze(0)).min(1).values
+    if out_probs is not None:
+        out_probs.copy_(probs)
+        probs = out_probs
+    if out_tokens is not None:
+        out_tokens.copy_(tokens)
+        tokens = out_tokens
+    return LanguageProbs(probs, tokens)
+
+
+def _lp_accept(logits, languages, out_probs, out_tokens):
+    """the args struct of a call that mopk_language_probs takes, None of one it refuses; an out_ buffer that is None is left NULL
+    (the query looks at alignment and stride only; the launcher fills it in)"""
+    if not _stat_logits_ok(logits):
+        return None
+    a = L.LanguageProbsArgs()
+    a.R, a.V = logits.shape
+    a.n = languages.n
+    a.dtype = L.MOPK_BF16 if logits.dtype == torch.bfloat16 else L.MOPK_F32
+    a.logits, a.logits_ld = logits.data_ptr(), a.V if a.R == 1 else logits.stride(0)   # a single row: its stride is never used
+    a.probs_ld = a.n
+    if out_probs is not None:
+        if not out_probs.is_cuda or out_probs.stride(1) != 1 or (a.R > 1 and out_probs.stride(0) < a.n):
+            return None
+        a.probs, a.probs_ld = out_probs.data_ptr(), a.n if a.R == 1 else out_probs.stride(0)
+    if out_tokens is not None:
+        if not (out_tokens.is_cuda and out_tokens.is_contiguous()):
+            return None
+        a.tokens = out_tokens.data_ptr()
+    a.ids = languages.table(logits.device).data_ptr()
+    return a if L.lib().mopk_language_probs_supported(C.byref(a)) else None
+
+
+def language_probs_supported(logits: torch.Tensor, languages: LanguageTokens, out_probs=None, out_tokens=None) -> bool:
+    """True if mopk_language_probs takes this call: CUDA fp32 / bf16 logits with unit inner stride and a row stride >= V (one row:
+    any), a CUDA out_probs with unit inner stride and a row stride >= n, a contiguous CUDA out_tokens (the library's own query
+    decides the rest).  Raises ValueError on bad arguments."""
+    _lp_check(logits, languages, out_probs, out_tokens, "language_probs_supported")
+    return _lp_accept(logits, languages, out_probs, out_tokens) is not None
+
+
+def language_probs(logits: torch.Tensor, languages: LanguageTokens, out_probs=None, out_tokens=None) -> LanguageProbs:
+    """the probability of each language and the most probable one -> LanguageProbs(probs (R, n) fp32, tokens (R,) int32): Whisper's
+    detect_language on the logits that follow <|startoftranscript|>.  Inference only.
+
+    logits: (R, V) fp32 or bf16, any row stride >= V (a column of a (B, T, V) tensor is one).  languages: a LanguageTokens built
+    for V, n tokens t_0 ... t_{n-1}.  Per row, in fp32: x_i = float(logits[r, t_i]); probs[r, i] = exp(x_i - lse(x)), the softmax
+    over the language tokens alone (every other token is masked, as in Whisper), 0 where x_i = -inf; tokens[r] = the t_i with the
+    largest x_i, ties to the smaller token id (the argmax over the masked vocabulary).  A row without a finite language entry is
+    outside the contract (its values are unspecified).  out_probs: a static fp32 (R, n) result buffer, any row stride >= n (what
+    lies behind column n of a row is left alone); out_tokens: a static int32 (R,) one.  Runs the HIP kernel (mopk_language_probs:
+    one launch, one workgroup per row) when language_probs_supported() accepts the call, else language_probs_torch();
+    LAST_PATH["language_probs"] records which.  No host sync; bitwise reproducible."""
+    _lp_check(logits, languages, out_probs, out_tokens, "language_probs")
+    with torch.no_grad():
+        a = _lp_accept(logits, languages, out_probs, out_tokens)
+        if a is None:
+            LAST_PATH["language_probs"] = L.PATH_GENERIC
+            return language_probs_torch(logits, languages, out_probs, out_tokens)
+        if out_probs is None:
+            out_probs = torch.empty(a.R, a.n, dtype=torch.float32, device=logits.device)
+            a.probs = out_probs.data_ptr()
+        if out_tokens is None:
+            out_tokens = torch.empty(a.R, dtype=torch.int32, device=logits.device)
+            a.tokens = out_tokens.data_ptr()
+        _row_launch(a, "mopk_language_probs", "language_probs")
+        return LanguageProbs(out_probs, out_tokens)
 
 
 class GreedyState:
