@@ -1106,6 +1106,71 @@ typedef struct MopkLanguageProbsArgs {
 int mopk_language_probs_supported(const MopkLanguageProbsArgs *a);   /* 1 if the kernel takes this call (V, n, dtype, strides, alignment) */
 int mopk_language_probs(const MopkLanguageProbsArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * The MoP mel gate of every WhisperMoP encoder layer (mop/models/whisper_mop.py:91-124 MoP2D), all layers in one launch.  (Added
+ * under version 118: new exports only; callers detect it with mopk_mel_gate_supported.)
+ * MoP2D (1x1 conv -> kxk conv -> cat -> 1x1 conv -> mean over frequency -> 1 + a0 g0 - a1 g1) has no bias and no non-linearity,
+ * so it folds (mop_amd/ops.py mel_gate_taps, in torch) into a 1-D stencil over time with F input channels, p = k / 2:
+ *     gates[b,l,t] = 1 + sum_{i<k} sum_{f<F} mel[b, t+i-p, f] W[l,i,f]       (frames outside [0, T) are zero).
+ * With lens (device int32 (B)): rows t >= lens[b] of mel are NOT READ and count as zeros, gates[b,l,t >= lens[b]] = 1 exactly.
+ *   _fwd: a workgroup stages MOPK_MEL_GATE_TILE frames plus the 2p halo of one item in LDS once (converted to fp32) and writes
+ *         every layer's gate of the tile from it; the taps sit in LDS too, and more than MOPK_MEL_GATE_LAYERS layers go in
+ *         chunks of that many (one launch per chunk).  Each gate is one fp32 sum in a fixed order (i outer, f inner) that does
+ *         not depend on T or B, so a clip's columns are bitwise those of the clip alone.
+ *   _bwd: dW[l,i,f] = sum_{b,t < lens[b]} dgates[b,l,t] mel[b,t+i-p,f].  Workgroup j sums the tiles j, j + P, ... (P =
+ *         min(tiles, 256)) into registers and writes one partial row of `workspace`; a second launch sums the P rows in a fixed
+ *         order.  No atomics: bitwise reproducible.  No gradient of mel.
+ * mel: element strides (mel_sb, mel_st), innermost contiguous, element-aligned (16-byte aligned rows take vector loads, others
+ * scalar loads).  W, gates, dgates, dW: contiguous fp32.  Odd k <= 7, F <= 128, any B, T, L >= 1. */
+#define MOPK_MEL_GATE_TILE 32
+#define MOPK_MEL_GATE_LAYERS 8
+#define MOPK_MEL_GATE_MAX_K 7
+#define MOPK_MEL_GATE_MAX_F 128
+typedef struct MopkMelGateArgs {
+    int32_t B, T, F, L, k;
+    int32_t mel_dtype;                   /* MopkDtype: F32 or BF16 */
+    const void *mel;                     /* (B,T,F) */
+    int64_t mel_sb, mel_st;              /* element strides, mel_st >= F */
+    const float *W;                      /* (L,k,F) fp32 contiguous */
+    const int32_t *lens;                 /* device (B) int32 or NULL; values are clamped into [0, T] */
+    float *gates;                        /* fwd out (B,L,T) fp32 contiguous */
+    const float *dgates;                 /* bwd in  (B,L,T) fp32 contiguous */
+    float *dW;                           /* bwd out (L,k,F) fp32 contiguous */
+    void *workspace;                     /* bwd: mopk_mel_gate_workspace_bytes() */
+} MopkMelGateArgs;
+int mopk_mel_gate_supported(const MopkMelGateArgs *a);                /* 1 if the kernels take this call (shape, dtype, strides, alignment) */
+size_t mopk_mel_gate_workspace_bytes(const MopkMelGateArgs *a);
+int mopk_mel_gate_fwd(const MopkMelGateArgs *a, void *stream);
+int mopk_mel_gate_bwd(const MopkMelGateArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
+ * Residual add and per-token gate of the WhisperMoP encoder block in one launch.  (Added under version 118: new exports only;
+ * callers detect it with mopk_gated_residual_supported.)
+ *   _fwd: out[b,t,:] = (x[b,t,:] + a[b,t,:]) gate[b,t].
+ *   _bwd: dr[b,t,:] = dout[b,t,:] gate[b,t] (the gradient of both x and a), dgate[b,t] = sum_d dout[b,t,d] (x + a)[b,t,d] with
+ *         r recomputed from x and a.  One wave owns a row and reduces it by shuffles: no atomics, bitwise reproducible.
+ * x / a: (B,T,D) with element strides (sb, st), innermost contiguous.  gate: (B,T) fp32 with batch stride gate_sb, t contiguous.
+ * o_dtype must be the promotion of x_dtype and a_dtype.  out / dout / dr: contiguous (B,T,D) o_dtype; dgate contiguous (B,T) fp32.
+ * D % 8 == 0, strides multiples of 8, 16-byte aligned x / a / out / dout / dr; no workspace. */
+typedef struct MopkGatedResidualArgs {
+    int32_t B, T, D;
+    int32_t x_dtype, a_dtype, o_dtype;   /* MopkDtype */
+    const void *x;
+    int64_t x_sb, x_st;
+    const void *a;
+    int64_t a_sb, a_st;
+    const float *gate;                   /* (B,T) fp32 */
+    int64_t gate_sb;                     /* element stride between the gate's rows, >= T */
+    void *out;                           /* fwd out */
+    const void *dout;                    /* bwd in */
+    void *dr;                            /* bwd out */
+    float *dgate;                        /* bwd out (B,T) fp32 */
+} MopkGatedResidualArgs;
+int mopk_gated_residual_supported(const MopkGatedResidualArgs *a);    /* 1 if the kernels take this call (shape, dtypes, strides, alignment) */
+size_t mopk_gated_residual_workspace_bytes(const MopkGatedResidualArgs *a);   /* 0: the kernels need none */
+int mopk_gated_residual_fwd(const MopkGatedResidualArgs *a, void *stream);
+int mopk_gated_residual_bwd(const MopkGatedResidualArgs *a, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

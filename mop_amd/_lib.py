@@ -161,6 +161,24 @@ class TokenGateArgs(C.Structure):
     ]
 
 
+class MelGateArgs(C.Structure):
+    """MopkMelGateArgs: the MoP mel gate of every WhisperMoP encoder layer, folded to taps (L,k,F)."""
+    _fields_ = [
+        ("B", C.c_int32), ("T", C.c_int32), ("F", C.c_int32), ("L", C.c_int32), ("k", C.c_int32), ("mel_dtype", C.c_int32),
+        ("mel", _fp), ("mel_sb", C.c_int64), ("mel_st", C.c_int64), ("W", _fp), ("lens", _fp), ("gates", _fp), ("dgates", _fp),
+        ("dW", _fp), ("workspace", _fp),
+    ]
+
+
+class GatedResidualArgs(C.Structure):
+    """MopkGatedResidualArgs: (x + a) * gate[..., None] of the WhisperMoP encoder block."""
+    _fields_ = [
+        ("B", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("x_dtype", C.c_int32), ("a_dtype", C.c_int32), ("o_dtype", C.c_int32),
+        ("x", _fp), ("x_sb", C.c_int64), ("x_st", C.c_int64), ("a", _fp), ("a_sb", C.c_int64), ("a_st", C.c_int64),
+        ("gate", _fp), ("gate_sb", C.c_int64), ("out", _fp), ("dout", _fp), ("dr", _fp), ("dgate", _fp),
+    ]
+
+
 MOE_MAX_EXPERTS = 64
 
 
@@ -454,6 +472,14 @@ SYMBOLS = {
     "mopk_greedy_pick": (C.c_int, [C.POINTER(GreedyPickArgs), C.c_void_p]),
     "mopk_language_probs_supported": (C.c_int, [C.POINTER(LanguageProbsArgs)]),
     "mopk_language_probs": (C.c_int, [C.POINTER(LanguageProbsArgs), C.c_void_p]),
+    "mopk_mel_gate_supported": (C.c_int, [C.POINTER(MelGateArgs)]),
+    "mopk_mel_gate_workspace_bytes": (C.c_size_t, [C.POINTER(MelGateArgs)]),
+    "mopk_mel_gate_fwd": (C.c_int, [C.POINTER(MelGateArgs), C.c_void_p]),
+    "mopk_mel_gate_bwd": (C.c_int, [C.POINTER(MelGateArgs), C.c_void_p]),
+    "mopk_gated_residual_supported": (C.c_int, [C.POINTER(GatedResidualArgs)]),
+    "mopk_gated_residual_workspace_bytes": (C.c_size_t, [C.POINTER(GatedResidualArgs)]),
+    "mopk_gated_residual_fwd": (C.c_int, [C.POINTER(GatedResidualArgs), C.c_void_p]),
+    "mopk_gated_residual_bwd": (C.c_int, [C.POINTER(GatedResidualArgs), C.c_void_p]),
 }
 
 _lib = None

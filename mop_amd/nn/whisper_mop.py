@@ -4,8 +4,9 @@
 (plain SDPA: the causal flag and the additive bias for self-attention; rectangular SDPA with Nk = T_audio
 keys for cross-attention).  `EncoderBlock` (:241-264), `DecoderBlock` (:267-290), `WhisperMoP` (:296-424) and the factories
 `create_whisper_mop` / `create_whisper_baseline` (:427-437) follow the reference's constructors, forward signatures, return values,
-`state_dict` names and initialisation.  The mel-map gate `MoP2D` (:91-124, row a17), the LayerNorms, the MLP and the embeddings
-are stock PyTorch-ROCm layers.
+`state_dict` names and initialisation.  The mel-map gate `MoP2D` (:91-124, row a17) is linear in the mel map: the encoder folds
+all layers' gates into taps and computes them in one launch (`ops.mel_gate`), and every block applies its gate together with the
+residual add (`ops.gated_residual`).  The LayerNorms, the MLP and the embeddings are stock PyTorch-ROCm layers.
 """
 from __future__ import annotations
 
@@ -206,14 +207,37 @@ class FuseExcInh2D(nn.Module):
         return g[:, 0:1], g[:, 1:2], self.alpha[0], self.alpha[1]
 
 
+def _gate_dtype(mel: torch.Tensor) -> torch.dtype:
+    """the dtype MoP2D's convolutions give the gate of this mel: autocast's where it is on, else the mel's own"""
+    dev = mel.device.type
+    return torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else mel.dtype
+
+
+def _stacked_taps(mops, n_mels: int) -> torch.Tensor:
+    """ops.mel_gate_taps of several MoP2D modules at once -> (len(mops), k, n_mels)"""
+    return ops.mel_gate_taps(torch.stack([m.views.conv.weight for m in mops]), torch.stack([m.kernels.conv.weight for m in mops]),
+                             torch.stack([m.fuse.conv.weight for m in mops]), torch.stack([m.fuse.alpha for m in mops]), n_mels)
+
+
 class MoP2D(nn.Module):
-    """per-time-step gate 1 + a+ mean_F(g+) - a- mean_F(g-) from the raw mel map (reference :91-124)."""
+    """per-time-step gate 1 + a+ mean_F(g+) - a- mean_F(g-) from the raw mel map (reference :91-124).  The chain has no bias and
+    no non-linearity, so `gate` folds it into k x n_mels taps (`ops.mel_gate_taps`) and runs the gate alone on the HIP kernel
+    (`ops.mel_gate`); `forward` keeps the reference's convolutions for whoever wants the V / K maps."""
 
     def __init__(self, n_views: int, n_kernels: int, kernel_size: int):
         super().__init__()
         self.views = ViewsConv2D(n_views)
         self.kernels = Kernels2D(n_views, n_kernels, kernel_size)
         self.fuse = FuseExcInh2D(n_views + n_kernels)
+
+    def taps(self, n_mels: int) -> torch.Tensor:
+        """the gate folded into taps (1, k, n_mels) fp32 (ops.mel_gate_taps)"""
+        return _stacked_taps([self], n_mels)
+
+    def gate(self, mel2d: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """forward's gate_t (B,T,1) alone, without the maps: mel2d (B,1,T,F); lens: see ops.mel_gate"""
+        g = ops.mel_gate(mel2d[:, 0], self.taps(mel2d.shape[3]), lens)
+        return g.transpose(1, 2).to(_gate_dtype(mel2d))
 
     def forward(self, mel2d) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         V = self.views(mel2d)
@@ -307,12 +331,15 @@ class EncoderBlock(nn.Module):
         self.mlp = MLP(D, cfg.dropout, cfg.bias)
         self.mop = MoP2D(cfg.n_views, cfg.n_kernels, cfg.kernel_size)
 
-    def forward(self, x, mel2d, lens=None):
-        x = x + (self.attn(self.ln1(x)) if lens is None else self.attn(self.ln1(x), lens=lens))
-        gate_t, _, _ = self.mop(mel2d)
-        x = x * gate_t
+    def forward(self, x, mel2d, lens=None, gate_t=None):
+        """gate_t: this layer's gate (B,T) where the caller has it already (WhisperMoP computes all layers' in one launch);
+        None: the block computes its own from mel2d.  The residual add and the gate are one kernel (ops.gated_residual)."""
+        attn_out = self.attn(self.ln1(x)) if lens is None else self.attn(self.ln1(x), lens=lens)
+        if gate_t is None:
+            gate_t = self.mop.gate(mel2d, lens).squeeze(-1)
+        x = ops.gated_residual(x, attn_out, gate_t)
         x = x + self.mlp(self.ln2(x))
-        return x, gate_t.squeeze(-1)
+        return x, gate_t
 
 
 class DecoderBlock(nn.Module):
@@ -451,7 +478,7 @@ class WhisperMoP(nn.Module):
         mel may also be a list of B (T_b, n_mels) tensors, 1 <= T_b <= n_audio_ctx (clips of different lengths).  They are
         right-padded with zeros to T = max T_b; every encoder self-attention then runs with per-row lengths (ops.sdpa_core(q_lens,
         kv_lens): padding frames are neither queries nor keys), so item b comes out as it would alone.  Returns (EncodedAudio(out,
-        lens), gates): rows >= lens[b] of out and columns >= lens[b] of gates are unspecified.  A list of equal lengths runs the
+        lens), gates): rows >= lens[b] of out are unspecified, columns >= lens[b] of gates are 1.  A list of equal lengths runs the
         tensor path (lens None)."""
         alens = self._audio_check(mel, "encode")
         if alens is not None:
@@ -467,13 +494,17 @@ class WhisperMoP(nn.Module):
         if self.audio_pos is not None:
             x = x + self.audio_pos(self._pos(T_a, mel.device))
         x = self.drop(x)
-        mel2d = mel.unsqueeze(1).contiguous()                        # (B,1,T,F), as the reference's two transposes give
-        gate_layers = []
-        for blk in self.encoder:
-            x, gate_t = blk(x, mel2d) if audio_lens is None else blk(x, mel2d, audio_lens)
-            gate_layers.append(gate_t)
+        gates = self._gates(mel, audio_lens)                         # every layer's gate: they depend on the mel map alone
+        mel2d = mel.unsqueeze(1)                                     # (B,1,T,F), a view: the blocks are handed their gates
+        for blk, gate_t in zip(self.encoder, gates.unbind(1)):
+            x, _ = blk(x, mel2d, audio_lens, gate_t)
         x = self.enc_ln_f(x)
-        return x, torch.stack(gate_layers, dim=1)
+        return x, gates.to(_gate_dtype(mel))
+
+    def _gates(self, mel: torch.Tensor, audio_lens: Optional[torch.Tensor]) -> torch.Tensor:
+        """the encoder layers' mel gates (B, L_enc, T) fp32: one fold of all layers' MoP2D parameters (ops.mel_gate_taps) and
+        one ops.mel_gate launch; with audio_lens the columns >= audio_lens[b] are 1"""
+        return ops.mel_gate(mel, _stacked_taps([blk.mop for blk in self.encoder], mel.shape[2]), audio_lens)
 
     def decode(self, enc_out: torch.Tensor, dec_input_ids: torch.Tensor) -> torch.Tensor:
         """enc_out (B, T_audio, D) or an EncodedAudio, dec_input_ids (B, T_text) -> logits (B, T_text, vocab)."""
@@ -488,7 +519,7 @@ class WhisperMoP(nn.Module):
 
     def forward(self, mel: torch.Tensor, dec_input_ids: torch.Tensor, targets: Optional[torch.Tensor] = None):
         """mel: (B, T_audio, n_mels), or a list of B (T_b, n_mels) clips of different lengths (see encode): every item's logits
-        are then those of the item alone, and the gates' columns >= T_b are unspecified."""
+        are then those of the item alone, and the gates' columns >= T_b are 1."""
         alens = self._audio_check(mel, "forward")
         if alens is not None and dec_input_ids.shape[0] != len(alens):
             raise ValueError(f"forward: {dec_input_ids.shape[0]} rows of dec_input_ids for a batch of {len(alens)} mel inputs")
@@ -1830,10 +1861,11 @@ class WhisperMoP(nn.Module):
 
     @torch.no_grad()
     def get_gate_maps(self, mel: torch.Tensor):
-        """per-layer time gates of the encoder, (B, L_enc, T_audio); for a list of clips (see encode) the columns >= T_b of item b
-        are unspecified."""
-        _, gates = self.encode(mel)
-        return gates
+        """per-layer time gates of the encoder, (B, L_enc, T_audio), as encode returns them; for a list of clips (see encode) the
+        columns >= T_b of item b are 1.  The gates depend on the mel map alone, so the encoder is not run."""
+        mel, audio_lens = self._audio_pad(mel, self._audio_check(mel, "get_gate_maps"))
+        assert mel.shape[2] == self.cfg.n_mels, "mel dim mismatch"
+        return self._gates(mel, audio_lens).to(_gate_dtype(mel))
 
 
 class LogMelFrontend(nn.Module):

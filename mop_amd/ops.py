@@ -1588,6 +1588,168 @@ def token_gate_1d(x: torch.Tensor, a: Optional[torch.Tensor], u: torch.Tensor) -
     return _TokenGateFn.apply(x, a, u)
 
 
+# ---- MoP mel gate of the WhisperMoP encoder (mopk_mel_gate_*, mopk_gated_residual_*; reference mop/models/whisper_mop.py:91-124) ----
+# the two autograd Functions of this family are in mop_amd/mel_gate_fn.py (imported at the end of this file)
+def mel_gate_taps(Wv: torch.Tensor, Wk: torch.Tensor, Wf: torch.Tensor, alpha: torch.Tensor, n_mels: int) -> torch.Tensor:
+    """Fold the MoP2D chains of L encoder layers into taps W (L, k, n_mels), differentiable in all four parameters.
+
+    views = Wv mel ; K = conv2d(views, Wk, pad k//2) ; g = Wf [views ; K] ; gate = 1 + alpha0 mean_F g0 - alpha1 mean_F g1.  With
+    w = (alpha0, -alpha1) Wf, u[i,j] = sum_{kk,v} w[V+kk] Wk[kk,v,i,j] Wv[v] + [i = j = p] sum_v w[v] Wv[v] (p = k // 2) the chain is
+    one k x k stencil on the mel map, and its mean over frequency a stencil over time alone:
+    gate[t] = 1 + sum_{i,f} mel[t+i-p, f] W[i,f],  W[i,f] = (1/F) sum_{j : 0 <= f-(j-p) < F} u[i,j]  (the zero padding in frequency).
+    Wv (L,V,1,1) = views.conv.weight (the stacked conv weights' own (L,V,1,1,1) is taken too), Wk (L,K,V,k,k) = kernels.conv.weight, Wf (L,2,V+K,1,1) = fuse.conv.weight, alpha (L,2) =
+    fuse.alpha, each stacked over the layers: the number of launches does not grow with L.  fp32 (float64 for float64 parameters)."""
+    if Wv.dim() not in (4, 5) or Wk.dim() != 5 or Wf.dim() != 5 or alpha.dim() != 2:
+        raise ValueError(f"mel_gate_taps: expects Wv (L,V,1,1), Wk (L,K,V,k,k), Wf (L,2,V+K,1,1) and alpha (L,2), got "
+                         f"{tuple(Wv.shape)}, {tuple(Wk.shape)}, {tuple(Wf.shape)}, {tuple(alpha.shape)}")
+    Ln, V = Wv.shape[:2]
+    K, k = Wk.shape[1], Wk.shape[-1]
+    if (Wv.numel() != Ln * V or tuple(Wk.shape) != (Ln, K, V, k, k) or tuple(Wf.shape) != (Ln, 2, V + K, 1, 1)
+            or tuple(alpha.shape) != (Ln, 2) or int(n_mels) < 1):
+        raise ValueError(f"mel_gate_taps: inconsistent shapes Wv {tuple(Wv.shape)}, Wk {tuple(Wk.shape)}, Wf {tuple(Wf.shape)}, "
+                         f"alpha {tuple(alpha.shape)}, n_mels = {n_mels}")
+    with torch.autocast(device_type=Wv.device.type, enabled=False):
+        ct = torch.float64 if Wv.dtype == torch.float64 else torch.float32
+        Fm, p = int(n_mels), k // 2
+        wv = Wv.to(ct).reshape(Ln, V)
+        a = torch.stack((alpha[:, 0], -alpha[:, 1]), dim=1).to(ct)                     # (L,2)
+        w = torch.einsum("ls,lsc->lc", a, Wf.to(ct).reshape(Ln, 2, V + K))             # (L,V+K)
+        u = torch.einsum("lc,lcvij,lv->lij", w[:, V:], Wk.to(ct), wv)                  # (L,k,k)
+        j = torch.arange(k, device=Wv.device)
+        centre = ((j == p).unsqueeze(1) & (j == p).unsqueeze(0)).to(ct)
+        u = u + (w[:, :V] * wv).sum(dim=1).view(Ln, 1, 1) * centre
+        src = torch.arange(Fm, device=Wv.device).unsqueeze(0) - (j.unsqueeze(1) - p)   # (k,F): the bin f - (j - p) tap j reads from
+        inside = ((src >= 0) & (src < Fm)).to(ct) / Fm
+        return u @ inside                                                              # (L,k,F)
+
+
+def _mg_argcheck(mel: torch.Tensor, W: torch.Tensor, lens: Optional[torch.Tensor]) -> None:
+    if mel.dim() != 3 or W.dim() != 3 or W.shape[2] != mel.shape[2] or W.shape[0] < 1 or W.shape[1] < 1:
+        raise ValueError(f"mel_gate: expects mel (B,T,F) and taps W (L,k,F), got {tuple(mel.shape)} and {tuple(W.shape)}")
+    if not mel.dtype.is_floating_point or not W.dtype.is_floating_point:
+        raise ValueError(f"mel_gate: mel and W must be floating point, got {mel.dtype} and {W.dtype}")
+    if W.device != mel.device:
+        raise ValueError(f"mel_gate: W is on {W.device}, mel on {mel.device}")
+    if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (mel.shape[0],) or lens.device != mel.device):
+        raise ValueError(f"mel_gate: lens must be an int32 ({mel.shape[0]},) tensor on {mel.device}, got {lens.dtype} "
+                         f"{tuple(lens.shape)} on {lens.device}")
+
+
+def mel_gate_torch(mel: torch.Tensor, W: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the folded gates in torch ops (any device / dtype, differentiable in mel and W): gates (B,L,T) in the promotion of the two
+    dtypes.  Rows t >= lens[b] of mel are replaced by zeros (whatever they hold), columns t >= lens[b] of the gates are 1."""
+    _mg_argcheck(mel, W, lens)
+    B, T, Fm = mel.shape
+    k = W.shape[1]
+    p = k // 2
+    ct = torch.promote_types(mel.dtype, W.dtype)
+    m = mel.to(ct)
+    if lens is not None:
+        live = torch.arange(T, device=mel.device).unsqueeze(0) < lens.unsqueeze(1)     # (B,T)
+        m = torch.where(live.unsqueeze(-1), m, torch.zeros((), dtype=ct, device=mel.device))
+    win = F.pad(m, (0, 0, p, k - 1 - p)).unfold(1, k, 1)                               # (B,T,F,k): frames t-p .. t-p+k-1
+    gates = 1 + torch.einsum("btfi,lif->blt", win, W.to(ct))
+    if lens is not None:
+        gates = torch.where(live.unsqueeze(1), gates, torch.ones((), dtype=ct, device=mel.device))
+    return gates
+
+
+def _mg_args(mel: torch.Tensor, W: torch.Tensor, lens: Optional[torch.Tensor]) -> L.MelGateArgs:
+    B, T, Fm = mel.shape
+    g = L.MelGateArgs()
+    g.B, g.T, g.F, g.L, g.k = B, T, Fm, W.shape[0], W.shape[1]
+    g.mel_dtype = _io_dtype(mel)
+    g.mel, g.mel_sb, g.mel_st = mel.data_ptr(), (mel.stride(0) if B > 1 else 0), (mel.stride(1) if T > 1 else Fm)
+    g.lens = _ptr(lens)
+    return g
+
+
+def mel_gate_supported(mel: torch.Tensor, W: torch.Tensor, lens: Optional[torch.Tensor] = None) -> bool:
+    """True if mopk_mel_gate_* take this call: a GPU mel (B,T,F) in fp32 / bf16 that needs no gradient, innermost dimension
+    contiguous, fp32 taps (L,k,F) with an odd k <= 7 and F <= 128, lens None or a contiguous int32 (B,) (the library's own query)."""
+    if mel.dim() != 3 or W.dim() != 3 or not mel.is_cuda or not W.is_cuda or mel.numel() == 0 or W.numel() == 0:
+        return False
+    if mel.dtype not in (torch.float32, torch.bfloat16) or W.dtype != torch.float32 or mel.stride(-1) != 1:
+        return False
+    if W.shape[2] != mel.shape[2] or (mel.requires_grad and torch.is_grad_enabled()):
+        return False
+    if lens is not None and (not lens.is_cuda or lens.dtype != torch.int32 or lens.dim() != 1 or not lens.is_contiguous()):
+        return False
+    return bool(L.lib().mopk_mel_gate_supported(C.byref(_mg_args(mel, W, lens))))
+
+
+def mel_gate(mel: torch.Tensor, W: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gates (B,L,T) fp32 with gates[b,l,t] = 1 + sum_{i,f} mel[b,t+i-p,f] W[l,i,f] (p = k // 2, frames outside [0,T) are zero): the
+    MoP2D gates of all L encoder layers from one pass over the mel map, one HIP launch forward (per 8 layers) and two backward
+    (dW, bitwise reproducible; the parameters' gradients flow on through mel_gate_taps).  mel: (B,T,F); W: (L,k,F) from
+    mel_gate_taps; lens: None or int32 (B,) on the device: rows t >= lens[b] of mel are not read and count as zeros, columns
+    t >= lens[b] of the gates are exactly 1.  Calls the kernels do not take (mel_gate_supported: CPU tensors, float64, fp16, an
+    even k, a mel that requires grad) run mel_gate_torch; LAST_PATH["mel_gate_fwd"] records which (PATH_FUSED / PATH_GENERIC)."""
+    _mg_argcheck(mel, W, lens)
+    if not mel_gate_supported(mel, W, lens):
+        LAST_PATH["mel_gate_fwd"] = L.PATH_GENERIC
+        return mel_gate_torch(mel, W, lens)
+    return _mel_gate_fn._MelGateFn.apply(mel, W, lens)
+
+
+def _gr_argcheck(x: torch.Tensor, a: torch.Tensor, gate: torch.Tensor) -> None:
+    if x.dim() != 3 or a.shape != x.shape or tuple(gate.shape) != tuple(x.shape[:2]):
+        raise ValueError(f"gated_residual: expects x and a (B,T,D) and gate (B,T), got {tuple(x.shape)}, {tuple(a.shape)} and "
+                         f"{tuple(gate.shape)}")
+    if not (x.dtype.is_floating_point and a.dtype.is_floating_point and gate.dtype.is_floating_point):
+        raise ValueError(f"gated_residual: x, a and gate must be floating point, got {x.dtype}, {a.dtype} and {gate.dtype}")
+    if a.device != x.device or gate.device != x.device:
+        raise ValueError(f"gated_residual: x is on {x.device}, a on {a.device}, gate on {gate.device}")
+
+
+def gated_residual_torch(x: torch.Tensor, a: torch.Tensor, gate: torch.Tensor) -> torch.Tensor:
+    """(x + a) * gate[..., None] in torch ops (any device / dtype), in the promotion of x's and a's dtypes"""
+    _gr_argcheck(x, a, gate)
+    r = x + a
+    return (r * gate.unsqueeze(-1)).to(r.dtype)
+
+
+def _gr_args(x: torch.Tensor, a: torch.Tensor, gate: Optional[torch.Tensor]) -> L.GatedResidualArgs:
+    """gate: fp32 (B,T) with a contiguous last dimension; None (support query only): a contiguous one yet to be made"""
+    B, T, D = x.shape
+    g = L.GatedResidualArgs()
+    g.B, g.T, g.D = B, T, D
+    g.x_dtype, g.a_dtype = _io_dtype(x), _io_dtype(a)
+    g.x, g.x_sb, g.x_st = x.data_ptr(), (x.stride(0) if B > 1 else 0), (x.stride(1) if T > 1 else D)
+    g.a, g.a_sb, g.a_st = a.data_ptr(), (a.stride(0) if B > 1 else 0), (a.stride(1) if T > 1 else D)
+    g.gate, g.gate_sb = _ptr(gate), (gate.stride(0) if gate is not None and B > 1 else T)
+    g.o_dtype = L.MOPK_F32 if torch.float32 in (x.dtype, a.dtype) else L.MOPK_BF16
+    return g
+
+
+def gated_residual_supported(x: torch.Tensor, a: torch.Tensor, gate: torch.Tensor) -> bool:
+    """True if mopk_gated_residual_* take this call: GPU tensors, x and a (B,T,D) in fp32 / bf16 (mixed pairs included) with
+    D % 8 == 0, innermost dimension contiguous, row strides multiples of 8, 16-byte aligned data, gate (B,T) in fp32 / bf16 /
+    fp16 (the kernels read it as fp32) (the library's own query)."""
+    if any(not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 3 or t.stride(-1) != 1 for t in (x, a)):
+        return False
+    if a.shape != x.shape or x.numel() == 0 or not gate.is_cuda or tuple(gate.shape) != tuple(x.shape[:2]):
+        return False
+    if gate.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    as_is = gate.dtype == torch.float32 and gate.stride(-1) == 1                  # else gated_residual makes a fresh fp32 copy
+    return bool(L.lib().mopk_gated_residual_supported(C.byref(_gr_args(x, a, gate if as_is else None))))
+
+
+def gated_residual(x: torch.Tensor, a: torch.Tensor, gate: torch.Tensor) -> torch.Tensor:
+    """out = (x + a) * gate[..., None]: the WhisperMoP encoder block's residual add and mel gate as one HIP kernel, and
+    dr = dout * gate, dgate = sum_d dout (x + a) as one more.  x, a: (B,T,D); gate: (B,T).  Output dtype: the promotion of x and
+    a.  Calls the kernels do not take (gated_residual_supported) run gated_residual_torch; LAST_PATH["gated_residual_fwd"]
+    records which (PATH_FUSED / PATH_GENERIC)."""
+    _gr_argcheck(x, a, gate)
+    if not gated_residual_supported(x, a, gate):
+        LAST_PATH["gated_residual_fwd"] = L.PATH_GENERIC
+        return gated_residual_torch(x, a, gate)
+    if gate.dtype != torch.float32 or gate.stride(-1) != 1:
+        gate = gate.to(torch.float32).contiguous()
+    return _mel_gate_fn._GatedResidualFn.apply(x, a, gate)
+
+
 # ---- top-1 routed MoE MLP (mopk_moe_*; reference mop/models/components.py:84-121 MoEMLP) ----
 def moe_mlp_torch(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.Tensor], w1s, w2s,
                   residual: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -4390,3 +4552,6 @@ def log_mel(audio: torch.Tensor, filters: torch.Tensor, n_fft: int = 400, hop_le
         a.out = out.data_ptr()                                                     # in place of the stand-in
         _row_launch(a, "mopk_log_mel", "log_mel", audio.device, "mopk_log_mel_workspace_bytes")
         return out
+
+
+from . import mel_gate_fn as _mel_gate_fn  # noqa: E402  (it reads this module's helpers, all defined by now)
