@@ -261,8 +261,11 @@ def test_shapes_outside_the_fused_kernels_take_the_generic_path():
     m3(x3).sum().backward()
     assert ops.LAST_PATH["edgewise_fwd"] == ops.LAST_PATH["edgewise_bwd"] == _lib.PATH_GENERIC
     m2 = _mk(96, 2, 3, 2, seed=6).cuda().eval()                           # dk = 48
-    m2(torch.randn(1, 16, 96, device="cuda"))
-    assert ops.LAST_PATH["edgewise_fwd"] == _lib.PATH_GENERIC
+    ops.LAST_PATH.pop("edgewise_bwd", None)
+    x2 = torch.randn(1, 16, 96, device="cuda", requires_grad=True)         # (the numbers: tests/test_gpu_generic_head_sizes.py)
+    m2(x2).sum().backward()
+    assert ops.LAST_PATH["edgewise_fwd"] == _lib.PATH_GENERIC and ops.LAST_PATH["edgewise_bwd"] == _lib.PATH_GENERIC
+    assert torch.isfinite(x2.grad).all()
 
 
 @pytest.fixture(scope="module")
