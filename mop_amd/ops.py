@@ -804,16 +804,24 @@ def _heads_view(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
+def _bcast_keys(t: torch.Tensor, B, H, N, Nk) -> torch.Tensor:
+    """t, broadcastable to (B,H,N,Nk), as the (B,H,N,Nk) view the kernels index: element (b,h,i,j) at b*sb + h*sh + i*si + j, so the
+    key axis has stride 1.  B, H and N stay broadcast by stride 0; a key axis of extent 1 is the one axis written out (Nk copies of
+    what t holds, no more), since a stride-0 key axis would make the kernels read t[i + j]."""
+    while t.dim() < 4:
+        t = t.unsqueeze(0)
+    t = t.contiguous()
+    if t.shape[3] == 1 and Nk > 1:
+        t = t.expand(-1, -1, -1, Nk).contiguous()
+    return t.expand(B, H, N, Nk)
+
+
 def _mask_u8(attn_mask, B, H, N, dev, Nk=None):
     """reference convention: broadcastable to (B,H,N,Nk) (Nk = N unless given), 0 = blocked (attention_variants.py:43-44)."""
     if attn_mask is None:
         return None, (0, 0, 0)
     Nk = N if Nk is None else Nk
-    m = (attn_mask.to(dev) != 0).to(torch.uint8)
-    while m.dim() < 4:
-        m = m.unsqueeze(0)
-    m = m.contiguous().expand(B, H, N, Nk)
-    assert m.stride(3) == 1 or Nk == 1
+    m = _bcast_keys((attn_mask.to(dev) != 0).to(torch.uint8), B, H, N, Nk)
     return m, (m.stride(0), m.stride(1), m.stride(2))
 
 
@@ -828,10 +836,7 @@ def _bias_f32(bias, B, H, N, dev, Nk=None):
     if bias is None:
         return None, (0, 0, 0)
     Nk = N if Nk is None else Nk
-    b = bias.to(dev, torch.float32)
-    while b.dim() < 4:
-        b = b.unsqueeze(0)
-    b = b.contiguous().expand(B, H, N, Nk)
+    b = _bcast_keys(bias.to(dev, torch.float32), B, H, N, Nk)
     return b, (b.stride(0), b.stride(1), b.stride(2))
 
 
@@ -1027,7 +1032,8 @@ def sdpa_core(q, k=None, v=None, attn_mask=None, bias=None, causal=False, dropou
               q_lens=None, kv_lens=None):
     """q: (B,N,H,dk), k, v: (B,Nk,H,dk) views -- Nk != N is rectangular (cross-)attention: N queries attend to Nk keys -- or packed:
     q = the (B,N,3,H,dk) output of one qkv projection, k = v = None (square; one packed gradient comes back).  Returns (B,N,H*dk).
-    attn_mask: 0 = blocked; bias: additive; both broadcastable to (B,H,N,Nk).  causal needs Nk == N (ValueError otherwise).
+    attn_mask: 0 = blocked; bias: additive; both broadcastable to (B,H,N,Nk) along any axis, the key axis included (a (N,1) bias, a
+    (B,1,N,1) per-query mask; 0-d to 4-d, contiguous or not).  causal needs Nk == N (ValueError otherwise).
     A row with no open key (every key blocked, or a bias of -inf at every key) is 0, as in torch's SDPA.  bias gets no gradient:
     one that requires grad under grad mode raises NotImplementedError.
     dropout_p > 0: the probabilities are multiplied by keep / (1 - p) (mask = `dropout_keep_mask(seed, B, H, N, Nk)`, seed drawn
@@ -1403,6 +1409,8 @@ class _QuartetFn(torch.autograd.Function):
 @_half_via_fp32
 def quartet_core(q, k, v, q2, k2, mixture, quartet_scale, add_mask, eps, use_quartet, need_weights=False,
                  dropout_p: float = 0.0, seed: Optional[int] = None):
+    """q, k, v (and q2, k2 with use_quartet): (B,T,H,dk) views.  Returns (B,T,H*dk), and the (B,H,T,T) float32 weights with
+    need_weights.  add_mask: additive, broadcastable to (B,H,T,T) along any axis, the key axis included; it gets no gradient."""
     _refuse_bias_grad(add_mask, "quartet_core: add_mask")      # add_mask gets no gradient
     if q.shape[0] == 0:                   # q: (B,T,H,dk)
         out = _empty_batch(q, 0, q.shape[1], q.shape[2] * q.shape[3])
