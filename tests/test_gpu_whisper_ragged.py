@@ -11,8 +11,8 @@ import sys
 import pytest
 import torch
 
+from sample_rows import _perturbed
 from test_gpu_whisper_beam import _model
-from test_gpu_whisper_sample import _perturbed
 from test_whisper_ragged_cpu import naive_ragged_attention
 
 pytestmark = pytest.mark.gpu

@@ -10,29 +10,12 @@ import sys
 import pytest
 import torch
 
+from sample_rows import _perturbed, _z
 from test_gpu_whisper_beam import _model
 
 pytestmark = pytest.mark.gpu
 NEG = float("-inf")
 CHI2_1E6 = [23.93, 27.63, 30.66, 33.38, 35.89, 38.26, 40.52, 42.7, 44.81, 46.86, 48.87]     # chi2.isf(1e-6, df), df = 1 .. 11
-
-
-def _z(x, temperature):
-    from mop_amd import ops
-    return x.float() * torch.tensor(ops._f32(1.0 / temperature), device=x.device)
-
-
-def _perturbed(x, pos, temperature, seed):
-    """z + G of every (row, v), the torch path's own noise"""
-    from mop_amd import ops
-    R, V = x.shape
-    s = seed & 0xFFFFFFFFFFFFFFFF
-    r = torch.arange(R, device=x.device, dtype=torch.int64).unsqueeze(1)
-    rh = ops._hash32(ops._hash32((s & ops._M32) ^ ops._mul32(r, 0x9E3779B1)) ^ (s >> 32) ^ ops._mul32(
-        torch.full((1, 1), pos, dtype=torch.int64, device=x.device), 0x85EBCA77))
-    h = ops._hash32(rh ^ ops._mul32(torch.arange(V, device=x.device, dtype=torch.int64).unsqueeze(0), 0xC2B2AE3D))
-    u = ((h >> 9).to(torch.float32) + 0.5) * 2.0 ** -23
-    return _z(x, temperature) + -torch.log(-torch.log(u))
 
 
 def _kept64(x, temperature, top_k, top_p):
