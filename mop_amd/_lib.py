@@ -119,7 +119,6 @@ class SdpaLensArgs(C.Structure):
     _fields_ = [("base", SdpaArgs), ("q_lens", _fp), ("kv_lens", _fp)]
 
 
-# every symbol include/mopk.h declares: name -> (restype, argtypes)
 class CrossViewArgs(C.Structure):
     _fields_ = [
         ("B", C.c_int32), ("H", C.c_int32), ("N", C.c_int32), ("dk", C.c_int32),
@@ -369,6 +368,7 @@ LOG_MEL_TILE_FRAMES = 32   # MOPK_LOG_MEL_TILE_FRAMES
 LOG_MEL_F16 = 2            # MOPK_LOG_MEL_F16
 
 
+# every symbol include/mopk.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mopk_version": (C.c_int, []),
     "mopk_strerror": (C.c_char_p, [C.c_int]),

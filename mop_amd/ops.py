@@ -840,8 +840,38 @@ def _bias_f32(bias, B, H, N, dev, Nk=None):
     return b, (b.stride(0), b.stride(1), b.stride(2))
 
 
-def _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop) -> L.SdpaArgs:
-    """the MopkSdpaArgs fields forward and backward share; mask / bias: (tensor or None, strides) from _mask_u8 / _bias_f32"""
+_CORE_OPS = {   # core -> (export stem, support query that resolves PATH_AUTO, LAST_PATH / timing stem, directions LAST_PATH records)
+    "sdpa": ("mopk_sdpa", "mopk_sdpa_fused_supported", "sdpa", ("fwd", "bwd")),
+    "sdpa_lens": ("mopk_sdpa_lens", "mopk_sdpa_lens_supported", "sdpa", ("fwd", "bwd")),
+    "dualpath": ("mopk_dualpath", "mopk_dualpath_fused_supported", "dualpath", ("fwd", "bwd")),
+    "quartet": ("mopk_quartet", "mopk_quartet_fused_supported", "quartet", ("fwd",)),
+    "crossview": ("mopk_crossview", None, "crossview", ()),       # one path; crossview_core* record it
+}
+
+
+def _core_launch(core: str, a, dev, saved: Optional[torch.Tensor] = None):
+    """the tail these cores share, on the args struct `a` (or the one it wraps as .base); forward when `saved` is None, else the
+    backward on the forward's `saved`.  Forward: PATH_AUTO is resolved first, so that forward, backward and the size queries agree,
+    and `saved` is sized and allocated.  Both: LAST_PATH in the directions `recorded` names, the workspace, the two pointers into
+    the struct, the launch (timed under stem_fwd / stem_bwd).  Returns (saved, the resolved path)."""
+    stem, query, key, recorded = _CORE_OPS[core]
+    lib, base, d = L.lib(), getattr(a, "base", a), ("fwd" if saved is None else "bwd")
+    if saved is None and base.path == L.PATH_AUTO:
+        base.path = L.PATH_FUSED if getattr(lib, query)(C.byref(a)) else L.PATH_GENERIC
+    path = base.path
+    if d in recorded:
+        LAST_PATH[f"{key}_{d}"] = path
+    if saved is None:
+        saved = _bytes(getattr(lib, stem + "_saved_bytes")(C.byref(a)), dev)
+    ws = _bytes(getattr(lib, stem + "_workspace_bytes")(C.byref(a)), dev)
+    base.saved, base.workspace = saved.data_ptr(), ws.data_ptr()
+    _launch(f"{stem}_{d}", a, f"{key}_{d}")
+    return saved, path
+
+
+def _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop, lens=None):
+    """the MopkSdpaArgs fields forward and backward share; mask / bias: (tensor or None, strides) from _mask_u8 / _bias_f32.
+    lens: (q_lens or None, kv_lens or None), int32 (B,) device tensors -> the MopkSdpaLensArgs that wraps them"""
     B, N, H, dk = q.shape
     a = L.SdpaArgs()
     a.B, a.H, a.N, a.dk, a.Nk = B, H, N, dk, k.shape[1]
@@ -850,72 +880,62 @@ def _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop) -> L.SdpaArgs:
     a.mask, (a.mask_sb, a.mask_sh, a.mask_si) = _ptr(mask[0]), mask[1]
     a.bias, (a.bias_sb, a.bias_sh, a.bias_si) = _ptr(bias[0]), bias[1]
     a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
-    return a
+    return a if lens is None else L.SdpaLensArgs(base=a, q_lens=_ptr(lens[0]), kv_lens=_ptr(lens[1]))
+
+
+def _sdpa_fwd(ctx, q, k, v, mask, bias, lens, causal, prec, path, drop):
+    """the forward of _SdpaFn (lens None) and _SdpaLensFn (mask = bias = None)"""
+    _require_gpu(q, "SDPA")
+    # packed form: q is the (B,N,3,H,dk) output of one qkv projection and k = v = None.  The kernels read the three strided views and
+    # the backward writes ONE packed gradient -- autograd then has no per-view zero-fill + copy + add to assemble it from three
+    ctx.packed = k is None
+    if ctx.packed:
+        q, k, v = q.contiguous().unbind(2)
+    q, k, v = _heads_view(q), _heads_view(k), _heads_view(v)
+    B, N, H, dk = q.shape
+    Nk = k.shape[1]                # key / value length (cross-attention); N for self-attention
+    dev = q.device
+    mask, bias = _mask_u8(mask, B, H, N, dev, Nk), _bias_f32(bias, B, H, N, dev, Nk)
+    y = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
+    a = _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop, lens)
+    saved, path = _core_launch("sdpa" if lens is None else "sdpa_lens", a, dev)
+    ctx.save_for_backward(q, k, v, y, saved)
+    ctx.meta = (mask, bias, causal, prec, path, drop, lens)
+    return y.view(B, N, H * dk)
+
+
+def _sdpa_bwd(ctx, saved_tensors, dy):
+    """the backward of both on dy as _grad_in returns it, (B,N,H,dk): one packed gradient or three, Nk rows for keys and values"""
+    q, k, v, y, saved = saved_tensors
+    B, N, H, dk = q.shape
+    Nk = k.shape[1]
+    dev = q.device
+    a = _sdpa_args(q, k, v, y, *ctx.meta)
+    base = getattr(a, "base", a)
+    base.dy = _v4(dy)
+    if ctx.packed:
+        dqkv = torch.empty(B, N, 3, H, dk, dtype=q.dtype, device=dev)
+        dq, dk_, dv = dqkv.unbind(2)
+    else:
+        dq = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
+        dk_, dv = (torch.empty(B, Nk, H, dk, dtype=q.dtype, device=dev) for _ in range(2))
+    base.dq, base.dk_, base.dv = _v4(dq), _v4(dk_), _v4(dv)
+    _core_launch("sdpa" if base is a else "sdpa_lens", a, dev, saved)
+    if ctx.packed:
+        return dqkv, None, None, None, None, None, None, None, None
+    return dq, dk_, dv, None, None, None, None, None, None
 
 
 class _SdpaFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, mask, bias, causal, prec, path, drop=(0.0, 0)):
-        _require_gpu(q, "SDPA")
-        lib = L.lib()
-        # packed form: q is the (B,N,3,H,dk) output of one qkv projection and k = v = None.  The kernels read the three strided views and
-        # the backward writes ONE packed gradient -- autograd then has no per-view zero-fill + copy + add to assemble it from three
-        ctx.packed = k is None
-        if ctx.packed:
-            q, k, v = q.contiguous().unbind(2)
-        q, k, v = _heads_view(q), _heads_view(k), _heads_view(v)
-        B, N, H, dk = q.shape
-        Nk = k.shape[1]                # key / value length (cross-attention); N for self-attention
-        dev = q.device
-        mask, bias = _mask_u8(mask, B, H, N, dev, Nk), _bias_f32(bias, B, H, N, dev, Nk)
-        y = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
-        a = _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop)
-        if path == L.PATH_AUTO:       # resolve once so forward, backward and the size queries agree
-            path = L.PATH_FUSED if lib.mopk_sdpa_fused_supported(C.byref(a)) else L.PATH_GENERIC
-            a.path = path
-        LAST_PATH["sdpa_fwd"] = path
-        saved = _bytes(lib.mopk_sdpa_saved_bytes(C.byref(a)), dev)
-        ws = _bytes(lib.mopk_sdpa_workspace_bytes(C.byref(a)), dev)
-        a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        _launch("mopk_sdpa_fwd", a, "sdpa_fwd")
-        ctx.save_for_backward(q, k, v, y, saved)
-        ctx.meta = (causal, prec, path, mask, bias, drop)
-        return y.view(B, N, H * dk)
+        return _sdpa_fwd(ctx, q, k, v, mask, bias, None, causal, prec, path, drop)
 
     @staticmethod
     @_once_differentiable
     def backward(ctx, dy):
-        lib = L.lib()
-        q, k, v, y, saved = ctx.saved_tensors
-        causal, prec, path, mask, bias, drop = ctx.meta
-        B, N, H, dk = q.shape
-        Nk = k.shape[1]
-        dev = q.device
-        dy = _grad_in(dy, q.dtype, (B, N, H, dk))
-        a = _sdpa_args(q, k, v, y, mask, bias, causal, prec, path, drop)
-        a.dy = _v4(dy)
-        if ctx.packed:
-            dqkv = torch.empty(B, N, 3, H, dk, dtype=q.dtype, device=dev)
-            dq, dk_, dv = dqkv.unbind(2)
-        else:
-            dq = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
-            dk_, dv = (torch.empty(B, Nk, H, dk, dtype=q.dtype, device=dev) for _ in range(2))
-        a.dq, a.dk_, a.dv = _v4(dq), _v4(dk_), _v4(dv)
-        LAST_PATH["sdpa_bwd"] = path
-        ws = _bytes(lib.mopk_sdpa_workspace_bytes(C.byref(a)), dev)
-        a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        _launch("mopk_sdpa_bwd", a, "sdpa_bwd")
-        if ctx.packed:
-            return dqkv, None, None, None, None, None, None, None, None
-        return dq, dk_, dv, None, None, None, None, None, None
-
-
-def _sdpa_lens_args(q, k, v, y, lens, causal, prec, path, drop) -> L.SdpaLensArgs:
-    """the MopkSdpaLensArgs fields forward and backward share; lens: (q_lens or None, kv_lens or None), int32 (B,) device tensors"""
-    a = L.SdpaLensArgs()
-    a.base = _sdpa_args(q, k, v, y, (None, (0, 0, 0)), (None, (0, 0, 0)), causal, prec, path, drop)
-    a.q_lens, a.kv_lens = _ptr(lens[0]), _ptr(lens[1])
-    return a
+        ts = ctx.saved_tensors
+        return _sdpa_bwd(ctx, ts, _grad_in(dy, ts[0].dtype, ts[0].shape))
 
 
 class _SdpaLensFn(torch.autograd.Function):
@@ -923,55 +943,13 @@ class _SdpaLensFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, q_lens, kv_lens, causal, prec, path, drop=(0.0, 0)):
-        _require_gpu(q, "SDPA")
-        lib = L.lib()
-        ctx.packed = k is None                     # packed (B,N,3,H,dk) projection, as in _SdpaFn
-        if ctx.packed:
-            q, k, v = q.contiguous().unbind(2)
-        q, k, v = _heads_view(q), _heads_view(k), _heads_view(v)
-        B, N, H, dk = q.shape
-        dev = q.device
-        lens = (q_lens, kv_lens)
-        y = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
-        a = _sdpa_lens_args(q, k, v, y, lens, causal, prec, path, drop)
-        if path == L.PATH_AUTO:       # resolve once so forward, backward and the size queries agree
-            path = L.PATH_FUSED if lib.mopk_sdpa_lens_supported(C.byref(a)) else L.PATH_GENERIC
-            a.base.path = path
-        LAST_PATH["sdpa_fwd"] = path
-        saved = _bytes(lib.mopk_sdpa_lens_saved_bytes(C.byref(a)), dev)
-        ws = _bytes(lib.mopk_sdpa_lens_workspace_bytes(C.byref(a)), dev)
-        a.base.saved, a.base.workspace = saved.data_ptr(), ws.data_ptr()
-        _launch("mopk_sdpa_lens_fwd", a, "sdpa_fwd")
-        ctx.save_for_backward(q, k, v, y, saved)
-        ctx.meta = (causal, prec, path, lens, drop)
-        return y.view(B, N, H * dk)
+        return _sdpa_fwd(ctx, q, k, v, None, None, (q_lens, kv_lens), causal, prec, path, drop)
 
     @staticmethod
     @_once_differentiable
     def backward(ctx, dy):
-        lib = L.lib()
-        q, k, v, y, saved = ctx.saved_tensors
-        causal, prec, path, lens, drop = ctx.meta
-        B, N, H, dk = q.shape
-        Nk = k.shape[1]
-        dev = q.device
-        dy = _grad_in(dy, q.dtype, (B, N, H, dk))
-        a = _sdpa_lens_args(q, k, v, y, lens, causal, prec, path, drop)
-        a.base.dy = _v4(dy)
-        if ctx.packed:
-            dqkv = torch.empty(B, N, 3, H, dk, dtype=q.dtype, device=dev)
-            dq, dk_, dv = dqkv.unbind(2)
-        else:
-            dq = torch.empty(B, N, H, dk, dtype=q.dtype, device=dev)
-            dk_, dv = (torch.empty(B, Nk, H, dk, dtype=q.dtype, device=dev) for _ in range(2))
-        a.base.dq, a.base.dk_, a.base.dv = _v4(dq), _v4(dk_), _v4(dv)
-        LAST_PATH["sdpa_bwd"] = path
-        ws = _bytes(lib.mopk_sdpa_lens_workspace_bytes(C.byref(a)), dev)
-        a.base.saved, a.base.workspace = saved.data_ptr(), ws.data_ptr()
-        _launch("mopk_sdpa_lens_bwd", a, "sdpa_bwd")
-        if ctx.packed:
-            return dqkv, None, None, None, None, None, None, None, None
-        return dq, dk_, dv, None, None, None, None, None, None
+        ts = ctx.saved_tensors
+        return _sdpa_bwd(ctx, ts, _grad_in(dy, ts[0].dtype, ts[0].shape))
 
 
 def _check_lens(t, B: int, dev, what: str) -> None:
@@ -1097,7 +1075,6 @@ class _CrossViewFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q1, k1, v1, q2, k2, mix, cfg, mask, causal, prec, drop=(0.0, 0)):
         _require_gpu(q1, "CrossViewMixerMSA")
-        lib = L.lib()
         ts = [_heads_view(t) for t in (q1, k1, v1, q2, k2)]
         B, N, H, dk = ts[0].shape
         dev = ts[0].device
@@ -1107,10 +1084,7 @@ class _CrossViewFn(torch.autograd.Function):
         a = _cv_args(ts, mx, y, cfg, mask, causal, prec, drop)
         kst = torch.zeros(B, H, dtype=torch.int32, device=dev)
         a.k_star = kst.data_ptr()
-        saved = _bytes(lib.mopk_crossview_saved_bytes(C.byref(a)), dev)
-        ws = _bytes(lib.mopk_crossview_workspace_bytes(C.byref(a)), dev)
-        a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        _launch("mopk_crossview_fwd", a, "crossview_fwd")
+        saved, _ = _core_launch("crossview", a, dev)
         LAST_PATH["crossview_k_star"] = kst
         ctx.save_for_backward(*ts, mx, saved)
         ctx.meta = (cfg, causal, prec, mask, drop)
@@ -1119,7 +1093,6 @@ class _CrossViewFn(torch.autograd.Function):
     @staticmethod
     @_once_differentiable
     def backward(ctx, dy):
-        lib = L.lib()
         *ts, mx, saved = ctx.saved_tensors
         cfg, causal, prec, mask, drop = ctx.meta
         B, N, H, dk = ts[0].shape
@@ -1131,9 +1104,7 @@ class _CrossViewFn(torch.autograd.Function):
         a.dq1, a.dk1, a.dv1, a.dq2, a.dk2 = (_v4(t) for t in outs)
         dmix = torch.empty(B, H, 4, dtype=torch.float32, device=dev)
         a.dmix_part = dmix.data_ptr()
-        ws = _bytes(lib.mopk_crossview_workspace_bytes(C.byref(a)), dev)
-        a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        _launch("mopk_crossview_bwd", a, "crossview_bwd")
+        _core_launch("crossview", a, dev, saved)
         return (*outs, dmix.sum((0, 1)).view(2, 2), None, None, None, None, None)
 
 
@@ -1204,20 +1175,11 @@ def _dp_args(ts, lg, y, gates, beta_not, hops, mask, causal, prec, path, drop) -
 
 def _dp_fwd(ts, lg, gates, beta_not, hops, mask, causal, prec, path, drop):
     """one mopk_dualpath_fwd call on six (B,N,H,dk) views -> (y (B,N,H,dk), saved, resolved path)"""
-    lib = L.lib()
     B, N, H, dk = ts[0].shape
     dev = ts[0].device
     y = torch.empty(B, N, H, dk, dtype=ts[0].dtype, device=dev)
     a = _dp_args(ts, lg, y, gates, beta_not, hops, mask, causal, prec, path, drop)
-    if path == L.PATH_AUTO:
-        path = L.PATH_FUSED if lib.mopk_dualpath_fused_supported(C.byref(a)) else L.PATH_GENERIC
-        a.path = path
-    LAST_PATH["dualpath_fwd"] = path
-    saved = _bytes(lib.mopk_dualpath_saved_bytes(C.byref(a)), dev)
-    ws = _bytes(lib.mopk_dualpath_workspace_bytes(C.byref(a)), dev)
-    a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-    _launch("mopk_dualpath_fwd", a, "dualpath_fwd")
-    return y, saved, path
+    return (y, *_core_launch("dualpath", a, dev))
 
 
 def _dp_bwd(ts, lg, y, saved, dy, gs, gates, beta_not, hops, mask, causal, prec, path, drop):
@@ -1229,10 +1191,7 @@ def _dp_bwd(ts, lg, y, saved, dy, gs, gates, beta_not, hops, mask, causal, prec,
     a.dq1, a.dk1, a.dv1, a.dq2, a.dk2, a.dv2 = (_v4(g) for g in gs)
     dlg = torch.empty(B, H, dtype=torch.float32, device=dev)
     a.dlogit_part = dlg.data_ptr()
-    LAST_PATH["dualpath_bwd"] = path
-    ws = _bytes(L.lib().mopk_dualpath_workspace_bytes(C.byref(a)), dev)
-    a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-    _launch("mopk_dualpath_bwd", a, "dualpath_bwd")
+    _core_launch("dualpath", a, dev, saved)
     return dlg
 
 
@@ -1350,7 +1309,6 @@ class _QuartetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, q2, k2, mixture, qscale, add_mask, eps, use_quartet, need_weights, prec, path, drop=(0.0, 0)):
         _require_gpu(q, "CausalSelfAttention")
-        lib = L.lib()
         ts = [_heads_view(t) for t in ((q, k, v, q2, k2) if use_quartet else (q, k, v))]
         B, T, H, dh = ts[0].shape
         dev = ts[0].device
@@ -1360,14 +1318,7 @@ class _QuartetFn(torch.autograd.Function):
         a = _qt_args(ts, sc, y, am, eps, prec, path, drop)
         attn = torch.empty(B, H, T, T, dtype=torch.float32, device=dev) if need_weights else None
         a.attn = _ptr(attn)
-        if path == L.PATH_AUTO:
-            path = L.PATH_FUSED if lib.mopk_quartet_fused_supported(C.byref(a)) else L.PATH_GENERIC
-            a.path = path
-        LAST_PATH["quartet_fwd"] = path
-        saved = _bytes(lib.mopk_quartet_saved_bytes(C.byref(a)), dev)
-        ws = _bytes(lib.mopk_quartet_workspace_bytes(C.byref(a)), dev)
-        a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        _launch("mopk_quartet_fwd", a, "quartet_fwd")
+        saved, path = _core_launch("quartet", a, dev)
         ctx.save_for_backward(*ts, *sc, y, saved)
         ctx.meta = (eps, use_quartet, prec, path, am, drop)
         out = y.view(B, T, H * dh)
@@ -1379,7 +1330,6 @@ class _QuartetFn(torch.autograd.Function):
     @staticmethod
     @_once_differentiable
     def backward(ctx, dy, *unused):
-        lib = L.lib()
         eps, use_quartet, prec, path, am, drop = ctx.meta
         n = 5 if use_quartet else 3
         *ts, y, saved = ctx.saved_tensors
@@ -1397,9 +1347,7 @@ class _QuartetFn(torch.autograd.Function):
             dmix = torch.empty(B, H, dtype=torch.float32, device=dev)
             dqs = torch.empty(B, H, dtype=torch.float32, device=dev)
             a.dmixture_part, a.dqscale_part = dmix.data_ptr(), dqs.data_ptr()
-        ws = _bytes(lib.mopk_quartet_workspace_bytes(C.byref(a)), dev)
-        a.saved, a.workspace = saved.data_ptr(), ws.data_ptr()
-        _launch("mopk_quartet_bwd", a, "quartet_bwd")
+        _core_launch("quartet", a, dev, saved)
         if use_quartet:
             return (gs[0], gs[1], gs[2], gs[3], gs[4], dmix.sum().reshape(1), dqs.sum().reshape(1),
                     None, None, None, None, None, None, None)

@@ -1,17 +1,14 @@
 """CPU checks of the top-1 MoE MLP line (no GPU): the reference's constructor signatures and defaults, state_dict layouts against
-the `moe_*` / `moevit_*` fixtures, ViT_MoP(use_moe=True) construction, MopkMoeArgs against gcc, the support query and bad-argument
+the `moe_*` / `moevit_*` fixtures, ViT_MoP(use_moe=True) construction, the support query and bad-argument
 returns of mopk_moe_*, and the no-CPU-fallback error."""
 import ctypes as C
 import inspect
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, golden_names, load_golden
+from conftest import golden_names, load_golden
 
 MOE_FIXTURES = golden_names("moe_") + golden_names("moevit_")
 
@@ -107,25 +104,6 @@ def test_cpu_tensor_raises_no_cpu_fallback():
     from mop_amd import ops
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.moe_route(torch.randn(4, 16), m.gate.weight, m.gate.bias)
-
-
-def test_moe_args_size_matches_gcc():
-    from mop_amd import _lib
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "mopk.h"
-int main(void){printf("%zu %zu %zu %zu %d\n", sizeof(MopkMoeArgs), offsetof(MopkMoeArgs, w1), offsetof(MopkMoeArgs, dw2),
- offsetof(MopkMoeArgs, workspace), MOPK_MOE_MAX_EXPERTS);return 0;}
-'''
-    with tempfile.TemporaryDirectory() as td:
-        cpath = os.path.join(td, "s.c")
-        open(cpath, "w").write(prog)
-        exe = os.path.join(td, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), cpath, "-o", exe])
-        got = list(map(int, subprocess.check_output([exe]).split()))
-    A = _lib.MoeArgs
-    assert got == [C.sizeof(A), A.w1.offset, A.dw2.offset, A.workspace.offset, _lib.MOE_MAX_EXPERTS]
 
 
 def _args(M=64, D=64, F=256, E=4, prec=1):

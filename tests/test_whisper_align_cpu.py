@@ -1,7 +1,7 @@
 """CPU checks of token-level timestamps (no GPU): ops.dtw_align_torch against a per-item double loop written here (Whisper's dtw_cpu
 rules in numpy float32, no call into ops; starts / ends must be equal) and on a planted staircase whose optimum is unique;
 ops.alignment_cost_torch against a float64 per-item restatement written here (numpy.median over an explicitly reflect-padded row);
-every ValueError; MopkAlignCostArgs and MopkDtwArgs against gcc; the support and workspace queries without a GPU; and
+every ValueError; the support and workspace queries without a GPU; and
 WhisperMoP.align_tokens with every core on its torch composition."""
 import ctypes as C
 
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from test_whisper_audio_lens_cpu import torch_cores  # noqa: F401  (a fixture: every core on its torch composition, lengths included)
-from test_whisper_beam_cpu import _gcc, _tiny_model
+from test_whisper_beam_cpu import _tiny_model
 
 NAN = float("nan")
 DTW_SHAPES = [(1, 1), (1, 9), (9, 1), (5, 5), (7, 3), (65, 130)]          # (N, M); (7, 3): more tokens than frames
@@ -249,22 +249,6 @@ def test_value_errors():
                     lambda: f(c, nt.float(), nf), lambda: f(c, nt, None)):
             with pytest.raises(ValueError):
                 bad()
-
-
-def test_args_layouts_match_gcc():
-    from mop_amd import _lib
-    prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"mopk.h\"\nint main(void){\n"
-    pairs = (("MopkAlignCostArgs", _lib.AlignCostArgs), ("MopkDtwArgs", _lib.DtwArgs))
-    for name, cls in pairs:
-        prog += f'printf("%zu\\n", sizeof({name}));\n'
-        prog += "".join(f'printf("%zu\\n", offsetof({name}, {f}));\n' for f, _ in cls._fields_)
-    prog += 'printf("%d\\n", MOPK_VERSION);\nreturn 0;}\n'
-    got = _gcc(prog)
-    for name, cls in pairs:
-        n = 1 + len(cls._fields_)
-        assert got[:n] == [C.sizeof(cls)] + [getattr(cls, f).offset for f, _ in cls._fields_], name
-        got = got[n:]
-    assert got == [118]
 
 
 def test_support_and_workspace_queries_need_no_gpu():

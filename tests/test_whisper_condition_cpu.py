@@ -1,7 +1,7 @@
 """CPU checks of transcribe's conditioning on the previous text (no GPU): ops.prompt_history_update_torch and
 ops.window_prompts_torch against a per-row Python-list restatement of their rules (hand-built rows for every branch, a random
-sweep), every ValueError of both ops and of the new keywords, MopkPromptHistoryArgs and MopkWindowPromptsArgs against gcc, the
-support queries and bad-argument returns of both entry points (no launch), and transcribe with every core routed through its torch
+sweep), every ValueError of both ops and of the new keywords, the support queries and bad-argument returns of both entry points
+(no launch; tests/test_abi.py compares the two structs with the header), and transcribe with every core routed through its torch
 composition against a naive host loop that keeps Python lists of history and calls the public decoders with list prompts."""
 import ctypes as C
 import inspect
@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from test_whisper_audio_lens_cpu import torch_cores  # noqa: F401  (a fixture: every core on its torch composition, lengths included)
-from test_whisper_beam_cpu import _gcc, _params, _tiny_model
+from test_whisper_beam_cpu import _params, _tiny_model
 from test_whisper_fallback_cpu import NO_SPEECH, same
 from test_whisper_transcribe_cpu import EOS, RULES, V, assert_transcripts_equal, ref_row, transcribe_model
 
@@ -306,23 +306,9 @@ PROMPT_FIELDS = ["A", "B", "n", "width", "Ts", "prev", "out_i64", "sot_i64", "hi
                  "kv_start"]
 
 
-def test_args_layouts_match_gcc():
-    from mop_amd import _lib
-    for struct, A, fields in (("MopkPromptHistoryArgs", _lib.PromptHistoryArgs, UPDATE_FIELDS),
-                              ("MopkWindowPromptsArgs", _lib.WindowPromptsArgs, PROMPT_FIELDS)):
-        prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"mopk.h\"\nint main(void){\n"
-        prog += f'printf("%zu\\n", sizeof({struct}));\n'
-        prog += "".join(f'printf("%zu %zu\\n", offsetof({struct}, {f}), sizeof((({struct} *)0)->{f}));\n' for f in fields)
-        prog += 'printf("%d\\n", MOPK_VERSION);\nreturn 0;}\n'
-        assert [n for n, _ in A._fields_] == fields
-        want = [C.sizeof(A)]
-        for f in fields:
-            want += [getattr(A, f).offset, getattr(A, f).size]
-        assert _gcc(prog) == want + [118], struct
-
-
 def update_args(n=223, S=445, T0=3, A=4):
     from mop_amd import _lib
+    assert UPDATE_FIELDS == [f for f, _ in _lib.PromptHistoryArgs._fields_]
     a = _lib.PromptHistoryArgs()
     a.A, a.B, a.n, a.T, a.T0, a.tokens_ld = A, A + 1, n, T0 + S, T0, T0 + S
     for f in UPDATE_FIELDS[6:]:
@@ -333,6 +319,7 @@ def update_args(n=223, S=445, T0=3, A=4):
 
 def prompt_args(n=223, width=228, Ts=4, A=4):
     from mop_amd import _lib
+    assert PROMPT_FIELDS == [f for f, _ in _lib.WindowPromptsArgs._fields_]
     a = _lib.WindowPromptsArgs()
     a.A, a.B, a.n, a.width, a.Ts, a.prev, a.out_i64, a.sot_i64, a.sot_ld = A, A + 1, n, width, Ts, PREV, 1, 1, 0
     for f in PROMPT_FIELDS[8:]:

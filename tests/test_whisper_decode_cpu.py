@@ -1,19 +1,17 @@
 """CPU checks of KV-cached WhisperMoP decoding (no GPU): signatures and defaults of init_decode_cache / decode_step / generate,
-MopkDecodeAttnArgs against gcc, the support query and bad-argument returns of mopk_decode_attn_*, the ValueErrors raised before any
+the support query and bad-argument returns of mopk_decode_attn_*, the ValueErrors raised before any
 device work, the torch composition of ops.decode_attention against float64 loops, the decode_step bookkeeping (positions, append,
 bottom-right causal alignment, the long-prompt prefill) with the attention cores routed through torch, and the whgen_* fixtures."""
 import ctypes as C
 import inspect
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import GOLDEN, ROOT, golden_names, load_golden
+from conftest import GOLDEN, golden_names, load_golden
 
 WHGEN = golden_names("whgen_")
 
@@ -41,25 +39,6 @@ def test_signatures():
                                                 graph=(False, P), return_logits=(False, K))
     assert _params(ops.decode_attention) == dict(q=(e, P), k_cache=(e, P), v_cache=(e, P), kv_len=(None, P), nk=(None, P),
                                                  causal=(False, P))
-
-
-def test_decode_attn_args_size_matches_gcc():
-    from mop_amd import _lib
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "mopk.h"
-int main(void){printf("%zu %zu %zu %zu %zu\n", sizeof(MopkDecodeAttnArgs), offsetof(MopkDecodeAttnArgs, q),
- offsetof(MopkDecodeAttnArgs, y), offsetof(MopkDecodeAttnArgs, kv_len), offsetof(MopkDecodeAttnArgs, workspace));return 0;}
-'''
-    with tempfile.TemporaryDirectory() as td:
-        cpath = os.path.join(td, "s.c")
-        open(cpath, "w").write(prog)
-        exe = os.path.join(td, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), cpath, "-o", exe])
-        got = list(map(int, subprocess.check_output([exe]).split()))
-    A = _lib.DecodeAttnArgs
-    assert got == [C.sizeof(A), A.q.offset, A.y.offset, A.kv_len.offset, A.workspace.offset]
 
 
 def _args(B=2, H=8, Tq=1, dk=64, cap=448, Nk=448, bf16=True, causal=0):

@@ -1,7 +1,7 @@
 """CPU checks of the decoding statistics and of transcribe's temperature fallback and no-speech skip (no GPU):
 ops.token_logprob_torch and ops.greedy_pick_torch against a float64 restatement written here (numpy log-softmax, a Python loop over
-the rows: filtered rows, the picked entry being eos, rows already done, an exact tie at the maximum), the two args structs against
-gcc and the library's support queries (no launch), generate / beam_search / sample with return_stats against recomputations from
+the rows: filtered rows, the picked entry being eos, rows already done, an exact tie at the maximum), the
+library's support queries (no launch), generate / beam_search / sample with return_stats against recomputations from
 the step logits and from a teacher-forced pass, no_speech_prob against decode(), and with_logit_rules(rules).transcribe under the
 policy against a naive loop over the same public decoders, with every core routed through its torch composition."""
 import ctypes as C
@@ -13,7 +13,6 @@ import pytest
 import torch
 
 from test_whisper_audio_lens_cpu import torch_cores  # noqa: F401  (a fixture: every core on its torch composition)
-from test_whisper_beam_cpu import _gcc
 from test_whisper_transcribe_cpu import EOS, RULES, TB, V, assert_transcripts_equal, transcribe_model
 
 LP_TOL = 1e-5                                  # the `lp` tolerance of tests/test_gpu_whisper_sample.py: the same quantity, the same steps
@@ -163,24 +162,6 @@ def test_op_value_errors():
 
 
 # ------------------------------------------------------------------ ABI
-TL_FIELDS = ["R", "V", "dtype", "token", "logits", "logits_ld", "tokens", "out"]
-GP_FIELDS = ["R", "V", "dtype", "eos", "hist_cap", "reserved", "logits", "logits_ld", "pos", "next_ids", "done", "sum_logprobs",
-             "n_tokens", "hist", "hist_ld"]
-
-
-def test_args_layouts_match_gcc():
-    from mop_amd import _lib
-    prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"mopk.h\"\nint main(void){\n"
-    for name, fields in (("MopkTokenLogprobArgs", TL_FIELDS), ("MopkGreedyPickArgs", GP_FIELDS)):
-        prog += f'printf("%zu\\n", sizeof({name}));\n'
-        prog += "".join(f'printf("%zu\\n", offsetof({name}, {f}));\n' for f in fields)
-    prog += 'printf("%d\\n", MOPK_VERSION);\nreturn 0;}\n'
-    T, G = _lib.TokenLogprobArgs, _lib.GreedyPickArgs
-    assert [f for f, _ in T._fields_] == TL_FIELDS and [f for f, _ in G._fields_] == GP_FIELDS
-    assert _gcc(prog) == ([C.sizeof(T)] + [getattr(T, f).offset for f in TL_FIELDS] + [C.sizeof(G)]
-                          + [getattr(G, f).offset for f in GP_FIELDS] + [118])
-
-
 def test_support_queries_and_bad_arguments_need_no_gpu(lib):
     from mop_amd import _lib
     t = _lib.TokenLogprobArgs()

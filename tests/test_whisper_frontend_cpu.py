@@ -1,7 +1,7 @@
 """CPU checks of the log-mel audio frontend (no GPU): a float64 numpy restatement of Whisper's log_mel_spectrogram (the yardstick
 of this file and of test_gpu_whisper_frontend.py, which imports it, the input builders and the tolerance constants),
 ops.log_mel_torch in float64 against it (and torch.stft where it runs), ops.mel_filterbank, every ValueError of ops.log_mel and
-LogMelFrontend, MopkLogMelArgs against gcc, the support query at the envelope's edges and the bad-argument returns of mopk_log_mel
+LogMelFrontend, the support query at the envelope's edges and the bad-argument returns of mopk_log_mel
 (no launch), and WhisperMoP.transcribe_audio with every core routed through its torch composition."""
 import ctypes as C
 import inspect
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from test_whisper_audio_lens_cpu import torch_cores  # noqa: F401  (a fixture: every core on its torch composition, lengths included)
-from test_whisper_beam_cpu import _gcc, _params
+from test_whisper_beam_cpu import _params
 from test_whisper_transcribe_cpu import EOS, RULES, V, transcribe_model
 
 SHAPES = ((16, 4, 3), (64, 16, 10), (400, 160, 80))          # (n_fft, hop, n_mels) of the small sweep
@@ -292,22 +292,9 @@ def lib():
     return _lib.lib()
 
 
-def test_args_layout_matches_gcc():
-    from mop_amd import _lib
-    prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"mopk.h\"\nint main(void){\n"
-    prog += 'printf("%zu\\n", sizeof(MopkLogMelArgs));\n'
-    prog += "".join(f'printf("%zu %zu\\n", offsetof(MopkLogMelArgs, {f}), sizeof(((MopkLogMelArgs *)0)->{f}));\n' for f in FIELDS)
-    prog += 'printf("%d %d %d\\n", MOPK_VERSION, MOPK_LOG_MEL_TILE_FRAMES, MOPK_LOG_MEL_F16);\nreturn 0;}\n'
-    A = _lib.LogMelArgs
-    assert [n for n, _ in A._fields_] == FIELDS
-    want = [C.sizeof(A)]
-    for f in FIELDS:
-        want += [getattr(A, f).offset, getattr(A, f).size]
-    assert _gcc(prog) == want + [118, _lib.LOG_MEL_TILE_FRAMES, _lib.LOG_MEL_F16]
-
-
 def _args(n_fft=400, hop=160, n_mels=80, B=3, L=4000):
     from mop_amd import _lib
+    assert FIELDS == [f for f, _ in _lib.LogMelArgs._fields_]
     a = _lib.LogMelArgs()
     a.B, a.L, a.n_fft, a.hop, a.n_mels, a.audio_ld = B, L, n_fft, hop, n_mels, L
     a.audio_dtype, a.out_dtype = _lib.MOPK_F32, _lib.MOPK_F32

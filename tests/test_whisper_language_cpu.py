@@ -1,6 +1,6 @@
 """CPU checks of language detection (no GPU): ops.language_probs_torch against a float64 restatement written here (numpy: plain
 rows, rows with -inf at some language entries, an exact tie between two language tokens listed in descending id order), the
-signatures and exports, MopkLanguageProbsArgs against gcc, the library's support query and bad-argument returns (no launch), every
+signatures and exports, the library's support query and bad-argument returns (no launch), every
 ValueError of LanguageTokens, the op, detect_language and transcribe's two keywords, and, with every core routed through its torch
 composition, detect_language against decode() and transcribe(languages=...) against transcribe with the prompts filled by hand."""
 import ctypes as C
@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from test_whisper_audio_lens_cpu import torch_cores  # noqa: F401  (a fixture: every core on its torch composition, lengths included)
-from test_whisper_beam_cpu import _gcc, _params, _tiny_model
+from test_whisper_beam_cpu import _params, _tiny_model
 from test_whisper_fallback_cpu import LP_TOL
 from test_whisper_transcribe_cpu import CLIPS, RULES, V, assert_transcripts_equal, transcribe_model
 
@@ -175,19 +175,6 @@ def test_op_value_errors():
                      (x, L, None, torch.empty(3, dtype=torch.int32, device="meta"))):
             with pytest.raises(ValueError):
                 fn(*args)
-
-
-def test_args_layout_matches_gcc():
-    from mop_amd import _lib
-    fields = [f for f, _ in _lib.LanguageProbsArgs._fields_]
-    assert fields == ["R", "V", "dtype", "n", "logits", "logits_ld", "ids", "probs", "probs_ld", "tokens"]
-    prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"mopk.h\"\nint main(void){printf(\"%zu\", sizeof(MopkLanguageProbsArgs));" + \
-        "".join(f"printf(\" %zu\", offsetof(MopkLanguageProbsArgs, {f}));" for f in fields) + \
-        "printf(\" %d %d\", MOPK_LANGUAGE_MAX_N, MOPK_VERSION);return 0;}"
-    got = _gcc(prog)
-    assert got[0] == C.sizeof(_lib.LanguageProbsArgs)
-    assert got[1:-2] == [getattr(_lib.LanguageProbsArgs, f).offset for f in fields]
-    assert got[-2:] == [_lib.LANGUAGE_MAX_N, 118]
 
 
 def test_support_query_and_bad_arguments_need_no_gpu(lib):

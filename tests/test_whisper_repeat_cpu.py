@@ -1,7 +1,7 @@
 """CPU checks of the repetition rules (no GPU): ops.repeat_rules_torch against a restatement written here (plain loops and sets
 over Python floats, no call into ops) on hand-built rows with stated answers and over a sweep of vocabularies, row counts, dtypes,
 n-gram sizes, penalties and histories, bit for bit on every row (nothing here is a near tie); every ValueError; the signatures;
-MopkRepeatRulesArgs against gcc; the library's support query; and generate / beam_search / sample / transcribe under the rules
+the library's support query; and generate / beam_search / sample / transcribe under the rules
 with every core on its torch composition: no repeated bigram, the timestamp grammar intact, and nothing changed without rules."""
 import ctypes as C
 import inspect
@@ -12,7 +12,7 @@ import struct
 import pytest
 import torch
 
-from test_whisper_beam_cpu import _gcc, _tiny_model
+from test_whisper_beam_cpu import _tiny_model
 from test_whisper_audio_lens_cpu import torch_cores  # noqa: F401  (a fixture: every core on its torch composition, lengths included)
 from test_whisper_rules_cpu import MODEL_RULES, _peaked_tiny_model, bits, check_grammar
 
@@ -292,16 +292,6 @@ def test_signatures():
     assert _params(WhisperMoP._transcribe)["repeat_rules"] == (None, K) and "repeat_rules" not in _params(RuledDecoding.transcribe)
     for fn in (WhisperMoP.generate, WhisperMoP.beam_search, WhisperMoP.sample, WhisperMoP.transcribe):
         assert "repeat_rules" not in _params(fn), fn.__name__                     # the public signatures stay
-
-
-def test_args_layout_matches_gcc():
-    from mop_amd import _lib
-    fields = [f for f, _ in _lib.RepeatRulesArgs._fields_]
-    prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"mopk.h\"\nint main(void){printf(\"%zu\", sizeof(MopkRepeatRulesArgs));" + \
-        "".join(f"printf(\" %zu\", offsetof(MopkRepeatRulesArgs, {f}));" for f in fields) + "return 0;}"
-    got = _gcc(prog)
-    assert got[0] == C.sizeof(_lib.RepeatRulesArgs)
-    assert got[1:] == [getattr(_lib.RepeatRulesArgs, f).offset for f in fields]
 
 
 def test_support_query_and_bad_arguments_need_no_gpu():

@@ -1,7 +1,7 @@
 """CPU checks of Whisper's logit rules (no GPU): ops.logit_rules_torch against a restatement written here (a plain per-row loop in
 rule order, rule 3e in float64, no call into ops) over three vocabulary shapes, 1 / 3 / 16 rows, fp32 / bf16 and hand-built
 histories that reach every branch; both outcomes of the dominance rule on random rows and on hand-built ones; every ValueError;
-MopkLogitRulesArgs against gcc; and generate / beam_search / sample under rules with every core on its torch composition, whose
+and generate / beam_search / sample under rules with every core on its torch composition, whose
 outputs must obey the timestamp grammar.  The decoders' own signatures are pinned by the older tests, so the rules come in through
 WhisperMoP.with_logit_rules(rules)."""
 import ctypes as C
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_whisper_beam_cpu import _gcc, _tiny_model
+from test_whisper_beam_cpu import _tiny_model
 from test_whisper_ragged_cpu import torch_cores  # noqa: F401  (a fixture: every core on its torch composition)
 
 NEG = float("-inf")
@@ -250,16 +250,6 @@ def test_argument_errors():
                  lambda: d.sample(mel, ids, 5, eos_token_id=71)):
         with pytest.raises(ValueError):                      # before any device work: a CPU encode would raise RuntimeError
             call()
-
-
-def test_args_layout_matches_gcc():
-    from mop_amd import _lib
-    fields = [f for f, _ in _lib.LogitRulesArgs._fields_]
-    prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"mopk.h\"\nint main(void){printf(\"%zu\", sizeof(MopkLogitRulesArgs));" + \
-        "".join(f"printf(\" %zu\", offsetof(MopkLogitRulesArgs, {f}));" for f in fields) + "return 0;}"
-    got = _gcc(prog)
-    assert got[0] == C.sizeof(_lib.LogitRulesArgs)
-    assert got[1:] == [getattr(_lib.LogitRulesArgs, f).offset for f in fields]
 
 
 def test_support_query_and_bad_arguments_need_no_gpu():

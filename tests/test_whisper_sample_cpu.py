@@ -1,4 +1,4 @@
-"""CPU checks of WhisperMoP sampling (no GPU): signatures and defaults of sample and ops.sample_tokens*, MopkSampleArgs against gcc,
+"""CPU checks of WhisperMoP sampling (no GPU): signatures and defaults of sample and ops.sample_tokens*,
 the support query and bad-argument returns of mopk_sample_*, the ValueErrors raised before any device work, ops.sample_tokens_torch
 against a plain-Python restatement of the documented rule on hand-built rows (exact ties at the top-k and nucleus boundaries, -inf
 logits, top_k >= V, temperature 0), and sample with every core routed through its torch composition against a naive oracle that
@@ -11,7 +11,7 @@ import struct
 import pytest
 import torch
 
-from test_whisper_beam_cpu import _gcc, _params, _tiny_model, torch_cores  # noqa: F401  (torch_cores is a fixture)
+from test_whisper_beam_cpu import _params, _tiny_model, torch_cores  # noqa: F401  (torch_cores is a fixture)
 
 NEG = float("-inf")
 M32 = 0xFFFFFFFF
@@ -35,19 +35,6 @@ def test_signatures():
     for f in (ops.sample_tokens, ops.sample_tokens_torch, ops.sample_tokens_supported):
         assert _params(f) == dict(logits=(e, P), pos=(e, P), temperature=(1.0, P), top_k=(0, P), top_p=(1.0, P), seed=(0, P),
                                   out=(None, P)), f.__name__
-
-
-def test_sample_args_layout_matches_gcc():
-    from mop_amd import _lib
-    fields = ["R", "n", "V", "logits_dtype", "top_k", "greedy", "inv_temp", "top_p", "seed", "logits", "logits_sb", "logits_sk", "pos",
-              "tokens", "logprobs", "workspace"]
-    prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"mopk.h\"\nint main(void){\n"
-    prog += 'printf("%zu\\n", sizeof(MopkSampleArgs));\n'
-    for f in fields:
-        prog += f'printf("%zu\\n", offsetof(MopkSampleArgs, {f}));\n'
-    prog += 'printf("%d\\n", MOPK_SAMPLE_MAX_V);\nreturn 0;}\n'
-    A = _lib.SampleArgs
-    assert _gcc(prog) == [C.sizeof(A)] + [getattr(A, f).offset for f in fields] + [1 << 24]
 
 
 def _args(R=8, n=1, V=51865, bf16=True, top_k=50, top_p=0.95, inv_temp=1.0 / 0.7, greedy=0):

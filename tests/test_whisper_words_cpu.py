@@ -1,7 +1,7 @@
 """CPU checks of word timestamps (no GPU): ops.WordRules and from_pieces, ops.word_spans_torch and ops.alignment_rows_torch
 against plain Python-list restatements written from Whisper's algorithm (word records, the two while loops of
 merge_punctuations over records whose "text" is the tuple of their tokens' classes, numpy.median), hand-built rows for every
-rule and a random sweep of shapes, every ValueError, MopkAlignmentRowsArgs and MopkWordSpansArgs against gcc, and
+rule and a random sweep of shapes, every ValueError, and
 WhisperMoP.align_words and transcribe(word_timestamps=True) with every core routed through its torch composition against
 align_tokens plus the restatement and against a naive host loop."""
 import ctypes as C
@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from test_whisper_audio_lens_cpu import torch_cores  # noqa: F401  (a fixture: every core on its torch composition, lengths included)
-from test_whisper_beam_cpu import _gcc, _params, _tiny_model
+from test_whisper_beam_cpu import _params, _tiny_model
 from test_whisper_transcribe_cpu import EOS, RULES, TB, V, ref_row, transcribe_model
 
 BEGIN, PRE, APP, END = 1, 2, 4, 8
@@ -384,27 +384,6 @@ def test_op_value_errors():
 
 
 # ------------------------------------------------------------------ ABI
-ROWS_FIELDS = ["R", "T", "T0", "Tp", "nots", "eos", "out_i64", "sot_i64", "tokens", "tokens_ld", "n_take", "sot", "sot_ld", "ids",
-               "n_tokens", "col"]
-SPANS_FIELDS = ["R", "N", "V", "median_cap", "tokens", "tokens_ld", "times", "times_ld", "probs", "probs_ld", "n_text", "table",
-                "starts", "ends", "out_probs", "tok_begin", "tok_end", "n_words"]
-
-
-def test_args_layouts_match_gcc():
-    from mop_amd import _lib
-    for struct, A, fields in (("MopkAlignmentRowsArgs", _lib.AlignmentRowsArgs, ROWS_FIELDS),
-                              ("MopkWordSpansArgs", _lib.WordSpansArgs, SPANS_FIELDS)):
-        prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"mopk.h\"\nint main(void){\n"
-        prog += f'printf("%zu\\n", sizeof({struct}));\n'
-        prog += "".join(f'printf("%zu %zu\\n", offsetof({struct}, {f}), sizeof((({struct} *)0)->{f}));\n' for f in fields)
-        prog += 'printf("%d\\n", MOPK_VERSION);\nreturn 0;}\n'
-        assert [n for n, _ in A._fields_] == fields
-        want = [C.sizeof(A)]
-        for f in fields:
-            want += [getattr(A, f).offset, getattr(A, f).size]
-        assert _gcc(prog) == want + [118], struct
-
-
 def test_support_queries_and_bad_arguments_need_no_gpu():
     from mop_amd import _lib, build
     build.build_lib()
