@@ -985,6 +985,47 @@ size_t mopk_log_mel_workspace_bytes(const MopkLogMelArgs *a);    /* from the sha
 int mopk_log_mel(const MopkLogMelArgs *a, void *stream);
 
 /* --------------------------------------------------------------------------
+ * Sample-rate conversion of a batch of waveforms (the stage in front of mopk_log_mel; inference only): the windowed-sinc (Hann)
+ * polyphase resampler.  (Added under version 118: new exports only; callers detect it with mopk_resample_supported.)
+ * With o / n the reduced input / output rates, K the caller's tap table and w its centre offset, clip b of len_b = min(lens[b], L)
+ * samples (L without lens), taken as zero outside [0, len_b), gives len_out_b = ceil(n * len_b / o) samples (64-bit product):
+ *   y[f * n + p] = sum_{s < S} K[p][s] * x[f * o + first[p] + s - w],   0 <= p < n,   f * n + p < len_out_b,
+ * an fmaf chain in ascending s from 0, fp32.  Row p of K holds the S consecutive taps of phase p that can be non-zero, first[p]
+ * is the index of its first tap in the full (n, 2 w + o) table; first[p] is clamped into [0, 2 w + o - S] on the device, so no
+ * table content makes the kernel read outside the span it staged.  A sample x[q] is the mean over the C channels, summed in
+ * ascending channel order in fp32 and multiplied by the fp32 reciprocal of C, of the converted input: fp32, bf16 and fp16 exactly, int16 times 2^-15.
+ * The identity (orig == new) is the table n = o = S = 1, w = 0, K = 1, first = 0.
+ * One launch.  A workgroup takes one clip's tile of 1024 consecutive outputs, stages the contiguous input span the tile reads
+ * (conversion, channel mean and the [0, len_b) bound applied once, reads outside the bound never issued) and, when span and
+ * table fit 64 KiB together, the table into LDS; otherwise the table is read through L2.  Outputs m >= len_out_b of the row are
+ * written as zeros and out_lens[b] = len_out_b by the same launch.  A sample depends on its own clip only: bit-identical to the
+ * clip run alone.  No workspace, no host synchronisation, no raised LDS limit (capturable without a warm-up).
+ * Takes 1 <= B <= 65535, 1 <= C <= 64, 1 <= S <= 2 w + o, S <= table_ld, n * table_ld <= 2^22, Lout = ceil(n * L / o) < 2^31
+ * and a span ((1024 + n - 2) / n) * o + 2 w + o <= 12288 samples (o / n up to 11 at the default filter width). */
+typedef struct MopkResampleArgs {
+    int32_t B;                           /* clips */
+    int32_t C;                           /* channels, averaged */
+    int32_t L;                           /* samples per channel and row of audio */
+    int32_t Lout;                        /* samples per row of out: ceil(n * L / o) */
+    int32_t o, n;                        /* input / output rate over their gcd */
+    int32_t w;                           /* centre offset of the tap table */
+    int32_t S;                           /* taps per phase */
+    int32_t table_ld;                    /* element stride between rows of table, >= S (odd: conflict-free in LDS) */
+    int32_t audio_dtype;                 /* MOPK_F32, MOPK_BF16, MOPK_LOG_MEL_F16 (IEEE half) or 3: int16 */
+    int32_t out_dtype;                   /* MOPK_F32 or MOPK_BF16 (one rounding of the fp32 result) */
+    int32_t reserved;
+    const void *audio;                   /* device; sample (b, c, q) at audio + b * audio_sb + c * audio_sc + q * audio_sl elements */
+    int64_t audio_sb, audio_sc, audio_sl;
+    const int32_t *lens;                 /* device (B) sample counts, clamped into [0, L]; NULL: every clip has L */
+    const float *table;                  /* device (n, table_ld) fp32, contiguous; columns >= S are copied along and never used */
+    const int32_t *first;                /* device (n) */
+    void *out;                           /* (B, Lout) out, contiguous */
+    int32_t *out_lens;                   /* (B) out, or NULL */
+} MopkResampleArgs;
+int mopk_resample_supported(const MopkResampleArgs *a);          /* 1 if the kernel takes this call (shape, dtypes, alignment) */
+int mopk_resample(const MopkResampleArgs *a, void *stream);
+
+/* --------------------------------------------------------------------------
  * Per-step decoding statistics on last-position logits (WhisperMoP.generate / beam_search / sample with return_stats, and the
  * temperature fallback and no-speech skip of WhisperMoP.transcribe; inference only).  (Added under version 118: new exports only;
  * callers detect them with the _supported queries.)  Row r (0 <= r < R) reads x at logits + r * logits_ld elements, F32 or BF16,

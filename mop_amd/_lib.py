@@ -338,6 +338,17 @@ class LogMelArgs(C.Structure):
     ]
 
 
+class ResampleArgs(C.Structure):
+    """MopkResampleArgs: polyphase sample-rate conversion of a batch of waveforms (ops.resample)."""
+    _fields_ = [
+        ("B", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("Lout", C.c_int32), ("o", C.c_int32), ("n", C.c_int32),
+        ("w", C.c_int32), ("S", C.c_int32), ("table_ld", C.c_int32), ("audio_dtype", C.c_int32), ("out_dtype", C.c_int32),
+        ("reserved", C.c_int32),
+        ("audio", _fp), ("audio_sb", C.c_int64), ("audio_sc", C.c_int64), ("audio_sl", C.c_int64), ("lens", _fp), ("table", _fp),
+        ("first", _fp), ("out", _fp), ("out_lens", _fp),
+    ]
+
+
 class TokenLogprobArgs(C.Structure):
     """MopkTokenLogprobArgs: the log-probability of one token per row of last-position logits (WhisperMoP's no_speech_prob)."""
     _fields_ = [
@@ -466,6 +477,8 @@ SYMBOLS = {
     "mopk_log_mel_supported": (C.c_int, [C.POINTER(LogMelArgs)]),
     "mopk_log_mel_workspace_bytes": (C.c_size_t, [C.POINTER(LogMelArgs)]),
     "mopk_log_mel": (C.c_int, [C.POINTER(LogMelArgs), C.c_void_p]),
+    "mopk_resample_supported": (C.c_int, [C.POINTER(ResampleArgs)]),
+    "mopk_resample": (C.c_int, [C.POINTER(ResampleArgs), C.c_void_p]),
     "mopk_token_logprob_supported": (C.c_int, [C.POINTER(TokenLogprobArgs)]),
     "mopk_token_logprob": (C.c_int, [C.POINTER(TokenLogprobArgs), C.c_void_p]),
     "mopk_greedy_pick_supported": (C.c_int, [C.POINTER(GreedyPickArgs)]),

@@ -10,6 +10,7 @@ residual add (`ops.gated_residual`).  The LayerNorms, the MLP and the embeddings
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, NamedTuple, Optional, Tuple
 
@@ -1871,7 +1872,8 @@ class WhisperMoP(nn.Module):
 class LogMelFrontend(nn.Module):
     """waveform -> Whisper's log-mel spectrogram (ops.log_mel: the HIP STFT kernel), the stage in front of `WhisperMoP.encode`,
     `generate`, `beam_search`, `sample`, `align_tokens` and `transcribe`.  The Slaney mel filterbank (ops.mel_filterbank) is a
-    non-persistent buffer.  Out of scope: resampling (audio must be at sample_rate), Whisper's 30 s zero padding, file decoding."""
+    non-persistent buffer.  Audio must be mono float samples at sample_rate; ResampledLogMelFrontend takes any other rate, int16
+    samples and several channels (ops.resample in front).  Out of scope: Whisper's 30 s zero padding, file decoding."""
 
     def __init__(self, n_mels: int = 80, sample_rate: int = 16000, n_fft: int = 400, hop_length: int = 160):
         super().__init__()
@@ -1927,6 +1929,105 @@ class LogMelFrontend(nn.Module):
                 lens = lens.pin_memory().to(padded.device, non_blocking=True)
         mel = ops.log_mel(padded, self.filters, self.n_fft, self.hop_length, lens)
         return [mel[b, :n[b] // self.hop_length] for b in range(len(n))]
+
+
+def _pad_waveforms(audio, min_samples: int, what: str):
+    """a non-empty list of clips, each 1-D (L_b,) or 2-D (C_b, L_b), of one dtype and device -> (padded, lens, n): the clips in one
+    zero-padded buffer, their lengths as an int32 device tensor (one pinned asynchronous copy; None when all are equal) and as
+    Python ints.  Clips of one form stay as they are, (B, L_max) or (B, C, L_max) in their own dtype, and ops.resample converts and
+    averages them; a list that mixes channel counts is averaged clip by clip here with the same operations in the same order
+    (ops._rs_mono), so a clip comes out as it would alone either way."""
+    if not isinstance(audio, (list, tuple)) or len(audio) == 0:
+        raise ValueError(f"{what}: audio must be a (B, L) or (B, C, L) tensor or a non-empty list of (L_b,) or (C, L_b) clips")
+    for b, x in enumerate(audio):
+        if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or 0 in x.shape:
+            raise ValueError(f"{what}: clip {b} must be a non-empty 1-D (L,) or 2-D (C, L) tensor of samples, got "
+                             f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        if x.dtype != audio[0].dtype or not (x.dtype.is_floating_point or x.dtype == torch.int16):
+            raise ValueError(f"{what}: clips must share one floating or int16 dtype, clip {b} is {x.dtype}")
+        if x.device != audio[0].device:
+            raise ValueError(f"{what}: clip {b} is on {x.device}, clip 0 on {audio[0].device}")
+        if x.shape[-1] < min_samples:
+            raise ValueError(f"{what}: clip {b} has {x.shape[-1]} samples, fewer than the {min_samples} it needs")
+    n = [int(x.shape[-1]) for x in audio]
+    dev = audio[0].device
+    if len({tuple(x.shape[:-1]) for x in audio}) == 1:
+        padded = torch.zeros(len(n), *audio[0].shape[:-1], max(n), dtype=audio[0].dtype, device=dev)
+        for b, x in enumerate(audio):
+            padded[b, ..., :n[b]] = x
+    else:
+        cd = torch.float64 if audio[0].dtype == torch.float64 else torch.float32
+        padded = torch.zeros(len(n), max(n), dtype=cd, device=dev)
+        for b, x in enumerate(audio):
+            padded[b, :n[b]] = ops._rs_mono(x.unsqueeze(0) if x.dim() == 2 else x.reshape(1, 1, -1), cd)[0]
+    lens = None
+    if min(n) != max(n):
+        lens = torch.tensor(n, dtype=torch.int32)
+        if dev.type == "cuda":                                         # an asynchronous copy: the host does not wait for it
+            lens = lens.pin_memory().to(dev, non_blocking=True)
+    return padded, lens, n
+
+
+class Resample(nn.Module):
+    """waveform at orig_rate -> waveform at new_rate (ops.resample: the HIP polyphase kernel; its docstring states the filter),
+    mono: the channels of a multi-channel clip are averaged, int16 samples are scaled by 2^-15.  No parameters, no buffers."""
+
+    def __init__(self, orig_rate: int, new_rate: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+        super().__init__()
+        ops._rs_param_check(orig_rate, new_rate, lowpass_filter_width, rolloff, "Resample")
+        self.orig_rate, self.new_rate, self.lowpass_filter_width, self.rolloff = orig_rate, new_rate, lowpass_filter_width, rolloff
+
+    def out_samples(self, samples: int) -> int:
+        """the length of a clip of `samples` samples after conversion: ceil(new samples / orig) over the reduced rates"""
+        g = math.gcd(self.orig_rate, self.new_rate)
+        return -(-(self.new_rate // g) * samples // (self.orig_rate // g))
+
+    @torch.no_grad()
+    def forward(self, audio):
+        """audio: a (B, L) or (B, C, L) tensor -> (B, ceil(n L / o)) fp32; or a list of B clips, each (L_b,) or (C_b, L_b), of
+        different lengths and channel counts -> a list of B (len_out_b,) tensors, views of one padded buffer."""
+        kw = dict(lowpass_filter_width=self.lowpass_filter_width, rolloff=self.rolloff)
+        if isinstance(audio, torch.Tensor):
+            return ops.resample(audio, self.orig_rate, self.new_rate, **kw)[0]
+        padded, lens, n = _pad_waveforms(audio, 1, "Resample")
+        out = ops.resample(padded, self.orig_rate, self.new_rate, lens, **kw)[0]
+        return [out[b, :self.out_samples(n[b])] for b in range(len(n))]
+
+
+class ResampledLogMelFrontend(LogMelFrontend):
+    """a LogMelFrontend for audio at input_sample_rate: ops.resample to sample_rate, then ops.log_mel with the lengths the resampler
+    wrote, one device tensor between the two and no host sync.  Takes what `Resample` takes: float or int16 samples, mono or
+    multi-channel.  WhisperMoP.transcribe_audio takes it as any LogMelFrontend."""
+
+    def __init__(self, input_sample_rate: int, n_mels: int = 80, sample_rate: int = 16000, n_fft: int = 400, hop_length: int = 160,
+                 lowpass_filter_width: int = 6, rolloff: float = 0.99):
+        super().__init__(n_mels, sample_rate, n_fft, hop_length)
+        ops._rs_param_check(input_sample_rate, sample_rate, lowpass_filter_width, rolloff, "ResampledLogMelFrontend")
+        self.input_sample_rate = input_sample_rate
+        self.resampler = Resample(input_sample_rate, sample_rate, lowpass_filter_width, rolloff)
+
+    @property
+    def min_samples(self) -> int:
+        """the shortest clip in INPUT samples: the fewest that resample to LogMelFrontend.min_samples"""
+        g = math.gcd(self.input_sample_rate, self.sample_rate)
+        return (super().min_samples - 1) * (self.input_sample_rate // g) // (self.sample_rate // g) + 1
+
+    @torch.no_grad()
+    def forward(self, audio):
+        """audio: a (B, L) or (B, C, L) tensor at input_sample_rate -> (B, ceil(n L / o) // hop_length, n_mels) fp32; or a list of B
+        clips, each (L_b,) or (C_b, L_b) -> a list of B (T_b, n_mels) tensors, T_b = ceil(n L_b / o) // hop_length, views of one
+        padded buffer."""
+        what, rs = "ResampledLogMelFrontend", self.resampler
+        kw = dict(lowpass_filter_width=rs.lowpass_filter_width, rolloff=rs.rolloff)
+        if isinstance(audio, torch.Tensor):
+            if audio.dim() not in (2, 3) or audio.shape[-1] < self.min_samples:
+                raise ValueError(f"{what}: audio must be a (B, L) or (B, C, L) tensor with L >= {self.min_samples} or a non-empty list "
+                                 f"of clips, got {tuple(audio.shape)}")
+            return ops.log_mel(ops.resample(audio, rs.orig_rate, rs.new_rate, **kw)[0], self.filters, self.n_fft, self.hop_length)
+        padded, lens, n = _pad_waveforms(audio, self.min_samples, what)
+        wave, out_lens = ops.resample(padded, rs.orig_rate, rs.new_rate, lens, **kw)
+        mel = ops.log_mel(wave, self.filters, self.n_fft, self.hop_length, out_lens)
+        return [mel[b, :rs.out_samples(n[b]) // self.hop_length] for b in range(len(n))]
 
 
 class RuledDecoding:

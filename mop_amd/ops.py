@@ -4510,4 +4510,209 @@ def log_mel(audio: torch.Tensor, filters: torch.Tensor, n_fft: int = 400, hop_le
         return out
 
 
+# --------------------------------------------------------------------------------------
+# Audio frontend (Resample, ResampledLogMelFrontend): sample-rate conversion in front of log_mel
+RESAMPLE_TILE = 1024            # outputs per workgroup of the kernel (RS_TILE of csrc/resample.hip)
+RESAMPLE_MAX_SPAN, RESAMPLE_MAX_CHANNELS, RESAMPLE_MAX_TABLE = 12288, 64, 1 << 22
+_RS_I16 = 3                     # MopkResampleArgs.audio_dtype of int16 samples
+_RS_FILTERS = {}                # (o, n, lpw, rolloff) -> (w, S, table (n, S) float64, first (n,) int64) on the host
+_RS_TABLES = {}                 # (o, n, lpw, rolloff, device, dtype) -> (table (n, S | 1) dtype, first (n,) int32) on the device
+
+
+def _rs_dims(o: int, n: int, lpw: int, rolloff: float):
+    """(w, S) of the reduced rate pair: the centre offset of the tap table and the taps per phase that can be non-zero"""
+    if o == n:
+        return 0, 1
+    base = min(o, n) * rolloff
+    return math.ceil(lpw * o / base), math.floor(2 * lpw * o / base) + 1
+
+
+def _rs_filter(o: int, n: int, lpw: int, rolloff: float):
+    """the compact tap table of the reduced rate pair, float64 on the host, kept per (o, n, lpw, rolloff): (w, S, table (n, S),
+    first (n,)) with table[p, s] = K[p, first[p] + s] of the definition in `resample`.  first[p] is the first tap of phase p with
+    |t| < lpw, moved down where the run would end behind the full row, so a row is a slice of the full table and every tap it
+    leaves out has |t| >= lpw: below 2e-49 in float64, a zero in float32.  Only n x (S + 4) taps are ever evaluated.  The
+    identity (o == n) is the single tap 1."""
+    key = (o, n, lpw, float(rolloff))
+    if key not in _RS_FILTERS:
+        w, S = _rs_dims(o, n, lpw, rolloff)
+        if o == n:
+            _RS_FILTERS[key] = (w, S, torch.ones(1, 1, dtype=torch.float64), torch.zeros(1, dtype=torch.int64))
+        else:
+            base, width = min(o, n) * rolloff, 2 * w + o
+            p = torch.arange(n, dtype=torch.float64).unsqueeze(1)
+
+            def t_of(j):                                     # j: (n, k) int64 tap indices -> the unclamped t
+                return (-p / n + (j.to(torch.float64) - w) / o) * base
+
+            lo = (torch.floor(w + o * p / n - lpw * o / base).to(torch.int64) - 1).clamp(0, width - 1)       # at or before the run
+            j = lo + torch.arange(S + 4).unsqueeze(0)
+            inside = (t_of(j).abs() < lpw) & (j < width)
+            first = (lo[:, 0] + inside.to(torch.int64).argmax(1)).clamp(max=width - S)
+            t = t_of(first.unsqueeze(1) + torch.arange(S).unsqueeze(0)).clamp(-lpw, lpw)
+            table = (base / o) * torch.cos(t * (math.pi / (2 * lpw))) ** 2 * torch.sinc(t)
+            _RS_FILTERS[key] = (w, S, table, first)
+    return _RS_FILTERS[key]
+
+
+def _rs_tables(o: int, n: int, lpw: int, rolloff: float, device, dtype):
+    """(w, S, table (n, S | 1) in dtype: the float64 taps rounded once, an odd row stride with a zero behind an even S, first
+    (n,) int32), on the device, kept per (o, n, lpw, rolloff, device, dtype)"""
+    key = (o, n, lpw, float(rolloff), str(device), dtype)
+    w, S, table, first = _rs_filter(o, n, lpw, rolloff)
+    if key not in _RS_TABLES:
+        padded = torch.zeros(n, S | 1, dtype=torch.float64)
+        padded[:, :S] = table
+        _RS_TABLES[key] = (padded.to(dtype).to(device).contiguous(), first.to(torch.int32).to(device).contiguous())
+    return (w, S) + _RS_TABLES[key]
+
+
+def _rs_param_check(orig_rate, new_rate, lowpass_filter_width, rolloff, what: str) -> None:
+    for name, v in (("orig_rate", orig_rate), ("new_rate", new_rate), ("lowpass_filter_width", lowpass_filter_width)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{what}: {name} must be an int >= 1, got {v!r}")
+    if isinstance(rolloff, bool) or not isinstance(rolloff, (int, float)) or not 0.0 < rolloff <= 1.0:
+        raise ValueError(f"{what}: rolloff must be a number in (0, 1], got {rolloff!r}")
+
+
+def _rs_check(audio, orig_rate, new_rate, lens, lowpass_filter_width, rolloff, out_dtype, what: str) -> None:
+    """validate a resample call before any device work"""
+    _rs_param_check(orig_rate, new_rate, lowpass_filter_width, rolloff, what)
+    if (not isinstance(audio, torch.Tensor) or audio.dim() not in (2, 3) or 0 in audio.shape
+            or audio.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.float64, torch.int16)):
+        raise ValueError(f"{what}: audio must be a non-empty (B, L) or (B, C, L) tensor of float32, bfloat16, float16, float64 or "
+                         f"int16 samples, got {(tuple(audio.shape), audio.dtype) if isinstance(audio, torch.Tensor) else type(audio).__name__}")
+    if lens is not None:
+        if not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or lens.shape != (audio.shape[0],):
+            raise ValueError(f"{what}: lens must be an int32 ({audio.shape[0]},) tensor of sample counts, got "
+                             f"{(tuple(lens.shape), lens.dtype) if isinstance(lens, torch.Tensor) else type(lens).__name__}")
+        if lens.device != audio.device:
+            raise ValueError(f"{what}: lens is on {lens.device}, the audio on {audio.device}")
+    allowed = (torch.float32, torch.bfloat16) + ((torch.float64,) if audio.dtype == torch.float64 else ())
+    if out_dtype not in allowed:
+        raise ValueError(f"{what}: out_dtype must be torch.float32 or torch.bfloat16 (torch.float64 for float64 audio), got {out_dtype!r}")
+
+
+def _rs_mono(audio: torch.Tensor, cd: torch.dtype) -> torch.Tensor:
+    """(B, L) or (B, C, L) samples -> (B, L) in cd as the kernel stages them: int16 times 2^-15, the channels summed in ascending
+    order and multiplied by the reciprocal of C (rounded to fp32 first when cd is float32, as the kernel's)"""
+    x = audio.to(cd)
+    if audio.dtype == torch.int16:
+        x = x * 2.0 ** -15
+    if x.dim() == 2:
+        return x
+    m = x[:, 0]
+    for c in range(1, x.shape[1]):
+        m = m + x[:, c]
+    inv = 1.0 / x.shape[1] if cd == torch.float64 else float(torch.tensor(1.0) / torch.tensor(float(x.shape[1])))
+    return m * inv if x.shape[1] > 1 else m
+
+
+def resample_torch(audio: torch.Tensor, orig_rate: int, new_rate: int, lens: Optional[torch.Tensor] = None, *,
+                   lowpass_filter_width: int = 6, rolloff: float = 0.99, out_dtype: torch.dtype = torch.float32):
+    """the restatement of `resample` in torch ops (CPU or GPU, no host sync): the mono samples behind each clip's length set to
+    zero and padded by the filter's reach, then one gather, multiply and add per tap over the whole (B, Lout) output, the S taps
+    in ascending order as in the kernel (elementwise: a clip's samples do not depend on the batch around it); zeros behind
+    len_out_b.  Computes in float32, in float64 for float64 audio.  -> (out, out_lens or None)."""
+    _rs_check(audio, orig_rate, new_rate, lens, lowpass_filter_width, rolloff, out_dtype, "resample_torch")
+    cd = torch.float64 if audio.dtype == torch.float64 else torch.float32
+    g = math.gcd(orig_rate, new_rate)
+    o, n, dev = orig_rate // g, new_rate // g, audio.device
+    w, S, table, first = _rs_tables(o, n, lowpass_filter_width, rolloff, dev, cd)
+    x = _rs_mono(audio, cd)
+    B, Lm = x.shape
+    Lout = -(-n * Lm // o)
+    out_lens = None
+    if lens is not None:
+        ln = lens.long().clamp(0, Lm)
+        x = torch.where(torch.arange(Lm, device=dev).unsqueeze(0) < ln.unsqueeze(1), x, 0.0)
+        out_lens = ((n * ln + (o - 1)) // o).to(torch.int32)
+    m = torch.arange(Lout, device=dev)
+    f = m // n
+    p = m - f * n
+    reach = (-(-Lout // n) - 1) * o + 2 * w + o                  # one past the last padded index a tap can touch
+    xp = torch.nn.functional.pad(x, (w, max(reach - w - Lm, 0)))
+    at = f * o + first.long()[p]                                 # padded index of each output's first tap
+    acc = torch.zeros(B, Lout, dtype=cd, device=dev)
+    for s in range(S):
+        acc = acc + table[:, s][p] * xp[:, at + s]
+    if out_lens is not None:
+        acc = torch.where(m.unsqueeze(0) < out_lens.unsqueeze(1), acc, 0.0)
+    return acc.to(out_dtype), out_lens
+
+
+def _rs_accept(audio, orig_rate, new_rate, lens, lowpass_filter_width, rolloff, out_dtype):
+    """the args struct (without the outputs) of a call that mopk_resample takes, None of one it refuses"""
+    if not audio.is_cuda or audio.dtype == torch.float64 or out_dtype == torch.float64:
+        return None
+    if lens is not None and lens.shape[0] > 1 and lens.stride(0) != 1:
+        return None
+    g = math.gcd(orig_rate, new_rate)
+    o, n = orig_rate // g, new_rate // g
+    B, Cn, Lm = (audio.shape[0], 1, audio.shape[1]) if audio.dim() == 2 else audio.shape
+    Lout = -(-n * Lm // o)
+    w, S = _rs_dims(o, n, lowpass_filter_width, rolloff)
+    # the envelope, before any table is built for a pair far outside it (the library's own query decides the rest)
+    if (Lm >= 2 ** 31 or Lout >= 2 ** 31 or Cn > RESAMPLE_MAX_CHANNELS or n * (S | 1) > RESAMPLE_MAX_TABLE
+            or ((RESAMPLE_TILE + n - 2) // n) * o + 2 * w + o > RESAMPLE_MAX_SPAN):
+        return None
+    _, _, table, first = _rs_tables(o, n, lowpass_filter_width, rolloff, audio.device, torch.float32)
+    a = L.ResampleArgs()
+    a.B, a.C, a.L, a.Lout, a.o, a.n, a.w, a.S, a.table_ld = B, Cn, Lm, Lout, o, n, w, S, table.shape[1]
+    a.audio_dtype = {torch.float32: L.MOPK_F32, torch.bfloat16: L.MOPK_BF16, torch.float16: L.LOG_MEL_F16, torch.int16: _RS_I16}[audio.dtype]
+    a.out_dtype = L.MOPK_BF16 if out_dtype == torch.bfloat16 else L.MOPK_F32
+    a.audio, a.audio_sb, a.audio_sl = audio.data_ptr(), audio.stride(0), audio.stride(-1)
+    a.audio_sc = audio.stride(1) if audio.dim() == 3 else 0
+    a.lens, a.table, a.first = _ptr(lens), table.data_ptr(), first.data_ptr()
+    a.out = a.table                                                                # a stand-in: only its alignment is looked at
+    return a if L.lib().mopk_resample_supported(C.byref(a)) else None
+
+
+def resample_supported(audio: torch.Tensor, orig_rate: int, new_rate: int, lens: Optional[torch.Tensor] = None, *,
+                       lowpass_filter_width: int = 6, rolloff: float = 0.99, out_dtype: torch.dtype = torch.float32) -> bool:
+    """True if mopk_resample takes this call.  The envelope, with o / n the rates over their gcd, w = ceil(lpw o / base),
+    S = floor(2 lpw o / base) + 1 and base = min(o, n) rolloff: CUDA float32 / bfloat16 / float16 / int16 audio of ANY element
+    strides (no copy is made), out_dtype float32 or bfloat16, a contiguous lens; B <= 65535, C <= RESAMPLE_MAX_CHANNELS = 64,
+    L < 2^31 and ceil(n L / o) < 2^31; a staged span ((RESAMPLE_TILE + n - 2) // n) o + 2 w + o <= RESAMPLE_MAX_SPAN = 12288 samples
+    (48 KiB of LDS: o / n up to 11 at the default width, e.g. 176.4 kHz -> 16 kHz; S is bounded with it, S <= 2 w + o); a
+    table of n (S | 1) <= RESAMPLE_MAX_TABLE = 2^22 taps (16 MiB; it sits in LDS when span and table fit 64 KiB together, else it is
+    read through L2).  Every pair of 8000, 11025, 12000, 22050, 24000, 32000, 44100, 48000, 96000 -> 16000 is inside, as are the
+    abstract pairs (2, 3) and (3, 2), all with the table in LDS.  Raises ValueError on bad arguments."""
+    _rs_check(audio, orig_rate, new_rate, lens, lowpass_filter_width, rolloff, out_dtype, "resample_supported")
+    return _rs_accept(audio, orig_rate, new_rate, lens, lowpass_filter_width, rolloff, out_dtype) is not None
+
+
+def resample(audio: torch.Tensor, orig_rate: int, new_rate: int, lens: Optional[torch.Tensor] = None, *,
+             lowpass_filter_width: int = 6, rolloff: float = 0.99, out_dtype: torch.dtype = torch.float32):
+    """Sample-rate conversion of a batch of clips from orig_rate to new_rate -> (out (B, ceil(n L / o)) in out_dtype, out_lens
+    int32 (B,) on the device, or None without lens): the stage in front of `log_mel`.  Inference only.
+
+    audio: (B, L), or (B, C, L) whose channels are averaged (summed in ascending order in fp32, times the fp32 reciprocal of C); float32 /
+    bfloat16 / float16 samples as they are, int16 times 2^-15 (Whisper's / 32768); any strides, so a channel-first tensor and the
+    transposed view of a channel-last one both go to the kernel without a copy.  lens: int32 (B,) DEVICE tensor of sample counts
+    (None: L), clamped into [0, L].
+    The definition (the windowed-sinc, Hann, polyphase resampler): g = gcd(orig, new), o = orig / g, n = new / g, lpw =
+    lowpass_filter_width, base = min(o, n) rolloff, w = ceil(lpw o / base).  Tap j in [0, 2 w + o) of phase p in [0, n):
+    t = clamp((-p / n + (j - w) / o) base, -lpw, lpw), K[p, j] = (base / o) cos(t pi / (2 lpw))^2 sinc(pi t), sinc(0) = 1.  Clip b
+    of len_b samples, zero outside [0, len_b): y[f n + p] = sum_j K[p, j] x[f o + j - w] for f n + p < len_out_b = ceil(n len_b
+    / o); samples >= len_out_b of the row are zeros, out_lens[b] = len_out_b.  orig_rate == new_rate is the identity: the
+    converted, downmixed samples exactly.  K is built in float64 on the host and rounded once to fp32, per (o, n, lpw, rolloff,
+    device); only the S = floor(2 lpw o / base) + 1 taps per phase with |t| < lpw are kept (the others are zeros in fp32).
+    Runs the HIP kernel (mopk_resample: one launch, an fp32 fmaf chain over the S taps in ascending order) when
+    resample_supported() accepts the call, else resample_torch(); LAST_PATH["resample"] records which.  No host sync; bitwise
+    reproducible; every clip comes out bit for bit as it would alone."""
+    _rs_check(audio, orig_rate, new_rate, lens, lowpass_filter_width, rolloff, out_dtype, "resample")
+    with torch.no_grad():
+        a = _rs_accept(audio, orig_rate, new_rate, lens, lowpass_filter_width, rolloff, out_dtype)
+        if a is None:
+            LAST_PATH["resample"] = L.PATH_GENERIC
+            return resample_torch(audio, orig_rate, new_rate, lens, lowpass_filter_width=lowpass_filter_width, rolloff=rolloff,
+                                  out_dtype=out_dtype)
+        out = torch.empty(a.B, a.Lout, dtype=out_dtype, device=audio.device)
+        out_lens = torch.empty(a.B, dtype=torch.int32, device=audio.device) if lens is not None else None
+        a.out, a.out_lens = out.data_ptr(), _ptr(out_lens)                         # in place of the stand-in
+        _row_launch(a, "mopk_resample", "resample")
+        return out, out_lens
+
+
 from . import mel_gate_fn as _mel_gate_fn  # noqa: E402  (it reads this module's helpers, all defined by now)
