@@ -133,6 +133,19 @@ def test_support_query_needs_no_gpu(lib):
     assert lib.mopk_moe_workspace_bytes(C.byref(_args(M=0)), 1) == 0
 
 
+def test_support_query_at_the_int32_element_bound(lib):
+    """M F and M D stay below 2^31 (the kernels index rows with int64 but the scan and the tile walk count in int32): the largest
+    accepted products with D, F multiples of 8 and the first refused ones"""
+    ok = lambda a: lib.mopk_moe_supported(C.byref(a))
+    assert (2 ** 20 - 1) * 2048 == 2 ** 31 - 2048
+    assert ok(_args(M=2 ** 20 - 1, D=8, F=2048, E=2)) == 1
+    assert ok(_args(M=2 ** 20, D=8, F=2048, E=2)) == 0
+    assert ok(_args(M=2 ** 20 - 1, D=2048, F=8, E=2)) == 1
+    assert ok(_args(M=2 ** 20, D=2048, F=8, E=2)) == 0
+    assert ok(_args(M=2 ** 20 - 1, D=2048, F=2048, E=2, prec=0)) == 1
+    assert ok(_args(M=2 ** 20, D=8, F=8, E=2)) == 1
+
+
 def test_bad_arguments_return_before_any_launch(lib):
     from mop_amd import _lib
     for fn in (lib.mopk_moe_route, lib.mopk_moe_fwd, lib.mopk_moe_bwd):
