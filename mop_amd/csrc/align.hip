@@ -147,22 +147,15 @@ int ac_check(const MopkAlignCostArgs *a) {
     if (a->width < 1 || a->width % 2 == 0) return MOPK_ERR_BAD_ARG;
     if (a->cost_ld < a->M) return MOPK_ERR_BAD_ARG;
     if (a->N > AC_MAXN || a->width > AC_MAXWIDTH || a->B > 65535) return MOPK_ERR_UNSUPPORTED;
-    if (((uintptr_t)a->probs & 3) || ((uintptr_t)a->cost & 3) || ((uintptr_t)a->n_tokens & 3) || ((uintptr_t)a->n_frames & 3))
-        return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->probs, a->cost, a->n_tokens, a->n_frames)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
 template <int WIDTH> int ac_launch(const MopkAlignCostArgs *a, hipStream_t st) {
     const size_t lds = ac_lds_bytes(a->N, WIDTH);
     const int tile = 1 << ac_tile_log2(a->N);
-    auto kfn = ac_cost_kernel<WIDTH>;
-    static size_t lds_set = 0;                                  // sticky per instantiation; may not be set during stream capture
-    if (lds_set < lds) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MOPK_ERR_LAUNCH;
-        lds_set = lds;
-    }
-    hipLaunchKernelGGL(kfn, dim3((unsigned)((a->M + tile - 1) / tile), (unsigned)a->B), dim3(AC_THREADS), lds, st, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    // the raised dynamic-LDS limit is kept per (instantiation, device) by launch_big_lds: it may not be set during stream capture
+    return launch_big_lds<ac_cost_kernel<WIDTH>>(dim3((unsigned)((a->M + tile - 1) / tile), (unsigned)a->B), dim3(AC_THREADS), lds, st, *a);
 }
 
 // ---- dynamic time warping ----
@@ -235,9 +228,7 @@ int dtw_check(const MopkDtwArgs *a) {
     if (a->B <= 0 || a->N <= 0 || a->M <= 0) return MOPK_ERR_BAD_SHAPE;
     if (a->row0 < 0 || a->row0 >= a->N || a->cost_ld < a->M) return MOPK_ERR_BAD_ARG;
     if (a->N - a->row0 > DTW_MAXR) return MOPK_ERR_UNSUPPORTED;
-    if (((uintptr_t)a->cost & 3) || ((uintptr_t)a->n_rows & 3) || ((uintptr_t)a->n_cols & 3) || ((uintptr_t)a->starts & 3) ||
-        ((uintptr_t)a->ends & 3))
-        return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->cost, a->n_rows, a->n_cols, a->starts, a->ends)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -253,7 +244,7 @@ int mopk_alignment_cost_supported(const MopkAlignCostArgs *a) { return ac_check(
 int mopk_alignment_cost(const MopkAlignCostArgs *a, void *stream) {
     const int rc = ac_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->probs || !a->cost || !a->n_tokens || !a->n_frames) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->probs, a->cost, a->n_tokens, a->n_frames)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     switch (a->width) {
         case 1: return ac_launch<1>(a, st);
@@ -274,10 +265,10 @@ size_t mopk_dtw_workspace_bytes(const MopkDtwArgs *a) {
 int mopk_dtw_align(const MopkDtwArgs *a, void *stream) {
     const int rc = dtw_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->cost || !a->n_rows || !a->n_cols || !a->starts || !a->ends || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->cost, a->n_rows, a->n_cols, a->starts, a->ends, a->workspace)) return MOPK_ERR_BAD_ARG;
     const int threads = (a->N - a->row0 + WAVE - 1) / WAVE * WAVE;
     hipLaunchKernelGGL(dtw_kernel, dim3((unsigned)a->B), dim3(threads), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

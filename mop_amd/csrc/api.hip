@@ -48,23 +48,21 @@ static int ew_validate(const MopkEdgewiseArgs *a, bool bwd) {
         if ((x->gate_mode != 0 && x->gate_mode != 1) || x->n_lens < 0 || x->n_lens > MOPK_MAX_LENS) return MOPK_ERR_BAD_ARG;
         for (int l = 0; l < x->n_lens; ++l) if (x->lens_dil[l] < 1) return MOPK_ERR_BAD_ARG;
         if (x->n_lens > 0 && (!x->lens_w || (bwd && !x->dlens_w))) return MOPK_ERR_BAD_ARG;
-        if (dense && (!x->W1 || !x->b1 || !x->W2 || !x->b2 || (x->use_k3 && (!x->W3 || !x->b3)))) return MOPK_ERR_BAD_ARG;
-        if (dense && bwd && (!x->dW1 || !x->db1 || !x->dW2 || !x->db2 || (x->use_k3 && (!x->dW3 || !x->db3)))) return MOPK_ERR_BAD_ARG;
+        if (dense && (any_null(x->W1, x->b1, x->W2, x->b2) || (x->use_k3 && any_null(x->W3, x->b3)))) return MOPK_ERR_BAD_ARG;
+        if (dense && bwd && (any_null(x->dW1, x->db1, x->dW2, x->db2) || (x->use_k3 && any_null(x->dW3, x->db3)))) return MOPK_ERR_BAD_ARG;
         // lens banks, the 3x3 convolution and every dense-head backward: generic path only (the fused forward takes the plain dense head)
         if (a->path == MOPK_PATH_FUSED && (x->n_lens > 0 || (dense && x->use_k3))) return MOPK_ERR_UNSUPPORTED;
         // extra feature channels (given as row / column means): low-rank head on the fused path only
-        if (x->n_extra < 0 || (x->n_extra > 0 && (!x->row_extra || !x->col_extra || (bwd && (!x->d_row_extra || !x->d_col_extra))))) return MOPK_ERR_BAD_ARG;
+        if (x->n_extra < 0 || (x->n_extra > 0 && (any_null(x->row_extra, x->col_extra) || (bwd && any_null(x->d_row_extra, x->d_col_extra))))) return MOPK_ERR_BAD_ARG;
         if (x->n_extra > 0 && (dense || x->n_lens > 0 || a->path != MOPK_PATH_FUSED)) return MOPK_ERR_UNSUPPORTED;
     }
-    if (!a->q.ptr || !a->k.ptr || !a->v0.ptr || !a->vL.ptr || !a->sqk || !a->vs0 || !a->vsL || !a->chain_logit || !a->saved ||
-        !a->workspace)
+    if (any_null(a->q.ptr, a->k.ptr, a->v0.ptr, a->vL.ptr, a->sqk, a->vs0, a->vsL, a->chain_logit, a->saved, a->workspace))
         return MOPK_ERR_BAD_ARG;
-    if (!dense && (!a->Wr || !a->br || !a->Wc || !a->bc)) return MOPK_ERR_BAD_ARG;
+    if (!dense && any_null(a->Wr, a->br, a->Wc, a->bc)) return MOPK_ERR_BAD_ARG;
     if (!bwd && !a->y.ptr) return MOPK_ERR_BAD_ARG;
-    if (bwd && (!a->dy.ptr || !a->dq.ptr || !a->dk_.ptr || !a->dv0.ptr || !a->dvL.ptr || !a->dsqk_part ||
-                !a->dvs0_part || !a->dvsL_part || !a->dlogit_part))
+    if (bwd && any_null(a->dy.ptr, a->dq.ptr, a->dk_.ptr, a->dv0.ptr, a->dvL.ptr, a->dsqk_part, a->dvs0_part, a->dvsL_part, a->dlogit_part))
         return MOPK_ERR_BAD_ARG;
-    if (bwd && !dense && (!a->dWr || !a->dbr || !a->dWc || !a->dbc)) return MOPK_ERR_BAD_ARG;
+    if (bwd && !dense && any_null(a->dWr, a->dbr, a->dWc, a->dbc)) return MOPK_ERR_BAD_ARG;
     if ((a->q.sv == 0) != (a->k.sv == 0)) return MOPK_ERR_BAD_ARG;
     if (bwd && ((a->dq.sv == 0) != (a->q.sv == 0) || (a->dk_.sv == 0) != (a->k.sv == 0))) return MOPK_ERR_BAD_ARG;
     return MOPK_OK;
@@ -132,7 +130,7 @@ int mopk_edgewise_lowrank_fwd(const MopkEdgewiseArgs *a, void *stream) {
     return mopk_edgewise_fwd(a, stream);
 }
 int mopk_edgewise_reduce_parts(const MopkEdgewiseArgs *a, float *dsqk, float *dvs0, float *dvsL, float *dlogit, void *stream) {
-    if (!a || !dsqk || !dvs0 || !dvsL || !dlogit || !a->dsqk_part || !a->dvs0_part || !a->dvsL_part || !a->dlogit_part)
+    if (!a || any_null(dsqk, dvs0, dvsL, dlogit, a->dsqk_part, a->dvs0_part, a->dvsL_part, a->dlogit_part))
         return MOPK_ERR_BAD_ARG;
     if (a->B <= 0 || a->H <= 0 || a->V <= 0 || a->dk <= 0) return MOPK_ERR_BAD_SHAPE;
     return ew_reduce_parts(a, dsqk, dvs0, dvsL, dlogit, (hipStream_t)stream);
@@ -143,7 +141,6 @@ int mopk_edgewise_lowrank_bwd(const MopkEdgewiseArgs *a, void *stream) {
 }
 
 // ---- sibling cores (generic multi-kernel paths, attn_generic.hip) ----
-static bool v4ok(const MopkView4 &v) { return v.ptr != nullptr; }
 static int base_ok(int B, int H, int N, int dk, int io, int prec) {
     if (B <= 0 || H <= 0 || N <= 0 || dk <= 0) return MOPK_ERR_BAD_SHAPE;
     if ((io != MOPK_F32 && io != MOPK_BF16) || (prec != MOPK_PREC_FP32 && prec != MOPK_PREC_BF16)) return MOPK_ERR_BAD_ARG;
@@ -175,7 +172,7 @@ size_t mopk_sdpa_workspace_bytes(const MopkSdpaArgs *a) {
 }
 int mopk_sdpa_fwd(const MopkSdpaArgs *a, void *stream) {
     int rc = sdpa_check(a); if (rc) return rc;
-    if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !a->saved || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
     if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return MOPK_ERR_BAD_ARG;
     if (sdpa_use_flash(a, false)) return sdpa_flash_fwd(a, (hipStream_t)stream);
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
@@ -183,8 +180,7 @@ int mopk_sdpa_fwd(const MopkSdpaArgs *a, void *stream) {
 }
 int mopk_sdpa_bwd(const MopkSdpaArgs *a, void *stream) {      // the fused path also reads `y` (the forward's output)
     int rc = sdpa_check(a); if (rc) return rc;
-    if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !v4ok(a->dy) || !v4ok(a->dq) || !v4ok(a->dk_) || !v4ok(a->dv) ||
-        !a->saved || !a->workspace)
+    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->dy.ptr, a->dq.ptr, a->dk_.ptr, a->dv.ptr, a->saved, a->workspace))
         return MOPK_ERR_BAD_ARG;
     if (sdpa_use_flash(a, false)) return sdpa_flash_bwd(a, (hipStream_t)stream);   // same decision as the forward (saved layout)
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
@@ -195,7 +191,7 @@ static int sdpa_lens_check(const MopkSdpaLensArgs *a) {
     if (!a) return MOPK_ERR_BAD_ARG;
     int rc = sdpa_check(&a->base); if (rc) return rc;
     if (a->base.mask || a->base.bias) return MOPK_ERR_BAD_ARG;              // a mask / bias tensor goes with mopk_sdpa_*, not with lengths
-    if (((uintptr_t)a->q_lens & 3) || ((uintptr_t)a->kv_lens & 3)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->q_lens, a->kv_lens)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 int mopk_sdpa_lens_supported(const MopkSdpaLensArgs *a) { return sdpa_lens_check(a) == MOPK_OK && mopk_sdpa_fused_supported(&a->base); }
@@ -204,7 +200,7 @@ size_t mopk_sdpa_lens_workspace_bytes(const MopkSdpaLensArgs *a) { return sdpa_l
 int mopk_sdpa_lens_fwd(const MopkSdpaLensArgs *l, void *stream) {
     int rc = sdpa_lens_check(l); if (rc) return rc;
     const MopkSdpaArgs *a = &l->base;
-    if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !a->saved || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
     if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return MOPK_ERR_BAD_ARG;
     if (sdpa_use_flash(a, false)) return sdpa_flash_lens_fwd(a, l->q_lens, l->kv_lens, (hipStream_t)stream);
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
@@ -213,8 +209,7 @@ int mopk_sdpa_lens_fwd(const MopkSdpaLensArgs *l, void *stream) {
 int mopk_sdpa_lens_bwd(const MopkSdpaLensArgs *l, void *stream) {
     int rc = sdpa_lens_check(l); if (rc) return rc;
     const MopkSdpaArgs *a = &l->base;
-    if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !v4ok(a->dy) || !v4ok(a->dq) || !v4ok(a->dk_) || !v4ok(a->dv) ||
-        !a->saved || !a->workspace)
+    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->dy.ptr, a->dq.ptr, a->dk_.ptr, a->dv.ptr, a->saved, a->workspace))
         return MOPK_ERR_BAD_ARG;
     if (sdpa_use_flash(a, false)) return sdpa_flash_lens_bwd(a, l->q_lens, l->kv_lens, (hipStream_t)stream);
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
@@ -225,10 +220,10 @@ size_t mopk_crossview_workspace_bytes(const MopkCrossViewArgs *a) { return (a &&
 static int cv_validate(const MopkCrossViewArgs *a, bool bwd) {
     if (!a) return MOPK_ERR_BAD_ARG;
     int rc = base_ok(a->B, a->H, a->N, a->dk, a->io_dtype, a->precision); if (rc) return rc;
-    if (!v4ok(a->q1) || !v4ok(a->k1) || !v4ok(a->v1) || !v4ok(a->q2) || !v4ok(a->k2) || !a->mix || !a->saved || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->q1.ptr, a->k1.ptr, a->v1.ptr, a->q2.ptr, a->k2.ptr, a->mix, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
     if (a->anchor_mode < 0 || a->anchor_mode > 2 || a->dropout_p < 0.f || a->dropout_p >= 1.f) return MOPK_ERR_BAD_ARG;
-    if (!bwd && !v4ok(a->y)) return MOPK_ERR_BAD_ARG;
-    if (bwd && (!v4ok(a->dy) || !v4ok(a->dq1) || !v4ok(a->dk1) || !v4ok(a->dv1) || !v4ok(a->dq2) || !v4ok(a->dk2) || !a->dmix_part)) return MOPK_ERR_BAD_ARG;
+    if (!bwd && !a->y.ptr) return MOPK_ERR_BAD_ARG;
+    if (bwd && any_null(a->dy.ptr, a->dq1.ptr, a->dk1.ptr, a->dv1.ptr, a->dq2.ptr, a->dk2.ptr, a->dmix_part)) return MOPK_ERR_BAD_ARG;
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
@@ -244,9 +239,9 @@ int mopk_dualpath_fwd(const MopkDualPathArgs *a, void *stream) {
     if (!a) return MOPK_ERR_BAD_ARG;
     int rc = base_ok(a->B, a->H, a->N, a->dk, a->io_dtype, a->precision); if (rc) return rc;
     if (a->hops < 2 && a->hops != 0) return MOPK_ERR_BAD_SHAPE;
-    if (!v4ok(a->q1) || !v4ok(a->k1) || !v4ok(a->v1) || !v4ok(a->q2) || !v4ok(a->k2) || !v4ok(a->y) || !a->saved || !a->workspace)
+    if (any_null(a->q1.ptr, a->k1.ptr, a->v1.ptr, a->q2.ptr, a->k2.ptr, a->y.ptr, a->saved, a->workspace))
         return MOPK_ERR_BAD_ARG;
-    if (a->hops > 0 && (!v4ok(a->v2) || !a->chain_logit)) return MOPK_ERR_BAD_ARG;
+    if (a->hops > 0 && any_null(a->v2.ptr, a->chain_logit)) return MOPK_ERR_BAD_ARG;
     if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return MOPK_ERR_BAD_ARG;
     if (dp_use_flash(a)) return dp_flash_fwd(a, (hipStream_t)stream);
     if (a->path == MOPK_PATH_FUSED || a->hops == 0) return MOPK_ERR_UNSUPPORTED;   // hops == 0 (no transport term) exists on the fused kernels only
@@ -256,10 +251,8 @@ int mopk_dualpath_bwd(const MopkDualPathArgs *a, void *stream) {
     if (!a) return MOPK_ERR_BAD_ARG;
     int rc = base_ok(a->B, a->H, a->N, a->dk, a->io_dtype, a->precision); if (rc) return rc;
     if (a->hops < 2 && a->hops != 0) return MOPK_ERR_BAD_SHAPE;
-    if (!v4ok(a->q1) || !v4ok(a->k1) || !v4ok(a->v1) || !v4ok(a->q2) || !v4ok(a->k2) || !v4ok(a->y) ||
-        !v4ok(a->dy) || !v4ok(a->dq1) || !v4ok(a->dk1) || !v4ok(a->dv1) || !v4ok(a->dq2) || !v4ok(a->dk2) ||
-        !a->dlogit_part || !a->saved || !a->workspace) return MOPK_ERR_BAD_ARG;
-    if (a->hops > 0 && (!v4ok(a->v2) || !v4ok(a->dv2) || !a->chain_logit)) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->q1.ptr, a->k1.ptr, a->v1.ptr, a->q2.ptr, a->k2.ptr, a->y.ptr, a->dy.ptr, a->dq1.ptr, a->dk1.ptr, a->dv1.ptr, a->dq2.ptr, a->dk2.ptr, a->dlogit_part, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
+    if (a->hops > 0 && any_null(a->v2.ptr, a->dv2.ptr, a->chain_logit)) return MOPK_ERR_BAD_ARG;
     if (dp_use_flash(a)) return dp_flash_bwd(a, (hipStream_t)stream);        // same decision as the forward (saved layout)
     if (a->path == MOPK_PATH_FUSED || a->hops == 0) return MOPK_ERR_UNSUPPORTED;
     return dp_bwd(a, (hipStream_t)stream);
@@ -273,8 +266,8 @@ size_t mopk_quartet_workspace_bytes(const MopkQuartetArgs *a) { return !qt_ok(a)
 int mopk_quartet_fwd(const MopkQuartetArgs *a, void *stream) {
     if (!a) return MOPK_ERR_BAD_ARG;
     int rc = base_ok(a->B, a->H, a->T, a->dh, a->io_dtype, a->precision); if (rc) return rc;
-    if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !a->saved || !a->workspace) return MOPK_ERR_BAD_ARG;
-    if (a->use_quartet && (!v4ok(a->q2) || !v4ok(a->k2) || !a->mixture || !a->quartet_scale)) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
+    if (a->use_quartet && any_null(a->q2.ptr, a->k2.ptr, a->mixture, a->quartet_scale)) return MOPK_ERR_BAD_ARG;
     if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return MOPK_ERR_BAD_ARG;
     if (qt_use_flash(a)) return qt_flash_fwd(a, (hipStream_t)stream);
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
@@ -283,10 +276,8 @@ int mopk_quartet_fwd(const MopkQuartetArgs *a, void *stream) {
 int mopk_quartet_bwd(const MopkQuartetArgs *a, void *stream) {    // the fused path also reads `y` (the forward's output)
     if (!a) return MOPK_ERR_BAD_ARG;
     int rc = base_ok(a->B, a->H, a->T, a->dh, a->io_dtype, a->precision); if (rc) return rc;
-    if (!v4ok(a->q) || !v4ok(a->k) || !v4ok(a->v) || !v4ok(a->y) || !v4ok(a->dy) || !v4ok(a->dq) || !v4ok(a->dk_) || !v4ok(a->dv) ||
-        !a->saved || !a->workspace) return MOPK_ERR_BAD_ARG;
-    if (a->use_quartet && (!v4ok(a->q2) || !v4ok(a->k2) || !v4ok(a->dq2) || !v4ok(a->dk2) || !a->dmixture_part || !a->dqscale_part ||
-                           !a->mixture || !a->quartet_scale)) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->dy.ptr, a->dq.ptr, a->dk_.ptr, a->dv.ptr, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
+    if (a->use_quartet && any_null(a->q2.ptr, a->k2.ptr, a->dq2.ptr, a->dk2.ptr, a->dmixture_part, a->dqscale_part, a->mixture, a->quartet_scale)) return MOPK_ERR_BAD_ARG;
     if (qt_use_flash(a)) return qt_flash_bwd(a, (hipStream_t)stream);
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
     return qt_bwd(a, (hipStream_t)stream);

@@ -37,15 +37,13 @@ static int gather(int io, const MopkView4 &v, float *out, const Dm &d, hipStream
     const int64_t tot = d.BH * d.N * d.dk;
     if (io == MOPK_BF16) hipLaunchKernelGGL((gather_kernel<unsigned short>), dim3((tot + 255) / 256), dim3(256), 0, st, v, out, d);
     else hipLaunchKernelGGL((gather_kernel<float>), dim3((tot + 255) / 256), dim3(256), 0, st, v, out, d);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 static int scatter(int io, const float *in, const MopkView4 &v, const Dm &d, hipStream_t st) {
     const int64_t tot = d.BH * d.N * d.dk;
     if (io == MOPK_BF16) hipLaunchKernelGGL((scatter_kernel<unsigned short>), dim3((tot + 255) / 256), dim3(256), 0, st, in, v, d);
     else hipLaunchKernelGGL((scatter_kernel<float>), dim3((tot + 255) / 256), dim3(256), 0, st, in, v, d);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 struct MaskSpec {
@@ -107,8 +105,7 @@ static int zero_tail(float *buf, const Dm &d, const int32_t *lens, hipStream_t s
     if (!lens) return MOPK_OK;
     const int64_t tot = d.BH * d.N * d.dk;
     hipLaunchKernelGGL(zero_tail_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, buf, d, lens);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 static inline GemmDesc gd0(int M, int N, int K, int nb) {
@@ -201,7 +198,7 @@ int sdpa_lens_fwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int32_t *k
     const int64_t rows = d.BH * d.N;
     hipLaunchKernelGGL(masked_softmax_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.P, b.P, d, m);
     if (a->dropout_p > 0.f) drop_map(b.P, b.dP, d, a->dropout_p, a->dropout_seed, st);     // dropped weights in a workspace plane; P stays in `saved`
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     RET_IF(gemm_map_vec(a->dropout_p > 0.f ? b.dP : b.P, false, b.v, b.y, d, 1.f, 0.f, mf, st));
     return scatter(a->io_dtype, b.y, a->y, d, st);
 }
@@ -215,7 +212,7 @@ int sdpa_lens_bwd(const MopkSdpaArgs *a, const int32_t *q_lens, hipStream_t st) 
     RET_IF(zero_tail(b.dy, d, q_lens, st));
     RET_IF(drop_bwd_pair(b.P, b.dy, b.v, b.dP, b.dv, d, a->dropout_p, a->dropout_seed, mf, st));
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.P, b.dP, d, 1.f / sqrtf((float)d.dk));
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     RET_IF(gemm_map_vec(b.dP, false, b.k, b.dq, d, 1.f, 0.f, mf, st));
     RET_IF(gemm_map_vec(b.dP, true, b.q, b.dk, d, 1.f, 0.f, mf, st));
     RET_IF(scatter(a->io_dtype, b.dq, a->dq, d, st)); RET_IF(scatter(a->io_dtype, b.dk, a->dk_, dkey, st));
@@ -351,14 +348,14 @@ int dp_fwd(const MopkDualPathArgs *a, hipStream_t st) {
     const MaskSpec m = dp_mask(a);
     hipLaunchKernelGGL(masked_softmax_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.S1, b.A1, d, m);   // :206
     hipLaunchKernelGGL(masked_softmax_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.S2, b.A2, d, m);   // :207
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     const float *Tprev = b.A1;                                                        // :214-216
     for (int i = 1; i < a->hops; ++i) {
         RET_IF(gemm_map_map(Tprev, false, b.A2, false, b.T + (size_t)(i - 1) * nn, d, 0.f, mf, st));
         Tprev = b.T + (size_t)(i - 1) * nn;
     }
     hipLaunchKernelGGL(dp_mix_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, *a, d, b, Tprev, m);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     for (int i = 1; i < a->hops; ++i)                                                 // :224-226
         RET_IF(gemm_map_vec(b.A2, false, b.tr + (size_t)(i - 1) * nd, b.tr + (size_t)i * nd, d, 1.f, 0.f, mf, st));
     RET_IF(gemm_map_vec(b.A1, false, b.tr + (size_t)(a->hops - 1) * nd, b.ychain, d, 1.f, 0.f, mf, st));   // :227
@@ -366,8 +363,7 @@ int dp_fwd(const MopkDualPathArgs *a, hipStream_t st) {
     RET_IF(gemm_map_vec(a->dropout_p > 0.f ? b.dP : b.P, false, b.v1, b.ybase, d, 1.f, 0.f, mf, st));
     if (a->io_dtype == MOPK_BF16) hipLaunchKernelGGL((combine2_kernel<unsigned short>), dim3((nd + 255) / 256), dim3(256), 0, st, b.ybase, b.ychain, b.wsig, a->y, d);
     else hipLaunchKernelGGL((combine2_kernel<float>), dim3((nd + 255) / 256), dim3(256), 0, st, b.ybase, b.ychain, b.wsig, a->y, d);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 int dp_bwd(const MopkDualPathArgs *a, hipStream_t st) {
     const Dm d = mkdm(a->B, a->H, a->N, a->dk);
@@ -397,7 +393,7 @@ int dp_bwd(const MopkDualPathArgs *a, hipStream_t st) {
     RET_IF(scatter(a->io_dtype, gt, a->dv2, d, st));                                 // dv2
     const float *Cf = hops >= 2 ? b.T + (size_t)(hops - 2) * nn : b.A1;
     hipLaunchKernelGGL(dp_mix_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, *a, d, b, Cf, m);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     if (a->g_chain != 0.f) {                                                          // chain T_i = T_{i-1} A2
         const float *D = b.dC;
         float *pp[2] = {b.D0, b.D1};
@@ -409,11 +405,11 @@ int dp_bwd(const MopkDualPathArgs *a, hipStream_t st) {
             D = pp[cur]; cur ^= 1;
         }
         hipLaunchKernelGGL(axpy2_kernel, dim3((nn + 255) / 256), dim3(256), 0, st, b.dA1, D, nn);   // dA1 += D
-        MOPK_CHECK_LAUNCH();
+        if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     }
     hipLaunchKernelGGL(dp_final_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.A1, b.dA1, b.dS1, d, sc);
     hipLaunchKernelGGL(dp_final_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.A2, b.dA2, b.dS2, d, sc);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     RET_IF(gemm_map_vec(b.dS1, false, b.k1, b.dq, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dq, a->dq1, d, st));
     RET_IF(gemm_map_vec(b.dS1, true, b.q1, b.dk, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dk, a->dk1, d, st));
     RET_IF(gemm_map_vec(b.dS2, false, b.k2, b.dq, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dq, a->dq2, d, st));
@@ -555,7 +551,7 @@ int qt_fwd(const MopkQuartetArgs *a, hipStream_t st) {
         drop_map(b.P, b.dP, d, a->dropout_p, a->dropout_seed, st);
         if (a->attn) hipLaunchKernelGGL(drop_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.P, d.LD, a->attn, d.N, fa_drop(a->dropout_p, a->dropout_seed), rows, d.N, d.N);
     }
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     RET_IF(gemm_map_vec(a->dropout_p > 0.f ? b.dP : b.P, false, b.v, b.y, d, 1.f, 0.f, mf, st));   // :121
     return scatter(a->io_dtype, b.y, a->y, d, st);
 }
@@ -569,20 +565,20 @@ int qt_bwd(const MopkQuartetArgs *a, hipStream_t st) {
     RET_IF(drop_bwd_pair(b.P, b.dy, b.v, b.dP, b.dv, d, a->dropout_p, a->dropout_seed, mf, st));
     RET_IF(scatter(a->io_dtype, b.dv, a->dv, d, st));
     hipLaunchKernelGGL(qt_mix_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, *a, d, b);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     const float eps1 = a->use_quartet ? a->eps : 1e-5f;
     hipLaunchKernelGGL(znorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.dP, b.z1, b.sd1, d, eps1, sc);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     RET_IF(gemm_map_vec(b.dP, false, b.k, b.dq, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dq, a->dq, d, st));
     RET_IF(gemm_map_vec(b.dP, true, b.q, b.dk, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dk, a->dk_, d, st));
     if (a->use_quartet) {
         hipLaunchKernelGGL(znorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.dz2, b.z2, b.sd2, d, a->eps, sc);
-        MOPK_CHECK_LAUNCH();
+        if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
         RET_IF(gemm_map_vec(b.dz2, false, b.k2, b.dq, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dq, a->dq2, d, st));
         RET_IF(gemm_map_vec(b.dz2, true, b.q2, b.dk, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dk, a->dk2, d, st));
         hipLaunchKernelGGL(rowsum_part_kernel, dim3((int)d.BH), dim3(256), 0, st, b.rowdm, a->dmixture_part, d.N);
         hipLaunchKernelGGL(rowsum_part_kernel, dim3((int)d.BH), dim3(256), 0, st, b.rowdqs, a->dqscale_part, d.N);
-        MOPK_CHECK_LAUNCH();
+        if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     }
     return MOPK_OK;
 }
@@ -752,7 +748,7 @@ int cv_fwd(const MopkCrossViewArgs *a, hipStream_t st) {
     }
     const float *Aw = prior ? b.A : b.P;
     if (a->dropout_p > 0.f) { drop_map(Aw, b.dA, d, a->dropout_p, a->dropout_seed, st); Aw = b.dA; }                     // :151 (workspace plane)
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     RET_IF(gemm_map_vec(Aw, false, b.v1, b.y, d, 1.f, 0.f, mf, st));                                                     // :152
     return scatter(a->io_dtype, b.y, a->y, d, st);
 }
@@ -775,7 +771,7 @@ int cv_bwd(const MopkCrossViewArgs *a, hipStream_t st) {
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.P, b.dS, d, 1.f);
     hipLaunchKernelGGL(cv_dmix_kernel, dim3((unsigned)d.BH), dim3(256), 0, st, b, d, a->dmix_part);
     hipLaunchKernelGGL(cv_ds_kernel, pix, dim3(256), 0, st, b, d, a->mix, a->t1, a->t2, sc, prior ? 1 : 0);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     RET_IF(gemm_map_vec(b.g1, false, b.k1, b.dq1, d, 1.f, 0.f, mf, st)); RET_IF(gemm_map_vec(b.g12, false, b.k2, b.dq1, d, 1.f, 1.f, mf, st));
     RET_IF(gemm_map_vec(b.g1, true, b.q1, b.dk1, d, 1.f, 0.f, mf, st)); RET_IF(gemm_map_vec(b.g21, true, b.q2, b.dk1, d, 1.f, 1.f, mf, st));
     RET_IF(gemm_map_vec(b.g2, false, b.k2, b.dq2, d, 1.f, 0.f, mf, st)); RET_IF(gemm_map_vec(b.g21, false, b.k1, b.dq2, d, 1.f, 1.f, mf, st));

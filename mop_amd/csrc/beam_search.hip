@@ -291,7 +291,7 @@ int bs_check(const MopkBeamArgs *a) {
     if (!(a->length_penalty == a->length_penalty) || a->length_penalty == INFINITY || a->length_penalty == -INFINITY)
         return MOPK_ERR_BAD_ARG;
     const int es = a->logits_dtype == MOPK_BF16 ? 2 : 4;
-    if ((uintptr_t)a->logits % es || (uintptr_t)a->workspace & 15) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(es - 1, a->logits) || misaligned(15, a->workspace)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -321,8 +321,7 @@ size_t mopk_beam_workspace_bytes(const MopkBeamArgs *a) {
 int mopk_beam_step(const MopkBeamArgs *a, void *stream) {
     const int rc = bs_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->logits || !a->pos || !a->scores || !a->next_ids || !a->parents || !a->hist || !a->rows || !a->fin_tokens ||
-        !a->fin_scores || !a->fin_count || !a->done || !a->workspace)
+    if (any_null(a->logits, a->pos, a->scores, a->next_ids, a->parents, a->hist, a->rows, a->fin_tokens, a->fin_scores, a->fin_count, a->done, a->workspace))
         return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     switch (a->K) {
@@ -335,7 +334,7 @@ int mopk_beam_step(const MopkBeamArgs *a, void *stream) {
         case 7: bs_launch<14>(a, st); break;
         default: bs_launch<16>(a, st); break;
     }
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

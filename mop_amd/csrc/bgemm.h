@@ -215,7 +215,7 @@ inline int bgemm(const GemmDesc &d, bool mfma, hipStream_t st) {
     const bool akc = d.a_cs == 1, bnc = d.b_cs == 1;
     if (mfma) {
         // 16-byte loads need the contiguous index to be stride 1 and every other stride / the base to keep 16-byte alignment
-        auto al = [](const float *p, int64_t s0, int64_t s1, int64_t s2) { return ((uintptr_t)p % 16 == 0) && s0 % 4 == 0 && s1 % 4 == 0 && s2 % 4 == 0; };
+        auto al = [](const float *p, int64_t s0, int64_t s1, int64_t s2) { return !misaligned(15, p) && s0 % 4 == 0 && s1 % 4 == 0 && s2 % 4 == 0; };
         const bool vecA = akc ? al(d.A, d.a_rs, d.a_b0, d.a_b1) : (d.a_rs == 1 && al(d.A, d.a_cs, d.a_b0, d.a_b1));
         const bool vecB = bnc ? al(d.B, d.b_rs, d.b_b0, d.b_b1) : (d.b_rs == 1 && al(d.B, d.b_cs, d.b_b0, d.b_b1));
         const bool big = d.M > 96 && d.N > 96;             // N x N outputs: 128 x 128 tiles; N x dk / dk x N ones stay at 64 x 64
@@ -231,8 +231,7 @@ inline int bgemm(const GemmDesc &d, bool mfma, hipStream_t st) {
         else if (bnc) MOPK_BG(false, true); else MOPK_BG(false, false);
 #undef MOPK_BG
     }
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 }  // namespace mopk

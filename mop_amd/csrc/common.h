@@ -1,4 +1,4 @@
-// Shared device/host helpers for libmopk (gfx950 only).
+// Shared device helpers for libmopk (gfx950 only); the host side of a launch is host_launch.h, included at the end.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -119,9 +119,6 @@ struct Carver {
     }
 };
 
-#define MOPK_CHECK_LAUNCH()                                   \
-    do {                                                      \
-        if (hipGetLastError() != hipSuccess) return MOPK_ERR_LAUNCH; \
-    } while (0)
-
 }  // namespace mopk
+
+#include "host_launch.h"   // every unit here holds both kernels and their entry points

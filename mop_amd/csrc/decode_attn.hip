@@ -261,8 +261,6 @@ int da_chunk(const MopkDecodeAttnArgs *a) {
 
 int da_nsplit(const MopkDecodeAttnArgs *a) { return (a->cap + da_chunk(a) - 1) / da_chunk(a); }
 
-bool da_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 int da_check(const MopkDecodeAttnArgs *a) {
     if (!a) return MOPK_ERR_BAD_ARG;
     if (a->B <= 0 || a->H <= 0 || a->Tq <= 0 || a->dk <= 0 || a->cap <= 0) return MOPK_ERR_BAD_SHAPE;
@@ -274,9 +272,8 @@ int da_check(const MopkDecodeAttnArgs *a) {
     if (da_nsplit(a) > 65535 || (int64_t)a->B * a->H > 0x7fffffff) return MOPK_ERR_UNSUPPORTED;
     const int vec = 16 / da_esize(a);                             // elements per 16-byte vector: K / V row strides
     for (const MopkView4 *t : {&a->k, &a->v})
-        if (t->sb % vec || t->sh % vec || t->sn % vec || (t->ptr && !da_al16(t->ptr))) return MOPK_ERR_UNSUPPORTED;
-    if (a->workspace && !da_al16(a->workspace)) return MOPK_ERR_UNSUPPORTED;
-    if (a->kv_len && ((uintptr_t)a->kv_len & 3)) return MOPK_ERR_UNSUPPORTED;
+        if (t->sb % vec || t->sh % vec || t->sn % vec || misaligned(15, t->ptr)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(15, a->workspace) || misaligned(3, a->kv_len)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -309,7 +306,7 @@ int da_rows_check(const MopkDecodeAttnRowsArgs *a) {
     const int rc = da_check(&a->base);
     if (rc != MOPK_OK) return rc;
     if (a->rows_ld < a->base.cap) return MOPK_ERR_BAD_SHAPE;
-    if ((uintptr_t)a->rows & 3) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->rows)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -318,10 +315,10 @@ int da_ragged_check(const MopkDecodeAttnRaggedArgs *a) {
     const int rc = da_check(&a->base);
     if (rc != MOPK_OK) return rc;
     if (!a->kv_start) return MOPK_ERR_BAD_ARG;
-    if ((uintptr_t)a->kv_start & 3) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->kv_start)) return MOPK_ERR_UNSUPPORTED;
     if (a->rows) {
         if (a->rows_ld < a->base.cap) return MOPK_ERR_BAD_SHAPE;
-        if ((uintptr_t)a->rows & 3) return MOPK_ERR_UNSUPPORTED;
+        if (misaligned(3, a->rows)) return MOPK_ERR_UNSUPPORTED;
     }
     return MOPK_OK;
 }
@@ -332,7 +329,7 @@ int da_lens_check(const MopkDecodeAttnLensArgs *a) {
     const int rc = da_check(&a->base);
     if (rc != MOPK_OK) return rc;
     if (a->base.kv_len || a->base.causal || !a->kv_lens) return MOPK_ERR_BAD_ARG;
-    if ((uintptr_t)a->kv_lens & 3) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->kv_lens)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -372,10 +369,10 @@ size_t mopk_decode_attn_workspace_bytes(const MopkDecodeAttnArgs *a) {
 int mopk_decode_attn_fwd(const MopkDecodeAttnArgs *a, void *stream) {
     const int rc = da_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->q.ptr || !a->k.ptr || !a->v.ptr || !a->y.ptr || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->workspace)) return MOPK_ERR_BAD_ARG;
     if (a->io_dtype == MOPK_BF16) da_launch<unsigned short, false>(a, nullptr, 0, (hipStream_t)stream);
     else da_launch<float, false>(a, nullptr, 0, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_decode_attn_rows_supported(const MopkDecodeAttnRowsArgs *a) { return da_rows_check(a) == MOPK_OK; }
@@ -388,10 +385,10 @@ int mopk_decode_attn_rows_fwd(const MopkDecodeAttnRowsArgs *a, void *stream) {
     const int rc = da_rows_check(a);
     if (rc != MOPK_OK) return rc;
     const MopkDecodeAttnArgs *b = &a->base;
-    if (!b->q.ptr || !b->k.ptr || !b->v.ptr || !b->y.ptr || !b->workspace || !a->rows) return MOPK_ERR_BAD_ARG;
+    if (any_null(b->q.ptr, b->k.ptr, b->v.ptr, b->y.ptr, b->workspace, a->rows)) return MOPK_ERR_BAD_ARG;
     if (b->io_dtype == MOPK_BF16) da_launch<unsigned short, true>(b, a->rows, a->rows_ld, (hipStream_t)stream);
     else da_launch<float, true>(b, a->rows, a->rows_ld, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_decode_attn_ragged_supported(const MopkDecodeAttnRaggedArgs *a) { return da_ragged_check(a) == MOPK_OK; }
@@ -404,7 +401,7 @@ int mopk_decode_attn_ragged_fwd(const MopkDecodeAttnRaggedArgs *a, void *stream)
     const int rc = da_ragged_check(a);
     if (rc != MOPK_OK) return rc;
     const MopkDecodeAttnArgs *b = &a->base;
-    if (!b->q.ptr || !b->k.ptr || !b->v.ptr || !b->y.ptr || !b->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(b->q.ptr, b->k.ptr, b->v.ptr, b->y.ptr, b->workspace)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (a->rows) {
         if (b->io_dtype == MOPK_BF16) da_launch<unsigned short, true>(b, a->rows, a->rows_ld, st, a->kv_start);
@@ -413,7 +410,7 @@ int mopk_decode_attn_ragged_fwd(const MopkDecodeAttnRaggedArgs *a, void *stream)
         if (b->io_dtype == MOPK_BF16) da_launch<unsigned short, false>(b, nullptr, 0, st, a->kv_start);
         else da_launch<float, false>(b, nullptr, 0, st, a->kv_start);
     }
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 #else  // MOPK_DECODE_LENS: the unit of the per-row key counts
@@ -429,11 +426,11 @@ int mopk_decode_attn_lens_fwd(const MopkDecodeAttnLensArgs *a, void *stream) {
     const int rc = da_lens_check(a);
     if (rc != MOPK_OK) return rc;
     const MopkDecodeAttnArgs *b = &a->base;
-    if (!b->q.ptr || !b->k.ptr || !b->v.ptr || !b->y.ptr || !b->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(b->q.ptr, b->k.ptr, b->v.ptr, b->y.ptr, b->workspace)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (b->io_dtype == MOPK_BF16) da_launch_lens<unsigned short>(b, a->kv_lens, st);
     else da_launch_lens<float>(b, a->kv_lens, st);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 #endif
 

@@ -1049,37 +1049,28 @@ int MOPK_CAT(ew_fused_fwd_nt, MOPK_INST_NT, _dk, MOPK_INST_DK)(const MopkEdgewis
     FusedDenseW dw{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
     if (dense) { dw.W1 = a->ext->W1; dw.b1 = a->ext->b1; dw.W2 = a->ext->W2; dw.b2 = a->ext->b2; }
     else if (a->ext && a->ext->n_extra > 0) { dw.E = a->ext->n_extra; dw.rowx = a->ext->row_extra; dw.colx = a->ext->col_extra; }
-#define MOPK_LAUNCH(IOT_, SAVE_, HEAD_) do {                                                                      \
-        auto kfn = ew_fused_fwd_kernel<NT, DK, IOT_, SAVE_, HEAD_>;                                               \
-        static int lds_set = 0;      /* per instantiation and per process: the attribute is sticky (and may not be set during stream capture) */ \
-        if (lds_set < lds) { if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return MOPK_ERR_LAUNCH; lds_set = lds; } \
-        hipLaunchKernelGGL(kfn, grid, block, lds, st, *a, dw);                                                    \
-    } while (0)
+    // the raised dynamic-LDS limit is kept per (instantiation, device) by launch_big_lds: it may not be set during stream capture
+#define MOPK_LAUNCH(IOT_, SAVE_, HEAD_) return launch_big_lds<ew_fused_fwd_kernel<NT, DK, IOT_, SAVE_, HEAD_>>(grid, block, lds, st, *a, dw)
     if (dense) { if (a->io_dtype == MOPK_BF16) MOPK_LAUNCH(unsigned short, true, 1); else MOPK_LAUNCH(float, true, 1); }
     else if (a->io_dtype == MOPK_BF16) { if (a->save_for_backward) MOPK_LAUNCH(unsigned short, true, 0); else MOPK_LAUNCH(unsigned short, false, 0); }
     else { if (a->save_for_backward) MOPK_LAUNCH(float, true, 0); else MOPK_LAUNCH(float, false, 0); }
 #undef MOPK_LAUNCH
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
 }
 #else
+// every per-instantiation function below is declared, and every (nt, dk) lookup written, by expanding MOPK_FUSED_INSTS
 #define MOPK_DECL(NT_, DK_) int ew_fused_fwd_nt##NT_##_dk##DK_(const MopkEdgewiseArgs *a, hipStream_t st); \
                             size_t ew_fused_saved_nt##NT_##_dk##DK_(const MopkEdgewiseArgs *a);
-MOPK_DECL(1, 16) MOPK_DECL(1, 32) MOPK_DECL(1, 64) MOPK_DECL(2, 16) MOPK_DECL(2, 32) MOPK_DECL(2, 64)
-MOPK_DECL(3, 16) MOPK_DECL(3, 32) MOPK_DECL(3, 64) MOPK_DECL(4, 16) MOPK_DECL(4, 32) MOPK_DECL(4, 64) MOPK_DECL(5, 16) MOPK_DECL(5, 32) MOPK_DECL(5, 64) MOPK_DECL(6, 16) MOPK_DECL(6, 32) MOPK_DECL(6, 64) MOPK_DECL(7, 16) MOPK_DECL(7, 32) MOPK_DECL(7, 64)
+MOPK_FUSED_INSTS(MOPK_DECL)
 #undef MOPK_DECL
-static int pick_nt(int N) { return N <= 32 ? 1 : N <= 64 ? 2 : N <= 96 ? 3 : N <= 128 ? 4 : N <= 160 ? 5 : N <= 192 ? 6 : N <= 224 ? 7 : 0; }
 int ew_fused_bwd_lds_bytes(int nt, int dk, int V);
-template <int NT, int DK> static int lds_fwd(int V) { return FusedCfg<NT, DK>::lds_bytes(V); }
 static int ew_fused_lds_bytes(int nt, int dk, int V) {
     int f = 1 << 30;
-#define MOPK_L(NT_) (dk == 16 ? lds_fwd<NT_, 16>(V) : dk == 32 ? lds_fwd<NT_, 32>(V) : lds_fwd<NT_, 64>(V))
-    switch (nt) { case 1: f = MOPK_L(1); break; case 2: f = MOPK_L(2); break; case 3: f = MOPK_L(3); break; case 4: f = MOPK_L(4); break; case 5: f = MOPK_L(5); break; case 6: f = MOPK_L(6); break; case 7: f = MOPK_L(7); break; default: break; }
+#define MOPK_L(NT_, DK_) if (nt == NT_ && dk == DK_) f = FusedCfg<NT_, DK_>::lds_bytes(V);
+    MOPK_FUSED_INSTS(MOPK_L)
 #undef MOPK_L
     const int bw = ew_fused_bwd_lds_bytes(nt, dk, V);
     return f > bw ? f : bw;
 }
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 int ew_fused_fwd_supported(const MopkEdgewiseArgs *a) {
     if (a->precision != MOPK_PREC_BF16) return 0;             // fused kernels are the bf16-MFMA path
@@ -1087,11 +1078,11 @@ int ew_fused_fwd_supported(const MopkEdgewiseArgs *a) {
     if (a->ext && a->ext->n_lens > 0) return 0;               // lens banks: generic path
     if (a->ext && a->ext->gate_mode != 0) {                   // dense gate head: forward only, without the 3x3 convolution, full record
         if (a->ext->gate_mode != 1 || a->ext->use_k3 || !a->save_for_backward) return 0;
-        if (!a->ext->W1 || !a->ext->b1 || !a->ext->W2 || !a->ext->b2) return 0;
+        if (any_null(a->ext->W1, a->ext->b1, a->ext->W2, a->ext->b2)) return 0;
         if (a->ext->n_extra != 0) return 0;                   // extra feature channels: low-rank head only
     }
     if (a->ext && a->ext->n_extra != 0) {
-        if (a->ext->n_extra < 0 || 2 * a->V + 2 + a->ext->n_extra > WST - 1 || !a->ext->row_extra || !a->ext->col_extra) return 0;
+        if (a->ext->n_extra < 0 || 2 * a->V + 2 + a->ext->n_extra > WST - 1 || any_null(a->ext->row_extra, a->ext->col_extra)) return 0;
     }
     if (a->q.sv != 0 || a->k.sv != 0) return 0;               // share_qkv only (per-view K restaging not built)
     if (pick_nt(a->N) == 0) return 0;
@@ -1100,36 +1091,23 @@ int ew_fused_fwd_supported(const MopkEdgewiseArgs *a) {
     if (ew_fused_lds_bytes(pick_nt(a->N), a->dk, a->V) > 160 * 1024) return 0;   // forward AND backward must fit
     const int es = a->io_dtype == MOPK_BF16 ? 2 : 4;
     const int64_t al = 16 / es;                               // vector loads: 8 (bf16) / 4 (fp32) element alignment
-    const MopkView4 vs[3] = {a->v0, a->vL, a->y};
-    for (const auto &v : vs) if (!aligned16(v.ptr) || v.sb % al || v.sh % al || v.sn % al) return 0;
-    if (!aligned16(a->q.ptr) || a->q.sb % al || a->q.sh % al || a->q.sn % al) return 0;
-    if (!aligned16(a->k.ptr) || a->k.sb % al || a->k.sh % al || a->k.sn % al) return 0;
-    return 1;
+    return views_aligned16(al, a->v0, a->vL, a->y, a->q, a->k);
 }
 
+// both are called for supported arguments only: (pick_nt(N), dk) is in the list
 size_t ew_fused_saved_bytes(const MopkEdgewiseArgs *a) {
-#define MOPK_DKS(NT_) switch (a->dk) { case 16: return ew_fused_saved_nt##NT_##_dk16(a); case 32: return ew_fused_saved_nt##NT_##_dk32(a); default: return ew_fused_saved_nt##NT_##_dk64(a); }
-    switch (pick_nt(a->N)) { case 1: MOPK_DKS(1) case 2: MOPK_DKS(2) case 3: MOPK_DKS(3) case 4: MOPK_DKS(4) case 5: MOPK_DKS(5) case 6: MOPK_DKS(6) case 7: MOPK_DKS(7) default: return 0; }
-#undef MOPK_DKS
+    const int nt = pick_nt(a->N);
+#define MOPK_GO(NT_, DK_) if (nt == NT_ && a->dk == DK_) return ew_fused_saved_nt##NT_##_dk##DK_(a);
+    MOPK_FUSED_INSTS(MOPK_GO)
+#undef MOPK_GO
+    return 0;
 }
 int ew_fused_fwd(const MopkEdgewiseArgs *a, hipStream_t st) {
     if (!ew_fused_fwd_supported(a)) return MOPK_ERR_UNSUPPORTED;
-#define MOPK_DK(NT_)                                                         \
-    switch (a->dk) {                                                         \
-        case 16: return ew_fused_fwd_nt##NT_##_dk16(a, st);                  \
-        case 32: return ew_fused_fwd_nt##NT_##_dk32(a, st);                  \
-        default: return ew_fused_fwd_nt##NT_##_dk64(a, st);                  \
-    }
-    switch (pick_nt(a->N)) {
-        case 1: MOPK_DK(1)
-        case 2: MOPK_DK(2)
-        case 3: MOPK_DK(3)
-        case 4: MOPK_DK(4)
-        case 5: MOPK_DK(5)
-        case 6: MOPK_DK(6)
-        default: MOPK_DK(7)
-    }
-#undef MOPK_DK
+    const int nt = pick_nt(a->N);
+#define MOPK_GO(NT_, DK_) if (nt == NT_ && a->dk == DK_) return ew_fused_fwd_nt##NT_##_dk##DK_(a, st);
+    MOPK_FUSED_INSTS(MOPK_GO)
+#undef MOPK_GO
     return MOPK_ERR_UNSUPPORTED;
 }
 #endif

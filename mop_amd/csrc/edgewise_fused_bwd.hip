@@ -1610,7 +1610,7 @@ int MOPK_CAT(ew_fused_bwd_nt, MOPK_INST_NT, _dk, MOPK_INST_DK)(const MopkEdgewis
     const int lds = Cfg::lds_bytes(a_in->V);
     const int n_extra = a_in->ext && a_in->ext->gate_mode == 0 ? a_in->ext->n_extra : 0;
     if (lds > 160 * 1024 || 2 * a_in->V + 2 + n_extra > WST - 1) return MOPK_ERR_UNSUPPORTED;
-    if (n_extra && (!a_in->ext->row_extra || !a_in->ext->col_extra || !a_in->ext->d_row_extra || !a_in->ext->d_col_extra)) return MOPK_ERR_BAD_ARG;
+    if (n_extra && any_null(a_in->ext->row_extra, a_in->ext->col_extra, a_in->ext->d_row_extra, a_in->ext->d_col_extra)) return MOPK_ERR_BAD_ARG;
     MopkEdgewiseArgs args = *a_in;
     if (!a_in->save_for_backward) {
         // small `saved`: rebuild the full record (chain + mix state) by running the forward in export mode into the workspace
@@ -1633,25 +1633,21 @@ int MOPK_CAT(ew_fused_bwd_nt, MOPK_INST_NT, _dk, MOPK_INST_DK)(const MopkEdgewis
     if (dense) { dw.W1 = a->ext->W1; dw.b1 = a->ext->b1; dw.W2 = a->ext->W2; dw.b2 = a->ext->b2; }
     else if (n_extra) { dw.E = n_extra; dw.rowx = a->ext->row_extra; dw.colx = a->ext->col_extra; dw.drowx = a->ext->d_row_extra; dw.dcolx = a->ext->d_col_extra; }
     const dim3 block(NT * 64);
-#define MOPK_LAUNCH_H(IOT_, PH_, GRID_, HEAD_) do {                                                               \
-        auto kfn = ew_fused_bwd_kernel<NT, DK, IOT_, PH_, HEAD_>;                                                 \
-        static int lds_set = 0;      /* per instantiation and per process: the attribute is sticky (and may not be set during stream capture) */ \
-        if (lds_set < lds) { if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return MOPK_ERR_LAUNCH; lds_set = lds; } \
-        hipLaunchKernelGGL(kfn, dim3(GRID_), block, lds, st, *a, W, dw);                                          \
+    // the raised dynamic-LDS limit is kept per (instantiation, device) by launch_big_lds: it may not be set during stream capture
+#define MOPK_LAUNCH_H(IOT_, PH_, GRID_, HEAD_) launch_big_lds<ew_fused_bwd_kernel<NT, DK, IOT_, PH_, HEAD_>>(dim3(GRID_), block, lds, st, *a, W, dw)
+#define MOPK_LAUNCH(IOT_, PH_, GRID_) do {                                                                        \
+        const int rc = dense ? MOPK_LAUNCH_H(IOT_, PH_, GRID_, 1) : MOPK_LAUNCH_H(IOT_, PH_, GRID_, 0);           \
+        if (rc != MOPK_OK) return rc;                                                                             \
     } while (0)
-#define MOPK_LAUNCH(IOT_, PH_, GRID_) do { if (dense) MOPK_LAUNCH_H(IOT_, PH_, GRID_, 1); else MOPK_LAUNCH_H(IOT_, PH_, GRID_, 0); } while (0)
     if (a->io_dtype == MOPK_BF16) MOPK_LAUNCH(unsigned short, PH_A, nwgA); else MOPK_LAUNCH(float, PH_A, nwgA);
-    MOPK_CHECK_LAUNCH();
     {   // launch B: the two D-chains
         if (a->io_dtype == MOPK_BF16) MOPK_LAUNCH(unsigned short, PH_B, nwgB); else MOPK_LAUNCH(float, PH_B, nwgB);
     }
     if (a->io_dtype == MOPK_BF16) MOPK_LAUNCH(unsigned short, PH_C, nwgA); else MOPK_LAUNCH(float, PH_C, nwgA);
 #undef MOPK_LAUNCH
 #undef MOPK_LAUNCH_H
-    MOPK_CHECK_LAUNCH();
     if (dense) ew_fused_dense_dw_reduce(a, W, nwgA, st); else ew_fused_dw_reduce(a, W, nwgA, st);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 #else
 // sum the per-workgroup dW partials: out[idx] = sum_bh dwp[bh][idx]   (deterministic order)
@@ -1698,48 +1694,39 @@ void ew_fused_dense_dw_reduce(const MopkEdgewiseArgs *a, const BwdWs &W, int nwg
 int ew_fused_fwd_supported(const MopkEdgewiseArgs *a);
 #define MOPK_DECL(NT_, DK_) int ew_fused_bwd_nt##NT_##_dk##DK_(const MopkEdgewiseArgs *a, hipStream_t st); \
                             size_t ew_fused_bwd_ws_nt##NT_##_dk##DK_(const MopkEdgewiseArgs *a);
-MOPK_DECL(1, 16) MOPK_DECL(1, 32) MOPK_DECL(1, 64) MOPK_DECL(2, 16) MOPK_DECL(2, 32) MOPK_DECL(2, 64)
-MOPK_DECL(3, 16) MOPK_DECL(3, 32) MOPK_DECL(3, 64) MOPK_DECL(4, 16) MOPK_DECL(4, 32) MOPK_DECL(4, 64) MOPK_DECL(5, 16) MOPK_DECL(5, 32) MOPK_DECL(5, 64) MOPK_DECL(6, 16) MOPK_DECL(6, 32) MOPK_DECL(6, 64) MOPK_DECL(7, 16) MOPK_DECL(7, 32) MOPK_DECL(7, 64)
+MOPK_FUSED_INSTS(MOPK_DECL)
 #undef MOPK_DECL
-static int pick_nt_b(int N) { return N <= 32 ? 1 : N <= 64 ? 2 : N <= 96 ? 3 : N <= 128 ? 4 : N <= 160 ? 5 : N <= 192 ? 6 : N <= 224 ? 7 : 0; }
-#define MOPK_BWD_DISPATCH(PFX, ...)                                                   \
-    switch (pick_nt_b(a->N)) {                                                       \
-        case 1: switch (a->dk) { case 16: return PFX##nt1_dk16(__VA_ARGS__); case 32: return PFX##nt1_dk32(__VA_ARGS__); default: return PFX##nt1_dk64(__VA_ARGS__); } \
-        case 2: switch (a->dk) { case 16: return PFX##nt2_dk16(__VA_ARGS__); case 32: return PFX##nt2_dk32(__VA_ARGS__); default: return PFX##nt2_dk64(__VA_ARGS__); } \
-        case 3: switch (a->dk) { case 16: return PFX##nt3_dk16(__VA_ARGS__); case 32: return PFX##nt3_dk32(__VA_ARGS__); default: return PFX##nt3_dk64(__VA_ARGS__); } \
-        case 4: switch (a->dk) { case 16: return PFX##nt4_dk16(__VA_ARGS__); case 32: return PFX##nt4_dk32(__VA_ARGS__); default: return PFX##nt4_dk64(__VA_ARGS__); } \
-        case 5: switch (a->dk) { case 16: return PFX##nt5_dk16(__VA_ARGS__); case 32: return PFX##nt5_dk32(__VA_ARGS__); default: return PFX##nt5_dk64(__VA_ARGS__); } \
-        case 6: switch (a->dk) { case 16: return PFX##nt6_dk16(__VA_ARGS__); case 32: return PFX##nt6_dk32(__VA_ARGS__); default: return PFX##nt6_dk64(__VA_ARGS__); } \
-        default: switch (a->dk) { case 16: return PFX##nt7_dk16(__VA_ARGS__); case 32: return PFX##nt7_dk32(__VA_ARGS__); default: return PFX##nt7_dk64(__VA_ARGS__); } \
-    }
-template <int NT, int DK> static int lds_bwd(int V) { return BwdCfg<NT, DK>::lds_bytes(V); }
 int ew_fused_bwd_lds_bytes(int nt, int dk, int V) {
-#define MOPK_L(NT_) (dk == 16 ? lds_bwd<NT_, 16>(V) : dk == 32 ? lds_bwd<NT_, 32>(V) : lds_bwd<NT_, 64>(V))
-    switch (nt) { case 1: return MOPK_L(1); case 2: return MOPK_L(2); case 3: return MOPK_L(3); case 4: return MOPK_L(4); case 5: return MOPK_L(5); case 6: return MOPK_L(6); case 7: return MOPK_L(7); default: return 1 << 30; }
+#define MOPK_L(NT_, DK_) if (nt == NT_ && dk == DK_) return BwdCfg<NT_, DK_>::lds_bytes(V);
+    MOPK_FUSED_INSTS(MOPK_L)
 #undef MOPK_L
+    return 1 << 30;
 }
 int ew_fused_bwd_supported(const MopkEdgewiseArgs *a) {
     if (!ew_fused_fwd_supported(a)) return 0;
     if (a->ext && a->ext->gate_mode != 0) {                   // dense head (no 3x3): one 16-slot row holds dW1[k][0..C-1] and db1[k]
-        if (a->V > 6 || !a->ext->dW1 || !a->ext->db1 || !a->ext->dW2 || !a->ext->db2) return 0;
+        if (a->V > 6 || any_null(a->ext->dW1, a->ext->db1, a->ext->dW2, a->ext->db2)) return 0;
     }
     if (a->dq.sv != 0 || a->dk_.sv != 0) return 0;
     // the backward reads dy and writes dq / dk / dv with 16-byte vectors, like the forward does q, k, v, y
     const int64_t al = 16 / (a->io_dtype == MOPK_BF16 ? 2 : 4);
-    auto ok = [&](const void *p, int64_t sb, int64_t sh, int64_t sn) {
-        return p != nullptr && ((uintptr_t)p & 15) == 0 && sb % al == 0 && sh % al == 0 && sn % al == 0;
-    };
-    if (!ok(a->dy.ptr, a->dy.sb, a->dy.sh, a->dy.sn) || !ok(a->dq.ptr, a->dq.sb, a->dq.sh, a->dq.sn) ||
-        !ok(a->dk_.ptr, a->dk_.sb, a->dk_.sh, a->dk_.sn) || !ok(a->dv0.ptr, a->dv0.sb, a->dv0.sh, a->dv0.sn) ||
-        !ok(a->dvL.ptr, a->dvL.sb, a->dvL.sh, a->dvL.sn)) return 0;
-    return 1;
+    return !any_null(a->dy.ptr, a->dq.ptr, a->dk_.ptr, a->dv0.ptr, a->dvL.ptr) && views_aligned16(al, a->dy, a->dq, a->dk_, a->dv0, a->dvL);
 }
+// both are called for supported arguments only: (pick_nt(N), dk) is in the list
 size_t ew_fused_bwd_ws_bytes(const MopkEdgewiseArgs *a) {
-    MOPK_BWD_DISPATCH(ew_fused_bwd_ws_, a)
+    const int nt = pick_nt(a->N);
+#define MOPK_GO(NT_, DK_) if (nt == NT_ && a->dk == DK_) return ew_fused_bwd_ws_nt##NT_##_dk##DK_(a);
+    MOPK_FUSED_INSTS(MOPK_GO)
+#undef MOPK_GO
+    return 0;
 }
 int ew_fused_bwd(const MopkEdgewiseArgs *a, hipStream_t st) {
     if (!ew_fused_bwd_supported(a)) return MOPK_ERR_UNSUPPORTED;
-    MOPK_BWD_DISPATCH(ew_fused_bwd_, a, st)
+    const int nt = pick_nt(a->N);
+#define MOPK_GO(NT_, DK_) if (nt == NT_ && a->dk == DK_) return ew_fused_bwd_nt##NT_##_dk##DK_(a, st);
+    MOPK_FUSED_INSTS(MOPK_GO)
+#undef MOPK_GO
+    return MOPK_ERR_UNSUPPORTED;
 }
 #endif
 

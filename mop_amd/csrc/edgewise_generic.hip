@@ -1104,7 +1104,7 @@ static int ew_generic_fwd_t(const MopkEdgewiseArgs *a, hipStream_t st) {
     const int BHi = (int)d.BH;
     const dim3 pix((N * N + 255) / 256, BHi);        // thread per edge (i,j) of one (b,h)
     hipLaunchKernelGGL((ew_prep_kernel<T>), dim3((tot + 255) / 256), dim3(256), 0, st, *a, d, s);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     {   // S_v = Qe_v K^T                                                :500-503
         GemmDesc g = gd(N, N, dk, V, BHi);
         g.A = s.Qe; g.a_rs = dk; g.a_cs = 1; g.a_b0 = ndv; g.a_b1 = nd1;
@@ -1116,7 +1116,7 @@ static int ew_generic_fwd_t(const MopkEdgewiseArgs *a, hipStream_t st) {
     const RowMask rm{a->mask, a->mask_sb, a->mask_sh, a->mask_si, a->H, N};
     hipLaunchKernelGGL(softmax_rows_kernel, dim3((rowsV + 3) / 4), dim3(256), 0, st, s.S, s.A, s.rS, rowsV, N, LD, rm, rows1);  // :504-507
     hipLaunchKernelGGL(colmean_kernel, dim3((N + 255) / 256, V * BHi), dim3(256), 0, st, s.S, s.cS, N, LD);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     // chains                                                            :508-515
     for (int m = 1; m < V; ++m) {
         GemmDesc g = gd(N, N, N, 1, BHi);
@@ -1149,7 +1149,7 @@ static int ew_generic_fwd_t(const MopkEdgewiseArgs *a, hipStream_t st) {
         hipLaunchKernelGGL(gate_ab_kernel, dim3((rows1 + 255) / 256), dim3(256), 0, st, *a, d, s);                    // :325-326
     }
     hipLaunchKernelGGL(mix_fwd_kernel, dim3((rows1 + 3) / 4), dim3(256), 0, st, *a, d, s);                            // :537-551
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     {   // y_base = P V0 ; y_chain = A0(A1(...(A_{V-1} VL))) = Cf VL      :554-560
         GemmDesc g = gd(N, dk, N, 1, BHi);
         const float *Pm = s.P;
@@ -1165,8 +1165,7 @@ static int ew_generic_fwd_t(const MopkEdgewiseArgs *a, hipStream_t st) {
         RET_IF(bgemm(g, mf, st));
     }
     hipLaunchKernelGGL((combine_y_kernel<T>), dim3((tot + 255) / 256), dim3(256), 0, st, *a, d, w.ybase, s.ychain, s.wsig);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 template <typename T>
@@ -1185,7 +1184,7 @@ static int ew_generic_bwd_t(const MopkEdgewiseArgs *a, hipStream_t st) {
     const float *Cf = s.T + (V - 2) * nnv;
     hipLaunchKernelGGL((prep_dy_kernel<T>), dim3((tot + 255) / 256), dim3(256), 0, st, *a, d, w.dyc);
     hipLaunchKernelGGL(dlogit_kernel, dim3(BHi), dim3(256), 0, st, w.dyc, s.ychain, s.wsig, a->dlogit_part, nd1);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     {
         GemmDesc g = gd(N, N, dk, 1, BHi);           // dP = dy V0^T
         g.A = w.dyc; g.a_rs = dk; g.a_cs = 1; g.a_b1 = nd1;
@@ -1214,7 +1213,7 @@ static int ew_generic_bwd_t(const MopkEdgewiseArgs *a, hipStream_t st) {
         hipLaunchKernelGGL(dense_bwd_last_kernel, pix, dim3(256), 0, st, d, s, w, e);
         if (d.k3) hipLaunchKernelGGL(dense_k3_bwd_kernel, pix, dim3(256), 0, st, d, s, w, e);
         hipLaunchKernelGGL(dense_bwd_feat_kernel, pair_grid(N, BHi), dim3(TP * TP), 0, st, d, w, e);
-        MOPK_CHECK_LAUNCH();
+        if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
         // weight gradients: all-pairs pixel reductions, partials per block then a fixed-order sum (bit-reproducible)
         const int strips = (N + PR_PS - 1) / PR_PS, pc = ((N + strips - 1) / strips + 3) & ~3;   // N=197: 4 strips of 52
         const int64_t tiles = d.BH * N * strips;
@@ -1243,7 +1242,7 @@ static int ew_generic_bwd_t(const MopkEdgewiseArgs *a, hipStream_t st) {
         hipLaunchKernelGGL(lens_w_final_kernel, dim3((LV * 9 + 63) / 64), dim3(64), 0, st, w.part, e.dlens_w, LV, nchunk);
     }
     hipLaunchKernelGGL(dchain_seed_kernel, dim3((rows1 + 3) / 4), dim3(256), 0, st, *a, d, s, w);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     // chain backward.  T_m = T_{m-1} A_m : dA_m += T_{m-1}^T D ; D <- D A_m^T ; dA_0 += D
     hipMemsetAsync(w.dA, 0, sizeof(float) * V * nnv, st);
     for (int dir = 0; dir < 2; ++dir) {
@@ -1268,10 +1267,10 @@ static int ew_generic_bwd_t(const MopkEdgewiseArgs *a, hipStream_t st) {
         }
         const int first = dir == 0 ? 0 : V - 1;       // dA[first] += D
         hipLaunchKernelGGL(axpy_kernel, dim3((nnv + 255) / 256), dim3(256), 0, st, w.dA + first * nnv, D, nnv);
-        MOPK_CHECK_LAUNCH();
+        if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     }
     hipLaunchKernelGGL(ds_final_kernel, dim3((rows1 + 3) / 4), dim3(256), 0, st, *a, d, s, w);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     {
         GemmDesc g = gd(N, dk, N, V, BHi);           // dQe_v = dS_v K
         g.A = w.dA; g.a_rs = LD; g.a_cs = 1; g.a_b0 = nnv; g.a_b1 = nn1;
@@ -1288,8 +1287,7 @@ static int ew_generic_bwd_t(const MopkEdgewiseArgs *a, hipStream_t st) {
         }
     }
     hipLaunchKernelGGL((scale_bwd_kernel<T>), dim3(BHi, (dk + 63) / 64), dim3(64, 4), 0, st, *a, d, s, w);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 // ---- batch reduction of the small per-(b) partial gradients: 16 outputs x 16 batch slices per block, slices combined in a
@@ -1333,8 +1331,7 @@ int ew_reduce_parts(const MopkEdgewiseArgs *a, float *dsqk, float *dvs0, float *
     const int n_sqk = a->V * a->H * a->dk, n_vs = a->H * a->dk, total = n_sqk + 2 * n_vs;
     hipLaunchKernelGGL(ew_reduce_parts_kernel, dim3((total + 15) / 16 + 1), dim3(256), 0, st, a->dsqk_part, a->dvs0_part,
                        a->dvsL_part, a->dlogit_part, dsqk, dvs0, dvsL, dlogit, a->B, n_sqk, n_vs, a->B * a->H);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 int ew_generic_fwd(const MopkEdgewiseArgs *a, hipStream_t st) {

@@ -117,8 +117,7 @@ template <typename T> static int ew_params_fwd_t(const MopkEdgewiseParamArgs *p,
     hipLaunchKernelGGL((ew_params_fwd_kernel<T>), dim3((n_pack + 255) / 256), dim3(256), 0, st, (const T *)p->q_scale,
                        (const T *)p->k_scale, (const T *)p->v_scale, (const T *)p->Wr, (const T *)p->br, (const T *)p->Wc,
                        (const T *)p->bc, (const T *)p->chain_logit, p->pack, d);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 template <typename T> static int ew_params_bwd_t(const MopkEdgewiseParamArgs *p, hipStream_t st) {
@@ -129,18 +128,16 @@ template <typename T> static int ew_params_bwd_t(const MopkEdgewiseParamArgs *p,
     hipLaunchKernelGGL((ew_params_bwd_kernel<T>), dim3(n_red + 1 + n_cvt), dim3(256), 0, st, p->dsqk_part, p->dvs0_part,
                        p->dvsL_part, p->dlogit_part, p->dWr, p->dbr, p->dWc, p->dbc, (const T *)p->q_scale, (const T *)p->k_scale, g,
                        d, n_red);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 static int ew_params_validate(const MopkEdgewiseParamArgs *p, bool bwd) {
     if (!p) return MOPK_ERR_BAD_ARG;
     if (p->B <= 0 || p->V < 2 || p->H <= 0 || p->dk <= 0 || p->r < 1 || p->C < 1) return MOPK_ERR_BAD_SHAPE;
     if (p->io_dtype != MOPK_F32 && p->io_dtype != MOPK_BF16) return MOPK_ERR_BAD_ARG;
-    if (!p->q_scale || !p->k_scale) return MOPK_ERR_BAD_ARG;
-    if (!bwd && (!p->v_scale || !p->Wr || !p->br || !p->Wc || !p->bc || !p->chain_logit || !p->pack)) return MOPK_ERR_BAD_ARG;
-    if (bwd && (!p->dsqk_part || !p->dvs0_part || !p->dvsL_part || !p->dlogit_part || !p->dWr || !p->dbr || !p->dWc || !p->dbc ||
-                !p->gq_scale || !p->gk_scale || !p->gv_scale || !p->gWr || !p->gbr || !p->gWc || !p->gbc || !p->glogit))
+    if (any_null(p->q_scale, p->k_scale)) return MOPK_ERR_BAD_ARG;
+    if (!bwd && any_null(p->v_scale, p->Wr, p->br, p->Wc, p->bc, p->chain_logit, p->pack)) return MOPK_ERR_BAD_ARG;
+    if (bwd && any_null(p->dsqk_part, p->dvs0_part, p->dvsL_part, p->dlogit_part, p->dWr, p->dbr, p->dWc, p->dbc, p->gq_scale, p->gk_scale, p->gv_scale, p->gWr, p->gbr, p->gWc, p->gbc, p->glogit))
         return MOPK_ERR_BAD_ARG;
     return MOPK_OK;
 }

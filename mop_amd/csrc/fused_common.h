@@ -19,6 +19,13 @@ template <int B, int E, typename F> __device__ __forceinline__ void static_for(F
 constexpr int BTS = 24;         // bT row stride (ushorts): 16 k-slots + 8 pad (48 B, 16-B aligned)
 constexpr int WST = 27;         // row stride (floats) of the staged low-rank gate-head weights: up to 26 input channels + the bias in slot WST - 1
 
+// ---- THE list of (NT, DK) instantiations of the fused forward and backward (NT = tiles of 32 tokens, DK = head size).  Declarations,
+// dispatch and the LDS / saved / workspace lookups of both files expand it; mop_amd/build.py compiles NTS x DKS, and
+// tests/test_fused_insts_cpu.py holds the two lists equal.  The list stays on the one line below.
+#define MOPK_FUSED_INSTS(X) X(1, 16) X(1, 32) X(1, 64) X(2, 16) X(2, 32) X(2, 64) X(3, 16) X(3, 32) X(3, 64) X(4, 16) X(4, 32) X(4, 64) X(5, 16) X(5, 32) X(5, 64) X(6, 16) X(6, 32) X(6, 64) X(7, 16) X(7, 32) X(7, 64)
+// the one N -> NT rule (0: no instantiation takes this N)
+inline int pick_nt(int N) { return N <= 32 ? 1 : N <= 64 ? 2 : N <= 96 ? 3 : N <= 128 ? 4 : N <= 160 ? 5 : N <= 192 ? 6 : N <= 224 ? 7 : 0; }
+
 __host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int kperm16(int k) { return (k & 3) | ((k & 4) << 1) | ((k & 8) >> 1); }
 __device__ __forceinline__ int tile_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }

@@ -79,8 +79,8 @@ int lg_check(const MopkLanguageProbsArgs *a) {
     if (a->R <= 0 || a->V < 2 || a->n < 1 || a->n > MOPK_LANGUAGE_MAX_N) return MOPK_ERR_BAD_SHAPE;
     if (a->dtype != MOPK_F32 && a->dtype != MOPK_BF16) return MOPK_ERR_BAD_ARG;
     if (a->logits_ld < a->V || a->probs_ld < a->n) return MOPK_ERR_BAD_ARG;
-    if ((uintptr_t)a->logits % (a->dtype == MOPK_BF16 ? 2 : 4)) return MOPK_ERR_UNSUPPORTED;
-    if (((uintptr_t)a->ids & 3) || ((uintptr_t)a->probs & 3) || ((uintptr_t)a->tokens & 3)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(a->dtype == MOPK_BF16 ? 1 : 3, a->logits)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->ids, a->probs, a->tokens)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -96,11 +96,11 @@ int mopk_language_probs_supported(const MopkLanguageProbsArgs *a) { return lg_ch
 int mopk_language_probs(const MopkLanguageProbsArgs *a, void *stream) {
     const int rc = lg_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->logits || !a->ids || !a->probs || !a->tokens) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->logits, a->ids, a->probs, a->tokens)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (a->dtype == MOPK_BF16) hipLaunchKernelGGL((lg_row_kernel<unsigned short>), dim3((unsigned)a->R), dim3(LG_THREADS), 0, st, *a);
     else hipLaunchKernelGGL((lg_row_kernel<float>), dim3((unsigned)a->R), dim3(LG_THREADS), 0, st, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

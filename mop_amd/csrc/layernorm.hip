@@ -182,19 +182,18 @@ static int ln_parts(const MopkLayerNormArgs *a) {
     const int64_t wgs = (a->rows + LN_WAVES - 1) / LN_WAVES;
     return (int)(wgs < LN_MAX_PARTS ? wgs : LN_MAX_PARTS);
 }
-static bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 static int ln_validate(const MopkLayerNormArgs *a, bool bwd) {
     if (!a) return MOPK_ERR_BAD_ARG;
     if (a->rows <= 0 || a->dim <= 0) return MOPK_ERR_BAD_SHAPE;
     if (a->dim % 8 != 0 || a->dim > 4096) return MOPK_ERR_UNSUPPORTED;
     for (int dt : {a->x_dtype, a->y_dtype, a->p_dtype}) if (dt != MOPK_F32 && dt != MOPK_BF16) return MOPK_ERR_BAD_ARG;
-    if (!a->x || !a->gamma || a->x_ld < a->dim || a->y_ld < a->dim || a->x_ld % 8 || a->y_ld % 8) return MOPK_ERR_BAD_ARG;
-    if (!al16(a->x) || !al16(a->gamma) || (a->beta && !al16(a->beta))) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->x, a->gamma) || a->x_ld < a->dim || a->y_ld < a->dim || a->x_ld % 8 || a->y_ld % 8) return MOPK_ERR_BAD_ARG;
+    if (misaligned(15, a->x, a->gamma, a->beta)) return MOPK_ERR_BAD_ARG;
     if (!bwd) {
-        if (!a->y || !al16(a->y) || ((a->mean == nullptr) != (a->rstd == nullptr))) return MOPK_ERR_BAD_ARG;
+        if (!a->y || misaligned(15, a->y) || ((a->mean == nullptr) != (a->rstd == nullptr))) return MOPK_ERR_BAD_ARG;
     } else {
-        if (!a->dy || !a->dx || !a->mean || !a->rstd || !a->workspace) return MOPK_ERR_BAD_ARG;
-        if (!al16(a->dy) || !al16(a->dx) || (a->dres && !al16(a->dres))) return MOPK_ERR_BAD_ARG;
+        if (any_null(a->dy, a->dx, a->mean, a->rstd, a->workspace)) return MOPK_ERR_BAD_ARG;
+        if (misaligned(15, a->dy, a->dx, a->dres)) return MOPK_ERR_BAD_ARG;
     }
     return MOPK_OK;
 }
@@ -237,7 +236,7 @@ int mopk_layernorm_fwd(const MopkLayerNormArgs *a, void *stream) {
     const int rc = ln_validate(a, false);
     if (rc != MOPK_OK) return rc;
     ln_dispatch(a, false, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 int mopk_layernorm_bwd(const MopkLayerNormArgs *a, void *stream) {
     const int rc = ln_validate(a, true);
@@ -248,7 +247,7 @@ int mopk_layernorm_bwd(const MopkLayerNormArgs *a, void *stream) {
         hipLaunchKernelGGL(ln_reduce_kernel, dim3((n + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float *)a->workspace,
                            ln_parts(a), a->dim, a->dgamma, a->dbeta);
     }
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

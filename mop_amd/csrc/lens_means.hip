@@ -269,16 +269,11 @@ template <int DK> int lm_launch(const MopkLensMeansArgs *a, bool bwd, hipStream_
     const size_t lds = lm_smem_bytes<DK>(a->N, a->L, E, bwd, lm_gstride(a->N, lm_gpad(*a)));
     if (lds > 160 * 1024) return MOPK_ERR_UNSUPPORTED;
     const dim3 grid(a->B * a->H), block(LM_THREADS);
-#define LM_GO(KERNEL, IOT_) do {                                                                                                   \
-        auto kfn = KERNEL<DK, IOT_>;                                                                                               \
-        static size_t lds_set = 0;      /* sticky per instantiation; may not be set during stream capture */                       \
-        if (lds_set < lds) { if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MOPK_ERR_LAUNCH; lds_set = lds; } \
-        hipLaunchKernelGGL(kfn, grid, block, lds, st, *a);                                                                          \
-    } while (0)
-    if (bwd) { if (a->io_dtype == MOPK_BF16) LM_GO(lens_means_bwd_kernel, unsigned short); else LM_GO(lens_means_bwd_kernel, float); }
-    else { if (a->io_dtype == MOPK_BF16) LM_GO(lens_means_fwd_kernel, unsigned short); else LM_GO(lens_means_fwd_kernel, float); }
-#undef LM_GO
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    // the raised dynamic-LDS limit is kept per (instantiation, device) by launch_big_lds: it may not be set during stream capture
+    if (bwd) return a->io_dtype == MOPK_BF16 ? launch_big_lds<lens_means_bwd_kernel<DK, unsigned short>>(grid, block, lds, st, *a)
+                                             : launch_big_lds<lens_means_bwd_kernel<DK, float>>(grid, block, lds, st, *a);
+    return a->io_dtype == MOPK_BF16 ? launch_big_lds<lens_means_fwd_kernel<DK, unsigned short>>(grid, block, lds, st, *a)
+                                    : launch_big_lds<lens_means_fwd_kernel<DK, float>>(grid, block, lds, st, *a);
 }
 
 }  // namespace
@@ -300,13 +295,11 @@ int lens_means_run(const MopkLensMeansArgs *a, bool bwd, hipStream_t st) {
     if (a->N > LM_MAXN || a->L * a->V > LM_MAXE || (a->dk != 16 && a->dk != 32 && a->dk != 64)) return MOPK_ERR_UNSUPPORTED;
     if (a->io_dtype != MOPK_F32 && a->io_dtype != MOPK_BF16) return MOPK_ERR_BAD_ARG;
     for (int l = 0; l < a->L; ++l) if (a->dil[l] < 1) return MOPK_ERR_BAD_ARG;
-    if (!a->q.ptr || !a->k.ptr || !a->sqk || !a->lens_w) return MOPK_ERR_BAD_ARG;
-    if (!bwd && (!a->row || !a->col)) return MOPK_ERR_BAD_ARG;
-    if (bwd && (!a->d_row || !a->d_col || !a->dq.ptr || !a->dk_.ptr || !a->dsqk_part || !a->dlens_part)) return MOPK_ERR_BAD_ARG;
-    if (bwd && a->io_dtype == MOPK_BF16 && a->dk >= 32) {       // the 16-byte read-modify-write of dq / dk rows
-        const MopkView4 *vs[2] = {&a->dq, &a->dk_};
-        for (const MopkView4 *v : vs) if (((uintptr_t)v->ptr & 15) || v->sb % 8 || v->sh % 8 || v->sn % 8) return MOPK_ERR_BAD_ARG;
-    }
+    if (any_null(a->q.ptr, a->k.ptr, a->sqk, a->lens_w)) return MOPK_ERR_BAD_ARG;
+    if (!bwd && any_null(a->row, a->col)) return MOPK_ERR_BAD_ARG;
+    if (bwd && any_null(a->d_row, a->d_col, a->dq.ptr, a->dk_.ptr, a->dsqk_part, a->dlens_part)) return MOPK_ERR_BAD_ARG;
+    // the 16-byte read-modify-write of bf16 dq / dk rows
+    if (bwd && a->io_dtype == MOPK_BF16 && a->dk >= 32 && !views_aligned16(8, a->dq, a->dk_)) return MOPK_ERR_BAD_ARG;
     switch (a->dk) {
         case 16: return lm_launch<16>(a, bwd, st);
         case 32: return lm_launch<32>(a, bwd, st);

@@ -170,8 +170,8 @@ int lm_check(const MopkLogMelArgs *a) {
     if (a->out_dtype != MOPK_F32 && a->out_dtype != MOPK_BF16) return MOPK_ERR_BAD_ARG;
     if (a->audio_ld < a->L) return MOPK_ERR_BAD_ARG;
     const uintptr_t am = a->audio_dtype == MOPK_F32 ? 3 : 1, om = a->out_dtype == MOPK_F32 ? 3 : 1;
-    if (((uintptr_t)a->audio & am) || ((uintptr_t)a->out & om) || ((uintptr_t)a->lens & 3) || ((uintptr_t)a->filters & 3) ||
-        ((uintptr_t)a->bands & 3) || ((uintptr_t)a->twiddle & 7) || ((uintptr_t)a->window & 3) || ((uintptr_t)a->workspace & 3))
+    if (misaligned(am, a->audio) || misaligned(om, a->out) || misaligned(3, a->lens, a->filters, a->bands, a->window, a->workspace) ||
+        misaligned(7, a->twiddle))
         return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
@@ -179,20 +179,12 @@ int lm_check(const MopkLogMelArgs *a) {
 template <typename TIN> int lm_launch_tiles(const MopkLogMelArgs *a, float *g, float *part, int ntiles, hipStream_t st) {
     const size_t lds = lm_lds_bytes(a->n_fft);
     const int tpw = (lm_bin_tiles(a->n_fft) + LM_WAVES - 1) / LM_WAVES;        // 1 .. 3
-    auto kfn = tpw == 1 ? lm_tile_kernel<TIN, 1> : tpw == 2 ? lm_tile_kernel<TIN, 2> : lm_tile_kernel<TIN, 3>;
-    // The raised LDS limit is sticky per (device, instantiation) and may not be set during stream capture.  Two host threads
-    // that race here both set the same attribute to a sufficient value; a device past the table sets it on every call.
-    constexpr int LM_DEVS = 64;
-    static size_t lds_set[LM_DEVS][4] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return MOPK_ERR_LAUNCH;
-    const bool known = dev >= 0 && dev < LM_DEVS;
-    if (!known || lds_set[dev][tpw] < lds) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MOPK_ERR_LAUNCH;
-        if (known) lds_set[dev][tpw] = lds;
-    }
-    hipLaunchKernelGGL(kfn, dim3((unsigned)ntiles, (unsigned)a->B), dim3(LM_THREADS), lds, st, *a, g, part);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    const dim3 grid((unsigned)ntiles, (unsigned)a->B), block(LM_THREADS);
+    // the raised dynamic-LDS limit is kept per (instantiation, device) by launch_big_lds: it may not be set during stream capture
+    // (named in the order 2, 3, 1: the order in which the code object has always held the three kernels)
+    return tpw == 2 ? launch_big_lds<lm_tile_kernel<TIN, 2>>(grid, block, lds, st, *a, g, part)
+         : tpw == 3 ? launch_big_lds<lm_tile_kernel<TIN, 3>>(grid, block, lds, st, *a, g, part)
+                    : launch_big_lds<lm_tile_kernel<TIN, 1>>(grid, block, lds, st, *a, g, part);
 }
 
 }  // namespace
@@ -216,7 +208,7 @@ size_t mopk_log_mel_workspace_bytes(const MopkLogMelArgs *a) {
 int mopk_log_mel(const MopkLogMelArgs *a, void *stream) {
     const int rc = lm_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->audio || !a->filters || !a->twiddle || !a->window || !a->out || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->audio, a->filters, a->twiddle, a->window, a->out, a->workspace)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int T = a->L / a->hop, ntiles = lm_tiles(T);
     Carver c(a->workspace);
@@ -230,7 +222,7 @@ int mopk_log_mel(const MopkLogMelArgs *a, void *stream) {
     const dim3 grid((unsigned)(((int64_t)T * a->n_mels + LM_CHUNK - 1) / LM_CHUNK), (unsigned)a->B);
     if (a->out_dtype == MOPK_F32) hipLaunchKernelGGL(lm_finish_kernel<float>, grid, dim3(LM_THREADS), 0, st, *a, (const float *)g, (const float *)part, ntiles);
     else hipLaunchKernelGGL(lm_finish_kernel<unsigned short>, grid, dim3(LM_THREADS), 0, st, *a, (const float *)g, (const float *)part, ntiles);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -123,7 +123,7 @@ int lr_check(const MopkLogitRulesArgs *a) {
     if (a->tb < -1 || a->max_initial < -1) return MOPK_ERR_BAD_ARG;
     if (a->tb >= 0 && (a->tb >= a->V || a->eos < 0 || a->eos >= a->tb)) return MOPK_ERR_BAD_ARG;
     const int es = a->dtype == MOPK_BF16 ? 2 : 4;
-    if ((uintptr_t)a->logits % es || (uintptr_t)a->out % es || ((uintptr_t)a->hist & 3) || ((uintptr_t)a->pos & 3))
+    if (misaligned(es - 1, a->logits, a->out) || misaligned(3, a->hist, a->pos))
         return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
@@ -140,11 +140,11 @@ int mopk_logit_rules_supported(const MopkLogitRulesArgs *a) { return lr_check(a)
 int mopk_logit_rules(const MopkLogitRulesArgs *a, void *stream) {
     const int rc = lr_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->logits || !a->out || !a->hist || !a->pos || !a->mask) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->logits, a->out, a->hist, a->pos, a->mask)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (a->dtype == MOPK_BF16) hipLaunchKernelGGL((lr_row_kernel<unsigned short>), dim3((unsigned)a->R), dim3(LR_THREADS), 0, st, *a);
     else hipLaunchKernelGGL((lr_row_kernel<float>), dim3((unsigned)a->R), dim3(LR_THREADS), 0, st, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -228,7 +228,6 @@ __global__ __launch_bounds__(GR_WAVES * 64) void gr_bwd_kernel(MopkGatedResidual
     if (lane == 0) a.dgate[row] = s;
 }
 
-bool mg_al(const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
 bool mg_dtype_ok(int d) { return d == MOPK_F32 || d == MOPK_BF16; }
 
 // shape / dtype / stride / alignment rules shared by the support query and the entry points (pointers checked when non-null)
@@ -241,16 +240,13 @@ int mg_check(const MopkMelGateArgs *a) {
     if (a->B * tiles > ((int64_t)1 << 31) - 1 || (int64_t)a->L * a->k * a->F > ((int64_t)1 << 31) - 1) return MOPK_ERR_UNSUPPORTED;
     if (a->mel_st < a->F || a->mel_sb < 0) return MOPK_ERR_BAD_ARG;
     const uintptr_t es = a->mel_dtype == MOPK_F32 ? 4 : 2;
-    if (a->mel && !mg_al(a->mel, es)) return MOPK_ERR_UNSUPPORTED;
-    for (const void *p : {(const void *)a->W, (const void *)a->lens, (const void *)a->gates, (const void *)a->dgates,
-                          (const void *)a->dW, (const void *)a->workspace})
-        if (p && !mg_al(p, 4)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(es - 1, a->mel) || misaligned(3, a->W, a->lens, a->gates, a->dgates, a->dW, a->workspace)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
 // rows of 8-element chunks on 16-byte boundaries
 bool mg_vec(const MopkMelGateArgs *a) {
-    return a->F % 8 == 0 && a->mel_st % 8 == 0 && a->mel_sb % 8 == 0 && mg_al(a->mel, 16);
+    return a->F % 8 == 0 && a->mel_st % 8 == 0 && a->mel_sb % 8 == 0 && !misaligned(15, a->mel);
 }
 
 int mg_parts(const MopkMelGateArgs *a) {
@@ -286,10 +282,7 @@ int gr_check(const MopkGatedResidualArgs *a) {
     if (a->x_sb % 8 || a->x_st % 8 || a->x_st < a->D || a->x_sb < 0) return MOPK_ERR_UNSUPPORTED;
     if (a->a_sb % 8 || a->a_st % 8 || a->a_st < a->D || a->a_sb < 0) return MOPK_ERR_UNSUPPORTED;
     if (a->gate_sb < 0 || (a->B > 1 && a->gate_sb < a->T)) return MOPK_ERR_BAD_ARG;
-    for (const void *p : {a->x, a->a, (const void *)a->out, a->dout, (const void *)a->dr})
-        if (p && !mg_al(p, 16)) return MOPK_ERR_UNSUPPORTED;
-    for (const void *p : {(const void *)a->gate, (const void *)a->dgate})
-        if (p && !mg_al(p, 4)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(15, a->x, a->a, a->out, a->dout, a->dr) || misaligned(3, a->gate, a->dgate)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -325,20 +318,20 @@ size_t mopk_mel_gate_workspace_bytes(const MopkMelGateArgs *a) {
 int mopk_mel_gate_fwd(const MopkMelGateArgs *a, void *stream) {
     const int rc = mg_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->mel || !a->W || !a->gates) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->mel, a->W, a->gates)) return MOPK_ERR_BAD_ARG;
     mg_dispatch(a, false, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_mel_gate_bwd(const MopkMelGateArgs *a, void *stream) {
     const int rc = mg_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->mel || !a->dgates || !a->dW || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->mel, a->dgates, a->dW, a->workspace)) return MOPK_ERR_BAD_ARG;
     mg_dispatch(a, true, (hipStream_t)stream);
     const int n = a->L * a->k * a->F;
     hipLaunchKernelGGL(mg_reduce_kernel, dim3((n + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float *)a->workspace,
                        mg_parts(a), n, a->dW);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_gated_residual_supported(const MopkGatedResidualArgs *a) { return gr_check(a) == MOPK_OK; }
@@ -348,17 +341,17 @@ size_t mopk_gated_residual_workspace_bytes(const MopkGatedResidualArgs *) { retu
 int mopk_gated_residual_fwd(const MopkGatedResidualArgs *a, void *stream) {
     const int rc = gr_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->x || !a->a || !a->gate || !a->out) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->x, a->a, a->gate, a->out)) return MOPK_ERR_BAD_ARG;
     gr_dispatch(a, false, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_gated_residual_bwd(const MopkGatedResidualArgs *a, void *stream) {
     const int rc = gr_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->x || !a->a || !a->gate || !a->dout || !a->dr || !a->dgate) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->x, a->a, a->gate, a->dout, a->dr, a->dgate)) return MOPK_ERR_BAD_ARG;
     gr_dispatch(a, true, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -405,7 +405,6 @@ size_t moe_slab_bytes(const MopkMoeArgs *a) {
     return (size_t)moe_tiles_bound(a->M, a->E, moe_chunk(a->M)) * a->D * a->F * sizeof(float);
 }
 
-bool moe_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 bool moe_dt_ok(int d) { return d == MOPK_F32 || d == MOPK_BF16; }
 
 // argument rules shared by the support query and the entry points (pointers checked when non-null)
@@ -417,12 +416,9 @@ int moe_check(const MopkMoeArgs *a) {
     if (a->E > MOPK_MOE_MAX_EXPERTS || a->D % 8 || a->F % 8) return MOPK_ERR_UNSUPPORTED;
     if ((int64_t)a->M * a->F > ((int64_t)1 << 31) - 1 || (int64_t)a->M * a->D > ((int64_t)1 << 31) - 1) return MOPK_ERR_UNSUPPORTED;
     if (a->precision == MOPK_PREC_FP32 && (a->x_dtype | a->w_dtype | a->o_dtype) != MOPK_F32) return MOPK_ERR_UNSUPPORTED;
-    for (const void *p : {a->x, a->residual, (const void *)a->y, (const void *)a->u, (const void *)a->h, a->dy, (const void *)a->dx,
-                          (const void *)a->route, (const void *)a->workspace})
-        if (p && !moe_al16(p)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(15, a->x, a->residual, a->y, a->u, a->h, a->dy, a->dx, a->route, a->workspace)) return MOPK_ERR_UNSUPPORTED;
     for (int e = 0; e < a->E; ++e)
-        for (const void *p : {a->w1[e], a->w2[e], (const void *)a->dw1[e], (const void *)a->dw2[e]})
-            if (p && !moe_al16(p)) return MOPK_ERR_UNSUPPORTED;
+        if (misaligned(15, a->w1[e], a->w2[e], a->dw1[e], a->dw2[e])) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -455,7 +451,7 @@ void moe_gemm_p(const MopkMoeArgs *a, int chunk, float *slab, hipStream_t st) {
 int moe_route(const MopkMoeArgs *a, hipStream_t st) {
     hipLaunchKernelGGL(moe_logits_kernel, dim3((unsigned)((a->M + 3) / 4)), dim3(256), 0, st, *a);
     hipLaunchKernelGGL(moe_scan_kernel, dim3(1), dim3(MOE_SCAN_THREADS), 0, st, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // namespace
@@ -476,29 +472,29 @@ size_t mopk_moe_workspace_bytes(const MopkMoeArgs *a, int backward) {
 int mopk_moe_route(const MopkMoeArgs *a, void *stream) {
     const int rc = moe_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->x || !a->gate_w || !a->route) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->x, a->gate_w, a->route)) return MOPK_ERR_BAD_ARG;
     return moe_route(a, (hipStream_t)stream);
 }
 
 int mopk_moe_fwd(const MopkMoeArgs *a, void *stream) {
     const int rc = moe_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->x || !a->gate_w || !a->route || !a->u || !a->h || !a->y) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->x, a->gate_w, a->route, a->u, a->h, a->y)) return MOPK_ERR_BAD_ARG;
     for (int e = 0; e < a->E; ++e)
-        if (!a->w1[e] || !a->w2[e]) return MOPK_ERR_BAD_ARG;
+        if (any_null(a->w1[e], a->w2[e])) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (moe_route(a, st) != MOPK_OK) return MOPK_ERR_LAUNCH;
     moe_gemm_p<FC1>(a, 0, nullptr, st);
     moe_gemm_p<FC2>(a, 0, nullptr, st);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_moe_bwd(const MopkMoeArgs *a, void *stream) {
     const int rc = moe_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->x || !a->route || !a->u || !a->h || !a->dy || !a->dx || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->x, a->route, a->u, a->h, a->dy, a->dx, a->workspace)) return MOPK_ERR_BAD_ARG;
     for (int e = 0; e < a->E; ++e)
-        if (!a->w1[e] || !a->w2[e] || !a->dw1[e] || !a->dw2[e]) return MOPK_ERR_BAD_ARG;
+        if (any_null(a->w1[e], a->w2[e], a->dw1[e], a->dw2[e])) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int chunk = moe_chunk(a->M);
     float *slab1 = (float *)((char *)a->workspace + moe_du_bytes(a));
@@ -510,7 +506,7 @@ int mopk_moe_bwd(const MopkMoeArgs *a, void *stream) {
     const int64_t n = (int64_t)a->D * a->F;
     hipLaunchKernelGGL(moe_wsum_kernel, dim3((unsigned)((n / 4 + 255) / 256), (unsigned)a->E, 2), dim3(256), 0, st, *a, chunk,
                        (const float *)slab1, (const float *)slab2);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

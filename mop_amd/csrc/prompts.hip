@@ -75,9 +75,7 @@ int ph_check(const MopkPromptHistoryArgs *a) {
     if (a->A <= 0 || a->B <= 0 || a->n <= 0 || a->T <= 0) return MOPK_ERR_BAD_SHAPE;
     if (a->T0 < 0 || a->T0 >= a->T || a->tokens_ld < a->T) return MOPK_ERR_BAD_ARG;
     if (a->n > PH_MAXN || a->T - a->T0 > PH_MAXS) return MOPK_ERR_UNSUPPORTED;
-    if (((uintptr_t)a->hist & 3) || ((uintptr_t)a->hist_len & 3) || ((uintptr_t)a->tokens & 3) || ((uintptr_t)a->n_take & 3) ||
-        ((uintptr_t)a->item & 3) || ((uintptr_t)a->mode & 3))
-        return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->hist, a->hist_len, a->tokens, a->n_take, a->item, a->mode)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -88,8 +86,7 @@ int wp_check(const MopkWindowPromptsArgs *a) {
     if ((a->out_i64 != 0 && a->out_i64 != 1) || (a->sot_i64 != 0 && a->sot_i64 != 1)) return MOPK_ERR_BAD_ARG;
     if (a->width > WP_MAXW) return MOPK_ERR_UNSUPPORTED;
     const uintptr_t om = a->out_i64 ? 7 : 3, sm = a->sot_i64 ? 7 : 3;
-    if (((uintptr_t)a->hist & 3) || ((uintptr_t)a->hist_len & 3) || ((uintptr_t)a->item & 3) || ((uintptr_t)a->sot & sm) ||
-        ((uintptr_t)a->ids & om) || ((uintptr_t)a->kv_start & 3))
+    if (misaligned(3, a->hist, a->hist_len, a->item) || misaligned(sm, a->sot) || misaligned(om, a->ids) || misaligned(3, a->kv_start))
         return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
@@ -106,10 +103,10 @@ int mopk_prompt_history_update_supported(const MopkPromptHistoryArgs *a) { retur
 int mopk_prompt_history_update(const MopkPromptHistoryArgs *a, void *stream) {
     const int rc = ph_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->hist || !a->hist_len || !a->tokens || !a->n_take || !a->item || !a->mode) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->hist, a->hist_len, a->tokens, a->n_take, a->item, a->mode)) return MOPK_ERR_BAD_ARG;
     const int threads = (a->n + WAVE - 1) / WAVE * WAVE;
     hipLaunchKernelGGL(ph_row_kernel, dim3((unsigned)a->A), dim3(threads), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_window_prompts_supported(const MopkWindowPromptsArgs *a) { return wp_check(a) == MOPK_OK; }
@@ -117,10 +114,10 @@ int mopk_window_prompts_supported(const MopkWindowPromptsArgs *a) { return wp_ch
 int mopk_window_prompts(const MopkWindowPromptsArgs *a, void *stream) {
     const int rc = wp_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->hist || !a->hist_len || !a->item || !a->sot || !a->ids || !a->kv_start) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->hist, a->hist_len, a->item, a->sot, a->ids, a->kv_start)) return MOPK_ERR_BAD_ARG;
     const int threads = min((a->width + WAVE - 1) / WAVE * WAVE, WP_THREADS);
     hipLaunchKernelGGL(wp_row_kernel, dim3((unsigned)a->A), dim3(threads), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

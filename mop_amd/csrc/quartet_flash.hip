@@ -484,10 +484,6 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_dkv_kernel(MopkQuartetArgs a
 
 // ------------------------------------------------------------------ host side
 namespace {
-bool qt_al(const MopkView4 &v, int es) {
-    const int64_t al = 16 / es;
-    return ((uintptr_t)v.ptr & 15) == 0 && v.sb % al == 0 && v.sh % al == 0 && v.sn % al == 0;
-}
 struct QtBufs { float *stats, *lse, *delta, *rows, *spart; size_t nsaved, nwork; };
 QtBufs qt_carve_flash(void *saved, void *ws, const MopkQuartetArgs *a) {
     Carver cs(saved), cw(ws);
@@ -504,12 +500,12 @@ int qt_flash_supported(const MopkQuartetArgs *a, bool bwd) {
     if (a->precision != MOPK_PREC_BF16) return 0;
     if (a->attn) return 0;                                         // returned attention weights: generic path
     if (a->dh != 32 && a->dh != 64) return 0;
-    const int es = a->io_dtype == MOPK_BF16 ? 2 : 4;
-    if (!qt_al(a->q, es) || !qt_al(a->k, es) || !qt_al(a->v, es) || !qt_al(a->y, es)) return 0;
-    if (a->use_quartet && (!qt_al(a->q2, es) || !qt_al(a->k2, es))) return 0;
+    const int64_t al = a->io_dtype == MOPK_BF16 ? 8 : 4;           // elements per 16-byte vector
+    if (!views_aligned16(al, a->q, a->k, a->v, a->y)) return 0;
+    if (a->use_quartet && !views_aligned16(al, a->q2, a->k2)) return 0;
     if (bwd) {
-        if (!qt_al(a->dy, es) || !qt_al(a->dq, es) || !qt_al(a->dk_, es) || !qt_al(a->dv, es)) return 0;
-        if (a->use_quartet && (!qt_al(a->dq2, es) || !qt_al(a->dk2, es))) return 0;
+        if (!views_aligned16(al, a->dy, a->dq, a->dk_, a->dv)) return 0;
+        if (a->use_quartet && !views_aligned16(al, a->dq2, a->dk2)) return 0;
     }
     return 1;
 }
@@ -540,8 +536,7 @@ int qt_flash_fwd(const MopkQuartetArgs *a, hipStream_t st) {
     const dim3 grid(nq * a->B * a->H);
     QT_LAUNCH_STATS(qt_stats_kernel, grid, *a, b.stats);
     QT_LAUNCH(qt_fwd_kernel, grid, *a, (const float *)b.stats, b.lse);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 int qt_flash_bwd(const MopkQuartetArgs *a, hipStream_t st) {
     if (!qt_flash_supported(a, true)) return MOPK_ERR_UNSUPPORTED;
@@ -557,8 +552,7 @@ int qt_flash_bwd(const MopkQuartetArgs *a, hipStream_t st) {
                            a->mixture, a->dmixture_part, a->dqscale_part);
     QT_LAUNCH(qt_dq_kernel, grid, *a, (const float *)b.stats, (const float *)b.lse, (const float *)b.delta, (const float *)b.rows);
     QT_LAUNCH(qt_dkv_kernel, grid, *a, (const float *)b.stats, (const float *)b.lse, (const float *)b.delta, (const float *)b.rows);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 }  // namespace mopk

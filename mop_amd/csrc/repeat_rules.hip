@@ -112,7 +112,7 @@ int rr_check(const MopkRepeatRulesArgs *a) {
     if (a->out == a->logits && a->R > 1 && a->out_ld != a->logits_ld) return MOPK_ERR_BAD_ARG;   // in place: the same rows
     if (a->T - a->T0 > RR_MAX_G) return MOPK_ERR_UNSUPPORTED;
     const int es = a->dtype == MOPK_BF16 ? 2 : 4;
-    if ((uintptr_t)a->logits % es || (uintptr_t)a->out % es || ((uintptr_t)a->hist & 3) || ((uintptr_t)a->pos & 3))
+    if (misaligned(es - 1, a->logits, a->out) || misaligned(3, a->hist, a->pos))
         return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
@@ -129,11 +129,11 @@ int mopk_repeat_rules_supported(const MopkRepeatRulesArgs *a) { return rr_check(
 int mopk_repeat_rules(const MopkRepeatRulesArgs *a, void *stream) {
     const int rc = rr_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->logits || !a->out || !a->hist || !a->pos || !a->exempt) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->logits, a->out, a->hist, a->pos, a->exempt)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (a->dtype == MOPK_BF16) hipLaunchKernelGGL((rr_row_kernel<unsigned short>), dim3((unsigned)a->R), dim3(RR_THREADS), 0, st, *a);
     else hipLaunchKernelGGL((rr_row_kernel<float>), dim3((unsigned)a->R), dim3(RR_THREADS), 0, st, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

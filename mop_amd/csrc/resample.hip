@@ -136,8 +136,7 @@ int rs_check(const MopkResampleArgs *a) {
         return MOPK_ERR_BAD_ARG;
     if (a->out_dtype != MOPK_F32 && a->out_dtype != MOPK_BF16) return MOPK_ERR_BAD_ARG;
     const uintptr_t am = a->audio_dtype == MOPK_F32 ? 3 : 1, om = a->out_dtype == MOPK_F32 ? 3 : 1;
-    if (((uintptr_t)a->audio & am) || ((uintptr_t)a->out & om) || ((uintptr_t)a->lens & 3) || ((uintptr_t)a->table & 3) ||
-        ((uintptr_t)a->first & 3) || ((uintptr_t)a->out_lens & 3))
+    if (misaligned(am, a->audio) || misaligned(om, a->out) || misaligned(3, a->lens, a->table, a->first, a->out_lens))
         return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
@@ -150,7 +149,7 @@ template <typename TIN, typename TOUT> int rs_launch(const MopkResampleArgs *a, 
     const float inv_c = 1.0f / (float)a->C;                                     // rounded once, on the host
     if (tab_lds) hipLaunchKernelGGL((rs_kernel<TIN, TOUT, true>), grid, dim3(RS_THREADS), lds, st, *a, span_max, inv_c);
     else hipLaunchKernelGGL((rs_kernel<TIN, TOUT, false>), grid, dim3(RS_THREADS), lds, st, *a, span_max, inv_c);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 template <typename TIN> int rs_launch_out(const MopkResampleArgs *a, hipStream_t st) {
@@ -169,7 +168,7 @@ int mopk_resample_supported(const MopkResampleArgs *a) { return rs_check(a) == M
 int mopk_resample(const MopkResampleArgs *a, void *stream) {
     const int rc = rs_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->audio || !a->table || !a->first || !a->out) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->audio, a->table, a->first, a->out)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (a->audio_dtype == MOPK_F32) return rs_launch_out<float>(a, st);
     if (a->audio_dtype == MOPK_BF16) return rs_launch_out<unsigned short>(a, st);

@@ -239,7 +239,7 @@ int sp_check(const MopkSampleArgs *a) {
         if (a->top_k < 0 || !(a->top_p > 0.f) || !(a->top_p <= 1.f)) return MOPK_ERR_BAD_ARG;
     }
     const int es = a->logits_dtype == MOPK_BF16 ? 2 : 4;
-    if ((uintptr_t)a->logits % es) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(es - 1, a->logits)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -249,7 +249,7 @@ int sp_ragged_check(const MopkSampleRaggedArgs *a) {
     const int rc = sp_check(&a->base);
     if (rc != MOPK_OK) return rc;
     if (!a->pos_off) return MOPK_ERR_BAD_ARG;
-    if ((uintptr_t)a->pos_off & 3) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->pos_off)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 #endif
@@ -272,12 +272,12 @@ size_t mopk_sample_workspace_bytes(const MopkSampleArgs *a) {
 int mopk_sample_step(const MopkSampleArgs *a, void *stream) {
     const int rc = sp_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->logits || !a->pos || !a->tokens || !a->logprobs) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->logits, a->pos, a->tokens, a->logprobs)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (a->logits_dtype == MOPK_BF16)
         hipLaunchKernelGGL((sp_row_kernel<unsigned short, false>), dim3((unsigned)a->R), dim3(SP_THREADS), 0, st, *a, nullptr);
     else hipLaunchKernelGGL((sp_row_kernel<float, false>), dim3((unsigned)a->R), dim3(SP_THREADS), 0, st, *a, nullptr);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 #else   // the ragged exports: this file compiled a second time with -DMOPK_SAMPLE_RAGGED (mop_amd/build.py)
 int mopk_sample_ragged_supported(const MopkSampleRaggedArgs *a) { return sp_ragged_check(a) == MOPK_OK; }
@@ -290,12 +290,12 @@ int mopk_sample_ragged_step(const MopkSampleRaggedArgs *a, void *stream) {
     const int rc = sp_ragged_check(a);
     if (rc != MOPK_OK) return rc;
     const MopkSampleArgs *b = &a->base;
-    if (!b->logits || !b->pos || !b->tokens || !b->logprobs) return MOPK_ERR_BAD_ARG;
+    if (any_null(b->logits, b->pos, b->tokens, b->logprobs)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (b->logits_dtype == MOPK_BF16)
         hipLaunchKernelGGL((sp_row_kernel<unsigned short, true>), dim3((unsigned)b->R), dim3(SP_THREADS), 0, st, *b, a->pos_off);
     else hipLaunchKernelGGL((sp_row_kernel<float, true>), dim3((unsigned)b->R), dim3(SP_THREADS), 0, st, *b, a->pos_off);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 #endif
 

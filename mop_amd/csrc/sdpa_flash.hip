@@ -439,17 +439,13 @@ __global__ void __launch_bounds__(FA_NW * 64, DUAL ? 1 : 2) sdpa_flash_dkv_kerne
 
 // ------------------------------------------------------------------ host side
 #ifndef MOPK_SDPA_LENS
-static bool fa_aligned(const MopkView4 &v, int es) {
-    const int64_t al = 16 / es;
-    return ((uintptr_t)v.ptr & 15) == 0 && v.sb % al == 0 && v.sh % al == 0 && v.sn % al == 0;
-}
 int sdpa_flash_supported(const MopkSdpaArgs *a, bool bwd) {
     if (a->precision != MOPK_PREC_BF16) return 0;                 // fp32-exact arithmetic stays on the generic path
     if (a->dk != 32 && a->dk != 64) return 0;
     if (a->causal && sdpa_nk(*a) != a->N) return 0;               // causal is defined for square calls only
-    const int es = a->io_dtype == MOPK_BF16 ? 2 : 4;
-    if (!fa_aligned(a->q, es) || !fa_aligned(a->k, es) || !fa_aligned(a->v, es) || !fa_aligned(a->y, es)) return 0;
-    if (bwd && (!fa_aligned(a->dy, es) || !fa_aligned(a->dq, es) || !fa_aligned(a->dk_, es) || !fa_aligned(a->dv, es))) return 0;
+    const int64_t al = a->io_dtype == MOPK_BF16 ? 8 : 4;           // elements per 16-byte vector
+    if (!views_aligned16(al, a->q, a->k, a->v, a->y)) return 0;
+    if (bwd && !views_aligned16(al, a->dy, a->dq, a->dk_, a->dv)) return 0;
     return 1;
 }
 size_t sdpa_flash_saved_bytes(const MopkSdpaArgs *a) { return (size_t)a->B * a->H * a->N * sizeof(float) + 256; }   // row log-sum-exp
@@ -474,8 +470,7 @@ int sdpa_flash_fwd(const MopkSdpaArgs *a, hipStream_t st) {
     if (!sdpa_flash_supported(a, false)) return MOPK_ERR_UNSUPPORTED;
     const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H);
     FA_DISPATCH(sdpa_flash_fwd_kernel, false, grid, *a, (float *)a->saved, FaDual{});
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 int sdpa_flash_bwd(const MopkSdpaArgs *a, hipStream_t st) {
     if (!sdpa_flash_supported(a, true)) return MOPK_ERR_UNSUPPORTED;
@@ -483,13 +478,12 @@ int sdpa_flash_bwd(const MopkSdpaArgs *a, hipStream_t st) {
     float *delta = (float *)a->workspace;
     if (a->io_dtype == MOPK_BF16) hipLaunchKernelGGL((sdpa_flash_delta_kernel<unsigned short>), dim3((rows * (a->dk / 8) + 255) / 256), dim3(256), 0, st, *a, delta);
     else hipLaunchKernelGGL((sdpa_flash_delta_kernel<float>), dim3((rows * (a->dk / 8) + 255) / 256), dim3(256), 0, st, *a, delta);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H), kgrid(((sdpa_nk(*a) + FA_QB - 1) / FA_QB) * a->B * a->H);
     FA_DISPATCH(sdpa_flash_dq_kernel, false, grid, *a, (const float *)a->saved, (const float *)delta, FaDual{});
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     FA_DISPATCH(sdpa_flash_dkv_kernel, false, kgrid, *a, (const float *)a->saved, (const float *)delta, FaDual{});
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 // ------------------------------------------------------------------ dual path (MultiHopMSA) on the fused kernels
@@ -615,8 +609,7 @@ static int dp_plain_fwd(const MopkDualPathArgs *d, const MopkView4 &q, const Mop
     const MopkSdpaArgs *a = &s;
     const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H);
     FA_DISPATCH(sdpa_flash_fwd_kernel, false, grid, *a, lse, FaDual{});
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 static int dp_plain_bwd(const MopkDualPathArgs *d, const MopkView4 &q, const MopkView4 &k, const MopkView4 &v, const MopkView4 &y,
                         const MopkView4 &dy, const MopkView4 &dq, const MopkView4 &dk, const MopkView4 &dv, const float *lse, float *delta,
@@ -630,8 +623,7 @@ static int dp_plain_bwd(const MopkDualPathArgs *d, const MopkView4 &q, const Mop
     const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H);
     FA_DISPATCH(sdpa_flash_dq_kernel, false, grid, *a, lse, (const float *)delta, FaDual{});
     FA_DISPATCH(sdpa_flash_dkv_kernel, false, grid, *a, lse, (const float *)delta, FaDual{});
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 int dp_flash_fwd(const MopkDualPathArgs *a, hipStream_t st) {
@@ -647,7 +639,7 @@ int dp_flash_fwd(const MopkDualPathArgs *a, hipStream_t st) {
         const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H);
         const MopkSdpaArgs *keep = a ? &s : nullptr;
         { const MopkSdpaArgs *a = keep; FA_DISPATCH(sdpa_flash_fwd_kernel, true, grid, *a, L.lse_m, u); }
-        MOPK_CHECK_LAUNCH();
+        if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     }
     if (a->hops == 0) return MOPK_OK;                              // two-score attention only (CrossViewMixerMSA's fused path)
     MopkView4 t = a->v2;                                           // value transport A1 A2^(hops-1) v2   :224-227
@@ -658,8 +650,7 @@ int dp_flash_fwd(const MopkDualPathArgs *a, hipStream_t st) {
     }
     int rc = dp_plain_fwd(a, a->q1, a->k1, t, yc, L.lse_1, st); if (rc) return rc;
     DP_ELEM(dp_combine_kernel, a->y, o1, yc, a->chain_logit);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 int dp_flash_bwd(const MopkDualPathArgs *a, hipStream_t st) {
@@ -674,7 +665,7 @@ int dp_flash_bwd(const MopkDualPathArgs *a, hipStream_t st) {
     else if (a->io_dtype == MOPK_BF16) hipLaunchKernelGGL((dp_dlogit_kernel<unsigned short>), dim3(a->B * a->H), dim3(256), 0, st, a->dy, yc, a->chain_logit, a->dlogit_part, a->H, a->N, a->dk);
     else hipLaunchKernelGGL((dp_dlogit_kernel<float>), dim3(a->B * a->H), dim3(256), 0, st, a->dy, yc, a->chain_logit, a->dlogit_part, a->H, a->N, a->dk);
     if (a->hops > 0) DP_ELEM(dp_scale_kernel, g, a->dy, a->chain_logit);   // gradient reaching the transport term
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     {   // mixed-logit pass: dq1, dk1, dv1, dq2, dk2 straight into the caller's tensors
         MopkSdpaArgs s = dp_sdpa(a);
         s.q = a->q1; s.k = a->k1; s.v = a->v1; s.y = o1; s.dy = a->dy; s.dq = a->dq1; s.dk_ = a->dk1; s.dv = a->dv1;
@@ -687,7 +678,7 @@ int dp_flash_bwd(const MopkDualPathArgs *a, hipStream_t st) {
         const MopkSdpaArgs *keep = &s;
         { const MopkSdpaArgs *a = keep; FA_DISPATCH(sdpa_flash_dq_kernel, true, grid, *a, (const float *)L.lse_m, (const float *)W.delta, u);
           FA_DISPATCH(sdpa_flash_dkv_kernel, true, grid, *a, (const float *)L.lse_m, (const float *)W.delta, u); }
-        MOPK_CHECK_LAUNCH();
+        if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     }
     if (a->hops == 0) return MOPK_OK;
     // transport term backwards: yc = A1 t_{h-1}, t_i = A2 t_{i-1}, t_0 = v2
@@ -701,8 +692,7 @@ int dp_flash_bwd(const MopkDualPathArgs *a, hipStream_t st) {
         DP_ELEM(dp_add_kernel, a->dq2, tq); DP_ELEM(dp_add_kernel, a->dk2, tk);
         cur = nxt;
     }
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 
 #else   // MOPK_SDPA_LENS: the unit of the LENS = true instantiations (plain SDPA only: no mask / bias tensor, no dual path)
@@ -724,8 +714,7 @@ int sdpa_flash_lens_fwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int3
     const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H);
     const FaLens ln{q_lens, kv_lens};
     FA_LENS_DISPATCH(sdpa_flash_fwd_kernel, grid, *a, (float *)a->saved, FaDual{}, ln);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 int sdpa_flash_lens_bwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int32_t *kv_lens, hipStream_t st) {
     if (a->mask || a->bias || !sdpa_flash_supported(a, true)) return MOPK_ERR_UNSUPPORTED;
@@ -733,14 +722,13 @@ int sdpa_flash_lens_bwd(const MopkSdpaArgs *a, const int32_t *q_lens, const int3
     float *delta = (float *)a->workspace;       // delta of a padding row is dy . 0: never read by the LENS kernels
     if (a->io_dtype == MOPK_BF16) hipLaunchKernelGGL((sdpa_flash_delta_kernel<unsigned short>), dim3((rows * (a->dk / 8) + 255) / 256), dim3(256), 0, st, *a, delta);
     else hipLaunchKernelGGL((sdpa_flash_delta_kernel<float>), dim3((rows * (a->dk / 8) + 255) / 256), dim3(256), 0, st, *a, delta);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     const dim3 grid(((a->N + FA_QB - 1) / FA_QB) * a->B * a->H), kgrid(((sdpa_nk(*a) + FA_QB - 1) / FA_QB) * a->B * a->H);
     const FaLens ln{q_lens, kv_lens};
     FA_LENS_DISPATCH(sdpa_flash_dq_kernel, grid, *a, (const float *)a->saved, (const float *)delta, FaDual{}, ln);
-    MOPK_CHECK_LAUNCH();
+    if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     FA_LENS_DISPATCH(sdpa_flash_dkv_kernel, kgrid, *a, (const float *)a->saved, (const float *)delta, FaDual{}, ln);
-    MOPK_CHECK_LAUNCH();
-    return MOPK_OK;
+    return launch_status();
 }
 #endif  // MOPK_SDPA_LENS
 

@@ -105,8 +105,7 @@ int ts_check(const MopkTimestampSegmentsArgs *a) {
     if (a->T0 < 0 || a->T0 >= a->T || a->tokens_ld < a->T) return MOPK_ERR_BAD_ARG;
     if (a->eos < 0 || a->eos >= a->tb || a->f < 1) return MOPK_ERR_BAD_ARG;
     if (a->T - a->T0 > TS_MAXS) return MOPK_ERR_UNSUPPORTED;
-    if (((uintptr_t)a->tokens & 3) || ((uintptr_t)a->window & 3) || ((uintptr_t)a->starts & 3) || ((uintptr_t)a->ends & 3) ||
-        ((uintptr_t)a->tok_begin & 3) || ((uintptr_t)a->tok_end & 3) || ((uintptr_t)a->n_segments & 3) || ((uintptr_t)a->advance & 3))
+    if (misaligned(3, a->tokens, a->window, a->starts, a->ends, a->tok_begin, a->tok_end, a->n_segments, a->advance))
         return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
@@ -123,11 +122,10 @@ int mopk_timestamp_segments_supported(const MopkTimestampSegmentsArgs *a) { retu
 int mopk_timestamp_segments(const MopkTimestampSegmentsArgs *a, void *stream) {
     const int rc = ts_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->tokens || !a->window || !a->starts || !a->ends || !a->tok_begin || !a->tok_end || !a->n_segments || !a->advance)
-        return MOPK_ERR_BAD_ARG;
+    if (any_null(a->tokens, a->window, a->starts, a->ends, a->tok_begin, a->tok_end, a->n_segments, a->advance)) return MOPK_ERR_BAD_ARG;
     const int threads = (a->T - a->T0 + WAVE - 1) / WAVE * WAVE;
     hipLaunchKernelGGL(ts_row_kernel, dim3((unsigned)a->R), dim3(threads), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -257,7 +257,6 @@ __global__ __launch_bounds__(1024) void tg_reduce_kernel(const float *part, int 
     }
 }
 
-bool tg_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 bool tg_dtype_ok(int d) { return d == MOPK_F32 || d == MOPK_BF16; }
 
 // shape / dtype / stride / alignment rules shared by the support query and the entry points (pointers checked when non-null)
@@ -271,9 +270,7 @@ int tg_check(const MopkTokenGateArgs *a) {
     if (a->o_dtype != promo) return MOPK_ERR_UNSUPPORTED;
     if (a->x_sb % 8 || a->x_st % 8 || a->x_st < a->D) return MOPK_ERR_UNSUPPORTED;
     if (a->a && (a->a_sb % 8 || a->a_st % 8 || a->a_st < a->D)) return MOPK_ERR_UNSUPPORTED;
-    for (const void *p : {a->x, a->a, (const void *)a->u, (const void *)a->out, (const void *)a->dout, (const void *)a->dr,
-                          (const void *)a->du, (const void *)a->workspace})
-        if (p && !tg_al16(p)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(15, a->x, a->a, a->u, a->out, a->dout, a->dr, a->du, a->workspace)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -321,20 +318,20 @@ size_t mopk_token_gate_workspace_bytes(const MopkTokenGateArgs *a) {
 int mopk_token_gate_fwd(const MopkTokenGateArgs *a, void *stream) {
     const int rc = tg_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->x || !a->u || !a->out || !a->gate) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->x, a->u, a->out, a->gate)) return MOPK_ERR_BAD_ARG;
     tg_dispatch(a, false, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_token_gate_bwd(const MopkTokenGateArgs *a, void *stream) {
     const int rc = tg_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->x || !a->u || !a->gate || !a->dout || !a->dr || !a->du || !a->workspace) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->x, a->u, a->gate, a->dout, a->dr, a->du, a->workspace)) return MOPK_ERR_BAD_ARG;
     tg_dispatch(a, true, (hipStream_t)stream);
     const int n = 3 * a->D;
     hipLaunchKernelGGL(tg_reduce_kernel, dim3((n + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float *)a->workspace,
                        tg_parts(a), n, a->du);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

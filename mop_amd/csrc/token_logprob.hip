@@ -123,7 +123,7 @@ int tl_row_check(int R, int V, int dtype, const void *logits, int64_t ld) {
     if (R <= 0 || V < 2) return MOPK_ERR_BAD_SHAPE;
     if (dtype != MOPK_F32 && dtype != MOPK_BF16) return MOPK_ERR_BAD_ARG;
     if (ld < V) return MOPK_ERR_BAD_ARG;
-    if ((uintptr_t)logits % (dtype == MOPK_BF16 ? 2 : 4)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(dtype == MOPK_BF16 ? 1 : 3, logits)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -132,7 +132,7 @@ int tl_check(const MopkTokenLogprobArgs *a) {
     const int rc = tl_row_check(a->R, a->V, a->dtype, a->logits, a->logits_ld);
     if (rc != MOPK_OK) return rc;
     if (!a->tokens && (a->token < 0 || a->token >= a->V)) return MOPK_ERR_BAD_ARG;
-    if (((uintptr_t)a->tokens & 3) || ((uintptr_t)a->out & 3)) return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->tokens, a->out)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -142,9 +142,7 @@ int gp_check(const MopkGreedyPickArgs *a) {
     if (rc != MOPK_OK) return rc;
     if (a->eos < -1 || a->eos >= a->V || a->reserved != 0) return MOPK_ERR_BAD_ARG;
     if (a->hist_cap < 0 || (a->hist && a->hist_ld < a->hist_cap)) return MOPK_ERR_BAD_ARG;
-    if (((uintptr_t)a->pos & 3) || ((uintptr_t)a->next_ids & 3) || ((uintptr_t)a->done & 3) || ((uintptr_t)a->sum_logprobs & 3) ||
-        ((uintptr_t)a->n_tokens & 3) || ((uintptr_t)a->hist & 3))
-        return MOPK_ERR_UNSUPPORTED;
+    if (misaligned(3, a->pos, a->next_ids, a->done, a->sum_logprobs, a->n_tokens, a->hist)) return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
 
@@ -160,11 +158,11 @@ int mopk_token_logprob_supported(const MopkTokenLogprobArgs *a) { return tl_chec
 int mopk_token_logprob(const MopkTokenLogprobArgs *a, void *stream) {
     const int rc = tl_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->logits || !a->out) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->logits, a->out)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (a->dtype == MOPK_BF16) hipLaunchKernelGGL((tl_row_kernel<unsigned short>), dim3((unsigned)a->R), dim3(TL_THREADS), 0, st, *a);
     else hipLaunchKernelGGL((tl_row_kernel<float>), dim3((unsigned)a->R), dim3(TL_THREADS), 0, st, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_greedy_pick_supported(const MopkGreedyPickArgs *a) { return gp_check(a) == MOPK_OK; }
@@ -172,11 +170,11 @@ int mopk_greedy_pick_supported(const MopkGreedyPickArgs *a) { return gp_check(a)
 int mopk_greedy_pick(const MopkGreedyPickArgs *a, void *stream) {
     const int rc = gp_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->logits || !a->pos || !a->next_ids || !a->done || !a->sum_logprobs || !a->n_tokens) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->logits, a->pos, a->next_ids, a->done, a->sum_logprobs, a->n_tokens)) return MOPK_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (a->dtype == MOPK_BF16) hipLaunchKernelGGL((gp_row_kernel<unsigned short>), dim3((unsigned)a->R), dim3(TL_THREADS), 0, st, *a);
     else hipLaunchKernelGGL((gp_row_kernel<float>), dim3((unsigned)a->R), dim3(TL_THREADS), 0, st, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -186,8 +186,7 @@ int ar_check(const MopkAlignmentRowsArgs *a) {
     if ((a->out_i64 != 0 && a->out_i64 != 1) || (a->sot_i64 != 0 && a->sot_i64 != 1)) return MOPK_ERR_BAD_ARG;
     if (a->T - a->T0 > WS_MAXN) return MOPK_ERR_UNSUPPORTED;
     const uintptr_t om = a->out_i64 ? 7 : 3, sm = a->sot_i64 ? 7 : 3;
-    if (((uintptr_t)a->tokens & 3) || ((uintptr_t)a->n_take & 3) || ((uintptr_t)a->sot & sm) || ((uintptr_t)a->ids & om) ||
-        ((uintptr_t)a->n_tokens & 3) || ((uintptr_t)a->col & 3))
+    if (misaligned(3, a->tokens, a->n_take) || misaligned(sm, a->sot) || misaligned(om, a->ids) || misaligned(3, a->n_tokens, a->col))
         return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
@@ -197,9 +196,7 @@ int ws_check(const MopkWordSpansArgs *a) {
     if (a->R <= 0 || a->N <= 0 || a->V <= 0) return MOPK_ERR_BAD_SHAPE;
     if (a->tokens_ld < a->N || a->times_ld < (int64_t)a->N + 1 || a->probs_ld < a->N || a->median_cap < -1) return MOPK_ERR_BAD_ARG;
     if (a->N > WS_MAXN) return MOPK_ERR_UNSUPPORTED;
-    if (((uintptr_t)a->tokens & 3) || ((uintptr_t)a->times & 3) || ((uintptr_t)a->probs & 3) || ((uintptr_t)a->n_text & 3) ||
-        ((uintptr_t)a->starts & 3) || ((uintptr_t)a->ends & 3) || ((uintptr_t)a->out_probs & 3) || ((uintptr_t)a->tok_begin & 3) ||
-        ((uintptr_t)a->tok_end & 3) || ((uintptr_t)a->n_words & 3))
+    if (misaligned(3, a->tokens, a->times, a->probs, a->n_text, a->starts, a->ends, a->out_probs, a->tok_begin, a->tok_end, a->n_words))
         return MOPK_ERR_UNSUPPORTED;
     return MOPK_OK;
 }
@@ -216,10 +213,10 @@ int mopk_alignment_rows_supported(const MopkAlignmentRowsArgs *a) { return ar_ch
 int mopk_alignment_rows(const MopkAlignmentRowsArgs *a, void *stream) {
     const int rc = ar_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->tokens || !a->n_take || !a->sot || !a->ids || !a->n_tokens || !a->col) return MOPK_ERR_BAD_ARG;
+    if (any_null(a->tokens, a->n_take, a->sot, a->ids, a->n_tokens, a->col)) return MOPK_ERR_BAD_ARG;
     const int threads = (a->T - a->T0 + WAVE - 1) / WAVE * WAVE;
     hipLaunchKernelGGL(ar_row_kernel, dim3((unsigned)a->R), dim3(threads), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 int mopk_word_spans_supported(const MopkWordSpansArgs *a) { return ws_check(a) == MOPK_OK; }
@@ -227,12 +224,11 @@ int mopk_word_spans_supported(const MopkWordSpansArgs *a) { return ws_check(a) =
 int mopk_word_spans(const MopkWordSpansArgs *a, void *stream) {
     const int rc = ws_check(a);
     if (rc != MOPK_OK) return rc;
-    if (!a->tokens || !a->times || !a->probs || !a->n_text || !a->table || !a->starts || !a->ends || !a->out_probs ||
-        !a->tok_begin || !a->tok_end || !a->n_words)
+    if (any_null(a->tokens, a->times, a->probs, a->n_text, a->table, a->starts, a->ends, a->out_probs, a->tok_begin, a->tok_end, a->n_words))
         return MOPK_ERR_BAD_ARG;
     const int threads = (a->N + WAVE - 1) / WAVE * WAVE;
     hipLaunchKernelGGL(ws_row_kernel, dim3((unsigned)a->R), dim3(threads), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? MOPK_OK : MOPK_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"
