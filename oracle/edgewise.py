@@ -153,7 +153,7 @@ def dense_head_bwd(dZ, c, hp):
 # ----------------------------------------------------------------------------
 # attention core: everything between the qkv projection and the out projection
 # ----------------------------------------------------------------------------
-def core_fwd(qv, kv, v0, vL, Wr, br, Wc, bc, beta_not, chain_logit, dense=None, lens=None, drop=None, blocked=None):
+def core_fwd(qv, kv, v0, vL, Wr, br, Wc, bc, beta_not, chain_logit, dense=None, lens=None, drop=None, blocked=None, rnd=None):
     """EdgewiseMSA.forward :500-562 for per-view queries/keys.
 
     qv, kv : (V,B,H,N,dk)  per-view q_i, k_i   (:461-470)
@@ -165,25 +165,31 @@ def core_fwd(qv, kv, v0, vL, Wr, br, Wc, bc, beta_not, chain_logit, dense=None, 
              -inf before they enter the feature stack (:504-506 feed :518-546), which makes every output NaN for any blocking mask
              (SURVEY.md 8a note).  Here the mask acts on the attention probabilities only -- the per-view softmaxes (:507) and the final
              one (:549-551) -- while the gate features (scores, their means, lse, chain logs) see the unmasked finite scores.
+    rnd    : None or rnd(site, array) -> array, applied where a reduced-precision implementation stores an intermediate: 'A' the
+             per-view softmaxes, 'chain' every chain product, 'logC' the chain logarithms, 'P' the mixed softmax.  For models of
+             rounding noise (tests/edgewise_peaks.py); core_bwd then differentiates around the rounded values.
     returns y (B,H,N,dk) and a cache for core_bwd.
     """
     V, B, H, N, dk = qv.shape
     scale = 1.0 / math.sqrt(dk)
+    if rnd is None:
+        rnd = lambda site, x: x
     S = np.matmul(qv, np.swapaxes(kv, -1, -2)) * scale          # :500-503  (V,B,H,N,N)
     if blocked is not None:
         blocked = np.broadcast_to(np.asarray(blocked, dtype=bool), S.shape[1:])
         A = _masked_softmax(S, blocked[None])                     # :504-507
     else:
         A = _softmax(S, -1)                                       # :507
+    A = rnd("A", A)
     T = [A[0]]                                                    # :508-512 prefix products
     for i in range(1, V):
-        T.append(np.matmul(T[-1], A[i]))
+        T.append(rnd("chain", np.matmul(T[-1], A[i])))
     U = [A[V - 1]]                                                # :513-515
     for i in range(V - 2, -1, -1):
-        U.append(np.matmul(U[-1], A[i]))
+        U.append(rnd("chain", np.matmul(U[-1], A[i])))
     Cf, Cb = T[-1], U[-1]
-    Cr = np.log(Cf + EPS_CHAIN)                                   # :520
-    Cl = np.log(Cb + EPS_CHAIN)                                   # :521
+    Cr = rnd("logC", np.log(Cf + EPS_CHAIN))                      # :520
+    Cl = rnd("logC", np.log(Cb + EPS_CHAIN))                      # :521
     # feature stack [S_v, S_v^T, Cr, Cl] (:522) is only consumed through its
     # row/col means (:323-324); mean over rows of S_v^T == col-mean of S_v.
     Lz = lens_fwd(S, lens[0], lens[1]) if lens is not None else None     # (L,V,B,H,N,N)
@@ -224,6 +230,7 @@ def core_fwd(qv, kv, v0, vL, Wr, br, Wc, bc, beta_not, chain_logit, dense=None, 
         P = _masked_softmax(Smix, blocked)                        # :549-550
     else:
         P = _softmax(Smix, -1)                                    # :551
+    P = rnd("P", P)
     Pd = P if drop is None else P * drop                          # :552 attn_drop with the mask made explicit: drop = keep / (1 - p)
     y_base = np.matmul(Pd, v0)                                    # :554
     t = [None] * V                                                # :557-560 value transport

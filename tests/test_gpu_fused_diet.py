@@ -183,22 +183,12 @@ def _abi_inputs(N, dk):
 
 @functools.lru_cache(maxsize=None)
 def _abi_oracle(N, dk, same):
-    from oracle import edgewise as oe
+    from edgewise_peaks import core_oracle                               # the oracle in the core's layouts, stated once
     q, k, v0, vL, dy, small, head = _abi_inputs(N, dk)
     f = lambda t: t.numpy().astype(np.float64)
-    hv = lambda t: np.transpose(f(t), (0, 2, 1, 3))                      # (B,N,H,dk) -> (B,H,N,dk)
     sqk, vs0, vsL, lg = map(f, small)
-    qv = hv(q)[None] * (sqk * dk ** 0.5)[:, None, :, None, :]              # core_fwd scales the scores by 1 / sqrt(dk) itself
-    kv = np.broadcast_to(hv(k)[None], qv.shape)
-    vl = v0 if same else vL
-    y, cache = oe.core_fwd(qv, kv, hv(v0) * vs0[None, :, None], hv(vl) * vsL[None, :, None], *map(f, head), 0.5, float(lg[0]))
-    o = oe.core_bwd(hv(dy), cache)
-    tok = lambda t: np.transpose(t, (0, 2, 1, 3))
-    dq = tok((o["dqv"] * (sqk * dk ** 0.5)[:, None, :, None, :]).sum(0))
-    dk_ = tok(o["dkv"].sum(0))
-    dv0, dvL = tok(o["dv0"] * vs0[None, :, None]), tok(o["dvL"] * vsL[None, :, None])
-    pvs0, pvsL = (o["dv0"] * hv(v0)).sum(2), (o["dvL"] * hv(vl)).sum(2)   # per (b,h): d/d vs0, d/d vsL
-    return tok(y), dq, dk_, dv0, dvL, pvs0, pvsL
+    o = core_oracle(f(q), f(k), f(v0), f(v0 if same else vL), f(dy), sqk, vs0, vsL, float(lg[0]), tuple(map(f, head)), 0.5)
+    return o["y"], o["dq"], o["dk"], o["dv0"], o["dvL"], o["dvs0_bh"], o["dvsL_bh"]   # the last two per (b,h): d/d vs0, d/d vsL
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
