@@ -6,7 +6,7 @@
 // before a row's first 16-byte boundary and after its last whole vector are read one by one by the first / last slice), and each
 // thread keeps an online (max, sum-exp) pair and a sorted register list of its NC = 2K best (logit, index) entries.  The pairs are
 // combined and the lists merged pairwise through LDS in a fixed tree order; the slice writes (m, l) and its NC best entries (padded
-// with sentinels, index BS_SENT, which rank after every real entry, -inf ones included) to the workspace.  The slice count is chosen
+// with sentinels, index ROW_NONE, which rank after every real entry, -inf ones included) to the workspace.  The slice count is chosen
 // so that B * K * slices reaches about two workgroups per CU even at B = 1, K = 5.
 // Launch B (bs_item_kernel): one workgroup per batch item.  Each beam's log-sum-exp is merged from its slices in slice order; every
 // slice candidate becomes (score = scores[k] + (logit - lse[k]), flat index k * V + v) and the item's NC best are selected by the same
@@ -27,7 +27,6 @@ constexpr int BS_B_THREADS = 256;       // launch B workgroup
 constexpr int BS_MIN_VEC = 128;         // 16-byte vectors per slice at least: one per launch-A thread
 constexpr int BS_TARGET_WG = 512;       // launch-A workgroups aimed for (two per CU on a 256-CU MI355X)
 constexpr int BS_COLS = 256;            // history columns per reorder block
-constexpr int BS_SENT = 0x7fffffff;     // sentinel index: ranks after every real candidate
 
 // insert into a sorted register list of NC entries (dropped when it ranks after the last one)
 template <int NC>
@@ -94,7 +93,7 @@ __host__ __device__ inline BsWs bs_ws(const MopkBeamArgs &a, int nslice) {
 // whose own form hipcc compiles to 256 VGPRs and AGPR copies (a longer sorted list only adds entries after the first NC).
 template <typename T, int NC>
 __global__ __launch_bounds__(BS_A_THREADS) void bs_rows_kernel(MopkBeamArgs a, int nslice) {
-    constexpr int ES = (int)sizeof(T), EPV = 16 / ES;
+    constexpr int EPV = RowSpan<T>::EPV;
     constexpr int LN = NC == 14 ? 16 : NC;
     __shared__ float ws[BS_A_THREADS * LN];
     __shared__ int wi[BS_A_THREADS * LN];
@@ -104,15 +103,14 @@ __global__ __launch_bounds__(BS_A_THREADS) void bs_rows_kernel(MopkBeamArgs a, i
     if (a.done[b]) return;                                      // launch B leaves a done item untouched as well
     const int V = a.V;
     const T *x = (const T *)a.logits + (int64_t)b * a.logits_sb + (int64_t)k * a.logits_sk;
-    int head = (int)(((16 - ((uintptr_t)x & 15)) & 15) / ES);   // elements before the row's first 16-byte boundary
-    head = head < V ? head : V;
-    const int nvec = (V - head) / EPV, tail0 = head + nvec * EPV;
+    const RowSpan<T> sp(x, V);
+    const int head = sp.head, nvec = sp.nvec, tail0 = sp.tail0;
     const int u0 = (int)((int64_t)nvec * slice / nslice), u1 = (int)((int64_t)nvec * (slice + 1) / nslice);
 
     float ls[LN];
     int li[LN];
 #pragma unroll
-    for (int j = 0; j < LN; ++j) { ls[j] = -INFINITY; li[j] = BS_SENT; }
+    for (int j = 0; j < LN; ++j) { ls[j] = -INFINITY; li[j] = ROW_NONE; }
     float m = -INFINITY, l = 0.f;
     const uint4 *xv = (const uint4 *)(x + head);
     for (int u = u0 + tid; u < u1; u += BS_A_THREADS) {
@@ -140,8 +138,8 @@ __global__ __launch_bounds__(BS_A_THREADS) void bs_rows_kernel(MopkBeamArgs a, i
         bs_insert(ls, li, f, e);
     }
 
-    rm[tid] = m;
-    rl[tid] = l;
+    rm[tid] = m;                                                // pairwise trees through LDS, not row_helpers.h's wave-then-waves
+    rl[tid] = l;                                                // order: the step's results depend on this one
     bs_block_merge<LN, BS_A_THREADS>(ls, li, ws, wi);           // its first barrier also publishes rm / rl
 #pragma unroll 1
     for (int n = BS_A_THREADS / 2; n >= 1; n >>= 1) {
@@ -193,14 +191,14 @@ __global__ __launch_bounds__(BS_B_THREADS) void bs_item_kernel(MopkBeamArgs a, i
     float ls[NC];
     int li[NC];
 #pragma unroll
-    for (int j = 0; j < NC; ++j) { ls[j] = -INFINITY; li[j] = BS_SENT; }
+    for (int j = 0; j < NC; ++j) { ls[j] = -INFINITY; li[j] = ROW_NONE; }
     const int per_row = nslice * NC;
     const size_t c0 = (size_t)b * K * per_row;
     for (int i = tid; i < K * per_row; i += BS_B_THREADS) {
         const int k = i / per_row;
         const float x = w.cs[c0 + i];
         const int v = w.ci[c0 + i];
-        if (v == BS_SENT) continue;
+        if (v == ROW_NONE) continue;
         const float s = (x == -INFINITY || sc[k] == -INFINITY) ? -INFINITY : sc[k] + (x - lse[k]);
         bs_insert(ls, li, s, k * V + v);
     }
@@ -213,7 +211,7 @@ __global__ __launch_bounds__(BS_B_THREADS) void bs_item_kernel(MopkBeamArgs a, i
         for (int c = 0; c < NC && nl < K; ++c) {
             const float s = ws[c];
             const int flat = wi[c];
-            if (flat == BS_SENT) break;                         // unreachable: K * V >= NC real candidates
+            if (flat == ROW_NONE) break;                        // unreachable: K * V >= NC real candidates
             const int k = flat / V, v = flat - k * V;
             if (v == a.eos && isfinite(s)) {
                 if (nf < K) {
@@ -282,7 +280,7 @@ int bs_check(const MopkBeamArgs *a) {
     if (!a) return MOPK_ERR_BAD_ARG;
     if (a->B <= 0 || a->K <= 0 || a->V < 2 || a->T <= 0) return MOPK_ERR_BAD_SHAPE;
     if (a->K > MOPK_BEAM_MAX_K) return MOPK_ERR_UNSUPPORTED;
-    if ((int64_t)a->K * a->V >= BS_SENT || (int64_t)a->B * a->K > 0x7fffffff) return MOPK_ERR_UNSUPPORTED;
+    if ((int64_t)a->K * a->V >= ROW_NONE || (int64_t)a->B * a->K > 0x7fffffff) return MOPK_ERR_UNSUPPORTED;
     if (a->prompt_len < 1 || a->prompt_len >= a->T) return MOPK_ERR_BAD_SHAPE;
     if (a->hist_ld < a->T || a->rows_ld < a->T) return MOPK_ERR_BAD_SHAPE;
     if (a->logits_dtype != MOPK_F32 && a->logits_dtype != MOPK_BF16) return MOPK_ERR_BAD_ARG;

@@ -16,22 +16,17 @@ namespace {
 constexpr int LG_THREADS = 256;
 constexpr int LG_WAVES = LG_THREADS / WAVE;
 constexpr int LG_PER = MOPK_LANGUAGE_MAX_N / LG_THREADS;        // entries per thread
-constexpr int LG_NONE = 0x7fffffff;                             // id of "no entry yet": every real id ranks before it
 static_assert(LG_PER * LG_THREADS == MOPK_LANGUAGE_MAX_N, "a thread's share covers the table");
-
-struct LgLds {
-    float wm[LG_WAVES], wl[LG_WAVES], ws[LG_WAVES];
-    int wi[LG_WAVES];
-};
 
 template <typename T>
 __global__ __launch_bounds__(LG_THREADS) void lg_row_kernel(MopkLanguageProbsArgs a) {
-    __shared__ LgLds s;
+    __shared__ RowLseLds<LG_WAVES> sl;
+    __shared__ RowBestLds<LG_WAVES> sb;
     const int r = blockIdx.x, V = a.V, n = a.n, tid = threadIdx.x;
     const T *x = (const T *)a.logits + (int64_t)r * a.logits_ld;
     float f[LG_PER];
     float m = -INFINITY, l = 0.f, bs = -INFINITY;
-    int bi = LG_NONE;
+    int bi = ROW_NONE;                                          // a token id here: every real id ranks before it
 #pragma unroll
     for (int k = 0; k < LG_PER; ++k) {
         const int i = tid + k * LG_THREADS;
@@ -43,26 +38,12 @@ __global__ __launch_bounds__(LG_THREADS) void lg_row_kernel(MopkLanguageProbsArg
             if (row_before(f[k], t, bs, bi)) { bs = f[k]; bi = t; }
         }
     }
-    // block-wide merge: shuffles inside a wave, then the wave results in wave order (every thread gets the result)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        row_lse_merge(m, l, __shfl_xor(m, o, 64), __shfl_xor(l, o, 64));
-        const float s2 = __shfl_xor(bs, o, 64);
-        const int i2 = __shfl_xor(bi, o, 64);
-        if (row_before(s2, i2, bs, bi)) { bs = s2; bi = i2; }
-    }
-    const int w = tid / WAVE;
-    if ((tid & 63) == 0) { s.wm[w] = m; s.wl[w] = l; s.ws[w] = bs; s.wi[w] = bi; }
+    row_wave_lse_best(m, l, bs, bi);
+    sl.put(m, l);
+    sb.put(bs, bi);
     __syncthreads();
-    m = s.wm[0];
-    l = s.wl[0];
-    bs = s.ws[0];
-    bi = s.wi[0];
-#pragma unroll
-    for (int i = 1; i < LG_WAVES; ++i) {
-        row_lse_merge(m, l, s.wm[i], s.wl[i]);
-        if (row_before(s.ws[i], s.wi[i], bs, bi)) { bs = s.ws[i]; bi = s.wi[i]; }
-    }
+    sl.get(m, l);
+    sb.get(bs, bi);
     const float lse = m + logf(l);
     float *p = a.probs + (int64_t)r * a.probs_ld;
 #pragma unroll
@@ -70,8 +51,8 @@ __global__ __launch_bounds__(LG_THREADS) void lg_row_kernel(MopkLanguageProbsArg
         const int i = tid + k * LG_THREADS;
         if (i < n) p[i] = expf(f[k] - lse);
     }
-    // bi == LG_NONE is only reachable with NaN logits: the first language stands in
-    if (tid == 0) a.tokens[r] = bi != LG_NONE ? bi : min(max(a.ids[0], 0), V - 1);
+    // bi == ROW_NONE is only reachable with NaN logits: the first language stands in
+    if (tid == 0) a.tokens[r] = bi != ROW_NONE ? bi : min(max(a.ids[0], 0), V - 1);
 }
 
 int lg_check(const MopkLanguageProbsArgs *a) {

@@ -19,10 +19,6 @@ constexpr int LR_THREADS = 1024;
 constexpr int LR_WAVES = LR_THREADS / WAVE;
 #define LR_UNROLL 16                                            // loads in flight per thread: each pass is bound by L2 latency
 
-template <typename T> __device__ __forceinline__ T lr_ninf();
-template <> __device__ __forceinline__ float lr_ninf<float>() { return -INFINITY; }
-template <> __device__ __forceinline__ unsigned short lr_ninf<unsigned short>() { return 0xFF80; }
-
 struct LrRow {                                                  // rules 1-3d of one row
     int tb;                                                     // V when rule 3 is off: every token is a text token
     int text_lo, ts_lo, ts_hi;
@@ -33,7 +29,8 @@ struct LrRow {                                                  // rules 1-3d of
 };
 
 struct LrLds {
-    float wm[LR_WAVES], wl[LR_WAVES], wt[LR_WAVES];
+    RowLseLds<LR_WAVES> lse;
+    float wt[LR_WAVES];
     int last_ts;
 };
 
@@ -88,20 +85,16 @@ __global__ __launch_bounds__(LR_THREADS) void lr_row_kernel(MopkLogitRulesArgs a
             }
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
+        for (int o = 32; o > 0; o >>= 1) {                      // row_wave_lse and wave_max in one tree (row_helpers.h says why)
             row_lse_merge(m, l, __shfl_xor(m, o, 64), __shfl_xor(l, o, 64));
             mt = fmaxf(mt, __shfl_xor(mt, o, 64));
         }
-        const int w = tid / WAVE;
-        if ((tid & 63) == 0) { s.wm[w] = m; s.wl[w] = l; s.wt[w] = mt; }
+        s.lse.put(m, l);
+        if ((tid & 63) == 0) s.wt[tid / WAVE] = mt;
         __syncthreads();
-        m = s.wm[0];
-        l = s.wl[0];
+        s.lse.get(m, l);
         mt = s.wt[0];
-        for (int i = 1; i < LR_WAVES; ++i) {
-            row_lse_merge(m, l, s.wm[i], s.wl[i]);
-            mt = fmaxf(mt, s.wt[i]);
-        }
+        for (int i = 1; i < LR_WAVES; ++i) mt = fmaxf(mt, s.wt[i]);
         const float L = m == -INFINITY ? -INFINITY : m + logf(l);
         if (L > mt) row.text_lo = row.tb;
     }
@@ -110,7 +103,7 @@ __global__ __launch_bounds__(LR_THREADS) void lr_row_kernel(MopkLogitRulesArgs a
 #pragma unroll LR_UNROLL
     for (int v = tid; v < V; v += LR_THREADS) {
         const T e = x[v];
-        y[v] = row.blocked(v, a.mask[v]) ? lr_ninf<T>() : e;
+        y[v] = row.blocked(v, a.mask[v]) ? row_ninf<T>() : e;
     }
 }
 

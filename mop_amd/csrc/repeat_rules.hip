@@ -19,21 +19,15 @@ constexpr int RR_THREADS = 1024;
 constexpr int RR_MAX_G = 4096;                                  // generated tokens held in LDS (16 KB)
 constexpr int RR_PER = RR_MAX_G / RR_THREADS;                   // history positions per thread
 
-template <typename T> __device__ __forceinline__ T rr_ninf();
-template <> __device__ __forceinline__ float rr_ninf<float>() { return -INFINITY; }
-template <> __device__ __forceinline__ unsigned short rr_ninf<unsigned short>() { return 0xFF80; }
-
 // y[0:V] = x[0:V], bit for bit
 template <typename T>
 __device__ __forceinline__ void rr_copy_row(const T *x, T *y, int V, int tid) {
-    constexpr int EPV = 16 / (int)sizeof(T);                    // elements per 16 bytes
-    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
-    if ((xa ^ ya) & 15) {                                       // the rows are aligned differently: elements
+    if (((uintptr_t)x ^ (uintptr_t)y) & 15) {                   // the rows are aligned differently: elements
         for (int v = tid; v < V; v += RR_THREADS) y[v] = x[v];
         return;
     }
-    const int head = min((int)(((16 - (xa & 15)) & 15) / sizeof(T)), V);
-    const int nvec = (V - head) / EPV, tail = head + nvec * EPV;
+    const RowSpan<T> sp(x, V);
+    const int head = sp.head, nvec = sp.nvec, tail = sp.tail0;
     if (tid < head) y[tid] = x[tid];
     const uint4 *xv = (const uint4 *)(x + head);
     uint4 *yv = (uint4 *)(y + head);
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(RR_THREADS) void rr_row_kernel(MopkRepeatRulesArgs 
             for (int k = s - 2; k >= 0 && same; --k) same = sg[i + k] == sg[c0 + k];
             if (same) {
                 const int v = sg[i + s - 1];
-                if ((unsigned)v < (unsigned)V && !a.exempt[v]) y[v] = rr_ninf<T>();
+                if ((unsigned)v < (unsigned)V && !a.exempt[v]) y[v] = row_ninf<T>();
             }
         }
     }

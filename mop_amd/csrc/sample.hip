@@ -44,42 +44,18 @@ __device__ __forceinline__ uint64_t sp_mass(float z, float mz) { return (uint64_
 
 struct SpLds {
     uint64_t hist[SP_BINS];
-    float wf[SP_WAVES], wg[SP_WAVES];
-    int wi[SP_WAVES];
+    union {                                                     // used one after the other: a barrier follows every get()
+        RowLseLds<SP_WAVES> lse;
+        RowBestLds<SP_WAVES> best;
+    };
     uint64_t wu[SP_WAVES];
     uint32_t wk[SP_WAVES], wk2[SP_WAVES];
     uint32_t sel, exact;
     uint64_t above;
 };
 
-// block-wide reductions: shuffles inside a wave, then the SP_WAVES wave results in wave order (every thread gets the result)
-__device__ __forceinline__ void sp_block_lse(float &m, float &l, SpLds &s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) row_lse_merge(m, l, __shfl_xor(m, o, 64), __shfl_xor(l, o, 64));
-    const int w = threadIdx.x / WAVE;
-    if ((threadIdx.x & 63) == 0) { s.wf[w] = m; s.wg[w] = l; }
-    __syncthreads();
-    m = s.wf[0];
-    l = s.wg[0];
-    for (int i = 1; i < SP_WAVES; ++i) row_lse_merge(m, l, s.wf[i], s.wg[i]);
-    __syncthreads();
-}
-__device__ __forceinline__ void sp_block_best(float &sc, int &v, SpLds &s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float s2 = __shfl_xor(sc, o, 64);
-        const int v2 = __shfl_xor(v, o, 64);
-        if (row_before(s2, v2, sc, v)) { sc = s2; v = v2; }
-    }
-    const int w = threadIdx.x / WAVE;
-    if ((threadIdx.x & 63) == 0) { s.wf[w] = sc; s.wi[w] = v; }
-    __syncthreads();
-    sc = s.wf[0];
-    v = s.wi[0];
-    for (int i = 1; i < SP_WAVES; ++i)
-        if (row_before(s.wf[i], s.wi[i], sc, v)) { sc = s.wf[i]; v = s.wi[i]; }
-    __syncthreads();
-}
+// block-wide reductions: shuffles inside a wave, then the SP_WAVES wave results in wave order (every thread gets the result);
+// row_helpers.h has the (max, sum-exp) and best (score, index) ones
 __device__ __forceinline__ uint64_t sp_block_sum(uint64_t x, SpLds &s) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
@@ -176,21 +152,25 @@ __global__ __launch_bounds__(SP_THREADS) void sp_row_kernel(MopkSampleArgs a, co
 
     // pass 1: unscaled (max, sum-exp); greedy: the argmax; else the key range
     float m0 = -INFINITY, l0 = 0.f, best = -INFINITY;
-    int bv = 0x7fffffff;
+    int bv = ROW_NONE;
     uint32_t thr = 0xffffffffu, kmax = 0;                       // kept: key(z) >= thr (all of [0, V) before any filter)
 #pragma unroll SP_UNROLL
     for (int v = tid; v < V; v += SP_THREADS) {
         const float f = row.x_at(v);
         row_lse_add(m0, l0, f);
         if (row.greedy) {
-            if (f > best || bv == 0x7fffffff) { best = f; bv = v; }       // v rises: the first maximum of this thread
+            if (f > best || bv == ROW_NONE) { best = f; bv = v; }         // v rises: the first maximum of this thread
         } else {
             const uint32_t k = sp_key(f * row.it);
             thr = min(thr, k);
             kmax = max(kmax, k);
         }
     }
-    sp_block_lse(m0, l0, s);
+    row_wave_lse(m0, l0);
+    s.lse.put(m0, l0);
+    __syncthreads();
+    s.lse.get(m0, l0);
+    __syncthreads();
     if (!row.greedy) {
         sp_block_minmax(thr, kmax, s);
         if (a.top_k > 0 && a.top_k < V) thr = sp_select<false>(row, thr, kmax, (uint64_t)a.top_k, 0.f, s);
@@ -219,7 +199,11 @@ __global__ __launch_bounds__(SP_THREADS) void sp_row_kernel(MopkSampleArgs a, co
             }
         }
     }
-    sp_block_best(best, bv, s);
+    row_wave_best(best, bv);
+    s.best.put(best, bv);
+    __syncthreads();
+    s.best.get(best, bv);
+    __syncthreads();
     if (bv >= V) bv = 0;                                        // only reachable with NaN logits: keep the read inside the row
     if (tid == 0) {
         a.tokens[r] = bv;

@@ -16,24 +16,17 @@ namespace {
 
 constexpr int TL_THREADS = 1024;
 constexpr int TL_WAVES = TL_THREADS / WAVE;
-constexpr int TL_NONE = 0x7fffffff;                             // index of "no element yet": every real index ranks before it
-
-struct TlLds {
-    float wm[TL_WAVES], wl[TL_WAVES], ws[TL_WAVES];
-    int wi[TL_WAVES];
-};
 
 // this thread's share of row x[0, V): (m, l) and, with BEST, the best (bs, bi)
 template <typename T, bool BEST>
 __device__ __forceinline__ void tl_scan(const T *x, int V, float &m, float &l, float &bs, int &bi) {
-    constexpr int ES = (int)sizeof(T), EPV = 16 / ES;
+    constexpr int EPV = RowSpan<T>::EPV;
     const int tid = threadIdx.x;
-    int head = (int)(((16 - ((uintptr_t)x & 15)) & 15) / ES);   // elements before the row's first 16-byte boundary
-    head = head < V ? head : V;
-    const int nvec = (V - head) / EPV, tail0 = head + nvec * EPV;
+    const RowSpan<T> sp(x, V);
+    const int head = sp.head, tail0 = sp.tail0;                 // head + (V - tail0) < 2 * EPV scalar elements
     const uint4 *xv = (const uint4 *)(x + head);
 #pragma unroll 4
-    for (int u = tid; u < nvec; u += TL_THREADS) {
+    for (int u = tid; u < sp.nvec; u += TL_THREADS) {
         float f[EPV];
         row_unpack(xv[u], f, T());
 #pragma unroll
@@ -42,8 +35,7 @@ __device__ __forceinline__ void tl_scan(const T *x, int V, float &m, float &l, f
             if (BEST && row_before(f[e], head + u * EPV + e, bs, bi)) { bs = f[e]; bi = head + u * EPV + e; }
         }
     }
-    const int nt = V - tail0;                                   // head + nt < 2 * EPV scalar elements
-    if (tid < head + nt) {
+    if (tid < head + (V - tail0)) {
         const int e = tid < head ? tid : tail0 + (tid - head);
         const float f = ld_as_f32<T>(x + e);
         row_lse_add(m, l, f);
@@ -51,40 +43,18 @@ __device__ __forceinline__ void tl_scan(const T *x, int V, float &m, float &l, f
     }
 }
 
-// block-wide merge: shuffles inside a wave, then the wave results in wave order (every thread gets the result)
-template <bool BEST>
-__device__ __forceinline__ void tl_block_merge(float &m, float &l, float &bs, int &bi, TlLds &s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        row_lse_merge(m, l, __shfl_xor(m, o, 64), __shfl_xor(l, o, 64));
-        if (BEST) {
-            const float s2 = __shfl_xor(bs, o, 64);
-            const int i2 = __shfl_xor(bi, o, 64);
-            if (row_before(s2, i2, bs, bi)) { bs = s2; bi = i2; }
-        }
-    }
-    const int w = threadIdx.x / WAVE;
-    if ((threadIdx.x & 63) == 0) { s.wm[w] = m; s.wl[w] = l; s.ws[w] = bs; s.wi[w] = bi; }
-    __syncthreads();
-    m = s.wm[0];
-    l = s.wl[0];
-    bs = s.ws[0];
-    bi = s.wi[0];
-    for (int i = 1; i < TL_WAVES; ++i) {
-        row_lse_merge(m, l, s.wm[i], s.wl[i]);
-        if (BEST && row_before(s.ws[i], s.wi[i], bs, bi)) { bs = s.ws[i]; bi = s.wi[i]; }
-    }
-}
-
 template <typename T>
 __global__ __launch_bounds__(TL_THREADS) void tl_row_kernel(MopkTokenLogprobArgs a) {
-    __shared__ TlLds s;
+    __shared__ RowLseLds<TL_WAVES> s;
     const int r = blockIdx.x, V = a.V;
     const T *x = (const T *)a.logits + (int64_t)r * a.logits_ld;
     float m = -INFINITY, l = 0.f, bs = -INFINITY;
-    int bi = TL_NONE;
+    int bi = ROW_NONE;
     tl_scan<T, false>(x, V, m, l, bs, bi);
-    tl_block_merge<false>(m, l, bs, bi, s);
+    row_wave_lse(m, l);
+    s.put(m, l);
+    __syncthreads();
+    s.get(m, l);
     if (threadIdx.x == 0) {
         const int t = min(max(a.tokens ? a.tokens[r] : a.token, 0), V - 1);        // no read leaves the row
         a.out[r] = ld_as_f32<T>(x + t) - (m + logf(l));
@@ -93,7 +63,8 @@ __global__ __launch_bounds__(TL_THREADS) void tl_row_kernel(MopkTokenLogprobArgs
 
 template <typename T>
 __global__ __launch_bounds__(TL_THREADS) void gp_row_kernel(MopkGreedyPickArgs a) {
-    __shared__ TlLds s;
+    __shared__ RowLseLds<TL_WAVES> sl;
+    __shared__ RowBestLds<TL_WAVES> sb;
     const int r = blockIdx.x, V = a.V;
     const int p = *a.pos;
     const bool hist_on = a.hist != nullptr && p >= 0 && p < a.hist_cap;
@@ -106,9 +77,14 @@ __global__ __launch_bounds__(TL_THREADS) void gp_row_kernel(MopkGreedyPickArgs a
     }
     const T *x = (const T *)a.logits + (int64_t)r * a.logits_ld;
     float m = -INFINITY, l = 0.f, bs = -INFINITY;
-    int bi = TL_NONE;
+    int bi = ROW_NONE;
     tl_scan<T, true>(x, V, m, l, bs, bi);
-    tl_block_merge<true>(m, l, bs, bi, s);
+    row_wave_lse_best(m, l, bs, bi);
+    sl.put(m, l);
+    sb.put(bs, bi);
+    __syncthreads();
+    sl.get(m, l);
+    sb.get(bs, bi);
     if (threadIdx.x == 0) {
         const int t = bi < V ? bi : 0;                          // only reachable with NaN logits: keep the read inside the row
         a.sum_logprobs[r] += ld_as_f32<T>(x + t) - (m + logf(l));

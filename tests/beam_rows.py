@@ -78,6 +78,9 @@ class Partition:
 
 @functools.lru_cache(maxsize=None)
 def partition(V, dtype, base_mod16, B, K):
+    """who reads which element of a row that starts base_mod16 bytes behind a 16-byte boundary: head / nvec / tail0 restate
+    RowSpan of csrc/row_helpers.h (the one split every row kernel uses), the rest is bs_rows_kernel's deal of the vectors to slices
+    and threads"""
     es, E = 16 // epv(dtype), epv(dtype)
     head = min(((16 - base_mod16) & 15) // es, V)
     nvec = (V - head) // E

@@ -1,9 +1,9 @@
 """GPU checks of the decoding statistics and of transcribe's temperature fallback and no-speech skip: the mopk_token_logprob and
 mopk_greedy_pick kernels against the torch path on the same device tensors and against the float64 restatement of
 tests/test_whisper_fallback_cpu.py (fp32 and bf16; filtered rows, done rows, eos picks, exact ties; padded row strides, hist[::K],
-one row with degenerate strides; untouched padding; bitwise repeatability), generate with statistics against generate without,
-eagerly here and with graph=True in a process of its own, transcribe's fallback and skip cases against the naive loop on the
-device, and no host sync."""
+one row with degenerate strides; rows shorter than a 16-byte vector at every offset; untouched padding; bitwise repeatability),
+generate with statistics against generate without, eagerly here and with graph=True in a process of its own, transcribe's fallback
+and skip cases against the naive loop on the device, and no host sync."""
 import math
 import os
 import subprocess
@@ -74,6 +74,28 @@ def test_kernels_match_the_torch_path_and_the_restatement(V_, R, dtype):
             assert float(got[0]) == float("-inf")
         one = int(toks[-1])
         assert torch.equal(_logprob_both(ops, x, one, what), ops.token_logprob(x, torch.full((R,), one, dtype=torch.int32, device="cuda")))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("V_", range(2, 10))
+def test_rows_shorter_than_a_vector_at_every_offset(V_, dtype):
+    """rows with no whole 16-byte vector (csrc/row_helpers.h's RowSpan with nvec == 0, and head clamped to V where the row ends
+    before its first boundary): contiguous, and entered 1 ... EPV - 1 elements behind a 16-byte boundary"""
+    from mop_amd import ops
+    R, es = 3, torch.empty(0, dtype=dtype).element_size()
+    flat = torch.zeros(R * V_ + 16 // es, device="cuda", dtype=dtype)
+    for name, x, eos, done in stat_cases(V_, R, dtype, "cuda"):
+        kind = name if name != "filtered" or bool(torch.isinf(x[0]).any()) else "all kept"    # four entries can be a whole short row
+        toks = _tokens_for(x, kind)
+        for k in range(16 // es):
+            view = x if k == 0 else flat[k:k + R * V_].view(R, V_).copy_(x)
+            assert view.data_ptr() % 16 == k * es
+            what = (V_, dtype, name, k)
+            _pick_both(ops, view, eos, done, what)
+            got = _logprob_both(ops, view, toks, what)
+            if kind == "filtered":
+                assert float(got[0]) == float("-inf"), what
+            _logprob_both(ops, view, int(toks[-1]), what)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])

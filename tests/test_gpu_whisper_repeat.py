@@ -1,10 +1,10 @@
 """-m gpu: the repetition rules on the HIP kernel (mopk_repeat_rules).  ops.repeat_rules against ops.repeat_rules_torch on the same
 device tensors and against the restatement of tests/test_whisper_repeat_cpu.py over its sweep, bit for bit on every row, with a
 separate result and in place; long histories (n = 440, n past the kernel's 1024 threads, and the first history that goes to the
-torch path); padded row strides, hist[::K], the device-read position, a single row with degenerate strides; bitwise
-reproducibility; guard bands; generate under the rules against a naive re-decode loop (uniform and ragged prompts); graph replay
-of all three decoders; no repeated bigram in their outputs, clips of different lengths included; the unchanged default; no host
-sync."""
+torch path); rows shorter than a 16-byte vector at every offset; padded row strides, hist[::K], the device-read position, a
+single row with degenerate strides; bitwise reproducibility; guard bands; generate under the rules against a naive re-decode loop
+(uniform and ragged prompts); graph replay of all three decoders; no repeated bigram in their outputs, clips of different lengths
+included; the unchanged default; no host sync."""
 import os
 import subprocess
 import sys
@@ -42,6 +42,36 @@ def test_kernel_matches_the_torch_path_and_the_restatement(V, R, dtype):
     seen = sweep(_both_paths, V, R, dtype, "cuda")
     print(f"V={V} R={R} {dtype}: rows banned only / penalised only / both / neither: {seen}")
     assert all(seen)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("V", range(2, 10))
+def test_rows_shorter_than_a_vector_at_every_offset(V, dtype):
+    """the copy route on rows with no whole 16-byte vector (csrc/row_helpers.h's RowSpan with nvec == 0, and head clamped to V
+    where the row ends before its first boundary): contiguous, and entered 1 ... EPV - 1 elements behind a 16-byte boundary; with
+    the result allocated by the op (rows aligned differently once the input is off a boundary) and with an out buffer entered at
+    the input's offset (rows aligned alike).  build_case needs V >= 31, so the rows are built here"""
+    from mop_amd import ops
+    R, es = 3, torch.empty(0, dtype=dtype).element_size()
+    rules = ops.RepeatRules(V, 1.3, 2)
+    g = torch.Generator().manual_seed(V)
+    x = (torch.randn(R, V, generator=g) * 3).to(dtype)
+    hist = torch.randint(0, V, (R, T0 + 14), generator=g).to(torch.int32)
+    pos = torch.tensor([T0 + 12], dtype=torch.int32)
+    want, kinds = expected(x, hist, pos, rules)
+    assert all(pen for pen, _ in kinds)
+    hist, pos = hist.cuda(), pos.cuda()
+    src = torch.zeros(R * V + 16 // es, device="cuda", dtype=dtype)
+    for k in range(16 // es):
+        dst = torch.zeros_like(src)
+        view, out = (buf[k:k + R * V].view(R, V) for buf in (src, dst))
+        view.copy_(x)
+        assert view.data_ptr() % 16 == k * es and (view.data_ptr() ^ out.data_ptr()) % 16 == 0
+        assert_bits_equal(_both_paths(view, hist, pos, T0, rules), want, (V, dtype, k))
+        got = _both_paths(view, hist, pos, T0, rules, out=out)
+        assert got.data_ptr() == out.data_ptr()
+        assert_bits_equal(out, want, (V, dtype, k, "out"))
+        assert bool((dst[:k] == 0).all()) and bool((dst[k + R * V:] == 0).all())                  # nothing written beside the rows
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
