@@ -1212,6 +1212,56 @@ size_t mopk_gated_residual_workspace_bytes(const MopkGatedResidualArgs *a);   /*
 int mopk_gated_residual_fwd(const MopkGatedResidualArgs *a, void *stream);
 int mopk_gated_residual_bwd(const MopkGatedResidualArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * Cross-entropy of rows of logits against int64 class targets (ops.cross_entropy, ops.linear_cross_entropy, the language models'
+ * loss()).  (Added under version 118: new exports only; callers detect them with mopk_cross_entropy_supported.)
+ *
+ * A call holds R rows of a problem of n_rows rows: launch row r (0 <= r < R) is problem row row0 + r.  logits / dlogits are indexed
+ * by the launch row (row r at logits + r * logits_ld elements, F32 or BF16, element-aligned, unit inner stride); targets, lse,
+ * row_loss and grad by the problem row.  A whole problem in one call has row0 = 0, n_rows = R; a caller that holds only a chunk of
+ * the logits at a time (ops.linear_cross_entropy) walks row0 and keeps the per-row arrays whole.
+ *
+ * A row is IGNORED when its target t is ignore_index or lies outside [0, V) (torch asserts on the device for the latter): its loss
+ * is 0, its gradient is 0, it is not counted.  No read leaves a row for any target value.
+ *
+ * _fwd: lse[row] = m + logf(sum expf(x - m)), m = max x, in fp32 (-inf entries add nothing; a row without a finite entry is
+ *   outside the contract);  row_loss[row] = lse - x[t], 0 for an ignored row.  With `out`, a second launch (one workgroup) follows:
+ *   out[0] = sum of row_loss over the counted rows of [0, n_rows), accumulated in double in a fixed order;  out[1] = n_valid, their
+ *   number;  out[2] = sum / n_valid (NaN when no row counts);  out[3] = 1 / n_valid.  The sum reads row_loss of EVERY problem row:
+ *   the call with `out` is the last of a chunked problem.
+ * _bwd: dlogits[r, j] = g (expf(x_j - lse[row]) - [j == t]) in the logits' dtype, g = grad[row * grad_stride] (grad_stride 0: one
+ *   upstream scalar), times *scale when scale is given (out + 3 of the forward for a mean).  An ignored row is written as exact
+ *   zeros; grad and scale are not read for it.  Columns [V, ld) are not touched.  dlogits may be logits itself (same pointer and
+ *   stride); otherwise the two must not overlap, and each row of dlogits must sit as its row of logits does relative to 16 bytes
+ *   (pointers equal mod 16, strides equal mod 16 bytes; MOPK_ERR_UNSUPPORTED otherwise).
+ *
+ * One workgroup of 1024 threads per row; 16-byte loads and stores with scalar elements before a row's first 16-byte boundary and
+ * behind its last whole vector; the (max, sum-exp) pairs merged by wave shuffles and then in wave order.  Static LDS only, no float
+ * atomics, no workspace, no host synchronisation: bitwise reproducible, and a first call may be inside a stream capture. */
+typedef struct MopkCrossEntropyArgs {
+    int32_t R;                           /* rows of this call */
+    int32_t V;                           /* classes, >= 2 */
+    int32_t dtype;                       /* MopkDtype of logits and dlogits: F32 or BF16 */
+    int32_t row0;                        /* problem row of launch row 0, >= 0 */
+    int32_t n_rows;                      /* rows of the problem, >= row0 + R */
+    int32_t reserved;                    /* 0 */
+    int64_t ignore_index;
+    const void *logits;
+    int64_t logits_ld;                   /* element stride between rows, >= V */
+    const int64_t *targets;              /* device (n_rows) int64 */
+    float *lse;                          /* (n_rows): fwd out, bwd in */
+    float *row_loss;                     /* (n_rows): fwd out */
+    float *out;                          /* fwd: (4) out, or NULL: no reduce launch */
+    void *dlogits;                       /* bwd out */
+    int64_t dlogits_ld;                  /* element stride between its rows, >= V */
+    const float *grad;                   /* bwd: upstream gradient, one float or one per problem row */
+    int64_t grad_stride;                 /* element stride between its rows, >= 0; 0: one scalar for all */
+    const float *scale;                  /* bwd: one float that multiplies grad, or NULL */
+} MopkCrossEntropyArgs;
+int mopk_cross_entropy_supported(const MopkCrossEntropyArgs *a);      /* 1 if the kernels take this call (V, dtype, strides, alignment) */
+int mopk_cross_entropy_fwd(const MopkCrossEntropyArgs *a, void *stream);
+int mopk_cross_entropy_bwd(const MopkCrossEntropyArgs *a, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

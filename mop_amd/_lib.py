@@ -178,6 +178,15 @@ class GatedResidualArgs(C.Structure):
     ]
 
 
+class CrossEntropyArgs(C.Structure):
+    """MopkCrossEntropyArgs: cross-entropy of R rows of logits (rows row0 .. of a problem of n_rows) against int64 targets."""
+    _fields_ = [
+        ("R", C.c_int32), ("V", C.c_int32), ("dtype", C.c_int32), ("row0", C.c_int32), ("n_rows", C.c_int32), ("reserved", C.c_int32),
+        ("ignore_index", C.c_int64), ("logits", _fp), ("logits_ld", C.c_int64), ("targets", _fp), ("lse", _fp), ("row_loss", _fp),
+        ("out", _fp), ("dlogits", _fp), ("dlogits_ld", C.c_int64), ("grad", _fp), ("grad_stride", C.c_int64), ("scale", _fp),
+    ]
+
+
 MOE_MAX_EXPERTS = 64
 
 
@@ -493,6 +502,9 @@ SYMBOLS = {
     "mopk_gated_residual_workspace_bytes": (C.c_size_t, [C.POINTER(GatedResidualArgs)]),
     "mopk_gated_residual_fwd": (C.c_int, [C.POINTER(GatedResidualArgs), C.c_void_p]),
     "mopk_gated_residual_bwd": (C.c_int, [C.POINTER(GatedResidualArgs), C.c_void_p]),
+    "mopk_cross_entropy_supported": (C.c_int, [C.POINTER(CrossEntropyArgs)]),
+    "mopk_cross_entropy_fwd": (C.c_int, [C.POINTER(CrossEntropyArgs), C.c_void_p]),
+    "mopk_cross_entropy_bwd": (C.c_int, [C.POINTER(CrossEntropyArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -137,6 +137,16 @@ class _LMBase(nn.Module):
             loss = F.cross_entropy(logits.view(-1, logits.size(-1)), targets.view(-1))
         return logits, loss
 
+    def loss(self, idx: torch.Tensor, targets: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, *,
+             chunk_rows: Optional[int] = None, ignore_index: int = -100) -> torch.Tensor:
+        """the mean cross-entropy that forward(idx, attention_mask, targets)[1] returns, without the (B T, V) logits: the stack as
+        in forward, then ops.linear_cross_entropy on the head's input, chunk_rows rows of logits at a time"""
+        x = self._embed(idx)
+        for block in self.blocks:
+            x = block(x, attention_mask=attention_mask)
+        return ops.linear_cross_entropy(self.ln_f(x), self.lm_head.weight, targets, self.lm_head.bias,
+                                        ignore_index=ignore_index, chunk_rows=chunk_rows)
+
     def _init_weights(self, module):
         _init_gpt_weights(module)
 

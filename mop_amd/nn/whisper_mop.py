@@ -509,6 +509,10 @@ class WhisperMoP(nn.Module):
 
     def decode(self, enc_out: torch.Tensor, dec_input_ids: torch.Tensor) -> torch.Tensor:
         """enc_out (B, T_audio, D) or an EncodedAudio, dec_input_ids (B, T_text) -> logits (B, T_text, vocab)."""
+        return self.lm_head(self._decode_hidden(enc_out, dec_input_ids))
+
+    def _decode_hidden(self, enc_out, dec_input_ids: torch.Tensor) -> torch.Tensor:
+        """the decoder stack up to the head's input (B, T_text, D)"""
         B, T_t = dec_input_ids.shape
         x = self.wte(dec_input_ids)
         if self.text_pos is not None:
@@ -516,7 +520,20 @@ class WhisperMoP(nn.Module):
         x = self.drop(x)
         for blk in self.decoder:
             x = blk(x, enc_out)
-        return self.lm_head(self.dec_ln_f(x))
+        return self.dec_ln_f(x)
+
+    def loss(self, mel: torch.Tensor, dec_input_ids: torch.Tensor, targets: torch.Tensor, *, chunk_rows: Optional[int] = None,
+             ignore_index: int = -100):
+        """(loss, gates) as forward(mel, dec_input_ids, targets)[1:] returns them, without the (B T_text, vocab) logits: the encoder
+        and decoder as in forward, then ops.linear_cross_entropy on the head's input, chunk_rows rows of logits at a time"""
+        alens = self._audio_check(mel, "loss")
+        if alens is not None and dec_input_ids.shape[0] != len(alens):
+            raise ValueError(f"loss: {dec_input_ids.shape[0]} rows of dec_input_ids for a batch of {len(alens)} mel inputs")
+        enc_out, gates = self.encode(mel)
+        x = self._decode_hidden(enc_out, dec_input_ids)
+        loss = ops.linear_cross_entropy(x, self.lm_head.weight, targets, self.lm_head.bias, ignore_index=ignore_index,
+                                        chunk_rows=chunk_rows)
+        return loss, gates
 
     def forward(self, mel: torch.Tensor, dec_input_ids: torch.Tensor, targets: Optional[torch.Tensor] = None):
         """mel: (B, T_audio, n_mels), or a list of B (T_b, n_mels) clips of different lengths (see encode): every item's logits

@@ -4715,4 +4715,178 @@ def resample(audio: torch.Tensor, orig_rate: int, new_rate: int, lens: Optional[
         return out, out_lens
 
 
+# ---- cross-entropy of logits, and of a linear head without its (M, V) logits (mopk_cross_entropy_*; the language models' loss()) ----
+# the two autograd Functions of this family are in mop_amd/cross_entropy_fn.py (imported at the end of this file)
+CE_REDUCTIONS = ("mean", "sum", "none")
+# rows of logits that linear_cross_entropy holds at a time by default: of 512 / 1024 / 2048 / 4096 / M the fastest setting whose peak
+# memory stayed under a quarter of the unchunked torch head + loss in bf16 at both measured shapes, M = 8192, V = 50304 and
+# M = 3584, V = 51865 (tools/bench_cross_entropy.py, profiles/cross_entropy_bench.jsonl)
+LINEAR_CE_CHUNK_ROWS = 2048
+
+
+def _ce_check(logits, targets, ignore_index, reduction, what: str) -> None:
+    """validate a cross_entropy call before any device work"""
+    _stat_logits_check(logits, what)
+    R = logits.shape[0]
+    if not isinstance(targets, torch.Tensor) or tuple(targets.shape) != (R,) or targets.dtype != torch.long:
+        raise ValueError(f"{what}: targets must be an int64 ({R},) tensor, got "
+                         f"{(tuple(targets.shape), targets.dtype) if isinstance(targets, torch.Tensor) else type(targets).__name__}")
+    if targets.device != logits.device:
+        raise ValueError(f"{what}: targets are on {targets.device}, the logits on {logits.device}")
+    if not _is_index(ignore_index):
+        raise ValueError(f"{what}: ignore_index must be an int, got {ignore_index!r}")
+    if reduction not in CE_REDUCTIONS:
+        raise ValueError(f"{what}: reduction must be one of {CE_REDUCTIONS}, got {reduction!r}")
+
+
+def _ce_counted(targets: torch.Tensor, V: int, ignore_index: int) -> torch.Tensor:
+    """the rows that count: a target that is neither ignore_index nor outside [0, V)"""
+    return (targets != ignore_index) & (targets >= 0) & (targets < V)
+
+
+def cross_entropy_torch(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100, reduction: str = "mean") -> torch.Tensor:
+    """the restatement of `cross_entropy` in torch ops (no host sync): F.cross_entropy(logits.float(), targets) with every target
+    outside [0, V) treated as ignored, as the kernel treats it (torch alone asserts on the device)"""
+    _ce_check(logits, targets, ignore_index, reduction, "cross_entropy_torch")
+    t = torch.where(_ce_counted(targets, logits.shape[1], ignore_index), targets, torch.full_like(targets, ignore_index))
+    return F.cross_entropy(logits.float(), t, ignore_index=ignore_index, reduction=reduction)
+
+
+def _ce_args(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int, row0: int = 0):
+    """the args struct, without outputs, of logits that hold rows [row0, row0 + R) of the problem `targets` spans"""
+    a = L.CrossEntropyArgs()
+    a.R, a.V = logits.shape
+    a.dtype = L.MOPK_BF16 if logits.dtype == torch.bfloat16 else L.MOPK_F32
+    a.row0, a.n_rows = row0, targets.shape[0]
+    a.ignore_index = max(-2 ** 63, min(2 ** 63 - 1, ignore_index))
+    a.logits, a.logits_ld = logits.data_ptr(), a.V if a.R == 1 else logits.stride(0)   # a single row: its stride is never used
+    a.targets = targets.data_ptr()
+    return a
+
+
+def _ce_accept(logits, targets, ignore_index):
+    """the args struct of a call that mopk_cross_entropy_* take, None of one they refuse"""
+    if not _stat_logits_ok(logits) or not (targets.is_cuda and targets.is_contiguous()) or logits.shape[0] >= 2 ** 31:
+        return None
+    a = _ce_args(logits, targets, ignore_index)
+    return a if L.lib().mopk_cross_entropy_supported(C.byref(a)) else None
+
+
+def _ce_grad_like(logits: torch.Tensor) -> torch.Tensor:
+    """an empty (R, V) tensor laid out as the backward kernel needs it: every row sits as its row of `logits` does relative to a
+    16-byte boundary (the same row stride, or the smallest one >= V equal to it modulo a vector where the logits are a narrow
+    slice of a wide buffer).  Contiguous logits on a boundary get a contiguous tensor."""
+    R, V = logits.shape
+    epv = 16 // logits.element_size()
+    ld = V if R == 1 else logits.stride(0)
+    if ld - V >= epv:
+        ld = V + (ld - V) % epv
+    phase = (logits.data_ptr() % 16) // logits.element_size()
+    buf = torch.empty(phase + (R - 1) * ld + V, dtype=logits.dtype, device=logits.device)
+    return buf.as_strided((R, V), (ld, 1), buf.storage_offset() + phase)
+
+
+def cross_entropy_supported(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100, reduction: str = "mean") -> bool:
+    """True if mopk_cross_entropy_* take this call: CUDA fp32 / bf16 logits with unit inner stride and a row stride >= V (one row:
+    any), CUDA int64 targets (the library's own query decides the rest).  Raises ValueError on bad arguments."""
+    _ce_check(logits, targets, ignore_index, reduction, "cross_entropy_supported")
+    return _ce_accept(logits, targets.contiguous(), ignore_index) is not None
+
+
+def cross_entropy(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100, reduction: str = "mean",
+                  inplace_backward: bool = False) -> torch.Tensor:
+    """cross-entropy of (R, V) logits against int64 (R,) targets -> fp32: a scalar for "mean" / "sum", (R,) for "none".
+
+    Per row: lse - logits[r, t], lse = logsumexp of the row in fp32 (-inf entries add nothing).  A row whose target is ignore_index
+    or lies outside [0, V) is ignored: loss 0, gradient exactly 0, not counted by "mean" (torch asserts on the device for a target
+    outside the classes; here it is an ignored row).  "mean" over no counted row is NaN, as in torch.
+    logits: fp32 or bf16, unit inner stride, any row stride >= V, rows starting at any element (`logits[:, 1:]`, a padded buffer).
+    Differentiable in the logits, once.  The gradient g (softmax - onehot) comes in the logits' dtype, as a new tensor whose rows
+    are laid out like the logits'; with inplace_backward=True it is written over the logits themselves: the caller promises that
+    nothing reads them after this call (a second backward through the same graph then raises).
+    Runs the HIP kernels (mopk_cross_entropy_fwd: a row kernel and, for "mean" / "sum", a one-workgroup reduce; _bwd: one launch)
+    when cross_entropy_supported() accepts the call, else cross_entropy_torch() (CPU tensors, fp16, other strides);
+    LAST_PATH["cross_entropy_fwd"] / ["cross_entropy_bwd"] record which.  No host sync; bitwise reproducible; a row comes out bit
+    for bit as it would alone."""
+    _ce_check(logits, targets, ignore_index, reduction, "cross_entropy")
+    targets = targets.contiguous()
+    if _ce_accept(logits, targets, ignore_index) is None:
+        LAST_PATH["cross_entropy_fwd"] = LAST_PATH["cross_entropy_bwd"] = L.PATH_GENERIC
+        return cross_entropy_torch(logits, targets, ignore_index, reduction)
+    return _cross_entropy_fn._CrossEntropyFn.apply(logits, targets, ignore_index, reduction, bool(inplace_backward))
+
+
+def _lce_check(x, weight, targets, bias, ignore_index, reduction, chunk_rows, what: str):
+    """validate a linear_cross_entropy call -> (M, D, V)"""
+    if not isinstance(x, torch.Tensor) or x.dim() < 2 or not x.dtype.is_floating_point or x.numel() == 0:
+        raise ValueError(f"{what}: x must be a non-empty floating (..., D) tensor")
+    D = x.shape[-1]
+    M = x.numel() // D
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 2 or weight.shape[1] != D or weight.shape[0] < 2:
+        raise ValueError(f"{what}: weight must be a (V >= 2, D = {D}) tensor, got {tuple(getattr(weight, 'shape', ()))}")
+    V = weight.shape[0]
+    if bias is not None and tuple(bias.shape) != (V,):
+        raise ValueError(f"{what}: bias must be a ({V},) tensor, got {tuple(bias.shape)}")
+    if not isinstance(targets, torch.Tensor) or targets.numel() != M or targets.dtype != torch.long:
+        raise ValueError(f"{what}: targets must be an int64 tensor of {M} elements, one per row of x")
+    if any(t is not None and t.device != x.device for t in (weight, bias, targets)):
+        raise ValueError(f"{what}: x, weight, bias and targets must be on one device")
+    if not _is_index(ignore_index):
+        raise ValueError(f"{what}: ignore_index must be an int, got {ignore_index!r}")
+    if reduction not in CE_REDUCTIONS:
+        raise ValueError(f"{what}: reduction must be one of {CE_REDUCTIONS}, got {reduction!r}")
+    if chunk_rows is not None and (not _is_index(chunk_rows) or chunk_rows < 1):
+        raise ValueError(f"{what}: chunk_rows must be a positive int or None, got {chunk_rows!r}")
+    return M, D, V
+
+
+def _lce_dtype(x: torch.Tensor, weight: torch.Tensor) -> Optional[torch.dtype]:
+    """the dtype F.linear(x, weight) computes and returns in: the autocast dtype under autocast, else the operands' common one
+    (None: they differ, and F.linear itself raises)"""
+    if x.is_cuda and torch.is_autocast_enabled("cuda"):
+        return torch.get_autocast_dtype("cuda")
+    return x.dtype if x.dtype == weight.dtype else None
+
+
+def linear_cross_entropy_torch(x, weight, targets, bias=None, ignore_index=-100, reduction="mean", chunk_rows=None) -> torch.Tensor:
+    """the restatement of `linear_cross_entropy` in torch ops and torch's autograd: F.linear and cross_entropy_torch's row losses
+    chunk by chunk, summed once over all rows.  One chunk is F.cross_entropy(F.linear(x, weight, bias).float(), ...) itself.
+    Autograd keeps every chunk's logits: this path saves no memory."""
+    M, D, V = _lce_check(x, weight, targets, bias, ignore_index, reduction, chunk_rows, "linear_cross_entropy_torch")
+    x2, t = x.reshape(M, D), targets.reshape(M)
+    c = min(M, chunk_rows or LINEAR_CE_CHUNK_ROWS)
+    if c >= M:
+        return cross_entropy_torch(F.linear(x2, weight, bias), t, ignore_index, reduction)
+    rows = torch.cat([cross_entropy_torch(F.linear(x2[i:i + c], weight, bias), t[i:i + c], ignore_index, "none") for i in range(0, M, c)])
+    if reduction == "none":
+        return rows
+    return rows.sum() if reduction == "sum" else rows.sum() / _ce_counted(t, V, ignore_index).sum()
+
+
+def linear_cross_entropy(x: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                         ignore_index: int = -100, reduction: str = "mean", chunk_rows: Optional[int] = None) -> torch.Tensor:
+    """cross_entropy(F.linear(x, weight, bias), targets) -> fp32, holding at most chunk_rows x V logits at a time.
+
+    x: (..., D), weight: (V, D), bias: (V,) or None, targets: int64, one per row of x; the M rows of x are taken chunk_rows at a
+    time (None: LINEAR_CE_CHUNK_ROWS).  Per chunk: one GEMM for the logits (torch; in the autocast dtype under autocast, as F.linear
+    would), mopk_cross_entropy_fwd on them and, when x, weight or bias requires grad, mopk_cross_entropy_bwd over the same storage
+    (upstream 1, times 1 / n_valid for "mean"), then dx_c = g_c @ W and dW += g_c^T @ x_c, db += sum g_c.  dW and db are accumulated
+    in fp32 across the chunks and rounded once to the parameter's dtype.  The loss is the fixed-order sum over all M row losses: it
+    depends on the chunking only through what the GEMM itself does.  backward returns the stored gradients times the upstream
+    scalar as new tensors (retain_graph works).  Ignored rows as in `cross_entropy`.
+    The fused path takes CUDA fp32 / bf16 logits and reduction "mean" / "sum"; anything else ("none", CPU, fp16) runs
+    linear_cross_entropy_torch().  LAST_PATH["linear_cross_entropy"] records which; the fused path also records
+    LAST_PATH["cross_entropy_fwd"] / ["cross_entropy_bwd"].  No host sync."""
+    M, D, V = _lce_check(x, weight, targets, bias, ignore_index, reduction, chunk_rows, "linear_cross_entropy")
+    ldt = _lce_dtype(x, weight)
+    if (not x.is_cuda or ldt not in (torch.float32, torch.bfloat16) or reduction == "none" or M >= 2 ** 31
+            or (bias is not None and not torch.is_autocast_enabled("cuda") and bias.dtype != ldt)):
+        LAST_PATH["linear_cross_entropy"] = L.PATH_GENERIC
+        return linear_cross_entropy_torch(x, weight, targets, bias, ignore_index, reduction, chunk_rows)
+    LAST_PATH["linear_cross_entropy"] = L.PATH_FUSED
+    return _cross_entropy_fn._LinearCrossEntropyFn.apply(x, weight, bias, targets.reshape(M).contiguous(), ignore_index, reduction,
+                                                         min(M, chunk_rows or LINEAR_CE_CHUNK_ROWS), ldt)
+
+
 from . import mel_gate_fn as _mel_gate_fn  # noqa: E402  (it reads this module's helpers, all defined by now)
+from . import cross_entropy_fn as _cross_entropy_fn  # noqa: E402  (likewise)
