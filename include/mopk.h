@@ -237,6 +237,26 @@ int mopk_quartet_bwd(const MopkQuartetArgs *a, void *stream);  /* needs q,k,v,(q
 /* 1 if MOPK_PATH_AUTO runs this call on the fused kernels: bf16 arithmetic, dh 32/64, no add_mask, attn == NULL */
 int mopk_quartet_fused_supported(const MopkQuartetArgs *a);
 
+/* The Quartet core over a batch of right-padded rows.  (Added under version 118: new exports only, no layout of an existing
+ * struct changes; callers detect them with mopk_quartet_lens_fused_supported.)
+ * lens: device (B) int32 or NULL (= full rows); n_b = clamp(lens[b], 0, T).  Row i < n_b z-normalises both score maps over the
+ * keys j < n_b only -- mean, unbiased std with max(n_b - 1, 1), the same sd == 0 guard -- and attends to j <= i: it comes out
+ * as the row alone at T = n_b would.  Nothing at or beyond a length is used, NaN / Inf included.  Padding queries get y = 0 and
+ * dq = dq2 = 0 written, padding keys dk = dk2 = dv = 0; padding rows add nothing to dmixture_part / dqscale_part.  The dropout
+ * mask is indexed by the padded positions (b,h,i,j).  With need_weights (base.attn, generic path) rows and columns beyond a
+ * length of the returned map are 0.  With all lengths equal to T the results are bitwise those of mopk_quartet_fwd / _bwd on
+ * the same path.  base.add_mask must be NULL (MOPK_ERR_BAD_ARG otherwise).  Sizes, the path decision, argument checks and the
+ * path == FUSED refusals are those of mopk_quartet_* on base.  Pass the same lengths to _fwd and _bwd. */
+typedef struct MopkQuartetLensArgs {
+    MopkQuartetArgs base;    /* unchanged meaning; base.add_mask must be NULL */
+    const int32_t *lens;     /* device (B) int32, 4-byte aligned, or NULL */
+} MopkQuartetLensArgs;
+size_t mopk_quartet_lens_saved_bytes(const MopkQuartetLensArgs *a);
+size_t mopk_quartet_lens_workspace_bytes(const MopkQuartetLensArgs *a);
+int mopk_quartet_lens_fwd(const MopkQuartetLensArgs *a, void *stream);
+int mopk_quartet_lens_bwd(const MopkQuartetLensArgs *a, void *stream);
+int mopk_quartet_lens_fused_supported(const MopkQuartetLensArgs *a);
+
 /* --------------------------------------------------------------------------
  * Plain scaled-dot-product attention core.
  * Replaces BaselineMSA.forward attention_variants.py:42-46, MSA.forward
@@ -463,6 +483,19 @@ int mopk_token_gate_supported(const MopkTokenGateArgs *a);                /* 1 i
 size_t mopk_token_gate_workspace_bytes(const MopkTokenGateArgs *a);
 int mopk_token_gate_fwd(const MopkTokenGateArgs *a, void *stream);
 int mopk_token_gate_bwd(const MopkTokenGateArgs *a, void *stream);
+
+/* The token gate over right-padded rows (new exports under version 118; detect with mopk_token_gate_lens_supported).
+ * lens: device (B) int32 or NULL (= full rows); n_b = clamp(lens[b], 0, T).  r_t counts as 0 for t >= n_b, so gate_{n_b - 1} has
+ * no u2 term.  Rows t >= n_b get out = 0, dr = 0 and gate = 1 written and add nothing to du; they are never read (a NaN there
+ * changes nothing).  Full lengths are bitwise the call without lengths, du included.  Checks and the workspace size are base's. */
+typedef struct MopkTokenGateLensArgs {
+    MopkTokenGateArgs base;
+    const int32_t *lens;     /* device (B) int32, 4-byte aligned, or NULL */
+} MopkTokenGateLensArgs;
+int mopk_token_gate_lens_supported(const MopkTokenGateLensArgs *a);
+size_t mopk_token_gate_lens_workspace_bytes(const MopkTokenGateLensArgs *a);
+int mopk_token_gate_lens_fwd(const MopkTokenGateLensArgs *a, void *stream);
+int mopk_token_gate_lens_bwd(const MopkTokenGateLensArgs *a, void *stream);
 
 /* --------------------------------------------------------------------------
  * Top-1 routed mixture-of-experts MLP (mop/models/components.py:84-121 MoEMLP), optional residual add.  (Added under version 118:

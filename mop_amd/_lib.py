@@ -114,6 +114,11 @@ class SdpaArgs(C.Structure):
     ]
 
 
+class QuartetLensArgs(C.Structure):
+    """MopkQuartetLensArgs: the Quartet core over right-padded rows, row b has lens[b] real tokens (NULL = full rows)."""
+    _fields_ = [("base", QuartetArgs), ("lens", _fp)]
+
+
 class SdpaLensArgs(C.Structure):
     """MopkSdpaLensArgs: plain SDPA over right-padded rows, query rows i >= q_lens[b] padding, keys j >= kv_lens[b] blocked."""
     _fields_ = [("base", SdpaArgs), ("q_lens", _fp), ("kv_lens", _fp)]
@@ -158,6 +163,11 @@ class TokenGateArgs(C.Structure):
         ("x", _fp), ("x_sb", C.c_int64), ("x_st", C.c_int64), ("a", _fp), ("a_sb", C.c_int64), ("a_st", C.c_int64),
         ("u", _fp), ("out", _fp), ("gate", _fp), ("dout", _fp), ("dr", _fp), ("du", _fp), ("workspace", _fp),
     ]
+
+
+class TokenGateLensArgs(C.Structure):
+    """MopkTokenGateLensArgs: the token gate over right-padded rows, row b has lens[b] real tokens (NULL = full rows)."""
+    _fields_ = [("base", TokenGateArgs), ("lens", _fp)]
 
 
 class MelGateArgs(C.Structure):
@@ -413,6 +423,11 @@ SYMBOLS = {
     "mopk_quartet_fused_supported": (C.c_int, [C.POINTER(QuartetArgs)]),
     "mopk_quartet_fwd": (C.c_int, [C.POINTER(QuartetArgs), C.c_void_p]),
     "mopk_quartet_bwd": (C.c_int, [C.POINTER(QuartetArgs), C.c_void_p]),
+    "mopk_quartet_lens_saved_bytes": (C.c_size_t, [C.POINTER(QuartetLensArgs)]),
+    "mopk_quartet_lens_workspace_bytes": (C.c_size_t, [C.POINTER(QuartetLensArgs)]),
+    "mopk_quartet_lens_fused_supported": (C.c_int, [C.POINTER(QuartetLensArgs)]),
+    "mopk_quartet_lens_fwd": (C.c_int, [C.POINTER(QuartetLensArgs), C.c_void_p]),
+    "mopk_quartet_lens_bwd": (C.c_int, [C.POINTER(QuartetLensArgs), C.c_void_p]),
     "mopk_crossview_saved_bytes": (C.c_size_t, [C.POINTER(CrossViewArgs)]),
     "mopk_crossview_workspace_bytes": (C.c_size_t, [C.POINTER(CrossViewArgs)]),
     "mopk_crossview_fwd": (C.c_int, [C.POINTER(CrossViewArgs), C.c_void_p]),
@@ -433,6 +448,10 @@ SYMBOLS = {
     "mopk_token_gate_workspace_bytes": (C.c_size_t, [C.POINTER(TokenGateArgs)]),
     "mopk_token_gate_fwd": (C.c_int, [C.POINTER(TokenGateArgs), C.c_void_p]),
     "mopk_token_gate_bwd": (C.c_int, [C.POINTER(TokenGateArgs), C.c_void_p]),
+    "mopk_token_gate_lens_supported": (C.c_int, [C.POINTER(TokenGateLensArgs)]),
+    "mopk_token_gate_lens_workspace_bytes": (C.c_size_t, [C.POINTER(TokenGateLensArgs)]),
+    "mopk_token_gate_lens_fwd": (C.c_int, [C.POINTER(TokenGateLensArgs), C.c_void_p]),
+    "mopk_token_gate_lens_bwd": (C.c_int, [C.POINTER(TokenGateLensArgs), C.c_void_p]),
     "mopk_moe_supported": (C.c_int, [C.POINTER(MoeArgs)]),
     "mopk_moe_workspace_bytes": (C.c_size_t, [C.POINTER(MoeArgs), C.c_int]),
     "mopk_moe_route": (C.c_int, [C.POINTER(MoeArgs), C.c_void_p]),

@@ -46,6 +46,9 @@ def _jobs():
     # so are the per-row-length instantiations of the flash SDPA and of the decode attention (mopk_sdpa_lens_*, mopk_decode_attn_lens_*)
     jobs.append(("sdpa_flash.hip", ["-DMOPK_SDPA_LENS"], "sdpa_flash_lens.o"))
     jobs.append(("decode_attn.hip", ["-DMOPK_DECODE_LENS"], "decode_attn_lens.o"))
+    # and those of the Quartet flash kernels and of the token gate (mopk_quartet_lens_*, mopk_token_gate_lens_*)
+    jobs.append(("quartet_flash.hip", ["-DMOPK_QUARTET_LENS"], "quartet_flash_lens.o"))
+    jobs.append(("token_gate.hip", ["-DMOPK_TOKEN_GATE_LENS"], "token_gate_lens.o"))
     for s in FUSED + FUSED_INST_ONLY:
         stem = s.replace(".hip", "")
         # fused bf16-MFMA kernels: relaxed fp (reassociation, contraction, approximate reciprocals) but inf/nan kept;

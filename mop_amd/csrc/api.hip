@@ -32,6 +32,8 @@ int qt_flash_fwd(const MopkQuartetArgs *a, hipStream_t st); int qt_flash_bwd(con
 size_t cv_saved_bytes(const MopkCrossViewArgs *a); size_t cv_ws_bytes(const MopkCrossViewArgs *a);
 int cv_fwd(const MopkCrossViewArgs *a, hipStream_t st); int cv_bwd(const MopkCrossViewArgs *a, hipStream_t st);
 int qt_fwd(const MopkQuartetArgs *a, hipStream_t st); int qt_bwd(const MopkQuartetArgs *a, hipStream_t st);
+int qt_lens_fwd(const MopkQuartetArgs *a, const int32_t *lens, hipStream_t st); int qt_lens_bwd(const MopkQuartetArgs *a, const int32_t *lens, hipStream_t st);
+int qt_flash_lens_fwd(const MopkQuartetArgs *a, const int32_t *lens, hipStream_t st); int qt_flash_lens_bwd(const MopkQuartetArgs *a, const int32_t *lens, hipStream_t st);
 int lens_means_run(const MopkLensMeansArgs *a, bool bwd, hipStream_t st);
 int lens_means_supported(const MopkLensMeansArgs *a, bool bwd);
 
@@ -263,24 +265,56 @@ static bool qt_use_flash(const MopkQuartetArgs *a) { return a->path != MOPK_PATH
 int mopk_quartet_fused_supported(const MopkQuartetArgs *a) { return qt_ok(a) ? qt_flash_supported(a, false) : 0; }
 size_t mopk_quartet_saved_bytes(const MopkQuartetArgs *a) { return !qt_ok(a) ? 0 : (qt_use_flash(a) ? qt_flash_saved_bytes(a) : qt_saved_bytes(a)); }
 size_t mopk_quartet_workspace_bytes(const MopkQuartetArgs *a) { return !qt_ok(a) ? 0 : (qt_use_flash(a) ? qt_flash_ws_bytes(a) : qt_ws_bytes(a)); }
-int mopk_quartet_fwd(const MopkQuartetArgs *a, void *stream) {
+// argument checks of the forward / backward, shared with the entry points that take per-row lengths
+static int qt_check(const MopkQuartetArgs *a, bool bwd) {
     if (!a) return MOPK_ERR_BAD_ARG;
     int rc = base_ok(a->B, a->H, a->T, a->dh, a->io_dtype, a->precision); if (rc) return rc;
-    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
-    if (a->use_quartet && any_null(a->q2.ptr, a->k2.ptr, a->mixture, a->quartet_scale)) return MOPK_ERR_BAD_ARG;
-    if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return MOPK_ERR_BAD_ARG;
+    if (!bwd) {
+        if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
+        if (a->use_quartet && any_null(a->q2.ptr, a->k2.ptr, a->mixture, a->quartet_scale)) return MOPK_ERR_BAD_ARG;
+        if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return MOPK_ERR_BAD_ARG;
+        return MOPK_OK;
+    }
+    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->dy.ptr, a->dq.ptr, a->dk_.ptr, a->dv.ptr, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
+    if (a->use_quartet && any_null(a->q2.ptr, a->k2.ptr, a->dq2.ptr, a->dk2.ptr, a->dmixture_part, a->dqscale_part, a->mixture, a->quartet_scale)) return MOPK_ERR_BAD_ARG;
+    return MOPK_OK;
+}
+int mopk_quartet_fwd(const MopkQuartetArgs *a, void *stream) {
+    int rc = qt_check(a, false); if (rc) return rc;
     if (qt_use_flash(a)) return qt_flash_fwd(a, (hipStream_t)stream);
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
     return qt_fwd(a, (hipStream_t)stream);
 }
 int mopk_quartet_bwd(const MopkQuartetArgs *a, void *stream) {    // the fused path also reads `y` (the forward's output)
-    if (!a) return MOPK_ERR_BAD_ARG;
-    int rc = base_ok(a->B, a->H, a->T, a->dh, a->io_dtype, a->precision); if (rc) return rc;
-    if (any_null(a->q.ptr, a->k.ptr, a->v.ptr, a->y.ptr, a->dy.ptr, a->dq.ptr, a->dk_.ptr, a->dv.ptr, a->saved, a->workspace)) return MOPK_ERR_BAD_ARG;
-    if (a->use_quartet && any_null(a->q2.ptr, a->k2.ptr, a->dq2.ptr, a->dk2.ptr, a->dmixture_part, a->dqscale_part, a->mixture, a->quartet_scale)) return MOPK_ERR_BAD_ARG;
+    int rc = qt_check(a, true); if (rc) return rc;
     if (qt_use_flash(a)) return qt_flash_bwd(a, (hipStream_t)stream);
     if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
     return qt_bwd(a, (hipStream_t)stream);
+}
+// ---- the Quartet core with per-row lengths: the same path decision, sizes and checks as mopk_quartet_* on base ----
+static bool qt_lens_ok(const MopkQuartetLensArgs *l) { return l && qt_ok(&l->base) && !l->base.add_mask && !misaligned(3, l->lens); }
+int mopk_quartet_lens_fused_supported(const MopkQuartetLensArgs *l) { return qt_lens_ok(l) ? mopk_quartet_fused_supported(&l->base) : 0; }
+size_t mopk_quartet_lens_saved_bytes(const MopkQuartetLensArgs *l) { return qt_lens_ok(l) ? mopk_quartet_saved_bytes(&l->base) : 0; }
+size_t mopk_quartet_lens_workspace_bytes(const MopkQuartetLensArgs *l) { return qt_lens_ok(l) ? mopk_quartet_workspace_bytes(&l->base) : 0; }
+static int qt_lens_check(const MopkQuartetLensArgs *l, bool bwd) {
+    if (!l) return MOPK_ERR_BAD_ARG;
+    int rc = qt_check(&l->base, bwd); if (rc) return rc;
+    if (l->base.add_mask) return MOPK_ERR_BAD_ARG;                          // an additive mask goes with mopk_quartet_*, not with lengths
+    return misaligned(3, l->lens) ? MOPK_ERR_UNSUPPORTED : MOPK_OK;
+}
+int mopk_quartet_lens_fwd(const MopkQuartetLensArgs *l, void *stream) {
+    int rc = qt_lens_check(l, false); if (rc) return rc;
+    const MopkQuartetArgs *a = &l->base;
+    if (qt_use_flash(a)) return qt_flash_lens_fwd(a, l->lens, (hipStream_t)stream);
+    if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
+    return qt_lens_fwd(a, l->lens, (hipStream_t)stream);
+}
+int mopk_quartet_lens_bwd(const MopkQuartetLensArgs *l, void *stream) {
+    int rc = qt_lens_check(l, true); if (rc) return rc;
+    const MopkQuartetArgs *a = &l->base;
+    if (qt_use_flash(a)) return qt_flash_lens_bwd(a, l->lens, (hipStream_t)stream);
+    if (a->path == MOPK_PATH_FUSED) return MOPK_ERR_UNSUPPORTED;
+    return qt_lens_bwd(a, l->lens, (hipStream_t)stream);
 }
 
 }  // extern "C"

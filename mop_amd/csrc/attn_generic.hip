@@ -437,27 +437,49 @@ static QtBuf qt_carve(void *saved, void *ws, const Dm &d, size_t *ns, size_t *nw
 size_t qt_saved_bytes(const MopkQuartetArgs *a) { size_t s; qt_carve(nullptr, nullptr, mkdm(a->B, a->H, a->T, a->dh), &s, nullptr); return s; }
 size_t qt_ws_bytes(const MopkQuartetArgs *a) { size_t w; qt_carve(nullptr, nullptr, mkdm(a->B, a->H, a->T, a->dh), nullptr, &w); return w; }
 
-// z = (S - mean)/(std_unbiased + eps) over the FULL row (:95-98); in place; wave per row
-__global__ void znorm_kernel(float *S, float *sd, Dm d, float eps) {
+// per-row lengths of the Quartet core (mopk_quartet_lens_*): the n real tokens of batch row b, nullptr = all N
+__device__ __forceinline__ int qt_row_len(const int32_t *lens, int64_t b, int N) {
+    if (!lens) return N;
+    const int n = lens[b];
+    return n < 0 ? 0 : (n > N ? N : n);
+}
+// z = (S - mean)/(std_unbiased + eps) over the FULL row (:95-98); in place; wave per row.  With lengths the row is its first n
+// keys (count and loop bound); padding rows and columns are written 0 (sd = 0 on a padding row).
+__global__ void znorm_kernel(float *S, float *sd, Dm d, float eps, const int32_t *lens) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= d.BH * d.N) return;
     const int lane = threadIdx.x & 63;
+    const int n = qt_row_len(lens, row / d.N / d.H, d.N);
     float *p = S + row * d.LD;
+    if (row % d.N >= n) {
+        for (int j = lane; j < d.N; j += 64) p[j] = 0.f;
+        if (lane == 0) sd[row] = 0.f;
+        return;
+    }
     float sm = 0.f;
-    for (int j = lane; j < d.N; j += 64) sm += p[j];
-    const float mu = wave_sum(sm) / d.N;
+    for (int j = lane; j < n; j += 64) sm += p[j];
+    const float mu = wave_sum(sm) / n;
     float ss = 0.f;
-    for (int j = lane; j < d.N; j += 64) { const float t = p[j] - mu; ss += t * t; }
-    const float sdv = sqrtf(wave_sum(ss) / (float)max(d.N - 1, 1));
+    for (int j = lane; j < n; j += 64) { const float t = p[j] - mu; ss += t * t; }
+    const float sdv = sqrtf(wave_sum(ss) / (float)max(n - 1, 1));
     const float inv = 1.f / (sdv + eps);
-    for (int j = lane; j < d.N; j += 64) p[j] = (p[j] - mu) * inv;
+    for (int j = lane; j < n; j += 64) p[j] = (p[j] - mu) * inv;
+    for (int j = n + lane; j < d.N; j += 64) p[j] = 0.f;
     if (lane == 0) sd[row] = sdv;
 }
-__global__ void qt_mix_fwd_kernel(MopkQuartetArgs a, Dm d, QtBuf b) {
+// a row i < n sees j <= i < n through the causal edge alone; a padding row gets P = 0 (and a zero row of the returned weights)
+__global__ void qt_mix_fwd_kernel(MopkQuartetArgs a, Dm d, QtBuf b, const int32_t *lens) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= d.BH * d.N) return;
     const int lane = threadIdx.x & 63, i = row % d.N;
     const int64_t bh = row / d.N;
+    if (i >= qt_row_len(lens, bh / d.H, d.N)) {
+        for (int j = lane; j < d.N; j += 64) {
+            b.P[row * d.LD + j] = 0.f;
+            if (a.attn) a.attn[row * (int64_t)d.N + j] = 0.f;
+        }
+        return;
+    }
     const float *am = a.add_mask ? a.add_mask + (bh / d.H) * a.am_sb + (bh % d.H) * a.am_sh + i * a.am_si : nullptr;
     float mq = 0.f, qs = 0.f;
     if (a.use_quartet) { mq = sigmoidf_(*a.mixture); qs = *a.quartet_scale; }
@@ -484,10 +506,15 @@ __global__ void qt_mix_fwd_kernel(MopkQuartetArgs a, Dm d, QtBuf b) {
     }
 }
 // dsc = P(dP - dot); dz1 -> dP (in place), dz2 -> b.dz2 ; per-row partials of dm, dqs
-__global__ void qt_mix_bwd_kernel(MopkQuartetArgs a, Dm d, QtBuf b) {
+__global__ void qt_mix_bwd_kernel(MopkQuartetArgs a, Dm d, QtBuf b, const int32_t *lens) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= d.BH * d.N) return;
     const int lane = threadIdx.x & 63;
+    if (row % d.N >= qt_row_len(lens, row / d.N / d.H, d.N)) {     // a padding row: zero score gradients, nothing for the scalars
+        for (int j = lane; j < d.N; j += 64) { b.dP[row * d.LD + j] = 0.f; if (a.use_quartet) b.dz2[row * d.LD + j] = 0.f; }
+        if (lane == 0) { b.rowdm[row] = 0.f; b.rowdqs[row] = 0.f; }
+        return;
+    }
     const float *P = b.P + row * d.LD;
     float *dP = b.dP + row * d.LD;
     float dot = 0.f;
@@ -510,19 +537,22 @@ __global__ void qt_mix_bwd_kernel(MopkQuartetArgs a, Dm d, QtBuf b) {
     if (lane == 0) { b.rowdm[row] = sdm * mq * (1.f - mq); b.rowdqs[row] = sdq; }
 }
 // gradient through z-norm, times alpha; in place; wave per row
-__global__ void znorm_bwd_kernel(float *dz, const float *z, const float *sd, Dm d, float eps, float alpha) {
+__global__ void znorm_bwd_kernel(float *dz, const float *z, const float *sd, Dm d, float eps, float alpha, const int32_t *lens) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= d.BH * d.N) return;
     const int lane = threadIdx.x & 63;
+    int n = qt_row_len(lens, row / d.N / d.H, d.N);                // the row's keys: count and loop bound
+    if (row % d.N >= n) n = 0;                                     // a padding row is all zeros
     const float sdv = sd[row], den = sdv + eps;
     float sm = 0.f, sp = 0.f;
-    for (int j = lane; j < d.N; j += 64) { const float g = dz[row * d.LD + j]; sm += g; sp += g * z[row * d.LD + j] * den; }
-    sm = wave_sum(sm) / d.N; sp = wave_sum(sp);
-    const float c2 = sp / ((float)max(d.N - 1, 1) * fmaxf(sdv, 1e-30f) * den * den);
-    for (int j = lane; j < d.N; j += 64) {
+    for (int j = lane; j < n; j += 64) { const float g = dz[row * d.LD + j]; sm += g; sp += g * z[row * d.LD + j] * den; }
+    sm = wave_sum(sm) / max(n, 1); sp = wave_sum(sp);
+    const float c2 = sp / ((float)max(n - 1, 1) * fmaxf(sdv, 1e-30f) * den * den);
+    for (int j = lane; j < n; j += 64) {
         const int64_t o = row * d.LD + j;
         dz[o] = ((dz[o] - sm) / den - z[o] * den * c2) * alpha;
     }
+    for (int j = n + lane; j < d.N; j += 64) dz[row * d.LD + j] = 0.f;
 }
 __global__ void rowsum_part_kernel(const float *x, float *out, int N) {
     __shared__ float red[256];
@@ -532,21 +562,25 @@ __global__ void rowsum_part_kernel(const float *x, float *out, int N) {
     for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
     if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
-int qt_fwd(const MopkQuartetArgs *a, hipStream_t st) {
+// lens (mopk_quartet_lens_*; nullptr = full rows): the gathered padding rows are zeroed, the row kernels take n_b as the count and
+// the bound of a row, so P, y and -- in qt_lens_bwd -- every gradient come out 0 on padding rows through the GEMM chain
+int qt_lens_fwd(const MopkQuartetArgs *a, const int32_t *lens, hipStream_t st) {
     const Dm d = mkdm(a->B, a->H, a->T, a->dh);
     const QtBuf b = qt_carve(a->saved, a->workspace, d, nullptr, nullptr);
     const bool mf = a->precision == MOPK_PREC_BF16;
     const int64_t rows = d.BH * d.N;
     const float sc = 1.f / sqrtf((float)d.dk);
     RET_IF(gather(a->io_dtype, a->q, b.q, d, st)); RET_IF(gather(a->io_dtype, a->k, b.k, d, st)); RET_IF(gather(a->io_dtype, a->v, b.v, d, st));
+    RET_IF(zero_tail(b.q, d, lens, st)); RET_IF(zero_tail(b.k, d, lens, st)); RET_IF(zero_tail(b.v, d, lens, st));
     RET_IF(gemm_nt_scores(b.q, b.k, b.z1, d, sc, mf, st));                             // :88
-    hipLaunchKernelGGL(znorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.z1, b.sd1, d, a->use_quartet ? a->eps : 1e-5f);
+    hipLaunchKernelGGL(znorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.z1, b.sd1, d, a->use_quartet ? a->eps : 1e-5f, lens);
     if (a->use_quartet) {
         RET_IF(gather(a->io_dtype, a->q2, b.q2, d, st)); RET_IF(gather(a->io_dtype, a->k2, b.k2, d, st));
+        RET_IF(zero_tail(b.q2, d, lens, st)); RET_IF(zero_tail(b.k2, d, lens, st));
         RET_IF(gemm_nt_scores(b.q2, b.k2, b.z2, d, sc, mf, st));                       // :93
-        hipLaunchKernelGGL(znorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.z2, b.sd2, d, a->eps);
+        hipLaunchKernelGGL(znorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.z2, b.sd2, d, a->eps, lens);
     }
-    hipLaunchKernelGGL(qt_mix_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, *a, d, b);
+    hipLaunchKernelGGL(qt_mix_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, *a, d, b, lens);
     if (a->dropout_p > 0.f) {                                                          // :119; the returned weights are the dropped ones (:125-126)
         drop_map(b.P, b.dP, d, a->dropout_p, a->dropout_seed, st);
         if (a->attn) hipLaunchKernelGGL(drop_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.P, d.LD, a->attn, d.N, fa_drop(a->dropout_p, a->dropout_seed), rows, d.N, d.N);
@@ -555,24 +589,26 @@ int qt_fwd(const MopkQuartetArgs *a, hipStream_t st) {
     RET_IF(gemm_map_vec(a->dropout_p > 0.f ? b.dP : b.P, false, b.v, b.y, d, 1.f, 0.f, mf, st));   // :121
     return scatter(a->io_dtype, b.y, a->y, d, st);
 }
-int qt_bwd(const MopkQuartetArgs *a, hipStream_t st) {
+int qt_fwd(const MopkQuartetArgs *a, hipStream_t st) { return qt_lens_fwd(a, nullptr, st); }
+int qt_lens_bwd(const MopkQuartetArgs *a, const int32_t *lens, hipStream_t st) {
     const Dm d = mkdm(a->B, a->H, a->T, a->dh);
     const QtBuf b = qt_carve(a->saved, a->workspace, d, nullptr, nullptr);
     const bool mf = a->precision == MOPK_PREC_BF16;
     const int64_t rows = d.BH * d.N;
     const float sc = 1.f / sqrtf((float)d.dk);
     RET_IF(gather(a->io_dtype, a->dy, b.dy, d, st));
+    RET_IF(zero_tail(b.dy, d, lens, st));
     RET_IF(drop_bwd_pair(b.P, b.dy, b.v, b.dP, b.dv, d, a->dropout_p, a->dropout_seed, mf, st));
     RET_IF(scatter(a->io_dtype, b.dv, a->dv, d, st));
-    hipLaunchKernelGGL(qt_mix_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, *a, d, b);
+    hipLaunchKernelGGL(qt_mix_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, *a, d, b, lens);
     if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     const float eps1 = a->use_quartet ? a->eps : 1e-5f;
-    hipLaunchKernelGGL(znorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.dP, b.z1, b.sd1, d, eps1, sc);
+    hipLaunchKernelGGL(znorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.dP, b.z1, b.sd1, d, eps1, sc, lens);
     if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
     RET_IF(gemm_map_vec(b.dP, false, b.k, b.dq, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dq, a->dq, d, st));
     RET_IF(gemm_map_vec(b.dP, true, b.q, b.dk, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dk, a->dk_, d, st));
     if (a->use_quartet) {
-        hipLaunchKernelGGL(znorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.dz2, b.z2, b.sd2, d, a->eps, sc);
+        hipLaunchKernelGGL(znorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, b.dz2, b.z2, b.sd2, d, a->eps, sc, lens);
         if (launch_status() != MOPK_OK) return MOPK_ERR_LAUNCH;
         RET_IF(gemm_map_vec(b.dz2, false, b.k2, b.dq, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dq, a->dq2, d, st));
         RET_IF(gemm_map_vec(b.dz2, true, b.q2, b.dk, d, 1.f, 0.f, mf, st)); RET_IF(scatter(a->io_dtype, b.dk, a->dk2, d, st));
@@ -582,6 +618,7 @@ int qt_bwd(const MopkQuartetArgs *a, hipStream_t st) {
     }
     return MOPK_OK;
 }
+int qt_bwd(const MopkQuartetArgs *a, hipStream_t st) { return qt_lens_bwd(a, nullptr, st); }
 
 // =====================================================================  CrossViewMixerMSA
 struct CvBuf {

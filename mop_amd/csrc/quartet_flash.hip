@@ -8,12 +8,32 @@
 //   dS = (dz - mean(dz)) / den - (S - mu) sum(dz (S - mu)) / ((T-1) sd den^2),
 // so it is: delta, a row-sum pass over the causal region, a dQ pass and a dK/dV pass over ALL tiles.  Same X layout as
 // sdpa_flash.hip (lane = query, registers = keys; in the dK/dV pass lane = key, registers = queries).
+//
+// Per-row lengths (LENS = true, mopk_quartet_lens_*): a batch of right-padded rows, n_b = clamp(lens[b], 0, T) read once per
+// workgroup.  n_b stands wherever the row's extent is a BOUND or a COUNT -- tile loops, fetch bounds, the edge selects, T and T - 1 of
+// the statistics and of the z-norm backward -- and a.T stays the extent of the tensors and of stats / lse / delta / rows / spart.
+// Row i < n_b comes out as the row alone at T = n_b would; rows beyond a length are never loaded (zeros enter the MFMAs) and get
+// y = 0, lse = +inf, zero gradients written; a workgroup whose 128 queries (keys in the dK/dV pass) are all padding writes them and
+// leaves before the first barrier.  With full lengths every instruction sees the operands of the LENS = false kernel: bitwise equal
+// results.  The LENS = true instantiations live in a unit of their own (-DMOPK_QUARTET_LENS, mop_amd/build.py), so the code of
+// the others is what it was.
 #include "flash_common.h"
+#include <type_traits>
 
 namespace mopk {
 
 namespace {
 struct QtScal { float m, mq, qs, eps1, eps2; };        // sigmoid(mixture), m * quartet_scale, quartet_scale, eps of the two z-norms
+// the kernels' argument struct: MopkQuartetArgs itself, or (LENS) the struct that wraps it with the lengths
+template <bool LENS> using QtArgs = std::conditional_t<LENS, MopkQuartetLensArgs, MopkQuartetArgs>;
+__device__ __forceinline__ const MopkQuartetArgs &qt_base(const MopkQuartetArgs &a) { return a; }
+__device__ __forceinline__ const MopkQuartetArgs &qt_base(const MopkQuartetLensArgs &a) { return a.base; }
+__device__ __forceinline__ int qt_len(const MopkQuartetArgs &a, int) { return a.T; }
+__device__ __forceinline__ int qt_len(const MopkQuartetLensArgs &a, int b) {      // b comes from blockIdx: one scalar load per workgroup
+    if (!a.lens) return a.base.T;
+    const int n = a.lens[b];
+    return n < 0 ? 0 : (n > a.base.T ? a.base.T : n);
+}
 template <bool DUAL>
 __device__ __forceinline__ QtScal qt_scal(const MopkQuartetArgs &a) {
     QtScal s;
@@ -49,8 +69,9 @@ __device__ __forceinline__ float qt_am(const MopkQuartetArgs &a, const float *ba
 }  // namespace
 
 // ------------------------------------------------------------------ pass 1: row statistics over all T keys
-template <int DK, typename IOT, bool DUAL>
-__global__ void __launch_bounds__(FA_NW * 64) qt_stats_kernel(MopkQuartetArgs a, float *stats) {
+template <int DK, typename IOT, bool DUAL, bool LENS = false>
+__global__ void __launch_bounds__(FA_NW * 64) qt_stats_kernel(QtArgs<LENS> al, float *stats) {
+    const MopkQuartetArgs &a = qt_base(al);
     constexpr int LDK = DK + 8;
     __shared__ __attribute__((aligned(16))) unsigned short Ks[FA_KT * LDK], K2s[DUAL ? FA_KT * LDK : 8];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -59,7 +80,9 @@ __global__ void __launch_bounds__(FA_NW * 64) qt_stats_kernel(MopkQuartetArgs a,
     fa_block_id((N + FA_QB - 1) / FA_QB, qb, bh);
     const int b = bh / a.H, hh = bh % a.H;
     const int qi = qb * FA_QB + 32 * w + r;
-    const bool qok = qi < N;
+    const int n = qt_len(al, b);                     // LENS: the keys (and queries) of this row that are real; else N
+    if (LENS && qb * FA_QB >= n) return;             // workgroup-uniform: only padding queries, whose statistics nobody reads
+    const bool qok = qi < n;
     const float sc = rsqrtf((float)DK);
     bf16x8 qe[DK / 16], q2e[DUAL ? DK / 16 : 1];
     fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, sc);
@@ -69,18 +92,18 @@ __global__ void __launch_bounds__(FA_NW * 64) qt_stats_kernel(MopkQuartetArgs a,
         k2p = (const IOT *)a.k2.ptr + b * a.k2.sb + hh * a.k2.sh;
     }
     float pv1 = 0.f, pv2 = 0.f, s1 = 0.f, ss1 = 0.f, s2 = 0.f, ss2 = 0.f;   // sums of (S - pivot), pivot = S[i, 0]: no cancellation
-    const int nkt = (N + FA_KT - 1) / FA_KT;
+    const int nkt = (n + FA_KT - 1) / FA_KT;
     FaTile<DK> fk, fk2;
-    fa_fetch<DK, IOT>(fk, kp, a.k.sn, 0, N, 1.f, tid);
-    if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, a.k2.sn, 0, N, 1.f, tid);
+    fa_fetch<DK, IOT>(fk, kp, a.k.sn, 0, n, 1.f, tid);
+    if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, a.k2.sn, 0, n, 1.f, tid);
     for (int kt = 0; kt < nkt; ++kt) {
         const int k0 = kt * FA_KT;
         __syncthreads();
         fa_put<DK, true, false>(Ks, nullptr, fk, tid);
         if (DUAL) fa_put<DK, true, false>(K2s, nullptr, fk2, tid);
         if (kt + 1 < nkt) {
-            fa_fetch<DK, IOT>(fk, kp, a.k.sn, k0 + FA_KT, N, 1.f, tid);
-            if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, a.k2.sn, k0 + FA_KT, N, 1.f, tid);
+            fa_fetch<DK, IOT>(fk, kp, a.k.sn, k0 + FA_KT, n, 1.f, tid);
+            if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, a.k2.sn, k0 + FA_KT, n, 1.f, tid);
         }
         __syncthreads();
 #pragma unroll
@@ -91,7 +114,7 @@ __global__ void __launch_bounds__(FA_NW * 64) qt_stats_kernel(MopkQuartetArgs a,
             if (kt == 0 && hf == 0) { pv1 = __shfl(S1[0], r, 64); pv2 = __shfl(S2[0], r, 64); }   // key 0 sits in register 0 of half 0
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                if (k0 + 32 * hf + tile_row(g, h) < N) {
+                if (k0 + 32 * hf + tile_row(g, h) < n) {
                     const float d1 = S1[g] - pv1, d2 = S2[g] - pv2;
                     s1 += d1; ss1 = fmaf(d1, d1, ss1); s2 += d2; ss2 = fmaf(d2, d2, ss2);
                 }
@@ -100,7 +123,7 @@ __global__ void __launch_bounds__(FA_NW * 64) qt_stats_kernel(MopkQuartetArgs a,
     }
     s1 += __shfl_xor(s1, 32, 64); ss1 += __shfl_xor(ss1, 32, 64); s2 += __shfl_xor(s2, 32, 64); ss2 += __shfl_xor(ss2, 32, 64);
     if (qok && h == 0) {
-        const float T = (float)N, tm1 = (float)max(N - 1, 1);
+        const float T = (float)n, tm1 = (float)max(n - 1, 1);
         float4 o;
         o.x = pv1 + s1 / T; o.y = sqrtf(fmaxf((ss1 - s1 * s1 / T) / tm1, 0.f));          // mean, unbiased std   :96-97
         o.z = pv2 + s2 / T; o.w = sqrtf(fmaxf((ss2 - s2 * s2 / T) / tm1, 0.f));
@@ -109,8 +132,9 @@ __global__ void __launch_bounds__(FA_NW * 64) qt_stats_kernel(MopkQuartetArgs a,
 }
 
 // ------------------------------------------------------------------ pass 2: mixed logits, causal online softmax, A v
-template <int DK, typename IOT, bool DUAL, bool AM>
-__global__ void __launch_bounds__(FA_NW * 64, 2) qt_fwd_kernel(MopkQuartetArgs a, const float *stats, float *lse) {
+template <int DK, typename IOT, bool DUAL, bool AM, bool LENS = false>
+__global__ void __launch_bounds__(FA_NW * 64, 2) qt_fwd_kernel(QtArgs<LENS> al, const float *stats, float *lse) {
+    const MopkQuartetArgs &a = qt_base(al);
     constexpr int DT = DK / 32, LDK = DK + 8;
     __shared__ __attribute__((aligned(16))) unsigned short Ks[FA_KT * LDK], Vt[DK * FA_LDT], K2s[DUAL ? FA_KT * LDK : 8];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -120,29 +144,38 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_fwd_kernel(MopkQuartetArgs a
     const int b = bh / a.H, hh = bh % a.H;
     const int q0 = qb * FA_QB, qi = q0 + 32 * w + r;
     const bool qok = qi < N;
+    const int n = qt_len(al, b);                     // LENS: the real tokens of this row; qin = this lane's query is one of them
+    const bool qin = LENS ? qi < n : qok;
     const float sc = rsqrtf((float)DK);
     const QtScal qs = qt_scal<DUAL>(a);
     const float *amp = AM ? a.add_mask + b * a.am_sb + hh * a.am_sh : nullptr;
     bf16x8 qe[DK / 16], q2e[DUAL ? DK / 16 : 1];
-    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, sc);
+    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qin, h, sc);
     const IOT *kp = (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh, *vp = (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh, *k2p = nullptr;
     if (DUAL) {
-        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)a.q2.ptr + b * a.q2.sb + hh * a.q2.sh + (int64_t)qi * a.q2.sn, qok, h, sc);
+        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)a.q2.ptr + b * a.q2.sb + hh * a.q2.sh + (int64_t)qi * a.q2.sn, qin, h, sc);
         k2p = (const IOT *)a.k2.ptr + b * a.k2.sb + hh * a.k2.sh;
     }
-    const float4 st = qok ? ((const float4 *)stats)[(int64_t)bh * N + qi] : make_float4(0.f, 1.f, 0.f, 1.f);
-    const QtNorm n1 = qt_norm(st.x, st.y, qs.eps1, N, 0.f, 0.f), n2 = qt_norm(st.z, st.w, qs.eps2, N, 0.f, 0.f);
+    const float4 st = qin ? ((const float4 *)stats)[(int64_t)bh * N + qi] : make_float4(0.f, 1.f, 0.f, 1.f);
+    const QtNorm n1 = qt_norm(st.x, st.y, qs.eps1, n, 0.f, 0.f), n2 = qt_norm(st.z, st.w, qs.eps2, n, 0.f, 0.f);
     const FaDrop drop = fa_drop(a.dropout_p, a.dropout_seed);
     const uint32_t rowh = fa_drop_row(drop, bh, qi);
     float m = FA_NEG, l = 0.f;
     f32x16 O[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) O[dt] = fa_zero();
-    const int nkt = min((N + FA_KT - 1) / FA_KT, (min(q0 + FA_QB, N) + FA_KT - 1) / FA_KT);      // causal   :112-113
+    if (LENS && q0 >= n) {                           // workgroup-uniform: all 128 queries are padding -- write the zeros and leave
+        if (qok) {
+            fa_store_rows<DK, IOT>((IOT *)a.y.ptr + b * a.y.sb + hh * a.y.sh + (int64_t)qi * a.y.sn, O, h, 0.f);
+            if (h == 0) lse[(int64_t)bh * N + qi] = INFINITY;
+        }
+        return;
+    }
+    const int nkt = min((n + FA_KT - 1) / FA_KT, (min(q0 + FA_QB, n) + FA_KT - 1) / FA_KT);      // causal   :112-113
     FaTile<DK> fk, fv, fk2;
-    fa_fetch<DK, IOT>(fk, kp, a.k.sn, 0, N, 1.f, tid);
-    fa_fetch<DK, IOT>(fv, vp, a.v.sn, 0, N, 1.f, tid);
-    if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, a.k2.sn, 0, N, 1.f, tid);
+    fa_fetch<DK, IOT>(fk, kp, a.k.sn, 0, n, 1.f, tid);
+    fa_fetch<DK, IOT>(fv, vp, a.v.sn, 0, n, 1.f, tid);
+    if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, a.k2.sn, 0, n, 1.f, tid);
     for (int kt = 0; kt < nkt; ++kt) {
         const int k0 = kt * FA_KT;
         __syncthreads();
@@ -150,9 +183,9 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_fwd_kernel(MopkQuartetArgs a
         fa_put<DK, false, true>(nullptr, Vt, fv, tid);
         if (DUAL) fa_put<DK, true, false>(K2s, nullptr, fk2, tid);
         if (kt + 1 < nkt) {
-            fa_fetch<DK, IOT>(fk, kp, a.k.sn, k0 + FA_KT, N, 1.f, tid);
-            fa_fetch<DK, IOT>(fv, vp, a.v.sn, k0 + FA_KT, N, 1.f, tid);
-            if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, a.k2.sn, k0 + FA_KT, N, 1.f, tid);
+            fa_fetch<DK, IOT>(fk, kp, a.k.sn, k0 + FA_KT, n, 1.f, tid);
+            fa_fetch<DK, IOT>(fv, vp, a.v.sn, k0 + FA_KT, n, 1.f, tid);
+            if (DUAL) fa_fetch<DK, IOT>(fk2, k2p, a.k2.sn, k0 + FA_KT, n, 1.f, tid);
         }
         __syncthreads();
         f32x16 S[2];
@@ -167,7 +200,7 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_fwd_kernel(MopkQuartetArgs a
                 const int j = k0 + 32 * hf + tile_row(g, h);
                 float z1, z2;
                 const float lg = (qt_logit<DUAL>(S[hf][g], T2[g], n1, n2, qs, z1, z2) + qt_am<AM>(a, amp, qi, j)) * FA_LOG2E;
-                S[hf][g] = (j >= N || j > qi) ? FA_NEG : lg;
+                S[hf][g] = (j >= n || j > qi) ? FA_NEG : lg;
                 mx = fmaxf(mx, S[hf][g]);
             }
         }
@@ -198,6 +231,7 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_fwd_kernel(MopkQuartetArgs a
             fa_mm_cols<DK>(O, Vt, hf, r, h, lo, hi);
         }
     }
+    if (LENS && !qin) { m = INFINITY; l = INFINITY; }   // a padding query inside a live block is a row with no open key: y = 0 (O is finite), lse = +inf
     if (qok) {
         fa_store_rows<DK, IOT>((IOT *)a.y.ptr + b * a.y.sb + hh * a.y.sh + (int64_t)qi * a.y.sn, O, h, 1.f / l);
         if (h == 0) lse[(int64_t)bh * N + qi] = m + __builtin_amdgcn_logf(l);
@@ -221,9 +255,10 @@ __global__ void qt_delta_kernel(MopkQuartetArgs a, float *delta) {          // d
 }
 
 // row sums of the z-norm backward over the causal region + per-block partials of the two scalar gradients
-template <int DK, typename IOT, bool DUAL, bool AM>
-__global__ void __launch_bounds__(FA_NW * 64, 2) qt_rowsum_kernel(MopkQuartetArgs a, const float *stats, const float *lse, const float *delta,
+template <int DK, typename IOT, bool DUAL, bool AM, bool LENS = false>
+__global__ void __launch_bounds__(FA_NW * 64, 2) qt_rowsum_kernel(QtArgs<LENS> al, const float *stats, const float *lse, const float *delta,
                                                                float *rows, float *spart) {
+    const MopkQuartetArgs &a = qt_base(al);
     constexpr int LDK = DK + 8;
     __shared__ __attribute__((aligned(16))) unsigned short Ks[FA_KT * LDK], Vs[FA_KT * LDK], K2s[DUAL ? FA_KT * LDK : 8];
     __shared__ float red[2][FA_NW];
@@ -234,30 +269,40 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_rowsum_kernel(MopkQuartetArg
     const int b = bh / a.H, hh = bh % a.H;
     const int q0 = qb * FA_QB, qi = q0 + 32 * w + r;
     const bool qok = qi < N;
+    const int n = qt_len(al, b);                     // as in the forward
+    const bool qin = LENS ? qi < n : qok;
     const float sc = rsqrtf((float)DK);
     const QtScal qs = qt_scal<DUAL>(a);
     const float *amp = AM ? a.add_mask + b * a.am_sb + hh * a.am_sh : nullptr;
     bf16x8 qe[DK / 16], q2e[DUAL ? DK / 16 : 1], dof[DK / 16];
-    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, sc);
-    fa_frags<DK, IOT>(dof, (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh + (int64_t)qi * a.dy.sn, qok, h, 1.f);
+    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qin, h, sc);
+    fa_frags<DK, IOT>(dof, (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh + (int64_t)qi * a.dy.sn, qin, h, 1.f);
     const IOT *kp = (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh, *vp = (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh, *k2p = nullptr;
     if (DUAL) {
-        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)a.q2.ptr + b * a.q2.sb + hh * a.q2.sh + (int64_t)qi * a.q2.sn, qok, h, sc);
+        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)a.q2.ptr + b * a.q2.sb + hh * a.q2.sh + (int64_t)qi * a.q2.sn, qin, h, sc);
         k2p = (const IOT *)a.k2.ptr + b * a.k2.sb + hh * a.k2.sh;
     }
-    const float4 st = qok ? ((const float4 *)stats)[(int64_t)bh * N + qi] : make_float4(0.f, 1.f, 0.f, 1.f);
-    const QtNorm n1 = qt_norm(st.x, st.y, qs.eps1, N, 0.f, 0.f), n2 = qt_norm(st.z, st.w, qs.eps2, N, 0.f, 0.f);
-    const float Li = qok ? lse[(int64_t)bh * N + qi] : 0.f, di = qok ? delta[(int64_t)bh * N + qi] : 0.f;
+    const float4 st = qin ? ((const float4 *)stats)[(int64_t)bh * N + qi] : make_float4(0.f, 1.f, 0.f, 1.f);
+    const QtNorm n1 = qt_norm(st.x, st.y, qs.eps1, n, 0.f, 0.f), n2 = qt_norm(st.z, st.w, qs.eps2, n, 0.f, 0.f);
+    const float Li = qin ? lse[(int64_t)bh * N + qi] : 0.f, di = qin ? delta[(int64_t)bh * N + qi] : 0.f;
     const FaDrop drop = fa_drop(a.dropout_p, a.dropout_seed);
     const uint32_t rowh = fa_drop_row(drop, bh, qi);
     float A1 = 0.f, B1 = 0.f, A2 = 0.f, B2 = 0.f, gm = 0.f, gq = 0.f;
-    const int nkt = min((N + FA_KT - 1) / FA_KT, (min(q0 + FA_QB, N) + FA_KT - 1) / FA_KT);
+    if (LENS && q0 >= n) {                           // workgroup-uniform: only padding queries -- zero row sums and a zero partial
+        if (qok && h == 0) ((float4 *)rows)[(int64_t)bh * N + qi] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid == 0) {                              // qt_scalar_sum_kernel sums every block's partial
+            const int nq = (N + FA_QB - 1) / FA_QB;
+            spart[((int64_t)bh * nq + qb) * 2] = 0.f; spart[((int64_t)bh * nq + qb) * 2 + 1] = 0.f;
+        }
+        return;
+    }
+    const int nkt = min((n + FA_KT - 1) / FA_KT, (min(q0 + FA_QB, n) + FA_KT - 1) / FA_KT);
     for (int kt = 0; kt < nkt; ++kt) {
         const int k0 = kt * FA_KT;
         __syncthreads();
-        fa_stage<DK, IOT, true, false>(Ks, nullptr, kp, a.k.sn, k0, N, 1.f, tid);
-        fa_stage<DK, IOT, true, false>(Vs, nullptr, vp, a.v.sn, k0, N, 1.f, tid);
-        if (DUAL) fa_stage<DK, IOT, true, false>(K2s, nullptr, k2p, a.k2.sn, k0, N, 1.f, tid);
+        fa_stage<DK, IOT, true, false>(Ks, nullptr, kp, a.k.sn, k0, n, 1.f, tid);
+        fa_stage<DK, IOT, true, false>(Vs, nullptr, vp, a.v.sn, k0, n, 1.f, tid);
+        if (DUAL) fa_stage<DK, IOT, true, false>(K2s, nullptr, k2p, a.k2.sn, k0, n, 1.f, tid);
         __syncthreads();
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
@@ -268,7 +313,7 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_rowsum_kernel(MopkQuartetArg
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
                 const int j = k0 + 32 * hf + tile_row(g, h);
-                if (qok && j < N && j <= qi) {
+                if (qin && j < n && j <= qi) {
                     float z1, z2;
                     const float lg = qt_logit<DUAL>(S1[g], S2[g], n1, n2, qs, z1, z2) + qt_am<AM>(a, amp, qi, j);
                     const float dpd = drop.thresh ? (fa_drop_keep(drop, rowh, j) ? dP[g] * drop.inv_keep : 0.f) : dP[g];
@@ -298,6 +343,9 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_rowsum_kernel(MopkQuartetArg
     }
 }
 // per (b,h): fixed-order sum of the block partials; dmixture carries sigmoid'(mixture)
+#ifdef MOPK_QUARTET_LENS
+namespace {       // the lengths unit launches a copy of its own: the symbol belongs to the plain unit
+#endif
 __global__ void qt_scalar_sum_kernel(const float *spart, int nblk, int nbh, const float *mixture, float *dmix, float *dqs) {
     const int bh = blockIdx.x * blockDim.x + threadIdx.x;
     if (bh >= nbh) return;
@@ -306,6 +354,9 @@ __global__ void qt_scalar_sum_kernel(const float *spart, int nblk, int nbh, cons
     const float m = 1.f / (1.f + __expf(-*mixture));
     dmix[bh] = x * m * (1.f - m); dqs[bh] = y;
 }
+#ifdef MOPK_QUARTET_LENS
+}  // namespace
+#endif
 
 // gradient of one z-normalised map at one element: dense row correction included
 __device__ __forceinline__ float qt_dscore(float dz, float s, const QtNorm &n) {
@@ -313,9 +364,10 @@ __device__ __forceinline__ float qt_dscore(float dz, float s, const QtNorm &n) {
 }
 
 // dQ (and dQ2): per query block over ALL key tiles (the z-norm correction is dense)
-template <int DK, typename IOT, bool DUAL, bool AM>
-__global__ void __launch_bounds__(FA_NW * 64, 2) qt_dq_kernel(MopkQuartetArgs a, const float *stats, const float *lse, const float *delta,
+template <int DK, typename IOT, bool DUAL, bool AM, bool LENS = false>
+__global__ void __launch_bounds__(FA_NW * 64, 2) qt_dq_kernel(QtArgs<LENS> al, const float *stats, const float *lse, const float *delta,
                                                            const float *rows) {
+    const MopkQuartetArgs &a = qt_base(al);
     constexpr int DT = DK / 32, LDK = DK + 8;
     __shared__ __attribute__((aligned(16))) unsigned short Ks[FA_KT * LDK], Vs[FA_KT * LDK], Kt[DK * FA_LDT];
     __shared__ __attribute__((aligned(16))) unsigned short K2s[DUAL ? FA_KT * LDK : 8], K2t[DUAL ? DK * FA_LDT : 8];
@@ -326,33 +378,42 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_dq_kernel(MopkQuartetArgs a,
     const int b = bh / a.H, hh = bh % a.H;
     const int q0 = qb * FA_QB, qi = q0 + 32 * w + r;
     const bool qok = qi < N;
+    const int n = qt_len(al, b);                     // as in the forward
+    const bool qin = LENS ? qi < n : qok;
     const float sc = rsqrtf((float)DK);
     const QtScal qs = qt_scal<DUAL>(a);
     const float *amp = AM ? a.add_mask + b * a.am_sb + hh * a.am_sh : nullptr;
     bf16x8 qe[DK / 16], q2e[DUAL ? DK / 16 : 1], dof[DK / 16];
-    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qok, h, sc);
-    fa_frags<DK, IOT>(dof, (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh + (int64_t)qi * a.dy.sn, qok, h, 1.f);
+    fa_frags<DK, IOT>(qe, (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh + (int64_t)qi * a.q.sn, qin, h, sc);
+    fa_frags<DK, IOT>(dof, (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh + (int64_t)qi * a.dy.sn, qin, h, 1.f);
     const IOT *kp = (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh, *vp = (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh, *k2p = nullptr;
     if (DUAL) {
-        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)a.q2.ptr + b * a.q2.sb + hh * a.q2.sh + (int64_t)qi * a.q2.sn, qok, h, sc);
+        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & q2e, (const IOT *)a.q2.ptr + b * a.q2.sb + hh * a.q2.sh + (int64_t)qi * a.q2.sn, qin, h, sc);
         k2p = (const IOT *)a.k2.ptr + b * a.k2.sb + hh * a.k2.sh;
     }
-    const float4 st = qok ? ((const float4 *)stats)[(int64_t)bh * N + qi] : make_float4(0.f, 1.f, 0.f, 1.f);
-    const float4 rw = qok ? ((const float4 *)rows)[(int64_t)bh * N + qi] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const QtNorm n1 = qt_norm(st.x, st.y, qs.eps1, N, rw.x, rw.y), n2 = qt_norm(st.z, st.w, qs.eps2, N, rw.z, rw.w);
-    const float Li = qok ? lse[(int64_t)bh * N + qi] : 0.f, di = qok ? delta[(int64_t)bh * N + qi] : 0.f;
+    const float4 st = qin ? ((const float4 *)stats)[(int64_t)bh * N + qi] : make_float4(0.f, 1.f, 0.f, 1.f);
+    const float4 rw = qin ? ((const float4 *)rows)[(int64_t)bh * N + qi] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const QtNorm n1 = qt_norm(st.x, st.y, qs.eps1, n, rw.x, rw.y), n2 = qt_norm(st.z, st.w, qs.eps2, n, rw.z, rw.w);
+    const float Li = qin ? lse[(int64_t)bh * N + qi] : 0.f, di = qin ? delta[(int64_t)bh * N + qi] : 0.f;
     const FaDrop drop = fa_drop(a.dropout_p, a.dropout_seed);
     const uint32_t rowh = fa_drop_row(drop, bh, qi);
     f32x16 dQ[DT], dQ2[DUAL ? DT : 1];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) { dQ[dt] = fa_zero(); if (DUAL) dQ2[dt] = fa_zero(); }
-    const int nkt = (N + FA_KT - 1) / FA_KT;
+    if (LENS && q0 >= n) {                           // workgroup-uniform: only padding queries -- dq = dq2 = 0 are written
+        if (qok) {
+            fa_store_rows<DK, IOT>((IOT *)a.dq.ptr + b * a.dq.sb + hh * a.dq.sh + (int64_t)qi * a.dq.sn, dQ, h, 0.f);
+            if (DUAL) fa_store_rows<DK, IOT>((IOT *)a.dq2.ptr + b * a.dq2.sb + hh * a.dq2.sh + (int64_t)qi * a.dq2.sn, *(const f32x16(*)[DT]) & dQ2, h, 0.f);
+        }
+        return;
+    }
+    const int nkt = (n + FA_KT - 1) / FA_KT;
     for (int kt = 0; kt < nkt; ++kt) {
         const int k0 = kt * FA_KT;
         __syncthreads();
-        fa_stage<DK, IOT, true, true>(Ks, Kt, kp, a.k.sn, k0, N, 1.f, tid);
-        fa_stage<DK, IOT, true, false>(Vs, nullptr, vp, a.v.sn, k0, N, 1.f, tid);
-        if (DUAL) fa_stage<DK, IOT, true, true>(K2s, K2t, k2p, a.k2.sn, k0, N, 1.f, tid);
+        fa_stage<DK, IOT, true, true>(Ks, Kt, kp, a.k.sn, k0, n, 1.f, tid);
+        fa_stage<DK, IOT, true, false>(Vs, nullptr, vp, a.v.sn, k0, n, 1.f, tid);
+        if (DUAL) fa_stage<DK, IOT, true, true>(K2s, K2t, k2p, a.k2.sn, k0, n, 1.f, tid);
         __syncthreads();
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
@@ -372,7 +433,7 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_dq_kernel(MopkQuartetArgs a,
                     dz1 = DUAL ? dsc * ((1.f - qs.m) + qs.mq * z2) : dsc;
                     dz2 = dsc * qs.mq * z1;
                 }
-                const bool ok = qok && j < N;
+                const bool ok = qin && j < n;
                 g1[g] = ok ? qt_dscore(dz1, S1[g], n1) * sc : 0.f;
                 g2[g] = (DUAL && ok) ? qt_dscore(dz2, S2[g], n2) * sc : 0.f;
             }
@@ -389,9 +450,10 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_dq_kernel(MopkQuartetArgs a,
 }
 
 // dK, dK2, dV: per key block (lane = key) over ALL query tiles
-template <int DK, typename IOT, bool DUAL, bool AM>
-__global__ void __launch_bounds__(FA_NW * 64, 2) qt_dkv_kernel(MopkQuartetArgs a, const float *stats, const float *lse, const float *delta,
+template <int DK, typename IOT, bool DUAL, bool AM, bool LENS = false>
+__global__ void __launch_bounds__(FA_NW * 64, 2) qt_dkv_kernel(QtArgs<LENS> al, const float *stats, const float *lse, const float *delta,
                                                             const float *rows) {
+    const MopkQuartetArgs &a = qt_base(al);
     constexpr int DT = DK / 32, LDK = DK + 8;
     __shared__ __attribute__((aligned(16))) unsigned short Qs[FA_KT * LDK], Gs[FA_KT * LDK], Qt[DK * FA_LDT], Gt[DK * FA_LDT];
     __shared__ __attribute__((aligned(16))) unsigned short Q2s[DUAL ? FA_KT * LDK : 8], Q2t[DUAL ? DK * FA_LDT : 8];
@@ -404,35 +466,45 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_dkv_kernel(MopkQuartetArgs a
     const int b = bh / a.H, hh = bh % a.H;
     const int k0 = kb * FA_QB, kj = k0 + 32 * w + r;
     const bool kok = kj < N;
+    const int n = qt_len(al, b);                     // LENS: the real tokens of this row; kin = this lane's key is one of them
+    const bool kin = LENS ? kj < n : kok;
     const float sc = rsqrtf((float)DK);
     const QtScal qs = qt_scal<DUAL>(a);
     const float *amp = AM ? a.add_mask + b * a.am_sb + hh * a.am_sh : nullptr;
     const IOT *qp = (const IOT *)a.q.ptr + b * a.q.sb + hh * a.q.sh, *gp = (const IOT *)a.dy.ptr + b * a.dy.sb + hh * a.dy.sh, *q2p = nullptr;
     bf16x8 kf[DK / 16], vf[DK / 16], k2f[DUAL ? DK / 16 : 1];
-    fa_frags<DK, IOT>(kf, (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh + (int64_t)kj * a.k.sn, kok, h, 1.f);
-    fa_frags<DK, IOT>(vf, (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh + (int64_t)kj * a.v.sn, kok, h, 1.f);
+    fa_frags<DK, IOT>(kf, (const IOT *)a.k.ptr + b * a.k.sb + hh * a.k.sh + (int64_t)kj * a.k.sn, kin, h, 1.f);
+    fa_frags<DK, IOT>(vf, (const IOT *)a.v.ptr + b * a.v.sb + hh * a.v.sh + (int64_t)kj * a.v.sn, kin, h, 1.f);
     if (DUAL) {
-        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & k2f, (const IOT *)a.k2.ptr + b * a.k2.sb + hh * a.k2.sh + (int64_t)kj * a.k2.sn, kok, h, 1.f);
+        fa_frags<DK, IOT>(*(bf16x8(*)[DK / 16]) & k2f, (const IOT *)a.k2.ptr + b * a.k2.sb + hh * a.k2.sh + (int64_t)kj * a.k2.sn, kin, h, 1.f);
         q2p = (const IOT *)a.q2.ptr + b * a.q2.sb + hh * a.q2.sh;
     }
     f32x16 dK[DT], dV[DT], dK2[DUAL ? DT : 1];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) { dK[dt] = fa_zero(); dV[dt] = fa_zero(); if (DUAL) dK2[dt] = fa_zero(); }
     const FaDrop drop = fa_drop(a.dropout_p, a.dropout_seed);
-    const int nqt = (N + FA_KT - 1) / FA_KT;
+    if (LENS && k0 >= n) {                           // workgroup-uniform: only padding keys -- dk = dk2 = dv = 0 are written
+        if (kok) {
+            fa_store_rows<DK, IOT>((IOT *)a.dk_.ptr + b * a.dk_.sb + hh * a.dk_.sh + (int64_t)kj * a.dk_.sn, dK, h, 0.f);
+            fa_store_rows<DK, IOT>((IOT *)a.dv.ptr + b * a.dv.sb + hh * a.dv.sh + (int64_t)kj * a.dv.sn, dV, h, 0.f);
+            if (DUAL) fa_store_rows<DK, IOT>((IOT *)a.dk2.ptr + b * a.dk2.sb + hh * a.dk2.sh + (int64_t)kj * a.dk2.sn, *(const f32x16(*)[DT]) & dK2, h, 0.f);
+        }
+        return;
+    }
+    const int nqt = (n + FA_KT - 1) / FA_KT;
     for (int qt = 0; qt < nqt; ++qt) {
         const int i0 = qt * FA_KT;
         __syncthreads();
-        fa_stage<DK, IOT, true, true>(Qs, Qt, qp, a.q.sn, i0, N, sc, tid);        // q / sqrt(dk), rounded as in the forward
-        fa_stage<DK, IOT, true, true>(Gs, Gt, gp, a.dy.sn, i0, N, 1.f, tid);
-        if (DUAL) fa_stage<DK, IOT, true, true>(Q2s, Q2t, q2p, a.q2.sn, i0, N, sc, tid);
+        fa_stage<DK, IOT, true, true>(Qs, Qt, qp, a.q.sn, i0, n, sc, tid);        // q / sqrt(dk), rounded as in the forward
+        fa_stage<DK, IOT, true, true>(Gs, Gt, gp, a.dy.sn, i0, n, 1.f, tid);
+        if (DUAL) fa_stage<DK, IOT, true, true>(Q2s, Q2t, q2p, a.q2.sn, i0, n, sc, tid);
         if (tid < FA_KT) {
             const int i = i0 + tid;
             float4 st = make_float4(0.f, 1.f, 0.f, 1.f), rw = make_float4(0.f, 0.f, 0.f, 0.f);
             float L = 0.f, dl = 0.f;
-            if (i < N) { st = ((const float4 *)stats)[(int64_t)bh * N + i]; rw = ((const float4 *)rows)[(int64_t)bh * N + i];
+            if (i < n) { st = ((const float4 *)stats)[(int64_t)bh * N + i]; rw = ((const float4 *)rows)[(int64_t)bh * N + i];
                          L = lse[(int64_t)bh * N + i]; dl = delta[(int64_t)bh * N + i]; }
-            const QtNorm n1 = qt_norm(st.x, st.y, qs.eps1, N, rw.x, rw.y), n2 = qt_norm(st.z, st.w, qs.eps2, N, rw.z, rw.w);
+            const QtNorm n1 = qt_norm(st.x, st.y, qs.eps1, n, rw.x, rw.y), n2 = qt_norm(st.z, st.w, qs.eps2, n, rw.z, rw.w);
             Rs[tid][0] = make_float4(n1.mu, n1.inv, n1.cc, n1.am);
             Rs[tid][1] = make_float4(n1.bs, n2.mu, n2.inv, n2.cc);
             Rs[tid][2] = make_float4(n2.am, n2.bs, L, dl);
@@ -454,7 +526,7 @@ __global__ void __launch_bounds__(FA_NW * 64, 2) qt_dkv_kernel(MopkQuartetArgs a
                 const QtNorm n1{ra.x, ra.y, ra.z, ra.w, rb.x}, n2{rb.y, rb.z, rb.w, rc.x, rc.y};
                 float z1, z2, dz1 = 0.f, dz2 = 0.f, p = 0.f;
                 const float lg = qt_logit<DUAL>(S1[g], S2[g], n1, n2, qs, z1, z2) + qt_am<AM>(a, amp, i, kj);
-                const bool ok = kok && i < N;
+                const bool ok = kin && i < n;
                 if (ok && kj <= i) {
                     p = __builtin_amdgcn_exp2f(lg * FA_LOG2E - rc.z);
                     float dpd = dP[g], pk = 1.f;
@@ -496,6 +568,7 @@ QtBufs qt_carve_flash(void *saved, void *ws, const MopkQuartetArgs *a) {
 }
 }  // namespace
 
+#ifndef MOPK_QUARTET_LENS
 int qt_flash_supported(const MopkQuartetArgs *a, bool bwd) {
     if (a->precision != MOPK_PREC_BF16) return 0;
     if (a->attn) return 0;                                         // returned attention weights: generic path
@@ -511,6 +584,9 @@ int qt_flash_supported(const MopkQuartetArgs *a, bool bwd) {
 }
 size_t qt_flash_saved_bytes(const MopkQuartetArgs *a) { return qt_carve_flash(nullptr, nullptr, a).nsaved + 256; }
 size_t qt_flash_ws_bytes(const MopkQuartetArgs *a) { return qt_carve_flash(nullptr, nullptr, a).nwork + 256; }
+#else
+int qt_flash_supported(const MopkQuartetArgs *a, bool bwd);
+#endif
 
 #define QT_LAUNCH_T(KERNEL, DK_, IOT_, GRID, ...)                                                                \
     do { if (a->use_quartet) hipLaunchKernelGGL((KERNEL<DK_, IOT_, true>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__);      \
@@ -529,6 +605,7 @@ size_t qt_flash_ws_bytes(const MopkQuartetArgs *a) { return qt_carve_flash(nullp
 #define QT_LAUNCH(KERNEL, GRID, ...) QT_DISPATCH(QT_LAUNCH_TA, KERNEL, GRID, __VA_ARGS__)
 #define QT_LAUNCH_STATS(KERNEL, GRID, ...) QT_DISPATCH(QT_LAUNCH_T, KERNEL, GRID, __VA_ARGS__)
 
+#ifndef MOPK_QUARTET_LENS
 int qt_flash_fwd(const MopkQuartetArgs *a, hipStream_t st) {
     if (!qt_flash_supported(a, false)) return MOPK_ERR_UNSUPPORTED;
     const QtBufs b = qt_carve_flash(a->saved, a->workspace, a);
@@ -554,5 +631,44 @@ int qt_flash_bwd(const MopkQuartetArgs *a, hipStream_t st) {
     QT_LAUNCH(qt_dkv_kernel, grid, *a, (const float *)b.stats, (const float *)b.lse, (const float *)b.delta, (const float *)b.rows);
     return launch_status();
 }
+#else   // MOPK_QUARTET_LENS: the unit of the LENS = true instantiations (no additive mask: AM = false only)
+#define QT_LENS_T(KERNEL, DK_, IOT_, GRID, ...)                                                                  \
+    do { if (a->use_quartet) hipLaunchKernelGGL((KERNEL<DK_, IOT_, true, true>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__);      \
+         else hipLaunchKernelGGL((KERNEL<DK_, IOT_, false, true>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__); } while (0)
+#define QT_LENS_TA(KERNEL, DK_, IOT_, GRID, ...)                                                                 \
+    do { if (a->use_quartet) hipLaunchKernelGGL((KERNEL<DK_, IOT_, true, false, true>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__);   \
+         else hipLaunchKernelGGL((KERNEL<DK_, IOT_, false, false, true>), GRID, dim3(FA_NW * 64), 0, st, __VA_ARGS__); } while (0)
+#define QT_LENS(KERNEL, GRID, ...) QT_DISPATCH(QT_LENS_TA, KERNEL, GRID, __VA_ARGS__)
+#define QT_LENS_STATS(KERNEL, GRID, ...) QT_DISPATCH(QT_LENS_T, KERNEL, GRID, __VA_ARGS__)
+
+int qt_flash_lens_fwd(const MopkQuartetArgs *a, const int32_t *lens, hipStream_t st) {
+    if (!qt_flash_supported(a, false) || a->add_mask) return MOPK_ERR_UNSUPPORTED;
+    const QtBufs b = qt_carve_flash(a->saved, a->workspace, a);
+    const int nq = (a->T + FA_QB - 1) / FA_QB;
+    const dim3 grid(nq * a->B * a->H);
+    const MopkQuartetLensArgs l{*a, lens};
+    QT_LENS_STATS(qt_stats_kernel, grid, l, b.stats);
+    QT_LENS(qt_fwd_kernel, grid, l, (const float *)b.stats, b.lse);
+    return launch_status();
+}
+int qt_flash_lens_bwd(const MopkQuartetArgs *a, const int32_t *lens, hipStream_t st) {
+    if (!qt_flash_supported(a, true) || a->add_mask) return MOPK_ERR_UNSUPPORTED;
+    const QtBufs b = qt_carve_flash(a->saved, a->workspace, a);
+    const int64_t rows = (int64_t)a->B * a->H * a->T;
+    // delta of a padding row is dy . 0 (whatever dy holds there): never read by the LENS kernels
+    if (a->io_dtype == MOPK_BF16) hipLaunchKernelGGL((qt_delta_kernel<unsigned short>), dim3((rows + 3) / 4), dim3(256), 0, st, *a, b.delta);
+    else hipLaunchKernelGGL((qt_delta_kernel<float>), dim3((rows + 3) / 4), dim3(256), 0, st, *a, b.delta);
+    const int nq = (a->T + FA_QB - 1) / FA_QB;
+    const dim3 grid(nq * a->B * a->H);
+    const MopkQuartetLensArgs l{*a, lens};
+    QT_LENS(qt_rowsum_kernel, grid, l, (const float *)b.stats, (const float *)b.lse, (const float *)b.delta, b.rows, b.spart);
+    if (a->use_quartet)
+        hipLaunchKernelGGL(qt_scalar_sum_kernel, dim3((a->B * a->H + 63) / 64), dim3(64), 0, st, (const float *)b.spart, nq, a->B * a->H,
+                           a->mixture, a->dmixture_part, a->dqscale_part);
+    QT_LENS(qt_dq_kernel, grid, l, (const float *)b.stats, (const float *)b.lse, (const float *)b.delta, (const float *)b.rows);
+    QT_LENS(qt_dkv_kernel, grid, l, (const float *)b.stats, (const float *)b.lse, (const float *)b.delta, (const float *)b.rows);
+    return launch_status();
+}
+#endif  // MOPK_QUARTET_LENS
 
 }  // namespace mopk

@@ -10,7 +10,13 @@
 // workgroup du partials go to the workspace and a second launch sums them in a fixed order (no atomics: bitwise reproducible).
 // Algorithmic traffic: forward B*T*D*(sizeof x + sizeof a + sizeof out), backward B*T*D*(dout + x + a + dr) plus the halo rows
 // (2 per tile) and the du partials.  Static LDS only (< 3 KB forward, < 17 KB backward): nothing to set before a graph capture.
+//
+// Per-row lengths (LENS = true, mopk_token_gate_lens_*): right-padded rows, n_b = clamp(lens[b], 0, T).  r_t counts as 0 for
+// t >= n_b: "t < n_b" replaces "t < T" for every load, halo included, so gate_{n_b - 1} has no u2 term; rows t >= n_b are never
+// read and get out = 0, gate = 1, dr = 0 written, and add nothing to du.  Full lengths run the instructions of LENS = false on the
+// same operands (bitwise equal, du included).  The LENS = true instantiations are a unit of their own (-DMOPK_TOKEN_GATE_LENS).
 #include "common.h"
+#include <type_traits>
 
 namespace mopk {
 namespace {
@@ -21,6 +27,16 @@ constexpr int TG_TILE = TG_WAVES * TG_TPW;       // tokens per tile (16)
 constexpr int TG_MAX_VPL = 2;                    // 8-element chunks per lane: D <= 64 * 8 * 2 = 1024
 constexpr int TG_MAX_PARTS = 512;                // backward workgroups (du partial rows)
 
+// the kernels' argument struct: MopkTokenGateArgs itself, or (LENS) the struct that wraps it with the lengths
+template <bool LENS> using TgArgs = std::conditional_t<LENS, MopkTokenGateLensArgs, MopkTokenGateArgs>;
+__host__ __device__ __forceinline__ const MopkTokenGateArgs &tg_base(const MopkTokenGateArgs &a) { return a; }
+__host__ __device__ __forceinline__ const MopkTokenGateArgs &tg_base(const MopkTokenGateLensArgs &a) { return a.base; }
+__device__ __forceinline__ int tg_len(const MopkTokenGateArgs &a, int) { return a.T; }
+__device__ __forceinline__ int tg_len(const MopkTokenGateLensArgs &a, int b) {      // b is workgroup-uniform: a scalar load
+    if (!a.lens) return a.base.T;
+    const int n = a.lens[b];
+    return n < 0 ? 0 : (n > a.base.T ? a.base.T : n);
+}
 template <typename T> __device__ __forceinline__ void tg_ld8(const T *p, float (&v)[8]);
 template <> __device__ __forceinline__ void tg_ld8<float>(const float *p, float (&v)[8]) {
     const float4 a = *(const float4 *)p, b = *(const float4 *)(p + 4);
@@ -39,6 +55,16 @@ template <> __device__ __forceinline__ void tg_st8<float>(float *p, const float 
 }
 template <> __device__ __forceinline__ void tg_st8<unsigned short>(unsigned short *p, const float (&v)[8]) {
     *(uint4 *)p = make_uint4(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7]));
+}
+// zeros for the chunks this lane owns of one (D) output row
+template <typename OT, int VPL>
+__device__ __forceinline__ void tg_store_zero(OT *op, int lane, int nvec) {
+    const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nvec) tg_st8<OT>(op + 8 * c, z);
+    }
 }
 
 // r[i] = x + a for the chunks this lane owns (zeros past D)
@@ -99,12 +125,14 @@ __device__ __forceinline__ void tg_load_u(const float *u, int lane, int nvec, in
 }
 
 // gate_t = 1 + u0.r_{t-1} + u1.r_t + u2.r_{t+1} ; out_t = r_t gate_t
-template <typename XT, typename AT, typename OT, int VPL>
-__global__ __launch_bounds__(TG_WAVES * 64) void tg_fwd_kernel(MopkTokenGateArgs a) {
+template <typename XT, typename AT, typename OT, int VPL, bool LENS = false>
+__global__ __launch_bounds__(TG_WAVES * 64) void tg_fwd_kernel(TgArgs<LENS> al) {
+    const MopkTokenGateArgs &a = tg_base(al);
     __shared__ float q[TG_TILE + 2][4];          // slot j = token t0 - 1 + j: (u0.r, u1.r, u2.r)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int tiles = (a.T + TG_TILE - 1) / TG_TILE;
     const int b = blockIdx.x / tiles, t0 = (blockIdx.x % tiles) * TG_TILE;
+    const int n = tg_len(al, b);                 // LENS: the real tokens of this row; else T
     const int nvec = a.D >> 3;
     float uu[3][VPL][8];
     tg_load_u<VPL>(a.u, lane, nvec, a.D, uu);
@@ -113,7 +141,7 @@ __global__ __launch_bounds__(TG_WAVES * 64) void tg_fwd_kernel(MopkTokenGateArgs
     for (int j = 0; j < TG_TPW; ++j) {
         const int slot = 1 + w * TG_TPW + j, t = t0 + slot - 1;
         float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-        if (t < a.T) {
+        if (t < n) {
             tg_load_r<XT, AT, VPL>(a, b, t, lane, r[j]);
             d0 = tg_dot<VPL>(r[j], uu[0]); d1 = tg_dot<VPL>(r[j], uu[1]); d2 = tg_dot<VPL>(r[j], uu[2]);
         }
@@ -122,7 +150,7 @@ __global__ __launch_bounds__(TG_WAVES * 64) void tg_fwd_kernel(MopkTokenGateArgs
     if (w < 2) {                                 // halo: wave 0 the token before the tile (its u0 term), wave 1 the one after (u2)
         const int slot = w ? TG_TILE + 1 : 0, t = t0 + slot - 1;
         float d = 0.f;
-        if (t >= 0 && t < a.T) {
+        if (t >= 0 && t < n) {
             float h[VPL][8];
             tg_load_r<XT, AT, VPL>(a, b, t, lane, h);
             d = tg_dot<VPL>(h, w ? uu[2] : uu[0]);
@@ -134,6 +162,11 @@ __global__ __launch_bounds__(TG_WAVES * 64) void tg_fwd_kernel(MopkTokenGateArgs
     for (int j = 0; j < TG_TPW; ++j) {
         const int slot = 1 + w * TG_TPW + j, t = t0 + slot - 1;
         if (t >= a.T) continue;
+        if (LENS && t >= n) {                    // a padding row: out = 0, gate = 1 (wave-uniform)
+            if (lane == 0) a.gate[(int64_t)b * a.T + t] = 1.f;
+            tg_store_zero<OT, VPL>((OT *)a.out + ((int64_t)b * a.T + t) * a.D, lane, nvec);
+            continue;
+        }
         const float g = 1.f + q[slot - 1][0] + q[slot][1] + q[slot + 1][2];
         const int64_t row = (int64_t)b * a.T + t;
         if (lane == 0) a.gate[row] = g;
@@ -152,8 +185,9 @@ __global__ __launch_bounds__(TG_WAVES * 64) void tg_fwd_kernel(MopkTokenGateArgs
 }
 
 // dr_t = dout_t gate_t + u0 delta_{t+1} + u1 delta_t + u2 delta_{t-1} ;  du_s += delta_{t+1-s} r_t   (s = 0, 1, 2)
-template <typename XT, typename AT, typename OT, int VPL>
-__global__ __launch_bounds__(TG_WAVES * 64) void tg_bwd_kernel(MopkTokenGateArgs a, float *part) {
+template <typename XT, typename AT, typename OT, int VPL, bool LENS = false>
+__global__ __launch_bounds__(TG_WAVES * 64) void tg_bwd_kernel(TgArgs<LENS> al, float *part) {
+    const MopkTokenGateArgs &a = tg_base(al);
     __shared__ float dl[TG_TILE + 2];
     __shared__ float red[TG_WAVES][64 * 8];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -170,12 +204,13 @@ __global__ __launch_bounds__(TG_WAVES * 64) void tg_bwd_kernel(MopkTokenGateArgs
             for (int e = 0; e < 8; ++e) du[s][i][e] = 0.f;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int b = tile / tiles, t0 = (tile % tiles) * TG_TILE;
+        const int n = tg_len(al, b);
         float r[TG_TPW][VPL][8], go[TG_TPW][VPL][8];
 #pragma unroll
         for (int j = 0; j < TG_TPW; ++j) {
             const int slot = 1 + w * TG_TPW + j, t = t0 + slot - 1;
             float d = 0.f;
-            if (t < a.T) {
+            if (t < n) {
                 tg_load_r<XT, AT, VPL>(a, b, t, lane, r[j]);
                 tg_load_o<OT, VPL>((const OT *)a.dout + ((int64_t)b * a.T + t) * a.D, lane, nvec, go[j]);
                 d = tg_dot<VPL>(r[j], go[j]);
@@ -185,7 +220,7 @@ __global__ __launch_bounds__(TG_WAVES * 64) void tg_bwd_kernel(MopkTokenGateArgs
         if (w < 2) {
             const int slot = w ? TG_TILE + 1 : 0, t = t0 + slot - 1;
             float d = 0.f;
-            if (t >= 0 && t < a.T) {
+            if (t >= 0 && t < n) {
                 float h[VPL][8], g[VPL][8];
                 tg_load_r<XT, AT, VPL>(a, b, t, lane, h);
                 tg_load_o<OT, VPL>((const OT *)a.dout + ((int64_t)b * a.T + t) * a.D, lane, nvec, g);
@@ -199,8 +234,9 @@ __global__ __launch_bounds__(TG_WAVES * 64) void tg_bwd_kernel(MopkTokenGateArgs
             const int slot = 1 + w * TG_TPW + j, t = t0 + slot - 1;
             if (t >= a.T) continue;
             const int64_t row = (int64_t)b * a.T + t;
-            const float g = a.gate[row], dn = dl[slot + 1], dc = dl[slot], dp = dl[slot - 1];
             OT *op = (OT *)a.dr + row * a.D;
+            if (LENS && t >= n) { tg_store_zero<OT, VPL>(op, lane, nvec); continue; }       // a padding row: dr = 0, nothing for du
+            const float g = a.gate[row], dn = dl[slot + 1], dc = dl[slot], dp = dl[slot - 1];
 #pragma unroll
             for (int i = 0; i < VPL; ++i) {
                 const int c = lane + 64 * i;
@@ -279,26 +315,36 @@ int tg_parts(const MopkTokenGateArgs *a) {
     return (int)(tiles < TG_MAX_PARTS ? tiles : TG_MAX_PARTS);
 }
 
-template <typename XT, typename AT, typename OT>
-void tg_launch(const MopkTokenGateArgs *a, bool bwd, hipStream_t st) {
+template <typename XT, typename AT, typename OT, bool LENS>
+void tg_launch(const TgArgs<LENS> *al, bool bwd, hipStream_t st) {
+    const MopkTokenGateArgs *a = &tg_base(*al);
     const int vpl = (a->D / 8 + 63) / 64;
     const dim3 block(TG_WAVES * 64);
     const unsigned fwd_grid = (unsigned)(a->B * ((a->T + TG_TILE - 1) / TG_TILE));
 #define MOPK_TG(V_) do {                                                                                                       \
-        if (!bwd) hipLaunchKernelGGL((tg_fwd_kernel<XT, AT, OT, V_>), dim3(fwd_grid), block, 0, st, *a);                    \
-        else hipLaunchKernelGGL((tg_bwd_kernel<XT, AT, OT, V_>), dim3(tg_parts(a)), block, 0, st, *a, (float *)a->workspace); \
+        if (!bwd) hipLaunchKernelGGL((tg_fwd_kernel<XT, AT, OT, V_, LENS>), dim3(fwd_grid), block, 0, st, *al);                    \
+        else hipLaunchKernelGGL((tg_bwd_kernel<XT, AT, OT, V_, LENS>), dim3(tg_parts(a)), block, 0, st, *al, (float *)a->workspace); \
     } while (0)
     if (vpl == 1) MOPK_TG(1); else MOPK_TG(2);
 #undef MOPK_TG
 }
 
-void tg_dispatch(const MopkTokenGateArgs *a, bool bwd, hipStream_t st) {
+template <bool LENS>
+void tg_dispatch(const TgArgs<LENS> *al, bool bwd, hipStream_t st) {
+    const MopkTokenGateArgs *a = &tg_base(*al);
     const bool xb = a->x_dtype == MOPK_BF16;
     const bool ab = a->a ? a->a_dtype == MOPK_BF16 : xb;         // no branch: AT is never read, instantiate as x's type
-    if (xb && ab) tg_launch<unsigned short, unsigned short, unsigned short>(a, bwd, st);
-    else if (xb) tg_launch<unsigned short, float, float>(a, bwd, st);
-    else if (ab) tg_launch<float, unsigned short, float>(a, bwd, st);
-    else tg_launch<float, float, float>(a, bwd, st);
+    if (xb && ab) tg_launch<unsigned short, unsigned short, unsigned short, LENS>(al, bwd, st);
+    else if (xb) tg_launch<unsigned short, float, float, LENS>(al, bwd, st);
+    else if (ab) tg_launch<float, unsigned short, float, LENS>(al, bwd, st);
+    else tg_launch<float, float, float, LENS>(al, bwd, st);
+}
+
+// the reduction launch that ends either backward
+int tg_reduce(const MopkTokenGateArgs *a, hipStream_t st) {
+    const int n = 3 * a->D;
+    hipLaunchKernelGGL(tg_reduce_kernel, dim3((n + 63) / 64), dim3(1024), 0, st, (const float *)a->workspace, tg_parts(a), n, a->du);
+    return launch_status();
 }
 
 }  // namespace
@@ -308,6 +354,7 @@ using namespace mopk;
 
 extern "C" {
 
+#ifndef MOPK_TOKEN_GATE_LENS
 int mopk_token_gate_supported(const MopkTokenGateArgs *a) { return tg_check(a) == MOPK_OK; }
 
 size_t mopk_token_gate_workspace_bytes(const MopkTokenGateArgs *a) {
@@ -319,7 +366,7 @@ int mopk_token_gate_fwd(const MopkTokenGateArgs *a, void *stream) {
     const int rc = tg_check(a);
     if (rc != MOPK_OK) return rc;
     if (any_null(a->x, a->u, a->out, a->gate)) return MOPK_ERR_BAD_ARG;
-    tg_dispatch(a, false, (hipStream_t)stream);
+    tg_dispatch<false>(a, false, (hipStream_t)stream);
     return launch_status();
 }
 
@@ -327,11 +374,40 @@ int mopk_token_gate_bwd(const MopkTokenGateArgs *a, void *stream) {
     const int rc = tg_check(a);
     if (rc != MOPK_OK) return rc;
     if (any_null(a->x, a->u, a->gate, a->dout, a->dr, a->du, a->workspace)) return MOPK_ERR_BAD_ARG;
-    tg_dispatch(a, true, (hipStream_t)stream);
-    const int n = 3 * a->D;
-    hipLaunchKernelGGL(tg_reduce_kernel, dim3((n + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float *)a->workspace,
-                       tg_parts(a), n, a->du);
+    tg_dispatch<false>(a, true, (hipStream_t)stream);
+    return tg_reduce(a, (hipStream_t)stream);
+}
+#else   // MOPK_TOKEN_GATE_LENS: the unit of the LENS = true instantiations; checks and sizes are those of base
+static int tg_lens_check(const MopkTokenGateLensArgs *l) {
+    if (!l) return MOPK_ERR_BAD_ARG;
+    const int rc = tg_check(&l->base);
+    if (rc != MOPK_OK) return rc;
+    return misaligned(3, l->lens) ? MOPK_ERR_UNSUPPORTED : MOPK_OK;
+}
+int mopk_token_gate_lens_supported(const MopkTokenGateLensArgs *l) { return tg_lens_check(l) == MOPK_OK; }
+
+size_t mopk_token_gate_lens_workspace_bytes(const MopkTokenGateLensArgs *l) {
+    if (!l || l->base.B <= 0 || l->base.T <= 0 || l->base.D <= 0) return 0;
+    return (size_t)tg_parts(&l->base) * 3 * l->base.D * sizeof(float);
+}
+
+int mopk_token_gate_lens_fwd(const MopkTokenGateLensArgs *l, void *stream) {
+    const int rc = tg_lens_check(l);
+    if (rc != MOPK_OK) return rc;
+    const MopkTokenGateArgs *a = &l->base;
+    if (any_null(a->x, a->u, a->out, a->gate)) return MOPK_ERR_BAD_ARG;
+    tg_dispatch<true>(l, false, (hipStream_t)stream);
     return launch_status();
 }
+
+int mopk_token_gate_lens_bwd(const MopkTokenGateLensArgs *l, void *stream) {
+    const int rc = tg_lens_check(l);
+    if (rc != MOPK_OK) return rc;
+    const MopkTokenGateArgs *a = &l->base;
+    if (any_null(a->x, a->u, a->gate, a->dout, a->dr, a->du, a->workspace)) return MOPK_ERR_BAD_ARG;
+    tg_dispatch<true>(l, true, (hipStream_t)stream);
+    return tg_reduce(a, (hipStream_t)stream);
+}
+#endif  // MOPK_TOKEN_GATE_LENS
 
 }  // extern "C"

@@ -72,8 +72,9 @@ class MoPBlock(nn.Module):
         self.n_views = n_views
         self.n_kernels = n_kernels
 
-    def forward(self, x: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        x = self._gated_residual(x, self.attn(self.ln1(x), attention_mask=attention_mask))
+    def forward(self, x: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = self._gated_residual(x, self.attn(self.ln1(x), attention_mask=attention_mask, lens=lens), lens)
         return x + self.mlp(self.ln2(x))
 
     def taps(self) -> torch.Tensor:
@@ -86,21 +87,30 @@ class MoPBlock(nn.Module):
         g_pos, g_neg, a_pos, a_neg = self.fuse(torch.cat([V, K], dim=1))
         return 1 + a_pos * g_pos - a_neg * g_neg, V, K                 # (B,1,T)
 
-    def _gated_residual(self, x: torch.Tensor, a: Optional[torch.Tensor]) -> torch.Tensor:
-        """(x + a) * gate(x + a): one kernel where the library takes the call, the reference's composition otherwise"""
-        if self.kernels.conv.kernel_size[0] == 3 and ops.token_gate_supported(x, a):
-            return ops.token_gate_1d(x, a, self.taps())
+    @staticmethod
+    def _zero_tail(r: torch.Tensor, lens: Optional[torch.Tensor]) -> torch.Tensor:
+        """r (B,T,D) with the rows t >= lens[b] set to 0 (whatever they hold): what the gate of a right-padded row reads there"""
+        if lens is None:
+            return r
+        keep = torch.arange(r.shape[1], device=r.device).view(1, -1) < lens.to(r.device).view(-1, 1)
+        return torch.where(keep.unsqueeze(-1), r, torch.zeros((), dtype=r.dtype, device=r.device))
+
+    def _gated_residual(self, x: torch.Tensor, a: Optional[torch.Tensor], lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(x + a) * gate(x + a): one kernel where the library takes the call, the reference's composition otherwise.  lens: the
+        residual stream counts as 0 beyond a row's length, so its last token reads no padding and padding rows come out 0"""
+        if self.kernels.conv.kernel_size[0] == 3 and ops.token_gate_supported(x, a, lens):
+            return ops.token_gate_1d(x, a, self.taps(), lens)
         ops.LAST_PATH["token_gate_fwd"] = _lib.PATH_GENERIC
-        r = x if a is None else x + a
+        r = self._zero_tail(x if a is None else x + a, lens)
         return r * self._gate_torch(r)[0].transpose(1, 2)
 
-    def apply_mop(self, x):
+    def apply_mop(self, x, lens: Optional[torch.Tensor] = None):
         """the token gate applied to x (B,T,D)"""
-        return self._gated_residual(x, None)
+        return self._gated_residual(x, None, lens)
 
-    def get_gate_maps(self, x):
-        """(gate (B,1,T), views (B,V,T), kernels (B,K,T)) of x, in torch ops"""
-        return self._gate_torch(x)
+    def get_gate_maps(self, x, lens: Optional[torch.Tensor] = None):
+        """(gate (B,1,T), views (B,V,T), kernels (B,K,T)) of x, in torch ops; lens: of x with the rows beyond a length set to 0"""
+        return self._gate_torch(self._zero_tail(x, lens))
 
 
 class GPT_MoP(_LMBase):
@@ -120,23 +130,23 @@ class GPT_MoP(_LMBase):
         self.lm_head.weight = self.wte.weight
         self.apply(self._init_weights)
 
-    def forward(self, idx: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None):
-        x = self._embed(idx)
-        for block in self.blocks:
-            x = block(x, attention_mask=attention_mask)
-        return self._head(x, targets)
-
-    def get_gate_maps(self, x):
-        """per-layer gate maps of token ids x (B,T): (gates (B,L,1,T), views (B,L,V,T), kernels (B,L,K,T)); no attention mask"""
+    def get_gate_maps(self, x, lens: Optional[torch.Tensor] = None):
+        """per-layer gate maps of token ids x (B,T): (gates (B,L,1,T), views (B,L,V,T), kernels (B,L,K,T)); no attention mask.
+        x may be a list of 1-D token tensors as in forward, or come with int32 (B,) lengths: positions t < lens[b] are those of
+        row b alone"""
+        if isinstance(x, (list, tuple)):
+            if lens is not None:
+                raise ValueError("lens is taken from a list of token tensors: pass one or the other")
+            x, _, lens = self._batch(x)
         h = self._embed(x)
         gates, views, kernels = [], [], []
         for block in self.blocks:
-            r = h + block.attn(block.ln1(h))
-            g, V, K = block.get_gate_maps(r)
+            r = h + (block.attn(block.ln1(h)) if lens is None else block.attn(block.ln1(h), lens=lens))
+            g, V, K = block.get_gate_maps(r, lens)
             gates.append(g)
             views.append(V)
             kernels.append(K)
-            h = block.apply_mop(r)
+            h = block.apply_mop(r, lens)
             h = h + block.mlp(block.ln2(h))
         return torch.stack(gates, dim=1), torch.stack(views, dim=1), torch.stack(kernels, dim=1)
 

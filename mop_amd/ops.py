@@ -845,6 +845,7 @@ _CORE_OPS = {   # core -> (export stem, support query that resolves PATH_AUTO, L
     "sdpa_lens": ("mopk_sdpa_lens", "mopk_sdpa_lens_supported", "sdpa", ("fwd", "bwd")),
     "dualpath": ("mopk_dualpath", "mopk_dualpath_fused_supported", "dualpath", ("fwd", "bwd")),
     "quartet": ("mopk_quartet", "mopk_quartet_fused_supported", "quartet", ("fwd",)),
+    "quartet_lens": ("mopk_quartet_lens", "mopk_quartet_lens_fused_supported", "quartet", ("fwd",)),
     "crossview": ("mopk_crossview", None, "crossview", ()),       # one path; crossview_core* record it
 }
 
@@ -952,12 +953,12 @@ class _SdpaLensFn(torch.autograd.Function):
         return _sdpa_bwd(ctx, ts, _grad_in(dy, ts[0].dtype, ts[0].shape))
 
 
-def _check_lens(t, B: int, dev, what: str) -> None:
+def _check_lens(t, B: int, dev, what: str, op: str = "sdpa_core", beside: str = "q") -> None:
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != B:
-        raise ValueError(f"sdpa_core: {what} must be an int32 (B,) = ({B},) tensor, got "
+        raise ValueError(f"{op}: {what} must be an int32 (B,) = ({B},) tensor, got "
                          f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
     if t.device != dev:
-        raise ValueError(f"sdpa_core: {what} is on {t.device}, q on {dev}")
+        raise ValueError(f"{op}: {what} is on {t.device}, {beside} on {dev}")
 
 
 def sdpa_lens_mask(q_lens, kv_lens, B: int, N: int, Nk: int, device) -> torch.Tensor:
@@ -1288,9 +1289,10 @@ def dualpath_core(q1, k1, v1, q2, k2, v2, chain_logit, g_and, g_or, g_not, g_cha
                              int(hops), attn_mask, causal, _prec_for(q1.dtype), _PATH, drop)
 
 
-def _qt_args(ts, sc, y, am, eps, prec, path, drop) -> L.QuartetArgs:
+def _qt_args(ts, sc, y, am, eps, prec, path, drop, lens=None):
     """the MopkQuartetArgs fields forward and backward share; ts: the (B,T,H,dh) views q k v, plus q2 k2 with the quartet term,
-    whose float32 scalars are sc = (mixture, scale); am: (additive mask or None, strides) from _bias_f32"""
+    whose float32 scalars are sc = (mixture, scale); am: (additive mask or None, strides) from _bias_f32.
+    lens: int32 (B,) device tensor -> the MopkQuartetLensArgs that wraps them"""
     B, T, H, dh = ts[0].shape
     a = L.QuartetArgs()
     a.B, a.H, a.T, a.dh = B, H, T, dh
@@ -1302,70 +1304,128 @@ def _qt_args(ts, sc, y, am, eps, prec, path, drop) -> L.QuartetArgs:
         a.mixture, a.quartet_scale = sc[0].data_ptr(), sc[1].data_ptr()
     a.add_mask, (a.am_sb, a.am_sh, a.am_si) = _ptr(am[0]), am[1]
     a.dropout_p, a.dropout_seed = float(drop[0]), int(drop[1])
-    return a
+    return a if lens is None else L.QuartetLensArgs(base=a, lens=_ptr(lens))
+
+
+def _qt_fwd(ctx, q, k, v, q2, k2, mixture, qscale, add_mask, lens, eps, use_quartet, need_weights, prec, path, drop):
+    """the forward of _QuartetFn (lens None) and _QuartetLensFn (add_mask None)"""
+    _require_gpu(q, "CausalSelfAttention")
+    ts = [_heads_view(t) for t in ((q, k, v, q2, k2) if use_quartet else (q, k, v))]
+    B, T, H, dh = ts[0].shape
+    dev = ts[0].device
+    sc = [_f32c(mixture).reshape(1), _f32c(qscale).reshape(1)] if use_quartet else []
+    am = _bias_f32(add_mask, B, H, T, dev)
+    y = torch.empty(B, T, H, dh, dtype=ts[0].dtype, device=dev)
+    a = _qt_args(ts, sc, y, am, eps, prec, path, drop, lens)
+    attn = torch.empty(B, H, T, T, dtype=torch.float32, device=dev) if need_weights else None
+    getattr(a, "base", a).attn = _ptr(attn)
+    saved, path = _core_launch("quartet" if lens is None else "quartet_lens", a, dev)
+    ctx.save_for_backward(*ts, *sc, y, saved)
+    ctx.meta = (eps, use_quartet, prec, path, am, drop)
+    ctx.lens = lens
+    out = y.view(B, T, H * dh)
+    if need_weights:
+        ctx.mark_non_differentiable(attn)
+        return out, attn
+    return out
+
+
+def _qt_bwd(ctx, dy):
+    """the backward of both on dy as _grad_in returns it, (B,T,H,dh): the five (three) input gradients and the two scalar gradients
+    (None without the quartet term)"""
+    eps, use_quartet, prec, path, am, drop = ctx.meta
+    n = 5 if use_quartet else 3
+    *ts, y, saved = ctx.saved_tensors
+    ts, sc = ts[:n], ts[n:]
+    B, T, H, dh = ts[0].shape
+    dev = ts[0].device
+    a = _qt_args(ts, sc, y, am, eps, prec, path, drop, ctx.lens)
+    base = getattr(a, "base", a)
+    base.dy = _v4(dy)
+    gs = [torch.empty(B, T, H, dh, dtype=ts[0].dtype, device=dev) for _ in range(n)]
+    base.dq, base.dk_, base.dv = _v4(gs[0]), _v4(gs[1]), _v4(gs[2])
+    if use_quartet:
+        base.dq2, base.dk2 = _v4(gs[3]), _v4(gs[4])
+        dmix = torch.empty(B, H, dtype=torch.float32, device=dev)
+        dqs = torch.empty(B, H, dtype=torch.float32, device=dev)
+        base.dmixture_part, base.dqscale_part = dmix.data_ptr(), dqs.data_ptr()
+    _core_launch("quartet" if base is a else "quartet_lens", a, dev, saved)
+    if use_quartet:
+        return gs[0], gs[1], gs[2], gs[3], gs[4], dmix.sum().reshape(1), dqs.sum().reshape(1)
+    return gs[0], gs[1], gs[2], None, None, None, None
 
 
 class _QuartetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, q2, k2, mixture, qscale, add_mask, eps, use_quartet, need_weights, prec, path, drop=(0.0, 0)):
-        _require_gpu(q, "CausalSelfAttention")
-        ts = [_heads_view(t) for t in ((q, k, v, q2, k2) if use_quartet else (q, k, v))]
-        B, T, H, dh = ts[0].shape
-        dev = ts[0].device
-        sc = [_f32c(mixture).reshape(1), _f32c(qscale).reshape(1)] if use_quartet else []
-        am = _bias_f32(add_mask, B, H, T, dev)
-        y = torch.empty(B, T, H, dh, dtype=ts[0].dtype, device=dev)
-        a = _qt_args(ts, sc, y, am, eps, prec, path, drop)
-        attn = torch.empty(B, H, T, T, dtype=torch.float32, device=dev) if need_weights else None
-        a.attn = _ptr(attn)
-        saved, path = _core_launch("quartet", a, dev)
-        ctx.save_for_backward(*ts, *sc, y, saved)
-        ctx.meta = (eps, use_quartet, prec, path, am, drop)
-        out = y.view(B, T, H * dh)
-        if need_weights:
-            ctx.mark_non_differentiable(attn)
-            return out, attn
-        return out
+        return _qt_fwd(ctx, q, k, v, q2, k2, mixture, qscale, add_mask, None, eps, use_quartet, need_weights, prec, path, drop)
 
     @staticmethod
     @_once_differentiable
     def backward(ctx, dy, *unused):
-        eps, use_quartet, prec, path, am, drop = ctx.meta
-        n = 5 if use_quartet else 3
-        *ts, y, saved = ctx.saved_tensors
-        ts, sc = ts[:n], ts[n:]
-        B, T, H, dh = ts[0].shape
-        dev = ts[0].device
-        dy = _grad_in(dy, ts[0].dtype, (B, T, H, dh))
-        a = _qt_args(ts, sc, y, am, eps, prec, path, drop)
-        a.dy = _v4(dy)
-        gs = [torch.empty(B, T, H, dh, dtype=ts[0].dtype, device=dev) for _ in range(n)]
-        a.dq, a.dk_, a.dv = _v4(gs[0]), _v4(gs[1]), _v4(gs[2])
-        dmix = dqs = None
-        if use_quartet:
-            a.dq2, a.dk2 = _v4(gs[3]), _v4(gs[4])
-            dmix = torch.empty(B, H, dtype=torch.float32, device=dev)
-            dqs = torch.empty(B, H, dtype=torch.float32, device=dev)
-            a.dmixture_part, a.dqscale_part = dmix.data_ptr(), dqs.data_ptr()
-        _core_launch("quartet", a, dev, saved)
-        if use_quartet:
-            return (gs[0], gs[1], gs[2], gs[3], gs[4], dmix.sum().reshape(1), dqs.sum().reshape(1),
-                    None, None, None, None, None, None, None)
-        return (gs[0], gs[1], gs[2], None, None, None, None, None, None, None, None, None, None, None)
+        q = ctx.saved_tensors[0]
+        return (*_qt_bwd(ctx, _grad_in(dy, q.dtype, q.shape)), None, None, None, None, None, None, None)
+
+
+# _QuartetLensFn, the Function of the call with per-row lengths, is in mop_amd/gpt_lens_fn.py (imported at the end of this file)
 
 
 @_half_via_fp32
 def quartet_core(q, k, v, q2, k2, mixture, quartet_scale, add_mask, eps, use_quartet, need_weights=False,
-                 dropout_p: float = 0.0, seed: Optional[int] = None):
+                 dropout_p: float = 0.0, seed: Optional[int] = None, lens=None):
     """q, k, v (and q2, k2 with use_quartet): (B,T,H,dk) views.  Returns (B,T,H*dk), and the (B,H,T,T) float32 weights with
-    need_weights.  add_mask: additive, broadcastable to (B,H,T,T) along any axis, the key axis included; it gets no gradient."""
+    need_weights.  add_mask: additive, broadcastable to (B,H,T,T) along any axis, the key axis included; it gets no gradient.
+    lens: int32 (B,) tensor on q's device for a batch of right-padded rows, n_b = clamp(lens[b], 0, T) (mopk_quartet_lens_*;
+    `quartet_core_lens_torch` states the semantics).  Row i < n_b normalises both score maps over the keys j < n_b only and attends
+    to j <= i, so it comes out as the row alone would; padding rows give y = 0 (zero rows and columns of the returned weights),
+    get zero gradients and add nothing to the gradients of mixture / quartet_scale.  Nothing at or beyond a length is read (NaN
+    included), the dropout mask is indexed by the padded positions, full lengths are bitwise the call without lengths, and there
+    is no host synchronisation.  lens with add_mask raises ValueError."""
     _refuse_bias_grad(add_mask, "quartet_core: add_mask")      # add_mask gets no gradient
+    if lens is not None:
+        if add_mask is not None:
+            raise ValueError("quartet_core: lens and add_mask do not combine (an additive mask acts after the row normalisation)")
+        _check_lens(lens, q.shape[0], q.device, "lens", "quartet_core")
     if q.shape[0] == 0:                   # q: (B,T,H,dk)
         out = _empty_batch(q, 0, q.shape[1], q.shape[2] * q.shape[3])
         return (out, q.new_zeros((0, q.shape[2], q.shape[1], q.shape[1]), dtype=torch.float32)) if need_weights else out
     drop = _drop(dropout_p, seed)
+    if lens is not None:
+        return _gpt_lens_fn._QuartetLensFn.apply(q, k, v, q2, k2, mixture, quartet_scale, lens, eps, use_quartet, need_weights,
+                                    _prec_for(q.dtype), _PATH, drop)
     return _QuartetFn.apply(q, k, v, q2, k2, mixture, quartet_scale, add_mask, eps, use_quartet, need_weights,
                             _prec_for(q.dtype), _PATH, drop)
+
+
+def quartet_core_lens_torch(q, k, v, q2, k2, mixture, quartet_scale, lens, eps, use_quartet, need_weights=False):
+    """The semantics of `quartet_core(..., lens=)` in torch ops, on any device and dtype (no dropout): row b is the core on its
+    first n_b = clamp(lens[b], 0, T) tokens alone -- statistics over n_b keys, unbiased std with max(n_b - 1, 1) -- padded back
+    with zeros.  Reads lens on the host; the statement of the semantics and the tests' reference, not a fast path."""
+    B, T, H, dh = q.shape
+    y = q.new_zeros(B, T, H * dh)
+    attn = q.new_zeros(B, H, T, T)
+    for b, n in enumerate(int(x) for x in lens.clamp(0, T).tolist()):
+        if n == 0:
+            continue
+        hv = lambda t: t[b, :n].transpose(0, 1)                        # (H, n, dh)
+        def z(a, c, e):
+            s = (hv(a) @ hv(c).transpose(-1, -2)) / math.sqrt(dh)
+            mu = s.mean(-1, keepdim=True)
+            var = ((s - mu) ** 2).sum(-1, keepdim=True).div(max(n - 1, 1))
+            pos = var > 0                                              # sd == 0 (a single key): z = 0 with a zero gradient, not 0 * inf
+            sd = torch.where(pos, torch.where(pos, var, torch.ones_like(var)).sqrt(), torch.zeros_like(var))
+            return (s - mu) / (sd + e)
+        if use_quartet:
+            z1, z2 = z(q, k, eps), z(q2, k2, eps)
+            m = torch.sigmoid(mixture.to(z1.dtype)).reshape(())
+            sc = (1 - m) * z1 + m * (z1 * z2) * quartet_scale.to(z1.dtype).reshape(())
+        else:
+            sc = z(q, k, 1e-5)
+        causal = torch.ones(n, n, dtype=torch.bool, device=q.device).tril()
+        P = torch.softmax(sc.masked_fill(~causal, float("-inf")), -1)
+        y[b, :n] = (P @ hv(v)).transpose(0, 1).reshape(n, H * dh)
+        attn[b, :, :n, :n] = P
+    return (y, attn.detach().float()) if need_weights else y
 
 
 # ---- LayerNorm prologue / residual epilogue around the cores (SURVEY.md 8f rank 1; mopk_layernorm_*) ----
@@ -1460,16 +1520,22 @@ def token_gate_taps(Wv: torch.Tensor, Wk: torch.Tensor, Wf: torch.Tensor, alpha:
         return m @ f32(Wv)                                         # (3, D)
 
 
-def token_gate_1d_torch(x: torch.Tensor, a: Optional[torch.Tensor], u: torch.Tensor) -> torch.Tensor:
-    """the folded gate in torch ops (any device / dtype): r = x + a, out_t = r_t (1 + u0.r_{t-1} + u1.r_t + u2.r_{t+1})"""
+def token_gate_1d_torch(x: torch.Tensor, a: Optional[torch.Tensor], u: torch.Tensor, lens=None) -> torch.Tensor:
+    """the folded gate in torch ops (any device / dtype): r = x + a, out_t = r_t (1 + u0.r_{t-1} + u1.r_t + u2.r_{t+1}).
+    lens: int (B,) tensor of a right-padded batch -- r_t counts as 0 for t >= lens[b] (whatever it holds, NaN included), so the
+    last real token has no u2 term and padding rows come out 0 with zero gradients (torch ops on the device, no host sync)"""
     r = x if a is None else x + a
+    if lens is not None:
+        keep = torch.arange(r.shape[1], device=r.device).view(1, -1) < lens.to(r.device).view(-1, 1)
+        r = torch.where(keep.unsqueeze(-1), r, torch.zeros((), dtype=r.dtype, device=r.device))
     p = torch.einsum("btd,sd->bts", r, u.to(r.dtype))              # (B,T,3)
     gate = 1 + p[..., 1]
     gate = gate + F.pad(p[:, :-1, 0], (1, 0)) + F.pad(p[:, 1:, 2], (0, 1))
     return r * gate.unsqueeze(-1)
 
 
-def _tg_args(x: torch.Tensor, a: Optional[torch.Tensor]) -> L.TokenGateArgs:
+def _tg_args(x: torch.Tensor, a: Optional[torch.Tensor], lens=None):
+    """the MopkTokenGateArgs fields every call shares; lens: int32 (B,) device tensor -> the MopkTokenGateLensArgs that wraps them"""
     B, T, D = x.shape
     g = L.TokenGateArgs()
     g.B, g.T, g.D = B, T, D
@@ -1481,12 +1547,13 @@ def _tg_args(x: torch.Tensor, a: Optional[torch.Tensor]) -> L.TokenGateArgs:
         g.a, g.a_sb, g.a_st = a.data_ptr(), (a.stride(0) if B > 1 else 0), (a.stride(1) if T > 1 else D)
         f32 = f32 or a.dtype == torch.float32
     g.o_dtype = L.MOPK_F32 if f32 else L.MOPK_BF16
-    return g
+    return g if lens is None else L.TokenGateLensArgs(base=g, lens=_ptr(lens))
 
 
-def token_gate_supported(x: torch.Tensor, a: Optional[torch.Tensor] = None) -> bool:
+def token_gate_supported(x: torch.Tensor, a: Optional[torch.Tensor] = None, lens=None) -> bool:
     """True if mopk_token_gate_* take this call: GPU tensors, fp32 / bf16 (mixed pairs included), (B,T,D) with D % 8 == 0 and
-    D <= 1024, innermost dimension contiguous, row strides multiples of 8, 16-byte aligned data (the library's own query)."""
+    D <= 1024, innermost dimension contiguous, row strides multiples of 8, 16-byte aligned data (the library's own query).
+    lens: the same question for mopk_token_gate_lens_* with these int32 (B,) lengths."""
     ts = (x,) if a is None else (x, a)
     if any(not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 3 or t.stride(-1) != 1 for t in ts):
         return False
@@ -1494,53 +1561,78 @@ def token_gate_supported(x: torch.Tensor, a: Optional[torch.Tensor] = None) -> b
         return False
     if x.numel() == 0:
         return False
+    if lens is not None:
+        return bool(L.lib().mopk_token_gate_lens_supported(C.byref(_tg_args(x, a, lens))))
     return bool(L.lib().mopk_token_gate_supported(C.byref(_tg_args(x, a))))
+
+
+def _tg_fwd(ctx, x, a, u, lens):
+    """the forward of _TokenGateFn (lens None) and _TokenGateLensFn"""
+    ga = _tg_args(x, a, lens)
+    g = getattr(ga, "base", ga)
+    stem = "mopk_token_gate" if lens is None else "mopk_token_gate_lens"
+    B, T, D = x.shape
+    uc = u.detach().to(torch.float32).contiguous()
+    odt = torch.float32 if g.o_dtype == L.MOPK_F32 else torch.bfloat16
+    out = torch.empty(B, T, D, dtype=odt, device=x.device)
+    gate = torch.empty(B, T, dtype=torch.float32, device=x.device)
+    g.u, g.out, g.gate = uc.data_ptr(), out.data_ptr(), gate.data_ptr()
+    LAST_PATH["token_gate_fwd"] = L.PATH_FUSED
+    _launch(stem + "_fwd", ga, "token_gate_fwd")
+    ctx.save_for_backward(x, a, uc, gate)
+    ctx.u_dtype, ctx.lens, ctx.o_dtype = u.dtype, lens, odt
+    return out
+
+
+def _tg_bwd(ctx, dout):
+    """the backward of both on dout as _grad_in returns it: (dx, da, du)"""
+    lib = L.lib()
+    x, a, uc, gate = ctx.saved_tensors
+    ga = _tg_args(x, a, ctx.lens)
+    g = getattr(ga, "base", ga)
+    stem = "mopk_token_gate" if ctx.lens is None else "mopk_token_gate_lens"
+    odt = ctx.o_dtype
+    dr = torch.empty(x.shape, dtype=odt, device=x.device)
+    du = torch.empty(3, x.shape[2], dtype=torch.float32, device=x.device)
+    g.u, g.gate, g.dout, g.dr, g.du = uc.data_ptr(), gate.data_ptr(), dout.data_ptr(), dr.data_ptr(), du.data_ptr()
+    ws = _bytes(getattr(lib, stem + "_workspace_bytes")(C.byref(ga)), x.device)
+    g.workspace = ws.data_ptr()
+    LAST_PATH["token_gate_bwd"] = L.PATH_FUSED
+    _launch(stem + "_bwd", ga, "token_gate_bwd")
+    dx = dr.to(x.dtype) if ctx.needs_input_grad[0] else None
+    da = dr.to(a.dtype) if a is not None and ctx.needs_input_grad[1] else None
+    return dx, da, (du.to(ctx.u_dtype) if ctx.needs_input_grad[2] else None)
 
 
 class _TokenGateFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, a, u):
-        g = _tg_args(x, a)
-        B, T, D = x.shape
-        uc = u.detach().to(torch.float32).contiguous()
-        odt = torch.float32 if g.o_dtype == L.MOPK_F32 else torch.bfloat16
-        out = torch.empty(B, T, D, dtype=odt, device=x.device)
-        gate = torch.empty(B, T, dtype=torch.float32, device=x.device)
-        g.u, g.out, g.gate = uc.data_ptr(), out.data_ptr(), gate.data_ptr()
-        LAST_PATH["token_gate_fwd"] = L.PATH_FUSED
-        _launch("mopk_token_gate_fwd", g, "token_gate_fwd")
-        ctx.save_for_backward(x, a, uc, gate)
-        ctx.u_dtype = u.dtype
-        return out
+        return _tg_fwd(ctx, x, a, u, None)
 
     @staticmethod
     @_once_differentiable
     def backward(ctx, dout):
-        lib = L.lib()
-        x, a, uc, gate = ctx.saved_tensors
-        g = _tg_args(x, a)
-        odt = torch.float32 if g.o_dtype == L.MOPK_F32 else torch.bfloat16
-        dout = _grad_in(dout, odt)
-        dr = torch.empty(x.shape, dtype=odt, device=x.device)
-        du = torch.empty(3, x.shape[2], dtype=torch.float32, device=x.device)
-        g.u, g.gate, g.dout, g.dr, g.du = uc.data_ptr(), gate.data_ptr(), dout.data_ptr(), dr.data_ptr(), du.data_ptr()
-        ws = _bytes(lib.mopk_token_gate_workspace_bytes(C.byref(g)), x.device)
-        g.workspace = ws.data_ptr()
-        LAST_PATH["token_gate_bwd"] = L.PATH_FUSED
-        _launch("mopk_token_gate_bwd", g, "token_gate_bwd")
-        dx = dr.to(x.dtype) if ctx.needs_input_grad[0] else None
-        da = dr.to(a.dtype) if a is not None and ctx.needs_input_grad[1] else None
-        return dx, da, (du.to(ctx.u_dtype) if ctx.needs_input_grad[2] else None)
+        return _tg_bwd(ctx, _grad_in(dout, ctx.o_dtype))
 
 
-def token_gate_1d(x: torch.Tensor, a: Optional[torch.Tensor], u: torch.Tensor) -> torch.Tensor:
+# _TokenGateLensFn is in mop_amd/gpt_lens_fn.py
+
+
+def token_gate_1d(x: torch.Tensor, a: Optional[torch.Tensor], u: torch.Tensor, lens=None) -> torch.Tensor:
     """out = r * gate with r = x + a (a may be None) and gate_t = 1 + u0.r_{t-1} + u1.r_t + u2.r_{t+1} (zero padding per sequence):
     the GPT-MoP block's residual add and token gate as one HIP kernel forward and two launches backward.  x, a: (B,T,D); u: (3,D)
     from token_gate_taps.  Output dtype: the promotion of x and a.  Calls the kernels do not take (token_gate_supported) run the
-    same formula in torch ops; LAST_PATH["token_gate_fwd"] records which (PATH_FUSED / PATH_GENERIC)."""
-    if not token_gate_supported(x, a):
+    same formula in torch ops; LAST_PATH["token_gate_fwd"] records which (PATH_FUSED / PATH_GENERIC).
+    lens: int32 (B,) tensor on x's device for a batch of right-padded rows, n_b = clamp(lens[b], 0, T) (mopk_token_gate_lens_*):
+    r_t counts as 0 for t >= n_b, so the last real token has no u2 term; padding rows come out 0, get dr = 0, add nothing to du
+    and are never read (NaN included).  Full lengths are bitwise the call without lengths; no host synchronisation."""
+    if lens is not None:
+        _check_lens(lens, x.shape[0], x.device, "lens", "token_gate_1d", "x")
+    if not token_gate_supported(x, a, lens):
         LAST_PATH["token_gate_fwd"] = L.PATH_GENERIC
-        return token_gate_1d_torch(x, a, u)
+        return token_gate_1d_torch(x, a, u, lens)
+    if lens is not None:
+        return _gpt_lens_fn._TokenGateLensFn.apply(x, a, u, lens)
     return _TokenGateFn.apply(x, a, u)
 
 
@@ -4890,3 +4982,4 @@ def linear_cross_entropy(x: torch.Tensor, weight: torch.Tensor, targets: torch.T
 
 from . import mel_gate_fn as _mel_gate_fn  # noqa: E402  (it reads this module's helpers, all defined by now)
 from . import cross_entropy_fn as _cross_entropy_fn  # noqa: E402  (likewise)
+from . import gpt_lens_fn as _gpt_lens_fn  # noqa: E402  (likewise)
