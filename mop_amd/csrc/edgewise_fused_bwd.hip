@@ -1583,8 +1583,8 @@ static int bwd_grid(const MopkEdgewiseArgs *a, int items_per_bh) {
     int per_cu = NT <= 3 ? 8 / NT : 1;            // matches the __launch_bounds__ occupancy hint of the kernels
     if (lds * per_cu > 160 * 1024) per_cu = 160 * 1024 / lds;
     if (per_cu < 1) per_cu = 1;
-    const int n = a->B * a->H * items_per_bh, cap = 256 * per_cu;
-    return n < cap ? n : cap;
+    const int64_t n = (int64_t)a->B * a->H * items_per_bh, cap = 256 * per_cu;      // B * H * 2 passes 2^31 before B * H does
+    return (int)(n < cap ? n : cap);
 }
 static size_t a256h(size_t x) { return (x + 255) & ~(size_t)255; }
 // workspace = [per-workgroup scratch x grid | per-(b,h) hand-off x B*H | (save_for_backward == 0 only) full `saved` record + y scratch

@@ -197,7 +197,7 @@ extern "C" {
 int mopk_log_mel_supported(const MopkLogMelArgs *a) { return lm_check(a) == MOPK_OK; }
 
 size_t mopk_log_mel_workspace_bytes(const MopkLogMelArgs *a) {
-    if (!a || a->B <= 0 || a->L <= 0 || a->hop <= 0 || a->n_mels <= 0) return 0;
+    if (!a || a->B <= 0 || a->B > 65535 || a->L <= 0 || a->hop <= 0 || a->n_mels <= 0) return 0;      // B: the grid's y extent, as lm_check
     const int T = a->L / a->hop;
     Carver c(nullptr);
     c.take<float>((size_t)a->B * lm_tiles(T));

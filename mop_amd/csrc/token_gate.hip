@@ -358,7 +358,7 @@ extern "C" {
 int mopk_token_gate_supported(const MopkTokenGateArgs *a) { return tg_check(a) == MOPK_OK; }
 
 size_t mopk_token_gate_workspace_bytes(const MopkTokenGateArgs *a) {
-    if (!a || a->B <= 0 || a->T <= 0 || a->D <= 0) return 0;
+    if (!a || a->B <= 0 || a->T <= 0 || a->D <= 0 || (int64_t)a->B * a->T > ((int64_t)1 << 31) - 1) return 0;   // as tg_check
     return (size_t)tg_parts(a) * 3 * a->D * sizeof(float);
 }
 
@@ -387,7 +387,7 @@ static int tg_lens_check(const MopkTokenGateLensArgs *l) {
 int mopk_token_gate_lens_supported(const MopkTokenGateLensArgs *l) { return tg_lens_check(l) == MOPK_OK; }
 
 size_t mopk_token_gate_lens_workspace_bytes(const MopkTokenGateLensArgs *l) {
-    if (!l || l->base.B <= 0 || l->base.T <= 0 || l->base.D <= 0) return 0;
+    if (!l || l->base.B <= 0 || l->base.T <= 0 || l->base.D <= 0 || (int64_t)l->base.B * l->base.T > ((int64_t)1 << 31) - 1) return 0;
     return (size_t)tg_parts(&l->base) * 3 * l->base.D * sizeof(float);
 }
 

@@ -223,6 +223,7 @@ def test_quartet_fused_matches_generic_with_lengths(uq):
 
 
 # ---- token gate -------------------------------------------------------------------------------------------------------------
+TG_TOL = {"bf16": 1e-2, "fp32": 1e-4}    # the bounds of test_token_gate_op_against_float64 (tests/test_gpu_gpt.py)
 TG_LENS = (40, 33, 32, 17, 16, 1, 0)   # either side of and on the 16-token tile edges, a lone token, an empty row
 
 
@@ -265,7 +266,7 @@ def _nerr(a, b):
 def test_token_gate_rows_are_as_alone(D, dt, with_a):
     """the bounds of test_token_gate_op_against_float64 (tests/test_gpu_gpt.py)"""
     tdt = torch.bfloat16 if dt == "bf16" else torch.float32
-    tol = 1e-2 if dt == "bf16" else 1e-4
+    tol = TG_TOL[dt]
     x, a, u, dout = _tg_inputs(len(TG_LENS), 40, D, tdt, with_a, seed=D + with_a)
     ro, rdr, rdu = token_gate_rows_alone(x, a, u, TG_LENS, dout)
     lens = _lens(TG_LENS)

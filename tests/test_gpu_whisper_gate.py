@@ -25,6 +25,11 @@ FWD_SHAPES = [(1, 1, 1, 1, 1), (2, 3, 2, 1, 5), (3, 37, 10, 2, 3), (2, 65, 16, 3
               (2, 40, 16, 11, 3)]                       # B,T,F,L,k; the last: more layers than one launch holds (8)
 
 
+MG_FWD_TOL, MG_BWD_TOL = 1e-5, 1e-4                   # mel gate against float64: the gates, the tap gradients
+GR_TOL = {torch.float32: 1e-6, torch.bfloat16: 2.0 ** -8}      # gated residual against float64, by the dtype of the tensor
+GR_DGATE_TOL = 1e-5
+
+
 def _rel(got, ref):
     return float((got.detach().double().cpu() - ref.cpu()).abs().max() / ref.abs().max().clamp_min(1e-300))
 
@@ -59,7 +64,7 @@ def test_mel_gate_forward_against_float64(B, T, Fm, L, k, how):
     ref = ops.mel_gate_torch(mel.double(), W.double())
     e = _rel(got, ref)
     print(f"mel_gate fwd {how} B={B} T={T} F={Fm} L={L} k={k}: {e:.3e} (bound 1e-5)")
-    assert e <= 1e-5
+    assert e <= MG_FWD_TOL
 
 
 @pytest.mark.parametrize("T,Fm,L,k,lens", [(130, 80, 6, 5, (130, 1, 37, 64)), (70, 10, 2, 7, (70, 1, 33, 32)), (40, 16, 9, 3, (1, 40, 31, 2))])
@@ -117,7 +122,7 @@ def test_mel_gate_backward_against_float64_autograd_of_the_convolutions(B, T, Fm
     for name, g, r in zip(("dW", "Wv", "Wk", "Wf", "alpha"), got, ref):
         e = _rel(g.reshape(r.shape), r)
         print(f"mel_gate bwd {how} B={B} T={T} F={Fm} L={L} k={k} lens={lens} {name}: {e:.3e} (bound 1e-4)")
-        assert e <= 1e-4, name
+        assert e <= MG_BWD_TOL, name
     again = _mel_gate_grads(mel, prm, dg, dev_lens)
     assert all(torch.equal(a, b) for a, b in zip(got, again))
 
@@ -174,9 +179,9 @@ def test_gated_residual_against_float64(B, T, D, dt, strided):
     assert out.dtype == odt and dx.dtype == x.dtype and da.dtype == a.dtype and dgate.dtype == torch.float32 and dgate.shape == (B, T)
     r64 = x.double() + a.double()
     ref_out, ref_dr, ref_dg = r64 * gate.double().unsqueeze(-1), dout.double() * gate.double().unsqueeze(-1), (dout.double() * r64).sum(-1)
-    tol = {torch.float32: 1e-6, torch.bfloat16: 2.0 ** -8}
+    tol = GR_TOL
     for name, got, ref, bound in (("out", out, ref_out, tol[odt]), ("dx", dx, ref_dr, tol[x.dtype]), ("da", da, ref_dr, tol[a.dtype]),
-                                  ("dgate", dgate, ref_dg, 1e-5)):
+                                  ("dgate", dgate, ref_dg, GR_DGATE_TOL)):
         e = _rel(got, ref)
         print(f"gated_residual {dt} B={B} T={T} D={D} strided={strided} {name}: {e:.3e} (bound {bound:.1e})")
         assert e <= bound, name
