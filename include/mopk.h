@@ -1295,6 +1295,80 @@ int mopk_cross_entropy_supported(const MopkCrossEntropyArgs *a);      /* 1 if th
 int mopk_cross_entropy_fwd(const MopkCrossEntropyArgs *a, void *stream);
 int mopk_cross_entropy_bwd(const MopkCrossEntropyArgs *a, void *stream);
 
+/* --------------------------------------------------------------------------
+ * Fused AdamW step over a list of tensors (mop_amd.optim.FusedAdamW, ops.adamw_step): global gradient norm, clipping, the update,
+ * an optional weight EMA.  (Added under version 118: new exports only; callers detect them with mopk_adamw_supported.)
+ *
+ * A call takes one MopkAdamWArgs and a HOST array of n_tensors MopkOptimTensor.  The hyper-parameters of a call hold for all its
+ * tensors; an optimiser with several parameter groups makes one call with phases = MOPK_ADAMW_NORM over all tensors and one call
+ * with phases = MOPK_ADAMW_UPDATE per group.  Per element, in fp32, every product and sum rounded once (no contraction):
+ *   g' = coef * g                                     coef = stats.coef when use_norm, else 1;  g itself is never written
+ *   p  = p * decay                                    decay = fl(1 - lr * weight_decay)
+ *   m  = fl(b1) * m + fl(1 - b1) * g'
+ *   v  = fl(b2) * v + (fl(1 - b2) * g') * g'
+ *   p  = p - fl(lr / bc1) * (m / (sqrtf(v) / fl(sqrt(bc2)) + fl(eps)))       bc_i = 1 - b_i^(step + 1)
+ *   ema = fl(d) * ema + fl(1 - d) * p                 only with use_ema
+ * The constants fl(.) are computed in double (lr, the betas, eps, weight_decay and ema_decay travel as doubles; b^(step + 1) by
+ * repeated squaring in double, from the tensor's own device step count) and rounded to fp32 once.  With lr_dev, lr is read from
+ * that device float.  p, g and ema are F32 or BF16 (p and ema share p_dtype; g_dtype may differ); m and v are always fp32.  A
+ * BF16 p or ema is rounded to nearest even once, from the fp32 result.
+ *
+ * Launches.  The tensors are cut into chunks of MOPK_ADAMW_CHUNK elements (the last chunk of a tensor may be short; an empty
+ * tensor has none) and the chunk list into slices that travel as kernel arguments: a slice holds at most MOPK_ADAMW_MAX_TENSORS
+ * tensor parts and at most MOPK_ADAMW_MAX_CHUNKS chunks, is filled greedily in tensor order, and a tensor with more chunks than
+ * fit continues in the next slice.  With S slices (mopk_adamw_launches; a slice of empty tensors only launches its count kernel):
+ *   MOPK_ADAMW_NORM    S launches (one workgroup of 256 threads per chunk: each thread sums the squares of its elements in fp32 in
+ *                      index order, the workgroup merges by the wave shuffle tree and then the waves in wave order, one partial per
+ *                      chunk goes to the workspace; no atomics) + 1 launch (one workgroup sums the partials in double, thread-
+ *                      strided, same merge order; stats.norm = fl(sqrt(sum)), stats.coef = min(1, max_norm / (norm + 1e-6)) when
+ *                      clip, else 1 (a NaN norm gives a NaN coef, as torch's clamp does); stats.skip = skip_nonfinite and the norm
+ *                      is not finite; stats.skipped += stats.skip)
+ *   MOPK_ADAMW_UPDATE  S launches (grid min(chunks of the slice, 2048), grid-stride over chunks) + S launches that add 1 to the
+ *                      step counts (stream-ordered behind every update launch: no launch reads a count that it writes).
+ * With stats.skip set and use_norm, an update call writes nothing and advances no count.
+ * A chunk is read in 16-byte vectors from p's first 16-byte boundary on; the elements before it and behind the last whole vector
+ * are handled one by one, and a stream that does not share p's alignment is read or written element by element.
+ * No host synchronisation, no host-to-device copy, no allocation: a call may be captured in a HIP graph (the pointers are then
+ * fixed; step counts, bias corrections, lr_dev and the stats are read on the device at replay). */
+#define MOPK_ADAMW_CHUNK 4096            /* elements per chunk */
+#define MOPK_ADAMW_MAX_TENSORS 40        /* tensor parts per launch */
+#define MOPK_ADAMW_MAX_CHUNKS 4096       /* chunks per launch */
+#define MOPK_ADAMW_NORM 1                /* phases */
+#define MOPK_ADAMW_UPDATE 2
+typedef struct MopkOptimTensor {
+    void *p;                             /* (n) parameter, in / out */
+    const void *g;                       /* (n) gradient */
+    float *m;                            /* (n) fp32 first moment, in / out */
+    float *v;                            /* (n) fp32 second moment, in / out */
+    void *ema;                           /* (n) EMA of p in p_dtype, in / out; NULL without use_ema */
+    float *step;                         /* device fp32 scalar: steps taken so far, in / out */
+    int64_t n;                           /* elements, >= 0; 0: only step is touched, the other pointers may be NULL */
+    int32_t p_dtype;                     /* MopkDtype of p and ema */
+    int32_t g_dtype;                     /* MopkDtype of g */
+} MopkOptimTensor;
+typedef struct MopkAdamWStats {         /* 16 device bytes that outlive a call */
+    float norm;                          /* total gradient norm before clipping */
+    float coef;                          /* clip coefficient */
+    int32_t skip;                        /* 1: the step that follows is skipped */
+    int32_t skipped;                     /* steps skipped so far */
+} MopkAdamWStats;
+typedef struct MopkAdamWArgs {
+    int32_t n_tensors;
+    int32_t phases;                      /* MOPK_ADAMW_NORM | MOPK_ADAMW_UPDATE */
+    int32_t clip;                        /* norm: compute the clip coefficient from max_norm */
+    int32_t skip_nonfinite;              /* norm: set stats.skip on a non-finite norm */
+    int32_t use_norm;                    /* update: read coef and skip from stats (implied by MOPK_ADAMW_NORM in the same call) */
+    int32_t use_ema;
+    double lr, beta1, beta2, eps, weight_decay, ema_decay, max_norm;
+    const float *lr_dev;                 /* device float that replaces lr, or NULL */
+    MopkAdamWStats *stats;               /* device; needed by the norm phase and by use_norm */
+    float *workspace;                    /* device, mopk_adamw_workspace_bytes; norm phase only */
+} MopkAdamWArgs;
+int mopk_adamw_supported(const MopkAdamWArgs *a, const MopkOptimTensor *t);   /* 1 if the kernels take this call (dtypes, alignment, counts) */
+size_t mopk_adamw_workspace_bytes(const MopkAdamWArgs *a, const MopkOptimTensor *t);   /* one fp32 partial per chunk; reads only n */
+int mopk_adamw_launches(const MopkAdamWArgs *a, const MopkOptimTensor *t);    /* kernel launches mopk_adamw_step makes for this call */
+int mopk_adamw_step(const MopkAdamWArgs *a, const MopkOptimTensor *t, void *stream);
+
 /* -------------------------------------------------------------------------- */
 int mopk_version(void);
 const char *mopk_strerror(int status);

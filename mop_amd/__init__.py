@@ -5,6 +5,7 @@ surface (`mop_amd.nn`).  Device side: hand-written gfx950 HIP kernels behind the
 include/mopk.h, loaded with ctypes (`mop_amd._lib`).  There is no CPU fallback.
 """
 from . import nn  # noqa: F401
+from . import optim  # noqa: F401
 from .ops import get_precision, set_precision  # noqa: F401
 
 __version__ = "0.1.0"

@@ -197,6 +197,36 @@ class CrossEntropyArgs(C.Structure):
     ]
 
 
+ADAMW_CHUNK = 4096          # MOPK_ADAMW_CHUNK: elements per chunk
+ADAMW_MAX_TENSORS = 40      # MOPK_ADAMW_MAX_TENSORS: tensor parts per launch
+ADAMW_MAX_CHUNKS = 4096     # MOPK_ADAMW_MAX_CHUNKS: chunks per launch
+ADAMW_NORM, ADAMW_UPDATE = 1, 2
+
+
+class OptimTensor(C.Structure):
+    """MopkOptimTensor: one tensor of a fused optimiser step."""
+    _fields_ = [
+        ("p", _fp), ("g", _fp), ("m", _fp), ("v", _fp), ("ema", _fp), ("step", _fp), ("n", C.c_int64),
+        ("p_dtype", C.c_int32), ("g_dtype", C.c_int32),
+    ]
+
+
+class AdamWStats(C.Structure):
+    """MopkAdamWStats: the 16 device bytes a FusedAdamW keeps between steps."""
+    _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("skip", C.c_int32), ("skipped", C.c_int32)]
+
+
+class AdamWArgs(C.Structure):
+    """MopkAdamWArgs: the phases and hyper-parameters of one mopk_adamw_step call."""
+    _fields_ = [
+        ("n_tensors", C.c_int32), ("phases", C.c_int32), ("clip", C.c_int32), ("skip_nonfinite", C.c_int32), ("use_norm", C.c_int32),
+        ("use_ema", C.c_int32),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+        ("ema_decay", C.c_double), ("max_norm", C.c_double),
+        ("lr_dev", _fp), ("stats", _fp), ("workspace", _fp),
+    ]
+
+
 MOE_MAX_EXPERTS = 64
 
 
@@ -524,6 +554,10 @@ SYMBOLS = {
     "mopk_cross_entropy_supported": (C.c_int, [C.POINTER(CrossEntropyArgs)]),
     "mopk_cross_entropy_fwd": (C.c_int, [C.POINTER(CrossEntropyArgs), C.c_void_p]),
     "mopk_cross_entropy_bwd": (C.c_int, [C.POINTER(CrossEntropyArgs), C.c_void_p]),
+    "mopk_adamw_supported": (C.c_int, [C.POINTER(AdamWArgs), C.POINTER(OptimTensor)]),
+    "mopk_adamw_workspace_bytes": (C.c_size_t, [C.POINTER(AdamWArgs), C.POINTER(OptimTensor)]),
+    "mopk_adamw_launches": (C.c_int, [C.POINTER(AdamWArgs), C.POINTER(OptimTensor)]),
+    "mopk_adamw_step": (C.c_int, [C.POINTER(AdamWArgs), C.POINTER(OptimTensor), C.c_void_p]),
 }
 
 _lib = None

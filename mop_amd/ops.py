@@ -4980,6 +4980,190 @@ def linear_cross_entropy(x: torch.Tensor, weight: torch.Tensor, targets: torch.T
                                                          min(M, chunk_rows or LINEAR_CE_CHUNK_ROWS), ldt)
 
 
+# ---- fused AdamW step: gradient norm, clipping, update, weight EMA (mopk_adamw_*; mop_amd.optim.FusedAdamW holds the state) ----
+# A step is a list of groups.  A group is a dict: "params", "grads", "exp_avgs", "exp_avg_sqs", "steps" (lists of equal length;
+# exp_avg / exp_avg_sq fp32, step an fp32 scalar tensor), "emas" (a list, or None without an EMA), "lr" (a float or a one-element
+# fp32 tensor), "beta1", "beta2", "eps", "weight_decay".  `stats` is the int32 (4,) tensor behind MopkAdamWStats.
+ADAMW_GROUP_KEYS = ("params", "grads", "exp_avgs", "exp_avg_sqs", "steps", "emas", "lr", "beta1", "beta2", "eps", "weight_decay")
+
+
+def _adamw_check(groups, max_grad_norm, ema_decay, stats, what: str) -> None:
+    """validate an adamw_step call before any device work"""
+    if not isinstance(stats, torch.Tensor) or stats.dtype != torch.int32 or tuple(stats.shape) != (4,) or not stats.is_contiguous():
+        raise ValueError(f"{what}: stats must be a contiguous int32 (4,) tensor")
+    if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+        raise ValueError(f"{what}: max_grad_norm must be positive, got {max_grad_norm!r}")
+    if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+        raise ValueError(f"{what}: ema_decay must lie in [0, 1], got {ema_decay!r}")
+    for g in groups:
+        missing = [k for k in ADAMW_GROUP_KEYS if k not in g]
+        if missing:
+            raise ValueError(f"{what}: a group lacks {missing}")
+        n = len(g["params"])
+        lists = [g["grads"], g["exp_avgs"], g["exp_avg_sqs"], g["steps"]] + ([g["emas"]] if ema_decay is not None else [])
+        if any(x is None or len(x) != n for x in lists):
+            raise ValueError(f"{what}: the tensor lists of a group must have one entry per parameter ({n})")
+        for i, p in enumerate(g["params"]):
+            if p.is_complex() or not p.dtype.is_floating_point:
+                raise ValueError(f"{what}: parameters must be real floating tensors, got {p.dtype}")
+            if g["grads"][i].is_sparse:
+                raise ValueError(f"{what}: sparse gradients are not supported")
+            if g["grads"][i].shape != p.shape or any(x[i].shape != p.shape for x in lists[1:3] + lists[4:]):
+                raise ValueError(f"{what}: gradient, moments and EMA must have the parameter's shape {tuple(p.shape)}")
+            if p.device != stats.device:
+                raise ValueError(f"{what}: a parameter is on {p.device}, the stats on {stats.device}: one step updates one device")
+
+
+def _adamw_scalar(x, device) -> torch.Tensor:
+    return x.detach().reshape(()).double() if isinstance(x, torch.Tensor) else torch.tensor(float(x), dtype=torch.float64, device=device)
+
+
+def adamw_step_torch(groups, *, max_grad_norm=None, ema_decay=None, skip_nonfinite=False, stats: torch.Tensor) -> None:
+    """the restatement of `adamw_step` in torch ops, tensor by tensor, without a host sync: include/mopk.h's formulae in fp32 with
+    the constants rounded from double, the global norm as clip_grad_norm_ takes it (the norm of the tensors' norms), a skipped step
+    by torch.where.  exp_avg and exp_avg_sq are fp32; any floating parameter and gradient dtype, any strides."""
+    _adamw_check(groups, max_grad_norm, ema_decay, stats, "adamw_step_torch")
+    dev, f32 = stats.device, torch.float32
+    use_norm = max_grad_norm is not None or skip_nonfinite
+    coef = keep = None
+    with torch.no_grad():
+        if use_norm:
+            norms = [torch.linalg.vector_norm(x.detach().float()) for g in groups for x in g["grads"]]
+            norm = torch.linalg.vector_norm(torch.stack(norms)) if norms else torch.zeros((), dtype=f32, device=dev)
+            coef = torch.ones_like(norm) if max_grad_norm is None else torch.clamp(float(max_grad_norm) / (norm + 1e-6), max=1.0)
+            skip = ~torch.isfinite(norm) if skip_nonfinite else torch.zeros((), dtype=torch.bool, device=dev)
+            fstats = stats.view(f32)
+            fstats[0], fstats[1], stats[2] = norm, coef, skip.to(torch.int32)
+            stats[3] += skip.to(torch.int32)
+            keep = ~skip if skip_nonfinite else None
+        for g in groups:
+            lr, b1, b2 = _adamw_scalar(g["lr"], dev), float(g["beta1"]), float(g["beta2"])
+            decay = (1.0 - lr * float(g["weight_decay"])).to(f32)
+            b1f, omb1, b2f, omb2 = (torch.tensor(x, dtype=torch.float64).to(f32).item() for x in (b1, 1.0 - b1, b2, 1.0 - b2))
+            eps = torch.tensor(float(g["eps"]), dtype=torch.float64).to(f32).item()
+            for i, p in enumerate(g["params"]):
+                p, m, v, step = p.detach(), g["exp_avgs"][i], g["exp_avg_sqs"][i], g["steps"][i]
+                k = step.double() + 1.0
+                step_size = (lr / (1.0 - torch.pow(torch.tensor(b1, dtype=torch.float64, device=dev), k))).to(f32)
+                sqrt_bc2 = torch.sqrt(1.0 - torch.pow(torch.tensor(b2, dtype=torch.float64, device=dev), k)).to(f32)
+                gp = g["grads"][i].detach().to(f32)
+                if coef is not None:
+                    gp = coef * gp
+                m_new = b1f * m + omb1 * gp
+                v_new = b2f * v + (omb2 * gp) * gp
+                pf = p.to(f32) * decay
+                p_new = (pf - step_size * (m_new / (torch.sqrt(v_new) / sqrt_bc2 + eps))).to(p.dtype)
+                new = [(p, p_new), (m, m_new), (v, v_new), (step, step + 1.0)]
+                if ema_decay is not None:
+                    d, omd = (torch.tensor(x, dtype=torch.float64).to(f32).item() for x in (float(ema_decay), 1.0 - float(ema_decay)))
+                    e = g["emas"][i]
+                    new.append((e, (d * e.to(f32) + omd * p_new.to(f32)).to(e.dtype)))
+                for old, val in new:
+                    old.copy_(val if keep is None else torch.where(keep, val, old))
+
+
+def _adamw_dtype(t: torch.Tensor):
+    return {torch.float32: L.MOPK_F32, torch.bfloat16: L.MOPK_BF16}.get(t.dtype)
+
+
+def _adamw_accept(groups, max_grad_norm, ema_decay, skip_nonfinite, stats, cache=None):
+    """the (args, tensor array) pairs of a step that mopk_adamw_* take -- first the norm call over all tensors when one is needed,
+    then one update call per group -- or None of a step they refuse.  `cache` (a dict the caller keeps) saves rebuilding the tensor
+    arrays while no pointer changes."""
+    if not stats.is_cuda:
+        return None
+    use_ema, dev = ema_decay is not None, stats.device
+    rows = []
+    for g in groups:
+        lr = g["lr"]
+        if isinstance(lr, torch.Tensor) and not (lr.is_cuda and lr.device == dev and lr.dtype == torch.float32 and lr.numel() == 1):
+            return None
+        for i, p in enumerate(g["params"]):
+            gr, m, v, st = g["grads"][i], g["exp_avgs"][i], g["exp_avg_sqs"][i], g["steps"][i]
+            e = g["emas"][i] if use_ema else None
+            ts = [p, gr, m, v, st] + ([e] if use_ema else [])
+            if (_adamw_dtype(p) is None or _adamw_dtype(gr) is None or m.dtype != torch.float32 or v.dtype != torch.float32
+                    or st.dtype != torch.float32 or st.numel() != 1 or (use_ema and e.dtype != p.dtype)
+                    or not all(t.device == dev and t.layout == torch.strided and t.is_contiguous() for t in ts)):
+                return None
+            rows.append((p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), e.data_ptr() if use_ema else None, st.data_ptr(),
+                         p.numel(), _adamw_dtype(p), _adamw_dtype(gr)))
+    key = (tuple(rows), tuple(len(g["params"]) for g in groups))
+    if cache is not None and cache.get("key") == key:
+        arrays, whole = cache["arrays"], cache["whole"]
+    else:
+        whole = (L.OptimTensor * max(len(rows), 1))()
+        for j, r in enumerate(rows):
+            t = whole[j]
+            t.p, t.g, t.m, t.v, t.ema, t.step, t.n, t.p_dtype, t.g_dtype = r
+        arrays, o = [], 0
+        for g in groups:
+            n = len(g["params"])
+            arrays.append((L.OptimTensor * max(n, 1)).from_buffer(whole, o * C.sizeof(L.OptimTensor)) if n else None)
+            o += n
+        if cache is not None:
+            cache.update(key=key, arrays=arrays, whole=whole, ws=None)
+    lib, calls = L.lib(), []
+    use_norm = max_grad_norm is not None or skip_nonfinite
+    if use_norm:
+        a = L.AdamWArgs()
+        a.n_tensors, a.phases, a.clip, a.skip_nonfinite = len(rows), L.ADAMW_NORM, max_grad_norm is not None, bool(skip_nonfinite)
+        a.max_norm, a.stats = float(max_grad_norm or 0.0), stats.data_ptr()
+        ws = cache.get("ws") if cache is not None else None
+        if ws is None:
+            ws = torch.empty(lib.mopk_adamw_workspace_bytes(C.byref(a), whole) // 4, dtype=torch.float32, device=dev)
+            if cache is not None:
+                cache["ws"] = ws
+        a.workspace = ws.data_ptr()
+        calls.append((a, whole, ws))
+    for g, arr in zip(groups, arrays):
+        if arr is None:
+            continue
+        a = L.AdamWArgs()
+        a.n_tensors, a.phases, a.use_norm, a.use_ema = len(g["params"]), L.ADAMW_UPDATE, use_norm, use_ema
+        lr = g["lr"]
+        if isinstance(lr, torch.Tensor):
+            a.lr_dev = lr.data_ptr()
+        else:
+            a.lr = float(lr)
+        a.beta1, a.beta2, a.eps, a.weight_decay = float(g["beta1"]), float(g["beta2"]), float(g["eps"]), float(g["weight_decay"])
+        a.ema_decay, a.stats = float(ema_decay or 0.0), stats.data_ptr()
+        calls.append((a, arr, lr))
+    if not all(lib.mopk_adamw_supported(C.byref(a), arr) for a, arr, _ in calls):
+        return None
+    return calls
+
+
+def adamw_supported(groups, *, max_grad_norm=None, ema_decay=None, skip_nonfinite=False, stats: torch.Tensor) -> bool:
+    """True if mopk_adamw_step takes this step: every tensor CUDA, on one device, contiguous; parameters, gradients and EMA fp32
+    or bf16; fp32 moments and step counts (the library's own query decides the rest).  Raises ValueError on bad arguments."""
+    _adamw_check(groups, max_grad_norm, ema_decay, stats, "adamw_supported")
+    return _adamw_accept(groups, max_grad_norm, ema_decay, skip_nonfinite, stats) is not None
+
+
+def adamw_launches(groups, *, max_grad_norm=None, ema_decay=None, skip_nonfinite=False, stats: torch.Tensor) -> int:
+    """kernel launches `adamw_step` makes for this step on the fused path (mopk_adamw_launches), 0 for a step it refuses"""
+    calls = _adamw_accept(groups, max_grad_norm, ema_decay, skip_nonfinite, stats)
+    return 0 if calls is None else sum(L.lib().mopk_adamw_launches(C.byref(a), arr) for a, arr, _ in calls)
+
+
+def adamw_step(groups, *, max_grad_norm=None, ema_decay=None, skip_nonfinite=False, stats: torch.Tensor, cache=None) -> None:
+    """One AdamW step over all tensors of `groups`, in place: the global gradient norm and clip coefficient when max_grad_norm or
+    skip_nonfinite asks for them (stats: norm, coef, skip, skipped), the decoupled-weight-decay update with fp32 moments, the weight
+    EMA with ema_decay, step counts + 1.  Gradients are never written.  With skip_nonfinite a non-finite norm leaves every tensor
+    and count as it was.  Runs mopk_adamw_step (the launch count is mopk_adamw_launches) when adamw_supported() accepts the step,
+    else adamw_step_torch(); LAST_PATH["adamw"] records which.  No host sync, no host-to-device copy."""
+    _adamw_check(groups, max_grad_norm, ema_decay, stats, "adamw_step")
+    calls = _adamw_accept(groups, max_grad_norm, ema_decay, skip_nonfinite, stats, cache)
+    if calls is None:
+        LAST_PATH["adamw"] = L.PATH_GENERIC
+        return adamw_step_torch(groups, max_grad_norm=max_grad_norm, ema_decay=ema_decay, skip_nonfinite=skip_nonfinite, stats=stats)
+    LAST_PATH["adamw"] = L.PATH_FUSED
+    st = _stream()
+    for a, arr, _ in calls:
+        L.check(L.lib().mopk_adamw_step(C.byref(a), arr, st), "mopk_adamw_step")
+
+
 from . import mel_gate_fn as _mel_gate_fn  # noqa: E402  (it reads this module's helpers, all defined by now)
 from . import cross_entropy_fn as _cross_entropy_fn  # noqa: E402  (likewise)
 from . import gpt_lens_fn as _gpt_lens_fn  # noqa: E402  (likewise)

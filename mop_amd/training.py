@@ -16,12 +16,22 @@ import torch
 import torch.distributed as dist
 from torch import nn, optim
 
+from .optim import FusedAdamW
 from .parallel import FlatGradBucket
 
 
-def make_optimizer_and_schedule(model: nn.Module, lr: float, weight_decay: float, steps: int, warmup_frac: float = 0.0
-                                ) -> Tuple[optim.Optimizer, optim.lr_scheduler.LRScheduler]:
-    opt = optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
+def make_optimizer_and_schedule(model: nn.Module, lr: float, weight_decay: float, steps: int, warmup_frac: float = 0.0,
+                                fused: bool = False, max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None,
+                                skip_nonfinite: bool = False) -> Tuple[optim.Optimizer, optim.lr_scheduler.LRScheduler]:
+    """fused=True: mop_amd.optim.FusedAdamW (clipping, update and weight EMA in one step on HIP kernels) under the same schedule;
+    max_grad_norm, ema_decay and skip_nonfinite are its arguments and need fused=True"""
+    if fused:
+        opt = FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay,
+                         skip_nonfinite=skip_nonfinite)
+    elif max_grad_norm is not None or ema_decay is not None or skip_nonfinite:
+        raise ValueError("max_grad_norm, ema_decay and skip_nonfinite need fused=True (torch.optim.AdamW has none of them)")
+    else:
+        opt = optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
     warm = int(max(steps, 1) * max(warmup_frac, 0.0))
     if warm > 0:
         sched = optim.lr_scheduler.SequentialLR(

@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="capture the model's forward + backward into HIP graphs (torch.cuda.make_graphed_callables) and replay them; "
                          "the optimizer step stays eager")
+    ap.add_argument("--fused-opt", action="store_true",
+                    help="step with mop_amd.optim.FusedAdamW (the AdamW update on HIP kernels) instead of torch.optim.AdamW")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank, local = int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
@@ -46,7 +48,7 @@ def main():
     torch.manual_seed(0)                                   # identical initial weights on every rank
     model = ViTEdgewise(dim=args.dim, depth=args.depth, heads=args.heads, n_classes=100, n_views=args.views, share_qkv=True,
                         gate_mode="lowrank", gate_rank=4, gate_init="mix5", drop_path=0.0).cuda().to(torch.bfloat16)
-    opt, sched = make_optimizer_and_schedule(model, args.lr, args.weight_decay, args.steps, args.warmup_frac)
+    opt, sched = make_optimizer_and_schedule(model, args.lr, args.weight_decay, args.steps, args.warmup_frac, fused=args.fused_opt)
     g = torch.Generator(device="cuda").manual_seed(1234 + rank)            # each rank draws its own shard
     x = torch.randn(args.batch, 3, 32, 32, device="cuda", generator=g).to(torch.bfloat16)
     y = torch.randint(0, 100, (args.batch,), device="cuda", generator=g)
